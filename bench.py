@@ -18,6 +18,14 @@ N > 1: launched by torch.distributed.run, one rank per GPU, one independent stre
 collective -- weak scaling; value = all units of all ranks / max-over-ranks time.
 --dry-run: the rank path (rank_info -> process group -> device selection -> stream assignment -> plan generation ->
 barrier -> aggregate) without touching a GPU, over gloo; tests/test_multistream_gloo.py runs it with two ranks.
+
+A plain run measures the headline only: it sets up (grows the map / builds the index), warms up, times --steps steps and
+prints the result line.  --full adds everything else measured or checked on the way: the roofline blocks and per-kernel
+times, the exploring-regime window, the PCIe-inclusive pass, the passes that price GetTimings, the CPU baseline with its
+in-run parity check against the oracle, and (C2 at N = 1) the embedded C3 / C5 runs; the full result also goes to
+bench_detail[_<config>].json.
+--dump-outputs DIR: after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float32 / float64,
+at most 64 MB; a fixed, seeded sample of the larger outputs), for output-for-output comparisons of two builds.
 """
 import argparse
 import hashlib
@@ -460,6 +468,47 @@ def finish_ranks(world, dist):
         dist.destroy_process_group()
 
 
+# =====================================================================================================================
+# --dump-outputs: what the timed path computed in its last step, as its caller would receive it
+DUMP_LIMIT = 64 << 20                      # bytes, all files together
+DUMP_SURFELS = 1 << 18                     # sampled surfel slots (the C2 map has 5.5 M)
+DUMP_QUERIES = 1 << 15                     # sampled C5 self-queries (of 50 M)
+SURFEL_FLOAT_ROWS = list(range(11))        # result rows of the surfel SoA (11 - 16 and 23 are scratch)
+SURFEL_INT_ROWS = [17, 18, 19, 20, 21, 22, 24]
+
+
+def sample_index(n, m, seed):
+    """A fixed, seeded sample of m of the n indices, ascending (all of them when n <= m)."""
+    if n <= m:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """One DIR/<name>.npy per array; every array float32 or float64, integers converted exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "outputs of %d bytes exceed the dump limit" % total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def integrate_outputs(wl):
+    """C2 / C3: the last timed frame's preprocessed images (depth, normals, radii) and the surfel map behind its Integrate --
+    the counts, and every result row of a seeded sample of the slots (the map itself is 100 B per slot)."""
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    depth, normals, radius = wl.pipe.download_work()
+    rows = rec.debug_download_surfels(n)
+    sel = sample_index(n, DUMP_SURFELS, 0x5EED0D)
+    return {"depth_final": depth.astype(np.float32), "normals": normals, "radius": radius,
+            "surfel_counts": np.array([n, live, n - live], np.float64),   # slots, live surfels, merged slots
+            "surfel_sample_index": sel.astype(np.float64),
+            "surfel_float_rows": rows[np.ix_(SURFEL_FLOAT_ROWS, sel)],
+            "surfel_int_rows": rows[np.ix_(SURFEL_INT_ROWS, sel)].view(np.uint32).astype(np.float64)}
+
+
 
 # =====================================================================================================================
 # The line the driver reads.  Its record keeps the last 8 000 characters of stdout: the LAST line has to be short (round 5's
@@ -599,6 +648,8 @@ def emit(result, args):
     paths = [args.detail_out] if getattr(args, "detail_out", "") else [os.path.join(ROOT, name)]
     if not getattr(args, "detail_out", "") and os.path.isdir(os.path.join(ROOT, "gpurun_out")):
         paths.append(os.path.join(ROOT, "gpurun_out", name))
+    if not getattr(args, "full", True) and not getattr(args, "detail_out", ""):
+        paths = []   # (a plain run: the line is the whole result)
     written = []
     for p in paths:
         try:
@@ -664,6 +715,11 @@ def main():
                          "share a GPU: rank r uses device r mod device_count -- the C4 path on a 1-GPU box)")
     ap.add_argument("--check-all-ranks", action="store_true", help="N > 1: every rank runs the in-run parity check (oracle) on its own stream")
     ap.add_argument("--dry-run", action="store_true", help="rank path only (no GPU, gloo): see the module docstring")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline (roofline, per-kernel times, extra passes, "
+                    "CPU baseline and parity checks, the embedded C3 / C5 runs, the detail file); without it the --cpu-frames, "
+                    "--host-frames, --growth-frames, --timing-frames, --no-check and --check-all-ranks passes do not run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--full-line", action="store_true", help="tools: print the full result as the last line (not for the driver: it "
                     "keeps 8 000 characters of stdout)")
@@ -692,6 +748,7 @@ def run_integrate(args):
     from surfelmeshing_amd import multistream
     rank, local_rank, world, dist, torch = init_ranks(args)
     log = (rank == 0) and not args.quiet
+    lean = not args.full and not args.ub   # a plain run: the headline only (--ub runs keep their calibration)
     cap = args.cap or int(target_live * 1.25)
     assign = multistream.stream_assignment(rank)   # one independent stream per rank, no data-path collective
 
@@ -740,8 +797,8 @@ def run_integrate(args):
         info["parity_check"] = r.get("parity_check")
         info["cpu_frames_per_s"] = r["value"]
 
-    probe_before = handover_probe(wl)
-    g_end, n_live = wl.grow(log, (args.growth_frames, growth_check) if args.growth_frames > 0 else None)
+    probe_before = handover_probe(wl) if not lean else None
+    g_end, n_live = wl.grow(log, (args.growth_frames, growth_check) if args.growth_frames > 0 and not lean else None)
     if log:
         print("# grown to %d live surfels in %d frames, %.1fs" % (n_live, g_end, time.time() - t0), file=sys.stderr)
 
@@ -767,15 +824,15 @@ def run_integrate(args):
     # need the host (statistics, per-kernel times, PCIe-inclusive pass, the snapshot for the CPU baseline) follow.
     W_user, W = W, SETTLE
     total = W + cal + W_user + K
-    do_host = args.host_frames if (rank == 0 and world == 1 and not ub) else 0   # PCIe-inclusive pass: rank 0 at N = 1 only
-    do_cpu = rank == 0 and world == 1 and cpu_frames > 0 and not ub   # CPU baseline: rank 0 at N = 1 only
-    chk_frames = max(1, cpu_frames) if (world > 1 and args.check_all_ranks) else 0
-    do_timing = args.timing_frames if (rank == 0 and world == 1 and not ub) else 0   # the passes that price GetTimings
+    do_host = args.host_frames if (rank == 0 and world == 1 and not ub and not lean) else 0   # PCIe-inclusive pass: rank 0 at N = 1 only
+    do_cpu = rank == 0 and world == 1 and cpu_frames > 0 and not ub and not lean   # CPU baseline: rank 0 at N = 1 only
+    chk_frames = max(1, cpu_frames) if (world > 1 and args.check_all_ranks and not lean) else 0
+    do_timing = args.timing_frames if (rank == 0 and world == 1 and not ub and not lean) else 0   # the passes that price GetTimings
     stamps_start = total + 1 + reps                        # stage times by the stamps (reps frames, like the events' pass)
     host_start = stamps_start + reps
     timing_start = host_start + do_host
     cpu_start = timing_start + 4 * do_timing               # its frames: behind everything else
-    n_plan = cpu_start + (cpu_frames if do_cpu else 0) + chk_frames
+    n_plan = cpu_start + (cpu_frames if do_cpu else 0) + chk_frames if not lean else total
     for j in range(-4, n_plan + 4):
         wl.render(first + j, 4 + j)
     plan = [wl.plan(first + j, 4 + j) for j in range(n_plan)]
@@ -811,38 +868,45 @@ def run_integrate(args):
     warm_steps = wl.steps(plan[W + cal:W + cal + W_user]) if W_user > 0 else None
     timed_steps = wl.steps(plan[W + cal + W_user:W + cal + W_user + K])
     wl.pipe.run_array(*settle_steps)
-    # short calibration pass: which kernel of the frame lasts longest?  Judged IN the frame -- pipelining on, time stamps
-    # around one kernel at a time for a few frames each (alone on the chip the candidates lie within 10 % of each other
-    # and the choice flipped from run to run; beside the other chains of the frame they do not).  Every kernel of the
-    # frame takes part: the Integrate slots on their streams and the three preprocessing stages on the driver's.
-    cal_ms = {}
-    rec.set_overlap(not args.no_overlap)
-    for idx, name in enumerate(cal_names):
-        if name in PRE_STAGES:
-            wl.pipe.profile_begin(PRE_STAGES.index(name), per)
-        else:
-            rec.profile_begin(name, per)
-        wl.pipe.run_array(*cal_steps[idx])
-        api.StreamSynchronize(None)
-        ms, n = wl.pipe.profile_end() if name in PRE_STAGES else rec.profile_end()
-        cal_ms[name] = ms if n > 0 else 0.0
-    rec.set_overlap(False)
-    # value distributions of the frame in front of the warm-up frames (counters on for this frame only)
-    rec.set_stats_enabled(True)
-    wl.pipe.run_array(*stats_step)
-    st_before = rec.stats()
-    rec.set_stats_enabled(False)
-    rec.set_overlap(not args.no_overlap)
-    in_timed = [n for n in cal_names if not ("hoist-pre" in ub and n in PRE_STAGES)]
-    dominant = max(in_timed, key=lambda n: cal_ms[n])
-    dominant_hbm = max((n for n in in_timed if n not in PRE_STAGES), key=lambda n: cal_ms[n])
-    # The kernel that is timed with events in the timed region is the frame's longest HBM-side kernel -- the edge kernel
-    # (reg_accumulate) in every kernel trace of rounds 3 - 6 -- unless the 4-frame calibration finds another one MORE THAN 15 %
-    # longer: pass B and the blend calibrate within a few per cent of it, the choice used to flip from run to run, and WHICH
-    # kernel carries the events changes the frame rate (blend, with the event hand-over of rounds 3 - 6: - 10 %, the "slow
-    # mode"; pass B: - 3.6 %; the edge kernel: - 0.6 %; profiles/r6_ab_notes.md section 14)
-    if "reg_accumulate" in in_timed and cal_ms.get("reg_accumulate", 0.0) > 0 and cal_ms[dominant_hbm] <= 1.15 * cal_ms["reg_accumulate"]:
-        dominant_hbm = "reg_accumulate"
+    if lean:
+        # a plain run times no kernel of its own: the calibration frames run as further settle frames, so that the timed
+        # window starts at the same frame of the trajectory as in a --full run
+        rec.set_overlap(not args.no_overlap)
+        wl.pipe.run_array(*wl.steps(plan[W:W + cal]))
+        dominant = dominant_hbm = None
+    else:
+        # short calibration pass: which kernel of the frame lasts longest?  Judged IN the frame -- pipelining on, time stamps
+        # around one kernel at a time for a few frames each (alone on the chip the candidates lie within 10 % of each other
+        # and the choice flipped from run to run; beside the other chains of the frame they do not).  Every kernel of the
+        # frame takes part: the Integrate slots on their streams and the three preprocessing stages on the driver's.
+        cal_ms = {}
+        rec.set_overlap(not args.no_overlap)
+        for idx, name in enumerate(cal_names):
+            if name in PRE_STAGES:
+                wl.pipe.profile_begin(PRE_STAGES.index(name), per)
+            else:
+                rec.profile_begin(name, per)
+            wl.pipe.run_array(*cal_steps[idx])
+            api.StreamSynchronize(None)
+            ms, n = wl.pipe.profile_end() if name in PRE_STAGES else rec.profile_end()
+            cal_ms[name] = ms if n > 0 else 0.0
+        rec.set_overlap(False)
+        # value distributions of the frame in front of the warm-up frames (counters on for this frame only)
+        rec.set_stats_enabled(True)
+        wl.pipe.run_array(*stats_step)
+        st_before = rec.stats()
+        rec.set_stats_enabled(False)
+        rec.set_overlap(not args.no_overlap)
+        in_timed = [n for n in cal_names if not ("hoist-pre" in ub and n in PRE_STAGES)]
+        dominant = max(in_timed, key=lambda n: cal_ms[n])
+        dominant_hbm = max((n for n in in_timed if n not in PRE_STAGES), key=lambda n: cal_ms[n])
+        # The kernel that is timed with events in the timed region is the frame's longest HBM-side kernel -- the edge kernel
+        # (reg_accumulate) in every kernel trace of rounds 3 - 6 -- unless the 4-frame calibration finds another one MORE THAN 15 %
+        # longer: pass B and the blend calibrate within a few per cent of it, the choice used to flip from run to run, and WHICH
+        # kernel carries the events changes the frame rate (blend, with the event hand-over of rounds 3 - 6: - 10 %, the "slow
+        # mode"; pass B: - 3.6 %; the edge kernel: - 0.6 %; profiles/r6_ab_notes.md section 14)
+        if "reg_accumulate" in in_timed and cal_ms.get("reg_accumulate", 0.0) > 0 and cal_ms[dominant_hbm] <= 1.15 * cal_ms["reg_accumulate"]:
+            dominant_hbm = "reg_accumulate"
 
     def sync_all():
         torch.cuda.synchronize()
@@ -866,7 +930,8 @@ def run_integrate(args):
     dominant = args.profile_kernel or dominant_hbm
     rec.set_timing_enabled(timing_mode)
     wl.pipe.set_read_timings({"off": 0, "nowait": 1, "block": 2}[args.read_timings])
-    rec.profile_begin(dominant, args.profile_frames or K)
+    if not lean:
+        rec.profile_begin(dominant, args.profile_frames or K)
     _lib.check(_lib.load().smx_debug_marker(None, 1))   # delimits the timed region in rocprofv3 kernel traces
     sync_all()
     t_start = time.perf_counter()
@@ -881,9 +946,11 @@ def run_integrate(args):
     enqueue_each = multistream.per_rank(1e3 * enqueue_local / K, world, dist if world > 1 else None, reduce_device(args))
     if world > 1:
         dist.barrier()
-    dom_ms, dom_n = rec.profile_end()
+    dom_ms, dom_n = rec.profile_end() if not lean else (0.0, 0)
     wl.pipe.set_read_timings(0)
-    timeline = stamp_timeline(rec) if timing_mode == 4 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, integrate_outputs(wl))   # (before any pass behind the window moves the map on)
+    timeline = stamp_timeline(rec) if (timing_mode == 4 and not lean) else None
     if args.dump_stamps:   # (diagnosis: a -DSMX_STAMPS build only)
         import ctypes as _C
         wg = np.zeros((3, 8192, 16), np.uint64)
@@ -909,6 +976,15 @@ def run_integrate(args):
                 "in_frame_ms_before_the_bound_was_applied": cal_ms,
                 "dominant_in_timed_region": {"kernel": dominant, "avg_launch_ms": dom_ms, "launches": dom_n},
                 "frame_before_timed_window": {k: st_before[k] for k in ("surfels_size", "n_visible", "n_recent", "n_new")}}))
+        finish_ranks(world, dist)
+        return 0
+
+    if lean:
+        n_slots, live = rec.surfels_size(), rec.surfel_count()
+        if rank == 0:
+            emit(dict(headline(args, width, height, target_live, cap, world, fps, elapsed, K, W_user, enqueue_local, enqueue_each,
+                               each_rank, seen),
+                      config=workload_config(args, width, height, live, n_slots, cap, world)), args)
         finish_ranks(world, dist)
         return 0
 
@@ -965,19 +1041,9 @@ def run_integrate(args):
 
     ref_bytes = reference_model_bytes(st, P)
     live = st["surfels_size"] - st["merge_count"]
-    result = {
-        "metric": "RGB-D frames/s integrated @640x480, 5M live surfels; achieved HBM GB/s" if args.config == "C2" else
-                  "RGB-D frames/s integrated @%dx%d, %dM surfel cap; achieved HBM GB/s" % (width, height, target_live // 1000000),
-        "value": fps, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W_user,
-        "ms_per_step": 1e3 * elapsed / K, "host_enqueue_ms_per_step": 1e3 * enqueue_local / K,
-        "host_enqueue_ms_per_step_per_rank": enqueue_each, "host_cores": os.cpu_count(), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "per_rank_frames_per_s": each_rank, ("rccl_ranks_seen" if args.backend == "nccl" else "gloo_ranks_seen"): seen,
-        "config": {"workload": "%s: synthetic room stream %dx%d, raw depth + colour frames resident in HBM, full preprocessing + "
-                               "Integrate per frame, %d live surfels (%d slots), steady-state re-traversal" %
-                               (args.config, width, height, live, st["surfels_size"]),
-                   "max_surfel_count": cap, "streams": world, "parallelism": "1 independent stream per GPU",
-                   "backend": args.backend if world > 1 else None},
+    result = dict(headline(args, width, height, target_live, cap, world, fps, elapsed, K, W_user, enqueue_local, enqueue_each,
+                           each_rank, seen), **{
+        "config": workload_config(args, width, height, live, st["surfels_size"], cap, world),
         "distributions": st,
         "steady_state": {"settle_frames": SETTLE, "note": "untimed frames of the re-traversal in front of the calibration passes, the --warmup frames and the timed window",
                          "frame_before_timed_window": {k: st_before[k] for k in ("surfels_size", "n_visible", "n_recent", "n_new")},
@@ -996,7 +1062,7 @@ def run_integrate(args):
         "growth_phase": getattr(wl, "growth", None),
         "reference_model_bytes_per_frame": ref_bytes,
         "reference_model_GBs": ref_bytes * (K / elapsed) / 1e9,
-    }
+    })
 
     parity_all = None
     if world > 1 and args.check_all_ranks:
@@ -1034,6 +1100,27 @@ def run_integrate(args):
     return 0
 
 
+def headline(args, width, height, target_live, cap, world, fps, elapsed, K, W_user, enqueue_local, enqueue_each, each_rank, seen):
+    """The keys of the result line that a plain run and a --full run share (C2 / C3)."""
+    return {
+        "metric": "RGB-D frames/s integrated @640x480, 5M live surfels; achieved HBM GB/s" if args.config == "C2" else
+                  "RGB-D frames/s integrated @%dx%d, %dM surfel cap; achieved HBM GB/s" % (width, height, target_live // 1000000),
+        "value": fps, "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W_user,
+        "ms_per_step": 1e3 * elapsed / K, "host_enqueue_ms_per_step": 1e3 * enqueue_local / K,
+        "host_enqueue_ms_per_step_per_rank": enqueue_each, "host_cores": os.cpu_count(), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "per_rank_frames_per_s": each_rank, ("rccl_ranks_seen" if args.backend == "nccl" else "gloo_ranks_seen"): seen,
+    }
+
+
+def workload_config(args, width, height, live, slots, cap, world):
+    return {"workload": "%s: synthetic room stream %dx%d, raw depth + colour frames resident in HBM, full preprocessing + "
+                        "Integrate per frame, %d live surfels (%d slots), steady-state re-traversal" %
+                        (args.config, width, height, live, slots),
+            "max_surfel_count": cap, "streams": world, "parallelism": "1 independent stream per GPU",
+            "backend": args.backend if world > 1 else None}
+
+
 def other_configs(args, log):
     """BASELINE.json's other single-GPU configurations, short runs of this same script in processes of their own behind the
     C2 work (this process keeps its ~2 GB map; the chip has 288 GB): C3 = 1280x960 stream / 20 M surfel cap, C5 = 50 M-point
@@ -1051,7 +1138,7 @@ def other_configs(args, log):
         import tempfile
         tmpdir = tempfile.mkdtemp(prefix="smx_bench_")
         detail = os.path.join(tmpdir, "bench_detail_%s.json" % name)
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--quiet", "--no-other-configs", "--detail-out", detail] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--quiet", "--no-other-configs", "--detail-out", detail] + extra
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -1358,7 +1445,7 @@ def cpu_baseline(wl, plan, W, frames, state0, merge0, cap, check, log, time_one_
 # =====================================================================================================================
 # C1: BASELINE.json configs[0] -- single 640x480 synthetic depth frame, bilateral filter + erosion + normals via the
 # naive CPU loops (erosion supplies the zero border the normals stage assumes, cuda_depth_processing.cu:659-662)
-def c1_timing(width=640, height=480, reps_all=10, reps_one=3):
+def c1_timing(width=640, height=480, reps_all=10, reps_one=3, warmup=0, outputs=None):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle as orc
     from oracle import binding
@@ -1368,34 +1455,61 @@ def c1_timing(width=640, height=480, reps_all=10, reps_one=3):
     depth, _ = s.frame(0)
     cores = min(os.cpu_count() or 1, 32)
     res = {}
+
+    def step():
+        a = orc.bilateral_filter_and_cutoff(depth, max_depth=50000, depth_valid_region_radius=333.0 * sc)
+        a = orc.erode_depth_map(a, 2)
+        return orc.compute_normals_and_drop_bad_pixels(a, s.fx, s.fy, s.cx, s.cy)
     for threads, reps in ((cores, reps_all), (1, reps_one)):
+        if reps <= 0:
+            continue
         binding.set_row_threads(threads)
+        for _ in range(warmup if threads == cores else 0):
+            step()
         t0 = time.perf_counter()
         for _ in range(reps):
-            a = orc.bilateral_filter_and_cutoff(depth, max_depth=50000, depth_valid_region_radius=333.0 * sc)
-            a = orc.erode_depth_map(a, 2)
-            orc.compute_normals_and_drop_bad_pixels(a, s.fx, s.fy, s.cx, s.cy)
+            out = step()
         res[threads] = (time.perf_counter() - t0) / reps
+        if threads == cores and outputs is not None:
+            outputs["depth"], outputs["normals"] = out[0].astype(np.float32), np.asarray(out[1], np.float32)
     binding.set_row_threads(1)
-    return {"workload": "C1: one %dx%d frame, bilateral + erosion(2) + normals (oracle, gcc -O2)" % (width, height),
-            "ms_all_cores": 1e3 * res[cores], "cores": cores, "ms_one_core": 1e3 * res[1],
-            "ns_per_pixel_one_core": 1e9 * res[1] / (width * height)}
+    r = {"workload": "C1: one %dx%d frame, bilateral + erosion(2) + normals (oracle, gcc -O2)" % (width, height),
+         "ms_all_cores": 1e3 * res[cores], "cores": cores}
+    if 1 in res:
+        r.update(ms_one_core=1e3 * res[1], ns_per_pixel_one_core=1e9 * res[1] / (width * height))
+    return r
 
 
 def run_c1(args):
-    r = c1_timing()
-    print(json.dumps({"metric": "single 640x480 depth frame: bilateral filter + erosion + normals, naive CPU loop (BASELINE.json configs[0])",
-                      "value": 1e3 / r["ms_all_cores"], "unit": "frames/s", "n_gpus": 0, "steps": 10, "warmup": 0,
-                      "ms_per_step": r["ms_all_cores"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                      "dtype": "f32", "data": "synthetic", "config": {"workload": r["workload"]},
-                      "cpu_baseline": {"value": 1e3 / r["ms_all_cores"], "unit": "frames/s", "cores": r["cores"], "kind": "port",
-                                       "sample": "10 repetitions of the frame", "one_core_ms": r["ms_one_core"],
-                                       "ns_per_pixel_one_core": r["ns_per_pixel_one_core"]}}))
+    steps = args.steps if args.steps is not None else 10
+    warm = args.warmup if args.warmup is not None else 0
+    outputs = {} if args.dump_outputs else None
+    r = c1_timing(reps_all=steps, reps_one=3 if args.full else 0, warmup=warm, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+    line = {"metric": "single 640x480 depth frame: bilateral filter + erosion + normals, naive CPU loop (BASELINE.json configs[0])",
+            "value": 1e3 / r["ms_all_cores"], "unit": "frames/s", "n_gpus": 0, "steps": steps, "warmup": warm,
+            "ms_per_step": r["ms_all_cores"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic", "config": {"workload": r["workload"]}}
+    if args.full:
+        line["cpu_baseline"] = {"value": 1e3 / r["ms_all_cores"], "unit": "frames/s", "cores": r["cores"], "kind": "port",
+                                "sample": "%d repetitions of the frame" % steps, "one_core_ms": r["ms_one_core"],
+                                "ns_per_pixel_one_core": r["ns_per_pixel_one_core"]}
+    print(json.dumps(line))
     return 0
 
 
 # =====================================================================================================================
 # C5: BASELINE.json configs[4] -- 50 M live surfels, neighbor search dominant
+C5_METRIC = "radius-neighbor queries/s, every one of 50M surfels queries its own neighbourhood, K=64 (BASELINE.json configs[4])"
+
+
+def c5_config(n, spacing, world):
+    return {"workload": "C5: %d surfel positions on the room surface (spacing %.2f mm), index cell = search radius = "
+                        "1.5 x spacing, self-queries for all points (smx_nn_query_self), K = 64" % (n, spacing * 1e3),
+            "streams": world, "parallelism": "1 independent cloud per GPU"}
+
+
 def run_c5(args):
     import ctypes as C
     from surfelmeshing_amd import multistream
@@ -1466,7 +1580,7 @@ def run_c5(args):
         return (time.perf_counter() - t) / reps
 
     build()
-    t_build = timed(build, 3)
+    t_build = timed(build, 3) if args.full else None
     info = nn.stats()
     for _ in range(warm):
         query_self(1.0)
@@ -1482,6 +1596,26 @@ def run_c5(args):
     elapsed_local = time.perf_counter() - t_start
     qps, elapsed, _ = multistream.aggregate_throughput(float(n) * steps, elapsed_local, world, dist if world > 1 else None, reduce_device(args))
     _lib.check(L.smx_debug_marker(None, 2))
+    ms_step = 1e3 * elapsed / steps
+    if args.dump_outputs and rank == 0:
+        # the last step's results of a seeded sample of the self-queries; entries behind a query's count are -1
+        sel = sample_index(n, DUMP_QUERIES, 0xC5D)
+        sel_t = torch.from_numpy(sel).to(dev_t)
+        cnt = t_cnt[sel_t].cpu().numpy()
+        idx = t_idx.view(n, Kn)[sel_t].cpu().numpy().view(np.uint32).astype(np.float64)
+        d2 = t_d2.view(n, Kn)[sel_t].cpu().numpy()
+        unused = np.arange(Kn)[None, :] >= np.minimum(cnt, Kn)[:, None]
+        idx[unused], d2[unused] = -1.0, -1.0
+        dump_outputs(args.dump_outputs, {"query_index": sel.astype(np.float64), "count": cnt.astype(np.float64),
+                                         "neighbor_index": idx, "neighbor_dist2": d2})
+    if not args.full:
+        if rank == 0:
+            emit({"metric": C5_METRIC, "value": qps, "unit": "queries/s", "n_gpus": world, "steps": steps, "warmup": warm,
+                  "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                  "data": "synthetic", "config": c5_config(n, spacing, world)}, args)
+        nn.close()
+        finish_ranks(world, dist)
+        return 0
     # counters of one more pass -> algorithmic bytes per query (16 (position + r^2) + 12 x the candidates
     # staged per tile, amortised over the queries of the tile + 8 per result + 4 (count))
     nn.set_stats_enabled(True)
@@ -1490,7 +1624,6 @@ def run_c5(args):
     nn.set_stats_enabled(False)
     cnt1 = t_cnt.cpu().numpy().copy()
     bytes_per_query = 16.0 + 12.0 * st1["staged_candidates"] / n + 8.0 * st1["results"] / n + 4.0
-    ms_step = 1e3 * elapsed / steps
     achieved = bytes_per_query * n / (ms_step * 1e-3) / 1e9
     # secondary numbers: twice the radius (max search-range factor, main.cc:392), and the general batch entry point
     t_2r = timed(lambda: query_self(4.0), 2)
@@ -1528,12 +1661,10 @@ def run_c5(args):
                                "wave-instructions per cycle x 2.4 GHz (4 SIMD-32 per CU, 2 cycles per wave64 instruction); the "
                                "measured ceiling is 1.79 per CU per cycle (profiles/r17_counter_calibration.md)"}
     result = {
-        "metric": "radius-neighbor queries/s, every one of 50M surfels queries its own neighbourhood, K=64 (BASELINE.json configs[4])",
+        "metric": C5_METRIC,
         "value": qps, "unit": "queries/s", "n_gpus": world, "steps": steps, "warmup": warm, "ms_per_step": ms_step,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "C5: %d surfel positions on the room surface (spacing %.2f mm), index cell = search radius = "
-                               "1.5 x spacing, self-queries for all points (smx_nn_query_self), K = 64" % (n, spacing * 1e3),
-                   "streams": world, "parallelism": "1 independent cloud per GPU"},
+        "config": c5_config(n, spacing, world),
         "distributions": {"n_points": n, "n_bricks": info["n_bricks"], "grid_cells": info["dim"], "key_bits": info["key_bits"],
                           "mean_results": float(cnt1.mean()), "max_results": int(cnt1.max()), "tiles": st1["tiles"],
                           "staged_candidates_per_query": st1["staged_candidates"] / n, "distance_tests_per_query": st1["distance_tests"] / n},

@@ -77,3 +77,19 @@ def test_emit_writes_the_detail_file_and_prints_one_short_line(tmp_path, capsys)
     assert len(out) == 1 and len(out[0]) < 6000
     assert json.load(open(A.detail_out))["roofline"]["kernels"]      # everything measured is in the detail file
     assert json.loads(out[0])["detail"]
+
+
+def test_c1_steps_set_the_timed_repetitions_and_outputs_are_dumped(tmp_path, orc):
+    """C1 needs no GPU: --steps is the number of timed repetitions, and --dump-outputs writes the last one's images."""
+    import subprocess
+    import sys
+    import numpy as np
+    out = tmp_path / "c1"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(1e3 / d["ms_per_step"])
+    depth, normals = np.load(out / "depth.npy"), np.load(out / "normals.npy")
+    assert depth.dtype == normals.dtype == np.float32 and depth.shape == (480, 640) and normals.shape == (480, 640, 2)
+    assert (depth > 0).sum() > 10000

@@ -532,7 +532,7 @@ def test_c3_resolution_parity_with_state_injection(smx):
     empty map (> 1 M slots), the GPU state re-injected into a fresh object through debug_upload_surfels, then five more
     frames on both sides -- every surfel row, the association images, the blended depth and the counters bit-equal after
     EVERY frame.  The camera pans 6 degrees per frame with the counting variant of the outlier cull (4 of 8 neighbours),
-    so every frame adds ~10^5 surfels.  (The 20 M-slot state itself is compared inside `bench.py --config C3`:
+    so every frame adds ~10^5 surfels.  (The 20 M-slot state itself is compared inside `bench.py --full --config C3`:
     parity_check in its JSON line, kept under profiles/.)"""
     import os
     from oracle import binding

@@ -148,7 +148,7 @@ def test_bench_line_of_a_real_run_is_compact_and_complete(tmp_path):
     from common import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
                         "--surfels", "300000", "--cpu-frames", "2", "--host-frames", "20", "--growth-frames", "0", "--timing-frames", "0",
                         "--detail-out", detail], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -167,6 +167,47 @@ def test_bench_line_of_a_real_run_is_compact_and_complete(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_and_dumps_the_same_outputs_every_time(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (no --full) prints the headline only, and --dump-outputs writes what the last
+    timed step computed: the same arrays in two runs, and the same as a --full run's timed window (its extra passes off)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from common import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2", "--surfels", "300000",
+            "--quiet"]
+    full = ["--full", "--cpu-frames", "0", "--host-frames", "0", "--growth-frames", "0", "--timing-frames", "0",
+            "--detail-out", str(tmp_path / "detail.json")]
+    dumps = []
+    for k, extra in enumerate(([], [], full)):
+        out = tmp_path / ("dump%d" % k)
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env,
+                           cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 8 and d["warmup"] == 2 and d["value"] > 0 and d["unit"] == "frames/s"
+        assert d["ms_per_step"] == pytest.approx(1e3 / d["value"], rel=1e-3) and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["metric"].startswith("RGB-D frames/s integrated @640x480")
+        if not extra:
+            assert d["roofline"] is None and "cpu_baseline" not in d and "detail" not in d
+        files = sorted(out.iterdir())
+        arrays = {f.stem: np.load(f) for f in files}
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        assert {"depth_final", "normals", "radius", "surfel_counts", "surfel_float_rows", "surfel_int_rows"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["surfel_counts"][1] >= 300000 and (arrays["depth_final"] > 0).sum() > 10000
+        dumps.append(arrays)
+    for other in dumps[1:]:
+        assert set(other) == set(dumps[0])
+        for name, a in dumps[0].items():
+            assert np.array_equal(a.view(np.uint8), other[name].view(np.uint8)), name
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_share_one_gpu_over_gloo():
     """C4 readiness without the 8-GPU node: bench.py's REAL timed path with two ranks under torch.distributed.run, process
     group gloo (RCCL refuses two ranks on one device; the streams are independent, the only collectives are the barrier and
@@ -179,7 +220,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     # (started plainly: bench.py --gpus 2 launches its own two ranks under torch.distributed.run)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--backend", "gloo", "--surfels", "300000", "--steps", "20", "--warmup", "5",
+                        "--gpus", "2", "--backend", "gloo", "--surfels", "300000", "--steps", "20", "--warmup", "5", "--full",
                         "--cpu-frames", "2", "--host-frames", "0", "--check-all-ranks", "--quiet"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 for rep in $(seq $REPS); do
   for v in "$@"; do
     if [ $v = NEW ]; then unset SMX_LIB_PATH; else export SMX_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/libsmx_$v.so; fi
-    timeout 600 python bench.py --full-line --config C5 --steps 3 --warmup 1 --cpu-frames 0 --quiet 2>/dev/null | python -c "import sys,json
+    timeout 600 python bench.py --full --full-line --config C5 --steps 3 --warmup 1 --cpu-frames 0 --quiet 2>/dev/null | python -c "import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); ds=d['distributions']

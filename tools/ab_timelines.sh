@@ -9,7 +9,7 @@ for rep in $(seq $REPS); do
     f="$v"; [ "$v" = "-" ] && f=""
     unset SMX_LIB_PATH
     case "$f" in LIB=*) n="${f%% *}"; n="${n#LIB=}"; export SMX_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/libsmx_$n.so; f="${f#LIB=$n}";; esac
-    timeout 300 python bench.py --full-line --config $CFG --steps $STEPS --warmup $WARM --cpu-frames 0 --host-frames 0 --timing-frames 0 --growth-frames 0 --no-other-configs --quiet $f 2>/dev/null | V="$v" python -c "import sys,json,os
+    timeout 300 python bench.py --full --full-line --config $CFG --steps $STEPS --warmup $WARM --cpu-frames 0 --host-frames 0 --timing-frames 0 --growth-frames 0 --no-other-configs --quiet $f 2>/dev/null | V="$v" python -c "import sys,json,os
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); k=d['roofline'].get('kernels',{})

@@ -6,7 +6,7 @@ set -u
 TAG=${1:-abXX}; REPS=${2:-2}; shift; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out; mkdir -p $OUT
-CMD="python bench.py --steps 300 --warmup 20 --cpu-frames 0 --host-frames 0 --quiet $*"
+CMD="python bench.py --full --steps 300 --warmup 20 --cpu-frames 0 --host-frames 0 --quiet $*"
 for v in HEAD NEW; do
   if [ $v = HEAD ]; then export SMX_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/libsmx_head.so; else unset SMX_LIB_PATH; fi
   [ $v = HEAD ] && [ ! -f build/ab/libsmx_head.so ] && continue

@@ -8,7 +8,7 @@ for cfg in C2 C3; do
   rm -f $OUT/${TAG}_ub_$cfg.jsonl
   for rep in 1 2; do
     for ub in "" hoist-pre no-reg hoist-pre,no-reg front-only hoist-pre,front-only; do
-      flags="--config $cfg --cpu-frames 0 --host-frames 0 --quiet"; [ -n "$ub" ] && flags="$flags --ub $ub"
+      flags="--full --config $cfg --cpu-frames 0 --host-frames 0 --quiet"; [ -n "$ub" ] && flags="$flags --ub $ub"
       timeout 300 python bench.py $flags 2>>$OUT/${TAG}_ub.err | tail -1 >> $OUT/${TAG}_ub_$cfg.jsonl
     done
   done
@@ -36,7 +36,7 @@ bash tools/calib.sh r17 | tail -60
 for C in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES" "SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES"; do
   N=$(echo $C | cut -d' ' -f1)
   rm -rf /tmp/prof_pmc
-  timeout 600 rocprofv3 --pmc $C --output-format csv -d /tmp/prof_pmc -o run -- python bench.py --steps 20 --warmup 5 --cpu-frames 0 --host-frames 0 --quiet > /tmp/pmc_$N.log 2>&1
+  timeout 600 rocprofv3 --pmc $C --output-format csv -d /tmp/prof_pmc -o run -- python bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --host-frames 0 --quiet > /tmp/pmc_$N.log 2>&1
   python tools/pmc_summary.py /tmp/prof_pmc $OUT/${TAG}_${N}.md > /dev/null || tail -5 /tmp/pmc_$N.log
 done
 cat $OUT/${TAG}_gputests.txt
