@@ -516,6 +516,30 @@ int smx_nn_get_stats(smx_nn nn, smx_stream s, smx_nn_stats* out);
 int smx_recon_deform_by_creation_frame(smx_recon r, smx_stream s, const float* frame_T, uint32_t n_frames,
                                        const uint8_t* reactivate, uint32_t frame_index, int32_t inputs_on_device);
 
+/* ---- map compaction (not in the reference: its map only grows) ----
+ * Removes every slot whose RadiusSquared < 0 (the merge mark) from [0, surfels_size()), keeping the remaining slots
+ * in ascending order.  Synchronous: returns when the map is compacted.
+ *   kept slots    slot i is kept iff !(RadiusSquared[i] < 0) and moves to old_to_new[i] = its rank among the kept
+ *                 slots; every attribute row except the scratch rows 11-16 and 23 moves bit for bit.
+ *   removed slots old_to_new[i] = 0xFFFFFFFF.
+ *   links         the neighbour links of kept slots (rows 19-22) go through the same map; a link to a removed slot
+ *                 becomes 0xFFFFFFFF.
+ *   counts        afterwards surfels_size() == surfel_count() (unchanged) and the merge count is 0.
+ *   links_dropped the valid links held by removed slots plus the links of kept slots that pointed into removed slots.
+ *                 A merged slot keeps its outgoing links in the reference's semantics, and the regulariser still takes
+ *                 one last gradient term from it when its neighbour re-enters the window; compaction removes that term.
+ *                 links_dropped == 0 means that the continuation is an exact relabelling of the uncompacted run.
+ * old_to_new may be NULL; otherwise it holds >= surfels_size() entries (capacity), and is a device pointer if
+ * on_device, a host pointer otherwise.  A capacity that is too small fails with SMX_ERR_INVALID_ARGUMENT and leaves
+ * the map unchanged.  new_size and links_dropped (host pointers) may be NULL.
+ * The call is ordered after everything enqueued on the object before it (the pipelined regulariser and a deferred
+ * smx_recon_integrate_hooks wait included); the next smx_recon_integrate may use any frame_index, as after a state
+ * upload.  With delta tracking on, the next smx_recon_transfer_changed_to_cpu delivers every slot in [0, new_size).
+ * A neighbour index (smx_nn) built before the call is stale: the caller rebuilds it, and remaps every slot index it
+ * holds (mesher triangles, candidate lists) through old_to_new. */
+int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t capacity, int32_t on_device,
+                      uint32_t* new_size, uint32_t* links_dropped);
+
 /* ---- candidate lists for the mesher, straight from the device-resident map ----
  * Replaces, for the surfels of one batch (e.g. one changed-surfel delta), the per-surfel octree query at the top of
  * SurfelMeshing::TriangulateSurfel (APP/surfel_meshing.cc:417-425) with the widest radius that function can ask for,

@@ -527,6 +527,18 @@ class CUDASurfelReconstruction {
                              u32 frame_index) {
     SMX_SHIM_CHECK(smx_recon_deform_by_creation_frame(handle_, stream, frame_T, frame_count, reactivate, frame_index, 0));
   }
+  // Not in the reference: removes the merged slots from the map and keeps the rest in order (synchronous; see
+  // smx_recon_compact in smx.h).  old_to_new (resized to the old slot count) receives each old slot's new index or
+  // 0xFFFFFFFF; a mesher remaps its triangles and candidate lists through it and rebuilds its neighbour index.
+  void Compact(cudaStream_t stream, std::vector<u32>* old_to_new = nullptr, u32* links_dropped = nullptr) {
+    u32 n = 0;
+    if (old_to_new) {
+      n = surfels_size();
+      old_to_new->resize(n);
+    }
+    SMX_SHIM_CHECK(smx_recon_compact(handle_, stream, old_to_new && n ? old_to_new->data() : nullptr, n, 0, nullptr,
+                                     links_dropped));
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

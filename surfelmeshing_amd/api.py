@@ -496,6 +496,21 @@ class CUDASurfelReconstruction:
             _lib.check(rc)
         return d
 
+    def Compact(self, stream, return_map=True):
+        """Not in the reference: removes the merged slots from the map, keeping the rest in ascending order
+        (synchronous; smx_recon_compact).  Returns (old_to_new, new_size, links_dropped): old_to_new (uint32 per old
+        slot: its new index, or 0xFFFFFFFF for a removed slot) is None unless return_map.  links_dropped == 0 means the
+        continuation is an exact relabelling of the uncompacted run.  A neighbour index built before is stale."""
+        old_to_new = None
+        if return_map:
+            old_to_new = np.empty(self._counts_on(stream)[1], np.uint32)
+        new_size, dropped = C.c_uint32(0), C.c_uint32(0)
+        ptr = old_to_new.ctypes.data_as(C.c_void_p) if old_to_new is not None and old_to_new.size else None
+        cap = old_to_new.size if old_to_new is not None else 0
+        _lib.check(_lib.load().smx_recon_compact(self._h, _sv(stream), ptr, C.c_uint32(cap), C.c_int32(0),
+                                                 C.byref(new_size), C.byref(dropped)))
+        return old_to_new, int(new_size.value), int(dropped.value)
+
     def DeformByCreationFrame(self, stream, frame_T, reactivate=None, frame_index=0):
         """The loop-closure hook the reference describes but does not ship (README.md:152-176): surfels created at
         frame c move by the rigid correction frame_T[c] ([n_frames, 3, 4] / [n_frames, 12]); reactivate[c] != 0
@@ -547,8 +562,11 @@ class CUDASurfelReconstruction:
         return tuple(out), int(call.value)
 
     def _counts(self):
+        return self._counts_on(self._last_stream)
+
+    def _counts_on(self, stream):
         a, b = C.c_uint32(), C.c_uint32()
-        _lib.check(_lib.load().smx_recon_counts(self._h, _sv(self._last_stream), C.byref(a), C.byref(b)))
+        _lib.check(_lib.load().smx_recon_counts(self._h, _sv(stream), C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def surfel_count(self):

@@ -3129,6 +3129,106 @@ k_delta_gather(Surfels S, uint8_t* __restrict__ dirty8, const uint32_t* __restri
     }
 }
 
+// ---- map compaction (smx_recon_compact; not in the reference) -----------------------------------------------------
+// Count / scan / map / scatter over kSeg-slot segments, four slots per lane as in the delta kernels above: per-segment
+// counts of the kept slots (!(RadiusSquared < 0): the merge mark), k_delta_scan over the counts, old_to_new for every
+// old slot, then one scatter launch per record group.  A stable compaction IN PLACE races (a workgroup would overwrite
+// source records that an earlier workgroup has not read yet), so each group is scattered into the staging buffer
+// (16 B per old slot) and copied back before the next group is scattered: peak extra memory 16 B + 4 B per slot.
+// The G record (rows 11-13, the parked next smooth position) is scratch within a call and does not move.
+__global__ void __launch_bounds__(kBlock)
+k_compact_count(Surfels S, uint32_t n, uint8_t* __restrict__ keep4, uint32_t* __restrict__ seg_count) {
+  __shared__ uint32_t wave_tot[kBlock / 64];
+  const uint32_t lane_id = blockIdx.x * kBlock + threadIdx.x, i0 = lane_id * 4;
+  uint32_t bits = 0;
+  if (i0 < n) {   // (i0 + 3 < pitch: the group arrays are padded to a multiple of 64 slots)
+    const float r0 = S.f(kRadiusSq, i0), r1 = S.f(kRadiusSq, i0 + 1), r2 = S.f(kRadiusSq, i0 + 2), r3 = S.f(kRadiusSq, i0 + 3);
+    bits = (!(r0 < 0) ? 1u : 0u) | ((i0 + 1 < n && !(r1 < 0)) ? 2u : 0u) | ((i0 + 2 < n && !(r2 < 0)) ? 4u : 0u) |
+           ((i0 + 3 < n && !(r3 < 0)) ? 8u : 0u);
+    keep4[lane_id] = (uint8_t)bits;
+  }
+  uint32_t total;
+  (void)block_excl_scan((uint32_t)__popc(bits), wave_tot, total);
+  if (threadIdx.x == 0) seg_count[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(kBlock)
+k_compact_map(const uint8_t* __restrict__ keep4, const uint32_t* __restrict__ seg_offset, uint32_t n, uint32_t* __restrict__ map) {
+  __shared__ uint32_t wave_tot[kBlock / 64];
+  const uint32_t lane_id = blockIdx.x * kBlock + threadIdx.x, i0 = lane_id * 4;
+  const uint32_t bits = i0 < n ? keep4[lane_id] : 0u;
+  uint32_t seg_total;
+  uint32_t off = seg_offset[blockIdx.x] + block_excl_scan((uint32_t)__popc(bits), wave_tot, seg_total);
+  if (i0 >= n) return;
+  uint32_t m[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m[j] = (bits & (1u << j)) ? off++ : kInvalid;
+  *reinterpret_cast<uint4*>(&map[i0]) = make_uint4(m[0], m[1], m[2], m[3]);   // (map has pitch entries)
+}
+// One record group: the records of the kept slots go to out[old_to_new[i]] (one 16-byte load and store per record).
+// Lane l of a segment's workgroup takes the slots l, l + 256, l + 512, l + 768 of it, so that every load instruction of
+// a wavefront reads 1 KB in one piece and the stores (ascending destinations with gaps) stay nearly contiguous.  (Four
+// consecutive slots per lane, as in the count kernel, left every instruction 64 B-strided: 75 us per group at C2.)
+// kLinks (group T): the four links go through the map as well, and the links that compaction drops are counted --
+// those of removed slots and those of kept slots into removed ones.
+template <bool kLinks>
+__global__ void __launch_bounds__(kBlock)
+k_compact_scatter(Surfels S, int g, const uint32_t* __restrict__ map, uint32_t n, float4* __restrict__ out,
+                  uint32_t* __restrict__ dropped) {
+  __shared__ uint32_t wave_tot[kBlock / 64];
+  const uint32_t base = blockIdx.x * kSeg + threadIdx.x;
+  uint32_t dst[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) dst[j] = base + j * kBlock < n ? map[base + j * kBlock] : kInvalid;
+  uint32_t drop = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t i = base + j * kBlock;
+    if (i >= n) continue;
+    if (kLinks) {
+      const uint4 t = *reinterpret_cast<const uint4*>(S.group(kGroupT, i));
+      uint32_t nb[4] = {t.x, t.y, t.z, t.w};
+      if (dst[j] == kInvalid) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) drop += nb[q] != kInvalid ? 1u : 0u;
+        continue;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (nb[q] == kInvalid) continue;
+        nb[q] = nb[q] < n ? map[nb[q]] : kInvalid;   // (the map is read-mostly and small: these gathers hit the caches)
+        drop += nb[q] == kInvalid ? 1u : 0u;
+      }
+      out[dst[j]] = make_float4(__uint_as_float(nb[0]), __uint_as_float(nb[1]), __uint_as_float(nb[2]), __uint_as_float(nb[3]));
+    } else if (dst[j] != kInvalid) {
+      out[dst[j]] = *S.group(g, i);
+    }
+  }
+  if (kLinks) {
+    uint32_t total;
+    (void)block_excl_scan(drop, wave_tot, total);
+    if (threadIdx.x == 0 && total) atomicAdd(dropped, total);
+  }
+}
+__global__ void __launch_bounds__(kBlock)
+k_compact_copy(Surfels S, int g, const float4* __restrict__ src, const uint32_t* __restrict__ total) {
+  const uint32_t K = *total;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < K; i += gridDim.x * kBlock) *S.group(g, i) = src[i];
+}
+// The device state after compaction: the new count, no merged slots, every other counter reset (as a state upload does).
+__global__ void k_compact_finish(DevState* st, const uint32_t* __restrict__ total) {
+  if (threadIdx.x != 0) return;
+  DevState h;
+  memset(&h, 0, sizeof(h));
+  h.surfel_count = *total;
+  *st = h;
+}
+// Delta tracking: every slot of the compacted map counts as changed, the marks at and above the new count are cleared.
+__global__ void __launch_bounds__(kBlock)
+k_compact_dirty(uint8_t* __restrict__ dirty8, uint32_t bytes, const uint32_t* __restrict__ total) {
+  const uint32_t K = *total;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < bytes; i += gridDim.x * kBlock) dirty8[i] = i < K ? 1 : 0;
+}
+
 // Boundary conversion between the grouped records and the reference's row layout: out[k][i] = row rows[k] of
 // slot i (pack) and back (unpack).  Rows without storage read as 0.
 struct RowList { int n; int rows[kRows]; };
@@ -3389,6 +3489,9 @@ struct smx_recon_s {
   uint8_t* flags_buf[2];    // the flag table is double-buffered by frame (L.flags8 = the current frame's)
   bool have_frame;          // an Integrate call has been made since creation / the last state upload
   uint32_t last_frame;      // its frame_index: the segment culling of pass A presumes that it never decreases
+  uint32_t* cmp_map;        // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
+  uint32_t* cmp_seg;        // offsets [nseg], and [0] = new count, [1] = links dropped
+  uint32_t* cmp_out;
 };
 
 // kernel slots of one Integrate call (launch order)
@@ -3697,7 +3800,8 @@ int smx_recon_destroy(smx_recon r) {
                   r->tb.pairs, r->tb.count, r->tb.ovf, r->ovf_count_set[0], r->ovf_count_set[1],
                   r->vis_count_set[0], r->vis_count_set[1], r->L.seg_act, r->L.seg_streak, r->sw.surv_list, r->sw.copy_list, r->sw.count, r->blended_depth, r->cand_q, r->cand_slots, r->cand_state, r->L.dirty8, r->delta_seg, r->delta_total, r->staging, r->S.base, r->grad_acc, r->reg_rec, r->fb.rec, r->fb.count, r->L.vis_list, r->L.recent_list, r->L.vis_seg, r->L.seg_box, r->L.recent_seg, r->L.vis_chunks.desc, r->L.rec_chunks.desc, r->L.acc_chunks.desc, r->L.rec_chunks.count, r->flags_buf[0], r->flags_buf[1], r->L.hot_epoch, r->L.seg_targets,
                   r->merge_flag, r->L.act_list, r->bb.distance_map, r->bb.new_distance_map,
-                  r->bb.deltas, r->bb.new_deltas, r->new_flags, r->new_ranks, r->tmp_u32, r->block_sums, r->block_offsets, r->st};
+                  r->bb.deltas, r->bb.new_deltas, r->new_flags, r->new_ranks, r->tmp_u32, r->block_sums, r->block_offsets, r->st,
+                  r->cmp_map, r->cmp_seg, r->cmp_out};
   if (r->reg_stream) { (void)hipStreamSynchronize(r->reg_stream); (void)hipStreamDestroy(r->reg_stream); }
   if (r->dir_host) { (void)hipDeviceSynchronize(); (void)hipHostFree(r->dir_host); }
   if (r->ts_host) (void)hipHostFree(r->ts_host);
@@ -4537,6 +4641,83 @@ int smx_recon_debug_upload_surfels(smx_recon r, smx_stream s, const float* rows,
   int rc = invalidate_derived(r, st);
   if (rc != SMX_OK) return rc;
   SMX_HIP(hipStreamSynchronize(st));
+  return SMX_OK;
+}
+
+int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t capacity, int32_t on_device,
+                      uint32_t* new_size, uint32_t* links_dropped) {
+  SMX_CHECK_ARG(r != nullptr);
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  uint32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  if (old_to_new && capacity < n) {   // (nothing has been changed yet)
+    set_error("old_to_new holds %u entries, the map has %u slots", capacity, n);
+    return SMX_ERR_INVALID_ARGUMENT;
+  }
+  if (!r->cmp_map) {
+    int rc = dev_alloc(&r->cmp_map, r->S.pitch, false);
+    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_seg, (size_t)r->nseg, false);
+    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_out, 2, false);
+    if (rc != SMX_OK) return rc;
+  }
+  SMX_HIP(hipMemsetAsync(r->cmp_out, 0, 2 * sizeof(uint32_t), st));
+  const dim3 b(kBlock);
+  if (n) {
+    const int nseg_used = div_up((long long)n, kSeg);
+    // (merge_flag -- one byte per slot, reset below -- holds the keep bits: a byte per four slots)
+    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, r->cmp_seg);
+    hipLaunchKernelGGL(k_delta_scan, dim3(1), dim3(1024), 0, st, r->cmp_seg, nseg_used, r->cmp_out);
+    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, r->cmp_seg, n, r->cmp_map);
+    SMX_LAUNCH_CHECK();
+    int rc = acquire_staging(r, st, (size_t)4 * n);
+    if (rc != SMX_OK) return rc;
+    float4* tmp = reinterpret_cast<float4*>(r->staging);
+    const int groups[5] = {kGroupP, kGroupS, kGroupN, kGroupC, kGroupT};
+    for (int g : groups) {
+      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
+      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
+      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, r->cmp_out);
+    }
+    SMX_LAUNCH_CHECK();
+    rc = release_staging(r, st);
+    if (rc != SMX_OK) return rc;
+  }
+  // Derived state: everything a state upload resets (smx_recon_debug_upload_surfels), and the state an upload of the
+  // same slots never had to care about, because compaction changes WHICH SLOT a byte belongs to:
+  //  * both copies of the double-buffered flag table: zeroed, the current one rebuilt from the records, and copied
+  //    into the other (pass A of the next call reads the current copy; the other one is relied on through seg_streak);
+  //  * seg_streak = 0: a streak >= 2 means "the copy written two calls ago already holds this segment's bytes";
+  //  * hot_epoch = this call's epoch: every group counts as hot for the next calls (a group that looks hot only costs
+  //    gathers; the hold-off of invalidate_derived keeps pass B unfiltered for two calls in any case, after which
+  //    every mark it reads has been written after the compaction);
+  //  * seg_targets = all groups: a superset of the groups a segment's links point into, which is all the skip test
+  //    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
+  // The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
+  // has been read again, and reading a segment resets its streak).
+  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, r->cmp_out);
+  SMX_HIP(hipMemsetAsync(r->grad_acc, 0, 2 * r->S.pitch * sizeof(long long), st));
+  SMX_HIP(hipMemsetAsync(r->fb.count, 0, (size_t)r->nsegB * kCountStride * sizeof(uint32_t), st));
+  SMX_HIP(hipMemsetAsync(r->merge_flag, 0, r->S.pitch, st));
+  if (r->L.dirty8)
+    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), r->cmp_out);
+  SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
+  SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
+  SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
+  SMX_HIP(hipMemsetAsync(r->L.hot_epoch, (int)(r->L.epoch & 255u), (size_t)r->L.n_hot_groups + 64, st));
+  SMX_HIP(hipMemsetAsync(r->L.seg_targets, 0xFF, (size_t)r->nsegB * kBlockB * sizeof(uint16_t), st));
+  { const int rci = invalidate_derived(r, st); if (rci != SMX_OK) return rci; }   // (rebuilds the current flag table)
+  uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
+  SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
+  if (old_to_new && n)
+    SMX_HIP(hipMemcpyAsync(old_to_new, r->cmp_map, (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  uint32_t out[2] = {0, 0};
+  SMX_HIP(hipMemcpyAsync(out, r->cmp_out, sizeof(out), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  if (new_size) *new_size = out[0];
+  if (links_dropped) *links_dropped = out[1];
   return SMX_OK;
 }
 

@@ -155,6 +155,11 @@ class FramePipeline:
         self.preprocess(frame_index, other_frames, others_TR_reference)
         self.integrate(frame_index, global_T_frame)
 
+    def compact(self, return_map=True):
+        """Removes the merged slots from the map (CUDASurfelReconstruction.Compact): (old_to_new, new_size,
+        links_dropped).  The frame loop may go on with any frame index afterwards."""
+        return self.reconstruction.Compact(self.stream, return_map)
+
 
 # ---- native driver (include/smx_driver.h): the same per-frame sequence in C++ -----------------------
 import ctypes as _C

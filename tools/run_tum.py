@@ -1,7 +1,8 @@
 """The reference application's reconstruction loop (APP/main.cc:884-1267, without the mesher and the viewer) on a TUM
 RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> optional OBJ / PLY export.
       python tools/run_tum.py <dataset_folder> [--trajectory groundtruth.txt] [--export_mesh out.obj]
-                              [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L] ...
+                              [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
+                              [--compact_every N] [--compact_at_fill F] ...
 With --synthetic N it first writes an N-frame synthetic dataset into the folder (the test stream), so that the whole
 path can be exercised without data."""
 import argparse
@@ -28,6 +29,10 @@ def main():
     ap.add_argument("--end_frame", type=int, default=2 ** 31)
     ap.add_argument("--export_mesh")
     ap.add_argument("--export_point_cloud")
+    ap.add_argument("--compact_every", type=int, default=0,
+                    help="remove the merged slots from the map before every N-th integrated frame (0 = never)")
+    ap.add_argument("--compact_at_fill", type=float, default=0.0,
+                    help="remove the merged slots before a frame when surfels_size() >= F * max_surfel_count (0 = never)")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
@@ -65,6 +70,7 @@ def main():
     uploaded = set()
     t0 = time.time()
     done = 0
+    compactions, removed = 0, 0
     for f in range(args.start_frame, n):
         # main.cc:905-968: everything up to f + half + 1 is on the GPU before frame f is processed
         for g in range(f, min(n - 1, f + half + 1) + 1):
@@ -78,6 +84,12 @@ def main():
         others = [f - k for k in range(1, half + 1)] + [f + k for k in range(1, half + 1)]    # main.cc:1039-1059
         G = video.depth_frame(f).global_T_frame()
         T = others_TR_reference(G, [video.depth_frame(g).global_T_frame() for g in others], args.depth_scaling)
+        if done and ((args.compact_every > 0 and done % args.compact_every == 0) or
+                     (args.compact_at_fill > 0 and
+                      pipe.reconstruction.surfels_size() >= args.compact_at_fill * args.max_surfel_count)):
+            before = pipe.reconstruction.surfels_size()
+            _, after, _ = pipe.compact(return_map=False)
+            compactions, removed = compactions + 1, removed + before - after
         pipe.process(f, others, T, G)
         done += 1
         old = f - half - 1                                                                      # main.cc:1226-1240
@@ -88,6 +100,8 @@ def main():
     rec = pipe.reconstruction
     print("%d frames integrated in %.2f s (%.1f frames/s incl. PNG decoding); %d surfels (%d merged)" % (
         done, dt, done / max(dt, 1e-9), rec.surfels_size(), rec.surfels_size() - rec.surfel_count()))
+    if compactions:
+        print("%d compactions removed %d merged slots" % (compactions, removed))
     if args.export_mesh:
         export.SaveMeshAsOBJ(rec, args.export_mesh)
         print("Wrote %s." % args.export_mesh)
