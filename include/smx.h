@@ -540,6 +540,84 @@ int smx_recon_deform_by_creation_frame(smx_recon r, smx_stream s, const float* f
 int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t capacity, int32_t on_device,
                       uint32_t* new_size, uint32_t* links_dropped);
 
+/* ---- viewer buffers: UpdateVisualizationBuffers, .h:100-108 / .cc:361-403 ----
+ * The reference's three fill kernels (APP/cuda_surfel_reconstruction_kernels.cu:278-351, 434-449, 498-514) over
+ * slots [0, surfels_size()) -- merged slots included -- into device buffers the caller owns (a viewer maps its GL
+ * buffers itself and passes the pointers; the library does no graphics interop).  A NULL buffer is skipped; each
+ * buffer receives slots [0, min(surfels_size(), its capacity)) and nothing beyond its capacity is written.  The slot
+ * count is read on the device: the call enqueues work on s, ordered after the pipelined regulariser, and does not
+ * synchronise with the host.  It changes no map state.
+ *   vertex_buffer         4 floats per slot (Point3fC3u8): smooth x, y, z, then the 32 colour bits (uchar4 r, g, b, w).
+ *                         x is NaN when creation_stamp > latest_triangulated_frame_index && slot < latest_mesh_surfel_count.
+ *                         Colour, by precedence of the flags below:
+ *                           LAST_UPDATE or CREATION  age = int(frame_index - stamp) (u32 difference), stamp = the creation
+ *                                                  stamp if CREATION is set, the last-update stamp otherwise; age < 1 ->
+ *                                                  (255, 80, 80), age > max -> (40, 40, 255), else grey 255 -
+ *                                                  u8(255.99 * clamp((age - 1) / (max - 1))); max = 3000 for CREATION,
+ *                                                  surfel_integration_active_window_size otherwise
+ *                           RADII                  red = u8(255.99 * clamp((sqrt(r^2) - 0.0005) / 0.0095)), green = 255 -
+ *                                                  red, blue = 80 (a merged slot: NaN -> clamp gives 0 -> (0, 255, 80))
+ *                           NORMALS                u8(127.995 * (n + 1)) per axis
+ *                           none                   the colour row's 32 bits as they are
+ *                         (clamp is fminf(1, fmaxf(0, .)); the byte w is 0 in the computed modes)
+ *   neighbor_index_buffer 8 u32 per slot: (slot, neighbour k or slot if the link is invalid) for k = 0..3
+ *   normal_vertex_buffer  6 floats per slot: smooth position, smooth position + sqrt(r^2) * normal */
+enum {
+  SMX_VIS_LAST_UPDATE = 1,   /* visualize_last_update_timestamp */
+  SMX_VIS_CREATION = 2,      /* visualize_creation_timestamp */
+  SMX_VIS_RADII = 4,         /* visualize_radii */
+  SMX_VIS_NORMALS = 8        /* visualize_normals */
+};
+int smx_recon_update_visualization_buffers(smx_recon r, smx_stream s, uint32_t frame_index,
+    uint32_t latest_triangulated_frame_index, uint32_t latest_mesh_surfel_count,
+    int32_t surfel_integration_active_window_size, int32_t flags,
+    float* vertex_buffer, uint32_t vertex_capacity,
+    uint32_t* neighbor_index_buffer, uint32_t neighbor_capacity,
+    float* normal_vertex_buffer, uint32_t normal_capacity);
+
+/* ---- headless map rendering (not in the reference: its viewer draws the vertex buffer with OpenGL) ----
+ * Rasterises the live slots (i < surfels_size(), RadiusSquared >= 0) as splats into a 64-bit z-buffer and resolves it
+ * into images of any size, from any camera.  p = smooth position, n = normal, c = R^T (p - t), n_c = R^T n for
+ * global_T_camera = [R | t] (row-major 3x4, inverted on the host as in smx_recon_integrate, here in double precision;
+ * the splat geometry is evaluated in double precision too, the key's depth is that value rounded to float).  A slot is drawn if
+ * near_z < c.z < far_z; u = fx c.x / c.z + cx, v = fy c.y / c.z + cy (pixel-corner convention: pixel (x, y) spans
+ * [x, x+1) x [y, y+1)).
+ *   SMX_SPLAT_SQUARE  pixel covered iff |x + 1/2 - u| <= h and |y + 1/2 - v| <= h, h = splat_half_extent_in_pixels
+ *                     (h = 0: the pixel (floor u, floor v) only); depth c.z.
+ *   SMX_SPLAT_DISC    a disc of radius rho = disc_radius_factor * sqrt(r^2) around p, normal n.  Candidate pixels: centre
+ *                     within e of (u, v) per axis, e = max_splat_extent_in_pixels if c.z - rho <= near_z, else
+ *                     min(max extent, 2 max(fx, fy) rho / (c.z - rho)).  Ray d = ((x + 1/2 - cx) / fx, (y + 1/2 - cy) / fy, 1);
+ *                     skipped if |n_c . d| < 1e-4; t = (n_c . c) / (n_c . d); covered iff t > near_z and
+ *                     |t d - c|^2 <= rho^2; depth t.
+ * Z-test: every pixel keeps the minimum of (float_bits(depth) << 32) | slot (ties go to the lower slot): the result
+ * does not depend on scheduling, two renders are bit-identical.  Outputs (each may be NULL; otherwise exactly
+ * height x width with the element size given, any pitch):
+ *   depth  float   the winner's depth, 0 where no splat covers the pixel
+ *   index  u32     the winning slot, 0xFFFFFFFF where empty
+ *   normal float4  (n_c, 0) of the winner, zeros where empty
+ *   color  uchar4  the winner's vertex-buffer colour (smx_recon_update_visualization_buffers, color_flags) with alpha
+ *                  255; (0, 0, 0, 0) where empty
+ * Enqueued on s after the pipelined regulariser, no host synchronisation; the map is only read (no delta marks, stats
+ * or stamps change), so a render is valid between any two smx_recon_integrate calls.  The z-buffer (width x height x
+ * 8 bytes) belongs to the object and grows on demand (growing it waits for the device).  Invalid sizes, parameters or
+ * descriptors fail with SMX_ERR_INVALID_ARGUMENT. */
+enum { SMX_SPLAT_SQUARE = 0, SMX_SPLAT_DISC = 1 };
+typedef struct {
+  int32_t width, height;
+  float fx, fy, cx, cy;                    /* pixel-corner convention */
+  float global_T_camera[12];               /* row-major 3x4 */
+  float near_z, far_z;                     /* 0 < near_z < far_z */
+  int32_t splat_mode;                      /* SMX_SPLAT_* */
+  float splat_half_extent_in_pixels;       /* square mode, >= 0 (the reference viewer's default: 3) */
+  float disc_radius_factor;                /* disc mode, > 0 (default 1) */
+  float max_splat_extent_in_pixels;        /* disc mode, > 0 (default 16) */
+  int32_t color_flags;                     /* SMX_VIS_* */
+  uint32_t frame_index;                    /* for the age colours */
+  int32_t surfel_integration_active_window_size;
+} smx_render_params;
+int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, const smx_buffer_desc* depth,
+                     const smx_buffer_desc* index, const smx_buffer_desc* normal, const smx_buffer_desc* color);
+
 /* ---- candidate lists for the mesher, straight from the device-resident map ----
  * Replaces, for the surfels of one batch (e.g. one changed-surfel delta), the per-surfel octree query at the top of
  * SurfelMeshing::TriangulateSurfel (APP/surfel_meshing.cc:417-425) with the widest radius that function can ask for,

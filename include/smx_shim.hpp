@@ -62,6 +62,9 @@ static_assert(sizeof(::float2) == 8, "float2 must be two packed floats");
 #ifndef SMX_SHIM_NO_VEC_TYPES
 struct Vec3u8 { u8 v[3]; };
 #endif
+// element types of the render's normal and colour images (smx_recon_render): float4 (camera-frame normal, 0) and uchar4 (r, g, b, a)
+struct RenderNormal { float x, y, z, w; };
+struct RenderColor { u8 r, g, b, a; };
 
 // Row-major 3x4 rigid transform (host part of VIS/cuda/cuda_matrix.cuh:67-116).  As in the reference it is
 // constructible from ANY matrix type with (row, col) element access -- the call sites hand it an Eigen 3x4 from
@@ -546,7 +549,40 @@ class CUDASurfelReconstruction {
     SMX_SHIM_CHECK(smx_recon_check_triangles(handle_, stream, triangle_indices, count, long_edge_total_factor_squared,
                                              flags, 0));
   }
-  void UpdateVisualizationBuffers(cudaStream_t, u32, u32, u32, int, bool, bool, bool, bool) {}  // viewer only
+  // Not in the reference: the viewer's buffers.  The reference maps the GL buffers it received in its constructor; the
+  // library does no graphics interop, so a viewer maps them itself and passes the device pointers here (capacities in
+  // slots: 16 B per vertex, 32 B of neighbour index pairs, 24 B of normal vertices per slot; nullptr = not drawn).
+  void SetVisualizationBuffers(void* vertex_buffer, u32 vertex_capacity, void* neighbor_index_buffer,
+                               u32 neighbor_index_capacity, void* normal_vertex_buffer, u32 normal_vertex_capacity) {
+    vis_vertex_ = static_cast<float*>(vertex_buffer);
+    vis_vertex_capacity_ = vertex_capacity;
+    vis_neighbor_index_ = static_cast<u32*>(neighbor_index_buffer);
+    vis_neighbor_index_capacity_ = neighbor_index_capacity;
+    vis_normal_vertex_ = static_cast<float*>(normal_vertex_buffer);
+    vis_normal_vertex_capacity_ = normal_vertex_capacity;
+  }
+  // .h:100-108 / .cc:361-403: fills the buffers given to SetVisualizationBuffers (the reference's `if (...resource_)`
+  // checks); without them it does nothing.  Enqueued on `stream`, no host synchronisation.
+  void UpdateVisualizationBuffers(cudaStream_t stream, u32 frame_index, u32 latest_triangulated_frame_index,
+                                  u32 latest_mesh_surfel_count, int surfel_integration_active_window_size,
+                                  bool visualize_last_update_timestamp, bool visualize_creation_timestamp,
+                                  bool visualize_radii, bool visualize_normals) {
+    if (!vis_vertex_ && !vis_neighbor_index_ && !vis_normal_vertex_) return;
+    const int flags = (visualize_last_update_timestamp ? SMX_VIS_LAST_UPDATE : 0) |
+                      (visualize_creation_timestamp ? SMX_VIS_CREATION : 0) | (visualize_radii ? SMX_VIS_RADII : 0) |
+                      (visualize_normals ? SMX_VIS_NORMALS : 0);
+    SMX_SHIM_CHECK(smx_recon_update_visualization_buffers(
+        handle_, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
+        surfel_integration_active_window_size, flags, vis_vertex_, vis_vertex_capacity_, vis_neighbor_index_,
+        vis_neighbor_index_capacity_, vis_normal_vertex_, vis_normal_vertex_capacity_));
+  }
+  // Not in the reference: headless splat rendering of the map (smx_recon_render in smx.h); each image may be nullptr.
+  void Render(cudaStream_t stream, const smx_render_params& params, CUDABuffer<float>* depth, CUDABuffer<u32>* index,
+              CUDABuffer<RenderNormal>* normal, CUDABuffer<RenderColor>* color) {
+    SMX_SHIM_CHECK(smx_recon_render(handle_, stream, &params, depth ? depth->ToCUDA().desc() : nullptr,
+                                    index ? index->ToCUDA().desc() : nullptr, normal ? normal->ToCUDA().desc() : nullptr,
+                                    color ? color->ToCUDA().desc() : nullptr));
+  }
   void ExportVertices(cudaStream_t stream, CUDABuffer<float>* position_buffer, CUDABuffer<u8>* color_buffer) {
     SMX_SHIM_CHECK(smx_recon_export_vertices(handle_, stream, position_buffer->ToCUDA().desc(), color_buffer->ToCUDA().desc()));
   }
@@ -584,6 +620,10 @@ class CUDASurfelReconstruction {
  private:
   smx_recon handle_ = nullptr;
   cudaStream_t last_stream_ = nullptr;
+  float* vis_vertex_ = nullptr;   // SetVisualizationBuffers
+  u32* vis_neighbor_index_ = nullptr;
+  float* vis_normal_vertex_ = nullptr;
+  u32 vis_vertex_capacity_ = 0, vis_neighbor_index_capacity_ = 0, vis_normal_vertex_capacity_ = 0;
 };
 
 // ---- batched counterpart of CompressedOctree::FindNearestSurfelsWithinRadius (APP/octree.h:470-477) ----

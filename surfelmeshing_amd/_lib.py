@@ -47,6 +47,22 @@ class IntegrateParams(C.Structure):
         return p
 
 
+class RenderParams(C.Structure):
+    """smx_render_params: camera, splat shape and colour mode of smx_recon_render."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("global_T_camera", C.c_float * 12),
+                ("near_z", C.c_float), ("far_z", C.c_float),
+                ("splat_mode", C.c_int32),
+                ("splat_half_extent_in_pixels", C.c_float),
+                ("disc_radius_factor", C.c_float),
+                ("max_splat_extent_in_pixels", C.c_float),
+                ("color_flags", C.c_int32),
+                ("frame_index", C.c_uint32),
+                ("surfel_integration_active_window_size", C.c_int32)]
+
+
+
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
     _fields_ = [("frame_index", C.c_uint32), ("surfel_count", C.c_size_t),
@@ -94,7 +110,7 @@ EXPORTS = [
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",
-    "smx_recon_compact", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
+    "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
     "smx_recon_set_scan_mode", "smx_recon_debug_set_skip", "smx_recon_set_overlap", "smx_recon_integrate_hooks", "smx_recon_integrate_inputs_ready",
     "smx_nn_create", "smx_nn_destroy", "smx_nn_build", "smx_nn_query_batch", "smx_nn_query_self", "smx_nn_set_query_mode", "smx_nn_set_stats_enabled", "smx_nn_get_stats",
     "smx_synth_render_room",

@@ -22,10 +22,50 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import BufferDesc, IntegrateParams, SmxError, SurfelBuffersCPU, ReconStats  # noqa: F401
+from ._lib import BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats  # noqa: F401
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
+
+# smx.h: colour modes of the viewer buffers and the render, splat shapes of the render
+SMX_VIS_LAST_UPDATE, SMX_VIS_CREATION, SMX_VIS_RADII, SMX_VIS_NORMALS = 1, 2, 4, 8
+SMX_SPLAT_SQUARE, SMX_SPLAT_DISC = 0, 1
+
+
+def vis_flags(visualize_last_update_timestamp=False, visualize_creation_timestamp=False, visualize_radii=False,
+              visualize_normals=False):
+    return ((SMX_VIS_LAST_UPDATE if visualize_last_update_timestamp else 0) |
+            (SMX_VIS_CREATION if visualize_creation_timestamp else 0) |
+            (SMX_VIS_RADII if visualize_radii else 0) | (SMX_VIS_NORMALS if visualize_normals else 0))
+
+
+def make_render_params(width, height, fx, fy, cx, cy, global_T_camera, near_z=0.05, far_z=1000.0,
+                       splat_mode=SMX_SPLAT_SQUARE, splat_half_extent_in_pixels=3.0, disc_radius_factor=1.0,
+                       max_splat_extent_in_pixels=16.0, color_flags=0, frame_index=0,
+                       surfel_integration_active_window_size=2147483647):
+    """An smx_render_params.  Defaults: the reference viewer's --splat_half_extent_in_pixels (APP/main.cc:506), a disc as
+    large as the surfel, splats of at most 16 pixels, the surfels' own colours."""
+    T = np.asarray(global_T_camera, np.float32).reshape(12)
+    return RenderParams(int(width), int(height), fx, fy, cx, cy, (C.c_float * 12)(*[float(v) for v in T]), near_z,
+                        far_z, int(splat_mode), splat_half_extent_in_pixels, disc_radius_factor,
+                        max_splat_extent_in_pixels, int(color_flags), int(frame_index) & 0xFFFFFFFF,
+                        int(surfel_integration_active_window_size))
+
+
+def _slots_of(buf, slot_bytes):
+    """(device pointer, capacity in slots) of a viewer buffer: None, a CUDABuffer whose rows lie back to back, an
+    object with data_ptr() / numel() / element_size() (a torch tensor on the GPU), or a (pointer, capacity) pair."""
+    if buf is None:
+        return C.c_void_p(0), 0
+    if isinstance(buf, CUDABuffer):
+        d = buf.ToCUDA()
+        if d.height > 1 and d.pitch != d.width * buf.elem_bytes:
+            raise ValueError("a viewer buffer needs its rows back to back (height 1)")
+        return C.c_void_p(d.address), (d.width * d.height * buf.elem_bytes) // slot_bytes
+    if hasattr(buf, "data_ptr"):
+        return C.c_void_p(buf.data_ptr()), (buf.numel() * buf.element_size()) // slot_bytes
+    ptr, cap = buf
+    return C.c_void_p(int(ptr)), int(cap)
 
 
 def _stream(s):
@@ -533,8 +573,34 @@ class CUDASurfelReconstruction:
             C.c_float(long_edge_total_factor_squared), flags.ctypes.data_as(C.c_void_p), C.c_int32(0)))
         return flags
 
-    def UpdateVisualizationBuffers(self, *args, **kwargs):
-        """Viewer-only in the reference (OpenGL interop); nothing to do without a render window."""
+    def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
+                                   surfel_integration_active_window_size, visualize_last_update_timestamp=False,
+                                   visualize_creation_timestamp=False, visualize_radii=False, visualize_normals=False,
+                                   vertex_buffer=None, neighbor_index_buffer=None, normal_vertex_buffer=None):
+        """The reference fills its viewer's GL buffers (.cc:361-403); here the caller passes the device buffers it wants
+        filled (smx_recon_update_visualization_buffers): vertex_buffer 16 B per slot (Point3fC3u8), neighbor_index_buffer
+        32 B, normal_vertex_buffer 24 B; see _slots_of for what a buffer may be.  With none given it does nothing."""
+        if vertex_buffer is None and neighbor_index_buffer is None and normal_vertex_buffer is None:
+            return
+        vp, vc = _slots_of(vertex_buffer, 16)
+        ip, ic = _slots_of(neighbor_index_buffer, 32)
+        npt, nc = _slots_of(normal_vertex_buffer, 24)
+        flags = vis_flags(visualize_last_update_timestamp, visualize_creation_timestamp, visualize_radii,
+                          visualize_normals)
+        _lib.check(_lib.load().smx_recon_update_visualization_buffers(
+            self._h, _sv(stream), C.c_uint32(int(frame_index) & 0xFFFFFFFF),
+            C.c_uint32(int(latest_triangulated_frame_index) & 0xFFFFFFFF),
+            C.c_uint32(int(latest_mesh_surfel_count) & 0xFFFFFFFF), C.c_int32(surfel_integration_active_window_size),
+            C.c_int32(flags), vp, C.c_uint32(vc), ip, C.c_uint32(ic), npt, C.c_uint32(nc)))
+
+    def Render(self, stream, params, depth=None, index=None, normal=None, color=None):
+        """Not in the reference: splat rendering of the map (smx_recon_render) into height x width device images --
+        depth float, index uint32, normal float4, color uchar4 (CUDABuffer or BufferDesc; None = not wanted).
+        params: an smx_render_params (make_render_params).  Enqueued on `stream`, no host synchronisation."""
+        def opt(b):
+            return _d(b) if b is not None else None
+        _lib.check(_lib.load().smx_recon_render(self._h, _sv(stream), C.byref(params) if params is not None else None,
+                                                opt(depth), opt(index), opt(normal), opt(color)))
 
     def ExportVertices(self, stream, position_buffer, color_buffer):
         _lib.check(_lib.load().smx_recon_export_vertices(self._h, _sv(stream), _d(position_buffer), _d(color_buffer)))

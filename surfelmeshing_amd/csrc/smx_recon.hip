@@ -25,6 +25,7 @@
 // The surfel count, merge count and all list lengths live in device memory;
 // no kernel launch needs a host round trip.
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 
@@ -3266,6 +3267,177 @@ k_export(Surfels S, float* __restrict__ pos, uint8_t* __restrict__ col, const De
   }
 }
 
+// ---- viewer buffers (UpdateVisualizationBuffers) and headless rendering (smx_recon_render) ----
+struct VisColor { uint32_t frame; int window; int flags; };
+
+// float -> u8 for the colour conversions below: the reference converts values in [0, 256) (truncation); outside that
+// range its conversion is undefined, here it saturates (NaN -> 0)
+__device__ __forceinline__ uint32_t vis_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f); }
+__device__ __forceinline__ uint32_t vis_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
+
+// The colour word of UpdateSurfelVertexBufferCUDAKernel (kernels.cu:306-349) for one slot, flags in the reference
+// template's precedence (smx.h SMX_VIS_*).  Shared by the vertex buffer and the render's colour image.
+__device__ __forceinline__ uint32_t vis_color(const Surfels& S, uint32_t i, const VisColor& vc) {
+  if (vc.flags & (SMX_VIS_LAST_UPDATE | SMX_VIS_CREATION)) {
+    const bool creation = (vc.flags & SMX_VIS_CREATION) != 0;
+    const int age = (int)(vc.frame - (creation ? S.u(kCreationStamp, i) : S.u(kLastUpdateStamp, i)));
+    const int max_age = creation ? 3000 : vc.window;
+    if (age < 1) return vis_rgb(255, 80, 80);
+    if (age > max_age) return vis_rgb(40, 40, 255);
+    float blend = (float)(age - 1) * 1.0f / (float)(max_age - 1);
+    blend = fminf(1.0f, fmaxf(0.0f, blend));
+    const uint32_t intensity = (255u - vis_u8(255.99f * blend)) & 255u;
+    return vis_rgb(intensity, intensity, intensity);
+  }
+  if (vc.flags & SMX_VIS_RADII) {
+    const float radius = sqrtf(S.f(kRadiusSq, i));
+    float blend = (radius - 0.0005f) / (0.01f - 0.0005f);
+    blend = fminf(1.0f, fmaxf(0.0f, blend));
+    const uint32_t red = vis_u8(255.99f * blend);
+    return vis_rgb(red, 255u - red, 80u);
+  }
+  if (vc.flags & SMX_VIS_NORMALS) {
+    const float4 n = *S.group(kGroupN, i);
+    return vis_rgb(vis_u8(255.99f / 2.0f * (n.x + 1.0f)), vis_u8(255.99f / 2.0f * (n.y + 1.0f)),
+                   vis_u8(255.99f / 2.0f * (n.z + 1.0f)));
+  }
+  return S.u(kColor, i);
+}
+
+// The three fill kernels of UpdateVisualizationBuffers (kernels.cu:278-351, 434-449, 498-514) in one pass over the
+// slots; each buffer stops at its own capacity.  (The reference writes vertex components one float at a time; one
+// 16-byte record per slot here, 32 for the neighbour pairs.)
+__global__ void __launch_bounds__(kBlock)
+k_vis_fill(Surfels S, VisColor vc, uint32_t latest_triangulated, uint32_t latest_mesh_count,
+           float4* __restrict__ vtx, uint32_t vtx_cap, uint4* __restrict__ nbr, uint32_t nbr_cap,
+           float2* __restrict__ nvb, uint32_t nvb_cap, const DevState* st) {
+  const uint32_t N = min(st->surfel_count, max(vtx ? vtx_cap : 0u, max(nbr ? nbr_cap : 0u, nvb ? nvb_cap : 0u)));
+  const float nanv = __builtin_nanf("");
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
+    const float4 s = *S.group(kGroupS, i);
+    if (vtx && i < vtx_cap) {
+      const bool output_vertex = S.u(kCreationStamp, i) <= latest_triangulated || i >= latest_mesh_count;
+      vtx[i] = make_float4(output_vertex ? s.x : nanv, s.y, s.z, __uint_as_float(vis_color(S, i, vc)));
+    }
+    if (nbr && i < nbr_cap) {
+      const uint4 t = *reinterpret_cast<const uint4*>(S.group(kGroupT, i));
+      nbr[2 * (size_t)i + 0] = make_uint4(i, t.x == kInvalid ? i : t.x, i, t.y == kInvalid ? i : t.y);
+      nbr[2 * (size_t)i + 1] = make_uint4(i, t.z == kInvalid ? i : t.z, i, t.w == kInvalid ? i : t.w);
+    }
+    if (nvb && i < nvb_cap) {
+      const float4 n = *S.group(kGroupN, i);
+      const float radius = sqrtf(n.w);
+      nvb[3 * (size_t)i + 0] = make_float2(s.x, s.y);
+      nvb[3 * (size_t)i + 1] = make_float2(s.z, s.x + radius * n.x);
+      nvb[3 * (size_t)i + 2] = make_float2(s.y + radius * n.y, s.z + radius * n.z);
+    }
+  }
+}
+
+struct RenderCtx {
+  double L[12];   // camera_T_global (inverted on the host in double precision)
+  Mat34 Lf;       // ... rounded to float: the rotation part is exact (a transpose), used for the normal image
+  double fx, fy, cx, cy, near_z, far_z;
+  double half_extent;   // square mode
+  double disc_factor, max_extent, f_max;   // disc mode (f_max = max(fx, fy))
+  int W, H, mode;
+};
+
+// z-test: the smaller (depth bits, slot) key wins; a plain load first, so that a hidden splat costs no atomic
+__device__ __forceinline__ void render_zmin(unsigned long long* p, unsigned long long key) {
+  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+}
+
+// One thread per live slot: project, find the candidate pixel rectangle, z-test every covered pixel.  Streams the S
+// and N records (32 B per slot).  (No segment culling: the segment boxes bound the raw positions, not the smooth ones.)
+// The geometry is evaluated in double precision: neighbouring discs of one surface meet a pixel's ray at depths only
+// 1e-6 apart, and a float evaluation would order them by its rounding errors; the key then holds the depth as a float.
+__global__ void __launch_bounds__(kBlock)
+k_render_splat(Surfels S, RenderCtx rc, unsigned long long* __restrict__ zbuf, const DevState* st) {
+  const uint32_t N = st->surfel_count;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
+    const float4 nr = *S.group(kGroupN, i);
+    if (!(nr.w >= 0.0f)) continue;                       // merged
+    const float4 sp = *S.group(kGroupS, i);
+    const double* L = rc.L;
+    const double px = sp.x, py = sp.y, pz = sp.z;
+    const double cz = L[8] * px + L[9] * py + L[10] * pz + L[11];
+    if (!(cz > rc.near_z && cz < rc.far_z)) continue;
+    const double cx = L[0] * px + L[1] * py + L[2] * pz + L[3], cy = L[4] * px + L[5] * py + L[6] * pz + L[7];
+    const double u = rc.fx * cx / cz + rc.cx, v = rc.fy * cy / cz + rc.cy;
+    if (!(fabs(u) < 1e8 && fabs(v) < 1e8)) continue;   // (far outside any image; keeps the conversions below defined)
+    double e = rc.half_extent, rho = 0.0;
+    if (rc.mode == SMX_SPLAT_DISC) {
+      rho = rc.disc_factor * sqrt((double)nr.w);
+      const double dz = cz - rho;
+      e = dz <= rc.near_z ? rc.max_extent : fmin(rc.max_extent, 2.0 * rc.f_max * rho / dz);
+    }
+    // pixels whose centre x + 1/2 lies within e of u: u - e - 1/2 <= x <= u + e - 1/2 (square mode, h = 0: floor(u))
+    const bool point = rc.mode == SMX_SPLAT_SQUARE && e == 0.0;
+    const double x0f = point ? floor(u) : ceil(u - e - 0.5), x1f = point ? floor(u) : floor(u + e - 0.5);
+    const double y0f = point ? floor(v) : ceil(v - e - 0.5), y1f = point ? floor(v) : floor(v + e - 0.5);
+    const int x0 = (int)fmax(x0f, 0.0), x1 = (int)fmin(x1f, (double)(rc.W - 1));
+    const int y0 = (int)fmax(y0f, 0.0), y1 = (int)fmin(y1f, (double)(rc.H - 1));
+    if (rc.mode == SMX_SPLAT_SQUARE) {
+      const unsigned long long key = ((unsigned long long)__float_as_uint((float)cz) << 32) | i;
+      for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) render_zmin(&zbuf[(size_t)y * rc.W + x], key);
+    } else {
+      const double nx = L[0] * nr.x + L[1] * nr.y + L[2] * nr.z, ny = L[4] * nr.x + L[5] * nr.y + L[6] * nr.z;
+      const double nz = L[8] * nr.x + L[9] * nr.y + L[10] * nr.z;
+      const double n_dot_c = nx * cx + ny * cy + nz * cz;
+      const double rho2 = rho * rho;
+      for (int y = y0; y <= y1; ++y) {
+        const double dy = ((double)y + 0.5 - rc.cy) / rc.fy;
+        for (int x = x0; x <= x1; ++x) {
+          const double dx = ((double)x + 0.5 - rc.cx) / rc.fx;
+          const double n_dot_d = nx * dx + ny * dy + nz;
+          if (fabs(n_dot_d) < 1e-4) continue;
+          const double t = n_dot_c / n_dot_d;
+          if (!(t > rc.near_z)) continue;
+          const double ex = t * dx - cx, ey = t * dy - cy, ez = t - cz;
+          if (ex * ex + ey * ey + ez * ez <= rho2)
+            render_zmin(&zbuf[(size_t)y * rc.W + x], ((unsigned long long)__float_as_uint((float)t) << 32) | i);
+        }
+      }
+    }
+  }
+}
+
+// One thread per pixel: decode the key, gather only the winner's records.
+__global__ void __launch_bounds__(kBlock)
+k_render_resolve(Surfels S, RenderCtx rc, VisColor vc, const unsigned long long* __restrict__ zbuf,
+                 Img<float> depth, Img<uint32_t> index, Img<float4> normal, Img<uint32_t> color) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= rc.W || y >= rc.H) return;
+  const unsigned long long key = zbuf[(size_t)y * rc.W + x];
+  const bool empty = key == ~0ull;
+  const uint32_t slot = empty ? kInvalid : (uint32_t)key;
+  if (depth.address) depth(y, x) = empty ? 0.0f : __uint_as_float((uint32_t)(key >> 32));
+  if (index.address) index(y, x) = slot;
+  if (normal.address) {
+    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!empty) {
+      const float4 nr = *S.group(kGroupN, slot);
+      const Vec3 n = rotate(rc.Lf, Vec3{nr.x, nr.y, nr.z});
+      o = make_float4(n.x, n.y, n.z, 0.0f);
+    }
+    normal(y, x) = o;
+  }
+  if (color.address) color(y, x) = empty ? 0u : ((vis_color(S, slot, vc) & 0x00FFFFFFu) | 0xFF000000u);
+}
+
+bool render_desc_ok(const smx_buffer_desc* d, const smx_render_params* p, size_t elem) {
+  return !d || (d->address && d->width == p->width && d->height == p->height && d->pitch >= (size_t)p->width * elem &&
+                d->pitch % elem == 0 && (uintptr_t)d->address % elem == 0);
+}
+template <typename T>
+Img<T> render_img(const smx_buffer_desc* d) {
+  if (d) return as_img<T>(d);
+  Img<T> i; i.address = nullptr; i.height = 0; i.width = 0; i.pitch = 0;
+  return i;
+}
+
 // Candidate lists for the mesher: the rows the neighbour index is built from (smooth position,
 // NaN for merged slots so that the index leaves them out) and the per-query (position, radius^2) of a list of slots.
 __global__ void __launch_bounds__(kBlock)
@@ -3492,6 +3664,10 @@ struct smx_recon_s {
   uint32_t* cmp_map;        // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
   uint32_t* cmp_seg;        // offsets [nseg], and [0] = new count, [1] = links dropped
   uint32_t* cmp_out;
+  unsigned long long* zbuf; // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
+  size_t zbuf_px;           // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
+  hipEvent_t ev_render;
+  bool render_busy;
 };
 
 // kernel slots of one Integrate call (launch order)
@@ -3777,6 +3953,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_upd, evf), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_reg, evf), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_staging, hipEventDisableTiming), "hipEventCreateWithFlags"));
+  SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_render, hipEventDisableTiming), "hipEventCreateWithFlags"));
   r->overlap_enabled = 1;
   r->prof_slot = -1;
   r->timing_enabled = 4;   // (GetTimings is served by the stage stamps: on from the first call, like the reference's events)
@@ -3801,7 +3978,7 @@ int smx_recon_destroy(smx_recon r) {
                   r->vis_count_set[0], r->vis_count_set[1], r->L.seg_act, r->L.seg_streak, r->sw.surv_list, r->sw.copy_list, r->sw.count, r->blended_depth, r->cand_q, r->cand_slots, r->cand_state, r->L.dirty8, r->delta_seg, r->delta_total, r->staging, r->S.base, r->grad_acc, r->reg_rec, r->fb.rec, r->fb.count, r->L.vis_list, r->L.recent_list, r->L.vis_seg, r->L.seg_box, r->L.recent_seg, r->L.vis_chunks.desc, r->L.rec_chunks.desc, r->L.acc_chunks.desc, r->L.rec_chunks.count, r->flags_buf[0], r->flags_buf[1], r->L.hot_epoch, r->L.seg_targets,
                   r->merge_flag, r->L.act_list, r->bb.distance_map, r->bb.new_distance_map,
                   r->bb.deltas, r->bb.new_deltas, r->new_flags, r->new_ranks, r->tmp_u32, r->block_sums, r->block_offsets, r->st,
-                  r->cmp_map, r->cmp_seg, r->cmp_out};
+                  r->cmp_map, r->cmp_seg, r->cmp_out, r->zbuf};
   if (r->reg_stream) { (void)hipStreamSynchronize(r->reg_stream); (void)hipStreamDestroy(r->reg_stream); }
   if (r->dir_host) { (void)hipDeviceSynchronize(); (void)hipHostFree(r->dir_host); }
   if (r->ts_host) (void)hipHostFree(r->ts_host);
@@ -3811,6 +3988,7 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_upd) (void)hipEventDestroy(r->ev_upd);
   if (r->ev_reg) (void)hipEventDestroy(r->ev_reg);
   if (r->ev_staging) (void)hipEventDestroy(r->ev_staging);
+  if (r->ev_render) (void)hipEventDestroy(r->ev_render);
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
@@ -4392,6 +4570,84 @@ int smx_recon_export_vertices(smx_recon r, smx_stream s, const smx_buffer_desc* 
   hipLaunchKernelGGL(k_export, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S,
                      (float*)position_buffer->address, (uint8_t*)color_buffer->address, r->st);
   SMX_LAUNCH_CHECK();
+  return SMX_OK;
+}
+
+int smx_recon_update_visualization_buffers(smx_recon r, smx_stream s, uint32_t frame_index,
+    uint32_t latest_triangulated_frame_index, uint32_t latest_mesh_surfel_count,
+    int32_t surfel_integration_active_window_size, int32_t flags,
+    float* vertex_buffer, uint32_t vertex_capacity,
+    uint32_t* neighbor_index_buffer, uint32_t neighbor_capacity,
+    float* normal_vertex_buffer, uint32_t normal_capacity) {
+  SMX_CHECK_ARG(r != nullptr && (flags & ~15) == 0);
+  // (one 16-byte record per slot for the vertex and neighbour buffers, 8-byte stores for the normal vertices)
+  SMX_CHECK_ARG(((uintptr_t)vertex_buffer & 15u) == 0 && ((uintptr_t)neighbor_index_buffer & 15u) == 0 &&
+                ((uintptr_t)normal_vertex_buffer & 7u) == 0);
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  const uint32_t vc_ = vertex_buffer ? vertex_capacity : 0u, nc_ = neighbor_index_buffer ? neighbor_capacity : 0u;
+  const uint32_t nvc_ = normal_vertex_buffer ? normal_capacity : 0u;
+  if (vc_ == 0 && nc_ == 0 && nvc_ == 0) return SMX_OK;
+  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  VisColor vc;
+  vc.frame = frame_index; vc.window = surfel_integration_active_window_size; vc.flags = flags;
+  hipLaunchKernelGGL(k_vis_fill, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, vc, latest_triangulated_frame_index,
+                     latest_mesh_surfel_count, vc_ ? reinterpret_cast<float4*>(vertex_buffer) : nullptr, vc_,
+                     nc_ ? reinterpret_cast<uint4*>(neighbor_index_buffer) : nullptr, nc_,
+                     nvc_ ? reinterpret_cast<float2*>(normal_vertex_buffer) : nullptr, nvc_, r->st);
+  SMX_LAUNCH_CHECK();
+  return SMX_OK;
+}
+
+int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, const smx_buffer_desc* depth,
+                     const smx_buffer_desc* index, const smx_buffer_desc* normal, const smx_buffer_desc* color) {
+  SMX_CHECK_ARG(r != nullptr && p != nullptr);
+  SMX_CHECK_ARG(p->width > 0 && p->height > 0 && p->width <= 16384 && p->height <= 16384);
+  SMX_CHECK_ARG(std::isfinite(p->fx) && std::isfinite(p->fy) && p->fx > 0 && p->fy > 0 && std::isfinite(p->cx) && std::isfinite(p->cy));
+  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(p->global_T_camera[k]));
+  SMX_CHECK_ARG(std::isfinite(p->near_z) && p->near_z > 0 && p->far_z > p->near_z);
+  SMX_CHECK_ARG(p->splat_mode == SMX_SPLAT_SQUARE || p->splat_mode == SMX_SPLAT_DISC);
+  // (a splat's pixel rectangle is bounded by these: at most (2 x 1024 + 1)^2 pixels for one thread)
+  SMX_CHECK_ARG(p->splat_half_extent_in_pixels >= 0 && p->splat_half_extent_in_pixels <= 1024);
+  SMX_CHECK_ARG(p->max_splat_extent_in_pixels > 0 && p->max_splat_extent_in_pixels <= 1024);
+  SMX_CHECK_ARG(std::isfinite(p->disc_radius_factor) && p->disc_radius_factor > 0);
+  SMX_CHECK_ARG((p->color_flags & ~15) == 0);
+  SMX_CHECK_ARG(render_desc_ok(depth, p, 4) && render_desc_ok(index, p, 4) && render_desc_ok(normal, p, 16) &&
+                render_desc_ok(color, p, 4));
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  const size_t px = (size_t)p->width * p->height;
+  if (r->zbuf_px < px) {
+    if (r->zbuf) { SMX_HIP(hipDeviceSynchronize()); SMX_HIP(hipFree(r->zbuf)); r->zbuf = nullptr; r->zbuf_px = 0; }
+    r->render_busy = false;
+    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->zbuf), px * sizeof(unsigned long long)));
+    r->zbuf_px = px;
+  }
+  if (r->render_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_render, 0));   // (the previous render's resolve, on any stream)
+  RenderCtx rc;
+  {
+    const float* m = p->global_T_camera;
+    for (int i = 0; i < 3; ++i) {   // R^T, -(R^T t)
+      for (int k = 0; k < 3; ++k) rc.L[4 * i + k] = m[4 * k + i];
+      rc.L[4 * i + 3] = -(rc.L[4 * i + 0] * m[3] + rc.L[4 * i + 1] * m[7] + rc.L[4 * i + 2] * m[11]);
+    }
+    rc.Lf = se3_inverse(m);
+  }
+  rc.fx = p->fx; rc.fy = p->fy; rc.cx = p->cx; rc.cy = p->cy; rc.near_z = p->near_z; rc.far_z = p->far_z;
+  rc.half_extent = p->splat_half_extent_in_pixels;
+  rc.disc_factor = p->disc_radius_factor; rc.max_extent = p->max_splat_extent_in_pixels; rc.f_max = std::max(p->fx, p->fy);  // (float fields widened to double)
+  rc.W = p->width; rc.H = p->height; rc.mode = p->splat_mode;
+  VisColor vc;
+  vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
+  SMX_HIP(hipMemsetAsync(r->zbuf, 0xFF, px * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, r->zbuf, r->st);
+  hipLaunchKernelGGL(k_render_resolve, dim3(div_up(p->width, 64), div_up(p->height, 4)), dim3(kBlock), 0, st, r->S, rc, vc,
+                     r->zbuf, render_img<float>(depth), render_img<uint32_t>(index), render_img<float4>(normal),
+                     render_img<uint32_t>(color));
+  SMX_LAUNCH_CHECK();
+  SMX_HIP(hipEventRecord(r->ev_render, st));
+  r->render_busy = true;
   return SMX_OK;
 }
 

@@ -14,6 +14,29 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import numpy as np  # noqa: E402
 
 
+def write_render(args, rec, cam, global_T_camera, frame_index, name):
+    """One headless render of the map (surfelmeshing_amd.render) as an RGB PNG."""
+    from surfelmeshing_amd import render, tum
+    fx, fy, cx, cy = cam.parameters()
+    img = render.render_view(rec, cam.width(), cam.height(), fx, fy, cx, cy, global_T_camera,
+                             splat_mode=args.render_splat, color=args.render_color, outputs=("color",),
+                             frame_index=frame_index)
+    os.makedirs(args.render_dir, exist_ok=True)
+    tum.write_png(os.path.join(args.render_dir, name), np.ascontiguousarray(img["color"][:, :, :3]))
+
+
+def overview_pose(rec):
+    """A look-at pose from above and behind the bounding box of the live surfels, towards its centre."""
+    from surfelmeshing_amd import render
+    rows = rec.debug_download_surfels()
+    live = rows[7] >= 0
+    p = rows[3:6, live].astype(np.float64)
+    lo, hi = p.min(axis=1), p.max(axis=1)
+    centre, extent = (lo + hi) / 2, float(np.linalg.norm(hi - lo))
+    eye = centre + np.array([0.0, -0.6, -1.0]) * extent     # (y points down in the camera-style world frames used here)
+    return render.look_at(eye, centre, up=(0.0, -1.0, 0.0))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset_folder")
@@ -33,6 +56,13 @@ def main():
                     help="remove the merged slots from the map before every N-th integrated frame (0 = never)")
     ap.add_argument("--compact_at_fill", type=float, default=0.0,
                     help="remove the merged slots before a frame when surfels_size() >= F * max_surfel_count (0 = never)")
+    ap.add_argument("--render_dir", help="write headless renders of the map (render_%%06d.png) into this folder")
+    ap.add_argument("--render_every", type=int, default=0,
+                    help="render the map from the pose of every N-th integrated frame (0 = never)")
+    ap.add_argument("--render_splat", choices=("square", "disc"), default="square")
+    ap.add_argument("--render_color", choices=("color", "last_update", "creation", "radii", "normals"), default="color")
+    ap.add_argument("--render_overview", action="store_true",
+                    help="at the end, render one view from outside the map's bounds looking at its centre")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
@@ -92,6 +122,8 @@ def main():
             compactions, removed = compactions + 1, removed + before - after
         pipe.process(f, others, T, G)
         done += 1
+        if args.render_dir and args.render_every > 0 and done % args.render_every == 0:
+            write_render(args, pipe.reconstruction, cam, G, f, "render_%06d.png" % f)
         old = f - half - 1                                                                      # main.cc:1226-1240
         if old in uploaded:
             pipe.release(old)
@@ -102,6 +134,8 @@ def main():
         done, dt, done / max(dt, 1e-9), rec.surfels_size(), rec.surfels_size() - rec.surfel_count()))
     if compactions:
         print("%d compactions removed %d merged slots" % (compactions, removed))
+    if args.render_dir and args.render_overview:
+        write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png")
     if args.export_mesh:
         export.SaveMeshAsOBJ(rec, args.export_mesh)
         print("Wrote %s." % args.export_mesh)
