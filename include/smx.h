@@ -135,7 +135,9 @@ int smx_buffer_clear(smx_buffer b, smx_stream s, const void* pattern);
 int smx_buffer_set_to(smx_buffer dst, smx_buffer src, smx_stream s);
 
 /* ---- depth preprocessing free functions (APP/cuda_depth_processing.cuh:43-122) ---- */
-/* BilateralFilteringAndDepthCutoffCUDA, APP/cuda_depth_processing.cu:120-158 */
+/* BilateralFilteringAndDepthCutoffCUDA, APP/cuda_depth_processing.cu:120-158.  The disc radius is
+ * (int)(radius_factor * sigma_xy + 0.5f) as there; radii 0 .. 8 are implemented, a larger one is refused with
+ * SMX_ERR_INVALID_ARGUMENT before anything is launched (the output is left as it was). */
 int smx_bilateral_filtering_and_depth_cutoff(
     smx_stream s, float sigma_xy, float sigma_value_factor, uint16_t value_to_ignore,
     float radius_factor, uint16_t max_depth, float depth_valid_region_radius,

@@ -32,7 +32,9 @@ class PreprocessParams:
     pyramid_level: int = 0                          # main.cc:299-303, 751, 941-981: work at 1 / 2^level of the input size
 
     def max_depth_u16(self):
-        return int(np.uint16(min(self.depth_scaling * self.max_depth, 65535.0)))  # main.cc:1021
+        # main.cc:1021 multiplies two floats: the float32 product, as the native driver forms it (in float64
+        # 4500 * 2.87 is 12915.000000000002, in float32 12914.9995)
+        return int(min(np.float32(self.depth_scaling) * np.float32(self.max_depth), np.float32(65535.0)))
 
 
 def others_TR_reference(global_T_reference, global_T_others, depth_scaling):
@@ -181,6 +183,16 @@ class DriverConfig(_C.Structure):
                 ("integrate", IntegrateParams)]
 
 
+def driver_config(width, height, fx, fy, cx, cy, max_surfel_count, pre, params):
+    """The smx_driver_config of a camera, a map capacity, a PreprocessParams and an IntegrateParams: every preprocessing
+    field is taken from the attribute of `pre` that bears its name."""
+    cfg = DriverConfig(width=width, height=height, fx=fx, fy=fy, cx=cx, cy=cy, max_surfel_count=max_surfel_count,
+                       integrate=params)
+    for name, _ in DriverConfig._fields_[7:-1]:
+        setattr(cfg, name, getattr(pre, name))
+    return cfg
+
+
 class DriverStep(_C.Structure):
     _fields_ = [("frame_index", _C.c_uint32), ("other_count", _C.c_int32), ("other_frames", _C.c_uint32 * 8),
                 ("others_TR_reference", (_C.c_float * 12) * 8), ("global_T_frame", _C.c_float * 12)]
@@ -222,12 +234,7 @@ class NativeFramePipeline:
         self.params = params or IntegrateParams.defaults()
         self.stream = stream
         p = self.pre
-        cfg = DriverConfig(width, height, fx, fy, cx, cy, max_surfel_count, p.depth_scaling, p.max_depth,
-                           p.depth_valid_region_radius, p.observation_angle_threshold_deg, p.depth_erosion_radius,
-                           p.outlier_filtering_required_inliers, p.bilateral_filter_sigma_xy,
-                           p.bilateral_filter_radius_factor, p.bilateral_filter_sigma_depth_factor,
-                           p.outlier_filtering_depth_tolerance_factor, p.point_radius_extension_factor,
-                           p.point_radius_clamp_factor, self.params)
+        cfg = driver_config(width, height, fx, fy, cx, cy, max_surfel_count, p, self.params)
         self._d = _C.c_void_p()
         _smxlib.check(L.smx_driver_create(_C.byref(cfg), _C.byref(self._d)))
         rh = _C.c_void_p()

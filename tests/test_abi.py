@@ -98,3 +98,36 @@ def test_library_leaves_the_environment_alone_and_reports_what_it_wants():
     code = "import os; from surfelmeshing_amd import _lib; print(os.environ.get('GPU_MAX_HW_QUEUES'))"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=os.path.dirname(os.path.dirname(_lib.SO_PATH)))
     assert r.returncode == 0 and r.stdout.strip() == "8", (r.stdout, r.stderr[-500:])
+
+
+def test_driver_config_fields_mirror_the_header():
+    """DriverConfig (pipeline.py) is smx_driver_config (smx_driver.h) mirrored by hand: same field names, order and
+    types; and pipeline.driver_config(), which NativeFramePipeline calls, fills each preprocessing field from the
+    PreprocessParams attribute of the same name.  (What a wrong field does to a frame loop off its defaults is
+    tests/test_gpu_preprocess_params.py::test_native_driver_off_its_defaults.)"""
+    from surfelmeshing_amd.pipeline import DriverConfig
+    text = open(os.path.join(ROOT, "include", "smx_driver.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\}\s*smx_driver_config;", text).group(1)
+    declared = []
+    for ctype, names in re.findall(r"(\w+)\s+([\w\s,]+);", body):
+        declared += [(n.strip(), ctype) for n in names.split(",")]
+    ctypes_of = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
+    mirrored = [(n, t) for n, t in DriverConfig._fields_]
+    assert [n for n, _ in mirrored] == [n for n, _ in declared]
+    for (n, t), (_, c) in zip(mirrored[:-1], declared[:-1]):
+        assert t is ctypes_of[c], (n, t, c)
+    assert declared[-1] == ("integrate", "smx_integrate_params")
+    # every field arrives under its own name (a parameter set whose values are all different)
+    import dataclasses
+    import numpy as np
+    from surfelmeshing_amd._lib import IntegrateParams
+    from surfelmeshing_amd.pipeline import PreprocessParams, driver_config
+    values = {f.name: (3 + k if f.type in (int, "int") else 1.5 + 0.25 * k) for k, f in enumerate(dataclasses.fields(PreprocessParams))}
+    cfg = driver_config(160, 120, 131.25, 132.5, 80.0, 60.5, 60000, PreprocessParams(**values), IntegrateParams.defaults())
+    assert (cfg.width, cfg.height, cfg.fx, cfg.fy, cfg.cx, cfg.cy, cfg.max_surfel_count) == (160, 120, 131.25, 132.5, 80.0, 60.5, 60000)
+    carried = [n for n, _ in mirrored[7:-1]]
+    assert len(carried) == 12 and len({values[n] for n in carried}) == 12
+    for n in carried:
+        assert getattr(cfg, n) == values[n], n
+    assert bytes(cfg.integrate) == bytes(IntegrateParams.defaults())

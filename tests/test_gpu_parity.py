@@ -646,6 +646,9 @@ def test_changed_surfel_delta_reproduces_full_transfers(smx):
             for name in names:
                 a, b = getattr(mirror, name)[:n], getattr(ref, name)[:n]
                 assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (f, name)
+            oracle_all = po.recon.transfer_all()                # ... and what the ORACLE transfers, not only the HIP path's own
+            for short, _, name in smx.CUDASurfelDeltaCPU.ROWS:
+                assert np.array_equal(getattr(mirror, name)[:n].view(np.uint32), oracle_all[short].view(np.uint32)), (f, name)
     # the first delta carries everything, later ones only what moved
     assert sizes[0][0] == sizes[0][1] and all(c < 0.8 * n_ for c, n_ in sizes[3:]), sizes
     assert rec.TransferChangedToCPU(None, frames[-1]).count == 0   # nothing changed since
@@ -662,6 +665,10 @@ def test_changed_surfel_delta_reproduces_full_transfers(smx):
     for name in names:
         assert np.array_equal(getattr(mirror, name)[:ref.surfel_count].view(np.uint32),
                               getattr(ref, name)[:ref.surfel_count].view(np.uint32)), name
+    oracle_all = po.recon.transfer_all()
+    assert oracle_all["surfel_count"] == ref.surfel_count
+    for short, _, name in smx.CUDASurfelDeltaCPU.ROWS:
+        assert np.array_equal(getattr(mirror, name)[:ref.surfel_count].view(np.uint32), oracle_all[short].view(np.uint32)), name
     rec.SetDeltaTracking(None, False)
 
 
