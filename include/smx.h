@@ -620,6 +620,81 @@ typedef struct {
 int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, const smx_buffer_desc* depth,
                      const smx_buffer_desc* index, const smx_buffer_desc* normal, const smx_buffer_desc* color);
 
+/* ---- camera tracking against the map: frame-to-model point-to-plane ICP (not in the reference, which is fed by an
+ * external SLAM system) ----
+ * Inputs: the preprocessed depth and normal images of a frame exactly as smx_recon_integrate takes them, and a predicted
+ * pose global_T_pred.  The call renders the map once at the prediction with the object's own size and intrinsics (disc
+ * splats, by the kernels of smx_recon_render): model depth D (0 = empty) and model normal M in the prediction's camera
+ * frame; model vertex of pixel (x, y): q = D ((x + 1/2 - cx) / fx, (y + 1/2 - cy) / fy, 1).  State: T_rel (model camera
+ * <- frame camera), the identity at the start; answer global_T_frame = global_T_pred T_rel.
+ * One iteration at pixel stride s visits the frame pixels (x, y) = (s/2 + i s, s/2 + j s): vertex v = z ((x + 1/2 - cx) /
+ * fx, (y + 1/2 - cy) / fy, 1), z = depth / depth_scaling (skipped if depth == 0), normal n = (nx, ny, -sqrt(max(0, 1 -
+ * nx^2 - ny^2))); p = R_rel v + t_rel, m = R_rel n; skipped unless p.z > 0 and (u, w) = (floor(fx p.x / p.z + cx),
+ * floor(fy p.y / p.z + cy)) lies in the image and D(w, u) > 0 (the pixel is then "associated"); gates |p - q|^2 <=
+ * max_distance^2 and m . M >= cos(max_normal_angle); residual r = M . (p - q), Jacobian row J = (p x M, M) -- rotation
+ * first, then translation: the update is a twist applied on the left, in the model camera's frame.  The per-pixel terms
+ * are single precision, their sums double precision in a fixed order (per-workgroup partial sums, added in index
+ * order): two calls give the same bits.  x = -(J^T J)^-1 J^T r by an LDL^T factorisation, T_rel <- exp(x) T_rel', both
+ * in double precision on the device; T_rel is kept in double and handed to an iteration as 12 floats, T_rel' (the pose the
+ * iteration linearised at, which the twist corrects).  Levels run in the order given (coarse to fine); strides sample, no pyramid is built.
+ * Status, decided on the device per iteration, in this order:
+ *   NOT_FINITE       a sum or the solution is not finite;
+ *   DEGENERATE       pixels with depth but none associated (an empty render), or a pivot of the factorisation below
+ *                    min_pivot_ratio x the largest diagonal entry (one plane);
+ *   TOO_FEW_INLIERS  inliers < min_inliers in any iteration (nothing is solved below that floor), or -- judged on the
+ *                    LAST iteration run only -- inliers < min_inlier_fraction x pixels with depth;
+ *   CONVERGED        |rotation part of x| < convergence_rotation and |translation part| < convergence_translation: the
+ *                    remaining iterations of that level are skipped, the next level still runs;
+ *   OK               otherwise.
+ * A bad status (>= SMX_TRACK_TOO_FEW_INLIERS) is sticky: T_rel keeps the value it had before the failing iteration's
+ * update and the later kernels of the call return at once.  The host looks at nothing until the end: every iteration
+ * of every level is enqueued back to back on s (the render, one state-reset launch, then a reduce and a solve launch per
+ * iteration).  The call is ordered like smx_recon_render and changes no map state, delta mark, statistic or stamp.
+ * result is a device pointer if result_on_device (the call stays asynchronous), else a host pointer (the call returns
+ * with it filled).  model_depth_out / model_normal_out (may be NULL; the object's width x height, float / float4)
+ * receive the model images the call used: bit for bit what smx_recon_render gives for the same parameters.
+ * SMX_ERR_INVALID_ARGUMENT (nothing launched): wrong image sizes or element sizes, a stride outside {1, 2, 4, 8}, no
+ * level with iterations, more than 32 iterations in a level, non-positive gates, near_z >= far_z.  An empty map is no
+ * error (DEGENERATE). */
+enum { SMX_TRACK_OK = 0, SMX_TRACK_CONVERGED = 1, SMX_TRACK_TOO_FEW_INLIERS = 2,
+       SMX_TRACK_DEGENERATE = 3, SMX_TRACK_NOT_FINITE = 4 };
+typedef struct {            /* smx_track_params_default() fills the defaults */
+  int32_t level_stride[3];  int32_t level_iterations[3];   /* stride in {1,2,4,8}; 0 iterations = level unused */
+  float max_distance;  float max_normal_angle_deg;
+  float convergence_rotation;  float convergence_translation;
+  int32_t min_inliers;  float min_inlier_fraction;  float min_pivot_ratio;
+  float near_z, far_z, disc_radius_factor, max_splat_extent_in_pixels;
+} smx_track_params;
+typedef struct {
+  float global_T_frame[12];          /* the prediction itself if nothing could be solved */
+  int32_t status;  int32_t iterations_run;
+  uint32_t inliers;  uint32_t pixels_with_depth;          /* of the last iteration run */
+  float rms_residual;                                      /* metres, point-to-plane, last iteration */
+  float last_update_rotation, last_update_translation;
+  float information[36];                                   /* JtJ of the last iteration, row-major 6x6 */
+} smx_track_result;
+/* Defaults: levels (4, 4), (2, 5), (1, 10); gates 10 cm / 30 degrees; convergence 1e-5 rad / 1e-5 m; min_inliers 50,
+ * min_inlier_fraction 0.1, min_pivot_ratio 1e-6; near_z 0.05, far_z 20, disc_radius_factor 1, splats of <= 16 pixels. */
+int smx_track_params_default(smx_track_params* out);
+int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling,
+                    const smx_buffer_desc* depth /*u16*/, const smx_buffer_desc* normals /*float2*/,
+                    const float global_T_pred[12], const smx_track_params* params,
+                    smx_track_result* result, int32_t result_on_device,
+                    const smx_buffer_desc* model_depth_out /*float, may be NULL*/,
+                    const smx_buffer_desc* model_normal_out /*float4, may be NULL*/);
+/* Tests and tuning: one record per iteration of the last smx_recon_track call that produced sums (the iteration that
+ * raised a bad status included).  sums: [0..20] the upper triangle of JtJ row by row, [21..26] Jtr, [27] sum r^2,
+ * [28] inliers, [29] frame pixels with a depth at this stride, [30] of which associated with a model pixel.  x is zero
+ * where nothing was solved.  Synchronises s; *count = records of the call (at most `capacity` are written). */
+#define SMX_TRACK_SUMS 31
+typedef struct {
+  int32_t level, stride, status, reserved;   /* status after the iteration */
+  double sums[SMX_TRACK_SUMS];
+  double x[6];
+} smx_track_iteration;
+int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
+                                     int32_t* count);
+
 /* ---- candidate lists for the mesher, straight from the device-resident map ----
  * Replaces, for the surfels of one batch (e.g. one changed-surfel delta), the per-surfel octree query at the top of
  * SurfelMeshing::TriangulateSurfel (APP/surfel_meshing.cc:417-425) with the widest radius that function can ask for,

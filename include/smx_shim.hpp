@@ -583,6 +583,16 @@ class CUDASurfelReconstruction {
                                     index ? index->ToCUDA().desc() : nullptr, normal ? normal->ToCUDA().desc() : nullptr,
                                     color ? color->ToCUDA().desc() : nullptr));
   }
+  // Not in the reference: frame-to-model ICP of a preprocessed frame against the map rendered at the predicted pose
+  // (smx_recon_track; `pred` = 12 row-major floats of global_T_frame as predicted).  Synchronous: *result is filled on
+  // return; result->status >= SMX_TRACK_TOO_FEW_INLIERS means that the caller keeps its prediction.
+  void Track(cudaStream_t stream, float depth_scaling, const CUDABuffer<u16>& depth, const CUDABuffer<float2_>& normals,
+             const float* pred, const smx_track_params& params, smx_track_result* result,
+             CUDABuffer<float>* model_depth = nullptr, CUDABuffer<RenderNormal>* model_normal = nullptr) {
+    SMX_SHIM_CHECK(smx_recon_track(handle_, stream, depth_scaling, depth.ToCUDA().desc(), normals.ToCUDA().desc(), pred,
+                                   &params, result, 0, model_depth ? model_depth->ToCUDA().desc() : nullptr,
+                                   model_normal ? model_normal->ToCUDA().desc() : nullptr));
+  }
   void ExportVertices(cudaStream_t stream, CUDABuffer<float>* position_buffer, CUDABuffer<u8>* color_buffer) {
     SMX_SHIM_CHECK(smx_recon_export_vertices(handle_, stream, position_buffer->ToCUDA().desc(), color_buffer->ToCUDA().desc()));
   }

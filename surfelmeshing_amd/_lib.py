@@ -62,6 +62,48 @@ class RenderParams(C.Structure):
                 ("surfel_integration_active_window_size", C.c_int32)]
 
 
+class TrackParams(C.Structure):
+    """smx_track_params: schedule, gates, status thresholds and model-render settings of smx_recon_track."""
+    _fields_ = [("level_stride", C.c_int32 * 3), ("level_iterations", C.c_int32 * 3),
+                ("max_distance", C.c_float), ("max_normal_angle_deg", C.c_float),
+                ("convergence_rotation", C.c_float), ("convergence_translation", C.c_float),
+                ("min_inliers", C.c_int32), ("min_inlier_fraction", C.c_float), ("min_pivot_ratio", C.c_float),
+                ("near_z", C.c_float), ("far_z", C.c_float), ("disc_radius_factor", C.c_float),
+                ("max_splat_extent_in_pixels", C.c_float)]
+
+    @classmethod
+    def defaults(cls, levels=None, **kw):
+        """smx_track_params_default(), then `levels` (up to three (stride, iterations) pairs, coarse to fine) and
+        any field by name."""
+        p = cls()
+        check(load().smx_track_params_default(C.byref(p)))
+        if levels is not None:
+            levels = list(levels)
+            if not 1 <= len(levels) <= 3:
+                raise ValueError("one to three (stride, iterations) levels")
+            for k in range(3):
+                p.level_stride[k], p.level_iterations[k] = levels[k] if k < len(levels) else (1, 0)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+class TrackResult(C.Structure):
+    """smx_track_result"""
+    _fields_ = [("global_T_frame", C.c_float * 12), ("status", C.c_int32), ("iterations_run", C.c_int32),
+                ("inliers", C.c_uint32), ("pixels_with_depth", C.c_uint32), ("rms_residual", C.c_float),
+                ("last_update_rotation", C.c_float), ("last_update_translation", C.c_float),
+                ("information", C.c_float * 36)]
+
+
+TRACK_SUMS = 31   # SMX_TRACK_SUMS
+
+
+class TrackIteration(C.Structure):
+    """smx_track_iteration"""
+    _fields_ = [("level", C.c_int32), ("stride", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+                ("sums", C.c_double * TRACK_SUMS), ("x", C.c_double * 6)]
+
 
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
@@ -110,7 +152,7 @@ EXPORTS = [
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",
-    "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
+    "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_track_params_default", "smx_recon_track", "smx_recon_debug_track_iterations", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
     "smx_recon_set_scan_mode", "smx_recon_debug_set_skip", "smx_recon_set_overlap", "smx_recon_integrate_hooks", "smx_recon_integrate_inputs_ready",
     "smx_nn_create", "smx_nn_destroy", "smx_nn_build", "smx_nn_query_batch", "smx_nn_query_self", "smx_nn_set_query_mode", "smx_nn_set_stats_enabled", "smx_nn_get_stats",
     "smx_synth_render_room",

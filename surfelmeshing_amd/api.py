@@ -22,7 +22,8 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats  # noqa: F401
+from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
+                   TrackIteration, TrackParams, TrackResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
@@ -30,6 +31,31 @@ kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:7
 # smx.h: colour modes of the viewer buffers and the render, splat shapes of the render
 SMX_VIS_LAST_UPDATE, SMX_VIS_CREATION, SMX_VIS_RADII, SMX_VIS_NORMALS = 1, 2, 4, 8
 SMX_SPLAT_SQUARE, SMX_SPLAT_DISC = 0, 1
+# smx.h: outcome of smx_recon_track (>= SMX_TRACK_TOO_FEW_INLIERS: nothing usable was solved)
+SMX_TRACK_OK, SMX_TRACK_CONVERGED, SMX_TRACK_TOO_FEW_INLIERS, SMX_TRACK_DEGENERATE, SMX_TRACK_NOT_FINITE = range(5)
+TRACK_STATUS_NAMES = ("OK", "CONVERGED", "TOO_FEW_INLIERS", "DEGENERATE", "NOT_FINITE")
+
+
+class TrackOutcome:
+    """What CUDASurfelReconstruction.Track returns: global_T_frame (3 x 4 float32), status (SMX_TRACK_*), ok,
+    iterations_run, inliers, pixels_with_depth, rms_residual (metres), last_update_rotation / _translation,
+    information (6 x 6, JtJ of the last iteration: rotation first)."""
+
+    def __init__(self, res):
+        self.global_T_frame = np.array(res.global_T_frame, np.float32).reshape(3, 4)
+        self.status = int(res.status)
+        self.ok = self.status < SMX_TRACK_TOO_FEW_INLIERS
+        self.status_name = TRACK_STATUS_NAMES[self.status] if 0 <= self.status < 5 else "?"
+        self.iterations_run = int(res.iterations_run)
+        self.inliers, self.pixels_with_depth = int(res.inliers), int(res.pixels_with_depth)
+        self.rms_residual = float(res.rms_residual)
+        self.last_update_rotation = float(res.last_update_rotation)
+        self.last_update_translation = float(res.last_update_translation)
+        self.information = np.array(res.information, np.float32).reshape(6, 6)
+
+    def __repr__(self):
+        return "TrackOutcome(%s, %d iterations, %d / %d inliers, rms %.4g m)" % (
+            self.status_name, self.iterations_run, self.inliers, self.pixels_with_depth, self.rms_residual)
 
 
 def vis_flags(visualize_last_update_timestamp=False, visualize_creation_timestamp=False, visualize_radii=False,
@@ -601,6 +627,43 @@ class CUDASurfelReconstruction:
             return _d(b) if b is not None else None
         _lib.check(_lib.load().smx_recon_render(self._h, _sv(stream), C.byref(params) if params is not None else None,
                                                 opt(depth), opt(index), opt(normal), opt(color)))
+
+    def Track(self, stream, depth_scaling, depth_buffer, normals_buffer, global_T_pred, params=None, model_depth=None,
+              model_normal=None):
+        """Not in the reference: frame-to-model ICP of a preprocessed frame (depth u16, normals float2, as Integrate
+        takes them) against the map rendered at the predicted pose (smx_recon_track).  params: a TrackParams
+        (TrackParams.defaults()).  model_depth / model_normal (float / float4 CUDABuffer, optional) receive the model
+        images.  Synchronous; returns a TrackOutcome.  Changes no map state."""
+        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
+        p = params if params is not None else TrackParams.defaults()
+        res = TrackResult()
+        _lib.check(_lib.load().smx_recon_track(
+            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer),
+            T.ctypes.data_as(C.c_void_p), C.byref(p), C.byref(res), C.c_int32(0),
+            _d(model_depth) if model_depth is not None else None,
+            _d(model_normal) if model_normal is not None else None))
+        return TrackOutcome(res)
+
+    def TrackAsync(self, stream, depth_scaling, depth_buffer, normals_buffer, global_T_pred, params, result_buffer,
+                   model_depth=None, model_normal=None):
+        """The same call with the smx_track_result left in device memory (result_buffer: a CUDABuffer of at least
+        ctypes.sizeof(TrackResult) bytes in one row, or a device pointer): nothing waits for the host."""
+        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
+        ptr = result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer)
+        _lib.check(_lib.load().smx_recon_track(
+            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer),
+            T.ctypes.data_as(C.c_void_p), C.byref(params), C.c_void_p(ptr), C.c_int32(1),
+            _d(model_depth) if model_depth is not None else None,
+            _d(model_normal) if model_normal is not None else None))
+
+    def debug_track_iterations(self, stream=None):
+        """One dict per iteration of the last Track call (smx_recon_debug_track_iterations): level, stride, status,
+        sums (31 float64: JtJ upper triangle, Jtr, sum r^2, inliers, pixels with depth, associated), x (6)."""
+        recs = (TrackIteration * 96)()
+        n = C.c_int32(0)
+        _lib.check(_lib.load().smx_recon_debug_track_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
+        return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
+                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
 
     def ExportVertices(self, stream, position_buffer, color_buffer):
         _lib.check(_lib.load().smx_recon_export_vertices(self._h, _sv(stream), _d(position_buffer), _d(color_buffer)))

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "smx_common.hpp"
+#include "smx_track.hpp"
 #include <hip/hip_ext.h>
 
 using namespace smx;
@@ -3668,6 +3669,12 @@ struct smx_recon_s {
   size_t zbuf_px;           // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
   hipEvent_t ev_render;
   bool render_busy;
+  float* trk_depth;         // smx_recon_track (allocated by its first call): the model images [H][W] of the last call,
+  float4* trk_normal;       // the reduce kernel's per-workgroup partial sums, the call's device state, and the mark
+  double* trk_slabs;        // after the last call's kernels (the next call, on whatever stream, waits for it)
+  TrackDev* trk_state;
+  hipEvent_t ev_track;
+  bool track_busy;
 };
 
 // kernel slots of one Integrate call (launch order)
@@ -3954,6 +3961,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_reg, evf), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_staging, hipEventDisableTiming), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_render, hipEventDisableTiming), "hipEventCreateWithFlags"));
+  SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_track, hipEventDisableTiming), "hipEventCreateWithFlags"));
   r->overlap_enabled = 1;
   r->prof_slot = -1;
   r->timing_enabled = 4;   // (GetTimings is served by the stage stamps: on from the first call, like the reference's events)
@@ -3978,7 +3986,8 @@ int smx_recon_destroy(smx_recon r) {
                   r->vis_count_set[0], r->vis_count_set[1], r->L.seg_act, r->L.seg_streak, r->sw.surv_list, r->sw.copy_list, r->sw.count, r->blended_depth, r->cand_q, r->cand_slots, r->cand_state, r->L.dirty8, r->delta_seg, r->delta_total, r->staging, r->S.base, r->grad_acc, r->reg_rec, r->fb.rec, r->fb.count, r->L.vis_list, r->L.recent_list, r->L.vis_seg, r->L.seg_box, r->L.recent_seg, r->L.vis_chunks.desc, r->L.rec_chunks.desc, r->L.acc_chunks.desc, r->L.rec_chunks.count, r->flags_buf[0], r->flags_buf[1], r->L.hot_epoch, r->L.seg_targets,
                   r->merge_flag, r->L.act_list, r->bb.distance_map, r->bb.new_distance_map,
                   r->bb.deltas, r->bb.new_deltas, r->new_flags, r->new_ranks, r->tmp_u32, r->block_sums, r->block_offsets, r->st,
-                  r->cmp_map, r->cmp_seg, r->cmp_out, r->zbuf};
+                  r->cmp_map, r->cmp_seg, r->cmp_out, r->zbuf,
+                  r->trk_depth, r->trk_normal, r->trk_slabs, r->trk_state};
   if (r->reg_stream) { (void)hipStreamSynchronize(r->reg_stream); (void)hipStreamDestroy(r->reg_stream); }
   if (r->dir_host) { (void)hipDeviceSynchronize(); (void)hipHostFree(r->dir_host); }
   if (r->ts_host) (void)hipHostFree(r->ts_host);
@@ -3989,6 +3998,7 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_reg) (void)hipEventDestroy(r->ev_reg);
   if (r->ev_staging) (void)hipEventDestroy(r->ev_staging);
   if (r->ev_render) (void)hipEventDestroy(r->ev_render);
+  if (r->ev_track) (void)hipEventDestroy(r->ev_track);
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
@@ -4648,6 +4658,100 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(r->ev_render, st));
   r->render_busy = true;
+  return SMX_OK;
+}
+
+int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
+                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
+                    const smx_buffer_desc* model_normal_out) {
+  SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
+                result != nullptr);
+  const smx_track_params& p = *params;
+  SMX_CHECK_ARG(std::isfinite(depth_scaling) && depth_scaling > 0);
+  auto img_ok = [&](const smx_buffer_desc* d, size_t elem) {
+    return d->address && d->width == r->W && d->height == r->H && d->pitch >= (size_t)r->W * elem && d->pitch % elem == 0 &&
+           (uintptr_t)d->address % elem == 0;
+  };
+  SMX_CHECK_ARG(img_ok(depth, 2) && img_ok(normals, 8));
+  SMX_CHECK_ARG(!model_depth_out || img_ok(model_depth_out, 4));
+  SMX_CHECK_ARG(!model_normal_out || img_ok(model_normal_out, 16));
+  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(global_T_pred[k]));
+  int levels_used = 0;
+  for (int l = 0; l < kTrackLevels; ++l) {
+    SMX_CHECK_ARG(p.level_iterations[l] >= 0 && p.level_iterations[l] <= kTrackMaxIterationsPerLevel);
+    if (p.level_iterations[l] == 0) continue;
+    ++levels_used;
+    SMX_CHECK_ARG(p.level_stride[l] == 1 || p.level_stride[l] == 2 || p.level_stride[l] == 4 || p.level_stride[l] == 8);
+  }
+  SMX_CHECK_ARG(levels_used > 0);
+  SMX_CHECK_ARG(std::isfinite(p.max_distance) && p.max_distance > 0);
+  SMX_CHECK_ARG(p.max_normal_angle_deg > 0 && p.max_normal_angle_deg <= 180.0f);
+  SMX_CHECK_ARG(p.convergence_rotation >= 0 && p.convergence_translation >= 0 && p.min_inliers >= 0);
+  SMX_CHECK_ARG(p.min_inlier_fraction >= 0 && p.min_inlier_fraction <= 1 && p.min_pivot_ratio >= 0);
+  SMX_CHECK_ARG(std::isfinite(p.near_z) && p.near_z > 0 && p.far_z > p.near_z);
+  SMX_CHECK_ARG(std::isfinite(p.disc_radius_factor) && p.disc_radius_factor > 0);
+  SMX_CHECK_ARG(p.max_splat_extent_in_pixels > 0 && p.max_splat_extent_in_pixels <= 1024);
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  const size_t px = (size_t)r->W * r->H;
+  if (!r->trk_state) {
+    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_depth), px * sizeof(float)));
+    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_normal), px * sizeof(float4)));
+    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_slabs), sizeof(double) * kTrackMaxSlabs * kTrackSlabStride));
+    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_state), sizeof(TrackDev)));
+  }
+  if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
+  // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
+  smx_render_params rp;
+  memset(&rp, 0, sizeof(rp));
+  rp.width = r->W; rp.height = r->H; rp.fx = r->fx; rp.fy = r->fy; rp.cx = r->cx; rp.cy = r->cy;
+  for (int k = 0; k < 12; ++k) rp.global_T_camera[k] = global_T_pred[k];
+  rp.near_z = p.near_z; rp.far_z = p.far_z; rp.splat_mode = SMX_SPLAT_DISC;
+  rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
+  rp.surfel_integration_active_window_size = 2147483647;
+  smx_buffer_desc dd, nd;
+  dd.address = r->trk_depth; dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
+  nd.address = r->trk_normal; nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
+  { const int rcr = smx_recon_render(r, s, &rp, &dd, nullptr, &nd, nullptr); if (rcr != SMX_OK) return rcr; }
+  if (model_depth_out)
+    SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
+  if (model_normal_out)
+    SMX_HIP(hipMemcpy2DAsync(model_normal_out->address, model_normal_out->pitch, nd.address, nd.pitch, nd.pitch, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
+  TrackBuffers tb;
+  tb.model_depth = r->trk_depth; tb.model_normal = r->trk_normal; tb.slabs = r->trk_slabs; tb.state = r->trk_state;
+  const int rct = track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred,
+                                p, result_on_device ? result : nullptr);
+  if (rct != SMX_OK) return rct;
+  SMX_HIP(hipEventRecord(r->ev_track, st));
+  r->track_busy = true;
+  if (!result_on_device) {
+    SMX_HIP(hipMemcpyAsync(result, &r->trk_state->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  return SMX_OK;
+}
+
+int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
+                                     int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  *count = 0;
+  if (!r->trk_state || !r->track_busy) return SMX_OK;
+  SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
+  int32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  n = std::max(0, std::min(n, (int32_t)kTrackRing));
+  const int32_t m = std::min(n, capacity);
+  if (m > 0) {
+    SMX_HIP(hipMemcpyAsync(records, r->trk_state->ring, sizeof(smx_track_iteration) * (size_t)m, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  *count = n;
   return SMX_OK;
 }
 

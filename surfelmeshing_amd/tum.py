@@ -373,7 +373,30 @@ def write_tum_dataset(folder, frames, timestamps, calibration, trajectory=None, 
             write_png(os.path.join(folder, "depth", name + ".png"), d, filters=(4, 3, 2, 1, 0))
             f.write("%s rgb/%s.png %s depth/%s.png\n" % (name, name, name, name))
     if trajectory is not None:
-        with open(os.path.join(folder, trajectory_filename), "w") as f:
-            f.write("# timestamp tx ty tz qx qy qz qw\n")
-            for t, tr, q in trajectory:
-                f.write("%.6f %r %r %r %r %r %r %r\n" % ((t,) + tuple(float(v) for v in tr) + tuple(float(v) for v in q)))
+        write_tum_trajectory(os.path.join(folder, trajectory_filename), trajectory)
+
+
+def write_tum_trajectory(path, trajectory):
+    """A trajectory file in TUM format: trajectory = list of (timestamp, (tx, ty, tz), (qx, qy, qz, qw))."""
+    with open(path, "w") as f:
+        f.write("# timestamp tx ty tz qx qy qz qw\n")
+        for t, tr, q in trajectory:
+            f.write("%.6f %r %r %r %r %r %r %r\n" % ((t,) + tuple(float(v) for v in tr) + tuple(float(v) for v in q)))
+
+
+def quaternion_xyzw_from_matrix(R):
+    """Unit quaternion (x, y, z, w), w >= 0, of a 3 x 3 rotation matrix (Shepperd's method, float64)."""
+    R = np.asarray(R, np.float64)
+    k = [R[0, 0], R[1, 1], R[2, 2], R[0, 0] + R[1, 1] + R[2, 2]]
+    i = int(np.argmax(k))
+    if i == 3:
+        q = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], 1.0 + k[3]])
+    else:
+        j, l = (i + 1) % 3, (i + 2) % 3
+        q = np.zeros(4)
+        q[i] = 1.0 + R[i, i] - R[j, j] - R[l, l]
+        q[j] = R[i, j] + R[j, i]
+        q[l] = R[i, l] + R[l, i]
+        q[3] = R[l, j] - R[j, l]
+    q /= np.linalg.norm(q)
+    return -q if q[3] < 0 else q

@@ -2,7 +2,10 @@
 RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> optional OBJ / PLY export.
       python tools/run_tum.py <dataset_folder> [--trajectory groundtruth.txt] [--export_mesh out.obj]
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
-                              [--compact_every N] [--compact_at_fill F] ...
+                              [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]] ...
+With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
+ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
+that is there is used for the first pose and for an error report only.
 With --synthetic N it first writes an N-frame synthetic dataset into the folder (the test stream), so that the whole
 path can be exercised without data."""
 import argparse
@@ -37,6 +40,70 @@ def overview_pose(rec):
     return render.look_at(eye, centre, up=(0.0, -1.0, 0.0))
 
 
+def run_tracked(args, video, pipe, n, have_trajectory):
+    """The frame loop with tracked poses.  The first frame is integrated alone at the start pose, without the cull: the
+    map the next 2 * half frames are tracked against.  Then frame f + half is tracked against the map as it stands
+    (integrated up to f - 1) before frame f is integrated with the cull and the tracked poses of f - half .. f + half.
+    Returns the number of integrated frames."""
+    from surfelmeshing_amd import tum
+    from surfelmeshing_amd.pipeline import others_TR_reference
+    from surfelmeshing_amd.tracking import Tracker
+    half = args.outlier_filtering_frame_count // 2
+    first = args.start_frame
+    truth = {f: np.asarray(video.depth_frame(f).global_T_frame(), np.float64).reshape(3, 4) for f in range(first, n)} \
+        if have_trajectory else None
+    tracker = Tracker(pipe)
+    uploaded = set()
+
+    def need(g):
+        if g not in uploaded and g < n:
+            pipe.upload(g, video.depth_frame(g).GetImage(), video.color_frame(g).GetImage())
+            video.depth_frame(g).ClearImageAndDerivedData()
+            video.color_frame(g).ClearImageAndDerivedData()
+            uploaded.add(g)
+
+    def track(g):
+        need(g)
+        out = tracker.track(g)
+        if not out.ok:
+            print("frame %d: %s, keeping the prediction" % (g, out.status_name))
+
+    start = truth[first] if truth else np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
+    need(first)
+    tracker.set_pose(first, start)
+    pipe.process(first, [], None, tracker.poses[first])
+    integrated = [first]
+    for g in range(first + 1, min(n, first + 2 * half)):
+        track(g)
+    for f in range(first + half, n - half):
+        if f + half not in tracker.poses:
+            track(f + half)
+        others = [f - k for k in range(1, half + 1)] + [f + k for k in range(1, half + 1)]
+        for g in others:
+            need(g)
+        G = tracker.poses[f]
+        T = others_TR_reference(G, [tracker.poses[g] for g in others], args.depth_scaling) if others else None
+        pipe.process(f, others, T, G)
+        integrated.append(f)
+        old = f - half - 1
+        if old in uploaded:
+            pipe.release(old)
+    print("tracked %d frames, %d kept their prediction" % (len(tracker.outcomes), len(tracker.lost)))
+    if args.track_write_trajectory:
+        tum.write_tum_trajectory(args.track_write_trajectory, [
+            (video.depth_frame(f).timestamp, tracker.poses[f][:, 3], tum.quaternion_xyzw_from_matrix(tracker.poses[f][:, :3]))
+            for f in integrated])
+        print("Wrote %s." % args.track_write_trajectory)
+    if truth:
+        err = np.array([np.linalg.norm(tracker.poses[f][:, 3].astype(np.float64) - truth[f][:, 3]) for f in integrated])
+        still = np.array([np.linalg.norm(truth[first][:, 3] - truth[f][:, 3]) for f in integrated])
+        ate, ate_still = float(np.sqrt((err ** 2).mean())), float(np.sqrt((still ** 2).mean()))
+        print("ATE RMSE %.5f m over %d frames (a trajectory that never moves from the first pose: %.5f m, ratio %.3f)" % (
+            ate, len(integrated), ate_still, ate / max(ate_still, 1e-12)))
+    tracker.close()
+    return len(integrated)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset_folder")
@@ -63,6 +130,9 @@ def main():
     ap.add_argument("--render_color", choices=("color", "last_update", "creation", "radii", "normals"), default="color")
     ap.add_argument("--render_overview", action="store_true",
                     help="at the end, render one view from outside the map's bounds looking at its centre")
+    ap.add_argument("--track", action="store_true",
+                    help="track the camera against the map instead of reading the poses from the trajectory file")
+    ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
@@ -84,7 +154,9 @@ def main():
         tum.write_tum_dataset(args.dataset_folder, frames, stamps, (s.fx, s.fy, s.cx - 0.5, s.cy - 0.5), traj)
         args.max_depth = 10.0
 
-    video = tum.ReadTUMRGBDDatasetAssociatedAndCalibrated(args.dataset_folder, args.trajectory)
+    have_trajectory = os.path.exists(os.path.join(args.dataset_folder, args.trajectory))
+    video = tum.ReadTUMRGBDDatasetAssociatedAndCalibrated(
+        args.dataset_folder, args.trajectory if (have_trajectory or not args.track) else None)
     if video is None:
         sys.exit("Could not read dataset.")
     cam = video.depth_camera
@@ -101,7 +173,9 @@ def main():
     t0 = time.time()
     done = 0
     compactions, removed = 0, 0
-    for f in range(args.start_frame, n):
+    if args.track:
+        done = run_tracked(args, video, pipe, n, have_trajectory)
+    for f in range(args.start_frame, n if not args.track else args.start_frame):
         # main.cc:905-968: everything up to f + half + 1 is on the GPU before frame f is processed
         for g in range(f, min(n - 1, f + half + 1) + 1):
             if g not in uploaded:
