@@ -724,6 +724,56 @@ int smx_recon_neighbor_candidates(smx_recon r, smx_stream s, smx_nn nn, const ui
 int smx_recon_check_triangles(smx_recon r, smx_stream s, const uint32_t* triangles, uint32_t n_triangles,
                               float long_edge_total_factor_squared, uint8_t* flags, int32_t on_device);
 
+/* ---- triangulation of the map on the device: a localized Delaunay triangulation (not in the reference, whose
+ * advancing-front mesher is a sequential CPU algorithm; Gopi et al. 2000, Buchart et al. 2008) ----
+ * A pure function of the map as it stands, slots [0, surfels_size()): smooth position (rows 3-5), RadiusSquared (row 7),
+ * normal (rows 8-10).  A slot is live iff !(RadiusSquared < 0) and its smooth position is finite.
+ * Candidates of live slot p: the list smx_nn_query_self gives for p with r^2 = search_radius_factor^2 RadiusSquared[p]
+ * and k = max_neighbors (ascending by (dist^2, index)), without p itself, without every j with dot(n_p, n_j) <=
+ * cos(max_angle_between_normals), and without every j whose projection onto p's tangent plane has a squared length
+ * <= 1e-12 RadiusSquared[p].
+ * Star of p: the candidates' smooth positions are projected onto the plane through p with normal n_p (p = origin); the
+ * star is the set of Delaunay triangles of {origin} + {projections} that are incident to the origin: (origin, a, b)
+ * with a turn from a to b in (0, pi) and no other candidate strictly inside the circle through the three.  Fewer than
+ * two candidates: empty star.  More than max_star_degree star neighbours: empty star, counted in star_overflow.
+ * Agreement: {p, a, b} is accepted iff it is in the star of p, of a and of b.
+ * Filters, on the 3-D smooth positions: every interior angle within [min_triangle_angle, max_triangle_angle]; the
+ * triangle normal, oriented to have a positive dot with n_p + n_a + n_b, has a positive dot with each of the three.
+ * Output: uint32 [T][3], each triangle once, stored (p, a, b) with p the smallest slot index, counter-clockwise seen
+ * from the side the oriented normal points to, the array ascending by (p, a, b).  Two calls on the same map give the
+ * same bytes (count, exclusive scan, write: no atomic cursor).  Hence: every index is live, no triangle twice, every
+ * undirected edge in at most two triangles, every edge (u, v) has |uv|^2 <= factor^2 min(r^2_u, r^2_v).
+ * Where the three tangent planes disagree the triangle is rejected and a hole stays: no hole filling here. */
+typedef struct {              /* smx_mesh_params_default() fills the defaults (names as in the reference's main.cc) */
+  float max_angle_between_normals_deg;   /* 90 */
+  float min_triangle_angle_deg;          /* 10 */
+  float max_triangle_angle_deg;          /* 170 */
+  float search_radius_factor;            /* 1.0; allowed 1 .. 2 (max_neighbor_search_range_increase_factor) */
+  int32_t max_neighbors;                 /* 64; allowed 1 .. 64 */
+  int32_t max_star_degree;               /* 16: fixed at compile time, reported by the default call, not settable */
+} smx_mesh_params;
+typedef struct {
+  uint32_t n_live;             /* live slots */
+  uint32_t n_star_triangles;   /* distinct triangles that are in at least one star */
+  uint32_t n_triangles;        /* accepted by agreement and filters = T */
+  uint32_t star_overflow;      /* live slots whose star had more than max_star_degree neighbours */
+  uint32_t truncated_lists;    /* live slots whose candidate list came back full (max_neighbors entries) */
+} smx_mesh_stats;
+int smx_mesh_params_default(smx_mesh_params* out);
+/* Rebuilds `nn` over the map itself (smx_recon_build_neighbor_index with cell_size) and triangulates.  Ordered after
+ * everything enqueued on the object; synchronous like smx_recon_compact.  triangles: device pointer if on_device, host
+ * pointer otherwise, room for `capacity` triangles.  capacity < T: SMX_ERR_INVALID_ARGUMENT, *n_triangles = T, nothing
+ * is written (ask with capacity 0, allocate, call again); triangles == NULL with capacity 0 is that count-only form.
+ * stats may be NULL.  SMX_ERR_INVALID_ARGUMENT (nothing launched): max_neighbors outside 1 .. 64, search_radius_factor
+ * outside 1 .. 2, angles outside 0 .. 180 or min > max, a max_star_degree other than the default's.  Changes no map
+ * state.  Workspace (lists, rings, counts) is kept in the object and reused. */
+int smx_recon_triangulate(smx_recon r, smx_stream s, smx_nn nn, float cell_size, const smx_mesh_params* p,
+                          uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
+                          smx_mesh_stats* stats);
+/* Tools: milliseconds the last smx_recon_triangulate call spent in the index build, the list query, the star kernel,
+ * and agreement + scan + write (timed events on the call's stream).  Zeros before the first call. */
+int smx_recon_debug_mesh_timings(smx_recon r, float out_ms[4]);
+
 /* ---- benchmark input generator (not part of the reference's interface) ----
  * Renders one frame of the synthetic room stream into device buffers:
  * depth u16 = round(depth_scaling * z) with sigma = noise_sigma * z^2 noise and coherent 8x8

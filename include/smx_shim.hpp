@@ -457,6 +457,11 @@ class CUDASurfelsCPU {
 };
 
 // ---- APP/cuda_surfel_reconstruction.h -----------------------------------------------------------------
+// Thresholds of CUDASurfelReconstruction::Triangulate: smx_mesh_params, filled with the defaults.
+struct MeshParams : smx_mesh_params {
+  MeshParams() { SMX_SHIM_CHECK(smx_mesh_params_default(this)); }
+};
+
 class CUDASurfelReconstruction {
  public:
   // The three cudaGraphicsResource_t arguments and the render window of the reference's constructor are
@@ -541,6 +546,23 @@ class CUDASurfelReconstruction {
     }
     SMX_SHIM_CHECK(smx_recon_compact(handle_, stream, old_to_new && n ? old_to_new->data() : nullptr, n, 0, nullptr,
                                      links_dropped));
+  }
+  // Not in the reference: triangulates the map as it stands on the device (smx_recon_triangulate in smx.h: a localized
+  // Delaunay triangulation).  *triangles receives three slot indices per triangle, in the order smx.h describes.
+  // index: a neighbour index to rebuild and use (one is created for the call if null); stats may be null.  Synchronous.
+  void Triangulate(cudaStream_t stream, const MeshParams& params, std::vector<u32>* triangles, smx_nn index = nullptr,
+                   float cell_size = 0.05f, smx_mesh_stats* stats = nullptr) {
+    smx_nn nn = index;
+    if (!nn) SMX_SHIM_CHECK(smx_nn_create(-1, &nn));
+    u32 count = 0;
+    int rc = smx_recon_triangulate(handle_, stream, nn, cell_size, &params, nullptr, 0, 0, &count, stats);
+    if (rc == SMX_OK || (rc == SMX_ERR_INVALID_ARGUMENT && count > 0)) {   // (the capacity rule: the count came back)
+      triangles->resize((size_t)3 * count);
+      rc = count ? smx_recon_triangulate(handle_, stream, nn, cell_size, &params, triangles->data(), count, 0, &count, stats)
+                 : SMX_OK;
+    }
+    if (!index) (void)smx_nn_destroy(nn);
+    SMX_SHIM_CHECK(rc);
   }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.

@@ -105,6 +105,29 @@ class TrackIteration(C.Structure):
                 ("sums", C.c_double * TRACK_SUMS), ("x", C.c_double * 6)]
 
 
+class MeshParams(C.Structure):
+    """smx_mesh_params: thresholds of smx_recon_triangulate (names as in the reference's main.cc)."""
+    _fields_ = [("max_angle_between_normals_deg", C.c_float), ("min_triangle_angle_deg", C.c_float),
+                ("max_triangle_angle_deg", C.c_float), ("search_radius_factor", C.c_float),
+                ("max_neighbors", C.c_int32), ("max_star_degree", C.c_int32)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """smx_mesh_params_default(), then any field by name."""
+        p = cls()
+        check(load().smx_mesh_params_default(C.byref(p)))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+class MeshStats(C.Structure):
+    """smx_mesh_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")]
+
+
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
     _fields_ = [("frame_index", C.c_uint32), ("surfel_count", C.c_size_t),
@@ -148,7 +171,8 @@ EXPORTS = [
     "smx_compute_point_radii_and_remove_isolated_pixels", "smx_erode_normals_radii", "smx_erode_normals_radii_signal",
     "smx_recon_create", "smx_recon_destroy", "smx_recon_integrate", "smx_recon_regularize",
     "smx_recon_transfer_all_to_cpu", "smx_recon_set_delta_tracking", "smx_recon_transfer_changed_to_cpu", "smx_recon_export_vertices", "smx_recon_get_timings", "smx_recon_get_timings_nowait", "smx_recon_debug_stamp_ring", "smx_recon_debug_internal_stream",
-    "smx_recon_build_neighbor_index", "smx_recon_neighbor_candidates", "smx_recon_check_triangles", "smx_recon_deform_by_creation_frame",
+    "smx_recon_build_neighbor_index", "smx_recon_neighbor_candidates", "smx_recon_check_triangles",
+    "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings", "smx_recon_deform_by_creation_frame",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",

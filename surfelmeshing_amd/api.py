@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
-                   TrackIteration, TrackParams, TrackResult)
+                   MeshParams, MeshStats, TrackIteration, TrackParams, TrackResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
@@ -504,6 +504,7 @@ class CUDASurfelReconstruction:
                                                 depth_camera.height(), C.c_float(fx), C.c_float(fy), C.c_float(cx),
                                                 C.c_float(cy), C.c_int32(device_id), C.byref(self._h)))
         self._last_stream = None
+        self._device_id = int(device_id)
 
     def Integrate(self, stream, frame_index, depth_scaling, depth_buffer, normals_buffer, radius_buffer, color_buffer,
                   global_T_local, sensor_noise_factor, max_surfel_confidence, regularizer_weight,
@@ -598,6 +599,39 @@ class CUDASurfelReconstruction:
             self._h, _sv(stream), tri.ctypes.data_as(C.c_void_p), C.c_uint32(tri.shape[0]),
             C.c_float(long_edge_total_factor_squared), flags.ctypes.data_as(C.c_void_p), C.c_int32(0)))
         return flags
+
+    def Triangulate(self, stream, params=None, index=None, cell_size=None):
+        """Not in the reference: triangulates the map as it stands on the device (smx_recon_triangulate: a localized
+        Delaunay triangulation -- every surfel triangulates its neighbours in its tangent plane, a triangle is kept if
+        its three corners agree).  params: a MeshParams (MeshParams.defaults()); index: a SurfelNeighborIndex to
+        (re)build and use, one is created and closed here if None; cell_size of that index (default: 5 cm, results do
+        not depend on it).  Synchronous.  Returns (triangles [T,3] uint32 of slot indices -- p smallest, counter-
+        clockwise seen from the normals' side, ascending -- and a dict of smx_mesh_stats)."""
+        p = params if params is not None else MeshParams.defaults()
+        own = index is None
+        nn = SurfelNeighborIndex(self._device_id) if own else index
+        cs = C.c_float(0.05 if cell_size is None else cell_size)
+        try:
+            L = _lib.load()
+            T, st = C.c_uint32(0), MeshStats()
+            rc = L.smx_recon_triangulate(self._h, _sv(stream), nn._h, cs, C.byref(p), None, C.c_uint32(0), C.c_int32(0),
+                                         C.byref(T), C.byref(st))
+            if rc != 0 and not (rc == -1 and T.value > 0):   # (SMX_ERR_INVALID_ARGUMENT with the count: the capacity rule)
+                _lib.check(rc)
+            tri = np.zeros((T.value, 3), np.uint32)
+            if T.value:
+                _lib.check(L.smx_recon_triangulate(self._h, _sv(stream), nn._h, cs, C.byref(p), tri.ctypes.data_as(C.c_void_p),
+                                                   C.c_uint32(T.value), C.c_int32(0), C.byref(T), C.byref(st)))
+            return tri, {n: int(getattr(st, n)) for n, _ in MeshStats._fields_}
+        finally:
+            if own:
+                nn.close()
+
+    def debug_mesh_timings(self):
+        """Milliseconds of the last Triangulate call: index build, list query, star kernel, agreement + scan + write."""
+        out = (C.c_float * 4)()
+        _lib.check(_lib.load().smx_recon_debug_mesh_timings(self._h, out))
+        return dict(zip(("index_build", "list_query", "star", "agree_write"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

@@ -35,6 +35,7 @@
 
 #include "smx_common.hpp"
 #include "smx_track.hpp"
+#include "smx_mesh.hpp"
 #include <hip/hip_ext.h>
 
 using namespace smx;
@@ -3675,6 +3676,7 @@ struct smx_recon_s {
   TrackDev* trk_state;
   hipEvent_t ev_track;
   bool track_busy;
+  MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging
 };
 
 // kernel slots of one Integrate call (launch order)
@@ -3999,6 +4001,7 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_staging) (void)hipEventDestroy(r->ev_staging);
   if (r->ev_render) (void)hipEventDestroy(r->ev_render);
   if (r->ev_track) (void)hipEventDestroy(r->ev_track);
+  mesh_workspace_destroy(r->mesh);
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
@@ -4857,6 +4860,34 @@ int smx_recon_check_triangles(smx_recon r, smx_stream s, const uint32_t* triangl
     if (dflags) (void)hipFree(dflags);
   }
   return rc;
+}
+
+int smx_recon_triangulate(smx_recon r, smx_stream s, smx_nn nn, float cell_size, const smx_mesh_params* p,
+                          uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
+                          smx_mesh_stats* stats) {
+  SMX_CHECK_ARG(r != nullptr && nn != nullptr && p != nullptr && n_triangles != nullptr && cell_size > 0);
+  SMX_CHECK_ARG(triangles != nullptr || capacity == 0);
+  { const int rcp = mesh_check_params(*p); if (rcp != SMX_OK) return rcp; }
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  if (!r->mesh) { const int rcw = mesh_workspace_create(&r->mesh); if (rcw != SMX_OK) return rcw; }
+  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  { const int rcb = mesh_stamp_begin(r->mesh, st); if (rcb != SMX_OK) return rcb; }
+  // (the build orders st behind the pipelined regulariser, reads the slot count back and leaves merged slots out)
+  { const int rcb = smx_recon_build_neighbor_index(r, s, nn, cell_size); if (rcb != SMX_OK) return rcb; }
+  uint32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
+  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
+  return mesh_triangulate(r->mesh, st, nn, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0, r->S.quad(kGroupN, 1) - n0, n,
+                          *p, triangles, capacity, on_device, n_triangles, stats);
+}
+
+int smx_recon_debug_mesh_timings(smx_recon r, float out_ms[4]) {
+  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
+  SMX_ON_DEVICE(r->device);
+  return mesh_phase_ms(r->mesh, out_ms);
 }
 
 namespace {

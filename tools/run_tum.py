@@ -2,7 +2,10 @@
 RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> optional OBJ / PLY export.
       python tools/run_tum.py <dataset_folder> [--trajectory groundtruth.txt] [--export_mesh out.obj]
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
-                              [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]] ...
+                              [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
+                              [--mesh] ...
+With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
+without it the OBJ holds the vertices only.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.
@@ -130,6 +133,8 @@ def main():
     ap.add_argument("--render_color", choices=("color", "last_update", "creation", "radii", "normals"), default="color")
     ap.add_argument("--render_overview", action="store_true",
                     help="at the end, render one view from outside the map's bounds looking at its centre")
+    ap.add_argument("--mesh", action="store_true",
+                    help="triangulate the final map on the device; --export_mesh then writes the faces as well")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -210,8 +215,15 @@ def main():
         print("%d compactions removed %d merged slots" % (compactions, removed))
     if args.render_dir and args.render_overview:
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png")
+    triangles = None
+    if args.mesh:
+        from surfelmeshing_amd import meshing
+        t1 = time.time()
+        triangles, mesh_stats = meshing.mesh_map(rec)
+        print("%d triangles in %.1f ms; %s" % (triangles.shape[0], 1e3 * (time.time() - t1),
+                                              ", ".join("%s %d" % (k, mesh_stats[k]) for k in meshing.STAT_NAMES)))
     if args.export_mesh:
-        export.SaveMeshAsOBJ(rec, args.export_mesh)
+        export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles)
         print("Wrote %s." % args.export_mesh)
     if args.export_point_cloud:
         export.SavePointCloudAsPLY(rec, args.export_point_cloud, export_colors=True)
