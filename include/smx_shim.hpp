@@ -564,6 +564,27 @@ class CUDASurfelReconstruction {
     if (!index) (void)smx_nn_destroy(nn);
     SMX_SHIM_CHECK(rc);
   }
+  // Not in the reference: Triangulate's result, kept up to date (smx_recon_triangulate_update in smx.h: the object keeps
+  // the last triangulation and recomputes only around the slots that changed since).  The same bytes and statistics as
+  // Triangulate.  *update_stats (may be null) is that of the call that did the work.  full_above_fraction < 0: the default.
+  void TriangulateUpdate(cudaStream_t stream, const MeshParams& params, std::vector<u32>* triangles, smx_nn index = nullptr,
+                         float cell_size = 0.05f, smx_mesh_stats* stats = nullptr, smx_mesh_update_stats* update_stats = nullptr,
+                         float full_above_fraction = -1.0f) {
+    smx_nn nn = index;
+    if (!nn) SMX_SHIM_CHECK(smx_nn_create(-1, &nn));
+    u32 count = 0;
+    int rc = smx_recon_triangulate_update(handle_, stream, nn, cell_size, &params, full_above_fraction, nullptr, 0, 0, &count,
+                                          stats, update_stats);
+    if (rc == SMX_OK || (rc == SMX_ERR_INVALID_ARGUMENT && count > 0)) {   // (the capacity rule: the state has advanced)
+      triangles->resize((size_t)3 * count);
+      rc = count ? smx_recon_triangulate_update(handle_, stream, nn, cell_size, &params, full_above_fraction, triangles->data(),
+                                                count, 0, &count, stats, nullptr)
+                 : SMX_OK;
+    }
+    if (!index) (void)smx_nn_destroy(nn);
+    SMX_SHIM_CHECK(rc);
+  }
+  void ResetTriangulation() { SMX_SHIM_CHECK(smx_recon_triangulate_reset(handle_)); }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

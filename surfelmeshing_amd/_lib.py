@@ -128,6 +128,11 @@ class MeshStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")]
 
 
+class MeshUpdateStats(C.Structure):
+    """smx_mesh_update_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("mode", "n_changed", "n_dirty", "n_reagreed", "n_kept_triangles")]
+
+
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
     _fields_ = [("frame_index", C.c_uint32), ("surfel_count", C.c_size_t),
@@ -172,7 +177,8 @@ EXPORTS = [
     "smx_recon_create", "smx_recon_destroy", "smx_recon_integrate", "smx_recon_regularize",
     "smx_recon_transfer_all_to_cpu", "smx_recon_set_delta_tracking", "smx_recon_transfer_changed_to_cpu", "smx_recon_export_vertices", "smx_recon_get_timings", "smx_recon_get_timings_nowait", "smx_recon_debug_stamp_ring", "smx_recon_debug_internal_stream",
     "smx_recon_build_neighbor_index", "smx_recon_neighbor_candidates", "smx_recon_check_triangles",
-    "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings", "smx_recon_deform_by_creation_frame",
+    "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings",
+    "smx_recon_triangulate_update", "smx_recon_triangulate_reset", "smx_recon_debug_mesh_update_timings", "smx_recon_deform_by_creation_frame",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",

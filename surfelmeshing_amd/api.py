@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
-                   MeshParams, MeshStats, TrackIteration, TrackParams, TrackResult)
+                   MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
@@ -626,6 +626,47 @@ class CUDASurfelReconstruction:
         finally:
             if own:
                 nn.close()
+
+    def TriangulateUpdate(self, stream, params=None, index=None, cell_size=None, full_above_fraction=None):
+        """Not in the reference: Triangulate's result, kept up to date (smx_recon_triangulate_update: the object keeps the
+        last triangulation, finds the slots that changed since, and recomputes only their stars and the triangles around
+        them).  Arguments as Triangulate; full_above_fraction: the share of dirty slots above which the full path runs
+        (None: the library's default; it chooses the path, never the result).  Synchronous.  Returns (triangles, stats
+        dict, update stats dict: mode, n_changed, n_dirty, n_reagreed, n_kept_triangles) -- the update stats are those
+        of the call that did the work, the first of the ask-then-fill pair."""
+        p = params if params is not None else MeshParams.defaults()
+        own = index is None
+        nn = SurfelNeighborIndex(self._device_id) if own else index
+        cs = C.c_float(0.05 if cell_size is None else cell_size)
+        frac = C.c_float(-1.0 if full_above_fraction is None else full_above_fraction)
+        try:
+            L = _lib.load()
+            T, st, us = C.c_uint32(0), MeshStats(), MeshUpdateStats()
+            rc = L.smx_recon_triangulate_update(self._h, _sv(stream), nn._h, cs, C.byref(p), frac, None, C.c_uint32(0),
+                                                C.c_int32(0), C.byref(T), C.byref(st), C.byref(us))
+            if rc != 0 and not (rc == -1 and T.value > 0):   # (SMX_ERR_INVALID_ARGUMENT with the count: the capacity rule)
+                _lib.check(rc)
+            tri = np.zeros((T.value, 3), np.uint32)
+            if T.value:
+                # (the state has advanced: this call finds nothing changed and copies the kept array out)
+                _lib.check(L.smx_recon_triangulate_update(self._h, _sv(stream), nn._h, cs, C.byref(p), frac,
+                                                          tri.ctypes.data_as(C.c_void_p), C.c_uint32(T.value), C.c_int32(0),
+                                                          C.byref(T), C.byref(st), None))
+            return (tri, {n: int(getattr(st, n)) for n, _ in MeshStats._fields_},
+                    {n: int(getattr(us, n)) for n, _ in MeshUpdateStats._fields_})
+        finally:
+            if own:
+                nn.close()
+
+    def ResetTriangulation(self):
+        """Drops the state TriangulateUpdate keeps and frees its memory; the next update runs the full path."""
+        _lib.check(_lib.load().smx_recon_triangulate_reset(self._h))
+
+    def debug_mesh_update_timings(self):
+        """Milliseconds of the last TriangulateUpdate call, by phase."""
+        out = (C.c_float * 6)()
+        _lib.check(_lib.load().smx_recon_debug_mesh_update_timings(self._h, out))
+        return dict(zip(("diff", "index_builds", "reverse_test", "subset_lists", "stars", "agree_merge"), [float(v) for v in out]))
 
     def debug_mesh_timings(self):
         """Milliseconds of the last Triangulate call: index build, list query, star kernel, agreement + scan + write."""

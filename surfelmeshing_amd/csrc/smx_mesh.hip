@@ -9,6 +9,15 @@
 //                    agreement and filters and scans the counts inside the workgroup; <true> finds them again and
 //                    writes them at (workgroup offset + local offset), then orders its own few entries
 //   k_mesh_scan      one workgroup: exclusive scan of the workgroup totals
+// smx_recon_triangulate_update adds
+//   k_mesh_diff      a lane per slot, twice: <false> compares the slot's seven words bitwise with the kept snapshot, writes
+//                    the changed byte and counts the ghosts (snapshot positions of changed slots that were live) per
+//                    workgroup; <true> writes the rows of the two index builds, the ghosts at (workgroup offset + local
+//                    offset), the state bytes and radii of the reverse test, and the new snapshot
+//   k_mesh_worklist  a lane per slot, twice: counts / writes the ascending list of the slots whose star is recomputed
+//   k_mesh_star<true>   the star kernel over that list; marks the members of the old and of the new ring in a byte row
+//   k_mesh_agree<.., true>   slots with the byte set recount and rewrite, the others reuse their kept counts and copy
+//                    their kept run of the previous output
 // The arithmetic is in smx_mesh.hpp; nothing here decides a sign by itself.
 #include <algorithm>
 #include <cmath>
@@ -21,7 +30,8 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-enum : int { kStLive = 0, kStStar, kStOverflow, kStTruncated, kStTotal, kStWords = 8 };
+enum : int { kStLive = 0, kStStar, kStOverflow, kStTruncated, kStTotal, kStChanged, kStKept, kStReagreed, kStNoFilter,
+             kStWords = 16 };
 
 struct MeshK {
   const float4* smooth; size_t smooth_stride;
@@ -54,24 +64,39 @@ k_mesh_prepare(MeshK k, float* __restrict__ r2, uint32_t* __restrict__ stat) {
   if ((threadIdx.x & 63) == 0 && live) atomicAdd(&stat[kStLive], live);   // (integer: any order gives the same sum)
 }
 
+// What the update adds to the kernels' arguments.  kept[p]: bits 0-7 the triangles slot p owns, bits 8-15 the distinct star
+// triangles counted at p, bit 16 "p's candidate list came back full".
+constexpr uint32_t kKeptFullBit = 1u << 16;
+struct MeshU {
+  const uint32_t* work; uint32_t n_work;   // ascending slots whose star is recomputed; list row = position in this list
+  uint32_t n_prev;                         // slots below it have a kept ring row
+  uint8_t* in_a;                           // [n] 1 = owned triangles and star-triangle count are recomputed
+  uint32_t* kept;                          // [n]
+  const uint32_t* prev_tri; const uint32_t* prev_local; const uint32_t* prev_block;   // the previous output and its offsets
+};
+
+// kSubset = false: the slot is the work item (u is not read).  kSubset = true: the slot comes from u.work.
+template <bool kSubset>
 __global__ void __launch_bounds__(kBlock)
 k_mesh_star(MeshK k, const uint32_t* __restrict__ lists, const int32_t* __restrict__ counts, uint32_t* __restrict__ rings,
-            uint32_t* __restrict__ meta, uint32_t* __restrict__ stat) {
+            uint32_t* __restrict__ meta, uint32_t* __restrict__ stat, MeshU u) {
   __shared__ float sx[kWaves][64], sy[kWaves][64], sq[kWaves][64];
   __shared__ uint32_t s_ring[kWaves][kMeshMaxStarDegree];
   __shared__ uint32_t s_mask[kWaves];
   __shared__ uint8_t s_is_succ[kWaves][64], s_rank[kWaves][64];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // (every wavefront of the workgroup makes the same number of trips, so that the barriers below are uniform)
-  for (uint32_t base = blockIdx.x * kWaves; base < k.n; base += gridDim.x * kWaves) {
-    const uint32_t p = base + w;
-    const bool valid = p < k.n;
+  const uint32_t n_items = kSubset ? u.n_work : k.n;
+  for (uint32_t base = blockIdx.x * kWaves; base < n_items; base += gridDim.x * kWaves) {
+    const uint32_t item = base + w;
+    const bool valid = item < n_items;
+    const uint32_t p = !kSubset ? item : (valid ? u.work[item] : 0u);
     float4 ps = make_float4(0, 0, 0, 0), pn = make_float4(0, 0, 0, -1.0f);
     int cnt = 0;
     if (valid) {
       ps = k.smooth[(size_t)p * k.smooth_stride];
       pn = k.normal[(size_t)p * k.normal_stride];
-      cnt = counts[p];
+      cnt = counts[item];
     }
     const bool live = valid && slot_live(ps, pn);
     cnt = live ? min(max(cnt, 0), k.K) : 0;
@@ -79,7 +104,7 @@ k_mesh_star(MeshK k, const uint32_t* __restrict__ lists, const int32_t* __restri
     uint32_t j = kInvalid;
     float x = 0.0f, y = 0.0f, q = -1.0f;
     if (lane < cnt) {
-      j = lists[(size_t)p * k.K + lane];
+      j = lists[(size_t)item * k.K + lane];
       if (j < k.n) {
         const float4 js = k.smooth[(size_t)j * k.smooth_stride];
         const float4 jn = k.normal[(size_t)j * k.normal_stride];
@@ -117,11 +142,27 @@ k_mesh_star(MeshK k, const uint32_t* __restrict__ lists, const int32_t* __restri
     if (succ >= 0 && !overflow && (int)s_rank[w][succ] == (rank + 1 == deg ? 0 : rank + 1)) atomicOr(&s_mask[w], 1u << rank);
     __syncthreads();
     if (valid) {
-      if (lane < kMeshMaxStarDegree) rings[(size_t)p * kMeshMaxStarDegree + lane] = overflow ? kInvalid : s_ring[w][lane];
+      if (lane < kMeshMaxStarDegree) {
+        const uint32_t now = overflow ? kInvalid : s_ring[w][lane];
+        if (kSubset) {
+          // (plain byte stores of 1: every racing store writes the same value)
+          if (p < u.n_prev) {
+            const uint32_t old = rings[(size_t)p * kMeshMaxStarDegree + lane];
+            if (old < k.n) u.in_a[old] = 1;
+          }
+          if (now < k.n) u.in_a[now] = 1;
+        }
+        rings[(size_t)p * kMeshMaxStarDegree + lane] = now;
+      }
       if (lane == 0) {
         meta[p] = overflow ? kMeshOverflowBit : ((uint32_t)deg | (s_mask[w] << 8));
-        if (overflow) atomicAdd(&stat[kStOverflow], 1u);
-        if (live && cnt == k.K) atomicAdd(&stat[kStTruncated], 1u);
+        if (kSubset) {
+          u.in_a[p] = 1;
+          u.kept[p] = (live && cnt == k.K) ? kKeptFullBit : 0u;   // (the counts follow in k_mesh_agree: p is in A)
+        } else {
+          if (overflow) atomicAdd(&stat[kStOverflow], 1u);
+          if (live && cnt == k.K) atomicAdd(&stat[kStTruncated], 1u);
+        }
       }
     }
     __syncthreads();   // (the next trip rewrites the rows)
@@ -158,12 +199,16 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* t
 
 // One lane per slot p (no grid stride: the workgroup index is the scan's unit).  Every star triangle of p is looked up
 // in the rings of its other two corners; p owns it iff p is its smallest corner.
-template <bool kWrite>
+// kUpdate: only the slots with u.in_a set do that; the others take their two counts from u.kept and, in the write pass, copy
+// their run of the previous output (same workgroup, previous offsets) to the new offset.  The statistics that the star
+// kernel sums in the full call are summed here from the per-slot values.
+template <bool kWrite, bool kUpdate>
 __global__ void __launch_bounds__(kBlock)
 k_mesh_agree(MeshK k, const uint32_t* __restrict__ rings, const uint32_t* __restrict__ meta, uint32_t* __restrict__ local_off,
              uint32_t* __restrict__ block_sums, const uint32_t* __restrict__ block_off, uint32_t* __restrict__ tri,
-             uint32_t total, uint32_t* __restrict__ stat) {
+             uint32_t total, uint32_t* __restrict__ stat, MeshU u) {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  const bool redo = !kUpdate || (p < k.n && u.in_a[p] != 0);
   uint32_t own = 0, distinct = 0;
   uint32_t* out = nullptr;
   uint32_t room = 0;     // (entries from the slot's offset to the end of the output: the write pass never leaves the buffer)
@@ -174,7 +219,7 @@ k_mesh_agree(MeshK k, const uint32_t* __restrict__ rings, const uint32_t* __rest
   }
   const uint32_t mp = p < k.n ? meta[p] : 0u;
   const uint32_t deg = mesh_meta_degree(mp);
-  if (deg >= 2 && !(mp & kMeshOverflowBit)) {
+  if (redo && deg >= 2 && !(mp & kMeshOverflowBit)) {
     const uint32_t* ring_p = rings + (size_t)p * kMeshMaxStarDegree;
     for (uint32_t i = 0; i < deg; ++i) {
       if (!((mp >> (8 + i)) & 1u)) continue;
@@ -211,6 +256,31 @@ k_mesh_agree(MeshK k, const uint32_t* __restrict__ rings, const uint32_t* __rest
       ++own;
     }
   }
+  if (kUpdate) {
+    const uint32_t word = p < k.n ? u.kept[p] : 0u;
+    if (p >= k.n) {
+    } else if (redo) {
+      if (!kWrite) u.kept[p] = (word & kKeptFullBit) | own | (distinct << 8);
+    } else {
+      own = word & 0xFFu; distinct = (word >> 8) & 0xFFu;
+      if (kWrite) {
+        // (p is below the kept slot count, so its workgroup had an offset in the previous call)
+        const uint32_t* src = u.prev_tri + 3 * (size_t)(u.prev_block[blockIdx.x] + u.prev_local[p]);
+        const uint32_t m = own < room ? own : room;
+        for (uint32_t t = 0; t < 3 * m; ++t) out[t] = src[t];
+      }
+    }
+    if (!kWrite) {
+      const uint32_t ov = wave_sum((mp & kMeshOverflowBit) ? 1u : 0u), full = wave_sum((word & kKeptFullBit) ? 1u : 0u);
+      const uint32_t keep = wave_sum(redo ? 0u : own), again = wave_sum(redo && p < k.n ? 1u : 0u);
+      if ((threadIdx.x & 63) == 0) {
+        if (ov) atomicAdd(&stat[kStOverflow], ov);
+        if (full) atomicAdd(&stat[kStTruncated], full);
+        if (keep) atomicAdd(&stat[kStKept], keep);
+        if (again) atomicAdd(&stat[kStReagreed], again);
+      }
+    }
+  }
   if (!kWrite) {
     uint32_t total;
     const uint32_t off = block_exclusive_scan(own, &total);
@@ -237,6 +307,117 @@ k_mesh_scan(const uint32_t* __restrict__ block_sums, uint32_t nb, uint32_t* __re
   if (threadIdx.x == 0) stat[kStTotal] = carry;
 }
 
+// The diff of smx_recon_triangulate_update: one lane per slot (no grid stride: the workgroup is the scan's unit).
+struct MeshDiff {
+  uint32_t n_prev;
+  float4* snap_s; float4* snap_n;     // [n] the kept seven words: (smooth x, y, z, 0) and (normal x, y, z, RadiusSquared)
+  uint8_t* changed;                   // [n]
+  float* rows; size_t row_len;        // [3][row_len]: the n current positions (NaN where merged), then the ghosts
+  float* reverse_r2; uint8_t* state;  // [row_len] the reverse test's radii (0 unless unchanged and live) and state bytes
+  float* r2;                          // [n] RadiusSquared, the row smx_nn_query_self reads on the full path
+  uint32_t* near_bits; float inv_h;   // the coarse filter of the reverse test (mesh_coarse_cell); null = not used
+};
+// (an integer atomic whose result does not depend on the order: the bit is set, whoever sets it)
+__device__ __forceinline__ void mark_near(const MeshDiff& d, float x, float y, float z, uint32_t* stat) {
+  int ix, iy, iz;
+  if (!mesh_coarse_cell(x, y, z, d.inv_h, &ix, &iy, &iz)) { atomicOr(&stat[kStNoFilter], 1u); return; }
+  const uint32_t b = mesh_coarse_bit(ix, iy, iz);
+  atomicOr(&d.near_bits[b >> 5], 1u << (b & 31u));
+}
+template <bool kWrite>
+__global__ void __launch_bounds__(kBlock)
+k_mesh_diff(MeshK k, MeshDiff d, uint32_t* __restrict__ block_sums, const uint32_t* __restrict__ block_off,
+            uint32_t* __restrict__ stat) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = i < k.n;
+  float4 s = make_float4(0, 0, 0, 0), nr = make_float4(0, 0, 0, -1.0f), os = s, on = nr;
+  if (valid) {
+    s = k.smooth[(size_t)i * k.smooth_stride];
+    nr = k.normal[(size_t)i * k.normal_stride];
+    if (i < d.n_prev) { os = d.snap_s[i]; on = d.snap_n[i]; }
+  }
+  const float now[7] = {s.x, s.y, s.z, nr.w, nr.x, nr.y, nr.z}, kept[7] = {os.x, os.y, os.z, on.w, on.x, on.y, on.z};
+  const bool chg = valid && mesh_slot_changed(i, d.n_prev, now, kept);
+  const bool live = valid && slot_live(s, nr);
+  const bool ghost = chg && i < d.n_prev && slot_live(os, on);
+  uint32_t total;
+  const uint32_t off = block_exclusive_scan(ghost ? 1u : 0u, &total);
+  if (!kWrite) {
+    if (valid) d.changed[i] = chg ? 1 : 0;
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+    const uint32_t nl = wave_sum(live ? 1u : 0u), nc = wave_sum(chg ? 1u : 0u);
+    if ((threadIdx.x & 63) == 0) {
+      if (nl) atomicAdd(&stat[kStLive], nl);
+      if (nc) atomicAdd(&stat[kStChanged], nc);
+    }
+    return;
+  }
+  if (!valid) return;
+  const float nanv = __builtin_nanf("");
+  const bool merged = nr.w < 0.0f;
+  d.rows[i] = merged ? nanv : s.x;
+  d.rows[d.row_len + i] = merged ? nanv : s.y;
+  d.rows[2 * d.row_len + i] = merged ? nanv : s.z;
+  d.reverse_r2[i] = (!chg && live) ? nr.w : 0.0f;
+  d.state[i] = chg ? 0 : 1;
+  d.r2[i] = nr.w;
+  if (d.near_bits != nullptr) {
+    if (chg && live) mark_near(d, s.x, s.y, s.z, stat);
+    if (ghost) mark_near(d, os.x, os.y, os.z, stat);
+  }
+  if (ghost) {
+    const size_t g = (size_t)k.n + block_off[blockIdx.x] + off;
+    if (g < d.row_len) {
+      d.rows[g] = os.x; d.rows[d.row_len + g] = os.y; d.rows[2 * d.row_len + g] = os.z;
+      d.reverse_r2[g] = 0.0f;
+      d.state[g] = 0;
+    }
+  }
+  d.snap_s[i] = make_float4(s.x, s.y, s.z, 0.0f);
+  d.snap_n[i] = nr;
+}
+
+// The rows the reverse test's index is built over: the map's rows and the ghosts, without (NaN) every unchanged slot that
+// the coarse filter shows to have no changed point and no ghost in its ball.  A slot that is left out neither queries nor
+// is found; its count stays 0.
+__global__ void __launch_bounds__(kBlock)
+k_mesh_reverse_rows(uint32_t n, size_t row_len, const float* __restrict__ rows, float* __restrict__ out,
+                    const uint8_t* __restrict__ changed, const float* __restrict__ reverse_r2, float f2, float inv_h,
+                    float max_r2, const uint32_t* __restrict__ near_bits, const uint32_t* __restrict__ stat) {
+  const bool filter = stat[kStNoFilter] == 0;
+  const float nanv = __builtin_nanf("");
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < row_len; i += (size_t)gridDim.x * kBlock) {
+    const float x = rows[i], y = rows[row_len + i], z = rows[2 * row_len + i];
+    bool keep = true;
+    int ix, iy, iz;
+    if (filter && i < n && changed[i] == 0 && f2 * reverse_r2[i] <= max_r2 && mesh_coarse_cell(x, y, z, inv_h, &ix, &iy, &iz)) {
+      keep = false;
+      for (int c = 0; c < 27 && !keep; ++c) {
+        const uint32_t b = mesh_coarse_bit(ix + c % 3 - 1, iy + (c / 3) % 3 - 1, iz + c / 9 - 1);
+        keep = (near_bits[b >> 5] >> (b & 31u)) & 1u;
+      }
+    }
+    out[i] = keep ? x : nanv; out[row_len + i] = keep ? y : nanv; out[2 * row_len + i] = keep ? z : nanv;
+  }
+}
+
+// D as an ascending slot list: every changed slot, and every slot whose reverse query found a changed point or a ghost
+// (only an unchanged live slot asks with a radius, and unchanged points are skipped by their state byte).
+template <bool kWrite>
+__global__ void __launch_bounds__(kBlock)
+k_mesh_worklist(uint32_t n, const uint8_t* __restrict__ changed, const int32_t* __restrict__ reverse_count, int32_t all,
+                uint32_t* __restrict__ block_sums, const uint32_t* __restrict__ block_off, uint32_t* __restrict__ work) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool in_d = i < n && (all || changed[i] != 0 || (reverse_count != nullptr && reverse_count[i] > 0));
+  uint32_t total;
+  const uint32_t off = block_exclusive_scan(in_d ? 1u : 0u, &total);
+  if (!kWrite) {
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+  } else if (in_d) {
+    work[block_off[blockIdx.x] + off] = i;
+  }
+}
+
 template <typename T>
 int grow(T** p, size_t* cap, size_t want) {
   if (want <= *cap) return SMX_OK;
@@ -244,6 +425,24 @@ int grow(T** p, size_t* cap, size_t want) {
   *cap = 0;
   const size_t c = want + want / 8 + 1024;
   SMX_HIP(hipMalloc(reinterpret_cast<void**>(p), c * sizeof(T)));
+  *cap = c;
+  return SMX_OK;
+}
+
+// ... keeping the first `keep` elements (the kept state of the update)
+template <typename T>
+int grow_keep(T** p, size_t* cap, size_t want, size_t keep, hipStream_t st) {
+  if (want <= *cap) return SMX_OK;
+  const size_t c = want + want / 8 + 1024;
+  T* fresh = nullptr;
+  SMX_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), c * sizeof(T)));
+  if (*p && keep > 0) {
+    const hipError_t e = hipMemcpyAsync(fresh, *p, std::min(keep, *cap) * sizeof(T), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) { (void)hipFree(fresh); SMX_HIP(e); }
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  if (*p) SMX_HIP(hipFree(*p));
+  *p = fresh;
   *cap = c;
   return SMX_OK;
 }
@@ -259,6 +458,22 @@ struct MeshWorkspace {
   uint32_t* stat;
   hipEvent_t ev[5];
   bool timed;
+  // smx_recon_triangulate_update: the kept state (rings and meta above belong to it while `have` is set) ...
+  bool have;
+  uint32_t n_prev, t_prev;
+  smx_mesh_params prm;
+  smx_mesh_stats last_stats;
+  int cur;                                                       // which of the double-buffered sets holds the kept output
+  float4* snap_s; float4* snap_n; uint32_t* kept; size_t snap_s_cap, snap_n_cap, kept_cap;                  // [n]
+  uint32_t* utri[2]; uint32_t* ulocal[2]; uint32_t* ublock[2]; size_t utri_cap[2], ulocal_cap[2], ublock_cap[2];
+  // ... and its workspace
+  uint8_t* changed; uint8_t* in_a; uint32_t* work; size_t changed_cap, in_a_cap, work_cap;                   // [n]
+  float* rows; float* reverse_r2; uint8_t* state; size_t rows_cap, reverse_r2_cap, state_cap;                // [n + ghosts]
+  float* reverse_rows; size_t reverse_rows_cap; uint32_t* near_bits;                                         // the coarse filter
+  uint32_t* reverse_idx; float* reverse_d2; int32_t* reverse_count; size_t ridx_cap, rd2_cap, rcount_cap;     // [n + ghosts]
+  smx_nn reverse_nn;                                             // the index of the reverse test
+  hipEvent_t uev[8];
+  bool utimed;
 };
 
 int mesh_workspace_create(MeshWorkspace** out) {
@@ -267,6 +482,7 @@ int mesh_workspace_create(MeshWorkspace** out) {
   *out = w;
   SMX_HIP(hipMalloc(reinterpret_cast<void**>(&w->stat), kStWords * sizeof(uint32_t)));
   for (int i = 0; i < 5; ++i) SMX_HIP(hipEventCreate(&w->ev[i]));
+  for (int i = 0; i < 8; ++i) SMX_HIP(hipEventCreate(&w->uev[i]));
   return SMX_OK;
 }
 
@@ -275,6 +491,8 @@ void mesh_workspace_destroy(MeshWorkspace* w) {
   void* ptrs[] = {w->lists, w->d2, w->counts, w->r2, w->meta, w->local_off, w->rings, w->block_sums, w->block_off, w->tri, w->stat};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 5; ++i) if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
+  (void)mesh_update_reset(w);
+  for (int i = 0; i < 8; ++i) if (w->uev[i]) (void)hipEventDestroy(w->uev[i]);
   delete w;
 }
 
@@ -305,6 +523,7 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
                      const float4* normal, size_t normal_stride, uint32_t n, const smx_mesh_params& p, uint32_t* triangles,
                      uint32_t capacity, int32_t on_device, uint32_t* n_triangles, smx_mesh_stats* stats) {
   SMX_HIP(hipEventRecord(w->ev[1], st));   // (the index is built)
+  w->have = false;                         // (the rings are shared with smx_recon_triangulate_update: its kept state is gone)
   *n_triangles = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n == 0) return SMX_OK;
@@ -338,11 +557,12 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
   if (rc != SMX_OK) return rc;
   SMX_HIP(hipEventRecord(w->ev[2], st));
   const unsigned star_grid = (unsigned)std::min<uint32_t>((uint32_t)div_up(n, kWaves), 16384u);
-  hipLaunchKernelGGL(k_mesh_star, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists, w->counts, w->rings, w->meta, w->stat);
+  hipLaunchKernelGGL(k_mesh_star<false>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists, w->counts, w->rings, w->meta, w->stat,
+                     MeshU{});
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(w->ev[3], st));
-  hipLaunchKernelGGL(k_mesh_agree<false>, dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off, w->block_sums,
-                     nullptr, nullptr, 0u, w->stat);
+  hipLaunchKernelGGL((k_mesh_agree<false, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off,
+                     w->block_sums, nullptr, nullptr, 0u, w->stat, MeshU{});
   hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
   SMX_LAUNCH_CHECK();
   uint32_t h[kStWords];
@@ -369,8 +589,8 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
       if (rc != SMX_OK) return rc;
       dst = w->tri;
     }
-    hipLaunchKernelGGL(k_mesh_agree<true>, dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off, nullptr,
-                       w->block_off, dst, T, nullptr);
+    hipLaunchKernelGGL((k_mesh_agree<true, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off, nullptr,
+                       w->block_off, dst, T, nullptr, MeshU{});
     SMX_LAUNCH_CHECK();
     if (!on_device) SMX_HIP(hipMemcpyAsync(triangles, dst, (size_t)T * 12, hipMemcpyDeviceToHost, st));
   }
@@ -378,6 +598,259 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
   SMX_HIP(hipStreamSynchronize(st));
   w->timed = true;
   return SMX_OK;
+}
+
+int mesh_update_reset(MeshWorkspace* w) {
+  if (!w) return SMX_OK;
+  w->have = false; w->utimed = false; w->n_prev = 0; w->t_prev = 0;
+  void** ptrs[] = {(void**)&w->snap_s, (void**)&w->snap_n, (void**)&w->kept, (void**)&w->utri[0], (void**)&w->utri[1],
+                   (void**)&w->ulocal[0], (void**)&w->ulocal[1], (void**)&w->ublock[0], (void**)&w->ublock[1], (void**)&w->changed,
+                   (void**)&w->in_a, (void**)&w->work, (void**)&w->rows, (void**)&w->reverse_r2, (void**)&w->state,
+                   (void**)&w->reverse_idx, (void**)&w->reverse_d2, (void**)&w->reverse_count, (void**)&w->reverse_rows,
+                   (void**)&w->near_bits};
+  for (void** p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
+  size_t* caps[] = {&w->snap_s_cap, &w->snap_n_cap, &w->kept_cap, &w->utri_cap[0], &w->utri_cap[1], &w->ulocal_cap[0],
+                    &w->ulocal_cap[1], &w->ublock_cap[0], &w->ublock_cap[1], &w->changed_cap, &w->in_a_cap, &w->work_cap,
+                    &w->rows_cap, &w->reverse_r2_cap, &w->state_cap, &w->ridx_cap, &w->rd2_cap, &w->rcount_cap, &w->reverse_rows_cap};
+  for (size_t* c : caps) *c = 0;
+  if (w->reverse_nn) { (void)smx_nn_destroy(w->reverse_nn); w->reverse_nn = nullptr; }
+  return SMX_OK;
+}
+
+int mesh_update_phase_ms(MeshWorkspace* w, float out_ms[6]) {
+  for (int i = 0; i < 6; ++i) out_ms[i] = 0.0f;
+  if (!w || !w->utimed) return SMX_OK;
+  float d[7];
+  for (int i = 0; i < 7; ++i) SMX_HIP(hipEventElapsedTime(&d[i], w->uev[i], w->uev[i + 1]));
+  // stamps: diff | reverse index build | reverse query and work list | index build over the map | lists | stars | agreement
+  out_ms[0] = d[0]; out_ms[1] = d[1] + d[3]; out_ms[2] = d[2]; out_ms[3] = d[4]; out_ms[4] = d[5]; out_ms[5] = d[6];
+  return SMX_OK;
+}
+
+namespace {
+bool same_params(const smx_mesh_params& a, const smx_mesh_params& b) {
+  return a.max_angle_between_normals_deg == b.max_angle_between_normals_deg && a.min_triangle_angle_deg == b.min_triangle_angle_deg &&
+         a.max_triangle_angle_deg == b.max_triangle_angle_deg && a.search_radius_factor == b.search_radius_factor &&
+         a.max_neighbors == b.max_neighbors && a.max_star_degree == b.max_star_degree;
+}
+}  // namespace
+
+int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn nn, float cell_size, const float4* smooth,
+                            size_t smooth_stride, const float4* normal, size_t normal_stride, uint32_t n,
+                            const smx_mesh_params& p, float full_above_fraction, MeshSubsetLists lists, void* lists_ctx,
+                            uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
+                            smx_mesh_stats* stats, smx_mesh_update_stats* update_stats) {
+  w->utimed = false;
+  SMX_HIP(hipEventRecord(w->uev[0], st));
+  *n_triangles = 0;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  smx_mesh_update_stats us;
+  memset(&us, 0, sizeof(us));
+  us.mode = !w->have ? 1u : !same_params(p, w->prm) ? 2u : n < w->n_prev ? 3u : 0u;
+  if (update_stats) *update_stats = us;
+  if (n == 0) {
+    w->have = false;
+    return smx_nn_build(nn, (smx_stream)st, nullptr, nullptr, nullptr, 0, cell_size, 1);
+  }
+  const float fraction = full_above_fraction < 0.0f ? kMeshUpdateDefaultFullAboveFraction : full_above_fraction;
+  const uint32_t n_prev = us.mode == 0 ? w->n_prev : 0u;   // (the full path: every slot is changed, nothing was live)
+  const int K = p.max_neighbors;
+  const uint32_t nb = (uint32_t)div_up(n, kBlock);
+  const int nw = w->cur ^ 1;                               // the set this call writes
+  w->have = false;                                         // (until this call has gone through)
+  int rc = grow_keep(&w->rings, &w->rings_cap, (size_t)n * kMeshMaxStarDegree, (size_t)n_prev * kMeshMaxStarDegree, st);
+  if (rc == SMX_OK) rc = grow_keep(&w->meta, &w->meta_cap, (size_t)n, (size_t)n_prev, st);
+  if (rc == SMX_OK) rc = grow_keep(&w->kept, &w->kept_cap, (size_t)n, (size_t)n_prev, st);
+  if (rc == SMX_OK) rc = grow_keep(&w->snap_s, &w->snap_s_cap, (size_t)n, (size_t)n_prev, st);
+  if (rc == SMX_OK) rc = grow_keep(&w->snap_n, &w->snap_n_cap, (size_t)n, (size_t)n_prev, st);
+  if (rc == SMX_OK) rc = grow(&w->r2, &w->r2_cap, (size_t)n);
+  if (rc == SMX_OK) rc = grow(&w->changed, &w->changed_cap, (size_t)n);
+  if (rc == SMX_OK) rc = grow(&w->in_a, &w->in_a_cap, (size_t)n);
+  if (rc == SMX_OK) rc = grow(&w->work, &w->work_cap, (size_t)n);
+  if (rc == SMX_OK) rc = grow(&w->block_sums, &w->sums_cap, (size_t)nb);
+  if (rc == SMX_OK) rc = grow(&w->block_off, &w->off_cap, (size_t)nb);
+  if (rc == SMX_OK) rc = grow(&w->ulocal[nw], &w->ulocal_cap[nw], (size_t)n);
+  if (rc == SMX_OK) rc = grow(&w->ublock[nw], &w->ublock_cap[nw], (size_t)nb);
+  if (rc != SMX_OK) return rc;
+  MeshK k;
+  k.smooth = smooth; k.smooth_stride = smooth_stride; k.normal = normal; k.normal_stride = normal_stride;
+  k.n = n; k.K = K;
+  const double rad = 3.14159265358979323846 / 180.0;
+  k.cos_max_normal = (float)std::cos((double)p.max_angle_between_normals_deg * rad);
+  k.cos_min_angle = (float)std::cos((double)p.min_triangle_angle_deg * rad);
+  k.cos_max_angle = (float)std::cos((double)p.max_triangle_angle_deg * rad);
+  const float f2 = p.search_radius_factor * p.search_radius_factor;
+  uint32_t h[kStWords];
+  auto read_stat = [&]() -> int {
+    SMX_HIP(hipMemcpyAsync(h, w->stat, sizeof(h), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+    return SMX_OK;
+  };
+
+  // ---- diff: changed bytes, ghost count, live count; then the rows, the reverse test's inputs and the new snapshot
+  MeshDiff d;
+  memset(&d, 0, sizeof(d));
+  d.n_prev = n_prev; d.snap_s = w->snap_s; d.snap_n = w->snap_n; d.changed = w->changed;
+  SMX_HIP(hipMemsetAsync(w->stat, 0, kStWords * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_mesh_diff<false>, dim3(nb), dim3(kBlock), 0, st, k, d, w->block_sums, nullptr, w->stat);
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
+  SMX_LAUNCH_CHECK();
+  if ((rc = read_stat()) != SMX_OK) return rc;
+  const uint32_t n_live = h[kStLive], n_changed = h[kStChanged], n_ghosts = h[kStTotal];
+  const size_t M = (size_t)n + n_ghosts;
+  rc = grow(&w->rows, &w->rows_cap, 3 * M);
+  if (rc == SMX_OK) rc = grow(&w->reverse_r2, &w->reverse_r2_cap, M);
+  if (rc == SMX_OK) rc = grow(&w->state, &w->state_cap, M);
+  if (rc != SMX_OK) return rc;
+  d.rows = w->rows; d.row_len = M; d.reverse_r2 = w->reverse_r2; d.state = w->state; d.r2 = w->r2;
+  const bool reverse = us.mode == 0 && n_changed > 0;
+  constexpr size_t kNearWords = (size_t)1 << (kMeshNearBitsLog2 - 5);
+  if (reverse) {
+    if (!w->near_bits) SMX_HIP(hipMalloc(reinterpret_cast<void**>(&w->near_bits), kNearWords * sizeof(uint32_t)));
+    SMX_HIP(hipMemsetAsync(w->near_bits, 0, kNearWords * sizeof(uint32_t), st));
+    d.near_bits = w->near_bits; d.inv_h = 1.0f / cell_size;
+  }
+  hipLaunchKernelGGL(k_mesh_diff<true>, dim3(nb), dim3(kBlock), 0, st, k, d, nullptr, w->block_off, w->stat);
+  SMX_LAUNCH_CHECK();
+  SMX_HIP(hipEventRecord(w->uev[1], st));
+  us.n_changed = n_changed;
+
+  // ---- nothing changed: the kept array is the answer
+  if (us.mode == 0 && n_changed == 0) {
+    for (int e = 2; e <= 3; ++e) SMX_HIP(hipEventRecord(w->uev[e], st));
+    rc = smx_nn_build(nn, (smx_stream)st, w->rows, w->rows + M, w->rows + 2 * M, n, cell_size, 1);
+    if (rc != SMX_OK) return rc;
+    for (int e = 4; e <= 6; ++e) SMX_HIP(hipEventRecord(w->uev[e], st));
+    const uint32_t T = w->t_prev;
+    us.n_kept_triangles = T;
+    *n_triangles = T;
+    if (stats) *stats = w->last_stats;
+    if (update_stats) *update_stats = us;
+    w->have = true;
+    int out_rc = SMX_OK;
+    if (capacity < T) {
+      set_error("triangles holds %u entries, the mesh has %u", capacity, T);
+      out_rc = SMX_ERR_INVALID_ARGUMENT;
+    } else if (T > 0) {
+      SMX_HIP(hipMemcpyAsync(triangles, w->utri[w->cur], (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    }
+    SMX_HIP(hipEventRecord(w->uev[7], st));
+    SMX_HIP(hipStreamSynchronize(st));
+    w->utimed = true;
+    return out_rc;
+  }
+
+  // ---- reverse test: which unchanged live slots have a changed point, or the kept position of one, in their ball
+  if (us.mode == 0) {
+    if (!w->reverse_nn) { rc = smx_nn_create(device, &w->reverse_nn); if (rc != SMX_OK) return rc; }
+    rc = grow(&w->reverse_idx, &w->ridx_cap, M);
+    if (rc == SMX_OK) rc = grow(&w->reverse_d2, &w->rd2_cap, M);
+    if (rc == SMX_OK) rc = grow(&w->reverse_count, &w->rcount_cap, M);
+    if (rc == SMX_OK) rc = grow(&w->reverse_rows, &w->reverse_rows_cap, 3 * M);
+    if (rc != SMX_OK) return rc;
+    // (a ball of radius <= cell_size / 2 stays within the 27 cells around its centre's)
+    hipLaunchKernelGGL(k_mesh_reverse_rows, dim3((unsigned)std::min<size_t>((size_t)div_up((long long)M, kBlock), 8192)), dim3(kBlock), 0, st,
+                       n, M, w->rows, w->reverse_rows, w->changed, w->reverse_r2, f2, 1.0f / cell_size, 0.25f * cell_size * cell_size,
+                       w->near_bits, w->stat);
+    SMX_LAUNCH_CHECK();
+    rc = smx_nn_build(w->reverse_nn, (smx_stream)st, w->reverse_rows, w->reverse_rows + M, w->reverse_rows + 2 * M, (uint32_t)M,
+                      cell_size, 1);
+    if (rc != SMX_OK) return rc;
+  }
+  SMX_HIP(hipEventRecord(w->uev[2], st));
+  auto count_work = [&](int32_t all) -> int {
+    hipLaunchKernelGGL(k_mesh_worklist<false>, dim3(nb), dim3(kBlock), 0, st, n, w->changed, all ? nullptr : w->reverse_count, all,
+                       w->block_sums, nullptr, nullptr);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
+    SMX_LAUNCH_CHECK();
+    return read_stat();
+  };
+  uint32_t n_work = n;
+  if (us.mode == 0) {
+    // (the index holds the changed points and the ghosts for this query: unchanged points carry state 1 and are skipped)
+    rc = smx_nn_query_self(w->reverse_nn, (smx_stream)st, w->reverse_r2, f2, 1, w->state, 1, w->reverse_idx, w->reverse_d2,
+                           w->reverse_count);
+    if (rc != SMX_OK) return rc;
+    if ((rc = count_work(0)) != SMX_OK) return rc;
+    n_work = h[kStTotal];
+    us.n_dirty = n_work;
+    if ((double)n_work > (double)fraction * (double)n) us.mode = 4;
+  }
+  const bool incremental = us.mode == 0;
+  if (!incremental) {
+    if ((rc = count_work(1)) != SMX_OK) return rc;
+    n_work = n;
+    if (us.mode != 4) us.n_dirty = n;
+  }
+  hipLaunchKernelGGL(k_mesh_worklist<true>, dim3(nb), dim3(kBlock), 0, st, n, w->changed, incremental ? w->reverse_count : nullptr,
+                     incremental ? 0 : 1, nullptr, w->block_off, w->work);
+  SMX_LAUNCH_CHECK();
+  SMX_HIP(hipEventRecord(w->uev[3], st));
+
+  // ---- the caller's index over the map, and the candidate lists of the work list
+  rc = smx_nn_build(nn, (smx_stream)st, w->rows, w->rows + M, w->rows + 2 * M, n, cell_size, 1);
+  if (rc != SMX_OK) return rc;
+  SMX_HIP(hipEventRecord(w->uev[4], st));
+  rc = grow(&w->lists, &w->lists_cap, (size_t)n_work * K);
+  if (rc == SMX_OK) rc = grow(&w->d2, &w->d2_cap, (size_t)n_work * K);
+  if (rc == SMX_OK) rc = grow(&w->counts, &w->counts_cap, (size_t)n_work);
+  if (rc != SMX_OK) return rc;
+  if (n_work > 0) {
+    if (incremental) rc = lists(lists_ctx, st, nn, w->work, n_work, f2, K, w->lists, w->d2, w->counts);
+    else rc = smx_nn_query_self(nn, (smx_stream)st, w->r2, f2, K, nullptr, 0, w->lists, w->d2, w->counts);
+    if (rc != SMX_OK) return rc;
+  }
+  SMX_HIP(hipEventRecord(w->uev[5], st));
+
+  // ---- stars of the work list; A = D + old rings + new rings
+  MeshU u;
+  memset(&u, 0, sizeof(u));
+  u.work = w->work; u.n_work = n_work; u.n_prev = n_prev; u.in_a = w->in_a; u.kept = w->kept;
+  u.prev_tri = w->utri[w->cur]; u.prev_local = w->ulocal[w->cur]; u.prev_block = w->ublock[w->cur];
+  SMX_HIP(hipMemsetAsync(w->in_a, 0, (size_t)n, st));
+  if (n_work > 0) {
+    const unsigned star_grid = (unsigned)std::min<uint32_t>((uint32_t)div_up(n_work, kWaves), 16384u);
+    hipLaunchKernelGGL(k_mesh_star<true>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists, w->counts, w->rings, w->meta, w->stat, u);
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_HIP(hipEventRecord(w->uev[6], st));
+
+  // ---- agreement: count, scan, write into the other output set
+  SMX_HIP(hipMemsetAsync(w->stat, 0, kStWords * sizeof(uint32_t), st));
+  hipLaunchKernelGGL((k_mesh_agree<false, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->ulocal[nw], w->block_sums,
+                     nullptr, nullptr, 0u, w->stat, u);
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->ublock[nw], w->stat);
+  SMX_LAUNCH_CHECK();
+  if ((rc = read_stat()) != SMX_OK) return rc;
+  const uint32_t T = h[kStTotal];
+  smx_mesh_stats ms;
+  ms.n_live = n_live; ms.n_star_triangles = h[kStStar]; ms.n_triangles = T;
+  ms.star_overflow = h[kStOverflow]; ms.truncated_lists = h[kStTruncated];
+  us.n_reagreed = h[kStReagreed]; us.n_kept_triangles = h[kStKept];
+  rc = grow(&w->utri[nw], &w->utri_cap[nw], (size_t)3 * T);
+  if (rc != SMX_OK) return rc;
+  if (T > 0) {
+    hipLaunchKernelGGL((k_mesh_agree<true, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->ulocal[nw], nullptr,
+                       w->ublock[nw], w->utri[nw], T, nullptr, u);
+    SMX_LAUNCH_CHECK();
+  }
+  // (the state has advanced, whether or not the caller's buffer holds the result)
+  w->cur = nw; w->n_prev = n; w->t_prev = T; w->prm = p; w->last_stats = ms; w->have = true;
+  *n_triangles = T;
+  if (stats) *stats = ms;
+  if (update_stats) *update_stats = us;
+  int out_rc = SMX_OK;
+  if (capacity < T) {
+    if (triangles != nullptr || capacity != 0) set_error("triangles holds %u entries, the mesh has %u", capacity, T);
+    else set_error("count only: the mesh has %u triangles", T);
+    out_rc = SMX_ERR_INVALID_ARGUMENT;
+  } else if (T > 0) {
+    SMX_HIP(hipMemcpyAsync(triangles, w->utri[nw], (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  }
+  SMX_HIP(hipEventRecord(w->uev[7], st));
+  SMX_HIP(hipStreamSynchronize(st));
+  w->utimed = true;
+  return out_rc;
 }
 
 }  // namespace smx

@@ -143,6 +143,38 @@ SMX_MESH_FN int mesh_triangle_filter(const MeshVec& P, const MeshVec& A, const M
   return flip ? 2 : 1;
 }
 
+// The changed-predicate of smx_recon_triangulate_update.  A slot's seven words, in the order smooth x, y,
+// z, RadiusSquared, normal x, y, z, are compared BITWISE with the kept snapshot: a NaN equals itself, -0 differs from +0
+// (conservative: a slot found changed is only recomputed).  Slots at or past the kept slot count are changed.
+SMX_MESH_FN uint32_t mesh_word_bits(float v) {
+  uint32_t u;
+  __builtin_memcpy(&u, &v, sizeof(u));
+  return u;
+}
+SMX_MESH_FN bool mesh_slot_changed(uint32_t slot, uint32_t n_prev, const float now[7], const float kept[7]) {
+  if (slot >= n_prev) return true;
+  uint32_t differs = 0;
+  for (int t = 0; t < 7; ++t) differs |= mesh_word_bits(now[t]) ^ mesh_word_bits(kept[t]);
+  return differs != 0;
+}
+
+// The coarse filter in front of the update's reverse test: a bit table over cells of edge h, hashed.  Changed points and
+// ghosts set the bit of their cell; an unchanged slot whose ball has radius <= h / 2 can only reach a point in one of the
+// 27 cells around its own, so if none of those bits is set it is left out of the reverse test.  Collisions only let more
+// slots through.  A coordinate whose cell index does not fit (|x / h| >= 2^20) gives false: the caller then does not filter.
+constexpr int kMeshNearBitsLog2 = 27;    // 16 MiB of bits
+SMX_MESH_FN bool mesh_coarse_cell(float x, float y, float z, float inv_h, int* ix, int* iy, int* iz) {
+  const float cx = x * inv_h, cy = y * inv_h, cz = z * inv_h;
+  if (!(fabsf(cx) < 1048576.0f && fabsf(cy) < 1048576.0f && fabsf(cz) < 1048576.0f)) return false;
+  *ix = (int)floorf(cx); *iy = (int)floorf(cy); *iz = (int)floorf(cz);
+  return true;
+}
+SMX_MESH_FN uint32_t mesh_coarse_bit(int ix, int iy, int iz) {
+  uint32_t h = (uint32_t)ix * 73856093u ^ (uint32_t)iy * 19349663u ^ (uint32_t)iz * 83492791u;
+  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
+  return h & ((1u << kMeshNearBitsLog2) - 1u);
+}
+
 #if !defined(SMX_MESH_HOST_ONLY)
 // ---- part 2: the interface between smx_recon.hip (owner of the map) and smx_mesh.hip (owner of the kernels) ----
 struct MeshWorkspace;   // lists, rings, counts, output staging, statistics, timed events; grows on demand, reused
@@ -158,6 +190,20 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
 // stamps of the last call: before the index build, and after each of build / list query / star / agreement+write
 int mesh_stamp_begin(MeshWorkspace* w, hipStream_t st);
 int mesh_phase_ms(MeshWorkspace* w, float out_ms[4]);
+
+// smx_recon_triangulate_update.  The kept state lives in the workspace.  `lists` fills the candidate lists
+// of a device list of slots from `nn` (the owner of the map does that: smx_recon_neighbor_candidates' route).  `nn` is
+// (re)built over the map here, from the rows the diff kernel writes (merged slots are NaN rows, as k_index_rows makes them).
+typedef int (*MeshSubsetLists)(void* ctx, hipStream_t st, smx_nn nn, const uint32_t* slots, uint32_t n_slots, float factor_squared,
+                               int K, uint32_t* out_idx, float* out_d2, int32_t* out_count);
+constexpr float kMeshUpdateDefaultFullAboveFraction = 0.2f;
+int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn nn, float cell_size, const float4* smooth,
+                            size_t smooth_stride, const float4* normal, size_t normal_stride, uint32_t n,
+                            const smx_mesh_params& p, float full_above_fraction, MeshSubsetLists lists, void* lists_ctx,
+                            uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
+                            smx_mesh_stats* stats, smx_mesh_update_stats* update_stats);
+int mesh_update_reset(MeshWorkspace* w);
+int mesh_update_phase_ms(MeshWorkspace* w, float out_ms[6]);
 #endif
 
 }  // namespace smx

@@ -4891,6 +4891,49 @@ int smx_recon_debug_mesh_timings(smx_recon r, float out_ms[4]) {
 }
 
 namespace {
+// the candidate lists of a device list of slots, by the route of smx_recon_neighbor_candidates
+int mesh_subset_lists(void* ctx, hipStream_t st, smx_nn nn, const uint32_t* slots, uint32_t n_slots, float factor_squared, int K,
+                      uint32_t* out_idx, float* out_d2, int32_t* out_count) {
+  return smx_recon_neighbor_candidates(static_cast<smx_recon>(ctx), (smx_stream)st, nn, slots, n_slots, factor_squared, K, nullptr,
+                                       0, 1, out_idx, out_d2, out_count, 1);
+}
+}  // namespace
+
+int smx_recon_triangulate_update(smx_recon r, smx_stream s, smx_nn nn, float cell_size, const smx_mesh_params* p,
+                                 float full_above_fraction, uint32_t* triangles, uint32_t capacity, int32_t on_device,
+                                 uint32_t* n_triangles, smx_mesh_stats* stats, smx_mesh_update_stats* update_stats) {
+  SMX_CHECK_ARG(r != nullptr && nn != nullptr && p != nullptr && n_triangles != nullptr && cell_size > 0);
+  SMX_CHECK_ARG(triangles != nullptr || capacity == 0);
+  SMX_CHECK_ARG(full_above_fraction < 0.0f || full_above_fraction <= 1.0f);
+  { const int rcp = mesh_check_params(*p); if (rcp != SMX_OK) return rcp; }
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  if (!r->mesh) { const int rcw = mesh_workspace_create(&r->mesh); if (rcw != SMX_OK) return rcw; }
+  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  uint32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
+  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
+  return mesh_triangulate_update(r->mesh, r->device, st, nn, cell_size, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0,
+                                 r->S.quad(kGroupN, 1) - n0, n, *p, full_above_fraction, mesh_subset_lists, r, triangles,
+                                 capacity, on_device, n_triangles, stats, update_stats);
+}
+
+int smx_recon_triangulate_reset(smx_recon r) {
+  SMX_CHECK_ARG(r != nullptr);
+  SMX_ON_DEVICE(r->device);
+  SMX_HIP(hipDeviceSynchronize());
+  return mesh_update_reset(r->mesh);
+}
+
+int smx_recon_debug_mesh_update_timings(smx_recon r, float out_ms[6]) {
+  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
+  SMX_ON_DEVICE(r->device);
+  return mesh_update_phase_ms(r->mesh, out_ms);
+}
+
+namespace {
 // stage times of one stamp record (ms); false if the record is not that call's or the call did not get through
 bool stage_ms_from_stamps(const unsigned long long* t, unsigned long long seq, int khz, float out_ms[7]) {
   // (a call whose second half was left out -- smx_recon_debug_set_skip front-only -- has no integration stamp: the stages that

@@ -3,9 +3,18 @@
     from surfelmeshing_amd import meshing
     triangles, stats = meshing.mesh_map(rec)                       # [T,3] uint32 slot indices
     export.SaveMeshAsOBJ(rec, "map.obj", triangles=triangles)
+
+Following the map while it grows (smx_recon_triangulate_update) -- the same triangles, recomputed only where
+the map changed:
+
+    mesher = meshing.MapMesher(rec)
+    for every few frames: triangles, stats, update_stats = mesher.update()
 """
 from ._lib import MeshParams as _MeshParamsPOD
 
+UPDATE_STAT_NAMES = ("mode", "n_changed", "n_dirty", "n_reagreed", "n_kept_triangles")
+UPDATE_MODES = ("incremental", "full: no state", "full: parameters differ", "full: fewer slots than kept",
+                "full: dirty fraction above the limit")
 STAT_NAMES = ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")
 
 
@@ -40,3 +49,40 @@ def mesh_map(rec, params=None, stream=None, index=None, cell_size=None):
     smx_mesh_params POD, or None for the defaults.  Returns (triangles [T,3] uint32, stats dict)."""
     pod = params.to_pod() if isinstance(params, MeshParams) else params
     return rec.Triangulate(stream, pod, index=index, cell_size=cell_size)
+
+
+class MapMesher:
+    """Keeps the mesh of `rec`'s map up to date.  Owns the neighbour index; update() returns what mesh_map would return
+    on the map as it stands, plus the update statistics, and keeps the triangles in .triangles / .stats."""
+
+    def __init__(self, rec, params=None, cell_size=None, full_above_fraction=None):
+        from .api import SurfelNeighborIndex
+        self._rec = rec
+        self._pod = params.to_pod() if isinstance(params, MeshParams) else params
+        self._cell_size = cell_size
+        self._fraction = full_above_fraction
+        self._index = SurfelNeighborIndex(rec._device_id)
+        self.triangles, self.stats, self.update_stats = None, None, None
+
+    @property
+    def index(self):
+        """The neighbour index, built over the map as of the last update()."""
+        return self._index
+
+    def update(self, stream=None):
+        self.triangles, self.stats, self.update_stats = self._rec.TriangulateUpdate(
+            stream, self._pod, index=self._index, cell_size=self._cell_size, full_above_fraction=self._fraction)
+        return self.triangles, self.stats, self.update_stats
+
+    def timings(self):
+        return self._rec.debug_mesh_update_timings()
+
+    def reset(self):
+        """Drops the kept state (and its device memory); the next update() runs the full path."""
+        self._rec.ResetTriangulation()
+        self.triangles, self.stats, self.update_stats = None, None, None
+
+    def close(self):
+        if self._index is not None:
+            self._index.close()
+            self._index = None

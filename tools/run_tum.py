@@ -3,9 +3,12 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
       python tools/run_tum.py <dataset_folder> [--trajectory groundtruth.txt] [--export_mesh out.obj]
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
                               [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
-                              [--mesh] ...
+                              [--mesh] [--mesh_every N [--mesh_check]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
+With --mesh_every N the mesh follows the map instead: every N integrated frames smx_recon_triangulate_update recomputes it
+where the map changed (one line per update: mode, counts, milliseconds); --export_mesh then writes the last update, made
+after the last frame.  --mesh_check triangulates once more at the end with the full call and fails if the two differ.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.
@@ -135,6 +138,10 @@ def main():
                     help="at the end, render one view from outside the map's bounds looking at its centre")
     ap.add_argument("--mesh", action="store_true",
                     help="triangulate the final map on the device; --export_mesh then writes the faces as well")
+    ap.add_argument("--mesh_every", type=int, default=0,
+                    help="keep the mesh up to date: update it every N integrated frames and after the last one (0 = never)")
+    ap.add_argument("--mesh_check", action="store_true",
+                    help="with --mesh_every: compare the last update with one full triangulation, exit 1 if they differ")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -174,6 +181,19 @@ def main():
     pipe = FramePipeline(cam.width(), cam.height(), fx, fy, cx, cy, args.max_surfel_count, pre)
     half = args.outlier_filtering_frame_count // 2
     n = min(video.frame_count(), args.end_frame)
+    mesher = None
+    if args.mesh_every > 0:
+        from surfelmeshing_amd import meshing
+        mesher = meshing.MapMesher(pipe.reconstruction)
+
+    def update_mesh(frames_done):
+        t = time.time()
+        tri, st, us = mesher.update()
+        ph = mesher.timings()
+        print("mesh update after %d frames: %s; changed %d, dirty %d, reagreed %d, kept %d triangles of %d; %.2f ms "
+              "(device phases %.2f ms)" % (frames_done, meshing.UPDATE_MODES[us["mode"]], us["n_changed"], us["n_dirty"],
+                                           us["n_reagreed"], us["n_kept_triangles"], tri.shape[0], 1e3 * (time.time() - t),
+                                           sum(ph.values())), flush=True)
     uploaded = set()
     t0 = time.time()
     done = 0
@@ -201,6 +221,8 @@ def main():
             compactions, removed = compactions + 1, removed + before - after
         pipe.process(f, others, T, G)
         done += 1
+        if mesher is not None and done % args.mesh_every == 0:
+            update_mesh(done)
         if args.render_dir and args.render_every > 0 and done % args.render_every == 0:
             write_render(args, pipe.reconstruction, cam, G, f, "render_%06d.png" % f)
         old = f - half - 1                                                                      # main.cc:1226-1240
@@ -216,7 +238,18 @@ def main():
     if args.render_dir and args.render_overview:
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png")
     triangles = None
-    if args.mesh:
+    if mesher is not None:
+        update_mesh(done)                         # (nothing changed since the last one: the kept array)
+        triangles = mesher.triangles
+        if args.mesh_check:
+            want, want_stats = meshing.mesh_map(rec)
+            same = want.tobytes() == triangles.tobytes() and want_stats == mesher.stats
+            print("mesh check: the last update %s the full triangulation (%d triangles)" % (
+                "equals" if same else "DIFFERS FROM", want.shape[0]))
+            if not same:
+                sys.exit(1)
+        mesher.close()
+    elif args.mesh:
         from surfelmeshing_amd import meshing
         t1 = time.time()
         triangles, mesh_stats = meshing.mesh_map(rec)
