@@ -47,6 +47,13 @@ void set_error(const char* fmt, ...);
     }                                                                                  \
   } while (0)
 
+// For calls that return an smx status themselves: evaluate once, return the code from the enclosing function unless SMX_OK.
+#define SMX_CALL(expr)                                                                 \
+  do {                                                                                 \
+    const int rc__ = (expr);                                                           \
+    if (rc__ != SMX_OK) return rc__;                                                   \
+  } while (0)
+
 // Objects (smx_recon, smx_nn) remember the device they were created on and make it the calling thread's current
 // device for the duration of every entry point, so that one process can drive one object per GPU from one thread
 // per GPU -- or from a single thread -- without calling smx_set_device between the calls.  The

@@ -1347,7 +1347,7 @@ extern "C" {
 int smx_nn_create(int32_t device_id, smx_nn* out) {
   SMX_CHECK_ARG(out != nullptr);
   int device = 0;
-  { const int rcd = resolve_device(device_id, &device); if (rcd != SMX_OK) return rcd; }
+  SMX_CALL(resolve_device(device_id, &device));
   SMX_ON_DEVICE(device);
   smx_nn_s* nn = new smx_nn_s();
   memset(nn, 0, sizeof(*nn));

@@ -1,8 +1,10 @@
-// smx_recon.hip -- the surfel reconstruction object and its gfx950 kernels.
+// smx_recon.hip -- the surfel reconstruction object's frame loop and its gfx950 kernels.
 //
-// Behaviour: CUDASurfelReconstruction::Integrate / Regularize / TransferAllToCPU /
-// ExportVertices of the reference (APP/cuda_surfel_reconstruction.{h,cc},
+// Behaviour: CUDASurfelReconstruction::Integrate / Regularize / GetTimings of the
+// reference (APP/cuda_surfel_reconstruction.{h,cc},
 // APP/cuda_surfel_reconstruction_kernels.{cc,cu}); cited per kernel below.
+// The object itself and the surfel layout are in smx_recon_state.hpp; TransferAllToCPU,
+// ExportVertices and the other services on the finished map are in smx_recon_map.hip.
 //
 // Structure (DESIGN.md "Frame pipeline") -- this is NOT the reference's launch
 // sequence.  The reference scans all N surfel slots in every surfel kernel
@@ -33,92 +35,13 @@
 #include <atomic>
 #include <vector>
 
-#include "smx_common.hpp"
-#include "smx_track.hpp"
+#include "smx_recon_state.hpp"
 #include "smx_mesh.hpp"
 #include <hip/hip_ext.h>
 
 using namespace smx;
 
 namespace {
-
-// Attribute ids = the reference's SoA row numbers, APP/cuda_surfel_reconstruction_kernels.cuh:49-78 (the
-// storage itself is grouped differently, see Surfels below)
-enum : int {
-  kX = 0, kY = 1, kZ = 2, kSmoothX = 3, kSmoothY = 4, kSmoothZ = 5, kConfidence = 6, kRadiusSq = 7,
-  kNormalX = 8, kNormalY = 9, kNormalZ = 10, kGradX = 11, kGradY = 12, kGradZ = 13,
-  kCreationStamp = 17, kLastUpdateStamp = 18, kNeighbor0 = 19, kGradCount = 23, kColor = 24, kRows = 25
-};
-
-struct DevState {
-  uint32_t surfel_count;   // slots in use (incl. merged zombies)
-  uint32_t merge_count;
-  uint32_t create_base_next;  // slot count seen by k_new_flags_scan (which may run beside the previous frame's pass B)
-  uint32_t recent_count;   // statistics: slots inside the regulariser window
-  uint32_t create_base;
-  uint32_t new_count;
-  uint32_t capacity_clamped;
-  uint32_t n_visible, n_merged, n_edges, n_integrated, n_replaced, n_conflict_hits;
-  uint32_t n_window_edges, n_contributors;
-  uint32_t n_segments_skipped;
-  uint32_t reg_saturated;  // sticky: a regulariser term hit the +-16 m clamp or a sender-class counter came near its byte
-  uint32_t n_pairs, n_overflow_pairs, max_tile_pairs;   // statistics of the association tiles' bins
-};
-
-// HBM layout of the surfel attributes.  The reference keeps 25 separate rows (SoA, kernels.cuh:49-78); that is
-// ideal for its all-slot scans but makes every per-surfel gather touch one cache line per attribute.  Here
-// the attributes are grouped into six 16-byte records per slot, chosen by which kernels use them together,
-// and each group is its own array (group-major):
-//   P  X, Y, Z, LastUpdateStamp      -- exactly what pass A streams (16 B/slot), and what every projection needs
-//   S  SmoothX, SmoothY, SmoothZ, -   -- what the regulariser gathers per neighbour (one line instead of three)
-//   N  NormalX, NormalY, NormalZ, RadiusSquared
-//   T  Neighbor0..3                  -- what pass B streams (16 B/slot)
-//   C  Confidence, CreationStamp, Color, -
-//   G  GradientX, GradientY, GradientZ, -  (parked next smooth position)
-// (Rounds 1-2 kept a copy of T in the second half of a 32-byte S record, so that the regulariser could see with one
-// gather whether a neighbour lists the slot back; with the far-term bins nobody asks that question any more.)
-// The reference's row order only matters at the boundary (TransferAllToCPU, ExportVertices, the debug row
-// accessors); pack/unpack kernels convert there.  Rows 14-16 (Accum*, never used) and 23 (GradientCount,
-// replaced by the fixed-point accumulators) have no storage.
-enum : int { kGroupP = 0, kGroupS, kGroupN, kGroupT, kGroupC, kGroupG, kGroups };
-__host__ __device__ constexpr int row_group(int row) {
-  return row <= 2 ? kGroupP : row <= 5 ? kGroupS : row == 6 ? kGroupC : row == 7 ? kGroupN : row <= 10 ? kGroupN
-       : row <= 13 ? kGroupG : row <= 16 ? -1 : row == 17 ? kGroupC : row == 18 ? kGroupP : row <= 22 ? kGroupT
-       : row == 24 ? kGroupC : -1;
-}
-__host__ __device__ constexpr int row_sub(int row) {
-  return row <= 2 ? row : row <= 5 ? row - 3 : row == 6 ? 0 : row == 7 ? 3 : row <= 10 ? row - 8
-       : row <= 13 ? row - 11 : row == 17 ? 1 : row == 18 ? 3 : row <= 22 ? row - 19 : row == 24 ? 2 : -1;
-}
-// start of each group array in units of pitch x 16 bytes
-__host__ __device__ constexpr int group_start(int g) { return g; }
-constexpr int kQuadsPerSlot = 6;   // 96 bytes per slot
-#ifndef SMX_LAYOUT_NC
-#define SMX_LAYOUT_NC 0
-#endif
-struct Surfels {
-  float* base;
-  size_t pitch;  // slots per group array (multiple of 64)
-  __host__ __device__ __forceinline__ size_t quad(int g, uint32_t i) const {
-#if SMX_LAYOUT_NC
-    // (A/B, VERDICT r5 item 5: N and C of a slot side by side in one 32-byte record -- a visible slot costs the integration two
-    // lines instead of three -- P, S, T, G stay arrays of their own.  Measured: profiles/r6_ab_notes.md)
-    if (g == kGroupN) return (size_t)4 * pitch + 2 * (size_t)i;
-    if (g == kGroupC) return (size_t)4 * pitch + 2 * (size_t)i + 1;
-    return (size_t)(g == kGroupP ? 0 : g == kGroupS ? 1 : g == kGroupT ? 2 : 3) * pitch + (size_t)i;
-#else
-    return (size_t)group_start(g) * pitch + (size_t)i;
-#endif
-  }
-  __device__ __forceinline__ float& f(int row, uint32_t i) const { return base[quad(row_group(row), i) * 4 + row_sub(row)]; }
-  __device__ __forceinline__ uint32_t& u(int row, uint32_t i) const {
-    return reinterpret_cast<uint32_t*>(base)[quad(row_group(row), i) * 4 + row_sub(row)];
-  }
-  // whole 16-byte group of slot i
-  __device__ __forceinline__ float4* group(int g, uint32_t i) const { return reinterpret_cast<float4*>(base) + quad(g, i); }
-  __device__ __forceinline__ void set_neighbors(uint32_t i, const uint4& t) const { *reinterpret_cast<uint4*>(group(kGroupT, i)) = t; }
-  __device__ __forceinline__ void set_neighbor(uint32_t i, int q, uint32_t v) const { u(kNeighbor0 + q, i) = v; }
-};
 
 struct FrameCtx {
   Mat34 L;  // local_T_global
@@ -169,14 +92,6 @@ __device__ __forceinline__ void ts_begin(unsigned long long* ts, int k) {
 __device__ __forceinline__ void ts_end(unsigned long long* ts, int k, uint32_t block, uint32_t n_blocks) {
   if (ts && threadIdx.x == 0 && block < n_blocks && block + kTsTail >= n_blocks) atomicMax(&ts[k], (unsigned long long)wall_clock64());
 }
-
-struct Scratch {
-  uint32_t* supporting;
-  uint32_t* counts;
-  long long* depth_sums;
-  uint32_t* confl_key;
-  float* first_depth;
-};
 
 struct Proj { Vec3 g, l; float u, v; int px, py; };
 
@@ -247,79 +162,14 @@ __device__ __forceinline__ float meas_normal_z(float nx, float ny) {
   return -sqrtf(t > 0.f ? t : 0.f);
 }
 
-constexpr int kBlock = 256;
 static_assert(kBlock / 64 == 4, "pass A sums four wavefronts' marks");
 static_assert(sizeof(uchar3) == 3, "uchar3 must be packed like the reference's Vec3u8");
 
-// Work lists are SEGMENTED: the slots [s*kSeg, (s+1)*kSeg) are scanned by one workgroup, which writes the
-// indices it selects to list[s*kSeg ...] (ascending) and their number to seg[s].  No global counter, no
-// atomics, and the list order is deterministic.
-constexpr int kSeg = 1024;
-// Pass B uses larger segments (kSegB slots, one 1024-thread workgroup each): the in-segment regulariser sums
-// live in 128 KB of LDS, and the larger the segment the fewer edges leave it (image-row neighbours are a few
-// hundred slots apart), i.e. the fewer 64-bit global atomics remain.
-constexpr int kSegB = 1024;
-constexpr int kBlockB = kSegB / 4;
-// The non-empty 256-entry chunks of a segmented list, appended by the pass that builds the list: descriptor = chunk id
-// (segment * chunks-per-segment + sub-chunk) | (entries - 1) << 24.  The list kernels walk these instead of probing every
-// chunk of every segment: on the frame's binding cycle each dependent memory round trip costs microseconds, and a probe
-// that finds an empty chunk is one (profiles/r04_critical_cycle_notes.md).
-// The descriptors go to kSubLists INTERLEAVED sub-lists, each with a counter in a cache line of its own: walk step w is
-// entry w / kSubLists of sub-list w % kSubLists.  Rounds 1-3 had ONE list behind ONE counter: a returning atomic per
-// non-empty segment, 1 300 per launch of pass A at C2 and 5 400 at C3, all arriving within the same few microseconds at
-// the end of their workgroups' chains -- and atomics on one address retire at ~12 ns each, so the tail of the launch was
-// that queue.  Sixteen counters take a sixteenth each; the producers deal their segments round-robin, so the sub-lists
-// stay equally long up to the spread of the descriptors per segment, and a walk that covers kSubLists x the longest one
-// meets few empty steps.  A consumer still finds its first descriptor without waiting for any counter (its place does
-// not depend on them), which is what a prefix over the sub-lists would have cost.
-constexpr uint32_t kCountStride = 32;     // one counter per 128-byte line: atomics on one line serialise, whatever word they hit
-constexpr uint32_t kSubLists = 16;
 constexpr uint32_t kAccCount = 16;        // acc_chunks.count = rec_chunks.count + kAccCount: the second half of the same lines
-struct Chunks { uint32_t* desc; uint32_t* count; uint32_t stride; };   // desc[k * stride + j], count[k * kCountStride]
-struct Lists {
-  Chunks vis_chunks, rec_chunks;   // (vis_chunks: only the kSubLists counters = the lengths of the visible list's runs)
-  Chunks acc_chunks;      // segments the edge kernel has work in (descriptor = segment); its counters share rec_chunks' lines (kAccCount)
-  uint32_t* vis_list;     // slots that project into the image this frame: kSubLists dense runs, run k at k * vis_region (vis_*)
-  uint32_t vis_region;    // entries per run: every kSubLists-th surviving segment's slots at most
-  float* seg_box;         // per pass-A segment: min xyz, max xyz, covered slot count (u32), newest stamp (u32)
-  uint32_t* vis_seg;
-  uint8_t* seg_streak;      // per pass-A segment: in how many calls in a row pass A has culled it (k_scan_visible, step 2)
-  uint32_t* recent_list;  // slots whose last update stamp lies inside the regulariser window
-  uint32_t* recent_seg;
-  uint32_t* act_list;     // per pass-B segment: the slots the edge kernel has work for (ActEntry), ascending
-  uint8_t* flags8;        // per slot: bit 0 = stamp inside the regulariser window, bit 1 = detach request
-  uint8_t* dirty8;        // delta tracking (null = off): 1 = a transferred attribute of the slot changed since the
-                          // last smx_recon_transfer_changed_to_cpu
-  // "Hot" groups (pass B's filter for its far flag gathers, see k_neighbor_scan): per group of slots the number
-  // (mod 256) of the last Integrate call in which the group held a slot inside the regulariser window (pass A) or a
-  // flag byte / link record of it was written.  `epoch` = this call's number.  (At C2 a group is 2048 slots, at C3 8192.)
-  uint8_t* seg_act;       // per pass-A segment: 1 = pass A found visible or recently updated slots in it this frame
-  uint32_t descending;    // != 0: this call's all-slot kernels walk the segments downwards (segment_of_block)
-  uint8_t* hot_epoch;
-  uint16_t* seg_targets;  // per pass-B segment: bitmap of the groups its links point into (see k_neighbor_scan)
-  uint32_t n_hot_groups;
-  uint32_t epoch;
-  int hot_shift;          // slots per group = 1 << hot_shift: the smallest power of two >= 1024 that keeps the table <= 4 KB
-};
 constexpr int kMaxHotGroups = 4096;
 // hot = active in this call or the previous one (or, seen from the pass B that runs beside it, in the next one)
 __device__ __forceinline__ bool group_is_hot(uint32_t last, uint32_t epoch) { return ((epoch - last + 1u) & 255u) <= 2u; }
 
-// Far-term bins of the regulariser (k_reg_accumulate -> k_reg_step): one bin per destination segment of kSegB slots.
-// A gradient term whose target lies outside the sender's segment is APPENDED to the target segment's bin -- record =
-// (target's position in its segment | sender class << 10, gx, gy, gz in 2^-22 fixed point) -- and the segment's
-// workgroup of k_reg_step sums its bin in LDS.  The reference pushes these terms with four float atomics each
-// (kernels.cu:2176-2182); rounds 1-2 used exclusive "inbox" slots for symmetric links and two packed 64-bit atomics for
-// the rest (0.43 M device-scope atomics and 0.39 M random 16-byte stores per frame at C2, and 64 bytes of inbox per
-// recent slot read back by the step).  Appending costs one returning atomic per (sender workgroup, destination segment)
-// -- 55 k per frame -- and the records of such a pair are adjacent.
-struct FarBins {
-  uint4* rec;            // [segments][cap]
-  uint32_t* count;       // [segments * kCountStride]: word 0 = terms appended since the bin was last consumed (may exceed cap),
-                         // word 1 = "some terms for this segment went to grad_acc instead"; both zeroed by the consumer
-  uint32_t cap;
-  uint32_t hash_mask;    // size - 1 of the sender's LDS table of destinations (kFarHash - 1; tests shrink it)
-};
 constexpr uint32_t kFarBinCap = 4096;   // records per bin (64 KB per 1024 slots: what the inbox took)
 constexpr int kFarHash = 1024;          // destinations one sender workgroup can address through the bins
 
@@ -343,15 +193,6 @@ static_assert(kTilePx == kBlock, "the tile kernel runs choose_segment_direction 
 // bit 9: the slot is active for integration (kernels.cu:77-87) -- inactive visible slots still take part in the merge phase
 constexpr uint32_t kPairSecond = 1u << 8, kPairActive = 1u << 9;
 constexpr uint32_t kTileBinCap = 8192;   // pairs per bin (64 KB): 32 per pixel before a tile spills to the overflow list
-struct TileBins {
-  uint2* pairs;          // [n_tiles][cap]: (slot, code)
-  uint32_t* count;       // [n_tiles * kCountStride]: pairs appended in this call (zeroed again by the tile's workgroup); may exceed cap,
-  uint4* ovf;            // in which case the rest went to this list: (tile, slot, code, -), room for 2 pairs per slot
-  uint32_t* ovf_count;   // this call's overflow counter (two in alternation: the tile kernel zeroes the next call's)
-  uint32_t cap;
-  int tiles_x;
-  uint32_t n_tiles;
-};
 
 // Pass A appends its pairs (<= 8 per lane: 4 slots x 2 pixels; key = tile << 10 | code, kNoPair = none) with ONE
 // returning device-scope atomic per (workgroup, tile): every pair takes a rank from an LDS counter of its tile (the
@@ -384,28 +225,6 @@ __device__ __forceinline__ bool stamp_outside_window(uint32_t stamp, uint32_t fr
 }
 __device__ __forceinline__ uint8_t make_flags(uint32_t stamp, uint32_t color, uint32_t frame, int reg_window) {
   return (uint8_t)(((color >> 24) == 1u ? 2u : 0u) | (stamp_outside_window(stamp, frame, reg_window) ? 0u : 1u));
-}
-
-// Exclusive prefix sum of one value per thread over a workgroup of kWaves wavefronts (wave64 shuffles + LDS).
-template <int kWaves = kBlock / 64>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* wave_tot /* LDS [kWaves] */, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_up(incl, off);
-    if (lane >= (uint32_t)off) incl += t;
-  }
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  uint32_t wave_off = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if ((uint32_t)w < wave) wave_off += wave_tot[w];
-    total += wave_tot[w];
-  }
-  return wave_off + incl - mine;
 }
 
 // The same for counts that are zero in most wavefronts (pass B's list ranks): a wavefront without any skips the shuffles.
@@ -532,11 +351,8 @@ __device__ __forceinline__ void out_store16(void* p, unsigned long long a, unsig
 }
 
 // ---------------------------------------------------------------------------------------------
-// The reference's 5 clears (cuda_surfel_reconstruction.cc:134-138) have no counterpart: k_assoc_tiles writes every pixel
+// of the association images with plain stores.
 // of the association images with plain stores.  The maps of the multi-launch blend fallback (kernels.cc:165-166):
-struct BlendBufs {
-  uint8_t* distance_map; uint8_t* new_distance_map; float* deltas; float* new_deltas;
-};
 
 // (value-distribution counters: only while statistics are on.  Two steps: the cull step's counter in front of it, the
 // others behind the stream's wait for the previous call's second half, whose kernels may still be adding to them)
@@ -573,11 +389,6 @@ __global__ void k_reset_frame_stats(DevState* st, int cull_only) {
 // that was already culled in the two previous calls: the two copies of the flag table alternate by call, nothing but
 // pass A writes flag bytes of slots that are not visible, so the table written two calls ago already holds this call's
 // bytes (seg_streak).
-struct SegWork {
-  uint32_t* surv_list;   // segments pass A has to read in this call (any order)
-  uint32_t* copy_list;   // culled segments whose flag bytes have to be copied
-  uint32_t* count;       // [0] survivors, [1] copies; zeroed for the next call by k_assoc_tiles
-};
 __global__ void __launch_bounds__(kBlock)
 k_cull_segments(FrameCtx c, Lists L, SegWork sw, DevState* st, uint32_t nseg_alloc, uint32_t max_new_slots, unsigned long long ts_seq) {
   SMX_SET_WAVE_PRIO();
@@ -3132,427 +2943,6 @@ k_delta_gather(Surfels S, uint8_t* __restrict__ dirty8, const uint32_t* __restri
     }
 }
 
-// ---- map compaction (smx_recon_compact; not in the reference) -----------------------------------------------------
-// Count / scan / map / scatter over kSeg-slot segments, four slots per lane as in the delta kernels above: per-segment
-// counts of the kept slots (!(RadiusSquared < 0): the merge mark), k_delta_scan over the counts, old_to_new for every
-// old slot, then one scatter launch per record group.  A stable compaction IN PLACE races (a workgroup would overwrite
-// source records that an earlier workgroup has not read yet), so each group is scattered into the staging buffer
-// (16 B per old slot) and copied back before the next group is scattered: peak extra memory 16 B + 4 B per slot.
-// The G record (rows 11-13, the parked next smooth position) is scratch within a call and does not move.
-__global__ void __launch_bounds__(kBlock)
-k_compact_count(Surfels S, uint32_t n, uint8_t* __restrict__ keep4, uint32_t* __restrict__ seg_count) {
-  __shared__ uint32_t wave_tot[kBlock / 64];
-  const uint32_t lane_id = blockIdx.x * kBlock + threadIdx.x, i0 = lane_id * 4;
-  uint32_t bits = 0;
-  if (i0 < n) {   // (i0 + 3 < pitch: the group arrays are padded to a multiple of 64 slots)
-    const float r0 = S.f(kRadiusSq, i0), r1 = S.f(kRadiusSq, i0 + 1), r2 = S.f(kRadiusSq, i0 + 2), r3 = S.f(kRadiusSq, i0 + 3);
-    bits = (!(r0 < 0) ? 1u : 0u) | ((i0 + 1 < n && !(r1 < 0)) ? 2u : 0u) | ((i0 + 2 < n && !(r2 < 0)) ? 4u : 0u) |
-           ((i0 + 3 < n && !(r3 < 0)) ? 8u : 0u);
-    keep4[lane_id] = (uint8_t)bits;
-  }
-  uint32_t total;
-  (void)block_excl_scan((uint32_t)__popc(bits), wave_tot, total);
-  if (threadIdx.x == 0) seg_count[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(kBlock)
-k_compact_map(const uint8_t* __restrict__ keep4, const uint32_t* __restrict__ seg_offset, uint32_t n, uint32_t* __restrict__ map) {
-  __shared__ uint32_t wave_tot[kBlock / 64];
-  const uint32_t lane_id = blockIdx.x * kBlock + threadIdx.x, i0 = lane_id * 4;
-  const uint32_t bits = i0 < n ? keep4[lane_id] : 0u;
-  uint32_t seg_total;
-  uint32_t off = seg_offset[blockIdx.x] + block_excl_scan((uint32_t)__popc(bits), wave_tot, seg_total);
-  if (i0 >= n) return;
-  uint32_t m[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) m[j] = (bits & (1u << j)) ? off++ : kInvalid;
-  *reinterpret_cast<uint4*>(&map[i0]) = make_uint4(m[0], m[1], m[2], m[3]);   // (map has pitch entries)
-}
-// One record group: the records of the kept slots go to out[old_to_new[i]] (one 16-byte load and store per record).
-// Lane l of a segment's workgroup takes the slots l, l + 256, l + 512, l + 768 of it, so that every load instruction of
-// a wavefront reads 1 KB in one piece and the stores (ascending destinations with gaps) stay nearly contiguous.  (Four
-// consecutive slots per lane, as in the count kernel, left every instruction 64 B-strided: 75 us per group at C2.)
-// kLinks (group T): the four links go through the map as well, and the links that compaction drops are counted --
-// those of removed slots and those of kept slots into removed ones.
-template <bool kLinks>
-__global__ void __launch_bounds__(kBlock)
-k_compact_scatter(Surfels S, int g, const uint32_t* __restrict__ map, uint32_t n, float4* __restrict__ out,
-                  uint32_t* __restrict__ dropped) {
-  __shared__ uint32_t wave_tot[kBlock / 64];
-  const uint32_t base = blockIdx.x * kSeg + threadIdx.x;
-  uint32_t dst[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) dst[j] = base + j * kBlock < n ? map[base + j * kBlock] : kInvalid;
-  uint32_t drop = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t i = base + j * kBlock;
-    if (i >= n) continue;
-    if (kLinks) {
-      const uint4 t = *reinterpret_cast<const uint4*>(S.group(kGroupT, i));
-      uint32_t nb[4] = {t.x, t.y, t.z, t.w};
-      if (dst[j] == kInvalid) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) drop += nb[q] != kInvalid ? 1u : 0u;
-        continue;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (nb[q] == kInvalid) continue;
-        nb[q] = nb[q] < n ? map[nb[q]] : kInvalid;   // (the map is read-mostly and small: these gathers hit the caches)
-        drop += nb[q] == kInvalid ? 1u : 0u;
-      }
-      out[dst[j]] = make_float4(__uint_as_float(nb[0]), __uint_as_float(nb[1]), __uint_as_float(nb[2]), __uint_as_float(nb[3]));
-    } else if (dst[j] != kInvalid) {
-      out[dst[j]] = *S.group(g, i);
-    }
-  }
-  if (kLinks) {
-    uint32_t total;
-    (void)block_excl_scan(drop, wave_tot, total);
-    if (threadIdx.x == 0 && total) atomicAdd(dropped, total);
-  }
-}
-__global__ void __launch_bounds__(kBlock)
-k_compact_copy(Surfels S, int g, const float4* __restrict__ src, const uint32_t* __restrict__ total) {
-  const uint32_t K = *total;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < K; i += gridDim.x * kBlock) *S.group(g, i) = src[i];
-}
-// The device state after compaction: the new count, no merged slots, every other counter reset (as a state upload does).
-__global__ void k_compact_finish(DevState* st, const uint32_t* __restrict__ total) {
-  if (threadIdx.x != 0) return;
-  DevState h;
-  memset(&h, 0, sizeof(h));
-  h.surfel_count = *total;
-  *st = h;
-}
-// Delta tracking: every slot of the compacted map counts as changed, the marks at and above the new count are cleared.
-__global__ void __launch_bounds__(kBlock)
-k_compact_dirty(uint8_t* __restrict__ dirty8, uint32_t bytes, const uint32_t* __restrict__ total) {
-  const uint32_t K = *total;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < bytes; i += gridDim.x * kBlock) dirty8[i] = i < K ? 1 : 0;
-}
-
-// Boundary conversion between the grouped records and the reference's row layout: out[k][i] = row rows[k] of
-// slot i (pack) and back (unpack).  Rows without storage read as 0.
-struct RowList { int n; int rows[kRows]; };
-__global__ void __launch_bounds__(kBlock)
-k_pack_rows(Surfels S, RowList rl, float* __restrict__ out, uint32_t count) {
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock)
-    for (int k = 0; k < rl.n; ++k) {
-      const int g = row_group(rl.rows[k]), sub = row_sub(rl.rows[k]);
-      out[(size_t)k * count + i] = g < 0 ? 0.0f : S.base[S.quad(g, i) * 4 + sub];
-    }
-}
-__global__ void __launch_bounds__(kBlock)
-k_unpack_rows(Surfels S, RowList rl, const float* __restrict__ in, uint32_t count) {
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock)
-    for (int k = 0; k < rl.n; ++k) {
-      const int g = row_group(rl.rows[k]), sub = row_sub(rl.rows[k]);
-      if (g >= 0) S.base[S.quad(g, i) * 4 + sub] = in[(size_t)k * count + i];
-    }
-}
-
-// ExportVerticesCUDAKernel, kernels.cu:2412-2433
-__global__ void __launch_bounds__(kBlock)
-k_export(Surfels S, float* __restrict__ pos, uint8_t* __restrict__ col, const DevState* st) {
-  const uint32_t N = st->surfel_count;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
-    const bool merged = S.f(kRadiusSq, i) < 0;
-    const float nanv = __builtin_nanf("");
-    pos[3 * (size_t)i + 0] = merged ? nanv : S.f(kSmoothX, i);
-    pos[3 * (size_t)i + 1] = merged ? nanv : S.f(kSmoothY, i);
-    pos[3 * (size_t)i + 2] = merged ? nanv : S.f(kSmoothZ, i);
-    const uint32_t c = S.u(kColor, i);
-    col[3 * (size_t)i + 0] = (uint8_t)(c & 255u);
-    col[3 * (size_t)i + 1] = (uint8_t)((c >> 8) & 255u);
-    col[3 * (size_t)i + 2] = (uint8_t)((c >> 16) & 255u);
-  }
-}
-
-// ---- viewer buffers (UpdateVisualizationBuffers) and headless rendering (smx_recon_render) ----
-struct VisColor { uint32_t frame; int window; int flags; };
-
-// float -> u8 for the colour conversions below: the reference converts values in [0, 256) (truncation); outside that
-// range its conversion is undefined, here it saturates (NaN -> 0)
-__device__ __forceinline__ uint32_t vis_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f); }
-__device__ __forceinline__ uint32_t vis_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
-
-// The colour word of UpdateSurfelVertexBufferCUDAKernel (kernels.cu:306-349) for one slot, flags in the reference
-// template's precedence (smx.h SMX_VIS_*).  Shared by the vertex buffer and the render's colour image.
-__device__ __forceinline__ uint32_t vis_color(const Surfels& S, uint32_t i, const VisColor& vc) {
-  if (vc.flags & (SMX_VIS_LAST_UPDATE | SMX_VIS_CREATION)) {
-    const bool creation = (vc.flags & SMX_VIS_CREATION) != 0;
-    const int age = (int)(vc.frame - (creation ? S.u(kCreationStamp, i) : S.u(kLastUpdateStamp, i)));
-    const int max_age = creation ? 3000 : vc.window;
-    if (age < 1) return vis_rgb(255, 80, 80);
-    if (age > max_age) return vis_rgb(40, 40, 255);
-    float blend = (float)(age - 1) * 1.0f / (float)(max_age - 1);
-    blend = fminf(1.0f, fmaxf(0.0f, blend));
-    const uint32_t intensity = (255u - vis_u8(255.99f * blend)) & 255u;
-    return vis_rgb(intensity, intensity, intensity);
-  }
-  if (vc.flags & SMX_VIS_RADII) {
-    const float radius = sqrtf(S.f(kRadiusSq, i));
-    float blend = (radius - 0.0005f) / (0.01f - 0.0005f);
-    blend = fminf(1.0f, fmaxf(0.0f, blend));
-    const uint32_t red = vis_u8(255.99f * blend);
-    return vis_rgb(red, 255u - red, 80u);
-  }
-  if (vc.flags & SMX_VIS_NORMALS) {
-    const float4 n = *S.group(kGroupN, i);
-    return vis_rgb(vis_u8(255.99f / 2.0f * (n.x + 1.0f)), vis_u8(255.99f / 2.0f * (n.y + 1.0f)),
-                   vis_u8(255.99f / 2.0f * (n.z + 1.0f)));
-  }
-  return S.u(kColor, i);
-}
-
-// The three fill kernels of UpdateVisualizationBuffers (kernels.cu:278-351, 434-449, 498-514) in one pass over the
-// slots; each buffer stops at its own capacity.  (The reference writes vertex components one float at a time; one
-// 16-byte record per slot here, 32 for the neighbour pairs.)
-__global__ void __launch_bounds__(kBlock)
-k_vis_fill(Surfels S, VisColor vc, uint32_t latest_triangulated, uint32_t latest_mesh_count,
-           float4* __restrict__ vtx, uint32_t vtx_cap, uint4* __restrict__ nbr, uint32_t nbr_cap,
-           float2* __restrict__ nvb, uint32_t nvb_cap, const DevState* st) {
-  const uint32_t N = min(st->surfel_count, max(vtx ? vtx_cap : 0u, max(nbr ? nbr_cap : 0u, nvb ? nvb_cap : 0u)));
-  const float nanv = __builtin_nanf("");
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
-    const float4 s = *S.group(kGroupS, i);
-    if (vtx && i < vtx_cap) {
-      const bool output_vertex = S.u(kCreationStamp, i) <= latest_triangulated || i >= latest_mesh_count;
-      vtx[i] = make_float4(output_vertex ? s.x : nanv, s.y, s.z, __uint_as_float(vis_color(S, i, vc)));
-    }
-    if (nbr && i < nbr_cap) {
-      const uint4 t = *reinterpret_cast<const uint4*>(S.group(kGroupT, i));
-      nbr[2 * (size_t)i + 0] = make_uint4(i, t.x == kInvalid ? i : t.x, i, t.y == kInvalid ? i : t.y);
-      nbr[2 * (size_t)i + 1] = make_uint4(i, t.z == kInvalid ? i : t.z, i, t.w == kInvalid ? i : t.w);
-    }
-    if (nvb && i < nvb_cap) {
-      const float4 n = *S.group(kGroupN, i);
-      const float radius = sqrtf(n.w);
-      nvb[3 * (size_t)i + 0] = make_float2(s.x, s.y);
-      nvb[3 * (size_t)i + 1] = make_float2(s.z, s.x + radius * n.x);
-      nvb[3 * (size_t)i + 2] = make_float2(s.y + radius * n.y, s.z + radius * n.z);
-    }
-  }
-}
-
-struct RenderCtx {
-  double L[12];   // camera_T_global (inverted on the host in double precision)
-  Mat34 Lf;       // ... rounded to float: the rotation part is exact (a transpose), used for the normal image
-  double fx, fy, cx, cy, near_z, far_z;
-  double half_extent;   // square mode
-  double disc_factor, max_extent, f_max;   // disc mode (f_max = max(fx, fy))
-  int W, H, mode;
-};
-
-// z-test: the smaller (depth bits, slot) key wins; a plain load first, so that a hidden splat costs no atomic
-__device__ __forceinline__ void render_zmin(unsigned long long* p, unsigned long long key) {
-  if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-}
-
-// One thread per live slot: project, find the candidate pixel rectangle, z-test every covered pixel.  Streams the S
-// and N records (32 B per slot).  (No segment culling: the segment boxes bound the raw positions, not the smooth ones.)
-// The geometry is evaluated in double precision: neighbouring discs of one surface meet a pixel's ray at depths only
-// 1e-6 apart, and a float evaluation would order them by its rounding errors; the key then holds the depth as a float.
-__global__ void __launch_bounds__(kBlock)
-k_render_splat(Surfels S, RenderCtx rc, unsigned long long* __restrict__ zbuf, const DevState* st) {
-  const uint32_t N = st->surfel_count;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
-    const float4 nr = *S.group(kGroupN, i);
-    if (!(nr.w >= 0.0f)) continue;                       // merged
-    const float4 sp = *S.group(kGroupS, i);
-    const double* L = rc.L;
-    const double px = sp.x, py = sp.y, pz = sp.z;
-    const double cz = L[8] * px + L[9] * py + L[10] * pz + L[11];
-    if (!(cz > rc.near_z && cz < rc.far_z)) continue;
-    const double cx = L[0] * px + L[1] * py + L[2] * pz + L[3], cy = L[4] * px + L[5] * py + L[6] * pz + L[7];
-    const double u = rc.fx * cx / cz + rc.cx, v = rc.fy * cy / cz + rc.cy;
-    if (!(fabs(u) < 1e8 && fabs(v) < 1e8)) continue;   // (far outside any image; keeps the conversions below defined)
-    double e = rc.half_extent, rho = 0.0;
-    if (rc.mode == SMX_SPLAT_DISC) {
-      rho = rc.disc_factor * sqrt((double)nr.w);
-      const double dz = cz - rho;
-      e = dz <= rc.near_z ? rc.max_extent : fmin(rc.max_extent, 2.0 * rc.f_max * rho / dz);
-    }
-    // pixels whose centre x + 1/2 lies within e of u: u - e - 1/2 <= x <= u + e - 1/2 (square mode, h = 0: floor(u))
-    const bool point = rc.mode == SMX_SPLAT_SQUARE && e == 0.0;
-    const double x0f = point ? floor(u) : ceil(u - e - 0.5), x1f = point ? floor(u) : floor(u + e - 0.5);
-    const double y0f = point ? floor(v) : ceil(v - e - 0.5), y1f = point ? floor(v) : floor(v + e - 0.5);
-    const int x0 = (int)fmax(x0f, 0.0), x1 = (int)fmin(x1f, (double)(rc.W - 1));
-    const int y0 = (int)fmax(y0f, 0.0), y1 = (int)fmin(y1f, (double)(rc.H - 1));
-    if (rc.mode == SMX_SPLAT_SQUARE) {
-      const unsigned long long key = ((unsigned long long)__float_as_uint((float)cz) << 32) | i;
-      for (int y = y0; y <= y1; ++y)
-        for (int x = x0; x <= x1; ++x) render_zmin(&zbuf[(size_t)y * rc.W + x], key);
-    } else {
-      const double nx = L[0] * nr.x + L[1] * nr.y + L[2] * nr.z, ny = L[4] * nr.x + L[5] * nr.y + L[6] * nr.z;
-      const double nz = L[8] * nr.x + L[9] * nr.y + L[10] * nr.z;
-      const double n_dot_c = nx * cx + ny * cy + nz * cz;
-      const double rho2 = rho * rho;
-      for (int y = y0; y <= y1; ++y) {
-        const double dy = ((double)y + 0.5 - rc.cy) / rc.fy;
-        for (int x = x0; x <= x1; ++x) {
-          const double dx = ((double)x + 0.5 - rc.cx) / rc.fx;
-          const double n_dot_d = nx * dx + ny * dy + nz;
-          if (fabs(n_dot_d) < 1e-4) continue;
-          const double t = n_dot_c / n_dot_d;
-          if (!(t > rc.near_z)) continue;
-          const double ex = t * dx - cx, ey = t * dy - cy, ez = t - cz;
-          if (ex * ex + ey * ey + ez * ez <= rho2)
-            render_zmin(&zbuf[(size_t)y * rc.W + x], ((unsigned long long)__float_as_uint((float)t) << 32) | i);
-        }
-      }
-    }
-  }
-}
-
-// One thread per pixel: decode the key, gather only the winner's records.
-__global__ void __launch_bounds__(kBlock)
-k_render_resolve(Surfels S, RenderCtx rc, VisColor vc, const unsigned long long* __restrict__ zbuf,
-                 Img<float> depth, Img<uint32_t> index, Img<float4> normal, Img<uint32_t> color) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= rc.W || y >= rc.H) return;
-  const unsigned long long key = zbuf[(size_t)y * rc.W + x];
-  const bool empty = key == ~0ull;
-  const uint32_t slot = empty ? kInvalid : (uint32_t)key;
-  if (depth.address) depth(y, x) = empty ? 0.0f : __uint_as_float((uint32_t)(key >> 32));
-  if (index.address) index(y, x) = slot;
-  if (normal.address) {
-    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (!empty) {
-      const float4 nr = *S.group(kGroupN, slot);
-      const Vec3 n = rotate(rc.Lf, Vec3{nr.x, nr.y, nr.z});
-      o = make_float4(n.x, n.y, n.z, 0.0f);
-    }
-    normal(y, x) = o;
-  }
-  if (color.address) color(y, x) = empty ? 0u : ((vis_color(S, slot, vc) & 0x00FFFFFFu) | 0xFF000000u);
-}
-
-bool render_desc_ok(const smx_buffer_desc* d, const smx_render_params* p, size_t elem) {
-  return !d || (d->address && d->width == p->width && d->height == p->height && d->pitch >= (size_t)p->width * elem &&
-                d->pitch % elem == 0 && (uintptr_t)d->address % elem == 0);
-}
-template <typename T>
-Img<T> render_img(const smx_buffer_desc* d) {
-  if (d) return as_img<T>(d);
-  Img<T> i; i.address = nullptr; i.height = 0; i.width = 0; i.pitch = 0;
-  return i;
-}
-
-// Candidate lists for the mesher: the rows the neighbour index is built from (smooth position,
-// NaN for merged slots so that the index leaves them out) and the per-query (position, radius^2) of a list of slots.
-__global__ void __launch_bounds__(kBlock)
-k_index_rows(Surfels S, float* __restrict__ out, uint32_t count) {
-  const float nanv = __builtin_nanf("");
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
-    const float4 s = *S.group(kGroupS, i);
-    const bool merged = S.f(kRadiusSq, i) < 0;
-    out[i] = merged ? nanv : s.x;
-    out[(size_t)count + i] = merged ? nanv : s.y;
-    out[(size_t)2 * count + i] = merged ? nanv : s.z;
-  }
-}
-__global__ void __launch_bounds__(kBlock)
-k_candidate_queries(Surfels S, const uint32_t* __restrict__ slots, uint32_t nq, const DevState* st,
-                    float radius_factor_sq, float* __restrict__ q /* [4][nq]: x, y, z, r^2 */) {
-  const uint32_t N = st->surfel_count;
-  for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < nq; k += gridDim.x * kBlock) {
-    const uint32_t i = slots[k];
-    float4 s = make_float4(0, 0, 0, 0);
-    float r2 = -1.0f;  // out of range or merged: an empty ball
-    if (i < N) {
-      s = *S.group(kGroupS, i);
-      const float rs = S.f(kRadiusSq, i);
-      if (!(rs < 0)) r2 = radius_factor_sq * rs;  // surfel_meshing.cc:359-360
-    }
-    q[k] = s.x; q[(size_t)nq + k] = s.y; q[(size_t)2 * nq + k] = s.z; q[(size_t)3 * nq + k] = r2;
-  }
-}
-
-// The per-triangle tests of SurfelMeshing::CheckRemeshing (APP/surfel_meshing.cc:590-650) over the device-resident
-// map: one thread per triangle, three (S, N) record gathers.  Flag bits: see smx.h.
-__global__ void __launch_bounds__(kBlock)
-k_check_triangles(Surfels S, const uint32_t* __restrict__ tri, uint32_t n_tri, const DevState* st,
-                  float factor_sq, uint8_t* __restrict__ flags) {
-  const uint32_t N = st->surfel_count;
-  for (uint32_t t = blockIdx.x * kBlock + threadIdx.x; t < n_tri; t += gridDim.x * kBlock) {
-    const uint32_t v[3] = {tri[3 * (size_t)t], tri[3 * (size_t)t + 1], tri[3 * (size_t)t + 2]};
-    if (v[0] >= N || v[1] >= N || v[2] >= N) { flags[t] = 16; continue; }
-    Vec3 p[3], nrm[3];
-    float maxsq[3];
-    uint32_t f = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float4 s = *S.group(kGroupS, v[k]);
-      const float4 n = *S.group(kGroupN, v[k]);
-      p[k] = Vec3{s.x, s.y, s.z};
-      nrm[k] = Vec3{n.x, n.y, n.z};
-      maxsq[k] = factor_sq * n.w;   // :556-557, 593-596
-      if (n.w < 0) f |= 16u;        // :559
-    }
-    float e[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int b = (k + 1) % 3;
-      const float dx = p[b].x - p[k].x, dy = p[b].y - p[k].y, dz = p[b].z - p[k].z;
-      e[k] = dx * dx + dy * dy + dz * dz;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // :605-617
-      const int b = (k + 1) % 3, c = (k + 2) % 3;
-      if (e[k] > maxsq[k] && e[k] > maxsq[b] && (e[b] > maxsq[c] || e[c] > maxsq[c])) f |= 1u;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // :632-635, pivot k
-      const int r = (k + 1) % 3, l = (k + 2) % 3;
-      const float rx = p[r].x - p[k].x, ry = p[r].y - p[k].y, rz = p[r].z - p[k].z;
-      const float lx = p[l].x - p[k].x, ly = p[l].y - p[k].y, lz = p[l].z - p[k].z;
-      const float cx = ry * lz - rz * ly, cy = rz * lx - rx * lz, cz = rx * ly - ry * lx;
-      const float d0 = cx * nrm[k].x + cy * nrm[k].y + cz * nrm[k].z;
-      const float d1 = cx * nrm[r].x + cy * nrm[r].y + cz * nrm[r].z;
-      const float d2 = cx * nrm[l].x + cy * nrm[l].y + cz * nrm[l].z;
-      if (d0 <= 0 && d1 <= 0 && d2 <= 0) f |= (2u << k);
-    }
-    flags[t] = (uint8_t)f;
-  }
-}
-
-// The loop-closure hook the reference describes but does not ship (README.md:152-176, main.cc:1194-1200): a rigid
-// correction per creation frame.  Streams the C records (creation stamp); only moved slots touch P, S, N.
-__global__ void __launch_bounds__(kBlock)
-k_deform_by_creation_frame(Surfels S, const float* __restrict__ frame_T, uint32_t n_frames,
-                           const uint8_t* __restrict__ reactivate, uint32_t frame_index, uint8_t* __restrict__ dirty8,
-                           const DevState* st) {
-  const uint32_t N = st->surfel_count;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
-    const uint32_t c = S.u(kCreationStamp, i);
-    if (c >= n_frames) continue;
-    float4 nr = *S.group(kGroupN, i);
-    if (nr.w < 0) continue;  // merged
-    Mat34 T;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) T.m[k] = frame_T[12 * (size_t)c + k];
-    float4 pr = *S.group(kGroupP, i);
-    float4 sr = *S.group(kGroupS, i);
-    const Vec3 p = {pr.x, pr.y, pr.z};
-    const Vec3 q = mul(T, p);
-    const float ox = q.x - p.x, oy = q.y - p.y, oz = q.z - p.z;  // README.md:160-165: one offset for both positions
-    const Vec3 nn = rotate(T, Vec3{nr.x, nr.y, nr.z});            // README.md:166-168
-    const bool restamp = reactivate != nullptr && reactivate[c] && __float_as_uint(pr.w) != frame_index;
-    // a correction that leaves the slot as it is (identity rows) is not a change for the delta hand-off
-    if (ox == 0 && oy == 0 && oz == 0 && nn.x == nr.x && nn.y == nr.y && nn.z == nr.z && !restamp) continue;
-    pr.x = p.x + ox; pr.y = p.y + oy; pr.z = p.z + oz;
-    sr.x = sr.x + ox; sr.y = sr.y + oy; sr.z = sr.z + oz;
-    nr.x = nn.x; nr.y = nn.y; nr.z = nn.z;
-    if (restamp) pr.w = __uint_as_float(frame_index);             // README.md:172-174
-    *S.group(kGroupP, i) = pr;
-    *S.group(kGroupS, i) = sr;
-    *S.group(kGroupN, i) = nr;
-    if (dirty8) dirty8[i] = 1;
-  }
-}
-
 __global__ void __launch_bounds__(kBlock)
 k_decode_conflicting(const uint32_t* __restrict__ key, uint32_t* __restrict__ out, int P) {
   const int k = blockIdx.x * kBlock + threadIdx.x;
@@ -3567,117 +2957,6 @@ k_global_ranks(const uint32_t* __restrict__ local_rank, const uint32_t* __restri
 }
 
 }  // namespace
-
-// =============================================================================================
-struct smx_recon_s {
-  int device;               // the HIP device the object lives on (every entry point runs on it)
-  uint32_t max_surfels;
-  int W, H;
-  float fx, fy, cx, cy;
-  Surfels S;
-  long long* grad_acc;      // [slots][2] packed fixed point (see pack_pair), cross-segment contributions (atomics)
-  float4* reg_rec;          // two dense arrays [slots + kSegAcc] of the recent slots' results, by (segment, rank in its recent list):
-                            // the in-segment sums, then the own terms (each written by ONE store instruction per chunk: full sectors)
-  FarBins fb;               // far terms of the regulariser, per destination segment (see FarBins)
-  Lists L;
-  int nseg;                 // number of kSeg-slot segments (= workgroups of pass A)
-  int nsegB;                // number of kSegB-slot segments (= workgroups of pass B)
-  uint8_t* merge_flag;
-  bool table_valid;         // flag table's "recent" bits correspond to (table_frame, table_window)
-  uint32_t table_frame;
-  int table_window;
-  int stats_enabled;
-  hipEvent_t hook_consumed, hook_chain;   // smx_recon_integrate_hooks: one-shot, taken by the next Integrate call
-  hipEvent_t hook_ready;                  // smx_recon_integrate_inputs_ready: likewise
-  int blend_multi_launch;   // A/B switch: 1 = the reference's start + iteration launches instead of the fused kernel
-  Scratch sc;               // the association images (every pixel is rewritten by k_assoc_tiles in every call)
-  TileBins tb;              // pass A's pairs, binned by association tile
-  SegWork sw;               // pass A's work lists (k_cull_segments -> k_scan_visible)
-  bool sw_dirty;            // a call failed between the cull step and the tile kernel: the lists' counters are not zero
-  hipEvent_t pending_mark;  // != null: the caller's stream has not waited for the previous call's update + create yet (smx_recon_integrate)
-  uint32_t* ovf_count_set[2];   // overflow counters, alternating by call (the tile kernel zeroes the next call's)
-  unsigned long long* stamps;   // -DSMX_STAMPS builds: [3][8192 workgroups][16] shader clocks (tile kernel, blend kernel), wall clocks + counts (edge kernel)
-  int no_lds_tables;        // A/B switch (scan mode bit 4)
-  int blend_other_tile;     // A/B switch (scan mode bit 7)
-  int cu_count;             // compute units of the object's device
-  uint32_t bin_cap_full;    // the bins' allocated capacity (tb.cap is lowered by the A/B switch that forces overflows)
-  uint32_t* vis_count_set[2];   // chunk counters of the visible list, alternating by call (k_update_and_create zeroes the next call's)
-  uint32_t* dir_host;           // page-locked word: the direction the tile kernel last chose for the all-slot kernels
-  uint32_t* dir_dev;            // (segment_of_block); its device alias
-  int sc_cur;
-  int hot_holdoff;          // > 0: pass B does not use the hot-group table (decremented per Integrate call)
-  int hot_filter_enabled;   // A/B switch (smx_recon_set_scan_mode bit 2 clears it)
-  int fuse_edges;           // pass B does the edge work of its segment itself (one launch less); scan mode bit 9 sets it
-  uint16_t* blended_depth;  // [H][W] output of the fused blend (stored into the caller's depth by k_new_flags_scan)
-  BlendBufs bb;
-  uint8_t* new_flags;
-  uint32_t* new_ranks;
-  uint32_t* block_sums;     // per k_new_flags_scan workgroup: flagged pixels
-  uint32_t* block_offsets;  // exclusive scan of block_sums (written by k_new_create's workgroup 0)
-  uint32_t* tmp_u32;  // [W*H] debug decode target
-  int n_scan_blocks;
-  DevState* st;
-  int scan_mode;
-  int timing_enabled;       // bit 0: the reference's 14 stage events, bit 1: events around every kernel, bit 2: stage stamps (default)
-  bool have_timings;
-  unsigned long long* ts_ring;   // [kTsRing][kTsWords] stage stamps of the last kTsRing Integrate calls (StageStamps)
-  unsigned long long* ts_host;   // page-locked copy target of the ring (the waiting read)
-  volatile unsigned long long* ts_mapped;   // page-locked ring the tile kernel copies complete records into (the non-waiting read)
-  unsigned long long* ts_mapped_dev;        // ... its device alias
-  unsigned long long ts_seq;     // Integrate calls with stamps so far (a call's record: ts_ring[seq % kTsRing])
-  int wall_khz;                  // rate of the device's wall clock (hipDeviceAttributeWallClockRate)
-  hipEvent_t ev[14];
-  // per-kernel instrumentation (timing_enabled bit 1) and single-kernel profiling over many frames
-  hipEvent_t kev[2 * 16];
-  bool kev_recorded[16];
-  int prof_slot;
-  int prof_cap, prof_n;
-  hipEvent_t* prof_ev;
-  uint32_t* delta_seg;   // delta hand-off: per-segment counts / offsets, and the total
-  uint32_t* delta_total;
-  float* staging;    // row-layout staging for the boundary conversions (TransferAllToCPU, debug rows)
-  size_t staging_floats;
-  float* cand_q; uint32_t* cand_slots; uint8_t* cand_state;   // workspace of smx_recon_neighbor_candidates
-  uint32_t cand_cap, cand_state_cap;
-  hipEvent_t ev_staging;  // recorded after the last enqueued read of `staging`: TransferAllToCPU returns with its
-  bool staging_busy;      // row downloads in flight, and the next user may come on another stream
-  int grid_surfels;  // persistent grid for the grid-stride all-slot kernels
-  int grid_list;     // persistent grid of the chunked list kernels
-  int grid_acc;      // ... of the edge kernel (512-lane workgroups)
-  int grid_list_full; // (grid_list is lowered by the A/B switch that forces long walks)
-  int debug_skip;    // smx_recon_debug_set_skip (timing only)
-  // Frame pipelining: the regulariser of frame f runs on an internal stream while the caller's stream already
-  // executes clear / pass A / associate / merge / blend of frame f+1 (those read only P and N records, which the
-  // regulariser does not write, and a second copy of the flag table).  Every entry point first orders the
-  // caller's stream after the pending regulariser, so the API keeps its one-stream semantics.
-  int overlap_enabled;
-  hipStream_t reg_stream;     // high priority: the frame-to-frame critical path (integrate .. regulariser)
-  uint32_t* gate_count;       // blend workgroups that have released their output, all calls (k_front_gate)
-  uint32_t gate_expected;     // ... the value after the last call enqueued with the device-word hand-over
-  int handover_mode;          // smx_recon_set_handover_mode: 1 = device word + gate kernel for front -> integration, 0 = event
-  hipEvent_t ev_front;        // caller's stream: pass A .. flags of a call are enqueued
-  hipEvent_t ev_upd;          // internal stream: update + create of a call are enqueued (the inputs are consumed, the map is ready for the next pass A)
-  hipEvent_t ev_reg;          // internal stream: end of the work enqueued so far (recorded on demand by join_regularizer)
-  bool reg_pending;
-  hipStream_t last_stream;    // the caller's stream of the last Integrate call
-  uint8_t* flags_buf[2];    // the flag table is double-buffered by frame (L.flags8 = the current frame's)
-  bool have_frame;          // an Integrate call has been made since creation / the last state upload
-  uint32_t last_frame;      // its frame_index: the segment culling of pass A presumes that it never decreases
-  uint32_t* cmp_map;        // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
-  uint32_t* cmp_seg;        // offsets [nseg], and [0] = new count, [1] = links dropped
-  uint32_t* cmp_out;
-  unsigned long long* zbuf; // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
-  size_t zbuf_px;           // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
-  hipEvent_t ev_render;
-  bool render_busy;
-  float* trk_depth;         // smx_recon_track (allocated by its first call): the model images [H][W] of the last call,
-  float4* trk_normal;       // the reduce kernel's per-workgroup partial sums, the call's device state, and the mark
-  double* trk_slabs;        // after the last call's kernels (the next call, on whatever stream, waits for it)
-  TrackDev* trk_state;
-  hipEvent_t ev_track;
-  bool track_busy;
-  MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging
-};
 
 // kernel slots of one Integrate call (launch order)
 enum : int {
@@ -3715,19 +2994,6 @@ struct SlotTimer {
 };
 
 namespace {
-
-// Orders stream st after the regulariser that may still run on the internal stream.
-int join_regularizer(smx_recon r, hipStream_t st) {
-  // (the flag stays set: a later call may come with another stream, which has to be ordered as well; waiting on a
-  // completed event costs nothing on the device.  The mark is recorded here, on demand: the frame loop itself never
-  // needs it, and every event operation on the internal stream sits on the frame-to-frame critical chain.)
-  if (r->reg_pending) {
-    SMX_HIP(hipEventRecord(r->ev_reg, r->reg_stream));
-    SMX_HIP(hipStreamWaitEvent(st, r->ev_reg, 0));
-    if (st == r->last_stream) r->pending_mark = nullptr;   // (that stream now waits for more than the deferred mark covers)
-  }
-  return SMX_OK;
-}
 
 // zero_chunks: pass B appends to the recent list's chunk descriptors; inside Integrate the launch in front of it
 // (k_update_and_create) has reset their counter, everywhere else it is done here.
@@ -3790,7 +3056,40 @@ int ensure_staging(smx_recon r, size_t floats) {
   return SMX_OK;
 }
 
-// Every user of the shared staging buffer first orders its stream after the previous user's last read.
+// (for the create functions, whose failure paths have to release what exists so far instead of returning on the spot)
+int hip_rc(hipError_t e, const char* what) {
+  if (e == hipSuccess) return SMX_OK;
+  set_error("%s failed: %s", what, hipGetErrorString(e));
+  return SMX_ERR_HIP;
+}
+
+}  // namespace
+
+// ---- host helpers shared with smx_recon_map.hip (declared in smx_recon_state.hpp) ----
+namespace smx {
+
+int join_regularizer(smx_recon r, hipStream_t st) {
+  // (the flag stays set: a later call may come with another stream, which has to be ordered as well; waiting on a
+  // completed event costs nothing on the device.  The mark is recorded here, on demand: the frame loop itself never
+  // needs it, and every event operation on the internal stream sits on the frame-to-frame critical chain.)
+  if (r->reg_pending) {
+    SMX_HIP(hipEventRecord(r->ev_reg, r->reg_stream));
+    SMX_HIP(hipStreamWaitEvent(st, r->ev_reg, 0));
+    if (st == r->last_stream) r->pending_mark = nullptr;   // (that stream now waits for more than the deferred mark covers)
+  }
+  return SMX_OK;
+}
+
+int read_surfel_count(smx_recon r, hipStream_t st, uint32_t* n) {
+  SMX_HIP(hipMemcpyAsync(n, &r->st->surfel_count, sizeof(*n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  return SMX_OK;
+}
+
+void enqueue_segment_scan(hipStream_t st, uint32_t* seg_count, int nseg, uint32_t* total_out) {
+  hipLaunchKernelGGL(k_delta_scan, dim3(1), dim3(1024), 0, st, seg_count, nseg, total_out);
+}
+
 int acquire_staging(smx_recon r, hipStream_t st, size_t floats) {
   if (r->staging_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_staging, 0));
   return ensure_staging(r, floats);
@@ -3801,21 +3100,25 @@ int release_staging(smx_recon r, hipStream_t st) {
   return SMX_OK;
 }
 
-// (for the create functions, whose failure paths have to release what exists so far instead of returning on the spot)
-int hip_rc(hipError_t e, const char* what) {
-  if (e == hipSuccess) return SMX_OK;
-  set_error("%s failed: %s", what, hipGetErrorString(e));
-  return SMX_ERR_HIP;
-}
-
-template <typename T>
-int dev_alloc(T** p, size_t count, bool zero) {
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-  if (zero) SMX_HIP(hipMemset(*p, 0, count * sizeof(T)));
+// After surfel attributes were changed from outside the frame loop (state upload, deformation): drop the work
+// lists and segment boxes (count 0 = no box, the segment is scanned) and rebuild the flag table -- its detach bits
+// come from the colour words, the recent bits are refreshed per frame.
+int invalidate_derived(smx_recon r, hipStream_t st) {
+  SMX_HIP(hipMemsetAsync(r->L.vis_seg, 0, (size_t)r->nseg * 4, st));
+  SMX_HIP(hipMemsetAsync(r->L.seg_box, 0, (size_t)r->nseg * 8 * sizeof(float), st));
+  SMX_HIP(hipMemsetAsync(r->L.recent_seg, 0, (size_t)r->nsegB * 4, st));
+  SMX_HIP(hipMemsetAsync(r->vis_count_set[0], 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
+  SMX_HIP(hipMemsetAsync(r->vis_count_set[1], 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
+  SMX_HIP(hipMemsetAsync(r->L.rec_chunks.count, 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
+  hipLaunchKernelGGL(k_rebuild_flags, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, 0u, 0x7FFFFFFF, r->L.flags8, r->st);
+  SMX_LAUNCH_CHECK();
+  r->table_valid = false;
+  r->hot_holdoff = 3;     // (flags and links may have been rewritten: pass B gathers everything for two calls)
+  r->have_frame = false;  // (the boxes are gone, so any frame index may follow)
   return SMX_OK;
 }
 
-}  // namespace
+}  // namespace smx
 
 extern "C" {
 
@@ -3825,7 +3128,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_CHECK_ARG(out != nullptr && max_surfel_count > 0 && max_surfel_count <= (1u << 30));
   SMX_CHECK_ARG(width >= 3 && height >= 3);
   int device = 0;
-  { const int rcd = resolve_device(device_id, &device); if (rcd != SMX_OK) return rcd; }
+  SMX_CALL(resolve_device(device_id, &device));
   SMX_ON_DEVICE(device);
   {   // (once per process: what the application should have set before its first HIP call -- smx_runtime_advice)
     static std::atomic<int> advised{0};
@@ -4129,7 +3432,7 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
     // Time moves backwards (a sequence replayed on a live object, a loop-closure re-integration): the reference accepts
     // any index.  What presumes forward time here is derived state only -- the segments' newest-stamp cache behind
     // pass A's culling and the hot-group table behind pass B's filter -- so it is dropped: this call reads every segment.
-    { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+    SMX_CALL(join_regularizer(r, st));
     SMX_HIP(hipMemsetAsync(r->L.vis_seg, 0, (size_t)r->nseg * 4, st));
     SMX_HIP(hipMemsetAsync(r->L.seg_box, 0, (size_t)r->nseg * 8 * sizeof(float), st));
     r->hot_holdoff = 3;
@@ -4189,7 +3492,7 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
   // update + create.  The step kernel then sits on no cycle.
   const bool split = pipelined && (r->debug_skip & 16) != 0;
   // (a caller that comes with another stream than last time: that stream has not waited for the previous call's map yet)
-  if (r->reg_pending && r->last_stream != st) { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
+  if (r->reg_pending && r->last_stream != st) SMX_CALL(join_regularizer(r, st));
   r->last_stream = st;
   if (r->stats_enabled) hipLaunchKernelGGL(k_reset_frame_stats, dim3(1), dim3(1), 0, sF, r->st, 1);
   if (tm) SMX_HIP(hipEventRecord(r->ev[0], sF));
@@ -4434,7 +3737,7 @@ int smx_recon_regularize(smx_recon r, smx_stream s, uint32_t frame_index, float 
                          float radius_factor_for_regularization_neighbors, int32_t regularization_frame_window_size) {
   SMX_CHECK_ARG(r != nullptr);
   SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
+  SMX_CALL(join_regularizer(r, (hipStream_t)s));
   return enqueue_regularize(r, (hipStream_t)s, frame_index, radius_factor_for_regularization_neighbors,
                             regularizer_weight, regularization_frame_window_size, false, false, true);
 }
@@ -4455,11 +3758,11 @@ static int check_handover(smx_recon r, hipStream_t st) {
 int smx_recon_counts(smx_recon r, smx_stream s, uint32_t* surfel_count, uint32_t* surfels_size) {
   SMX_CHECK_ARG(r != nullptr);
   SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
+  SMX_CALL(join_regularizer(r, (hipStream_t)s));
   DevState h;
   SMX_HIP(hipMemcpyAsync(&h, r->st, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));
-  { const int rch = check_handover(r, (hipStream_t)s); if (rch != SMX_OK) return rch; }
+  SMX_CALL(check_handover(r, (hipStream_t)s));
   if (surfel_count) *surfel_count = h.surfel_count - h.merge_count;  // .h:125-128
   if (surfels_size) *surfels_size = h.surfel_count;
   return SMX_OK;
@@ -4468,11 +3771,11 @@ int smx_recon_counts(smx_recon r, smx_stream s, uint32_t* surfel_count, uint32_t
 int smx_recon_get_stats(smx_recon r, smx_stream s, smx_recon_stats* out) {
   SMX_CHECK_ARG(r != nullptr && out != nullptr);
   SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
+  SMX_CALL(join_regularizer(r, (hipStream_t)s));
   DevState h;
   SMX_HIP(hipMemcpyAsync(&h, r->st, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));
-  { const int rch = check_handover(r, (hipStream_t)s); if (rch != SMX_OK) return rch; }
+  SMX_CALL(check_handover(r, (hipStream_t)s));
   out->surfels_size = h.surfel_count; out->merge_count = h.merge_count;
   out->n_visible = h.n_visible; out->n_new = h.new_count; out->n_merged = h.n_merged;
   out->n_recent = h.recent_count; out->n_edges = h.n_edges;
@@ -4483,454 +3786,6 @@ int smx_recon_get_stats(smx_recon r, smx_stream s, smx_recon_stats* out) {
   out->regularizer_saturated = h.reg_saturated;
   out->n_pairs = h.n_pairs; out->n_overflow_pairs = h.n_overflow_pairs; out->max_tile_pairs = h.max_tile_pairs;
   return SMX_OK;
-}
-
-int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_index, smx_surfel_buffers_cpu* buf) {
-  SMX_CHECK_ARG(r != nullptr && buf != nullptr);
-  SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
-  hipStream_t st = (hipStream_t)s;
-  uint32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  buf->frame_index = frame_index;  // cc:345-346
-  buf->surfel_count = n;
-  if (n == 0) return SMX_OK;
-  const size_t bytes = (size_t)n * 4;
-  // the 8 rows are packed out of the grouped records into a row-layout staging buffer, then copied row by row
-  int rc = acquire_staging(r, st, (size_t)8 * n);
-  if (rc != SMX_OK) return rc;
-  RowList rl;
-  rl.n = 8;
-  const int want[8] = {kSmoothX, kSmoothY, kSmoothZ, kRadiusSq, kNormalX, kNormalY, kNormalZ, kLastUpdateStamp};
-  for (int k = 0; k < 8; ++k) rl.rows[k] = want[k];
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging, n);
-  SMX_LAUNCH_CHECK();
-  struct { int row; void* dst; } rows[8] = {
-      {kSmoothX, buf->surfel_x_buffer}, {kSmoothY, buf->surfel_y_buffer}, {kSmoothZ, buf->surfel_z_buffer},
-      {kRadiusSq, buf->surfel_radius_squared_buffer},
-      {kNormalX, buf->surfel_normal_x_buffer}, {kNormalY, buf->surfel_normal_y_buffer}, {kNormalZ, buf->surfel_normal_z_buffer},
-      {kLastUpdateStamp, buf->surfel_last_update_stamp_buffer}};  // cc:348-358
-  int k = 0;
-  for (auto& q : rows) {
-    SMX_CHECK_ARG(q.dst != nullptr);
-    SMX_HIP(hipMemcpyAsync(q.dst, r->staging + (size_t)k * n, bytes, hipMemcpyDeviceToHost, st));
-    ++k;
-  }
-  return release_staging(r, st);  // (the copies are still in flight: the caller synchronises, main.cc:1266-1267)
-}
-
-int smx_recon_set_delta_tracking(smx_recon r, smx_stream s, int32_t enabled) {
-  SMX_CHECK_ARG(r != nullptr && (enabled == 0 || enabled == 1));
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  SMX_HIP(hipStreamSynchronize(st));  // no kernel may be using the pointer that changes here
-  if (enabled && !r->L.dirty8) {
-    int rc = dev_alloc(&r->L.dirty8, (size_t)r->nseg * kSeg, false);
-    if (rc == SMX_OK && !r->delta_seg) rc = dev_alloc(&r->delta_seg, (size_t)r->nseg, true);
-    if (rc == SMX_OK && !r->delta_total) rc = dev_alloc(&r->delta_total, 1, true);
-    if (rc != SMX_OK) return rc;
-    SMX_HIP(hipMemset(r->L.dirty8, 1, (size_t)r->nseg * kSeg));  // everything that exists counts as changed
-  } else if (!enabled && r->L.dirty8) {
-    SMX_HIP(hipFree(r->L.dirty8));
-    r->L.dirty8 = nullptr;
-  }
-  return SMX_OK;
-}
-
-int smx_recon_transfer_changed_to_cpu(smx_recon r, smx_stream s, uint32_t frame_index, smx_surfel_delta_cpu* d) {
-  SMX_CHECK_ARG(r != nullptr && d != nullptr);
-  SMX_ON_DEVICE(r->device);
-  if (!r->L.dirty8) { set_error("delta tracking is off (smx_recon_set_delta_tracking)"); return SMX_ERR_INVALID_ARGUMENT; }
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  hipLaunchKernelGGL(k_delta_count, dim3(r->nseg), dim3(kBlock), 0, st, r->L.dirty8, r->delta_seg, r->st);
-  hipLaunchKernelGGL(k_delta_scan, dim3(1), dim3(1024), 0, st, r->delta_seg, r->nseg, r->delta_total);
-  SMX_LAUNCH_CHECK();
-  uint32_t total = 0, n = 0;
-  SMX_HIP(hipMemcpyAsync(&total, r->delta_total, 4, hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, 4, hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  d->frame_index = frame_index;
-  d->surfel_count = n;
-  d->count = total;
-  if (total > d->capacity) {  // (the marks are untouched: call again with larger arrays)
-    set_error("delta of %u slots does not fit the capacity %u", total, d->capacity);
-    return SMX_ERR_INVALID_ARGUMENT;
-  }
-  if (total == 0) return SMX_OK;
-  SMX_CHECK_ARG(d->surfel_index && d->x && d->y && d->z && d->radius_squared && d->normal_x && d->normal_y &&
-                d->normal_z && d->last_update_stamp);
-  int rc = acquire_staging(r, st, (size_t)9 * total);
-  if (rc != SMX_OK) return rc;
-  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg, r->staging, total,
-                     r->st);
-  SMX_LAUNCH_CHECK();
-  void* dst[9] = {d->surfel_index, d->x, d->y, d->z, d->radius_squared, d->normal_x, d->normal_y, d->normal_z,
-                  d->last_update_stamp};
-  for (int k = 0; k < 9; ++k)
-    SMX_HIP(hipMemcpyAsync(dst[k], r->staging + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  return SMX_OK;
-}
-
-int smx_recon_export_vertices(smx_recon r, smx_stream s, const smx_buffer_desc* position_buffer,
-                              const smx_buffer_desc* color_buffer) {
-  SMX_CHECK_ARG(r && position_buffer && color_buffer);
-  SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
-  hipLaunchKernelGGL(k_export, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S,
-                     (float*)position_buffer->address, (uint8_t*)color_buffer->address, r->st);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int smx_recon_update_visualization_buffers(smx_recon r, smx_stream s, uint32_t frame_index,
-    uint32_t latest_triangulated_frame_index, uint32_t latest_mesh_surfel_count,
-    int32_t surfel_integration_active_window_size, int32_t flags,
-    float* vertex_buffer, uint32_t vertex_capacity,
-    uint32_t* neighbor_index_buffer, uint32_t neighbor_capacity,
-    float* normal_vertex_buffer, uint32_t normal_capacity) {
-  SMX_CHECK_ARG(r != nullptr && (flags & ~15) == 0);
-  // (one 16-byte record per slot for the vertex and neighbour buffers, 8-byte stores for the normal vertices)
-  SMX_CHECK_ARG(((uintptr_t)vertex_buffer & 15u) == 0 && ((uintptr_t)neighbor_index_buffer & 15u) == 0 &&
-                ((uintptr_t)normal_vertex_buffer & 7u) == 0);
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  const uint32_t vc_ = vertex_buffer ? vertex_capacity : 0u, nc_ = neighbor_index_buffer ? neighbor_capacity : 0u;
-  const uint32_t nvc_ = normal_vertex_buffer ? normal_capacity : 0u;
-  if (vc_ == 0 && nc_ == 0 && nvc_ == 0) return SMX_OK;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  VisColor vc;
-  vc.frame = frame_index; vc.window = surfel_integration_active_window_size; vc.flags = flags;
-  hipLaunchKernelGGL(k_vis_fill, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, vc, latest_triangulated_frame_index,
-                     latest_mesh_surfel_count, vc_ ? reinterpret_cast<float4*>(vertex_buffer) : nullptr, vc_,
-                     nc_ ? reinterpret_cast<uint4*>(neighbor_index_buffer) : nullptr, nc_,
-                     nvc_ ? reinterpret_cast<float2*>(normal_vertex_buffer) : nullptr, nvc_, r->st);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, const smx_buffer_desc* depth,
-                     const smx_buffer_desc* index, const smx_buffer_desc* normal, const smx_buffer_desc* color) {
-  SMX_CHECK_ARG(r != nullptr && p != nullptr);
-  SMX_CHECK_ARG(p->width > 0 && p->height > 0 && p->width <= 16384 && p->height <= 16384);
-  SMX_CHECK_ARG(std::isfinite(p->fx) && std::isfinite(p->fy) && p->fx > 0 && p->fy > 0 && std::isfinite(p->cx) && std::isfinite(p->cy));
-  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(p->global_T_camera[k]));
-  SMX_CHECK_ARG(std::isfinite(p->near_z) && p->near_z > 0 && p->far_z > p->near_z);
-  SMX_CHECK_ARG(p->splat_mode == SMX_SPLAT_SQUARE || p->splat_mode == SMX_SPLAT_DISC);
-  // (a splat's pixel rectangle is bounded by these: at most (2 x 1024 + 1)^2 pixels for one thread)
-  SMX_CHECK_ARG(p->splat_half_extent_in_pixels >= 0 && p->splat_half_extent_in_pixels <= 1024);
-  SMX_CHECK_ARG(p->max_splat_extent_in_pixels > 0 && p->max_splat_extent_in_pixels <= 1024);
-  SMX_CHECK_ARG(std::isfinite(p->disc_radius_factor) && p->disc_radius_factor > 0);
-  SMX_CHECK_ARG((p->color_flags & ~15) == 0);
-  SMX_CHECK_ARG(render_desc_ok(depth, p, 4) && render_desc_ok(index, p, 4) && render_desc_ok(normal, p, 16) &&
-                render_desc_ok(color, p, 4));
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  const size_t px = (size_t)p->width * p->height;
-  if (r->zbuf_px < px) {
-    if (r->zbuf) { SMX_HIP(hipDeviceSynchronize()); SMX_HIP(hipFree(r->zbuf)); r->zbuf = nullptr; r->zbuf_px = 0; }
-    r->render_busy = false;
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->zbuf), px * sizeof(unsigned long long)));
-    r->zbuf_px = px;
-  }
-  if (r->render_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_render, 0));   // (the previous render's resolve, on any stream)
-  RenderCtx rc;
-  {
-    const float* m = p->global_T_camera;
-    for (int i = 0; i < 3; ++i) {   // R^T, -(R^T t)
-      for (int k = 0; k < 3; ++k) rc.L[4 * i + k] = m[4 * k + i];
-      rc.L[4 * i + 3] = -(rc.L[4 * i + 0] * m[3] + rc.L[4 * i + 1] * m[7] + rc.L[4 * i + 2] * m[11]);
-    }
-    rc.Lf = se3_inverse(m);
-  }
-  rc.fx = p->fx; rc.fy = p->fy; rc.cx = p->cx; rc.cy = p->cy; rc.near_z = p->near_z; rc.far_z = p->far_z;
-  rc.half_extent = p->splat_half_extent_in_pixels;
-  rc.disc_factor = p->disc_radius_factor; rc.max_extent = p->max_splat_extent_in_pixels; rc.f_max = std::max(p->fx, p->fy);  // (float fields widened to double)
-  rc.W = p->width; rc.H = p->height; rc.mode = p->splat_mode;
-  VisColor vc;
-  vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
-  SMX_HIP(hipMemsetAsync(r->zbuf, 0xFF, px * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, r->zbuf, r->st);
-  hipLaunchKernelGGL(k_render_resolve, dim3(div_up(p->width, 64), div_up(p->height, 4)), dim3(kBlock), 0, st, r->S, rc, vc,
-                     r->zbuf, render_img<float>(depth), render_img<uint32_t>(index), render_img<float4>(normal),
-                     render_img<uint32_t>(color));
-  SMX_LAUNCH_CHECK();
-  SMX_HIP(hipEventRecord(r->ev_render, st));
-  r->render_busy = true;
-  return SMX_OK;
-}
-
-int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
-                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
-                    const smx_buffer_desc* model_normal_out) {
-  SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
-                result != nullptr);
-  const smx_track_params& p = *params;
-  SMX_CHECK_ARG(std::isfinite(depth_scaling) && depth_scaling > 0);
-  auto img_ok = [&](const smx_buffer_desc* d, size_t elem) {
-    return d->address && d->width == r->W && d->height == r->H && d->pitch >= (size_t)r->W * elem && d->pitch % elem == 0 &&
-           (uintptr_t)d->address % elem == 0;
-  };
-  SMX_CHECK_ARG(img_ok(depth, 2) && img_ok(normals, 8));
-  SMX_CHECK_ARG(!model_depth_out || img_ok(model_depth_out, 4));
-  SMX_CHECK_ARG(!model_normal_out || img_ok(model_normal_out, 16));
-  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(global_T_pred[k]));
-  int levels_used = 0;
-  for (int l = 0; l < kTrackLevels; ++l) {
-    SMX_CHECK_ARG(p.level_iterations[l] >= 0 && p.level_iterations[l] <= kTrackMaxIterationsPerLevel);
-    if (p.level_iterations[l] == 0) continue;
-    ++levels_used;
-    SMX_CHECK_ARG(p.level_stride[l] == 1 || p.level_stride[l] == 2 || p.level_stride[l] == 4 || p.level_stride[l] == 8);
-  }
-  SMX_CHECK_ARG(levels_used > 0);
-  SMX_CHECK_ARG(std::isfinite(p.max_distance) && p.max_distance > 0);
-  SMX_CHECK_ARG(p.max_normal_angle_deg > 0 && p.max_normal_angle_deg <= 180.0f);
-  SMX_CHECK_ARG(p.convergence_rotation >= 0 && p.convergence_translation >= 0 && p.min_inliers >= 0);
-  SMX_CHECK_ARG(p.min_inlier_fraction >= 0 && p.min_inlier_fraction <= 1 && p.min_pivot_ratio >= 0);
-  SMX_CHECK_ARG(std::isfinite(p.near_z) && p.near_z > 0 && p.far_z > p.near_z);
-  SMX_CHECK_ARG(std::isfinite(p.disc_radius_factor) && p.disc_radius_factor > 0);
-  SMX_CHECK_ARG(p.max_splat_extent_in_pixels > 0 && p.max_splat_extent_in_pixels <= 1024);
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  const size_t px = (size_t)r->W * r->H;
-  if (!r->trk_state) {
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_depth), px * sizeof(float)));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_normal), px * sizeof(float4)));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_slabs), sizeof(double) * kTrackMaxSlabs * kTrackSlabStride));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_state), sizeof(TrackDev)));
-  }
-  if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
-  // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
-  smx_render_params rp;
-  memset(&rp, 0, sizeof(rp));
-  rp.width = r->W; rp.height = r->H; rp.fx = r->fx; rp.fy = r->fy; rp.cx = r->cx; rp.cy = r->cy;
-  for (int k = 0; k < 12; ++k) rp.global_T_camera[k] = global_T_pred[k];
-  rp.near_z = p.near_z; rp.far_z = p.far_z; rp.splat_mode = SMX_SPLAT_DISC;
-  rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
-  rp.surfel_integration_active_window_size = 2147483647;
-  smx_buffer_desc dd, nd;
-  dd.address = r->trk_depth; dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
-  nd.address = r->trk_normal; nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
-  { const int rcr = smx_recon_render(r, s, &rp, &dd, nullptr, &nd, nullptr); if (rcr != SMX_OK) return rcr; }
-  if (model_depth_out)
-    SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
-                             hipMemcpyDeviceToDevice, st));
-  if (model_normal_out)
-    SMX_HIP(hipMemcpy2DAsync(model_normal_out->address, model_normal_out->pitch, nd.address, nd.pitch, nd.pitch, (size_t)r->H,
-                             hipMemcpyDeviceToDevice, st));
-  TrackBuffers tb;
-  tb.model_depth = r->trk_depth; tb.model_normal = r->trk_normal; tb.slabs = r->trk_slabs; tb.state = r->trk_state;
-  const int rct = track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred,
-                                p, result_on_device ? result : nullptr);
-  if (rct != SMX_OK) return rct;
-  SMX_HIP(hipEventRecord(r->ev_track, st));
-  r->track_busy = true;
-  if (!result_on_device) {
-    SMX_HIP(hipMemcpyAsync(result, &r->trk_state->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  return SMX_OK;
-}
-
-int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
-                                     int32_t* count) {
-  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  *count = 0;
-  if (!r->trk_state || !r->track_busy) return SMX_OK;
-  SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
-  int32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  n = std::max(0, std::min(n, (int32_t)kTrackRing));
-  const int32_t m = std::min(n, capacity);
-  if (m > 0) {
-    SMX_HIP(hipMemcpyAsync(records, r->trk_state->ring, sizeof(smx_track_iteration) * (size_t)m, hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  *count = n;
-  return SMX_OK;
-}
-
-int smx_recon_build_neighbor_index(smx_recon r, smx_stream s, smx_nn nn, float cell_size) {
-  SMX_CHECK_ARG(r != nullptr && nn != nullptr && cell_size > 0);
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  uint32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  if (n == 0) return smx_nn_build(nn, s, nullptr, nullptr, nullptr, 0, cell_size, 1);
-  int rc = acquire_staging(r, st, (size_t)3 * n);
-  if (rc != SMX_OK) return rc;
-  hipLaunchKernelGGL(k_index_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, r->staging, n);
-  SMX_LAUNCH_CHECK();
-  rc = smx_nn_build(nn, s, r->staging, r->staging + n, r->staging + (size_t)2 * n, n, cell_size, 1);
-  if (rc != SMX_OK) return rc;
-  return release_staging(r, st);
-}
-
-int smx_recon_neighbor_candidates(smx_recon r, smx_stream s, smx_nn nn, const uint32_t* surfel_indices,
-                                  uint32_t n_indices, float radius_factor_squared, int32_t k,
-                                  const uint8_t* state, uint8_t skip_mask, int32_t inputs_on_device,
-                                  uint32_t* out_idx, float* out_d2, int32_t* out_count, int32_t outputs_on_device) {
-  SMX_CHECK_ARG(r != nullptr && nn != nullptr && radius_factor_squared >= 0 && k >= 1 && k <= 64);
-  SMX_ON_DEVICE(r->device);
-  SMX_CHECK_ARG(n_indices == 0 || (surfel_indices && out_idx && out_d2 && out_count));
-  if (n_indices == 0) return SMX_OK;
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  // workspace owned by the object, grown only when a batch is larger than any before it (then, and only then, the
-  // device is synchronised: earlier batches may still be reading the old buffers)
-  if (n_indices > r->cand_cap) {
-    SMX_HIP(hipDeviceSynchronize());
-    if (r->cand_q) { SMX_HIP(hipFree(r->cand_q)); r->cand_q = nullptr; }
-    if (r->cand_slots) { SMX_HIP(hipFree(r->cand_slots)); r->cand_slots = nullptr; }
-    r->cand_cap = 0;
-    const size_t cap = (size_t)n_indices + n_indices / 8 + 1024;
-    int rca = dev_alloc(&r->cand_q, 4 * cap, false);
-    if (rca == SMX_OK) rca = dev_alloc(&r->cand_slots, cap, false);
-    if (rca != SMX_OK) return rca;
-    r->cand_cap = (uint32_t)cap;
-  }
-  const uint8_t* dstate = state;
-  const uint32_t* dslots = surfel_indices;
-  if (!inputs_on_device) {
-    SMX_HIP(hipMemcpyAsync(r->cand_slots, surfel_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, st));
-    dslots = r->cand_slots;
-    if (state) {
-      uint32_t n = 0;
-      SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
-      SMX_HIP(hipStreamSynchronize(st));
-      if (n > r->cand_state_cap) {
-        SMX_HIP(hipDeviceSynchronize());
-        if (r->cand_state) { SMX_HIP(hipFree(r->cand_state)); r->cand_state = nullptr; }
-        r->cand_state_cap = 0;
-        const int rca = dev_alloc(&r->cand_state, (size_t)r->S.pitch, false);
-        if (rca != SMX_OK) return rca;
-        r->cand_state_cap = (uint32_t)r->S.pitch;
-      }
-      if (n > 0) SMX_HIP(hipMemcpyAsync(r->cand_state, state, n, hipMemcpyHostToDevice, st));
-      dstate = r->cand_state;
-    }
-  }
-  float* q = r->cand_q;
-  const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_indices + kBlock - 1) / kBlock, 4096);
-  hipLaunchKernelGGL(k_candidate_queries, dim3(blocks), dim3(kBlock), 0, st, r->S, dslots, n_indices, r->st,
-                     radius_factor_squared, q);
-  SMX_LAUNCH_CHECK();
-  // (device inputs and outputs: nothing below allocates or synchronises either)
-  return smx_nn_query_batch(nn, s, n_indices, q, q + n_indices, q + (size_t)2 * n_indices, q + (size_t)3 * n_indices, k,
-                            dstate, skip_mask, 1, out_idx, out_d2, out_count, outputs_on_device);
-}
-
-int smx_recon_check_triangles(smx_recon r, smx_stream s, const uint32_t* triangles, uint32_t n_triangles,
-                              float long_edge_total_factor_squared, uint8_t* flags, int32_t on_device) {
-  SMX_CHECK_ARG(r != nullptr && (n_triangles == 0 || (triangles && flags)));
-  SMX_ON_DEVICE(r->device);
-  if (n_triangles == 0) return SMX_OK;
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  uint32_t* dtri = nullptr;
-  uint8_t* dflags = nullptr;
-  int rc = SMX_OK;
-  hipError_t e = hipSuccess;
-  auto fail = [&](hipError_t err) { set_error("check triangles failed: %s", hipGetErrorString(err)); rc = SMX_ERR_HIP; };
-  if (!on_device) {
-    if ((e = hipMalloc(reinterpret_cast<void**>(&dtri), (size_t)n_triangles * 12)) != hipSuccess) fail(e);
-    else if ((e = hipMalloc(reinterpret_cast<void**>(&dflags), n_triangles)) != hipSuccess) fail(e);
-    else if ((e = hipMemcpyAsync(dtri, triangles, (size_t)n_triangles * 12, hipMemcpyHostToDevice, st)) != hipSuccess) fail(e);
-  }
-  if (rc == SMX_OK) {
-    const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_triangles + kBlock - 1) / kBlock, 8192);
-    hipLaunchKernelGGL(k_check_triangles, dim3(blocks), dim3(kBlock), 0, st, r->S, on_device ? triangles : dtri,
-                       n_triangles, r->st, long_edge_total_factor_squared, on_device ? flags : dflags);
-    if ((e = hipGetLastError()) != hipSuccess) fail(e);
-  }
-  if (!on_device) {
-    if (rc == SMX_OK && (e = hipMemcpyAsync(flags, dflags, n_triangles, hipMemcpyDeviceToHost, st)) != hipSuccess) fail(e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess && rc == SMX_OK) fail(e);
-    if (dtri) (void)hipFree(dtri);
-    if (dflags) (void)hipFree(dflags);
-  }
-  return rc;
-}
-
-int smx_recon_triangulate(smx_recon r, smx_stream s, smx_nn nn, float cell_size, const smx_mesh_params* p,
-                          uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
-                          smx_mesh_stats* stats) {
-  SMX_CHECK_ARG(r != nullptr && nn != nullptr && p != nullptr && n_triangles != nullptr && cell_size > 0);
-  SMX_CHECK_ARG(triangles != nullptr || capacity == 0);
-  { const int rcp = mesh_check_params(*p); if (rcp != SMX_OK) return rcp; }
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  if (!r->mesh) { const int rcw = mesh_workspace_create(&r->mesh); if (rcw != SMX_OK) return rcw; }
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  { const int rcb = mesh_stamp_begin(r->mesh, st); if (rcb != SMX_OK) return rcb; }
-  // (the build orders st behind the pipelined regulariser, reads the slot count back and leaves merged slots out)
-  { const int rcb = smx_recon_build_neighbor_index(r, s, nn, cell_size); if (rcb != SMX_OK) return rcb; }
-  uint32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
-  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
-  return mesh_triangulate(r->mesh, st, nn, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0, r->S.quad(kGroupN, 1) - n0, n,
-                          *p, triangles, capacity, on_device, n_triangles, stats);
-}
-
-int smx_recon_debug_mesh_timings(smx_recon r, float out_ms[4]) {
-  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
-  SMX_ON_DEVICE(r->device);
-  return mesh_phase_ms(r->mesh, out_ms);
-}
-
-namespace {
-// the candidate lists of a device list of slots, by the route of smx_recon_neighbor_candidates
-int mesh_subset_lists(void* ctx, hipStream_t st, smx_nn nn, const uint32_t* slots, uint32_t n_slots, float factor_squared, int K,
-                      uint32_t* out_idx, float* out_d2, int32_t* out_count) {
-  return smx_recon_neighbor_candidates(static_cast<smx_recon>(ctx), (smx_stream)st, nn, slots, n_slots, factor_squared, K, nullptr,
-                                       0, 1, out_idx, out_d2, out_count, 1);
-}
-}  // namespace
-
-int smx_recon_triangulate_update(smx_recon r, smx_stream s, smx_nn nn, float cell_size, const smx_mesh_params* p,
-                                 float full_above_fraction, uint32_t* triangles, uint32_t capacity, int32_t on_device,
-                                 uint32_t* n_triangles, smx_mesh_stats* stats, smx_mesh_update_stats* update_stats) {
-  SMX_CHECK_ARG(r != nullptr && nn != nullptr && p != nullptr && n_triangles != nullptr && cell_size > 0);
-  SMX_CHECK_ARG(triangles != nullptr || capacity == 0);
-  SMX_CHECK_ARG(full_above_fraction < 0.0f || full_above_fraction <= 1.0f);
-  { const int rcp = mesh_check_params(*p); if (rcp != SMX_OK) return rcp; }
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  if (!r->mesh) { const int rcw = mesh_workspace_create(&r->mesh); if (rcw != SMX_OK) return rcw; }
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  uint32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
-  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
-  return mesh_triangulate_update(r->mesh, r->device, st, nn, cell_size, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0,
-                                 r->S.quad(kGroupN, 1) - n0, n, *p, full_above_fraction, mesh_subset_lists, r, triangles,
-                                 capacity, on_device, n_triangles, stats, update_stats);
-}
-
-int smx_recon_triangulate_reset(smx_recon r) {
-  SMX_CHECK_ARG(r != nullptr);
-  SMX_ON_DEVICE(r->device);
-  SMX_HIP(hipDeviceSynchronize());
-  return mesh_update_reset(r->mesh);
-}
-
-int smx_recon_debug_mesh_update_timings(smx_recon r, float out_ms[6]) {
-  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
-  SMX_ON_DEVICE(r->device);
-  return mesh_update_phase_ms(r->mesh, out_ms);
 }
 
 namespace {
@@ -4979,7 +3834,7 @@ int smx_recon_get_timings(smx_recon r, float out_ms[7]) {
   // all of its work precedes the end of the internal stream's queue (or of the caller's stream's, not pipelined).
   if (r->reg_pending) { SMX_HIP(hipEventRecord(r->ev_reg, r->reg_stream)); SMX_HIP(hipEventSynchronize(r->ev_reg)); }
   if (!r->reg_pending || !r->overlap_enabled) SMX_HIP(hipStreamSynchronize(r->last_stream));
-  { const int rc = copy_stamp_ring(r); if (rc != SMX_OK) return rc; }
+  SMX_CALL(copy_stamp_ring(r));
   (void)stage_ms_from_stamps(r->ts_host + (size_t)(r->ts_seq % kTsRing) * kTsWords, r->ts_seq, r->wall_khz, out_ms);
   return SMX_OK;
 }
@@ -4988,7 +3843,7 @@ int smx_recon_debug_stamp_ring(smx_recon r, uint64_t* out, int32_t capacity_word
   SMX_CHECK_ARG(r != nullptr && out != nullptr && capacity_words >= kTsRing * kTsWords);
   SMX_ON_DEVICE(r->device);
   // (measurement: the raw stamp records of the last calls, read from the device ring -- the caller has synchronised)
-  { const int rc = copy_stamp_ring(r); if (rc != SMX_OK) return rc; }
+  SMX_CALL(copy_stamp_ring(r));
   for (int k = 0; k < kTsRing * kTsWords; ++k) out[k] = r->ts_host[k];
   if (wall_clock_khz) *wall_clock_khz = r->wall_khz;
   return SMX_OK;
@@ -5016,185 +3871,64 @@ int smx_recon_get_timings_nowait(smx_recon r, float out_ms[7], uint64_t* call_nu
   return SMX_OK;
 }
 
-int smx_recon_debug_download_surfels(smx_recon r, smx_stream s, float* rows, uint32_t count) {
-  SMX_CHECK_ARG(r != nullptr && rows != nullptr && count <= r->max_surfels);
+int smx_recon_set_delta_tracking(smx_recon r, smx_stream s, int32_t enabled) {
+  SMX_CHECK_ARG(r != nullptr && (enabled == 0 || enabled == 1));
   SMX_ON_DEVICE(r->device);
-  if (count == 0) return SMX_OK;
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
-  int rc = acquire_staging(r, (hipStream_t)s, (size_t)kRows * count);
-  if (rc != SMX_OK) return rc;
-  RowList rl;
-  rl.n = kRows;
-  for (int k = 0; k < kRows; ++k) rl.rows[k] = k;
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S, rl, r->staging, count);
-  SMX_HIP(hipMemcpyAsync(rows, r->staging, (size_t)kRows * count * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
-  SMX_HIP(hipStreamSynchronize((hipStream_t)s));
-  return SMX_OK;
-}
-
-// After surfel attributes were changed from outside the frame loop (state upload, deformation): drop the work
-// lists and segment boxes (count 0 = no box, the segment is scanned) and rebuild the flag table -- its detach bits
-// come from the colour words, the recent bits are refreshed per frame.
-static int invalidate_derived(smx_recon r, hipStream_t st) {
-  SMX_HIP(hipMemsetAsync(r->L.vis_seg, 0, (size_t)r->nseg * 4, st));
-  SMX_HIP(hipMemsetAsync(r->L.seg_box, 0, (size_t)r->nseg * 8 * sizeof(float), st));
-  SMX_HIP(hipMemsetAsync(r->L.recent_seg, 0, (size_t)r->nsegB * 4, st));
-  SMX_HIP(hipMemsetAsync(r->vis_count_set[0], 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
-  SMX_HIP(hipMemsetAsync(r->vis_count_set[1], 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
-  SMX_HIP(hipMemsetAsync(r->L.rec_chunks.count, 0, sizeof(uint32_t) * kSubLists * kCountStride, st));
-  hipLaunchKernelGGL(k_rebuild_flags, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, 0u, 0x7FFFFFFF, r->L.flags8, r->st);
-  SMX_LAUNCH_CHECK();
-  r->table_valid = false;
-  r->hot_holdoff = 3;     // (flags and links may have been rewritten: pass B gathers everything for two calls)
-  r->have_frame = false;  // (the boxes are gone, so any frame index may follow)
-  return SMX_OK;
-}
-
-int smx_recon_debug_upload_surfels(smx_recon r, smx_stream s, const float* rows, uint32_t count, uint32_t merge_count) {
-  SMX_CHECK_ARG(r != nullptr && count <= r->max_surfels && (rows != nullptr || count == 0));
-  SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
   hipStream_t st = (hipStream_t)s;
-  if (count) {
-    int rc = acquire_staging(r, st, (size_t)kRows * count);
+  SMX_CALL(join_regularizer(r, st));
+  SMX_HIP(hipStreamSynchronize(st));  // no kernel may be using the pointer that changes here
+  if (enabled && !r->L.dirty8) {
+    int rc = dev_alloc(&r->L.dirty8, (size_t)r->nseg * kSeg, false);
+    if (rc == SMX_OK && !r->delta_seg) rc = dev_alloc(&r->delta_seg, (size_t)r->nseg, true);
+    if (rc == SMX_OK && !r->delta_total) rc = dev_alloc(&r->delta_total, 1, true);
     if (rc != SMX_OK) return rc;
-    SMX_HIP(hipMemcpyAsync(r->staging, rows, (size_t)kRows * count * 4, hipMemcpyHostToDevice, st));
-    RowList rl;
-    rl.n = kRows;
-    for (int k = 0; k < kRows; ++k) rl.rows[k] = k;
-    hipLaunchKernelGGL(k_unpack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging, count);
+    SMX_HIP(hipMemset(r->L.dirty8, 1, (size_t)r->nseg * kSeg));  // everything that exists counts as changed
+  } else if (!enabled && r->L.dirty8) {
+    SMX_HIP(hipFree(r->L.dirty8));
+    r->L.dirty8 = nullptr;
   }
-  DevState h;
-  memset(&h, 0, sizeof(h));
-  h.surfel_count = count; h.merge_count = merge_count;
-  SMX_HIP(hipMemcpyAsync(r->st, &h, sizeof(h), hipMemcpyHostToDevice, st));
-  SMX_HIP(hipMemsetAsync(r->grad_acc, 0, 2 * r->S.pitch * sizeof(long long), st));
-  SMX_HIP(hipMemsetAsync(r->fb.count, 0, (size_t)r->nsegB * kCountStride * sizeof(uint32_t), st));
-  SMX_HIP(hipMemsetAsync(r->merge_flag, 0, r->S.pitch, st));
-  if (r->L.dirty8) SMX_HIP(hipMemsetAsync(r->L.dirty8, 1, (size_t)r->nseg * kSeg, st));
-  int rc = invalidate_derived(r, st);
-  if (rc != SMX_OK) return rc;
-  SMX_HIP(hipStreamSynchronize(st));
   return SMX_OK;
 }
 
-int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t capacity, int32_t on_device,
-                      uint32_t* new_size, uint32_t* links_dropped) {
-  SMX_CHECK_ARG(r != nullptr);
+int smx_recon_transfer_changed_to_cpu(smx_recon r, smx_stream s, uint32_t frame_index, smx_surfel_delta_cpu* d) {
+  SMX_CHECK_ARG(r != nullptr && d != nullptr);
   SMX_ON_DEVICE(r->device);
+  if (!r->L.dirty8) { set_error("delta tracking is off (smx_recon_set_delta_tracking)"); return SMX_ERR_INVALID_ARGUMENT; }
   hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  uint32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_CALL(join_regularizer(r, st));
+  hipLaunchKernelGGL(k_delta_count, dim3(r->nseg), dim3(kBlock), 0, st, r->L.dirty8, r->delta_seg, r->st);
+  enqueue_segment_scan(st, r->delta_seg, r->nseg, r->delta_total);
+  SMX_LAUNCH_CHECK();
+  uint32_t total = 0, n = 0;
+  SMX_HIP(hipMemcpyAsync(&total, r->delta_total, 4, hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
-  if (old_to_new && capacity < n) {   // (nothing has been changed yet)
-    set_error("old_to_new holds %u entries, the map has %u slots", capacity, n);
+  d->frame_index = frame_index;
+  d->surfel_count = n;
+  d->count = total;
+  if (total > d->capacity) {  // (the marks are untouched: call again with larger arrays)
+    set_error("delta of %u slots does not fit the capacity %u", total, d->capacity);
     return SMX_ERR_INVALID_ARGUMENT;
   }
-  if (!r->cmp_map) {
-    int rc = dev_alloc(&r->cmp_map, r->S.pitch, false);
-    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_seg, (size_t)r->nseg, false);
-    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_out, 2, false);
-    if (rc != SMX_OK) return rc;
-  }
-  SMX_HIP(hipMemsetAsync(r->cmp_out, 0, 2 * sizeof(uint32_t), st));
-  const dim3 b(kBlock);
-  if (n) {
-    const int nseg_used = div_up((long long)n, kSeg);
-    // (merge_flag -- one byte per slot, reset below -- holds the keep bits: a byte per four slots)
-    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, r->cmp_seg);
-    hipLaunchKernelGGL(k_delta_scan, dim3(1), dim3(1024), 0, st, r->cmp_seg, nseg_used, r->cmp_out);
-    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, r->cmp_seg, n, r->cmp_map);
-    SMX_LAUNCH_CHECK();
-    int rc = acquire_staging(r, st, (size_t)4 * n);
-    if (rc != SMX_OK) return rc;
-    float4* tmp = reinterpret_cast<float4*>(r->staging);
-    const int groups[5] = {kGroupP, kGroupS, kGroupN, kGroupC, kGroupT};
-    for (int g : groups) {
-      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
-      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
-      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, r->cmp_out);
-    }
-    SMX_LAUNCH_CHECK();
-    rc = release_staging(r, st);
-    if (rc != SMX_OK) return rc;
-  }
-  // Derived state: everything a state upload resets (smx_recon_debug_upload_surfels), and the state an upload of the
-  // same slots never had to care about, because compaction changes WHICH SLOT a byte belongs to:
-  //  * both copies of the double-buffered flag table: zeroed, the current one rebuilt from the records, and copied
-  //    into the other (pass A of the next call reads the current copy; the other one is relied on through seg_streak);
-  //  * seg_streak = 0: a streak >= 2 means "the copy written two calls ago already holds this segment's bytes";
-  //  * hot_epoch = this call's epoch: every group counts as hot for the next calls (a group that looks hot only costs
-  //    gathers; the hold-off of invalidate_derived keeps pass B unfiltered for two calls in any case, after which
-  //    every mark it reads has been written after the compaction);
-  //  * seg_targets = all groups: a superset of the groups a segment's links point into, which is all the skip test
-  //    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
-  // The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
-  // has been read again, and reading a segment resets its streak).
-  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, r->cmp_out);
-  SMX_HIP(hipMemsetAsync(r->grad_acc, 0, 2 * r->S.pitch * sizeof(long long), st));
-  SMX_HIP(hipMemsetAsync(r->fb.count, 0, (size_t)r->nsegB * kCountStride * sizeof(uint32_t), st));
-  SMX_HIP(hipMemsetAsync(r->merge_flag, 0, r->S.pitch, st));
-  if (r->L.dirty8)
-    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), r->cmp_out);
-  SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
-  SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
-  SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
-  SMX_HIP(hipMemsetAsync(r->L.hot_epoch, (int)(r->L.epoch & 255u), (size_t)r->L.n_hot_groups + 64, st));
-  SMX_HIP(hipMemsetAsync(r->L.seg_targets, 0xFF, (size_t)r->nsegB * kBlockB * sizeof(uint16_t), st));
-  { const int rci = invalidate_derived(r, st); if (rci != SMX_OK) return rci; }   // (rebuilds the current flag table)
-  uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
-  SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
-  if (old_to_new && n)
-    SMX_HIP(hipMemcpyAsync(old_to_new, r->cmp_map, (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  uint32_t out[2] = {0, 0};
-  SMX_HIP(hipMemcpyAsync(out, r->cmp_out, sizeof(out), hipMemcpyDeviceToHost, st));
+  if (total == 0) return SMX_OK;
+  SMX_CHECK_ARG(d->surfel_index && d->x && d->y && d->z && d->radius_squared && d->normal_x && d->normal_y &&
+                d->normal_z && d->last_update_stamp);
+  SMX_CALL(acquire_staging(r, st, (size_t)9 * total));
+  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg, r->staging, total,
+                     r->st);
+  SMX_LAUNCH_CHECK();
+  void* dst[9] = {d->surfel_index, d->x, d->y, d->z, d->radius_squared, d->normal_x, d->normal_y, d->normal_z,
+                  d->last_update_stamp};
+  for (int k = 0; k < 9; ++k)
+    SMX_HIP(hipMemcpyAsync(dst[k], r->staging + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
-  if (new_size) *new_size = out[0];
-  if (links_dropped) *links_dropped = out[1];
   return SMX_OK;
-}
-
-int smx_recon_deform_by_creation_frame(smx_recon r, smx_stream s, const float* frame_T, uint32_t n_frames,
-                                       const uint8_t* reactivate, uint32_t frame_index, int32_t inputs_on_device) {
-  SMX_CHECK_ARG(r != nullptr && (n_frames == 0 || frame_T != nullptr));
-  SMX_ON_DEVICE(r->device);
-  if (n_frames == 0) return SMX_OK;
-  hipStream_t st = (hipStream_t)s;
-  { const int rcj = join_regularizer(r, st); if (rcj != SMX_OK) return rcj; }
-  float* dT = nullptr;
-  uint8_t* dre = nullptr;
-  int rc = SMX_OK;
-  hipError_t e = hipSuccess;
-  auto fail = [&](hipError_t err) { set_error("deform failed: %s", hipGetErrorString(err)); rc = SMX_ERR_HIP; };
-  if (!inputs_on_device) {
-    if ((e = hipMalloc(reinterpret_cast<void**>(&dT), (size_t)n_frames * 48)) != hipSuccess) fail(e);
-    else if ((e = hipMemcpyAsync(dT, frame_T, (size_t)n_frames * 48, hipMemcpyHostToDevice, st)) != hipSuccess) fail(e);
-    if (rc == SMX_OK && reactivate) {
-      if ((e = hipMalloc(reinterpret_cast<void**>(&dre), n_frames)) != hipSuccess) fail(e);
-      else if ((e = hipMemcpyAsync(dre, reactivate, n_frames, hipMemcpyHostToDevice, st)) != hipSuccess) fail(e);
-    }
-  }
-  if (rc == SMX_OK) {
-    hipLaunchKernelGGL(k_deform_by_creation_frame, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S,
-                       inputs_on_device ? frame_T : dT, n_frames, inputs_on_device ? reactivate : dre, frame_index,
-                       r->L.dirty8, r->st);
-    if ((e = hipGetLastError()) != hipSuccess) fail(e);
-  }
-  // positions and stamps changed behind the work lists, segment boxes and the flag table
-  if (rc == SMX_OK) rc = invalidate_derived(r, st);
-  if (!inputs_on_device) {
-    if ((e = hipStreamSynchronize(st)) != hipSuccess && rc == SMX_OK) fail(e);
-    if (dT) (void)hipFree(dT);
-    if (dre) (void)hipFree(dre);
-  }
-  return rc;
 }
 
 int smx_recon_debug_download_scratch(smx_recon r, smx_stream s, int32_t which, void* dst) {
   SMX_CHECK_ARG(r != nullptr && dst != nullptr);
   SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
+  SMX_CALL(join_regularizer(r, (hipStream_t)s));
   hipStream_t st = (hipStream_t)s;
   const size_t P = (size_t)r->W * r->H;
   const void* src = nullptr; size_t bytes = 0;
@@ -5220,7 +3954,7 @@ int smx_recon_debug_download_scratch(smx_recon r, smx_stream s, int32_t which, v
 int smx_recon_debug_count_skipped_segments(smx_recon r, smx_stream s, uint32_t* out) {
   SMX_CHECK_ARG(r != nullptr && out != nullptr);
   SMX_ON_DEVICE(r->device);
-  { const int rcj = join_regularizer(r, (hipStream_t)s); if (rcj != SMX_OK) return rcj; }
+  SMX_CALL(join_regularizer(r, (hipStream_t)s));
   std::vector<uint32_t> marks((size_t)r->nsegB);
   SMX_HIP(hipMemcpyAsync(marks.data(), r->L.recent_seg, marks.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));

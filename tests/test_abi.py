@@ -29,6 +29,15 @@ def test_header_symbols_are_exported():
     assert sorted(DRIVER_EXPORTS) == driver
 
 
+def test_source_list_matches_csrc():
+    """build.SOURCES is the one list of translation units (the variant scripts under tools/ read it too): every
+    source file in csrc/ is in it and the other way round."""
+    from surfelmeshing_amd import build
+    on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp")))
+    assert sorted(build.SOURCES) == on_disk
+    assert len(set(build.SOURCES)) == len(build.SOURCES)
+
+
 def test_integrate_params_layout_matches_oracle_and_header():
     from surfelmeshing_amd._lib import IntegrateParams, BufferDesc, SurfelBuffersCPU
     import oracle

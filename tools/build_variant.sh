@@ -9,7 +9,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd); C=$ROOT/surfelmeshing_amd/csrc; O=$ROOT/
 mkdir -p $O
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -I $ROOT/include -I $C"
 OBJS=""
-for s in smx_buffer.hip smx_depth.hip smx_recon.hip smx_nn.hip smx_synth.hip smx_driver.cpp; do
+for s in $(cd $ROOT && python3 -c "from surfelmeshing_amd.build import SOURCES; print(' '.join(SOURCES))"); do
   b=${s%.*}
   if echo " $SRCS " | grep -q " $s "; then
     X=""; [ "${s##*.}" = cpp ] && X="-x hip"

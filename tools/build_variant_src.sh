@@ -4,5 +4,6 @@ set -e
 N=$1; SRC=$2; shift; shift
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/surfelmeshing_amd/csrc
 mkdir -p $R/build/ab
+OBJS=$(cd $R && python3 -c "from surfelmeshing_amd.build import SOURCES; print(' '.join('$C/' + s.rsplit('.', 1)[0] + '.o' for s in SOURCES))")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -I $R/include -I $C "$@" -x hip -c $SRC -o $R/build/ab/recon_$N.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/build/ab/libsmx_$N.so $C/smx_buffer.o $C/smx_depth.o $R/build/ab/recon_$N.o $C/smx_nn.o $C/smx_synth.o $C/smx_driver.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/build/ab/libsmx_$N.so ${OBJS/$C\/smx_recon.o/$R/build/ab/recon_$N.o}

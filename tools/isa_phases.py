@@ -5,6 +5,7 @@ since the previous such wait, in program order, plus registers and LDS.  A kerne
 need few phases; a loop of `load; wait; use` shows up as many.  (Branches are ignored: it is an upper bound per path.)
 
     python tools/isa_phases.py surfelmeshing_amd/csrc/smx_recon.hip [kernel-substring ...]
+(the frame kernels; the map services' kernels -- k_compact_*, k_render_*, k_vis_fill ... -- are in smx_recon_map.hip)
 """
 import os
 import re

@@ -1,6 +1,7 @@
 #!/bin/bash
 # bash tools/isa_regs.sh <source.hip> [pattern] [extra hipcc flags]: registers, LDS and scratch of the kernels of one source
 # file (device-only compile to assembly), to see what a change did to the occupancy before it goes to the GPU box.
+# (smx_recon.hip: the frame kernels and k_delta_*; smx_recon_map.hip: k_compact_*, k_render_*, k_vis_fill, k_pack_rows ...)
 SRC=$1; PAT=${2:-.}; shift; shift
 R=$(cd "$(dirname "$0")/.." && pwd); mkdir -p $R/build/isa
 OUT=$R/build/isa/$(basename $SRC .hip).s
