@@ -108,6 +108,12 @@ int smx_debug_marker(smx_stream s, int32_t id);
 /* (measurement) n ping-pongs of an empty kernel between two streams, each leg handed over by an event record + a stream wait:
  * mean time per leg in microseconds.  Synchronises both streams. */
 int smx_debug_handover_probe(smx_stream a, smx_stream b, int32_t n, float* us_per_handover);
+/* (measurement, process-wide) the device and page-locked host blocks smx_recon, smx_nn and the mesh workspace hold at this
+ * moment, and their bytes (smx_buffer and smx_host_alloc are not counted).  Either pointer may be null. */
+int smx_debug_live_allocations(uint64_t* blocks, uint64_t* bytes);
+/* (test hook, process-wide) makes the nth next allocation of those objects (0 = the next one) fail with the out-of-memory
+ * error -- on the host, HIP is not called -- and disarms itself; nth < 0 disarms a pending one. */
+int smx_debug_fail_allocation(int32_t nth);
 
 /* ---- CUDABuffer<T>  (VIS/cuda/cuda_buffer.h:45-129, cuda_buffer_inl.h:36-172) ---- */
 /* CUDABuffer(int height, int width): cudaMallocPitch */

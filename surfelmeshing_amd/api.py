@@ -171,6 +171,18 @@ def StreamSynchronize(stream=None):
     _lib.check(_lib.load().smx_stream_synchronize(_sv(stream)))
 
 
+def DebugLiveAllocations():
+    """(blocks, bytes) of device and page-locked memory the library's objects hold right now (smx_debug_live_allocations)."""
+    blocks, nbytes = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.load().smx_debug_live_allocations(C.byref(blocks), C.byref(nbytes)))
+    return blocks.value, nbytes.value
+
+
+def DebugFailAllocation(nth):
+    """Test hook: the nth next allocation of the library's objects fails (0 = the next one), nth < 0 disarms."""
+    _lib.check(_lib.load().smx_debug_fail_allocation(C.c_int32(nth)))
+
+
 class CUDABuffer:
     """CUDABuffer<T>(height, width): pitched 2-D device memory.  `dtype` is the numpy scalar type
     and `channels` the number of scalars per element (float2 -> (np.float32, 2), Vec3u8 -> (np.uint8, 3))."""

@@ -76,6 +76,17 @@ int smx_debug_marker(smx_stream s, int32_t id) {
   return SMX_OK;
 }
 
+int smx_debug_live_allocations(uint64_t* blocks, uint64_t* bytes) {
+  if (blocks) *blocks = mem_live_blocks.load();
+  if (bytes) *bytes = mem_live_bytes.load();
+  return SMX_OK;
+}
+
+int smx_debug_fail_allocation(int32_t nth) {
+  mem_fail_in.store(nth < 0 ? -1 : nth);
+  return SMX_OK;
+}
+
 const char* smx_last_error(void) { return g_error; }
 
 int smx_runtime_advice(char* text, size_t capacity) { return runtime_advice(text, capacity); }

@@ -8,12 +8,21 @@
 // camera-space z it produces is bit-identical across kernels (the reference
 // relies on the same property, APP/cuda_surfel_reconstruction_kernels.cu:775,
 // 1613, 1885 against :1463).
+//
+// Device memory (DESIGN.md "Who owns device memory"): mem_acquire / mem_release are the one way in and out for the
+// device and page-locked blocks of the objects, DevBuf<T> owns a block that may grow, DevBlocks the fixed blocks
+// of an object whose kernel-argument structs keep plain pointers to them.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <utility>
+#include <vector>
 
 #include "smx.h"
 
@@ -96,6 +105,99 @@ inline int resolve_device(int32_t device_id, int* out) {
   *out = dev;
   return SMX_OK;
 }
+
+// ---- device memory: one funnel, two owners ------------------------------------------------------------------------------
+// Every device and page-locked host block of smx_recon, smx_nn and the mesh workspace is taken and given back here, so
+// that the blocks and bytes alive can be counted (smx_debug_live_allocations) and a failure injected on the host
+// (smx_debug_fail_allocation).  `kind` of a block: kDeviceMemory, or the hipHostMalloc flags of a page-locked one.
+constexpr unsigned kDeviceMemory = 0xFFFFFFFFu;
+inline std::atomic<uint64_t> mem_live_blocks{0}, mem_live_bytes{0};
+inline std::atomic<int64_t> mem_fail_in{-1};   // allocations to go before the one that fails; < 0: not armed
+
+inline hipError_t mem_acquire(void** p, size_t bytes, unsigned kind = kDeviceMemory) {
+  *p = nullptr;
+  int64_t c = mem_fail_in.load();
+  while (c >= 0 && !mem_fail_in.compare_exchange_weak(c, c - 1)) {}
+  if (c == 0) return hipErrorOutOfMemory;   // (the injected failure: HIP is not called, and the hook is disarmed)
+  const hipError_t e = kind == kDeviceMemory ? hipMalloc(p, bytes) : hipHostMalloc(p, bytes, kind);
+  if (e == hipSuccess) { mem_live_blocks += 1; mem_live_bytes += bytes; }
+  return e;
+}
+inline void mem_release(void* p, size_t bytes, unsigned kind = kDeviceMemory) {
+  if (!p) return;
+  (void)(kind == kDeviceMemory ? hipFree(p) : hipHostFree(p));
+  mem_live_blocks -= 1; mem_live_bytes -= bytes;
+}
+
+// Move-only owner of one device block of T.  The destructor frees and never synchronises: whoever lets go of a block
+// that enqueued work may still use -- by growing it, resetting it or destroying its object -- orders that behind the
+// work first, at the call site.
+template <typename T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { DevBuf(std::move(o)).swap(*this); return *this; }   // (the old block goes with the temporary)
+  void swap(DevBuf& o) noexcept { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); }
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  size_t capacity() const { return bytes_ / sizeof(T); }   // elements
+  void reset() { mem_release(p_, bytes_); p_ = nullptr; bytes_ = 0; }
+  // Exactly `count` elements (at least one); what the buffer held is freed first, and it stays empty on failure.
+  int alloc(size_t count, bool zero) {
+    reset();
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    void* q = nullptr;
+    SMX_HIP(mem_acquire(&q, bytes));
+    p_ = static_cast<T*>(q); bytes_ = bytes;
+    if (zero) SMX_HIP(hipMemset(q, 0, bytes));
+    return SMX_OK;
+  }
+  // Room for `want` elements; a buffer that has to grow gets an eighth more, and its contents are discarded ...
+  int reserve(size_t want) { return want <= capacity() ? SMX_OK : alloc(want + want / 8 + 1024, false); }
+  // ... or its first `keep` elements are copied over on st, which is synchronised before the old block goes.
+  int reserve_keep(size_t want, size_t keep, hipStream_t st) {
+    if (want <= capacity()) return SMX_OK;
+    DevBuf fresh;
+    SMX_CALL(fresh.alloc(want + want / 8 + 1024, false));
+    if (p_ && keep > 0) {
+      SMX_HIP(hipMemcpyAsync(fresh.p_, p_, std::min(keep, capacity()) * sizeof(T), hipMemcpyDeviceToDevice, st));
+      SMX_HIP(hipStreamSynchronize(st));
+    }
+    *this = std::move(fresh);
+    return SMX_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// The fixed blocks of an object, recorded as they are allocated and given back together.  The pointers go to plain
+// members and to the structs that kernels take by value (views: they own nothing).
+class DevBlocks {
+ public:
+  DevBlocks() = default;
+  DevBlocks(const DevBlocks&) = delete;
+  DevBlocks& operator=(const DevBlocks&) = delete;
+  ~DevBlocks() { for (const Block& b : blocks_) mem_release(b.p, b.bytes, b.kind); }
+  template <typename T>
+  int alloc(T** p, size_t count, bool zero, unsigned kind = kDeviceMemory) {
+    void* q = nullptr;
+    SMX_HIP(mem_acquire(&q, count * sizeof(T), kind));
+    blocks_.push_back(Block{q, count * sizeof(T), kind});
+    *p = static_cast<T*>(q);
+    if (zero) SMX_HIP(hipMemset(q, 0, count * sizeof(T)));
+    return SMX_OK;
+  }
+  // (page-locked host memory; mapped = the device can address it too)
+  template <typename T>
+  int alloc_host(T** p, size_t count, bool mapped) { return alloc(p, count, false, mapped ? hipHostMallocMapped : hipHostMallocDefault); }
+
+ private:
+  struct Block { void* p; size_t bytes; unsigned kind; };
+  std::vector<Block> blocks_;
+};
 
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;
 

@@ -20,6 +20,7 @@
 //                    their kept run of the previous output
 // The arithmetic is in smx_mesh.hpp; nothing here decides a sign by itself.
 #include <algorithm>
+#include <memory>
 #include <cmath>
 
 #include "smx_mesh.hpp"
@@ -418,83 +419,55 @@ k_mesh_worklist(uint32_t n, const uint8_t* __restrict__ changed, const int32_t* 
   }
 }
 
-template <typename T>
-int grow(T** p, size_t* cap, size_t want) {
-  if (want <= *cap) return SMX_OK;
-  if (*p) { SMX_HIP(hipFree(*p)); *p = nullptr; }
-  *cap = 0;
-  const size_t c = want + want / 8 + 1024;
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(p), c * sizeof(T)));
-  *cap = c;
-  return SMX_OK;
-}
-
-// ... keeping the first `keep` elements (the kept state of the update)
-template <typename T>
-int grow_keep(T** p, size_t* cap, size_t want, size_t keep, hipStream_t st) {
-  if (want <= *cap) return SMX_OK;
-  const size_t c = want + want / 8 + 1024;
-  T* fresh = nullptr;
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), c * sizeof(T)));
-  if (*p && keep > 0) {
-    const hipError_t e = hipMemcpyAsync(fresh, *p, std::min(keep, *cap) * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) { (void)hipFree(fresh); SMX_HIP(e); }
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  if (*p) SMX_HIP(hipFree(*p));
-  *p = fresh;
-  *cap = c;
-  return SMX_OK;
-}
-
 }  // namespace
 
+// The kept state of smx_recon_triangulate_update and its workspace (rings and meta of the workspace belong to it while
+// `have` is set).  mesh_update_reset puts a fresh one in its place.
+struct MeshUpdate {
+  bool have = false;
+  bool utimed = false;
+  uint32_t n_prev = 0, t_prev = 0;
+  smx_mesh_params prm{};
+  smx_mesh_stats last_stats{};
+  int cur = 0;                                                   // which of the double-buffered sets holds the kept output
+  DevBuf<float4> snap_s, snap_n; DevBuf<uint32_t> kept;          // [n]
+  DevBuf<uint32_t> utri[2], ulocal[2], ublock[2];
+  DevBuf<uint8_t> changed, in_a; DevBuf<uint32_t> work;          // [n]
+  DevBuf<float> rows, reverse_r2; DevBuf<uint8_t> state;         // [n + ghosts]
+  DevBuf<float> reverse_rows; DevBuf<uint32_t> near_bits;        // the coarse filter
+  DevBuf<uint32_t> reverse_idx; DevBuf<float> reverse_d2; DevBuf<int32_t> reverse_count;   // [n + ghosts]
+  smx_nn reverse_nn = nullptr;                                   // the index of the reverse test
+};
+
+// (created value-initialised: events null, buffers empty)
 struct MeshWorkspace {
-  uint32_t* lists; float* d2; size_t lists_cap, d2_cap;          // [n][K]
-  int32_t* counts; float* r2; uint32_t* meta; uint32_t* local_off; size_t counts_cap, r2_cap, meta_cap, local_cap;   // [n]
-  uint32_t* rings; size_t rings_cap;                             // [n][16]
-  uint32_t* block_sums; uint32_t* block_off; size_t sums_cap, off_cap;
-  uint32_t* tri; size_t tri_cap;                                 // [T][3] when the caller's buffer is host memory
-  uint32_t* stat;
+  DevBuf<uint32_t> lists; DevBuf<float> d2;                      // [n][K]
+  DevBuf<int32_t> counts; DevBuf<float> r2; DevBuf<uint32_t> meta, local_off;   // [n]
+  DevBuf<uint32_t> rings;                                        // [n][16]
+  DevBuf<uint32_t> block_sums, block_off;
+  DevBuf<uint32_t> tri;                                          // [T][3] when the caller's buffer is host memory
+  DevBuf<uint32_t> stat;
   hipEvent_t ev[5];
   bool timed;
-  // smx_recon_triangulate_update: the kept state (rings and meta above belong to it while `have` is set) ...
-  bool have;
-  uint32_t n_prev, t_prev;
-  smx_mesh_params prm;
-  smx_mesh_stats last_stats;
-  int cur;                                                       // which of the double-buffered sets holds the kept output
-  float4* snap_s; float4* snap_n; uint32_t* kept; size_t snap_s_cap, snap_n_cap, kept_cap;                  // [n]
-  uint32_t* utri[2]; uint32_t* ulocal[2]; uint32_t* ublock[2]; size_t utri_cap[2], ulocal_cap[2], ublock_cap[2];
-  // ... and its workspace
-  uint8_t* changed; uint8_t* in_a; uint32_t* work; size_t changed_cap, in_a_cap, work_cap;                   // [n]
-  float* rows; float* reverse_r2; uint8_t* state; size_t rows_cap, reverse_r2_cap, state_cap;                // [n + ghosts]
-  float* reverse_rows; size_t reverse_rows_cap; uint32_t* near_bits;                                         // the coarse filter
-  uint32_t* reverse_idx; float* reverse_d2; int32_t* reverse_count; size_t ridx_cap, rd2_cap, rcount_cap;     // [n + ghosts]
-  smx_nn reverse_nn;                                             // the index of the reverse test
+  MeshUpdate upd;
   hipEvent_t uev[8];
-  bool utimed;
+  ~MeshWorkspace() {
+    (void)mesh_update_reset(this);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : uev) if (e) (void)hipEventDestroy(e);
+  }
 };
 
 int mesh_workspace_create(MeshWorkspace** out) {
-  MeshWorkspace* w = new MeshWorkspace();
-  memset(w, 0, sizeof(*w));
-  *out = w;
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(&w->stat), kStWords * sizeof(uint32_t)));
+  std::unique_ptr<MeshWorkspace> w(new MeshWorkspace());
+  SMX_CALL(w->stat.alloc(kStWords, false));
   for (int i = 0; i < 5; ++i) SMX_HIP(hipEventCreate(&w->ev[i]));
   for (int i = 0; i < 8; ++i) SMX_HIP(hipEventCreate(&w->uev[i]));
+  *out = w.release();   // (a complete workspace or none)
   return SMX_OK;
 }
 
-void mesh_workspace_destroy(MeshWorkspace* w) {
-  if (!w) return;
-  void* ptrs[] = {w->lists, w->d2, w->counts, w->r2, w->meta, w->local_off, w->rings, w->block_sums, w->block_off, w->tri, w->stat};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (int i = 0; i < 5; ++i) if (w->ev[i]) (void)hipEventDestroy(w->ev[i]);
-  (void)mesh_update_reset(w);
-  for (int i = 0; i < 8; ++i) if (w->uev[i]) (void)hipEventDestroy(w->uev[i]);
-  delete w;
-}
+void mesh_workspace_destroy(MeshWorkspace* w) { delete w; }
 
 int mesh_check_params(const smx_mesh_params& p) {
   SMX_CHECK_ARG(p.max_neighbors >= 1 && p.max_neighbors <= kMeshMaxNeighbors);
@@ -523,23 +496,23 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
                      const float4* normal, size_t normal_stride, uint32_t n, const smx_mesh_params& p, uint32_t* triangles,
                      uint32_t capacity, int32_t on_device, uint32_t* n_triangles, smx_mesh_stats* stats) {
   SMX_HIP(hipEventRecord(w->ev[1], st));   // (the index is built)
-  w->have = false;                         // (the rings are shared with smx_recon_triangulate_update: its kept state is gone)
+  w->upd.have = false;                     // (the rings are shared with smx_recon_triangulate_update: its kept state is gone)
   *n_triangles = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n == 0) return SMX_OK;
   const int K = p.max_neighbors;
   const uint32_t nb = (uint32_t)div_up(n, kBlock);
   // (a buffer that has to grow is freed first: the previous call ended with a synchronisation, nothing reads it)
-  int rc = grow(&w->lists, &w->lists_cap, (size_t)n * K);
-  if (rc == SMX_OK) rc = grow(&w->d2, &w->d2_cap, (size_t)n * K);
-  if (rc == SMX_OK) rc = grow(&w->counts, &w->counts_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->r2, &w->r2_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->meta, &w->meta_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->local_off, &w->local_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->rings, &w->rings_cap, (size_t)n * kMeshMaxStarDegree);
-  if (rc == SMX_OK) rc = grow(&w->block_sums, &w->sums_cap, (size_t)nb);
-  if (rc == SMX_OK) rc = grow(&w->block_off, &w->off_cap, (size_t)nb);
-  if (rc != SMX_OK) return rc;
+  SMX_CALL(w->lists.reserve((size_t)n * K));
+  SMX_CALL(w->d2.reserve((size_t)n * K));
+  SMX_CALL(w->counts.reserve((size_t)n));
+  SMX_CALL(w->r2.reserve((size_t)n));
+  SMX_CALL(w->meta.reserve((size_t)n));
+  SMX_CALL(w->local_off.reserve((size_t)n));
+  SMX_CALL(w->rings.reserve((size_t)n * kMeshMaxStarDegree));
+  SMX_CALL(w->block_sums.reserve((size_t)nb));
+  SMX_CALL(w->block_off.reserve((size_t)nb));
+  int rc = SMX_OK;
   MeshK k;
   k.smooth = smooth; k.smooth_stride = smooth_stride; k.normal = normal; k.normal_stride = normal_stride;
   k.n = n; k.K = K;
@@ -547,26 +520,26 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
   k.cos_max_normal = (float)std::cos((double)p.max_angle_between_normals_deg * rad);
   k.cos_min_angle = (float)std::cos((double)p.min_triangle_angle_deg * rad);
   k.cos_max_angle = (float)std::cos((double)p.max_triangle_angle_deg * rad);
-  SMX_HIP(hipMemsetAsync(w->stat, 0, kStWords * sizeof(uint32_t), st));
+  SMX_HIP(hipMemsetAsync(w->stat.get(), 0, kStWords * sizeof(uint32_t), st));
   const unsigned grid = (unsigned)std::min<uint32_t>(nb, 8192u);
-  hipLaunchKernelGGL(k_mesh_prepare, dim3(grid), dim3(kBlock), 0, st, k, w->r2, w->stat);
+  hipLaunchKernelGGL(k_mesh_prepare, dim3(grid), dim3(kBlock), 0, st, k, w->r2.get(), w->stat.get());
   SMX_LAUNCH_CHECK();
   // (a slot without finite coordinates is not indexed and gets count 0; a merged one was left out of the build)
-  rc = smx_nn_query_self(nn, (smx_stream)st, w->r2, p.search_radius_factor * p.search_radius_factor, K, nullptr, 0, w->lists,
-                         w->d2, w->counts);
+  rc = smx_nn_query_self(nn, (smx_stream)st, w->r2.get(), p.search_radius_factor * p.search_radius_factor, K, nullptr, 0, w->lists.get(),
+                         w->d2.get(), w->counts.get());
   if (rc != SMX_OK) return rc;
   SMX_HIP(hipEventRecord(w->ev[2], st));
   const unsigned star_grid = (unsigned)std::min<uint32_t>((uint32_t)div_up(n, kWaves), 16384u);
-  hipLaunchKernelGGL(k_mesh_star<false>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists, w->counts, w->rings, w->meta, w->stat,
+  hipLaunchKernelGGL(k_mesh_star<false>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists.get(), w->counts.get(), w->rings.get(), w->meta.get(), w->stat.get(),
                      MeshU{});
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(w->ev[3], st));
-  hipLaunchKernelGGL((k_mesh_agree<false, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off,
-                     w->block_sums, nullptr, nullptr, 0u, w->stat, MeshU{});
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
+  hipLaunchKernelGGL((k_mesh_agree<false, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings.get(), w->meta.get(), w->local_off.get(),
+                     w->block_sums.get(), nullptr, nullptr, 0u, w->stat.get(), MeshU{});
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums.get(), nb, w->block_off.get(), w->stat.get());
   SMX_LAUNCH_CHECK();
   uint32_t h[kStWords];
-  SMX_HIP(hipMemcpyAsync(h, w->stat, sizeof(h), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(h, w->stat.get(), sizeof(h), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   const uint32_t T = h[kStTotal];
   *n_triangles = T;
@@ -585,12 +558,11 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
   if (T > 0) {
     uint32_t* dst = triangles;
     if (!on_device) {
-      rc = grow(&w->tri, &w->tri_cap, (size_t)3 * T);
-      if (rc != SMX_OK) return rc;
-      dst = w->tri;
+      SMX_CALL(w->tri.reserve((size_t)3 * T));
+      dst = w->tri.get();
     }
-    hipLaunchKernelGGL((k_mesh_agree<true, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->local_off, nullptr,
-                       w->block_off, dst, T, nullptr, MeshU{});
+    hipLaunchKernelGGL((k_mesh_agree<true, false>), dim3(nb), dim3(kBlock), 0, st, k, w->rings.get(), w->meta.get(), w->local_off.get(), nullptr,
+                       w->block_off.get(), dst, T, nullptr, MeshU{});
     SMX_LAUNCH_CHECK();
     if (!on_device) SMX_HIP(hipMemcpyAsync(triangles, dst, (size_t)T * 12, hipMemcpyDeviceToHost, st));
   }
@@ -602,24 +574,14 @@ int mesh_triangulate(MeshWorkspace* w, hipStream_t st, smx_nn nn, const float4* 
 
 int mesh_update_reset(MeshWorkspace* w) {
   if (!w) return SMX_OK;
-  w->have = false; w->utimed = false; w->n_prev = 0; w->t_prev = 0;
-  void** ptrs[] = {(void**)&w->snap_s, (void**)&w->snap_n, (void**)&w->kept, (void**)&w->utri[0], (void**)&w->utri[1],
-                   (void**)&w->ulocal[0], (void**)&w->ulocal[1], (void**)&w->ublock[0], (void**)&w->ublock[1], (void**)&w->changed,
-                   (void**)&w->in_a, (void**)&w->work, (void**)&w->rows, (void**)&w->reverse_r2, (void**)&w->state,
-                   (void**)&w->reverse_idx, (void**)&w->reverse_d2, (void**)&w->reverse_count, (void**)&w->reverse_rows,
-                   (void**)&w->near_bits};
-  for (void** p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
-  size_t* caps[] = {&w->snap_s_cap, &w->snap_n_cap, &w->kept_cap, &w->utri_cap[0], &w->utri_cap[1], &w->ulocal_cap[0],
-                    &w->ulocal_cap[1], &w->ublock_cap[0], &w->ublock_cap[1], &w->changed_cap, &w->in_a_cap, &w->work_cap,
-                    &w->rows_cap, &w->reverse_r2_cap, &w->state_cap, &w->ridx_cap, &w->rd2_cap, &w->rcount_cap, &w->reverse_rows_cap};
-  for (size_t* c : caps) *c = 0;
-  if (w->reverse_nn) { (void)smx_nn_destroy(w->reverse_nn); w->reverse_nn = nullptr; }
+  if (w->upd.reverse_nn) (void)smx_nn_destroy(w->upd.reverse_nn);
+  w->upd = MeshUpdate{};
   return SMX_OK;
 }
 
 int mesh_update_phase_ms(MeshWorkspace* w, float out_ms[6]) {
   for (int i = 0; i < 6; ++i) out_ms[i] = 0.0f;
-  if (!w || !w->utimed) return SMX_OK;
+  if (!w || !w->upd.utimed) return SMX_OK;
   float d[7];
   for (int i = 0; i < 7; ++i) SMX_HIP(hipEventElapsedTime(&d[i], w->uev[i], w->uev[i + 1]));
   // stamps: diff | reverse index build | reverse query and work list | index build over the map | lists | stars | agreement
@@ -640,38 +602,39 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
                             const smx_mesh_params& p, float full_above_fraction, MeshSubsetLists lists, void* lists_ctx,
                             uint32_t* triangles, uint32_t capacity, int32_t on_device, uint32_t* n_triangles,
                             smx_mesh_stats* stats, smx_mesh_update_stats* update_stats) {
-  w->utimed = false;
+  MeshUpdate& up = w->upd;
+  up.utimed = false;
   SMX_HIP(hipEventRecord(w->uev[0], st));
   *n_triangles = 0;
   if (stats) memset(stats, 0, sizeof(*stats));
   smx_mesh_update_stats us;
   memset(&us, 0, sizeof(us));
-  us.mode = !w->have ? 1u : !same_params(p, w->prm) ? 2u : n < w->n_prev ? 3u : 0u;
+  us.mode = !up.have ? 1u : !same_params(p, up.prm) ? 2u : n < up.n_prev ? 3u : 0u;
   if (update_stats) *update_stats = us;
   if (n == 0) {
-    w->have = false;
+    up.have = false;
     return smx_nn_build(nn, (smx_stream)st, nullptr, nullptr, nullptr, 0, cell_size, 1);
   }
   const float fraction = full_above_fraction < 0.0f ? kMeshUpdateDefaultFullAboveFraction : full_above_fraction;
-  const uint32_t n_prev = us.mode == 0 ? w->n_prev : 0u;   // (the full path: every slot is changed, nothing was live)
+  const uint32_t n_prev = us.mode == 0 ? up.n_prev : 0u;  // (the full path: every slot is changed, nothing was live)
   const int K = p.max_neighbors;
   const uint32_t nb = (uint32_t)div_up(n, kBlock);
-  const int nw = w->cur ^ 1;                               // the set this call writes
-  w->have = false;                                         // (until this call has gone through)
-  int rc = grow_keep(&w->rings, &w->rings_cap, (size_t)n * kMeshMaxStarDegree, (size_t)n_prev * kMeshMaxStarDegree, st);
-  if (rc == SMX_OK) rc = grow_keep(&w->meta, &w->meta_cap, (size_t)n, (size_t)n_prev, st);
-  if (rc == SMX_OK) rc = grow_keep(&w->kept, &w->kept_cap, (size_t)n, (size_t)n_prev, st);
-  if (rc == SMX_OK) rc = grow_keep(&w->snap_s, &w->snap_s_cap, (size_t)n, (size_t)n_prev, st);
-  if (rc == SMX_OK) rc = grow_keep(&w->snap_n, &w->snap_n_cap, (size_t)n, (size_t)n_prev, st);
-  if (rc == SMX_OK) rc = grow(&w->r2, &w->r2_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->changed, &w->changed_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->in_a, &w->in_a_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->work, &w->work_cap, (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->block_sums, &w->sums_cap, (size_t)nb);
-  if (rc == SMX_OK) rc = grow(&w->block_off, &w->off_cap, (size_t)nb);
-  if (rc == SMX_OK) rc = grow(&w->ulocal[nw], &w->ulocal_cap[nw], (size_t)n);
-  if (rc == SMX_OK) rc = grow(&w->ublock[nw], &w->ublock_cap[nw], (size_t)nb);
-  if (rc != SMX_OK) return rc;
+  const int nw = up.cur ^ 1;                               // the set this call writes
+  up.have = false;                                         // (until this call has gone through)
+  SMX_CALL(w->rings.reserve_keep((size_t)n * kMeshMaxStarDegree, (size_t)n_prev * kMeshMaxStarDegree, st));
+  SMX_CALL(w->meta.reserve_keep((size_t)n, (size_t)n_prev, st));
+  SMX_CALL(up.kept.reserve_keep((size_t)n, (size_t)n_prev, st));
+  SMX_CALL(up.snap_s.reserve_keep((size_t)n, (size_t)n_prev, st));
+  SMX_CALL(up.snap_n.reserve_keep((size_t)n, (size_t)n_prev, st));
+  SMX_CALL(w->r2.reserve((size_t)n));
+  SMX_CALL(up.changed.reserve((size_t)n));
+  SMX_CALL(up.in_a.reserve((size_t)n));
+  SMX_CALL(up.work.reserve((size_t)n));
+  SMX_CALL(w->block_sums.reserve((size_t)nb));
+  SMX_CALL(w->block_off.reserve((size_t)nb));
+  SMX_CALL(up.ulocal[nw].reserve((size_t)n));
+  SMX_CALL(up.ublock[nw].reserve((size_t)nb));
+  int rc = SMX_OK;
   MeshK k;
   k.smooth = smooth; k.smooth_stride = smooth_stride; k.normal = normal; k.normal_stride = normal_stride;
   k.n = n; k.K = K;
@@ -682,7 +645,7 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
   const float f2 = p.search_radius_factor * p.search_radius_factor;
   uint32_t h[kStWords];
   auto read_stat = [&]() -> int {
-    SMX_HIP(hipMemcpyAsync(h, w->stat, sizeof(h), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(h, w->stat.get(), sizeof(h), hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
     return SMX_OK;
   };
@@ -690,27 +653,26 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
   // ---- diff: changed bytes, ghost count, live count; then the rows, the reverse test's inputs and the new snapshot
   MeshDiff d;
   memset(&d, 0, sizeof(d));
-  d.n_prev = n_prev; d.snap_s = w->snap_s; d.snap_n = w->snap_n; d.changed = w->changed;
-  SMX_HIP(hipMemsetAsync(w->stat, 0, kStWords * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_mesh_diff<false>, dim3(nb), dim3(kBlock), 0, st, k, d, w->block_sums, nullptr, w->stat);
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
+  d.n_prev = n_prev; d.snap_s = up.snap_s.get(); d.snap_n = up.snap_n.get(); d.changed = up.changed.get();
+  SMX_HIP(hipMemsetAsync(w->stat.get(), 0, kStWords * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_mesh_diff<false>, dim3(nb), dim3(kBlock), 0, st, k, d, w->block_sums.get(), nullptr, w->stat.get());
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums.get(), nb, w->block_off.get(), w->stat.get());
   SMX_LAUNCH_CHECK();
   if ((rc = read_stat()) != SMX_OK) return rc;
   const uint32_t n_live = h[kStLive], n_changed = h[kStChanged], n_ghosts = h[kStTotal];
   const size_t M = (size_t)n + n_ghosts;
-  rc = grow(&w->rows, &w->rows_cap, 3 * M);
-  if (rc == SMX_OK) rc = grow(&w->reverse_r2, &w->reverse_r2_cap, M);
-  if (rc == SMX_OK) rc = grow(&w->state, &w->state_cap, M);
-  if (rc != SMX_OK) return rc;
-  d.rows = w->rows; d.row_len = M; d.reverse_r2 = w->reverse_r2; d.state = w->state; d.r2 = w->r2;
+  SMX_CALL(up.rows.reserve(3 * M));
+  SMX_CALL(up.reverse_r2.reserve(M));
+  SMX_CALL(up.state.reserve(M));
+  d.rows = up.rows.get(); d.row_len = M; d.reverse_r2 = up.reverse_r2.get(); d.state = up.state.get(); d.r2 = w->r2.get();
   const bool reverse = us.mode == 0 && n_changed > 0;
   constexpr size_t kNearWords = (size_t)1 << (kMeshNearBitsLog2 - 5);
   if (reverse) {
-    if (!w->near_bits) SMX_HIP(hipMalloc(reinterpret_cast<void**>(&w->near_bits), kNearWords * sizeof(uint32_t)));
-    SMX_HIP(hipMemsetAsync(w->near_bits, 0, kNearWords * sizeof(uint32_t), st));
-    d.near_bits = w->near_bits; d.inv_h = 1.0f / cell_size;
+    if (!up.near_bits.get()) SMX_CALL(up.near_bits.alloc(kNearWords, false));
+    SMX_HIP(hipMemsetAsync(up.near_bits.get(), 0, kNearWords * sizeof(uint32_t), st));
+    d.near_bits = up.near_bits.get(); d.inv_h = 1.0f / cell_size;
   }
-  hipLaunchKernelGGL(k_mesh_diff<true>, dim3(nb), dim3(kBlock), 0, st, k, d, nullptr, w->block_off, w->stat);
+  hipLaunchKernelGGL(k_mesh_diff<true>, dim3(nb), dim3(kBlock), 0, st, k, d, nullptr, w->block_off.get(), w->stat.get());
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(w->uev[1], st));
   us.n_changed = n_changed;
@@ -718,58 +680,57 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
   // ---- nothing changed: the kept array is the answer
   if (us.mode == 0 && n_changed == 0) {
     for (int e = 2; e <= 3; ++e) SMX_HIP(hipEventRecord(w->uev[e], st));
-    rc = smx_nn_build(nn, (smx_stream)st, w->rows, w->rows + M, w->rows + 2 * M, n, cell_size, 1);
+    rc = smx_nn_build(nn, (smx_stream)st, up.rows.get(), up.rows.get() + M, up.rows.get() + 2 * M, n, cell_size, 1);
     if (rc != SMX_OK) return rc;
     for (int e = 4; e <= 6; ++e) SMX_HIP(hipEventRecord(w->uev[e], st));
-    const uint32_t T = w->t_prev;
+    const uint32_t T = up.t_prev;
     us.n_kept_triangles = T;
     *n_triangles = T;
-    if (stats) *stats = w->last_stats;
+    if (stats) *stats = up.last_stats;
     if (update_stats) *update_stats = us;
-    w->have = true;
+    up.have = true;
     int out_rc = SMX_OK;
     if (capacity < T) {
       set_error("triangles holds %u entries, the mesh has %u", capacity, T);
       out_rc = SMX_ERR_INVALID_ARGUMENT;
     } else if (T > 0) {
-      SMX_HIP(hipMemcpyAsync(triangles, w->utri[w->cur], (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+      SMX_HIP(hipMemcpyAsync(triangles, up.utri[up.cur].get(), (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     }
     SMX_HIP(hipEventRecord(w->uev[7], st));
     SMX_HIP(hipStreamSynchronize(st));
-    w->utimed = true;
+    up.utimed = true;
     return out_rc;
   }
 
   // ---- reverse test: which unchanged live slots have a changed point, or the kept position of one, in their ball
   if (us.mode == 0) {
-    if (!w->reverse_nn) { rc = smx_nn_create(device, &w->reverse_nn); if (rc != SMX_OK) return rc; }
-    rc = grow(&w->reverse_idx, &w->ridx_cap, M);
-    if (rc == SMX_OK) rc = grow(&w->reverse_d2, &w->rd2_cap, M);
-    if (rc == SMX_OK) rc = grow(&w->reverse_count, &w->rcount_cap, M);
-    if (rc == SMX_OK) rc = grow(&w->reverse_rows, &w->reverse_rows_cap, 3 * M);
-    if (rc != SMX_OK) return rc;
+    if (!up.reverse_nn) { rc = smx_nn_create(device, &up.reverse_nn); if (rc != SMX_OK) return rc; }
+    SMX_CALL(up.reverse_idx.reserve(M));
+    SMX_CALL(up.reverse_d2.reserve(M));
+    SMX_CALL(up.reverse_count.reserve(M));
+    SMX_CALL(up.reverse_rows.reserve(3 * M));
     // (a ball of radius <= cell_size / 2 stays within the 27 cells around its centre's)
     hipLaunchKernelGGL(k_mesh_reverse_rows, dim3((unsigned)std::min<size_t>((size_t)div_up((long long)M, kBlock), 8192)), dim3(kBlock), 0, st,
-                       n, M, w->rows, w->reverse_rows, w->changed, w->reverse_r2, f2, 1.0f / cell_size, 0.25f * cell_size * cell_size,
-                       w->near_bits, w->stat);
+                       n, M, up.rows.get(), up.reverse_rows.get(), up.changed.get(), up.reverse_r2.get(), f2, 1.0f / cell_size, 0.25f * cell_size * cell_size,
+                       up.near_bits.get(), w->stat.get());
     SMX_LAUNCH_CHECK();
-    rc = smx_nn_build(w->reverse_nn, (smx_stream)st, w->reverse_rows, w->reverse_rows + M, w->reverse_rows + 2 * M, (uint32_t)M,
+    rc = smx_nn_build(up.reverse_nn, (smx_stream)st, up.reverse_rows.get(), up.reverse_rows.get() + M, up.reverse_rows.get() + 2 * M, (uint32_t)M,
                       cell_size, 1);
     if (rc != SMX_OK) return rc;
   }
   SMX_HIP(hipEventRecord(w->uev[2], st));
   auto count_work = [&](int32_t all) -> int {
-    hipLaunchKernelGGL(k_mesh_worklist<false>, dim3(nb), dim3(kBlock), 0, st, n, w->changed, all ? nullptr : w->reverse_count, all,
-                       w->block_sums, nullptr, nullptr);
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->block_off, w->stat);
+    hipLaunchKernelGGL(k_mesh_worklist<false>, dim3(nb), dim3(kBlock), 0, st, n, up.changed.get(), all ? nullptr : up.reverse_count.get(), all,
+                       w->block_sums.get(), nullptr, nullptr);
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums.get(), nb, w->block_off.get(), w->stat.get());
     SMX_LAUNCH_CHECK();
     return read_stat();
   };
   uint32_t n_work = n;
   if (us.mode == 0) {
     // (the index holds the changed points and the ghosts for this query: unchanged points carry state 1 and are skipped)
-    rc = smx_nn_query_self(w->reverse_nn, (smx_stream)st, w->reverse_r2, f2, 1, w->state, 1, w->reverse_idx, w->reverse_d2,
-                           w->reverse_count);
+    rc = smx_nn_query_self(up.reverse_nn, (smx_stream)st, up.reverse_r2.get(), f2, 1, up.state.get(), 1, up.reverse_idx.get(), up.reverse_d2.get(),
+                           up.reverse_count.get());
     if (rc != SMX_OK) return rc;
     if ((rc = count_work(0)) != SMX_OK) return rc;
     n_work = h[kStTotal];
@@ -782,22 +743,21 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
     n_work = n;
     if (us.mode != 4) us.n_dirty = n;
   }
-  hipLaunchKernelGGL(k_mesh_worklist<true>, dim3(nb), dim3(kBlock), 0, st, n, w->changed, incremental ? w->reverse_count : nullptr,
-                     incremental ? 0 : 1, nullptr, w->block_off, w->work);
+  hipLaunchKernelGGL(k_mesh_worklist<true>, dim3(nb), dim3(kBlock), 0, st, n, up.changed.get(), incremental ? up.reverse_count.get() : nullptr,
+                     incremental ? 0 : 1, nullptr, w->block_off.get(), up.work.get());
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(w->uev[3], st));
 
   // ---- the caller's index over the map, and the candidate lists of the work list
-  rc = smx_nn_build(nn, (smx_stream)st, w->rows, w->rows + M, w->rows + 2 * M, n, cell_size, 1);
+  rc = smx_nn_build(nn, (smx_stream)st, up.rows.get(), up.rows.get() + M, up.rows.get() + 2 * M, n, cell_size, 1);
   if (rc != SMX_OK) return rc;
   SMX_HIP(hipEventRecord(w->uev[4], st));
-  rc = grow(&w->lists, &w->lists_cap, (size_t)n_work * K);
-  if (rc == SMX_OK) rc = grow(&w->d2, &w->d2_cap, (size_t)n_work * K);
-  if (rc == SMX_OK) rc = grow(&w->counts, &w->counts_cap, (size_t)n_work);
-  if (rc != SMX_OK) return rc;
+  SMX_CALL(w->lists.reserve((size_t)n_work * K));
+  SMX_CALL(w->d2.reserve((size_t)n_work * K));
+  SMX_CALL(w->counts.reserve((size_t)n_work));
   if (n_work > 0) {
-    if (incremental) rc = lists(lists_ctx, st, nn, w->work, n_work, f2, K, w->lists, w->d2, w->counts);
-    else rc = smx_nn_query_self(nn, (smx_stream)st, w->r2, f2, K, nullptr, 0, w->lists, w->d2, w->counts);
+    if (incremental) rc = lists(lists_ctx, st, nn, up.work.get(), n_work, f2, K, w->lists.get(), w->d2.get(), w->counts.get());
+    else rc = smx_nn_query_self(nn, (smx_stream)st, w->r2.get(), f2, K, nullptr, 0, w->lists.get(), w->d2.get(), w->counts.get());
     if (rc != SMX_OK) return rc;
   }
   SMX_HIP(hipEventRecord(w->uev[5], st));
@@ -805,21 +765,21 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
   // ---- stars of the work list; A = D + old rings + new rings
   MeshU u;
   memset(&u, 0, sizeof(u));
-  u.work = w->work; u.n_work = n_work; u.n_prev = n_prev; u.in_a = w->in_a; u.kept = w->kept;
-  u.prev_tri = w->utri[w->cur]; u.prev_local = w->ulocal[w->cur]; u.prev_block = w->ublock[w->cur];
-  SMX_HIP(hipMemsetAsync(w->in_a, 0, (size_t)n, st));
+  u.work = up.work.get(); u.n_work = n_work; u.n_prev = n_prev; u.in_a = up.in_a.get(); u.kept = up.kept.get();
+  u.prev_tri = up.utri[up.cur].get(); u.prev_local = up.ulocal[up.cur].get(); u.prev_block = up.ublock[up.cur].get();
+  SMX_HIP(hipMemsetAsync(up.in_a.get(), 0, (size_t)n, st));
   if (n_work > 0) {
     const unsigned star_grid = (unsigned)std::min<uint32_t>((uint32_t)div_up(n_work, kWaves), 16384u);
-    hipLaunchKernelGGL(k_mesh_star<true>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists, w->counts, w->rings, w->meta, w->stat, u);
+    hipLaunchKernelGGL(k_mesh_star<true>, dim3(star_grid), dim3(kBlock), 0, st, k, w->lists.get(), w->counts.get(), w->rings.get(), w->meta.get(), w->stat.get(), u);
     SMX_LAUNCH_CHECK();
   }
   SMX_HIP(hipEventRecord(w->uev[6], st));
 
   // ---- agreement: count, scan, write into the other output set
-  SMX_HIP(hipMemsetAsync(w->stat, 0, kStWords * sizeof(uint32_t), st));
-  hipLaunchKernelGGL((k_mesh_agree<false, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->ulocal[nw], w->block_sums,
-                     nullptr, nullptr, 0u, w->stat, u);
-  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums, nb, w->ublock[nw], w->stat);
+  SMX_HIP(hipMemsetAsync(w->stat.get(), 0, kStWords * sizeof(uint32_t), st));
+  hipLaunchKernelGGL((k_mesh_agree<false, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings.get(), w->meta.get(), up.ulocal[nw].get(), w->block_sums.get(),
+                     nullptr, nullptr, 0u, w->stat.get(), u);
+  hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, w->block_sums.get(), nb, up.ublock[nw].get(), w->stat.get());
   SMX_LAUNCH_CHECK();
   if ((rc = read_stat()) != SMX_OK) return rc;
   const uint32_t T = h[kStTotal];
@@ -827,15 +787,14 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
   ms.n_live = n_live; ms.n_star_triangles = h[kStStar]; ms.n_triangles = T;
   ms.star_overflow = h[kStOverflow]; ms.truncated_lists = h[kStTruncated];
   us.n_reagreed = h[kStReagreed]; us.n_kept_triangles = h[kStKept];
-  rc = grow(&w->utri[nw], &w->utri_cap[nw], (size_t)3 * T);
-  if (rc != SMX_OK) return rc;
+  SMX_CALL(up.utri[nw].reserve((size_t)3 * T));
   if (T > 0) {
-    hipLaunchKernelGGL((k_mesh_agree<true, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings, w->meta, w->ulocal[nw], nullptr,
-                       w->ublock[nw], w->utri[nw], T, nullptr, u);
+    hipLaunchKernelGGL((k_mesh_agree<true, true>), dim3(nb), dim3(kBlock), 0, st, k, w->rings.get(), w->meta.get(), up.ulocal[nw].get(), nullptr,
+                       up.ublock[nw].get(), up.utri[nw].get(), T, nullptr, u);
     SMX_LAUNCH_CHECK();
   }
   // (the state has advanced, whether or not the caller's buffer holds the result)
-  w->cur = nw; w->n_prev = n; w->t_prev = T; w->prm = p; w->last_stats = ms; w->have = true;
+  up.cur = nw; up.n_prev = n; up.t_prev = T; up.prm = p; up.last_stats = ms; up.have = true;
   *n_triangles = T;
   if (stats) *stats = ms;
   if (update_stats) *update_stats = us;
@@ -845,11 +804,11 @@ int mesh_triangulate_update(MeshWorkspace* w, int device, hipStream_t st, smx_nn
     else set_error("count only: the mesh has %u triangles", T);
     out_rc = SMX_ERR_INVALID_ARGUMENT;
   } else if (T > 0) {
-    SMX_HIP(hipMemcpyAsync(triangles, w->utri[nw], (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(triangles, up.utri[nw].get(), (size_t)T * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   }
   SMX_HIP(hipEventRecord(w->uev[7], st));
   SMX_HIP(hipStreamSynchronize(st));
-  w->utimed = true;
+  up.utimed = true;
   return out_rc;
 }
 

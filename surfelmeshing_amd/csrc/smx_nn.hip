@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 
 #include "smx_common.hpp"
@@ -1223,6 +1224,7 @@ k_query_stream(QueryArgs a) {
 
 }  // namespace
 
+// (created value-initialised: counts zero, buffers empty)
 struct smx_nn_s {
   int device;
   uint32_t n;          // points given to the last build
@@ -1230,32 +1232,30 @@ struct smx_nn_s {
   uint32_t n_bricks;
   Grid grid;
   // index (owned, grown on demand, reused by the next build)
-  size_t cap_points;
-  unsigned long long* keys[2];
-  uint32_t* vals[2];
-  float* rows;          // upload target for host rows [3][cap]
-  float4* sorted;
-  uint32_t* hist;       // [256][tiles] + scan workspaces behind it
-  size_t hist_elems;
-  BrickSlot* table;
+  size_t cap_points;    // what keys, vals, rows and sorted were sized for together (0 after a failed growth)
+  DevBuf<unsigned long long> keys[2];
+  DevBuf<uint32_t> vals[2];
+  DevBuf<float> rows;          // upload target for host rows [3][cap]
+  DevBuf<float4> sorted;
+  DevBuf<uint32_t> hist;       // [256][tiles] + scan workspaces behind it
+  DevBuf<BrickSlot> table;
   size_t table_slots;   // power of two
-  uint32_t* bbox;       // 6 order keys
-  uint32_t* partial;    // count partials
-  BuildCounts* counts;
+  DevBuf<uint32_t> bbox;       // 6 order keys
+  DevBuf<uint32_t> partial;    // count partials
+  DevBuf<BuildCounts> counts;
   // query workspace
-  size_t cap_queries;
-  unsigned long long* qkeys[2];
-  uint32_t* qvals[2];
-  uint32_t *qflags, *qtile_start;
-  uint8_t *tile_redo_q, *tile_redo_self;   // k_query_lanes' per-tile marks: one per query tile / per self tile (or table slot)
-  uint32_t* self_tile_start;    // the self queries' tiles in KEY order: tile t = points [start[t], start[t + 1]) of nn->sorted,
-  uint32_t* self_n_tiles;       // <= 64 points of one brick each (k_tile_flags over the point keys); their number (device word)
-  size_t cap_self_tiles, cap_tile_redo_self;
-  float* qrows;         // upload target for host queries [4][cap]
-  float4* qrec;         // queries in brick order
-  uint8_t* dstate; size_t cap_state;
-  uint32_t* didx; float* dd2; int32_t* dcnt; size_t cap_out;   // staging for host outputs [nq * k]
-  unsigned long long* stat;   // 4 counters (device), filled while stats_enabled
+  size_t cap_queries;   // likewise for qkeys .. qrec
+  DevBuf<unsigned long long> qkeys[2];
+  DevBuf<uint32_t> qvals[2];
+  DevBuf<uint32_t> qflags, qtile_start;
+  DevBuf<uint8_t> tile_redo_q, tile_redo_self;   // k_query_lanes' per-tile marks: one per query tile / per self tile (or table slot)
+  DevBuf<uint32_t> self_tile_start;    // the self queries' tiles in KEY order: tile t = points [start[t], start[t + 1]) of nn->sorted.get(),
+  DevBuf<uint32_t> self_n_tiles;       // <= 64 points of one brick each (k_tile_flags over the point keys); their number (device word)
+  DevBuf<float> qrows;         // upload target for host queries [4][cap]
+  DevBuf<float4> qrec;         // queries in brick order
+  DevBuf<uint8_t> dstate;
+  DevBuf<uint32_t> didx; DevBuf<float> dd2; DevBuf<int32_t> dcnt;   // staging for host outputs [nq * k]: grown together, dcnt last
+  DevBuf<unsigned long long> stat;   // 4 counters (device), filled while stats_enabled
   int stats_enabled;
   int query_mode;       // 2 = one lane per query (k_query_lanes; default), 0 = one wavefront per query over LDS-staged brick tiles
                         // (k_query_tiles), 1 = one wavefront per query from L1 / L2 (k_query_stream)
@@ -1263,20 +1263,6 @@ struct smx_nn_s {
 };
 
 namespace {
-
-void nn_free(smx_nn nn) {
-  void* ptrs[] = {nn->keys[0], nn->keys[1], nn->vals[0], nn->vals[1], nn->rows, nn->sorted, nn->hist, nn->table, nn->bbox,
-                  nn->partial, nn->counts, nn->qkeys[0], nn->qkeys[1], nn->qvals[0], nn->qvals[1], nn->qflags, nn->tile_redo_q, nn->tile_redo_self, nn->self_tile_start, nn->self_n_tiles,
-                  nn->qtile_start, nn->qrows, nn->qrec, nn->dstate, nn->didx, nn->dd2, nn->dcnt, nn->stat};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-}
-
-template <typename T>
-int grow(T** p, size_t count) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  return SMX_OK;
-}
 
 size_t sort_hist_elems(size_t n) { return (size_t)kRadix * ((n + kSortTile - 1) / kSortTile); }
 
@@ -1286,12 +1272,12 @@ int ensure_points(smx_nn nn, size_t n) {
   if (n <= nn->cap_points) return SMX_OK;
   SMX_HIP(hipDeviceSynchronize());
   const size_t cap = n + n / 8 + 1024;
-  int rc = SMX_OK;
-  for (int k = 0; k < 2 && rc == SMX_OK; ++k) { rc = grow(&nn->keys[k], cap); if (rc == SMX_OK) rc = grow(&nn->vals[k], cap); }
-  if (rc == SMX_OK) rc = grow(&nn->rows, 3 * cap);
-  if (rc == SMX_OK) rc = grow(&nn->sorted, cap);
-  nn->cap_points = rc == SMX_OK ? cap : 0;
-  return rc;
+  nn->cap_points = 0;
+  for (int k = 0; k < 2; ++k) { SMX_CALL(nn->keys[k].alloc(cap, false)); SMX_CALL(nn->vals[k].alloc(cap, false)); }
+  SMX_CALL(nn->rows.alloc(3 * cap, false));
+  SMX_CALL(nn->sorted.alloc(cap, false));
+  nn->cap_points = cap;
+  return SMX_OK;
 }
 // hist layout: [sort histograms for max_n][their scan levels][scan levels of a flag array of max_n]
 size_t hist_need(size_t max_n) {
@@ -1299,31 +1285,30 @@ size_t hist_need(size_t max_n) {
 }
 int ensure_hist(smx_nn nn, size_t max_n) {
   const size_t need = hist_need(max_n);
-  if (need <= nn->hist_elems) return SMX_OK;
+  if (need <= nn->hist.capacity()) return SMX_OK;
   SMX_HIP(hipDeviceSynchronize());
-  const size_t cap = need + need / 8;
-  const int rc = grow(&nn->hist, cap);
-  nn->hist_elems = rc == SMX_OK ? cap : 0;
-  return rc;
+  return nn->hist.alloc(need + need / 8, false);
 }
 int ensure_queries(smx_nn nn, size_t nq) {
   if (nq <= nn->cap_queries) return SMX_OK;
   SMX_HIP(hipDeviceSynchronize());
   const size_t cap = nq + nq / 8 + 1024;
-  int rc = SMX_OK;
-  for (int k = 0; k < 2 && rc == SMX_OK; ++k) { rc = grow(&nn->qkeys[k], cap); if (rc == SMX_OK) rc = grow(&nn->qvals[k], cap); }
-  if (rc == SMX_OK) rc = grow(&nn->qflags, cap + 1);
-  if (rc == SMX_OK) rc = grow(&nn->tile_redo_q, cap + 1);
-  if (rc == SMX_OK) rc = grow(&nn->qtile_start, cap + 2);
-  if (rc == SMX_OK) rc = grow(&nn->qrows, 4 * cap);
-  if (rc == SMX_OK) rc = grow(&nn->qrec, cap);
-  nn->cap_queries = rc == SMX_OK ? cap : 0;
-  return rc;
+  nn->cap_queries = 0;
+  for (int k = 0; k < 2; ++k) { SMX_CALL(nn->qkeys[k].alloc(cap, false)); SMX_CALL(nn->qvals[k].alloc(cap, false)); }
+  SMX_CALL(nn->qflags.alloc(cap + 1, false));
+  SMX_CALL(nn->tile_redo_q.alloc(cap + 1, false));
+  SMX_CALL(nn->qtile_start.alloc(cap + 2, false));
+  SMX_CALL(nn->qrows.alloc(4 * cap, false));
+  SMX_CALL(nn->qrec.alloc(cap, false));
+  nn->cap_queries = cap;
+  return SMX_OK;
 }
 
 // Sorts (keys[0], vals[0]) by the low `bits` bits; returns the index (0 / 1) of the buffers that hold the result.
-int radix_sort(unsigned long long* const keys[2], uint32_t* const vals[2], uint32_t n, int bits, uint32_t* hist,
-               hipStream_t st) {
+int radix_sort(const DevBuf<unsigned long long> (&key_bufs)[2], const DevBuf<uint32_t> (&val_bufs)[2], uint32_t n, int bits,
+               uint32_t* hist, hipStream_t st) {
+  unsigned long long* const keys[2] = {key_bufs[0].get(), key_bufs[1].get()};
+  uint32_t* const vals[2] = {val_bufs[0].get(), val_bufs[1].get()};
   const uint32_t tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
   const size_t hn = (size_t)kRadix * tiles;
   uint32_t* scan_ws = hist + hn;
@@ -1349,21 +1334,18 @@ int smx_nn_create(int32_t device_id, smx_nn* out) {
   int device = 0;
   SMX_CALL(resolve_device(device_id, &device));
   SMX_ON_DEVICE(device);
-  smx_nn_s* nn = new smx_nn_s();
-  memset(nn, 0, sizeof(*nn));
+  std::unique_ptr<smx_nn_s> nn(new smx_nn_s());
   nn->device = device;
   hipDeviceProp_t prop;
   SMX_HIP(hipGetDeviceProperties(&prop, device));
   const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   nn->query_mode = 2;           // lane per query, k_query_tiles for what it marks
   nn->grid_blocks = cus * 12;   // persistent grid of the tile kernel: 6 workgroups (24 wavefronts) fit a CU, two rounds
-  int rc = grow(&nn->bbox, 6);
-  if (rc == SMX_OK) rc = grow(&nn->partial, 6 * 2048);
-  if (rc == SMX_OK) rc = grow(&nn->counts, 1);
-  if (rc == SMX_OK) rc = grow(&nn->stat, 5);   // [4]: k_query_lanes' redo flag
-  if (rc != SMX_OK) { nn_free(nn); delete nn; return rc; }
-  SMX_HIP(hipMemset(nn->stat, 0, 5 * sizeof(unsigned long long)));
-  *out = nn;
+  SMX_CALL(nn->bbox.alloc(6, false));
+  SMX_CALL(nn->partial.alloc(6 * 2048, false));
+  SMX_CALL(nn->counts.alloc(1, false));
+  SMX_CALL(nn->stat.alloc(5, true));   // [4]: k_query_lanes' redo flag
+  *out = nn.release();
   return SMX_OK;
 }
 
@@ -1371,7 +1353,6 @@ int smx_nn_destroy(smx_nn nn) {
   if (!nn) return SMX_OK;
   SMX_ON_DEVICE(nn->device);
   (void)hipDeviceSynchronize();
-  nn_free(nn);
   delete nn;
   return SMX_OK;
 }
@@ -1383,23 +1364,22 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
   hipStream_t st = (hipStream_t)s;
   nn->n = n; nn->n_valid = 0; nn->n_bricks = 0;
   if (n == 0) return SMX_OK;
-  int rc = ensure_points(nn, n);
+  SMX_CALL(ensure_points(nn, n));
   const size_t hist_max_n = std::max<size_t>(n, nn->cap_queries);
-  if (rc == SMX_OK) rc = ensure_hist(nn, hist_max_n);
-  if (rc != SMX_OK) return rc;
+  SMX_CALL(ensure_hist(nn, hist_max_n));
   const float *dx = x, *dy = y, *dz = z;
   if (!rows_on_device) {
     const size_t cap = nn->cap_points;
-    SMX_HIP(hipMemcpyAsync(nn->rows, x, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    SMX_HIP(hipMemcpyAsync(nn->rows + cap, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    SMX_HIP(hipMemcpyAsync(nn->rows + 2 * cap, z, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    dx = nn->rows; dy = nn->rows + cap; dz = nn->rows + 2 * cap;
+    SMX_HIP(hipMemcpyAsync(nn->rows.get(), x, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    SMX_HIP(hipMemcpyAsync(nn->rows.get() + cap, y, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    SMX_HIP(hipMemcpyAsync(nn->rows.get() + 2 * cap, z, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    dx = nn->rows.get(); dy = nn->rows.get() + cap; dz = nn->rows.get() + 2 * cap;
   }
   const int grid = 2048;
-  hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(kBlock), 0, st, dx, dy, dz, n, nn->partial);
-  hipLaunchKernelGGL(k_bbox_finish, dim3(1), dim3(kBlock), 0, st, nn->partial, grid, nn->bbox);
+  hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(kBlock), 0, st, dx, dy, dz, n, nn->partial.get());
+  hipLaunchKernelGGL(k_bbox_finish, dim3(1), dim3(kBlock), 0, st, nn->partial.get(), grid, nn->bbox.get());
   uint32_t bb[6];
-  SMX_HIP(hipMemcpyAsync(bb, nn->bbox, sizeof(bb), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(bb, nn->bbox.get(), sizeof(bb), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));   // read-back 1 of 2: the grid dimensions decide the number of sort passes
   if (bb[0] > bb[3]) return SMX_OK;    // no indexable point
   float mn[3], mx[3];
@@ -1436,27 +1416,27 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
   g.cell = cell;
   for (int a = 0; a < 3; ++a) g.min[a] = mn[a];
 
-  hipLaunchKernelGGL(k_point_keys, dim3(grid), dim3(kBlock), 0, st, dx, dy, dz, n, g, nn->keys[0], nn->vals[0]);
-  const int cur = radix_sort(nn->keys, nn->vals, n, g.key_bits, nn->hist, st);
+  hipLaunchKernelGGL(k_point_keys, dim3(grid), dim3(kBlock), 0, st, dx, dy, dz, n, g, nn->keys[0].get(), nn->vals[0].get());
+  const int cur = radix_sort(nn->keys, nn->vals, n, g.key_bits, nn->hist.get(), st);
   if (cur != 0) { std::swap(nn->keys[0], nn->keys[1]); std::swap(nn->vals[0], nn->vals[1]); }   // result in [0]
-  hipLaunchKernelGGL(k_gather_records, dim3(grid), dim3(kBlock), 0, st, nn->vals[0], dx, dy, dz, n, nn->sorted);
-  hipLaunchKernelGGL(k_brick_count, dim3(grid), dim3(kBlock), 0, st, nn->keys[0], n, g.sentinel, nn->partial);
-  hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(kBlock), 0, st, nn->partial, grid, nn->counts);
+  hipLaunchKernelGGL(k_gather_records, dim3(grid), dim3(kBlock), 0, st, nn->vals[0].get(), dx, dy, dz, n, nn->sorted.get());
+  hipLaunchKernelGGL(k_brick_count, dim3(grid), dim3(kBlock), 0, st, nn->keys[0].get(), n, g.sentinel, nn->partial.get());
+  hipLaunchKernelGGL(k_sum_counts, dim3(1), dim3(kBlock), 0, st, nn->partial.get(), grid, nn->counts.get());
   BuildCounts h;
-  SMX_HIP(hipMemcpyAsync(&h, nn->counts, sizeof(h), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(&h, nn->counts.get(), sizeof(h), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));   // read-back 2 of 2: the hash table is sized to the occupied bricks
   size_t slots = 1024;
   while (slots < (size_t)h.n_bricks * 2) slots <<= 1;
   if (slots > nn->table_slots) {
-    rc = grow(&nn->table, slots);
-    if (rc == SMX_OK && slots > nn->cap_tile_redo_self) { rc = grow(&nn->tile_redo_self, slots); nn->cap_tile_redo_self = rc == SMX_OK ? slots : 0; }
-    nn->table_slots = rc == SMX_OK ? slots : 0;
-    if (rc != SMX_OK) return rc;
+    nn->table_slots = 0;
+    SMX_CALL(nn->table.alloc(slots, false));
+    if (slots > nn->tile_redo_self.capacity()) SMX_CALL(nn->tile_redo_self.alloc(slots, false));
+    nn->table_slots = slots;
   }
   slots = nn->table_slots;   // (a larger table left from an earlier build is simply sparser)
-  SMX_HIP(hipMemsetAsync(nn->table, 0, slots * sizeof(BrickSlot), st));
-  hipLaunchKernelGGL(k_brick_insert, dim3(grid), dim3(kBlock), 0, st, nn->keys[0], h.n_valid, nn->table, (uint32_t)(slots - 1));
-  hipLaunchKernelGGL(k_brick_ends, dim3(grid), dim3(kBlock), 0, st, nn->keys[0], h.n_valid, nn->table, (uint32_t)(slots - 1));
+  SMX_HIP(hipMemsetAsync(nn->table.get(), 0, slots * sizeof(BrickSlot), st));
+  hipLaunchKernelGGL(k_brick_insert, dim3(grid), dim3(kBlock), 0, st, nn->keys[0].get(), h.n_valid, nn->table.get(), (uint32_t)(slots - 1));
+  hipLaunchKernelGGL(k_brick_ends, dim3(grid), dim3(kBlock), 0, st, nn->keys[0].get(), h.n_valid, nn->table.get(), (uint32_t)(slots - 1));
 #if SMX_NN_SELF_SORTED
   // The self queries' tiles in KEY order (round 6).  Rounds 2-5 walked the brick TABLE: tile = hash slot -- half of the
   // slots empty (a round trip each to find out) and neighbouring bricks a random distance apart in the walk, so that each
@@ -1464,26 +1444,22 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
   // the tiles in flight at any moment are a few adjacent rows of bricks, and what one stages its neighbours find in the L2.
   if (h.n_valid > 0) {
     const size_t max_tiles = (size_t)h.n_bricks + (size_t)h.n_valid / kTile + 2;
-    if (max_tiles + 1 > nn->cap_self_tiles) {
+    if (!nn->self_n_tiles.get()) SMX_CALL(nn->self_n_tiles.alloc(4, false));
+    if (max_tiles + 1 > nn->self_tile_start.capacity()) {
       SMX_HIP(hipDeviceSynchronize());
-      rc = grow(&nn->self_tile_start, max_tiles + 1 + max_tiles / 8);
-      if (rc == SMX_OK && !nn->self_n_tiles) rc = grow(&nn->self_n_tiles, 4);
-      nn->cap_self_tiles = rc == SMX_OK ? max_tiles + 1 + max_tiles / 8 : 0;
-      if (rc != SMX_OK) return rc;
+      SMX_CALL(nn->self_tile_start.alloc(max_tiles + 1 + max_tiles / 8, false));
     }
-    if (max_tiles > nn->cap_tile_redo_self) {
+    if (max_tiles > nn->tile_redo_self.capacity()) {
       SMX_HIP(hipDeviceSynchronize());
-      rc = grow(&nn->tile_redo_self, std::max(max_tiles + max_tiles / 8, slots));
-      nn->cap_tile_redo_self = rc == SMX_OK ? std::max(max_tiles + max_tiles / 8, slots) : 0;
-      if (rc != SMX_OK) return rc;
+      SMX_CALL(nn->tile_redo_self.alloc(std::max(max_tiles + max_tiles / 8, slots), false));
     }
-    uint32_t* flags = nn->vals[1];   // (scratch of the sort: the order lives in vals[0])
-    hipLaunchKernelGGL(k_tile_flags, dim3((h.n_valid + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nn->keys[0], h.n_valid, kLocalBits, flags);
+    uint32_t* flags = nn->vals[1].get();   // (scratch of the sort: the order lives in vals[0])
+    hipLaunchKernelGGL(k_tile_flags, dim3((h.n_valid + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nn->keys[0].get(), h.n_valid, kLocalBits, flags);
     uint32_t* total = nullptr;
-    uint32_t* flag_ws = nn->hist + sort_hist_elems(hist_max_n) + scan_workspace_elems(sort_hist_elems(hist_max_n));
+    uint32_t* flag_ws = nn->hist.get() + sort_hist_elems(hist_max_n) + scan_workspace_elems(sort_hist_elems(hist_max_n));
     exclusive_scan_inplace(flags, h.n_valid, flag_ws, st, &total);
-    hipLaunchKernelGGL(k_tile_starts, dim3(grid), dim3(kBlock), 0, st, flags, h.n_valid, total, nn->self_tile_start);
-    SMX_HIP(hipMemcpyAsync(nn->self_n_tiles, total, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_tile_starts, dim3(grid), dim3(kBlock), 0, st, flags, h.n_valid, total, nn->self_tile_start.get());
+    SMX_HIP(hipMemcpyAsync(nn->self_n_tiles.get(), total, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   }
 #endif
   SMX_LAUNCH_CHECK();
@@ -1504,61 +1480,56 @@ int smx_nn_query_batch(smx_nn nn, smx_stream s, uint32_t nq, const float* qx, co
     else memset(out_count, 0, (size_t)nq * 4);
     return SMX_OK;
   }
-  int rc = ensure_queries(nn, nq);
+  SMX_CALL(ensure_queries(nn, nq));
   const size_t max_n = std::max<size_t>(nn->cap_queries, nn->n);
-  if (rc == SMX_OK) rc = ensure_hist(nn, max_n);
-  if (rc != SMX_OK) return rc;
+  SMX_CALL(ensure_hist(nn, max_n));
   QueryArgs a;
   memset(&a, 0, sizeof(a));
   const float *dqx, *dqy, *dqz, *dqr2;
-  a.nq = nq; a.K = k; a.skip_mask = skip_mask; a.g = nn->grid; a.table = nn->table; a.mask = (uint32_t)(nn->table_slots - 1);
-  a.sorted = nn->sorted; a.n_valid = nn->n_valid;
+  a.nq = nq; a.K = k; a.skip_mask = skip_mask; a.g = nn->grid; a.table = nn->table.get(); a.mask = (uint32_t)(nn->table_slots - 1);
+  a.sorted = nn->sorted.get(); a.n_valid = nn->n_valid;
   if (queries_on_device) {
     dqx = qx; dqy = qy; dqz = qz; dqr2 = r2; a.state = state;
   } else {
     const size_t cap = nn->cap_queries;
     const float* src[4] = {qx, qy, qz, r2};
-    for (int c = 0; c < 4; ++c) SMX_HIP(hipMemcpyAsync(nn->qrows + c * cap, src[c], (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    dqx = nn->qrows; dqy = nn->qrows + cap; dqz = nn->qrows + 2 * cap; dqr2 = nn->qrows + 3 * cap;
+    for (int c = 0; c < 4; ++c) SMX_HIP(hipMemcpyAsync(nn->qrows.get() + c * cap, src[c], (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    dqx = nn->qrows.get(); dqy = nn->qrows.get() + cap; dqz = nn->qrows.get() + 2 * cap; dqr2 = nn->qrows.get() + 3 * cap;
     if (state) {
-      if (nn->n > nn->cap_state) {
+      if (nn->n > nn->dstate.capacity()) {
         SMX_HIP(hipDeviceSynchronize());
-        const size_t cap_s = (size_t)nn->n + nn->n / 8;
-        rc = grow(&nn->dstate, cap_s);
-        nn->cap_state = rc == SMX_OK ? cap_s : 0;
-        if (rc != SMX_OK) return rc;
+        SMX_CALL(nn->dstate.alloc((size_t)nn->n + nn->n / 8, false));
       }
-      SMX_HIP(hipMemcpyAsync(nn->dstate, state, nn->n, hipMemcpyHostToDevice, st));
-      a.state = nn->dstate;
+      SMX_HIP(hipMemcpyAsync(nn->dstate.get(), state, nn->n, hipMemcpyHostToDevice, st));
+      a.state = nn->dstate.get();
     }
   }
   if (outputs_on_device) {
     a.out_idx = out_idx; a.out_d2 = out_d2; a.out_count = out_count;
   } else {
     const size_t need = (size_t)nq * (size_t)k;
-    if (need > nn->cap_out) {
+    if (need > nn->dcnt.capacity()) {
       SMX_HIP(hipDeviceSynchronize());
       const size_t cap_o = need + need / 8;
-      rc = grow(&nn->didx, cap_o);
-      if (rc == SMX_OK) rc = grow(&nn->dd2, cap_o);
-      if (rc == SMX_OK) rc = grow(&nn->dcnt, cap_o);
-      nn->cap_out = rc == SMX_OK ? cap_o : 0;
-      if (rc != SMX_OK) return rc;
+      nn->dcnt.reset();
+      SMX_CALL(nn->didx.alloc(cap_o, false));
+      SMX_CALL(nn->dd2.alloc(cap_o, false));
+      SMX_CALL(nn->dcnt.alloc(cap_o, false));
     }
-    a.out_idx = nn->didx; a.out_d2 = nn->dd2; a.out_count = nn->dcnt;
+    a.out_idx = nn->didx.get(); a.out_d2 = nn->dd2.get(); a.out_count = nn->dcnt.get();
   }
   const int grid = 2048;
-  hipLaunchKernelGGL(k_query_keys, dim3(grid), dim3(kBlock), 0, st, dqx, dqy, dqz, nq, nn->grid, nn->qkeys[0], nn->qvals[0]);
-  const int cur = radix_sort(nn->qkeys, nn->qvals, nq, nn->grid.brick_bits, nn->hist, st);
-  hipLaunchKernelGGL(k_gather_queries, dim3(grid), dim3(kBlock), 0, st, nn->qvals[cur], dqx, dqy, dqz, dqr2, nq, nn->qrec);
-  a.qrec = nn->qrec;
-  hipLaunchKernelGGL(k_tile_flags, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nn->qkeys[cur], nq, 0, nn->qflags);
+  hipLaunchKernelGGL(k_query_keys, dim3(grid), dim3(kBlock), 0, st, dqx, dqy, dqz, nq, nn->grid, nn->qkeys[0].get(), nn->qvals[0].get());
+  const int cur = radix_sort(nn->qkeys, nn->qvals, nq, nn->grid.brick_bits, nn->hist.get(), st);
+  hipLaunchKernelGGL(k_gather_queries, dim3(grid), dim3(kBlock), 0, st, nn->qvals[cur].get(), dqx, dqy, dqz, dqr2, nq, nn->qrec.get());
+  a.qrec = nn->qrec.get();
+  hipLaunchKernelGGL(k_tile_flags, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nn->qkeys[cur].get(), nq, 0, nn->qflags.get());
   uint32_t* total = nullptr;
-  uint32_t* flag_ws = nn->hist + sort_hist_elems(max_n) + scan_workspace_elems(sort_hist_elems(max_n));
-  exclusive_scan_inplace(nn->qflags, nq, flag_ws, st, &total);
-  hipLaunchKernelGGL(k_tile_starts, dim3(grid), dim3(kBlock), 0, st, nn->qflags, nq, total, nn->qtile_start);
-  a.qorder = nn->qvals[cur]; a.tile_start = nn->qtile_start; a.n_tiles = total;
-  a.stat = nn->stats_enabled ? nn->stat : nullptr;
+  uint32_t* flag_ws = nn->hist.get() + sort_hist_elems(max_n) + scan_workspace_elems(sort_hist_elems(max_n));
+  exclusive_scan_inplace(nn->qflags.get(), nq, flag_ws, st, &total);
+  hipLaunchKernelGGL(k_tile_starts, dim3(grid), dim3(kBlock), 0, st, nn->qflags.get(), nq, total, nn->qtile_start.get());
+  a.qorder = nn->qvals[cur].get(); a.tile_start = nn->qtile_start.get(); a.n_tiles = total;
+  a.stat = nn->stats_enabled ? nn->stat.get() : nullptr;
   const unsigned blocks = (unsigned)std::min<size_t>((size_t)nn->grid_blocks, ((size_t)nq + 15) / 16 + 1);
   if (nn->query_mode == 1) {
     const unsigned sb = (unsigned)std::min<size_t>(((size_t)nq + 3) / 4, 65536);
@@ -1566,8 +1537,8 @@ int smx_nn_query_batch(smx_nn nn, smx_stream s, uint32_t nq, const float* qx, co
   } else if (nn->query_mode == 0) {
     hipLaunchKernelGGL(k_query_tiles<false>, dim3(blocks), dim3(64 * kTileWaves), 0, st, a);
   } else {
-    a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat + 4);
-    a.tile_redo = nn->tile_redo_q;
+    a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat.get() + 4);
+    a.tile_redo = nn->tile_redo_q.get();
     SMX_HIP(hipMemsetAsync(a.redo_flag, 0, 4, st));
     const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, (size_t)nq + 1) & ~7u);   // (a multiple of 8: SMX_NN_XCD_MAP)
     if (a.state) hipLaunchKernelGGL((k_query_lanes<false, true>), dim3(lb), dim3(64), 0, st, a);
@@ -1597,21 +1568,21 @@ int smx_nn_query_self(smx_nn nn, smx_stream s, const float* radius_squared, floa
   if (nn->n_valid == 0) return SMX_OK;
   QueryArgs a;
   memset(&a, 0, sizeof(a));
-  a.nq = nn->n_valid; a.K = k; a.state = state; a.skip_mask = skip_mask; a.g = nn->grid; a.table = nn->table;
-  a.mask = (uint32_t)(nn->table_slots - 1); a.sorted = nn->sorted; a.n_valid = nn->n_valid;
+  a.nq = nn->n_valid; a.K = k; a.state = state; a.skip_mask = skip_mask; a.g = nn->grid; a.table = nn->table.get();
+  a.mask = (uint32_t)(nn->table_slots - 1); a.sorted = nn->sorted.get(); a.n_valid = nn->n_valid;
   a.out_idx = out_idx; a.out_d2 = out_d2; a.out_count = out_count;
   a.self_r2 = radius_squared; a.self_factor = factor;
-  a.stat = nn->stats_enabled ? nn->stat : nullptr;
+  a.stat = nn->stats_enabled ? nn->stat.get() : nullptr;
 #if SMX_NN_SELF_SORTED
-  a.tile_start = nn->self_tile_start; a.n_tiles = nn->self_n_tiles;   // tiles in key order (smx_nn_build)
+  a.tile_start = nn->self_tile_start.get(); a.n_tiles = nn->self_n_tiles.get();   // tiles in key order (smx_nn_build)
   const size_t tiles_bound = (size_t)nn->n_bricks + (size_t)nn->n_valid / kTile + 2;
 #else
   const size_t tiles_bound = nn->table_slots;
 #endif
   const unsigned blocks = (unsigned)std::min<size_t>((size_t)nn->grid_blocks, tiles_bound);
   if (nn->query_mode == 2) {
-    a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat + 4);
-    a.tile_redo = nn->tile_redo_self;
+    a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat.get() + 4);
+    a.tile_redo = nn->tile_redo_self.get();
     SMX_HIP(hipMemsetAsync(a.redo_flag, 0, 4, st));
     const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, tiles_bound) & ~7u);   // (a multiple of 8: SMX_NN_XCD_MAP)
     if (a.state) hipLaunchKernelGGL((k_query_lanes<true, true>), dim3(lb), dim3(64), 0, st, a);
@@ -1633,7 +1604,7 @@ int smx_nn_set_stats_enabled(smx_nn nn, smx_stream s, int32_t enabled) {
   SMX_CHECK_ARG(nn != nullptr);
   SMX_ON_DEVICE(nn->device);
   nn->stats_enabled = enabled ? 1 : 0;
-  SMX_HIP(hipMemsetAsync(nn->stat, 0, 4 * sizeof(unsigned long long), (hipStream_t)s));
+  SMX_HIP(hipMemsetAsync(nn->stat.get(), 0, 4 * sizeof(unsigned long long), (hipStream_t)s));
   return SMX_OK;
 }
 
@@ -1641,7 +1612,7 @@ int smx_nn_get_stats(smx_nn nn, smx_stream s, smx_nn_stats* out) {
   SMX_CHECK_ARG(nn != nullptr && out != nullptr);
   SMX_ON_DEVICE(nn->device);
   unsigned long long h[4];
-  SMX_HIP(hipMemcpyAsync(h, nn->stat, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)s));
+  SMX_HIP(hipMemcpyAsync(h, nn->stat.get(), sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));
   out->n_points = nn->n; out->n_indexed = nn->n_valid; out->n_bricks = nn->n_bricks;
   out->cell_size = nn->grid.cell;

@@ -3049,11 +3049,9 @@ int enqueue_regularize(smx_recon r, hipStream_t st, uint32_t frame, float rf, fl
 }
 
 int ensure_staging(smx_recon r, size_t floats) {
-  if (r->staging_floats >= floats) return SMX_OK;
-  if (r->staging) { SMX_HIP(hipDeviceSynchronize()); SMX_HIP(hipFree(r->staging)); r->staging = nullptr; r->staging_floats = 0; }
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->staging), floats * sizeof(float)));
-  r->staging_floats = floats;
-  return SMX_OK;
+  if (r->staging.capacity() >= floats) return SMX_OK;
+  if (r->staging.get()) SMX_HIP(hipDeviceSynchronize());   // (earlier users may still be reading the old block)
+  return r->staging.alloc(floats, false);
 }
 
 // (for the create functions, whose failure paths have to release what exists so far instead of returning on the spot)
@@ -3138,8 +3136,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
       if (!(quiet && quiet[0] == '1')) fprintf(stderr, "libsmx: %s\n", text);
     }
   }
-  smx_recon_s* r = new smx_recon_s();
-  memset(r, 0, sizeof(*r));
+  smx_recon_s* r = new smx_recon_s();   // (value-initialised: every member zero or empty)
   r->device = device;
   r->max_surfels = max_surfel_count;
   r->W = width; r->H = height; r->fx = fx; r->fy = fy; r->cx = cx; r->cy = cy;
@@ -3149,55 +3146,55 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
 #define SMX_TRY(x) do { rc = (x); if (rc != SMX_OK) { (void)smx_recon_destroy(r); return rc; } } while (0)  /* (no leak on a failed allocation) */
   // cuda_surfel_reconstruction.cc:59 -- 25 rows x max_surfel_count (zero-filled here so that the
   // padded tail of every row is defined)
-  SMX_TRY(dev_alloc(&r->S.base, (size_t)kQuadsPerSlot * 4 * r->S.pitch, true));
-  SMX_TRY(dev_alloc(&r->grad_acc, 2 * ((size_t)r->S.pitch + kSegAcc), true));
-  SMX_TRY(dev_alloc(&r->reg_rec, 2 * ((size_t)r->S.pitch + kSegAcc), true));
+  SMX_TRY(r->mem.alloc(&r->S.base, (size_t)kQuadsPerSlot * 4 * r->S.pitch, true));
+  SMX_TRY(r->mem.alloc(&r->grad_acc, 2 * ((size_t)r->S.pitch + kSegAcc), true));
+  SMX_TRY(r->mem.alloc(&r->reg_rec, 2 * ((size_t)r->S.pitch + kSegAcc), true));
   r->nseg = div_up((long long)r->S.pitch, kSeg);
   r->nsegB = div_up((long long)r->S.pitch, kSegB);
   r->fb.cap = kFarBinCap; r->fb.hash_mask = (uint32_t)kFarHash - 1u;
-  SMX_TRY(dev_alloc(&r->fb.rec, (size_t)r->nsegB * kFarBinCap, false));
-  SMX_TRY(dev_alloc(&r->fb.count, ((size_t)r->nsegB + 1) * kCountStride, true));
+  SMX_TRY(r->mem.alloc(&r->fb.rec, (size_t)r->nsegB * kFarBinCap, false));
+  SMX_TRY(r->mem.alloc(&r->fb.count, ((size_t)r->nsegB + 1) * kCountStride, true));
   r->L.vis_region = (uint32_t)(div_up(r->nseg, kSubLists) * kSeg);
-  SMX_TRY(dev_alloc(&r->L.vis_list, (size_t)kSubLists * r->L.vis_region, true));
-  SMX_TRY(dev_alloc(&r->L.recent_list, (size_t)r->nsegB * kSegB, false));
-  SMX_TRY(dev_alloc(&r->L.vis_seg, (size_t)r->nseg, true));
-  SMX_TRY(dev_alloc(&r->L.seg_box, (size_t)r->nseg * 8, true));
-  SMX_TRY(dev_alloc(&r->L.seg_act, (size_t)r->nseg, true));
-  SMX_TRY(dev_alloc(&r->L.seg_streak, (size_t)r->nseg, true));
-  SMX_TRY(dev_alloc(&r->sw.surv_list, (size_t)r->nseg + 65536, true));   // (+ room for the index a walk forms first)
-  SMX_TRY(dev_alloc(&r->sw.copy_list, (size_t)r->nseg + 65536, true));
-  SMX_TRY(dev_alloc(&r->sw.count, 2, true));
+  SMX_TRY(r->mem.alloc(&r->L.vis_list, (size_t)kSubLists * r->L.vis_region, true));
+  SMX_TRY(r->mem.alloc(&r->L.recent_list, (size_t)r->nsegB * kSegB, false));
+  SMX_TRY(r->mem.alloc(&r->L.vis_seg, (size_t)r->nseg, true));
+  SMX_TRY(r->mem.alloc(&r->L.seg_box, (size_t)r->nseg * 8, true));
+  SMX_TRY(r->mem.alloc(&r->L.seg_act, (size_t)r->nseg, true));
+  SMX_TRY(r->mem.alloc(&r->L.seg_streak, (size_t)r->nseg, true));
+  SMX_TRY(r->mem.alloc(&r->sw.surv_list, (size_t)r->nseg + 65536, true));   // (+ room for the index a walk forms first)
+  SMX_TRY(r->mem.alloc(&r->sw.copy_list, (size_t)r->nseg + 65536, true));
+  SMX_TRY(r->mem.alloc(&r->sw.count, 2, true));
   // (the direction word of segment_of_block: written by the tile kernel, read by the host without synchronisation)
-  SMX_TRY(hip_rc(hipHostMalloc(reinterpret_cast<void**>(&r->dir_host), 2 * sizeof(uint32_t), hipHostMallocMapped), "hipHostMalloc"));
+  SMX_TRY(r->mem.alloc_host(&r->dir_host, 2, true));
   r->dir_host[0] = 0;
   r->dir_host[1] = 0;   // (a front gate that gave up leaves its mark here as well: smx_recon_integrate reads it without a synchronisation)
   SMX_TRY(hip_rc(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->dir_dev), r->dir_host, 0), "hipHostGetDevicePointer"));
-  SMX_TRY(dev_alloc(&r->L.recent_seg, (size_t)r->nsegB, true));
+  SMX_TRY(r->mem.alloc(&r->L.recent_seg, (size_t)r->nsegB, true));
   // chunk descriptors: every chunk of every segment in the worst case, + room for the index a walk forms first
   // chunk descriptors: kSubLists interleaved sub-lists; one holds at most every kSubLists-th segment's chunks, + room for
   // the index a walk forms before it knows the lengths
   r->L.vis_chunks.stride = 0; r->L.vis_chunks.desc = nullptr;   // (the visible list is dense: counters only, vis_begin)
   r->L.rec_chunks.stride = (uint32_t)(div_up(r->nsegB, kSubLists) + 8192);
-  SMX_TRY(dev_alloc(&r->L.rec_chunks.desc, (size_t)kSubLists * r->L.rec_chunks.stride, true));
-  SMX_TRY(dev_alloc(&r->L.rec_chunks.count, (size_t)kSubLists * kCountStride, true));
+  SMX_TRY(r->mem.alloc(&r->L.rec_chunks.desc, (size_t)kSubLists * r->L.rec_chunks.stride, true));
+  SMX_TRY(r->mem.alloc(&r->L.rec_chunks.count, (size_t)kSubLists * kCountStride, true));
   static_assert(kSegAcc == kSegB && kAccCount < kCountStride, "pass B lists the edge kernel's segments by its own segment numbers");
   r->L.acc_chunks.stride = r->L.rec_chunks.stride;
   r->L.acc_chunks.count = r->L.rec_chunks.count + kAccCount;
-  SMX_TRY(dev_alloc(&r->L.acc_chunks.desc, (size_t)kSubLists * r->L.acc_chunks.stride, true));
-  SMX_TRY(dev_alloc(&r->flags_buf[0], (size_t)r->nsegB * kSegB, true));
-  SMX_TRY(dev_alloc(&r->flags_buf[1], (size_t)r->nsegB * kSegB, true));
+  SMX_TRY(r->mem.alloc(&r->L.acc_chunks.desc, (size_t)kSubLists * r->L.acc_chunks.stride, true));
+  SMX_TRY(r->mem.alloc(&r->flags_buf[0], (size_t)r->nsegB * kSegB, true));
+  SMX_TRY(r->mem.alloc(&r->flags_buf[1], (size_t)r->nsegB * kSegB, true));
   r->L.flags8 = r->flags_buf[0];
   r->L.hot_shift = 10;
   while ((((size_t)r->nseg * kSeg) >> r->L.hot_shift) + 1 > (size_t)kMaxHotGroups) ++r->L.hot_shift;
   r->L.n_hot_groups = (uint32_t)((((size_t)r->nseg * kSeg) >> r->L.hot_shift) + 1);
-  SMX_TRY(dev_alloc(&r->L.hot_epoch, (size_t)r->L.n_hot_groups + 64, true));   // (zeros: "last active in call 0")
-  SMX_TRY(dev_alloc(&r->L.seg_targets, (size_t)r->nsegB * kBlockB, true));   // (written by the unfiltered passes of the hold-off calls before anyone reads it)
+  SMX_TRY(r->mem.alloc(&r->L.hot_epoch, (size_t)r->L.n_hot_groups + 64, true));   // (zeros: "last active in call 0")
+  SMX_TRY(r->mem.alloc(&r->L.seg_targets, (size_t)r->nsegB * kBlockB, true));   // (written by the unfiltered passes of the hold-off calls before anyone reads it)
   r->L.epoch = 128;   // (far from the zeros)
   r->hot_filter_enabled = 1;
   r->fuse_edges = SMX_FUSE_EDGES;
   r->hot_holdoff = 3;
-  SMX_TRY(dev_alloc(&r->merge_flag, r->S.pitch, true));
-  SMX_TRY(dev_alloc(&r->gate_count, 32, true));   // (a line of its own)
+  SMX_TRY(r->mem.alloc(&r->merge_flag, r->S.pitch, true));
+  SMX_TRY(r->mem.alloc(&r->gate_count, 32, true));   // (a line of its own)
   r->gate_expected = 0;
   r->handover_mode = SMX_HANDOVER_FLAGS;
   {
@@ -3205,15 +3202,15 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
     const char* cc = getenv("ROCPROF_COUNTER_COLLECTION");
     if (cc && cc[0] && strcmp(cc, "0") != 0) r->handover_mode = 0;
   }
-  SMX_TRY(dev_alloc(&r->L.act_list, (size_t)r->nsegB * kSegB, true));
-  SMX_TRY(dev_alloc(&r->sc.supporting, P, true));
-  SMX_TRY(dev_alloc(&r->sc.counts, P, true));
-  SMX_TRY(dev_alloc(&r->sc.depth_sums, P, true));
-  SMX_TRY(dev_alloc(&r->sc.confl_key, P, true));
-  SMX_TRY(dev_alloc(&r->sc.first_depth, P, true));
+  SMX_TRY(r->mem.alloc(&r->L.act_list, (size_t)r->nsegB * kSegB, true));
+  SMX_TRY(r->mem.alloc(&r->sc.supporting, P, true));
+  SMX_TRY(r->mem.alloc(&r->sc.counts, P, true));
+  SMX_TRY(r->mem.alloc(&r->sc.depth_sums, P, true));
+  SMX_TRY(r->mem.alloc(&r->sc.confl_key, P, true));
+  SMX_TRY(r->mem.alloc(&r->sc.first_depth, P, true));
   for (int k = 0; k < 2; ++k) {
-    SMX_TRY(dev_alloc(&r->vis_count_set[k], (size_t)kSubLists * kCountStride, true));
-    SMX_TRY(dev_alloc(&r->ovf_count_set[k], 1, true));
+    SMX_TRY(r->mem.alloc(&r->vis_count_set[k], (size_t)kSubLists * kCountStride, true));
+    SMX_TRY(r->mem.alloc(&r->ovf_count_set[k], 1, true));
   }
   r->L.vis_chunks.count = r->vis_count_set[0];
   // Association tiles: one bin of kTileBinCap pairs per tile (a tile of 256 pixels holds ~600 pairs at C2; pairs
@@ -3221,34 +3218,30 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   r->tb.tiles_x = div_up(width, kTileW);
   r->tb.n_tiles = (uint32_t)(r->tb.tiles_x * div_up(height, kTileH));
   r->tb.cap = r->bin_cap_full = kTileBinCap;
-  SMX_TRY(dev_alloc(&r->tb.pairs, (size_t)r->tb.n_tiles * kTileBinCap, false));
-  SMX_TRY(dev_alloc(&r->tb.count, (size_t)r->tb.n_tiles * kCountStride, true));
-  SMX_TRY(dev_alloc(&r->tb.ovf, 2 * (size_t)r->S.pitch + 64, false));
+  SMX_TRY(r->mem.alloc(&r->tb.pairs, (size_t)r->tb.n_tiles * kTileBinCap, false));
+  SMX_TRY(r->mem.alloc(&r->tb.count, (size_t)r->tb.n_tiles * kCountStride, true));
+  SMX_TRY(r->mem.alloc(&r->tb.ovf, 2 * (size_t)r->S.pitch + 64, false));
   r->tb.ovf_count = r->ovf_count_set[0];
 #ifdef SMX_STAMPS
-  SMX_TRY(dev_alloc(&r->stamps, (size_t)3 * 16 * 8192, true));
+  SMX_TRY(r->mem.alloc(&r->stamps, (size_t)3 * 16 * 8192, true));
 #endif
-  SMX_TRY(dev_alloc(&r->blended_depth, P, true));
-  SMX_TRY(dev_alloc(&r->bb.distance_map, P, true));
-  SMX_TRY(dev_alloc(&r->bb.new_distance_map, P, true));
-  SMX_TRY(dev_alloc(&r->bb.deltas, P, true));
-  SMX_TRY(dev_alloc(&r->bb.new_deltas, P, true));
-  SMX_TRY(dev_alloc(&r->new_flags, P, true));
-  SMX_TRY(dev_alloc(&r->new_ranks, P, true));
-  SMX_TRY(dev_alloc(&r->tmp_u32, P, true));
+  SMX_TRY(r->mem.alloc(&r->blended_depth, P, true));
+  SMX_TRY(r->mem.alloc(&r->bb.distance_map, P, true));
+  SMX_TRY(r->mem.alloc(&r->bb.new_distance_map, P, true));
+  SMX_TRY(r->mem.alloc(&r->bb.deltas, P, true));
+  SMX_TRY(r->mem.alloc(&r->bb.new_deltas, P, true));
+  SMX_TRY(r->mem.alloc(&r->new_flags, P, true));
+  SMX_TRY(r->mem.alloc(&r->new_ranks, P, true));
+  SMX_TRY(r->mem.alloc(&r->tmp_u32, P, true));
   r->n_scan_blocks = div_up((long long)P, kScanPxPerBlock);
-  SMX_TRY(dev_alloc(&r->block_sums, (size_t)r->n_scan_blocks, true));
-  SMX_TRY(dev_alloc(&r->block_offsets, (size_t)r->n_scan_blocks, true));
-  SMX_TRY(dev_alloc(&r->st, 1, true));
-  SMX_TRY(dev_alloc(&r->ts_ring, (size_t)kTsRing * kTsWords, true));
-  SMX_TRY(hip_rc(hipHostMalloc(reinterpret_cast<void**>(&r->ts_host), sizeof(unsigned long long) * kTsRing * kTsWords, hipHostMallocDefault), "hipHostMalloc"));
-  {
-    void* m = nullptr;
-    SMX_TRY(hip_rc(hipHostMalloc(&m, sizeof(unsigned long long) * kTsRing * kTsWords, hipHostMallocMapped), "hipHostMalloc"));
-    memset(m, 0, sizeof(unsigned long long) * kTsRing * kTsWords);
-    r->ts_mapped = static_cast<volatile unsigned long long*>(m);
-    SMX_TRY(hip_rc(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->ts_mapped_dev), m, 0), "hipHostGetDevicePointer"));
-  }
+  SMX_TRY(r->mem.alloc(&r->block_sums, (size_t)r->n_scan_blocks, true));
+  SMX_TRY(r->mem.alloc(&r->block_offsets, (size_t)r->n_scan_blocks, true));
+  SMX_TRY(r->mem.alloc(&r->st, 1, true));
+  SMX_TRY(r->mem.alloc(&r->ts_ring, (size_t)kTsRing * kTsWords, true));
+  SMX_TRY(r->mem.alloc_host(&r->ts_host, (size_t)kTsRing * kTsWords, false));
+  SMX_TRY(r->mem.alloc_host(&r->ts_mapped, (size_t)kTsRing * kTsWords, true));
+  memset(const_cast<unsigned long long*>(r->ts_mapped), 0, sizeof(unsigned long long) * kTsRing * kTsWords);
+  SMX_TRY(hip_rc(hipHostGetDevicePointer(reinterpret_cast<void**>(&r->ts_mapped_dev), const_cast<unsigned long long*>(r->ts_mapped), 0), "hipHostGetDevicePointer"));
   SMX_TRY(hip_rc(hipDeviceGetAttribute(&r->wall_khz, hipDeviceAttributeWallClockRate, device), "hipDeviceGetAttribute"));
   if (r->wall_khz <= 0) r->wall_khz = 100000;   // (s_memrealtime: 100 MHz)
   for (int i = 0; i < 14; ++i) SMX_TRY(hip_rc(hipEventCreate(&r->ev[i]), "hipEventCreate"));
@@ -3286,18 +3279,8 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
 int smx_recon_destroy(smx_recon r) {
   if (!r) return SMX_OK;
   SMX_ON_DEVICE(r->device);
-  void* ptrs[] = {r->sc.supporting, r->sc.counts, r->sc.depth_sums, r->sc.confl_key, r->sc.first_depth,
-                  r->tb.pairs, r->tb.count, r->tb.ovf, r->ovf_count_set[0], r->ovf_count_set[1],
-                  r->vis_count_set[0], r->vis_count_set[1], r->L.seg_act, r->L.seg_streak, r->sw.surv_list, r->sw.copy_list, r->sw.count, r->blended_depth, r->cand_q, r->cand_slots, r->cand_state, r->L.dirty8, r->delta_seg, r->delta_total, r->staging, r->S.base, r->grad_acc, r->reg_rec, r->fb.rec, r->fb.count, r->L.vis_list, r->L.recent_list, r->L.vis_seg, r->L.seg_box, r->L.recent_seg, r->L.vis_chunks.desc, r->L.rec_chunks.desc, r->L.acc_chunks.desc, r->L.rec_chunks.count, r->flags_buf[0], r->flags_buf[1], r->L.hot_epoch, r->L.seg_targets,
-                  r->merge_flag, r->L.act_list, r->bb.distance_map, r->bb.new_distance_map,
-                  r->bb.deltas, r->bb.new_deltas, r->new_flags, r->new_ranks, r->tmp_u32, r->block_sums, r->block_offsets, r->st,
-                  r->cmp_map, r->cmp_seg, r->cmp_out, r->zbuf,
-                  r->trk_depth, r->trk_normal, r->trk_slabs, r->trk_state};
   if (r->reg_stream) { (void)hipStreamSynchronize(r->reg_stream); (void)hipStreamDestroy(r->reg_stream); }
-  if (r->dir_host) { (void)hipDeviceSynchronize(); (void)hipHostFree(r->dir_host); }
-  if (r->ts_host) (void)hipHostFree(r->ts_host);
-  if (r->ts_mapped) { (void)hipDeviceSynchronize(); (void)hipHostFree(const_cast<unsigned long long*>(r->ts_mapped)); }
-  if (r->ts_ring) (void)hipFree(r->ts_ring);
+  if (r->dir_host) (void)hipDeviceSynchronize();   // (the mapped words: the device may still be writing them)
   if (r->ev_front) (void)hipEventDestroy(r->ev_front);
   if (r->ev_upd) (void)hipEventDestroy(r->ev_upd);
   if (r->ev_reg) (void)hipEventDestroy(r->ev_reg);
@@ -3305,11 +3288,10 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_render) (void)hipEventDestroy(r->ev_render);
   if (r->ev_track) (void)hipEventDestroy(r->ev_track);
   mesh_workspace_destroy(r->mesh);
-  for (void* p : ptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
   if (r->prof_ev) { for (int i = 0; i < 2 * r->prof_cap; ++i) (void)hipEventDestroy(r->prof_ev[i]); delete[] r->prof_ev; }
-  delete r;
+  delete r;   // (mem and the DevBuf members give their blocks back)
   return SMX_OK;
 }
 
@@ -3878,14 +3860,15 @@ int smx_recon_set_delta_tracking(smx_recon r, smx_stream s, int32_t enabled) {
   SMX_CALL(join_regularizer(r, st));
   SMX_HIP(hipStreamSynchronize(st));  // no kernel may be using the pointer that changes here
   if (enabled && !r->L.dirty8) {
-    int rc = dev_alloc(&r->L.dirty8, (size_t)r->nseg * kSeg, false);
-    if (rc == SMX_OK && !r->delta_seg) rc = dev_alloc(&r->delta_seg, (size_t)r->nseg, true);
-    if (rc == SMX_OK && !r->delta_total) rc = dev_alloc(&r->delta_total, 1, true);
+    int rc = r->dirty.alloc((size_t)r->nseg * kSeg, false);
+    if (rc == SMX_OK && !r->delta_seg.get()) rc = r->delta_seg.alloc((size_t)r->nseg, true);
+    if (rc == SMX_OK && !r->delta_total.get()) rc = r->delta_total.alloc(1, true);
     if (rc != SMX_OK) return rc;
-    SMX_HIP(hipMemset(r->L.dirty8, 1, (size_t)r->nseg * kSeg));  // everything that exists counts as changed
+    SMX_HIP(hipMemset(r->dirty.get(), 1, (size_t)r->nseg * kSeg));  // everything that exists counts as changed
+    r->L.dirty8 = r->dirty.get();   // (the kernels' view of it: tracking is on once all three blocks exist)
   } else if (!enabled && r->L.dirty8) {
-    SMX_HIP(hipFree(r->L.dirty8));
     r->L.dirty8 = nullptr;
+    r->dirty.reset();
   }
   return SMX_OK;
 }
@@ -3896,11 +3879,11 @@ int smx_recon_transfer_changed_to_cpu(smx_recon r, smx_stream s, uint32_t frame_
   if (!r->L.dirty8) { set_error("delta tracking is off (smx_recon_set_delta_tracking)"); return SMX_ERR_INVALID_ARGUMENT; }
   hipStream_t st = (hipStream_t)s;
   SMX_CALL(join_regularizer(r, st));
-  hipLaunchKernelGGL(k_delta_count, dim3(r->nseg), dim3(kBlock), 0, st, r->L.dirty8, r->delta_seg, r->st);
-  enqueue_segment_scan(st, r->delta_seg, r->nseg, r->delta_total);
+  hipLaunchKernelGGL(k_delta_count, dim3(r->nseg), dim3(kBlock), 0, st, r->L.dirty8, r->delta_seg.get(), r->st);
+  enqueue_segment_scan(st, r->delta_seg.get(), r->nseg, r->delta_total.get());
   SMX_LAUNCH_CHECK();
   uint32_t total = 0, n = 0;
-  SMX_HIP(hipMemcpyAsync(&total, r->delta_total, 4, hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(&total, r->delta_total.get(), 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipMemcpyAsync(&n, &r->st->surfel_count, 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   d->frame_index = frame_index;
@@ -3914,13 +3897,13 @@ int smx_recon_transfer_changed_to_cpu(smx_recon r, smx_stream s, uint32_t frame_
   SMX_CHECK_ARG(d->surfel_index && d->x && d->y && d->z && d->radius_squared && d->normal_x && d->normal_y &&
                 d->normal_z && d->last_update_stamp);
   SMX_CALL(acquire_staging(r, st, (size_t)9 * total));
-  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg, r->staging, total,
+  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg.get(), r->staging.get(), total,
                      r->st);
   SMX_LAUNCH_CHECK();
   void* dst[9] = {d->surfel_index, d->x, d->y, d->z, d->radius_squared, d->normal_x, d->normal_y, d->normal_z,
                   d->last_update_stamp};
   for (int k = 0; k < 9; ++k)
-    SMX_HIP(hipMemcpyAsync(dst[k], r->staging + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(dst[k], r->staging.get() + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   return SMX_OK;
 }

@@ -459,12 +459,12 @@ int reset_accumulators(smx_recon r, hipStream_t st) {
 // stream whose work uses it.
 template <typename T>
 struct DevTemp {
-  T* p = nullptr;
   hipStream_t st;
+  DevBuf<T> buf;   // (freed after the destructor's body)
   explicit DevTemp(hipStream_t st_) : st(st_) {}
-  DevTemp(const DevTemp&) = delete;
-  ~DevTemp() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
-  int alloc(size_t count) { return dev_alloc(&p, count, false); }
+  ~DevTemp() { if (buf.get()) (void)hipStreamSynchronize(st); }
+  int alloc(size_t count) { return buf.alloc(count, false); }
+  T* get() const { return buf.get(); }
 };
 
 }  // namespace
@@ -488,7 +488,7 @@ int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_inde
   rl.n = 8;
   const int want[8] = {kSmoothX, kSmoothY, kSmoothZ, kRadiusSq, kNormalX, kNormalY, kNormalZ, kLastUpdateStamp};
   for (int k = 0; k < 8; ++k) rl.rows[k] = want[k];
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging, n);
+  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging.get(), n);
   SMX_LAUNCH_CHECK();
   struct { int row; void* dst; } rows[8] = {
       {kSmoothX, buf->surfel_x_buffer}, {kSmoothY, buf->surfel_y_buffer}, {kSmoothZ, buf->surfel_z_buffer},
@@ -498,7 +498,7 @@ int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_inde
   int k = 0;
   for (auto& q : rows) {
     SMX_CHECK_ARG(q.dst != nullptr);
-    SMX_HIP(hipMemcpyAsync(q.dst, r->staging + (size_t)k * n, bytes, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(q.dst, r->staging.get() + (size_t)k * n, bytes, hipMemcpyDeviceToHost, st));
     ++k;
   }
   return release_staging(r, st);  // (the copies are still in flight: the caller synchronises, main.cc:1266-1267)
@@ -560,11 +560,10 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   hipStream_t st = (hipStream_t)s;
   SMX_CALL(join_regularizer(r, st));
   const size_t px = (size_t)p->width * p->height;
-  if (r->zbuf_px < px) {
-    if (r->zbuf) { SMX_HIP(hipDeviceSynchronize()); SMX_HIP(hipFree(r->zbuf)); r->zbuf = nullptr; r->zbuf_px = 0; }
+  if (r->zbuf.capacity() < px) {
+    if (r->zbuf.get()) SMX_HIP(hipDeviceSynchronize());   // (the previous render may still be using the old block)
     r->render_busy = false;
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->zbuf), px * sizeof(unsigned long long)));
-    r->zbuf_px = px;
+    SMX_CALL(r->zbuf.alloc(px, false));
   }
   if (r->render_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_render, 0));   // (the previous render's resolve, on any stream)
   RenderCtx rc;
@@ -582,10 +581,10 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   rc.W = p->width; rc.H = p->height; rc.mode = p->splat_mode;
   VisColor vc;
   vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
-  SMX_HIP(hipMemsetAsync(r->zbuf, 0xFF, px * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, r->zbuf, r->st);
+  SMX_HIP(hipMemsetAsync(r->zbuf.get(), 0xFF, px * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, r->zbuf.get(), r->st);
   hipLaunchKernelGGL(k_render_resolve, dim3(div_up(p->width, 64), div_up(p->height, 4)), dim3(kBlock), 0, st, r->S, rc, vc,
-                     r->zbuf, render_img<float>(depth), render_img<uint32_t>(index), render_img<float4>(normal),
+                     r->zbuf.get(), render_img<float>(depth), render_img<uint32_t>(index), render_img<float4>(normal),
                      render_img<uint32_t>(color));
   SMX_LAUNCH_CHECK();
   SMX_HIP(hipEventRecord(r->ev_render, st));
@@ -627,11 +626,14 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
   const size_t px = (size_t)r->W * r->H;
-  if (!r->trk_state) {
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_depth), px * sizeof(float)));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_normal), px * sizeof(float4)));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_slabs), sizeof(double) * kTrackMaxSlabs * kTrackSlabStride));
-    SMX_HIP(hipMalloc(reinterpret_cast<void**>(&r->trk_state), sizeof(TrackDev)));
+  if (!r->trk_state.get()) {   // (all four or none: a call that fails here leaves nothing behind for the next one to trip over)
+    DevBuf<float> depth_img; DevBuf<float4> normal_img; DevBuf<double> slabs; DevBuf<TrackDev> state;
+    SMX_CALL(depth_img.alloc(px, false));
+    SMX_CALL(normal_img.alloc(px, false));
+    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackSlabStride, false));
+    SMX_CALL(state.alloc(1, false));
+    r->trk_depth = std::move(depth_img); r->trk_normal = std::move(normal_img);
+    r->trk_slabs = std::move(slabs); r->trk_state = std::move(state);
   }
   if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
   // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
@@ -643,8 +645,8 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
   rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
   rp.surfel_integration_active_window_size = 2147483647;
   smx_buffer_desc dd, nd;
-  dd.address = r->trk_depth; dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
-  nd.address = r->trk_normal; nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
+  dd.address = r->trk_depth.get(); dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
+  nd.address = r->trk_normal.get(); nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
   SMX_CALL(smx_recon_render(r, s, &rp, &dd, nullptr, &nd, nullptr));
   if (model_depth_out)
     SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
@@ -653,13 +655,13 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
     SMX_HIP(hipMemcpy2DAsync(model_normal_out->address, model_normal_out->pitch, nd.address, nd.pitch, nd.pitch, (size_t)r->H,
                              hipMemcpyDeviceToDevice, st));
   TrackBuffers tb;
-  tb.model_depth = r->trk_depth; tb.model_normal = r->trk_normal; tb.slabs = r->trk_slabs; tb.state = r->trk_state;
+  tb.model_depth = r->trk_depth.get(); tb.model_normal = r->trk_normal.get(); tb.slabs = r->trk_slabs.get(); tb.state = r->trk_state.get();
   SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
                          result_on_device ? result : nullptr));
   SMX_HIP(hipEventRecord(r->ev_track, st));
   r->track_busy = true;
   if (!result_on_device) {
-    SMX_HIP(hipMemcpyAsync(result, &r->trk_state->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(result, &r->trk_state.get()->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
   return SMX_OK;
@@ -671,15 +673,15 @@ int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iterat
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
   *count = 0;
-  if (!r->trk_state || !r->track_busy) return SMX_OK;
+  if (!r->trk_state.get() || !r->track_busy) return SMX_OK;
   SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
   int32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   n = std::max(0, std::min(n, (int32_t)kTrackRing));
   const int32_t m = std::min(n, capacity);
   if (m > 0) {
-    SMX_HIP(hipMemcpyAsync(records, r->trk_state->ring, sizeof(smx_track_iteration) * (size_t)m, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(records, r->trk_state.get()->ring, sizeof(smx_track_iteration) * (size_t)m, hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
   *count = n;
@@ -695,9 +697,9 @@ int smx_recon_build_neighbor_index(smx_recon r, smx_stream s, smx_nn nn, float c
   SMX_CALL(read_surfel_count(r, st, &n));
   if (n == 0) return smx_nn_build(nn, s, nullptr, nullptr, nullptr, 0, cell_size, 1);
   SMX_CALL(acquire_staging(r, st, (size_t)3 * n));
-  hipLaunchKernelGGL(k_index_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, r->staging, n);
+  hipLaunchKernelGGL(k_index_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, r->staging.get(), n);
   SMX_LAUNCH_CHECK();
-  SMX_CALL(smx_nn_build(nn, s, r->staging, r->staging + n, r->staging + (size_t)2 * n, n, cell_size, 1));
+  SMX_CALL(smx_nn_build(nn, s, r->staging.get(), r->staging.get() + n, r->staging.get() + (size_t)2 * n, n, cell_size, 1));
   return release_staging(r, st);
 }
 
@@ -713,37 +715,30 @@ int smx_recon_neighbor_candidates(smx_recon r, smx_stream s, smx_nn nn, const ui
   SMX_CALL(join_regularizer(r, st));
   // workspace owned by the object, grown only when a batch is larger than any before it (then, and only then, the
   // device is synchronised: earlier batches may still be reading the old buffers)
-  if (n_indices > r->cand_cap) {
+  if (n_indices > r->cand_slots.capacity()) {   // (cand_slots is allocated last: its capacity stands for both)
     SMX_HIP(hipDeviceSynchronize());
-    if (r->cand_q) { SMX_HIP(hipFree(r->cand_q)); r->cand_q = nullptr; }
-    if (r->cand_slots) { SMX_HIP(hipFree(r->cand_slots)); r->cand_slots = nullptr; }
-    r->cand_cap = 0;
+    r->cand_slots.reset();
     const size_t cap = (size_t)n_indices + n_indices / 8 + 1024;
-    int rca = dev_alloc(&r->cand_q, 4 * cap, false);
-    if (rca == SMX_OK) rca = dev_alloc(&r->cand_slots, cap, false);
-    if (rca != SMX_OK) return rca;
-    r->cand_cap = (uint32_t)cap;
+    SMX_CALL(r->cand_q.alloc(4 * cap, false));
+    SMX_CALL(r->cand_slots.alloc(cap, false));
   }
   const uint8_t* dstate = state;
   const uint32_t* dslots = surfel_indices;
   if (!inputs_on_device) {
-    SMX_HIP(hipMemcpyAsync(r->cand_slots, surfel_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, st));
-    dslots = r->cand_slots;
+    SMX_HIP(hipMemcpyAsync(r->cand_slots.get(), surfel_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, st));
+    dslots = r->cand_slots.get();
     if (state) {
       uint32_t n = 0;
       SMX_CALL(read_surfel_count(r, st, &n));
-      if (n > r->cand_state_cap) {
+      if (n > r->cand_state.capacity()) {
         SMX_HIP(hipDeviceSynchronize());
-        if (r->cand_state) { SMX_HIP(hipFree(r->cand_state)); r->cand_state = nullptr; }
-        r->cand_state_cap = 0;
-        SMX_CALL(dev_alloc(&r->cand_state, (size_t)r->S.pitch, false));
-        r->cand_state_cap = (uint32_t)r->S.pitch;
+        SMX_CALL(r->cand_state.alloc((size_t)r->S.pitch, false));
       }
-      if (n > 0) SMX_HIP(hipMemcpyAsync(r->cand_state, state, n, hipMemcpyHostToDevice, st));
-      dstate = r->cand_state;
+      if (n > 0) SMX_HIP(hipMemcpyAsync(r->cand_state.get(), state, n, hipMemcpyHostToDevice, st));
+      dstate = r->cand_state.get();
     }
   }
-  float* q = r->cand_q;
+  float* q = r->cand_q.get();
   const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_indices + kBlock - 1) / kBlock, 4096);
   hipLaunchKernelGGL(k_candidate_queries, dim3(blocks), dim3(kBlock), 0, st, r->S, dslots, n_indices, r->st,
                      radius_factor_squared, q);
@@ -765,14 +760,14 @@ int smx_recon_check_triangles(smx_recon r, smx_stream s, const uint32_t* triangl
   if (!on_device) {
     SMX_CALL(dtri.alloc((size_t)n_triangles * 3));
     SMX_CALL(dflags.alloc(n_triangles));
-    SMX_HIP(hipMemcpyAsync(dtri.p, triangles, (size_t)n_triangles * 12, hipMemcpyHostToDevice, st));
+    SMX_HIP(hipMemcpyAsync(dtri.get(), triangles, (size_t)n_triangles * 12, hipMemcpyHostToDevice, st));
   }
   const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_triangles + kBlock - 1) / kBlock, 8192);
-  hipLaunchKernelGGL(k_check_triangles, dim3(blocks), dim3(kBlock), 0, st, r->S, on_device ? triangles : dtri.p,
-                     n_triangles, r->st, long_edge_total_factor_squared, on_device ? flags : dflags.p);
+  hipLaunchKernelGGL(k_check_triangles, dim3(blocks), dim3(kBlock), 0, st, r->S, on_device ? triangles : dtri.get(),
+                     n_triangles, r->st, long_edge_total_factor_squared, on_device ? flags : dflags.get());
   SMX_LAUNCH_CHECK();
   if (!on_device) {
-    SMX_HIP(hipMemcpyAsync(flags, dflags.p, n_triangles, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(flags, dflags.get(), n_triangles, hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
   return SMX_OK;
@@ -853,8 +848,8 @@ int smx_recon_debug_download_surfels(smx_recon r, smx_stream s, float* rows, uin
   if (count == 0) return SMX_OK;
   SMX_CALL(join_regularizer(r, (hipStream_t)s));
   SMX_CALL(acquire_staging(r, (hipStream_t)s, (size_t)kRows * count));
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S, all_rows(), r->staging, count);
-  SMX_HIP(hipMemcpyAsync(rows, r->staging, (size_t)kRows * count * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
+  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S, all_rows(), r->staging.get(), count);
+  SMX_HIP(hipMemcpyAsync(rows, r->staging.get(), (size_t)kRows * count * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));
   return SMX_OK;
 }
@@ -866,8 +861,8 @@ int smx_recon_debug_upload_surfels(smx_recon r, smx_stream s, const float* rows,
   hipStream_t st = (hipStream_t)s;
   if (count) {
     SMX_CALL(acquire_staging(r, st, (size_t)kRows * count));
-    SMX_HIP(hipMemcpyAsync(r->staging, rows, (size_t)kRows * count * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_unpack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, all_rows(), r->staging, count);
+    SMX_HIP(hipMemcpyAsync(r->staging.get(), rows, (size_t)kRows * count * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_unpack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, all_rows(), r->staging.get(), count);
   }
   DevState h;
   memset(&h, 0, sizeof(h));
@@ -892,28 +887,27 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
     set_error("old_to_new holds %u entries, the map has %u slots", capacity, n);
     return SMX_ERR_INVALID_ARGUMENT;
   }
-  if (!r->cmp_map) {
-    int rc = dev_alloc(&r->cmp_map, r->S.pitch, false);
-    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_seg, (size_t)r->nseg, false);
-    if (rc == SMX_OK) rc = dev_alloc(&r->cmp_out, 2, false);
-    if (rc != SMX_OK) return rc;
+  if (!r->cmp_out.get()) {   // (allocated last: it stands for all three)
+    SMX_CALL(r->cmp_map.alloc(r->S.pitch, false));
+    SMX_CALL(r->cmp_seg.alloc((size_t)r->nseg, false));
+    SMX_CALL(r->cmp_out.alloc(2, false));
   }
-  SMX_HIP(hipMemsetAsync(r->cmp_out, 0, 2 * sizeof(uint32_t), st));
+  SMX_HIP(hipMemsetAsync(r->cmp_out.get(), 0, 2 * sizeof(uint32_t), st));
   const dim3 b(kBlock);
   if (n) {
     const int nseg_used = div_up((long long)n, kSeg);
     // (merge_flag -- one byte per slot, reset below -- holds the keep bits: a byte per four slots)
-    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, r->cmp_seg);
-    enqueue_segment_scan(st, r->cmp_seg, nseg_used, r->cmp_out);
-    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, r->cmp_seg, n, r->cmp_map);
+    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, r->cmp_seg.get());
+    enqueue_segment_scan(st, r->cmp_seg.get(), nseg_used, r->cmp_out.get());
+    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, r->cmp_seg.get(), n, r->cmp_map.get());
     SMX_LAUNCH_CHECK();
     SMX_CALL(acquire_staging(r, st, (size_t)4 * n));
-    float4* tmp = reinterpret_cast<float4*>(r->staging);
+    float4* tmp = reinterpret_cast<float4*>(r->staging.get());
     const int groups[5] = {kGroupP, kGroupS, kGroupN, kGroupC, kGroupT};
     for (int g : groups) {
-      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
-      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map, n, tmp, r->cmp_out + 1);
-      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, r->cmp_out);
+      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map.get(), n, tmp, r->cmp_out.get() + 1);
+      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map.get(), n, tmp, r->cmp_out.get() + 1);
+      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, r->cmp_out.get());
     }
     SMX_LAUNCH_CHECK();
     SMX_CALL(release_staging(r, st));
@@ -930,10 +924,10 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
   //    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
   // The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
   // has been read again, and reading a segment resets its streak).
-  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, r->cmp_out);
+  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, r->cmp_out.get());
   SMX_CALL(reset_accumulators(r, st));
   if (r->L.dirty8)
-    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), r->cmp_out);
+    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), r->cmp_out.get());
   SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
   SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
   SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
@@ -943,9 +937,9 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
   uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
   SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
   if (old_to_new && n)
-    SMX_HIP(hipMemcpyAsync(old_to_new, r->cmp_map, (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(old_to_new, r->cmp_map.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   uint32_t out[2] = {0, 0};
-  SMX_HIP(hipMemcpyAsync(out, r->cmp_out, sizeof(out), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(out, r->cmp_out.get(), sizeof(out), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   if (new_size) *new_size = out[0];
   if (links_dropped) *links_dropped = out[1];
@@ -963,14 +957,14 @@ int smx_recon_deform_by_creation_frame(smx_recon r, smx_stream s, const float* f
   DevTemp<uint8_t> dre(st);
   if (!inputs_on_device) {
     SMX_CALL(dT.alloc((size_t)n_frames * 12));
-    SMX_HIP(hipMemcpyAsync(dT.p, frame_T, (size_t)n_frames * 48, hipMemcpyHostToDevice, st));
+    SMX_HIP(hipMemcpyAsync(dT.get(), frame_T, (size_t)n_frames * 48, hipMemcpyHostToDevice, st));
     if (reactivate) {
       SMX_CALL(dre.alloc(n_frames));
-      SMX_HIP(hipMemcpyAsync(dre.p, reactivate, n_frames, hipMemcpyHostToDevice, st));
+      SMX_HIP(hipMemcpyAsync(dre.get(), reactivate, n_frames, hipMemcpyHostToDevice, st));
     }
   }
   hipLaunchKernelGGL(k_deform_by_creation_frame, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S,
-                     inputs_on_device ? frame_T : dT.p, n_frames, inputs_on_device ? reactivate : dre.p, frame_index,
+                     inputs_on_device ? frame_T : dT.get(), n_frames, inputs_on_device ? reactivate : dre.get(), frame_index,
                      r->L.dirty8, r->st);
   SMX_LAUNCH_CHECK();
   // positions and stamps changed behind the work lists, segment boxes and the flag table

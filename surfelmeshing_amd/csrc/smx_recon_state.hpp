@@ -216,7 +216,11 @@ struct SegWork {
 
 }  // namespace smx
 
+// Created value-initialised (everything zero / empty).  `mem` owns the blocks smx_recon_create allocates -- the pointers
+// in S, L, fb, sc, tb, sw, bb and the plain pointer members below are views of them -- and every buffer a service
+// allocates on demand is a DevBuf.
 struct smx_recon_s {
+  smx::DevBlocks mem;
   int device;               // the HIP device the object lives on (every entry point runs on it)
   uint32_t max_surfels;
   int W, H;
@@ -280,12 +284,11 @@ struct smx_recon_s {
   int prof_slot;
   int prof_cap, prof_n;
   hipEvent_t* prof_ev;
-  uint32_t* delta_seg;   // delta hand-off: per-segment counts / offsets, and the total
-  uint32_t* delta_total;
-  float* staging;    // row-layout staging for the boundary conversions (TransferAllToCPU, debug rows)
-  size_t staging_floats;
-  float* cand_q; uint32_t* cand_slots; uint8_t* cand_state;   // workspace of smx_recon_neighbor_candidates
-  uint32_t cand_cap, cand_state_cap;
+  smx::DevBuf<uint8_t> dirty;         // delta tracking: the block behind L.dirty8 while it is on
+  smx::DevBuf<uint32_t> delta_seg;    // delta hand-off: per-segment counts / offsets, and the total
+  smx::DevBuf<uint32_t> delta_total;
+  smx::DevBuf<float> staging;    // row-layout staging for the boundary conversions (TransferAllToCPU, debug rows)
+  smx::DevBuf<float> cand_q; smx::DevBuf<uint32_t> cand_slots; smx::DevBuf<uint8_t> cand_state;   // workspace of smx_recon_neighbor_candidates
   hipEvent_t ev_staging;  // recorded after the last enqueued read of `staging`: TransferAllToCPU returns with its
   bool staging_busy;      // row downloads in flight, and the next user may come on another stream
   int grid_surfels;  // persistent grid for the grid-stride all-slot kernels
@@ -310,17 +313,16 @@ struct smx_recon_s {
   uint8_t* flags_buf[2];    // the flag table is double-buffered by frame (L.flags8 = the current frame's)
   bool have_frame;          // an Integrate call has been made since creation / the last state upload
   uint32_t last_frame;      // its frame_index: the segment culling of pass A presumes that it never decreases
-  uint32_t* cmp_map;        // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
-  uint32_t* cmp_seg;        // offsets [nseg], and [0] = new count, [1] = links dropped
-  uint32_t* cmp_out;
-  unsigned long long* zbuf; // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
-  size_t zbuf_px;           // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
-  hipEvent_t ev_render;
+  smx::DevBuf<uint32_t> cmp_map;   // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
+  smx::DevBuf<uint32_t> cmp_seg;   // offsets [nseg], and [0] = new count, [1] = links dropped
+  smx::DevBuf<uint32_t> cmp_out;
+  smx::DevBuf<unsigned long long> zbuf;   // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
+  hipEvent_t ev_render;                   // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
   bool render_busy;
-  float* trk_depth;         // smx_recon_track (allocated by its first call): the model images [H][W] of the last call,
-  float4* trk_normal;       // the reduce kernel's per-workgroup partial sums, the call's device state, and the mark
-  double* trk_slabs;        // after the last call's kernels (the next call, on whatever stream, waits for it)
-  smx::TrackDev* trk_state;
+  smx::DevBuf<float> trk_depth;         // smx_recon_track (allocated by its first call, all four or none): the model images [H][W]
+  smx::DevBuf<float4> trk_normal;       // of the last call, the reduce kernel's per-workgroup partial sums, the call's device state,
+  smx::DevBuf<double> trk_slabs;        // and the mark after the last call's kernels (the next call, on whatever stream, waits for it)
+  smx::DevBuf<smx::TrackDev> trk_state;
   hipEvent_t ev_track;
   bool track_busy;
   smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging
@@ -340,12 +342,5 @@ int acquire_staging(smx_recon r, hipStream_t st, size_t floats);
 int release_staging(smx_recon r, hipStream_t st);
 // After surfel attributes were changed from outside the frame loop (state upload, compaction, deformation).
 int invalidate_derived(smx_recon r, hipStream_t st);
-
-template <typename T>
-int dev_alloc(T** p, size_t count, bool zero) {
-  SMX_HIP(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-  if (zero) SMX_HIP(hipMemset(*p, 0, count * sizeof(T)));
-  return SMX_OK;
-}
 
 }  // namespace smx

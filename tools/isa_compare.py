@@ -1,0 +1,83 @@
+"""python tools/isa_compare.py <old tree> <new tree>: is the device code of two checkouts the same, kernel by kernel?
+
+Every file of build.SOURCES is compiled device-only to gfx950 assembly in both trees (the flags of tools/isa_regs.sh).  Per
+kernel: the descriptor's registers, LDS and scratch, and the instruction stream with comments and directives dropped,
+basic-block labels renumbered and symbol names demangled without "(anonymous namespace)::" and "smx::" (the method of
+profiles/recon_split_isa.txt).  Prints one line per kernel and the number that differ; needs no GPU."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from surfelmeshing_amd.build import SOURCES, _hipcc  # noqa: E402
+
+STRIP = ("(anonymous namespace)::", "smx::")
+
+
+def compile_to_asm(root, src, out):
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-I", os.path.join(root, "include"),
+           "-I", os.path.join(root, "surfelmeshing_amd", "csrc"), "-x", "hip", "--cuda-device-only", "-S",
+           os.path.join(root, "surfelmeshing_amd", "csrc", src), "-o", out]
+    return subprocess.Popen(cmd, stderr=subprocess.DEVNULL)
+
+
+def demangle(names):
+    tool = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    out = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    for s in STRIP:
+        out = [o.replace(s, "") for o in out]
+    return out[:len(names)]
+
+
+def kernels(path):
+    """{mangled name: ((vgpr, sgpr, lds, scratch), normalised stream, instruction count)} in file order."""
+    s = open(path).read()
+    res = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S):
+        name, d = m.group(1), m.group(2)
+        desc = tuple(int(re.search(k + r"\s+(\d+)", d).group(1)) for k in
+                     (r"\.amdhsa_next_free_vgpr", r"\.amdhsa_next_free_sgpr", r"\.amdhsa_group_segment_fixed_size",
+                      r"\.amdhsa_private_segment_fixed_size"))
+        body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(name), s, re.S | re.M).group(1)
+        lines = [re.sub(r"\s*;.*$", "", ln).strip() for ln in body.split("\n")]
+        text = "\n".join(ln for ln in lines if ln and not (ln.startswith(".") and not ln.endswith(":")))
+        labels = {}
+        for lab in re.findall(r"\.LBB\d+_\d+", text):
+            labels.setdefault(lab, ".L%d" % len(labels))
+        text = re.sub(r"\.LBB\d+_\d+", lambda mm: labels[mm.group(0)], text)
+        syms = sorted(set(re.findall(r"_Z\w+", text)), key=len, reverse=True)
+        for sym, plain in zip(syms, demangle(syms) if syms else []):
+            text = text.replace(sym, plain)
+        res[name] = (desc, text, sum(1 for ln in text.split("\n") if not ln.endswith(":")))
+    return res
+
+
+def main(old, new):
+    tmp = tempfile.mkdtemp(prefix="isa_compare_")
+    jobs = []
+    for src in SOURCES:
+        outs = [os.path.join(tmp, "%s_%s.s" % (tag, src)) for tag in ("old", "new")]
+        jobs.append((src, outs, [compile_to_asm(root, src, out) for root, out in zip((old, new), outs)]))
+    print("%-70s %-18s %5s %5s %6s %7s %7s  %s" % ("kernel", "file", "vgpr", "sgpr", "lds", "scratch", "instrs", "verdict"))
+    total = differ = 0
+    for src, outs, procs in jobs:
+        if any(p.wait() != 0 for p in procs):
+            raise SystemExit("hipcc failed on " + src)
+        ko, kn = kernels(outs[0]), kernels(outs[1])
+        if list(ko) != list(kn):
+            raise SystemExit("%s: the two trees do not have the same kernels: %s" % (src, sorted(set(ko) ^ set(kn))))
+        for name, pretty in zip(kn, demangle(list(kn)) if kn else []):
+            same = ko[name][:2] == kn[name][:2]
+            total, differ = total + 1, differ + (not same)
+            print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (re.sub(r"\(.*$", "", pretty)[:70], src, *kn[name][0], kn[name][2],
+                                                          "identical" if same else "DIFFERS"))
+    shutil.rmtree(tmp)
+    print("%d kernels, %d differ" % (total, differ))
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])))
