@@ -44,19 +44,12 @@ struct WorkSet {
 // tenth slower for its whole length (period 165 instead of 150 us at C2: both stream hand-overs twice as long), 0 of 40 runs
 // with the preprocessing at the default priority, at 1.7 % less than the fast mode (6330 against 6440 frames/s; C3 1810
 // against 1804): the same in expectation, without the tail (profiles/r5_ab_notes.md).
-#ifndef SMX_PRE_PRIORITY
-#define SMX_PRE_PRIORITY 0
-#endif
-#ifndef SMX_PRE2_PRIORITY
-#define SMX_PRE2_PRIORITY SMX_PRE_PRIORITY
-#endif
+constexpr int kPrePriority = 0, kPre2Priority = kPrePriority;
 // Two preprocessing queues by default from this many pixels on (smx_driver_set_split_preprocessing overrides): at 1280 x 960
 // the single queue is the frame's pace-maker -- the caller's stream waits 150 - 230 us a frame for its images -- and two
 // queues are worth + 2.0 % (1 866 - 1 871 against 1 825 - 1 836 frames/s, profiles/r8o_C3_timelines.jsonl); at 640 x 480 the
 // surfel chains pace the frame and the second queue costs 2 - 3 % (profiles/r6_ab_notes.md section 2, r8p).
-#ifndef SMX_SPLIT_PRE_MIN_PIXELS
-#define SMX_SPLIT_PRE_MIN_PIXELS (1024 * 768)
-#endif
+constexpr long long kSplitPreMinPixels = 1024 * 768;
 struct smx_driver_s {
   smx_driver_config cfg;
   PinholeCamera4f camera;
@@ -102,12 +95,12 @@ struct smx_driver_s {
   explicit smx_driver_s(const smx_driver_config& c, const float* intr)
       : cfg(c), camera(c.width, c.height, intr), reconstruction(c.max_surfel_count, camera),
         work0(c.height, c.width), work1(c.height, c.width), work2(c.height, c.width), last(&work0), prev(&work0) {
-    // (preprocessing runs ahead of the frame loop; its priority: see SMX_PRE_PRIORITY)
-    SMX_SHIM_CHECK(smx_stream_create_with_priority(&pre_stream, SMX_PRE_PRIORITY));
-    SMX_SHIM_CHECK(smx_stream_create_with_priority(&pre_stream2, SMX_PRE2_PRIORITY));
+    // (preprocessing runs ahead of the frame loop; its priority: see kPrePriority)
+    SMX_SHIM_CHECK(smx_stream_create_with_priority(&pre_stream, kPrePriority));
+    SMX_SHIM_CHECK(smx_stream_create_with_priority(&pre_stream2, kPre2Priority));
     SMX_SHIM_CHECK(smx_event_create(&run_start));
     SMX_SHIM_CHECK(smx_stream_synchronize(nullptr));
-    split_pre = (long long)c.width * c.height >= (long long)SMX_SPLIT_PRE_MIN_PIXELS;
+    split_pre = (long long)c.width * c.height >= kSplitPreMinPixels;
   }
   ~smx_driver_s() {
     smx_stream_synchronize(pre_stream); smx_stream_synchronize(pre_stream2); smx_stream_synchronize(nullptr);
@@ -648,8 +641,8 @@ int smx_driver_set_pre_cu_mask(smx_driver d, const uint32_t* mask_words, uint32_
     SMX_SHIM_CHECK(smx_stream_create_with_cu_mask(&a, mask_words, n_words));
     SMX_SHIM_CHECK(smx_stream_create_with_cu_mask(&b, mask_words, n_words));
   } else {
-    SMX_SHIM_CHECK(smx_stream_create_with_priority(&a, SMX_PRE_PRIORITY));
-    SMX_SHIM_CHECK(smx_stream_create_with_priority(&b, SMX_PRE2_PRIORITY));
+    SMX_SHIM_CHECK(smx_stream_create_with_priority(&a, kPrePriority));
+    SMX_SHIM_CHECK(smx_stream_create_with_priority(&b, kPre2Priority));
   }
   smx_stream_destroy(d->pre_stream); smx_stream_destroy(d->pre_stream2);
   d->pre_stream = a; d->pre_stream2 = b;

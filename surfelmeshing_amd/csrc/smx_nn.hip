@@ -129,13 +129,10 @@ __device__ __forceinline__ int cell_coord(float p, float mn, float cell, int dim
   return c < 0 ? 0 : (c >= dim ? dim - 1 : c);
 }
 // The bricks' order in the sorted index -- and with it the order in which the self-query tiles are worked on -- follows a
-// Z-order (Morton) curve (SMX_NN_MORTON 1; 0 = rows, columns, planes: rounds 2 - 6).  A tile stages the bricks AROUND its own, and
+// Z-order (Morton) curve (rows, columns, planes in rounds 2 - 6).  A tile stages the bricks AROUND its own, and
 // with linear brick numbers the bricks of the next row lie a row of tiles away and those of the next plane hundreds of thousands:
 // whatever one tile staged was gone from the L2 when its neighbours came (hit rate 51 %, PMC traffic 1.74 x the algorithmic bytes,
 // unmoved by every tile-mapping variant of round 6).  Results do not depend on the order (rows are sorted by (d^2, index)).
-#ifndef SMX_NN_MORTON
-#define SMX_NN_MORTON 1
-#endif
 __host__ __device__ __forceinline__ unsigned long long spread3(unsigned long long v) {   // bit k of the 21-bit v -> bit 3 k
   v &= 0x1FFFFFull;
   v = (v | (v << 32)) & 0x1F00000000FFFFull;
@@ -145,14 +142,8 @@ __host__ __device__ __forceinline__ unsigned long long spread3(unsigned long lon
   v = (v | (v << 2)) & 0x1249249249249249ull;
   return v;
 }
-__device__ __forceinline__ unsigned long long brick_index(const Grid& g, int bx, int by, int bz) {
-#if SMX_NN_MORTON
-  (void)g;
+__device__ __forceinline__ unsigned long long brick_index(int bx, int by, int bz) {
   return spread3((unsigned long long)bx) | (spread3((unsigned long long)by) << 1) | (spread3((unsigned long long)bz) << 2);
-#else
-  return ((unsigned long long)bz * (unsigned long long)g.bdim[1] + (unsigned long long)by) * (unsigned long long)g.bdim[0] +
-         (unsigned long long)bx;
-#endif
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -165,7 +156,7 @@ k_point_keys(const float* __restrict__ x, const float* __restrict__ y, const flo
       const int cy = cell_coord(y[i], g.min[1], g.cell, g.dim[1]);
       const int cz = cell_coord(z[i], g.min[2], g.cell, g.dim[2]);
       const uint32_t local = (uint32_t)(((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3));
-      k = (brick_index(g, cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift) << kLocalBits) | local;
+      k = (brick_index(cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift) << kLocalBits) | local;
     }
     keys[i] = k;
     vals[i] = i;
@@ -335,32 +326,6 @@ __device__ __forceinline__ bool find_brick(const BrickSlot* __restrict__ table, 
   }
 }
 
-// The same look-up with the first kSpec probe positions requested TOGETHER: a miss (most of the 27 bricks around a surface
-// tile are empty) ends at the first empty slot of its probe sequence, two or three dependent round trips down the line when
-// they are taken one at a time -- and the tile's look-ups last as long as the longest of them.
-template <int kSpec>
-__device__ __forceinline__ bool find_brick_spec(const BrickSlot* __restrict__ table, uint32_t mask, unsigned long long brick,
-                                                uint32_t& start, uint32_t& end) {
-  uint32_t s = hash_brick(brick, mask);
-  uint4 e[kSpec];
-#pragma unroll
-  for (int u = 0; u < kSpec; ++u) e[u] = *reinterpret_cast<const uint4*>(&table[(s + (uint32_t)u) & mask]);
-#pragma unroll
-  for (int u = 0; u < kSpec; ++u) {
-    const unsigned long long key = ((unsigned long long)e[u].y << 32) | e[u].x;
-    if (key == brick + 1ull) { start = e[u].z; end = e[u].w; return true; }
-    if (key == 0ull) return false;
-  }
-  s = (s + (uint32_t)kSpec) & mask;
-  for (;;) {
-    const uint4 f = *reinterpret_cast<const uint4*>(&table[s]);
-    const unsigned long long key = ((unsigned long long)f.y << 32) | f.x;
-    if (key == brick + 1ull) { start = f.z; end = f.w; return true; }
-    if (key == 0ull) return false;
-    s = (s + 1u) & mask;
-  }
-}
-
 struct BuildCounts { uint32_t n_valid, n_bricks; };
 
 // counts of indexed points and of occupied bricks (one partial per workgroup, summed by k_sum_counts)
@@ -441,7 +406,7 @@ k_query_keys(const float* __restrict__ qx, const float* __restrict__ qy, const f
     const int cx = cell_coord(qx[q], g.min[0], g.cell, g.dim[0]);
     const int cy = cell_coord(qy[q], g.min[1], g.cell, g.dim[1]);
     const int cz = cell_coord(qz[q], g.min[2], g.cell, g.dim[2]);
-    keys[q] = brick_index(g, cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift);
+    keys[q] = brick_index(cx >> kBrickShift, cy >> kBrickShift, cz >> kBrickShift);
     vals[q] = q;
   }
 }
@@ -626,7 +591,7 @@ k_query_tiles(QueryArgs a) {
           const int bx = blo[0] + (int)(b % (unsigned long long)bn[0]);
           const int by = blo[1] + (int)((b / (unsigned long long)bn[0]) % (unsigned long long)bn[1]);
           const int bz = blo[2] + (int)(b / ((unsigned long long)bn[0] * (unsigned long long)bn[1]));
-          if (!find_brick(a.table, a.mask, brick_index(g, bx, by, bz), s, e)) { s = 0; e = 0; }
+          if (!find_brick(a.table, a.mask, brick_index(bx, by, bz), s, e)) { s = 0; e = 0; }
           clo[0] = bx << kBrickShift; clo[1] = by << kBrickShift; clo[2] = bz << kBrickShift;
           chi[0] = clo[0] + kBrickCells - 1; chi[1] = clo[1] + kBrickCells - 1; chi[2] = clo[2] + kBrickCells - 1;
         }
@@ -754,10 +719,7 @@ k_query_tiles(QueryArgs a) {
 // arithmetic, same total order: the rows are identical to k_query_tiles'.  What does not fit the simple shape --
 // more than kLaneCap matches, a region of more than 64 bricks or more than kStageL points -- is marked and answered
 // by k_query_tiles afterwards (same launch sequence, no host round trip).
-#ifndef SMX_STAGE_L
-#define SMX_STAGE_L 256
-#endif
-constexpr int kStageL = SMX_STAGE_L;     // staged points per tile, after the box filter (a surfel surface at cell = 1.5 x spacing: 60 - 100).
+constexpr int kStageL = 256;     // staged points per tile, after the box filter (a surfel surface at cell = 1.5 x spacing: 60 - 100).
 static_assert(kStageL <= 256, "a lane's list holds stage positions as bytes");
 // LDS decides how many of these one-wavefront workgroups a CU holds, and the kernel lives on that: 768 entries (17 KB with the
 // lists) 2.86 G queries/s at C5, 512: 3.32, 384: 3.87, 288 (9 KB: what the sorted keys needed to park in) 4.26 --
@@ -801,29 +763,15 @@ __device__ __forceinline__ void sort_lane_matches(const float4* __restrict__ sta
           }
         }
 }
-#ifndef SMX_NN_BRANCHFREE
-#define SMX_NN_BRANCHFREE 1   // (the walk's append: 1 = predicated, 0 = a branch per candidate as in rounds 3-5; profiles/r6_ab_notes.md)
-#endif
 // kFilter: the caller passed a state row (skip kFree / kCompleted surfels, APP/octree.cc:330-335) -- a template parameter,
 // because the test sits in the innermost loop: as a run-time (uniform) condition it cost every candidate an exec-mask
 // save, a branch and a restore whether a state row was there or not.
-#ifndef SMX_NN_STAGE_MLP
-#define SMX_NN_STAGE_MLP 6   // (1: 5.67, 2: 6.05, 4: 6.25 G queries/s at C5 with the table-order tiles; 6 on top of the key-order tiles: 6.86 -> 7.05; profiles/r6_ab_notes.md)
-#endif
-#ifndef SMX_NN_SELF_SORTED
-#define SMX_NN_SELF_SORTED 1
-#endif
-#ifndef SMX_NN_XCD_MAP
-#define SMX_NN_XCD_MAP 0   // (measured: 6.82 - 6.92 against 6.89 - 6.95 G queries/s without -- the kernel is not bound by its bytes; profiles/r6_ab_notes.md)
-#endif
-#ifndef SMX_NN_PROBE_SPEC
-#define SMX_NN_PROBE_SPEC 1
-#endif
-#ifndef SMX_NN_LANES_WAVES
-#define SMX_NN_LANES_WAVES 1   // (__launch_bounds__'s second argument: 1 = let the compiler have the registers it likes)
-#endif
+// (records per lane the staging loop requests before it looks at the first.  1: 5.67, 2: 6.05, 4: 6.25 G queries/s at C5 with the
+// table-order tiles; 6 on top of the key-order tiles: 6.86 -> 7.05; profiles/r6_ab_notes.md)
+constexpr int kStageMlp = 6;
+constexpr int kLanesWaves = 1;   // (__launch_bounds__'s second argument: 1 = let the compiler have the registers it likes)
 template <bool kSelf, bool kFilter>
-__global__ void __launch_bounds__(64, SMX_NN_LANES_WAVES)
+__global__ void __launch_bounds__(64, kLanesWaves)
 k_query_lanes(QueryArgs a) {
   // one block: the stage, then the lanes' lists; the sorted keys later lie over both (neither is needed any more once
   // every lane holds its keys in registers).  LDS is what limits the wavefronts per CU here.
@@ -838,18 +786,7 @@ k_query_lanes(QueryArgs a) {
   const Grid& g = a.g;
   const uint32_t n_tiles = (kSelf && !a.tile_start) ? a.mask + 1u : *a.n_tiles;
   const int K = a.K;
-#if SMX_NN_XCD_MAP
-  // Workgroup b runs on XCD b % 8, and every XCD has an L2 of its own: with tile = blockIdx + k * gridDim the eight
-  // neighbours of a tile in key order are staged by eight DIFFERENT L2s and each brick is fetched from memory once per XCD
-  // that needs it.  Here every XCD walks a contiguous eighth of the tiles, its workgroups side by side: what a tile stages,
-  // the tiles next to it (same row of bricks) and a row further (a few hundred tiles on) find in that XCD's L2.
-  const uint32_t xcd = blockIdx.x & 7u, wi = blockIdx.x >> 3, per_xcd = (n_tiles + 7u) / 8u, wgs_per_xcd = gridDim.x >> 3;
-  for (uint32_t ti = wi; ti < per_xcd; ti += wgs_per_xcd) {
-    const uint32_t t = xcd * per_xcd + ti;
-    if (t >= n_tiles) break;
-#else
   for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-#endif
     uint32_t sub_begin, sub_end;
     if (kSelf && !a.tile_start) {
       const uint4 slot = *reinterpret_cast<const uint4*>(&a.table[t]);
@@ -921,11 +858,7 @@ k_query_lanes(QueryArgs a) {
             const int bx = kb[0] + (int)(lane % (uint32_t)bn[0]);
             const int by = kb[1] + (int)((lane / (uint32_t)bn[0]) % (uint32_t)bn[1]);
             const int bz = kb[2] + (int)(lane / ((uint32_t)bn[0] * (uint32_t)bn[1]));
-#if SMX_NN_PROBE_SPEC > 1
-            if (!find_brick_spec<SMX_NN_PROBE_SPEC>(a.table, a.mask, brick_index(g, bx, by, bz), s, e)) { s = 0; e = 0; }
-#else
-            if (!find_brick(a.table, a.mask, brick_index(g, bx, by, bz), s, e)) { s = 0; e = 0; }
-#endif
+            if (!find_brick(a.table, a.mask, brick_index(bx, by, bz), s, e)) { s = 0; e = 0; }
           }
           const uint32_t len = e - s;
           uint32_t incl = len;
@@ -943,19 +876,18 @@ k_query_lanes(QueryArgs a) {
             // still care -- the walk was three quarters of this kernel's instructions.  (A record outside the box fails
             // d2 <= r2 for every query of the tile: cover_radius bounds |dx| of an accepted pair.)
             uint32_t cur = 0, kept = 0;
-#if SMX_NN_STAGE_MLP > 1
-            // (round 6: SMX_NN_STAGE_MLP records per lane requested before the first is looked at -- the loop was a chain of
+            // (round 6: kStageMlp records per lane requested before the first is looked at -- the loop was a chain of
             // dependent round trips, one per 64 records, five per tile at C5, in a kernel that is bound by exactly those)
-            for (uint32_t k0 = 0; k0 < total; k0 += 64 * SMX_NN_STAGE_MLP) {
-              float4 v[SMX_NN_STAGE_MLP];
+            for (uint32_t k0 = 0; k0 < total; k0 += 64 * kStageMlp) {
+              float4 v[kStageMlp];
 #pragma unroll
-              for (int u = 0; u < SMX_NN_STAGE_MLP; ++u) {
+              for (int u = 0; u < kStageMlp; ++u) {
                 const uint32_t k = min(k0 + 64u * u + lane, total - 1u);
                 while (k >= seg_end[cur]) ++cur;
                 v[u] = a.sorted[seg_src[cur] + k];
               }
 #pragma unroll
-              for (int u = 0; u < SMX_NN_STAGE_MLP; ++u) {
+              for (int u = 0; u < kStageMlp; ++u) {
                 const bool in = k0 + 64u * u + lane < total && v[u].x >= blo[0] && v[u].x <= bhi[0] && v[u].y >= blo[1] && v[u].y <= bhi[1] &&
                                 v[u].z >= blo[2] && v[u].z <= bhi[2];
                 const unsigned long long m = __ballot(in);
@@ -964,19 +896,6 @@ k_query_lanes(QueryArgs a) {
                 kept += (uint32_t)__popcll(m);
               }
             }
-#else
-            for (uint32_t k0 = 0; k0 < total; k0 += 64) {
-              const uint32_t k = min(k0 + lane, total - 1u);
-              while (k >= seg_end[cur]) ++cur;
-              const float4 v = a.sorted[seg_src[cur] + k];
-              const bool in = k0 + lane < total && v.x >= blo[0] && v.x <= bhi[0] && v.y >= blo[1] && v.y <= bhi[1] &&
-                              v.z >= blo[2] && v.z <= bhi[2];
-              const unsigned long long m = __ballot(in);
-              const uint32_t pos = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-              if (in && pos < (uint32_t)kStageL) stage[pos] = v;
-              kept += (uint32_t)__popcll(m);
-            }
-#endif
             __syncthreads();
             if (kept > (uint32_t)kStageL) { redo = ball; kept = 0; }   // (more than the stage holds: the other kernel)
             n_staged = total;   // (statistics: records read from the index; n_tests below counts the tests on the kept ones)
@@ -985,7 +904,6 @@ k_query_lanes(QueryArgs a) {
             // before the first test; a match is appended without a branch (a list that is full keeps overwriting its
             // spare last entry; cnt keeps counting and marks the query for the other kernel afterwards).
             const uint32_t lbase = lane * kLaneStride;
-#if SMX_NN_BRANCHFREE
             // Round 6: no branch in the walk.  A lane without a ball carries r^2 = -1 (no d^2 passes), so the test is the
             // compare alone; the append is predicated -- a match goes to entry min(cnt, kLaneCap) of the lane's list, a miss
             // to the list's dump byte (entry kLaneCap + 1; the stride leaves room) -- one byte store per candidate whatever
@@ -1009,26 +927,6 @@ k_query_lanes(QueryArgs a) {
               for (int u = 0; u < 4; ++u) test_one(rec[u], k0 + u);
             }
             for (; k0 < kept; ++k0) test_one(stage[k0], k0);
-#else
-            for (uint32_t k0 = 0; k0 < kept; k0 += 4) {
-              float4 rec[4];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) rec[u] = stage[min(k0 + u, kept - 1u)];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                const float dx = rec[u].x - px, dy = rec[u].y - py, dz = rec[u].z - pz;
-                const float d2 = dx * dx + dy * dy + dz * dz;
-                bool ok = ball && (k0 + u < kept) && d2 <= r2;
-                if (kFilter) {
-                  if (ok && (a.state[__float_as_uint(rec[u].w)] & a.skip_mask)) ok = false;
-                }
-                if (ok) {
-                  l_pos[lbase + min(cnt, (uint32_t)kLaneCap)] = (uint8_t)(k0 + u);
-                  ++cnt;
-                }
-              }
-            }
-#endif
             if (cnt > (uint32_t)kLaneCap) redo = true;
           }
         }
@@ -1167,7 +1065,7 @@ k_query_stream(QueryArgs a) {
           const int bx = blo[0] + (int)(b % (unsigned long long)bn[0]);
           const int by = blo[1] + (int)((b / (unsigned long long)bn[0]) % (unsigned long long)bn[1]);
           const int bz = blo[2] + (int)(b / ((unsigned long long)bn[0] * (unsigned long long)bn[1]));
-          if (!find_brick(a.table, a.mask, brick_index(g, bx, by, bz), s, e)) { s = 0; e = 0; }
+          if (!find_brick(a.table, a.mask, brick_index(bx, by, bz), s, e)) { s = 0; e = 0; }
         }
         unsigned long long segs = __ballot(e > s);
         while (segs) {
@@ -1398,14 +1296,12 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
       g.bdim[a] = (g.dim[a] + kBrickCells - 1) >> kBrickShift;
       bricks *= (unsigned long long)g.bdim[a];
     }
-#if SMX_NN_MORTON
     // (Z-order brick numbers: three interleaved fields as wide as the longest axis needs)
     int axis_bits = 1;
     for (int a = 0; a < 3; ++a) axis_bits = std::max(axis_bits, bit_length((unsigned long long)(g.bdim[a] - 1)));
     if (ok) bricks = 1ull << (3 * axis_bits);
     if (ok && 3 * axis_bits > 56) ok = false;
-#endif
-    if (ok && bit_length(bricks) <= (SMX_NN_MORTON ? 57 : 56)) {
+    if (ok && bit_length(bricks) <= 57) {
       g.sentinel = bricks << kLocalBits;
       g.key_bits = bit_length(g.sentinel);
       g.brick_bits = bit_length(bricks - 1);
@@ -1437,7 +1333,6 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
   SMX_HIP(hipMemsetAsync(nn->table.get(), 0, slots * sizeof(BrickSlot), st));
   hipLaunchKernelGGL(k_brick_insert, dim3(grid), dim3(kBlock), 0, st, nn->keys[0].get(), h.n_valid, nn->table.get(), (uint32_t)(slots - 1));
   hipLaunchKernelGGL(k_brick_ends, dim3(grid), dim3(kBlock), 0, st, nn->keys[0].get(), h.n_valid, nn->table.get(), (uint32_t)(slots - 1));
-#if SMX_NN_SELF_SORTED
   // The self queries' tiles in KEY order (round 6).  Rounds 2-5 walked the brick TABLE: tile = hash slot -- half of the
   // slots empty (a round trip each to find out) and neighbouring bricks a random distance apart in the walk, so that each
   // tile's 27 bricks came from memory anew (PMC traffic 1.78 x the algorithmic bytes).  In key order (brick index, row-major)
@@ -1461,7 +1356,6 @@ int smx_nn_build(smx_nn nn, smx_stream s, const float* x, const float* y, const 
     hipLaunchKernelGGL(k_tile_starts, dim3(grid), dim3(kBlock), 0, st, flags, h.n_valid, total, nn->self_tile_start.get());
     SMX_HIP(hipMemcpyAsync(nn->self_n_tiles.get(), total, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   }
-#endif
   SMX_LAUNCH_CHECK();
   nn->n_valid = h.n_valid; nn->n_bricks = h.n_bricks;
   return SMX_OK;
@@ -1540,7 +1434,7 @@ int smx_nn_query_batch(smx_nn nn, smx_stream s, uint32_t nq, const float* qx, co
     a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat.get() + 4);
     a.tile_redo = nn->tile_redo_q.get();
     SMX_HIP(hipMemsetAsync(a.redo_flag, 0, 4, st));
-    const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, (size_t)nq + 1) & ~7u);   // (a multiple of 8: SMX_NN_XCD_MAP)
+    const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, (size_t)nq + 1) & ~7u);   // (a multiple of 8: a whole number of workgroups per XCD)
     if (a.state) hipLaunchKernelGGL((k_query_lanes<false, true>), dim3(lb), dim3(64), 0, st, a);
     else hipLaunchKernelGGL((k_query_lanes<false, false>), dim3(lb), dim3(64), 0, st, a);
     a.redo = 1;
@@ -1573,18 +1467,14 @@ int smx_nn_query_self(smx_nn nn, smx_stream s, const float* radius_squared, floa
   a.out_idx = out_idx; a.out_d2 = out_d2; a.out_count = out_count;
   a.self_r2 = radius_squared; a.self_factor = factor;
   a.stat = nn->stats_enabled ? nn->stat.get() : nullptr;
-#if SMX_NN_SELF_SORTED
   a.tile_start = nn->self_tile_start.get(); a.n_tiles = nn->self_n_tiles.get();   // tiles in key order (smx_nn_build)
   const size_t tiles_bound = (size_t)nn->n_bricks + (size_t)nn->n_valid / kTile + 2;
-#else
-  const size_t tiles_bound = nn->table_slots;
-#endif
   const unsigned blocks = (unsigned)std::min<size_t>((size_t)nn->grid_blocks, tiles_bound);
   if (nn->query_mode == 2) {
     a.redo_flag = reinterpret_cast<uint32_t*>(nn->stat.get() + 4);
     a.tile_redo = nn->tile_redo_self.get();
     SMX_HIP(hipMemsetAsync(a.redo_flag, 0, 4, st));
-    const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, tiles_bound) & ~7u);   // (a multiple of 8: SMX_NN_XCD_MAP)
+    const unsigned lb = std::max(8u, (unsigned)std::min<size_t>((size_t)nn->grid_blocks * 4, tiles_bound) & ~7u);   // (a multiple of 8: a whole number of workgroups per XCD)
     if (a.state) hipLaunchKernelGGL((k_query_lanes<true, true>), dim3(lb), dim3(64), 0, st, a);
     else hipLaunchKernelGGL((k_query_lanes<true, false>), dim3(lb), dim3(64), 0, st, a);
     a.redo = 1;

@@ -282,77 +282,36 @@ __device__ __forceinline__ void choose_segment_direction(const uint8_t* __restri
 // "These loads travel together": pins loaded values at this point of the program, so that every load issued above is in
 // flight before the first of them is waited for.  Without it the compiler sinks independent loads below the branches
 // that follow (it cannot know that a dependent round trip costs microseconds on the frame's latency chain and a wasted
-// 16-byte load nothing): tools/isa_phases.py counts the waits per kernel.
+// 16-byte load nothing): tools/isa_phases.py counts the waits per kernel.  Pinned (each group A/B'd on its own, profiles/
+// r6_ab_notes.md section 12): the walk's first descriptor with its counters, the edge kernel's bin reservations, pass B's first
+// four loads, the step kernel's bin state + list entries; measured as not worth pinning: the records and pixel loads of
+// k_integrate and of the update kernel, pass A's records + flag bytes + next list entry.
 __device__ __forceinline__ void keep(uint32_t v) { asm volatile("" :: "v"(v)); }
 __device__ __forceinline__ void keep(int v) { asm volatile("" :: "v"(v)); }
 __device__ __forceinline__ void keep(float v) { asm volatile("" :: "v"(v)); }
 __device__ __forceinline__ void keep(const float2& v) { keep(v.x); keep(v.y); }
 __device__ __forceinline__ void keep(const float4& v) { keep(v.x); keep(v.y); keep(v.z); keep(v.w); }
+__device__ __forceinline__ void keep(const uint2& v) { keep(v.x); keep(v.y); }
 __device__ __forceinline__ void keep(const uint4& v) { keep(v.x); keep(v.y); keep(v.z); keep(v.w); }
-
-// Which groups of loads are pinned together by keep() (bit mask, A/B: profiles/r6_ab_notes.md section 12): 1 = the walk's first
-// descriptor with its counters, 2 = k_integrate's merge mark + records and its pixel loads, 4 = the update kernel's records and
-// pixel loads, 8 = the edge kernel's bin reservations, 16 = pass B's first four loads, 32 = the step kernel's bin state + list
-// entries, 64 = pass A's records + flag bytes + next list entry.
-#ifndef SMX_RT_MASK
-#define SMX_RT_MASK 57
-#endif
-template <int kBit, class T>
-__device__ __forceinline__ void keep_if(const T& v) { if (SMX_RT_MASK & kBit) keep(v); }
 
 // Wave priority of the surfel kernels (s_setprio 0 .. 3; 0 = the default every wavefront starts with).  The instruction arbiter
 // of a SIMD serves the highest priority first and the OLDEST wavefront among equals -- and the oldest wavefront beside these
 // short kernels is the bilateral filter's, which lives for the whole of its tile loop (A/B: profiles/r6_ab_notes.md section 13).
-#ifndef SMX_WAVE_PRIO
-#define SMX_WAVE_PRIO 1
-#endif
-#define SMX_SET_WAVE_PRIO() do { if (SMX_WAVE_PRIO) __builtin_amdgcn_s_setprio(SMX_WAVE_PRIO); } while (0)
-// Stores of a launch's streaming OUTPUTS -- records no lane of the same launch reads again.  A plain store leaves its line
-// dirty in the XCD's L2, and the launch boundary behind the kernel has to write all of them back before the next launch of
-// the stream may start (MI355X_MICROARCH.md, price table row "boundary": 1.45 - 1.9 us + dirty bytes / 6 TB/s; the edge
-// kernel leaves 30 MB, the frame 79 MB).  Flavours (tools/boundary.hip measures them behind writers of 0 - 64 MB; the
-// in-frame A/Bs are in profiles/r6_ab_notes.md): 0 = plain, 1 = nt (non-temporal: kept in the L2, marked for early
-// eviction), 2 = sc1 (write-through: leaves the L2 while the kernel still runs, the line is dropped), 3 = sc0 sc1.
-// One switch per store site so that each can be judged on its own:
-#ifndef SMX_ST_FARBIN
-#define SMX_ST_FARBIN 0    // k_reg_accumulate: far-term records into the destination segments' bins (sparse 16-byte stores)
-#endif
-#ifndef SMX_ST_REGREC
-#define SMX_ST_REGREC 0    // k_reg_accumulate: the recent slots' dense records (own term; in-segment sums)
-#endif
-#ifndef SMX_ST_STEP
-#define SMX_ST_STEP 0      // k_reg_step: the new smooth positions (scattered 16-byte records)
-#endif
-#ifndef SMX_ST_INT
-#define SMX_ST_INT 0       // k_integrate: the P / N / C records of the slots it changed
-#endif
-#ifndef SMX_ST_IMG
-#define SMX_ST_IMG 0       // k_assoc_tiles: the five association images
-#endif
+__device__ __forceinline__ void SMX_SET_WAVE_PRIO() { __builtin_amdgcn_s_setprio(1); }
+// Stores of a launch's streaming OUTPUTS -- records no lane of the same launch reads again: one plain 16-byte store.  (A plain
+// store leaves its line dirty in the XCD's L2 for the launch boundary to write back; non-temporal and write-through stores were
+// measured against it per store site and lost or made no difference: DESIGN.md "Retired variants".)
 typedef uint32_t v4u_t __attribute__((ext_vector_type(4)));
-template <int kFlavour>
-__device__ __forceinline__ void out_store16(void* p, const v4u_t& w) {
-  if (kFlavour == 1) __builtin_nontemporal_store(w, reinterpret_cast<v4u_t*>(p));
-  else if (kFlavour == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(p), "v"(w) : "memory");
-  else if (kFlavour == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(p), "v"(w) : "memory");
-  else *reinterpret_cast<v4u_t*>(p) = w;
-}
-template <int kFlavour>
-__device__ __forceinline__ void out_store16(void* p, const uint4& v) { const v4u_t w = {v.x, v.y, v.z, v.w}; out_store16<kFlavour>(p, w); }
-template <int kFlavour>
+__device__ __forceinline__ void out_store16(void* p, const v4u_t& w) { *reinterpret_cast<v4u_t*>(p) = w; }
+__device__ __forceinline__ void out_store16(void* p, const uint4& v) { const v4u_t w = {v.x, v.y, v.z, v.w}; out_store16(p, w); }
 __device__ __forceinline__ void out_store16(void* p, const float4& v) {
   const v4u_t w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-  out_store16<kFlavour>(p, w);
+  out_store16(p, w);
 }
-template <int kFlavour>
 __device__ __forceinline__ void out_store16(void* p, unsigned long long a, unsigned long long b) {
   const v4u_t w = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-  out_store16<kFlavour>(p, w);
+  out_store16(p, w);
 }
-
-// ---------------------------------------------------------------------------------------------
-// of the association images with plain stores.
-// of the association images with plain stores.  The maps of the multi-launch blend fallback (kernels.cc:165-166):
 
 // (value-distribution counters: only while statistics are on.  Two steps: the cull step's counter in front of it, the
 // others behind the stream's wait for the previous call's second half, whose kernels may still be adding to them)
@@ -496,9 +455,6 @@ k_scan_visible(Surfels S, FrameCtx c, Lists L, TileBins tb, SegWork sw, const ui
       const float4 p0 = P[0], p1 = P[1], p2 = P[2], p3 = P[3];
       const uint32_t of_word = *reinterpret_cast<const uint32_t*>(&flags_prev[il]);  // (detach bits carry over)
       next_seg = sw.surv_list[e + G < n_surv ? e + G : e];   // (no branch around the load: this entry again when it is the last)
-      // (the records, the old flag bytes and the next list entry: ONE round trip, pinned -- the compiler had asked for the
-      // next entry and waited, for the flag bytes and waited, and only then for the records: tools/isa_phases.py)
-      keep_if<64>(p0); keep_if<64>(p1); keep_if<64>(p2); keep_if<64>(p3); keep_if<64>(of_word); keep_if<64>(next_seg);
       if (base >= N) continue;   // (the cull step's bound on the slot count was generous)
       const uchar4 of = make_uchar4((uint8_t)(of_word & 255u), (uint8_t)((of_word >> 8) & 255u), (uint8_t)((of_word >> 16) & 255u), (uint8_t)(of_word >> 24));
       const uint32_t in_seg = (N - base < (uint32_t)kSeg) ? N - base : (uint32_t)kSeg;
@@ -662,7 +618,7 @@ __device__ __forceinline__ uint32_t walk_begin(const Chunks& ch, uint32_t n_slot
     cntv = ch.count[(threadIdx.x % kSubLists) * kCountStride];
     // (pinned: left to itself the compiler moves the descriptor's load behind the walk's first test -- `no step for this
     // workgroup' -- and the first step then begins a round trip late: tools/isa_phases.py)
-    keep_if<1>(desc); keep_if<1>(cntv);
+    keep(desc); keep(cntv);
     uint32_t longest = cntv;
 #pragma unroll
     for (uint32_t off = kSubLists / 2; off > 0; off >>= 1) longest = max(longest, (uint32_t)__shfl_xor((int)longest, (int)off));
@@ -696,7 +652,7 @@ __device__ __forceinline__ uint32_t vis_begin(const Lists& L, uint32_t n_slots_s
   if (kUseList) {
     ent = vis_load<true>(L, first);
     cntv = L.vis_chunks.count[(threadIdx.x % kSubLists) * kCountStride];
-    keep_if<1>(ent); keep_if<1>(cntv);
+    keep(ent); keep(cntv);
     uint32_t longest = (cntv + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
 #pragma unroll
     for (uint32_t off = kSubLists / 2; off > 0; off >>= 1) longest = max(longest, (uint32_t)__shfl_xor((int)longest, (int)off));
@@ -951,19 +907,11 @@ k_assoc_tiles(Surfels S, FrameCtx c, Scratch sc, Img<const uint16_t> depth, Img<
   SMX_STAMP(stamps, 4);
   if (in_image) {
     const size_t k = (size_t)y * c.W + x;
-#if SMX_ST_IMG   // (4- and 8-byte stores, full lines per wavefront row: non-temporal only -- a scalar sc1 store is a fabric write of its own)
-    __builtin_nontemporal_store(__int_as_float(t.zmin[lane]), &sc.first_depth[k]);
-    __builtin_nontemporal_store(t.sup[lane], &sc.supporting[k]);
-    __builtin_nontemporal_store(t.cnt[lane], &sc.counts[k]);
-    __builtin_nontemporal_store((long long)t.sum[lane], &sc.depth_sums[k]);
-    __builtin_nontemporal_store(t.confl[lane], &sc.confl_key[k]);
-#else
     sc.first_depth[k] = __int_as_float(t.zmin[lane]);
     sc.supporting[k] = t.sup[lane];
     sc.counts[k] = t.cnt[lane];
     sc.depth_sums[k] = (long long)t.sum[lane];
     sc.confl_key[k] = t.confl[lane];
-#endif
   }
   SMX_STAMP(stamps, 5);
   ts_end(c.ts, kTsTilesEnd, blockIdx.x, gridDim.x);
@@ -1307,9 +1255,6 @@ k_blend_tiles(int radius, float term, float ds, Img<const uint16_t> depth, Img<u
   if (gate_count) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (this wavefront's write-through stores have been acknowledged)
     __syncthreads();
-#if SMX_GATE_RELEASE
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-#endif
     if (threadIdx.x == 0) __hip_atomic_fetch_add(gate_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -1575,13 +1520,10 @@ k_integrate(Surfels S, FrameCtx c, Scratch sc, FrameIn in, Lists L,
     ent = (w + n_blocks < n_steps) ? vis_load<kUseList>(L, w + n_blocks) : 0u;   // (the next step's entries travel while this one is worked on)
     uint32_t i;
     if (!vis_entry<kUseList>(cur, w, cntv, n_scan, threadIdx.x, i)) continue;
-    // the merge mark and the three records the integration works on, requested together (pinned: the compiler would ask for
-    // the mark, wait, ask for P, wait for the activity test, and only then for N and C -- three round trips on a kernel
-    // that sits on both cycles of the frame)
+    // the merge mark and the three records the integration works on, requested together
     const uint32_t merge_mark = merge_flag[i];
     SurfelRegs R;
     R.P = *S.group(kGroupP, i); R.N = *S.group(kGroupN, i); R.C = *S.group(kGroupC, i);
-    keep_if<2>(merge_mark); keep_if<2>(R.P); keep_if<2>(R.N); keep_if<2>(R.C);
     if (merge_mark) {
       // apply the merge marks, kernels.cu:1987-1989 (decided in k_merge_decide)
       merge_flag[i] = 0;
@@ -1606,14 +1548,13 @@ k_integrate(Surfels S, FrameCtx c, Scratch sc, FrameIn in, Lists L,
     const bool second = quadrant(p, c, ox, oy);
     const PixelIn px0 = load_pixel(c, sc, in, p.px, p.py);
     const PixelIn px1 = load_pixel(c, sc, in, ox, oy);  // (the main pixel again if there is no second one)
-    if (SMX_RT_MASK & 2) { keep(px0); keep(px1); }   // (fourteen loads, one round trip: see above)
     integrate_or_conflict(R, c, px0, true, p.px, p.py, p.l, i, st);
     integrate_or_conflict(R, c, px1, second, ox, oy, p.l, i, st);
     if (R.dirty) {
       L.hot_epoch[i >> L.hot_shift] = (uint8_t)L.epoch;   // (stamp / colour mark may have changed, a replacement drops the links)
       if (L.dirty8) L.dirty8[i] = 1;
-      out_store16<SMX_ST_INT>(S.group(kGroupP, i), R.P); out_store16<SMX_ST_INT>(S.group(kGroupN, i), R.N);
-      out_store16<SMX_ST_INT>(S.group(kGroupC, i), R.C);
+      out_store16(S.group(kGroupP, i), R.P); out_store16(S.group(kGroupN, i), R.N);
+      out_store16(S.group(kGroupC, i), R.C);
       if (R.replaced) {
         *S.group(kGroupS, i) = make_float4(R.new_smooth.x, R.new_smooth.y, R.new_smooth.z, 0.0f);   // (whole records: see k_reg_step)
         S.set_neighbors(i, make_uint4(kInvalid, kInvalid, kInvalid, kInvalid));
@@ -1652,7 +1593,6 @@ __device__ __forceinline__ void update_neighbors_body(const Surfels& S, const Fr
     // the slot's three records in flight together (P: position + stamp, N: normal + r^2, T: neighbour ids)
     const float4 p4 = *S.group(kGroupP, i), n4 = *S.group(kGroupN, i);
     const uint4 t4 = *reinterpret_cast<const uint4*>(S.group(kGroupT, i));
-    keep_if<4>(p4); keep_if<4>(n4); keep_if<4>(t4);   // (pinned: N and T would otherwise be asked for behind the tests on P)
     if (!is_active(__float_as_uint(p4.w), c.frame, c.window)) continue;
     const Vec3 g = {p4.x, p4.y, p4.z};
     const Vec3 cam = mul(c.L, g);
@@ -1666,9 +1606,6 @@ __device__ __forceinline__ void update_neighbors_body(const Surfels& S, const Fr
     uint32_t cand[4];
 #pragma unroll
     for (int d = 0; d < 4; ++d) cand[d] = sc.supporting[(size_t)(y + kDY[d]) * c.W + (x + kDX[d])];
-    keep_if<4>(measurement_depth); keep_if<4>(obs_r2);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) keep_if<4>(cand[d]);
     const float occlusion_depth = (1 + c.sensor_noise_factor) * measurement_depth;
     if (cam.z > occlusion_depth) continue;
     const float surfel_distance = sqrtf(cam.x * cam.x + cam.y * cam.y + cam.z * cam.z);
@@ -1927,23 +1864,17 @@ constexpr int kBlockAcc = 256;
 static_assert(kSegAcc == kSegB && kBlockAcc == kBlockB, "the edge work runs on pass B's segments and workgroups (fused, or over its work lists)");
 __device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& ea, DevState* st, uint32_t base, uint32_t n_act,
                                              uint32_t ent_first, const uint32_t* later_entries, const EdgeLds& lds, uint32_t tid);
-#ifndef SMX_FUSE_EDGES
-#define SMX_FUSE_EDGES 0   // (default of the run-time switch; smx_recon_set_scan_mode bit 9 turns the fusion ON.  Measured: the fused
-                           // launch is shorter alone -- 58 us against 28 + 36 -- and LONGER in the frame, 90 us (heavy segments first) /
-                           // 72 us (last) against 34 + 42: C2 6150 / 6249 -> 5852 / 5825 frames/s, profiles/r5_ab_notes.md)
-#endif
-#ifndef SMX_FUSED_HEAVY_FIRST
-#define SMX_FUSED_HEAVY_FIRST 1
-#endif
-#ifndef SMX_FUSED_WGS_PER_CU
-#define SMX_FUSED_WGS_PER_CU 4   // (fused pass B: 36 KB of LDS per workgroup)
-#endif
+// (default of the run-time switch; smx_recon_set_scan_mode bit 9 turns the fusion ON.  Measured: the fused launch is shorter
+// alone -- 58 us against 28 + 36 -- and LONGER in the frame, 90 us (heavy segments first) / 72 us (last) against 34 + 42:
+// C2 6150 / 6249 -> 5852 / 5825 frames/s, profiles/r5_ab_notes.md)
+constexpr int kFuseEdgesDefault = 0;
+constexpr int kFusedWgsPerCu = 4;   // (fused pass B: 36 KB of LDS per workgroup)
 // kFused (A/B, off by default): the workgroup that finds work for the edge kernel in its segment does that work at once, from
 // the entries it has just ranked (in LDS instead of the global work list) -- one launch and its boundary less on the internal
-// stream, whose five launches a frame spend ~34 of their 154 us between kernels.  It loses in the frame (see SMX_FUSE_EDGES):
+// stream, whose five launches a frame spend ~34 of their 154 us between kernels.  It loses in the frame (see kFuseEdgesDefault):
 // 36 KB of LDS and 86 VGPRs for EVERY segment's workgroup, the streaming ones included, and the chip shared with the front.
 template <bool kDetach, bool kAccumulate, bool kFused = false>
-__global__ void __launch_bounds__(kBlockB, kFused ? SMX_FUSED_WGS_PER_CU : 1)
+__global__ void __launch_bounds__(kBlockB, kFused ? kFusedWgsPerCu : 1)
 k_neighbor_scan(Surfels S, int stats, int use_hot, Lists L, DevState* st, unsigned long long* ts, EdgeArgs ea, uint32_t descending) {
   SMX_SET_WAVE_PRIO();
   ts_begin(ts, kTsRegBegin);
@@ -1975,7 +1906,7 @@ k_neighbor_scan(Surfels S, int stats, int use_hot, Lists L, DevState* st, unsign
     if (threadIdx.x * 16 < L.n_hot_groups) he_first = *reinterpret_cast<const uint4*>(&L.hot_epoch[threadIdx.x * 16]);
     if (!stats) reached_first = L.seg_targets[(size_t)seg_id * kBlockB + threadIdx.x];
   }
-  keep_if<16>(N); keep_if<16>(detach_limit); keep_if<16>(he_first); keep_if<16>(reached_first);
+  keep(N); keep(detach_limit); keep(he_first); keep(reached_first);
   if (base >= N) return;
   // The far flag gathers (a link that leaves the segment: one random byte from the 5 MB table, 4.6 M per frame at C2,
   // 21 of this kernel's 55 us alone) are skipped where their result is known.  The flag byte of the target matters in
@@ -2221,36 +2152,6 @@ __device__ __forceinline__ void far_term_spill(long long* __restrict__ grad_acc,
   atomicAdd(&a[1], pack_pair(qz, 1 << (8 * (neighbor_count - 1))));
   fb.count[(size_t)(target / kSegB) * kCountStride + 1] = 1u;   // (the reader of that segment looks into grad_acc)
 }
-#ifndef SMX_LIST_WGS_PER_CU
-#define SMX_LIST_WGS_PER_CU 12   // (8 .. 32 measured: profiles/r17_ab_notes.md r26; the chunk lists hold ~3 000 steps at C2, ~10 000 at C3)
-#endif
-#ifndef SMX_PASS_A_WGS_PER_CU
-#define SMX_PASS_A_WGS_PER_CU 8
-#endif
-#ifndef SMX_EXT_STOP_EVENTS
-#define SMX_EXT_STOP_EVENTS 1   // (0: event records as packets of their own, the arrangement up to r22)
-#endif
-#ifndef SMX_GATE_RELEASE
-#define SMX_GATE_RELEASE 0   // (1: a device-scope release in front of the count, on top of the write-through stores -- A/B)
-#endif
-#ifndef SMX_HANDOVER_FLAGS
-#define SMX_HANDOVER_FLAGS 1   // (default of smx_recon_set_handover_mode)
-#endif
-#ifndef SMX_REG_PRIORITY_HIGH
-#define SMX_REG_PRIORITY_HIGH 1
-#endif
-#ifndef SMX_READY_WAIT_EARLY
-#define SMX_READY_WAIT_EARLY 2   // (where the call waits for its input images: 0 = between pass A and the tile kernel (rounds 3-4), 1 = next
-                                 // to the wait for the previous map (+0.5 %), 2 = at the very front of the call, in front of the cull step
-                                 // (+0.9 % on top: ONE barrier packet between the previous update + create and pass A); profiles/r5_ab_notes.md)
-#endif
-#ifndef SMX_ACC_WGS_PER_CU
-#define SMX_ACC_WGS_PER_CU 5   // (256-lane workgroups, 26 KB of LDS each; <= 96 VGPRs without scratch. 4 / 5 / 6 measured: profiles/r5_ab_notes.md)
-#endif
-#ifndef SMX_EDGE_ONEPASS
-#define SMX_EDGE_ONEPASS 1   // (0: the chunk-by-chunk form of rounds 5-6, kept for A/B -- profiles/r6_ab_notes.md section 11)
-#endif
-#if SMX_EDGE_ONEPASS
 // The edge work of ONE segment (k_reg_accumulate's step; also the tail of the fused pass B): n_act entries, the lane's
 // entry of the first chunk in ent_first, the entries of later chunks in later_entries[e] (global work list or LDS).
 //
@@ -2383,7 +2284,7 @@ __device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& e
       if (dsegk[k] != kInvalid) got[k] = atomicAdd(&fb.count[(size_t)dsegk[k] * kCountStride], cntk[k]);
     }
 #pragma unroll
-    for (int k = 0; k < kFarHash / kBlockAcc; ++k) keep_if<8>(got[k]);
+    for (int k = 0; k < kFarHash / kBlockAcc; ++k) keep(got[k]);
 #pragma unroll
     for (int k = 0; k < kFarHash / kBlockAcc; ++k) if (dsegk[k] != kInvalid) hcnt[k * kBlockAcc + tid] = got[k];
   }
@@ -2448,7 +2349,7 @@ __device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& e
               ++h;
             }
             if (pos < fb.cap)
-              out_store16<SMX_ST_FARBIN>(&fb.rec[(size_t)dseg * fb.cap + pos],
+              out_store16(&fb.rec[(size_t)dseg * fb.cap + pos],
                                          make_uint4((nb[q] % kSegB) | ((uint32_t)(neighbor_count - 1) << 10), (uint32_t)qx, (uint32_t)qy, (uint32_t)qz));
             else
               far_term_spill(grad_acc, fb, nb[q], qx, qy, qz, neighbor_count);
@@ -2464,7 +2365,7 @@ __device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& e
         }
       }
       // (second half of the slot's dense record; the first half -- the in-segment sums -- follows when the segment is through)
-      if (rec) out_store16<SMX_ST_REGREC>(&reg_rec[rec_own_offset + (size_t)(base + lrank[rel_own])], make_float4(rg.x, rg.y, rg.z, __int_as_float(own_count)));
+      if (rec) out_store16(&reg_rec[rec_own_offset + (size_t)(base + lrank[rel_own])], make_float4(rg.x, rg.y, rg.z, __int_as_float(own_count)));
     }
 #pragma unroll
     for (int k = 0; k + 1 < kCh; ++k) { entq[k] = entq[k + 1]; tq[k] = tq[k + 1]; }
@@ -2482,185 +2383,12 @@ __device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& e
     const uint32_t rank = lrank[rel];
     if (rank == 0xFFFFu) continue;
     const unsigned long long v0 = lacc[rel], v1 = lacc[kSegAcc + rel];
-    out_store16<SMX_ST_REGREC>(&reg_rec[(size_t)(base + rank)], v0, v1);
+    out_store16(&reg_rec[(size_t)(base + rank)], v0, v1);
   }
 }
-#else
-// The edge work of ONE segment (k_reg_accumulate's step; also the tail of the fused pass B): n_act entries, the lane's
-// entry of the first chunk in ent_first, the entries of later chunks in later_entries[e] (global work list or LDS).
-__device__ __forceinline__ void edge_segment(const Surfels& S, const EdgeArgs& ea, DevState* st, uint32_t base, uint32_t n_act,
-                                             uint32_t ent_first, const uint32_t* later_entries, const EdgeLds& lds, uint32_t tid) {
-  unsigned long long* const lacc = lds.lacc;
-  uint32_t* const hkey = lds.hkey; uint32_t* const hcnt = lds.hcnt;
-  uint16_t* const lrank = lds.lrank; uint32_t* const rec_wave = lds.rec_wave;
-  const float rf2 = ea.rf2, weight = ea.weight;
-  long long* const grad_acc = ea.grad_acc;
-  float4* const reg_rec = ea.reg_rec;
-  const size_t rec_own_offset = ea.rec_own_offset;
-  const FarBins& fb = ea.fb;
-#pragma unroll
-  for (int k = 0; k < kSegAcc * 2 / kBlockAcc; ++k) lacc[k * kBlockAcc + tid] = 0;
-#pragma unroll
-  for (int k = 0; k < kSegAcc / 2 / kBlockAcc; ++k) reinterpret_cast<uint32_t*>(lrank)[k * kBlockAcc + tid] = 0xFFFFFFFFu;
-  uint32_t rec_before = 0;   // recent entries in the chunks in front of this one
-  // A segment with more than 256 entries takes several chunks, one after the other (they share the LDS sums): the next
-  // chunk's entries are requested at the top of this one, and its slots' own records behind this chunk's first barrier,
-  // so that a chunk waits for its link records and its bin reservations only -- two dependent round trips instead of four
-  // (the dense segments, four chunks each, are what the launch lasts: 40 us alone without this, profiles/r5_ab_notes.md).
-  uint32_t ent = tid < n_act ? ent_first : kNoActEntry;
-  uint4 own_t = *reinterpret_cast<const uint4*>(S.group(kGroupT, base + (ent != kNoActEntry ? (ent & 1023u) : 0u)));
-  float4 own_s = *S.group(kGroupS, base + (ent != kNoActEntry ? (ent & 1023u) : 0u));
-  float4 own_n = *S.group(kGroupN, base + (ent != kNoActEntry ? (ent & 1023u) : 0u));
-#pragma unroll 1
-  for (uint32_t c0 = 0; c0 < n_act; c0 += kBlockAcc) {
-  const bool more = c0 + kBlockAcc < n_act;   // (uniform)
-  uint32_t ent_following = kNoActEntry;
-  if (more && c0 + kBlockAcc + tid < n_act) ent_following = later_entries[c0 + kBlockAcc + tid];
-  if (c0) __syncthreads();   // (the previous chunk's far stores have read the table)
-#pragma unroll
-  for (int k = 0; k < kFarHash / kBlockAcc; ++k) { hkey[k * kBlockAcc + tid] = kInvalid; hcnt[k * kBlockAcc + tid] = 0; }
-  const bool act = ent != kNoActEntry;
-  const uint32_t rel_own = act ? (ent & 1023u) : 0u;
-  const uint32_t mask = act ? ((ent >> 10) & 15u) : 0u;
-  const bool rec = act && ((ent >> 14) & 1u);
-  // A recent slot's results -- the in-segment sums and its own term -- go to two dense arrays at the slot's RANK among the
-  // segment's recent slots, which is its place in the recent list pass B wrote (both lists ascend by slot): the step
-  // kernel reads the records of a segment as coalesced runs.  (Two arrays of 16-byte records, not one of 32-byte records:
-  // the two halves are ready at different times, and a 16-byte store into a 32-byte record is a partial sector write --
-  // WRITE_SIZE booked 32 bytes for each, 30 MB a frame at C2 instead of 15, profiles/r40_WRITE_SIZE.md.)
-  const unsigned long long bal = __ballot(rec);
-  uint32_t rec_rank = rec_before + (uint32_t)__popcll(bal & ((1ull << (tid & 63u)) - 1ull));
-  if ((tid & 63u) == 0) rec_wave[tid >> 6] = (uint32_t)__popcll(bal);
-  // (the slot's own records: requested a chunk ahead; idle lanes hold the segment's first slot's)
-  const uint32_t i = base + rel_own;
-  __syncthreads();
-#pragma unroll
-  for (int wv = 0; wv < kBlockAcc / 64; ++wv) {
-    const uint32_t n = rec_wave[wv];
-    if ((uint32_t)wv < (tid >> 6)) rec_rank += n;
-    rec_before += n;
-  }
-  if (rec) lrank[rel_own] = (uint16_t)rec_rank;
-  const uint32_t nb[4] = {own_t.x, own_t.y, own_t.z, own_t.w};
-  // a recent slot needs every valid neighbour (its own step term, :2238-2256), any other slot only the neighbours inside
-  // the window (the terms it pushes): one 16-byte record per link, all requested before the first is used
-  uint32_t gmask = mask;
-  if (rec) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) if (nb[q] != kInvalid) gmask |= 1u << q;
-  }
-  float4 ts[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)   // the neighbour's smooth position; unused links read the slot's own record
-    ts[q] = *S.group(kGroupS, (gmask & (1u << q)) ? nb[q] : i);
-  // far terms wait in registers for their place in the destination's bin: (table entry | rank << 10, target, q22 x 3)
-  uint32_t far_where[4], far_target[4];
-  int far_q[4][3];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) far_where[q] = kInvalid;
-  if (act) {
-    const Vec3 sp = {own_s.x, own_s.y, own_s.z};
-    const Vec3 nrm = {own_n.x, own_n.y, own_n.z};
-    const float r2 = own_n.w;
-    const int neighbor_count = mask ? __popc(mask) : 1;
-    const float factor = 2 * weight / (float)neighbor_count;  // :2153
-    int own_count = 0;
-    Vec3 rg = {0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (!(gmask & (1u << q))) continue;
-      const Vec3 t = {ts[q].x - sp.x, ts[q].y - sp.y, ts[q].z - sp.z};
-      const float nd = nrm.x * t.x + nrm.y * t.y + nrm.z * t.z;
-      bool pruned = false;
-      if (mask & (1u << q)) {
-        const float f = factor * nd;
-        const Vec3 term = {f * nrm.x, f * nrm.y, f * nrm.z};   // (the weight term, :2182, travels as the sender's class)
-        // the fixed-point channel carries |component| < 16 m (q22_from_float clamps): a huge regularizer_weight or a
-        // corrupt position is reported instead of silently bending the gradient
-        if (!(fabsf(term.x) < 16.0f && fabsf(term.y) < 16.0f && fabsf(term.z) < 16.0f)) st->reg_saturated = 1u;
-        const int qx = q22_from_float(term.x), qy = q22_from_float(term.y), qz = q22_from_float(term.z);
-        const uint32_t rel = nb[q] - base;
-        if (rel < (uint32_t)kSegAcc) {
-          // component-major LDS layout: consecutive lanes (consecutive targets) hit consecutive banks
-          atomicAdd(&lacc[rel], pack_pair(qx, qy));
-          atomicAdd(&lacc[kSegAcc + rel], pack_pair(qz, 1 << (8 * (neighbor_count - 1))));
-        } else {
-          // find (or claim) the destination's entry in the LDS table, then draw a rank
-          const uint32_t dseg = nb[q] / kSegB;
-          uint32_t h = (dseg * 2654435761u) >> 16;
-          uint32_t where = kInvalid;
-          for (int probe = 0; probe < 16; ++probe) {
-            h &= fb.hash_mask;
-            const uint32_t seen = atomicCAS(&hkey[h], kInvalid, dseg);
-            if (seen == kInvalid || seen == dseg) { where = h | (atomicAdd(&hcnt[h], 1u) << 10); break; }
-            ++h;
-          }
-          if (where == kInvalid) {
-            far_term_spill(grad_acc, fb, nb[q], qx, qy, qz, neighbor_count);
-          } else {
-            far_where[q] = where; far_target[q] = nb[q] | ((uint32_t)(neighbor_count - 1) << 30);
-            far_q[q][0] = qx; far_q[q][1] = qy; far_q[q][2] = qz;
-          }
-        }
-        const float d2 = t.x * t.x + t.y * t.y + t.z * t.z;
-        if (d2 > rf2 * r2) { S.set_neighbor(i, q, kInvalid); pruned = true; }  // :2190-2192
-      }
-      // the slot's own regulariser term (RegularizeSurfelsCUDAKernel :2238-2256 sees the row after the pruning
-      // above): same neighbour positions, same n.t product, so it is formed here and k_reg_step gathers nothing
-      if (rec && !pruned) {
-        ++own_count;
-        rg.x = rg.x - nd * nrm.x; rg.y = rg.y - nd * nrm.y; rg.z = rg.z - nd * nrm.z;
-      }
-    }
-    // (second half of the slot's dense record; the first half -- the in-segment sums -- follows when the segment is through)
-    if (rec) out_store16<SMX_ST_REGREC>(&reg_rec[rec_own_offset + (size_t)(base + rec_rank)], make_float4(rg.x, rg.y, rg.z, __int_as_float(own_count)));
-  }
-  __syncthreads();
-  // one lane per destination reserves the workgroup's run in that bin; the table then holds the run's start
-#pragma unroll
-  for (int k = 0; k < kFarHash / kBlockAcc; ++k) {
-    const uint32_t e = k * kBlockAcc + tid;
-    const uint32_t dseg = hkey[e];
-    if (dseg != kInvalid) hcnt[e] = atomicAdd(&fb.count[(size_t)dseg * kCountStride], hcnt[e]);
-  }
-  // the next chunk's own records travel while the reservations return and the far records are stored
-  uint4 nxt_t = own_t; float4 nxt_s = own_s, nxt_n = own_n;
-  if (more) {
-    const uint32_t in = base + (ent_following != kNoActEntry ? (ent_following & 1023u) : 0u);
-    nxt_t = *reinterpret_cast<const uint4*>(S.group(kGroupT, in));
-    nxt_s = *S.group(kGroupS, in);
-    nxt_n = *S.group(kGroupN, in);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t where = far_where[q];
-    if (where == kInvalid) continue;
-    const uint32_t target = far_target[q] & 0x3FFFFFFFu, cls = far_target[q] >> 30;
-    const uint32_t pos = hcnt[where & 1023u] + (where >> 10);
-    if (pos < fb.cap)
-      out_store16<SMX_ST_FARBIN>(&fb.rec[(size_t)(target / kSegB) * fb.cap + pos],
-                                 make_uint4((target % kSegB) | (cls << 10), (uint32_t)far_q[q][0], (uint32_t)far_q[q][1], (uint32_t)far_q[q][2]));
-    else
-      far_term_spill(grad_acc, fb, target, far_q[q][0], far_q[q][1], far_q[q][2], (int)cls + 1);
-  }
-  ent = ent_following; own_t = nxt_t; own_s = nxt_s; own_n = nxt_n;
-  }   // chunks
-  // The in-segment sums of the recent slots: first half of their dense records, once every chunk's terms are in (the
-  // barriers above).  (Rounds 3-4 stored the sums of EVERY slot of the segment, zeros included -- 16 KB of full lines per
-  // workgroup, 39 MB a frame at C2, of which the step kernel read the recent slots' 7 MB: profiles/r31_WRITE_SIZE.md.)
-#pragma unroll
-  for (int k = 0; k < kSegAcc / kBlockAcc; ++k) {
-    const uint32_t rel = k * kBlockAcc + tid;
-    const uint32_t rank = lrank[rel];
-    if (rank == 0xFFFFu) continue;
-    const unsigned long long v0 = lacc[rel], v1 = lacc[kSegAcc + rel];
-    out_store16<SMX_ST_REGREC>(&reg_rec[(size_t)(base + rank)], v0, v1);
-  }
-}
-
-#endif   // SMX_EDGE_ONEPASS
-__global__ void __launch_bounds__(kBlockAcc, SMX_ACC_WGS_PER_CU)   // (second argument: wavefronts per SIMD = workgroups per CU here)
+// (256-lane workgroups, 26 KB of LDS each; <= 96 VGPRs without scratch.  4 / 5 / 6 measured: profiles/r5_ab_notes.md)
+constexpr int kAccWgsPerCu = 5;
+__global__ void __launch_bounds__(kBlockAcc, kAccWgsPerCu)   // (second argument: wavefronts per SIMD = workgroups per CU here)
 k_reg_accumulate(Surfels S, float rf2, float weight, long long* __restrict__ grad_acc,
                  float4* __restrict__ reg_rec, size_t rec_own_offset, FarBins fb,
                  const uint32_t* __restrict__ act_list, Chunks acc, DevState* st, unsigned long long* ts, unsigned long long* stamps,
@@ -2760,9 +2488,9 @@ k_reg_step(Surfels S, float weight, long long* __restrict__ grad_acc, const floa
       on[sub] = e < total;
       idx[sub] = on[sub] ? L.recent_list[seg_base + e] : seg_base;
     }
-    keep_if<32>(bin_state.x); keep_if<32>(bin_state.y);   // (the bin's state and the list entries: one round trip, not two)
+    keep(bin_state);   // (the bin's state and the list entries: one round trip, not two)
 #pragma unroll
-    for (int sub = 0; sub < kStepSub; ++sub) keep_if<32>(idx[sub]);
+    for (int sub = 0; sub < kStepSub; ++sub) keep(idx[sub]);
     float4 rp[kStepSub], rs[kStepSub], rn[kStepSub], rgr[kStepSub];
     ulonglong2 rl[kStepSub];
 #pragma unroll
@@ -2852,7 +2580,7 @@ k_reg_step(Surfels S, float weight, long long* __restrict__ grad_acc, const floa
       // (ONE 16-byte store, the unused fourth word included: three scalar stores leave four bytes of every record clean, so
       // no 64-byte sector of the S array is ever fully dirty and every write-back is a partial one -- sparse stores retire
       // at 21 G/s = 0.7 TB/s on this chip against 5 TB/s for full sectors, profiles/r17_counter_calibration.md)
-      out_store16<SMX_ST_STEP>(S.group(kGroupS, i), make_float4(sp.x - step * grad.x, sp.y - step * grad.y, sp.z - step * grad.z, rs[sub].w));
+      out_store16(S.group(kGroupS, i), make_float4(sp.x - step * grad.x, sp.y - step * grad.y, sp.z - step * grad.z, rs[sub].w));
     }
   }
   ts_end(ts, kTsRegEnd, blockIdx.x, min(gridDim.x, n_steps));   // (the workgroups that walked the last steps of the first round)
@@ -2981,7 +2709,7 @@ struct SlotTimer {
   SlotTimer(smx_recon r_, hipStream_t st_, int slot_, bool launch_carries = false) : r(r_), st(st_), slot(slot_) {
     kev = (r->timing_enabled & 2) != 0;
     prof = (r->prof_slot == slot) && r->prof_ev && r->prof_n < r->prof_cap;
-    by_launch = prof && launch_carries && SMX_EXT_STOP_EVENTS != 0;
+    by_launch = prof && launch_carries;
     if (kev) (void)hipEventRecord(r->kev[2 * slot], st);
     if (prof && !by_launch) (void)hipEventRecord(r->prof_ev[2 * r->prof_n], st);
   }
@@ -3022,7 +2750,7 @@ int enqueue_regularize(smx_recon r, hipStream_t st, uint32_t frame, float rf, fl
     const bool fused = !copy_only && r->fuse_edges != 0;
     // (fused: the heavy segments carry their edge work, the longest chains of the launch -- they go FIRST, the thousands of
     // workgroups that only stream or skip fill in behind them; not fused: last, see segment_of_block)
-    const uint32_t dir = fused && SMX_FUSED_HEAVY_FIRST ? (r->L.descending ? 0u : 1u) : r->L.descending;
+    const uint32_t dir = fused ? (r->L.descending ? 0u : 1u) : r->L.descending;
 #define SMX_LAUNCH_PASS_B(D, A, F) hipExtLaunchKernelGGL((k_neighbor_scan<D, A, F>), g, bB, lds_b, st, t.start(), t.stop(), 0, r->S, stats, use_hot, r->L, r->st, ts_first, ea, dir)
     if (copy_only) { if (detach) SMX_LAUNCH_PASS_B(true, false, false); else SMX_LAUNCH_PASS_B(false, false, false); }
     else if (fused) { if (detach) SMX_LAUNCH_PASS_B(true, true, true); else SMX_LAUNCH_PASS_B(false, true, true); }
@@ -3191,12 +2919,13 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(r->mem.alloc(&r->L.seg_targets, (size_t)r->nsegB * kBlockB, true));   // (written by the unfiltered passes of the hold-off calls before anyone reads it)
   r->L.epoch = 128;   // (far from the zeros)
   r->hot_filter_enabled = 1;
-  r->fuse_edges = SMX_FUSE_EDGES;
+  r->fuse_edges = kFuseEdgesDefault;
   r->hot_holdoff = 3;
   SMX_TRY(r->mem.alloc(&r->merge_flag, r->S.pitch, true));
   SMX_TRY(r->mem.alloc(&r->gate_count, 32, true));   // (a line of its own)
   r->gate_expected = 0;
-  r->handover_mode = SMX_HANDOVER_FLAGS;
+  constexpr int kHandoverModeDefault = 1;   // (smx_recon_set_handover_mode: the device word instead of an event)
+  r->handover_mode = kHandoverModeDefault;
   {
     // (a rocprofv3 that collects hardware counters serialises the dispatches of all queues: see k_front_gate)
     const char* cc = getenv("ROCPROF_COUNTER_COLLECTION");
@@ -3250,7 +2979,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
     // the regulariser is on the frame-to-frame critical path, the work it overlaps with is not
     int lo = 0, hi = 0;
     SMX_TRY(hip_rc(hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange"));
-    SMX_TRY(hip_rc(hipStreamCreateWithPriority(&r->reg_stream, hipStreamNonBlocking, SMX_REG_PRIORITY_HIGH ? hi : 0), "hipStreamCreateWithPriority"));
+    SMX_TRY(hip_rc(hipStreamCreateWithPriority(&r->reg_stream, hipStreamNonBlocking, hi), "hipStreamCreateWithPriority"));
   }
   // (device-scope release: these events order GPU streams, the host never reads data behind them)
   const unsigned evf = hipEventDisableTiming | hipEventReleaseToDevice;
@@ -3269,8 +2998,10 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   r->grid_surfels = cus * 8;  // 8 x 256-thread workgroups per CU: full occupancy, >> 256 workgroups
   r->cu_count = cus;
-  r->grid_acc = cus * SMX_ACC_WGS_PER_CU;
-  r->grid_list = r->grid_list_full = cus * SMX_LIST_WGS_PER_CU;  // (a walk step per listed chunk; workgroups without a step only cost)
+  r->grid_acc = cus * kAccWgsPerCu;
+  // (8 .. 32 measured: profiles/r17_ab_notes.md r26; the chunk lists hold ~3 000 steps at C2, ~10 000 at C3)
+  constexpr int kListWgsPerCu = 12;
+  r->grid_list = r->grid_list_full = cus * kListWgsPerCu;  // (a walk step per listed chunk; workgroups without a step only cost)
   r->stats_enabled = 1;
   *out = r;
   return SMX_OK;
@@ -3385,7 +3116,7 @@ int smx_recon_set_scan_mode(smx_recon r, int32_t mode) {
   r->no_lds_tables = (mode >> 4) & 1;                     // pass A reserves bin space per pair (the path of a pair that finds no entry in the workgroup's table)
   r->fb.cap = ((mode >> 5) & 1) ? 4u : kFarBinCap;        // 4 records per far-term bin: most far terms spill to grad_acc
   r->fb.hash_mask = ((mode >> 6) & 1) ? 1u : (uint32_t)kFarHash - 1u;   // 2 destinations per sender workgroup: the rest spills
-  r->fuse_edges = ((mode >> 9) & 1) ? 1 : SMX_FUSE_EDGES;   // one launch: the segment's workgroup of pass B does the segment's edge work itself
+  r->fuse_edges = ((mode >> 9) & 1) ? 1 : kFuseEdgesDefault;   // one launch: the segment's workgroup of pass B does the segment's edge work itself
   r->blend_other_tile = (mode >> 7) & 1;                  // the blend's other tile size (40 x 40 where it would take 32 x 32 and vice versa)
   return SMX_OK;
 }
@@ -3484,12 +3215,11 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
   r->sc_cur ^= 1;
   r->L.vis_chunks.count = r->vis_count_set[r->sc_cur];
   r->tb.ovf_count = r->ovf_count_set[r->sc_cur];
-#if SMX_READY_WAIT_EARLY == 2
   // (the wait for the input images at the very front of the call -- in a running pipeline they were ready long ago --
   // so that ONE barrier packet stands between the previous call's update + create and this call's pass A: 12.5 -> 8 us
-  // from update's end to pass A's begin)
+  // from update's end to pass A's begin.  Measured against a wait between pass A and the tile kernel, where the images are
+  // first read, and one next to the wait for the previous map (+0.5 %); here +0.9 % on top: profiles/r5_ab_notes.md)
   if (hook_ready) SMX_HIP(hipStreamWaitEvent(sF, hook_ready, 0));
-#endif
   { // the cull step: needs the pose and what the previous pass A left, nothing the previous call's second half writes --
     // so it goes in FRONT of this stream's wait for that half wherever the wait could be deferred (below)
     SlotTimer t(r, sF, kSlotCull);
@@ -3497,22 +3227,15 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
     r->sw_dirty = true;
     hipLaunchKernelGGL(k_cull_segments, dim3((unsigned)div_up(r->nseg, kBlock)), b, 0, sF, c, r->L, r->sw, r->st, (uint32_t)r->nseg, (uint32_t)P, r->ts_seq); }
   if (r->pending_mark) { SMX_HIP(hipStreamWaitEvent(sF, r->pending_mark, 0)); r->pending_mark = nullptr; }
-#if SMX_READY_WAIT_EARLY == 1
-  // (the wait for the input images next to the wait for the map: pass A and the tile kernel then follow each other without
-  // a barrier packet between them -- 38 -> 31 us from pass A's first workgroup to the tile kernel's at C2)
-  if (hook_ready) SMX_HIP(hipStreamWaitEvent(sF, hook_ready, 0));
-#endif
   if (r->stats_enabled) hipLaunchKernelGGL(k_reset_frame_stats, dim3(1), dim3(1), 0, sF, r->st, 0);
   { SlotTimer t(r, sF, kSlotScanVisible, true);
     const bool lds_tables = !r->no_lds_tables;
-    // chip-sized grid: as many workgroups as the chip holds at once (8 per CU) walk the survivor list
-    const dim3 ga((unsigned)(r->cu_count * SMX_PASS_A_WGS_PER_CU));
+    // chip-sized grid: as many workgroups as the chip holds at once walk the survivor list
+    constexpr int kPassAWgsPerCu = 8;   // (4 / 6 measured against 8: profiles/r17_ab_notes.md r24)
+    const dim3 ga((unsigned)(r->cu_count * kPassAWgsPerCu));
     hipExtLaunchKernelGGL(k_scan_visible, ga, b, 0, sF, t.start(), t.stop(), 0, r->S, c, r->L, r->tb, r->sw, flags_prev, r->st, lds_tables ? 1 : 0);
     r->table_valid = true; r->table_frame = frame_index; r->table_window = c.reg_window; }
   // (smx_recon_integrate_inputs_ready) from here on the input images are read
-#if !SMX_READY_WAIT_EARLY
-  if (hook_ready) SMX_HIP(hipStreamWaitEvent(sF, hook_ready, 0));
-#endif
   // (the tile kernel also leaves the direction for later launches' segment_of_block in host memory, see there)
   { SlotTimer t(r, sF, kSlotAssocTiles, true);
     hipExtLaunchKernelGGL(k_assoc_tiles, dim3(r->tb.n_tiles), dim3(kTilePx), 0, sF, t.start(), t.stop(), 0, r->S, c, r->sc, in.depth, in.normals, r->tb,
@@ -3550,7 +3273,7 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
     // blend used to push the hand-over onto an event record of its own behind the launch, and the profiled frame loop ran a
     // tenth slower than the one it was meant to describe: the "slow mode" of rounds 5 - 6 was bench.py profiling this kernel,
     // profiles/r6_ab_notes.md section 14.)
-    front_by_launch = !front_by_gate && SMX_EXT_STOP_EVENTS && pipelined && !split && !tm && !(r->timing_enabled & 2) && r->prof_slot != kSlotBlend;
+    front_by_launch = !front_by_gate && pipelined && !split && !tm && !(r->timing_enabled & 2) && r->prof_slot != kSlotBlend;
     uint32_t* const gate = front_by_gate ? r->gate_count : nullptr;
     if (front_by_gate) r->gate_expected += n_blend;
     const hipEvent_t start = front_by_gate ? t.start() : nullptr;
@@ -3624,7 +3347,7 @@ int smx_recon_integrate(smx_recon r, smx_stream s, uint32_t frame_index, float d
     const size_t lds = (size_t)r->n_scan_blocks * sizeof(uint32_t);
     // (the "map complete / inputs consumed" mark below as this launch's own completion event: no packet of its own between
     // this kernel and pass B on the internal stream)
-    mark_by_launch = SMX_EXT_STOP_EVENTS && !tm && !(r->timing_enabled & 2) && (pipelined || hook_consumed) && r->prof_slot != kSlotUpdateNeighbors;
+    mark_by_launch = !tm && !(r->timing_enabled & 2) && (pipelined || hook_consumed) && r->prof_slot != kSlotUpdateNeighbors;
     const hipEvent_t stop = mark_by_launch ? (hook_consumed ? hook_consumed : r->ev_upd) : nullptr;
     if (r->scan_mode) hipExtLaunchKernelGGL((k_update_and_create<false>), guc, b, (uint32_t)lds, sI, nullptr, stop, 0, r->S, c, r->sc, in, r->L, ca, ncb, r->st);
     else hipExtLaunchKernelGGL((k_update_and_create<true>), guc, b, (uint32_t)lds, sI, nullptr, stop, 0, r->S, c, r->sc, in, r->L, ca, ncb, r->st); }
@@ -3689,7 +3412,7 @@ int smx_recon_set_internal_cu_mask(smx_recon r, const uint32_t* mask_words, uint
   } else {
     int lo = 0, hi = 0;
     SMX_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    SMX_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, SMX_REG_PRIORITY_HIGH ? hi : 0));
+    SMX_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, hi));
   }
   (void)hipStreamDestroy(r->reg_stream);
   r->reg_stream = s;

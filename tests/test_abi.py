@@ -30,7 +30,7 @@ def test_header_symbols_are_exported():
 
 
 def test_source_list_matches_csrc():
-    """build.SOURCES is the one list of translation units (the variant scripts under tools/ read it too): every
+    """build.SOURCES is the one list of translation units (tools/build_variant.sh reads it too): every
     source file in csrc/ is in it and the other way round."""
     from surfelmeshing_amd import build
     on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp")))

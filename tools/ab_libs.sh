@@ -1,6 +1,6 @@
 #!/bin/bash
-# Same-box comparison of several builds: bash tools/ab_libs.sh <tag> <reps> name1 name2 ...   (build/ab/libsmx_<name>.so;
-# the name NEW = the in-tree library).  Prints frames/s and the kernels' stand-alone times of the untimed calibration pass.
+# Same-box comparison of several builds: bash tools/ab_libs.sh <tag> <reps> name1 name2 ...   (build/ab/libsmx_<name>.so,
+# built by tools/build_variant.sh; the name NEW = the in-tree library).  Prints frames/s and the kernels' stand-alone times of the untimed calibration pass.
 TAG=$1; REPS=$2; shift; shift
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 for rep in $(seq $REPS); do
