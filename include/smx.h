@@ -701,6 +701,70 @@ typedef struct {
 int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
                                      int32_t* count);
 
+/* ---- camera tracking with colour: point-to-plane ICP + a photometric term (not in the reference) ----
+ * Everything of smx_recon_track stays -- the render at the prediction, the sampling, the association, the two geometric
+ * gates, r, J, the status rules and their order, the LDL^T solve, the left twist, levels and convergence -- and a one-plane
+ * view that smx_recon_track reports as DEGENERATE is held in place by the map's colour (row 24) and the frame's colour
+ * image (uchar3, the object's size: the image smx_recon_integrate takes).  Additions:
+ * Model photometric image.  The same render also resolves colour with color_flags = 0 (uchar4, bit for bit what
+ * smx_recon_render gives); from it and the model depth D one kernel writes a dense float4 P[H][W] = (L, gx, gy, valid):
+ *   L  = ((0.299f r + 0.587f g) + 0.114f b) (1.0f / 255.0f)       (float, left to right; 0 at an empty pixel)
+ *   gx = 0.5f (L(x+1, y) - L(x-1, y)),  gy = 0.5f (L(x, y+1) - L(x, y-1))
+ *   valid = 1 iff 1 <= x <= W-2 and 1 <= y <= H-2, D > 0 at the pixel and at its four neighbours, and for each neighbour
+ *           |D(nb) - D(x, y)| <= gradient_max_relative_depth_step D(x, y); otherwise gx = gy = valid = 0.
+ * Frame intensity I_f(x, y): the same formula on the frame's colour at the sampled pixel.
+ * Photometric term of a sampled frame pixel that has depth, is associated with model pixel (u, w) and passes the distance
+ * gate (the normal gate does not apply): uc = fx p.x / p.z + cx, wc = fy p.y / p.z + cy (the values whose floors are u, w),
+ *   Lm = (L + gx (uc - (u + 1/2))) + gy (wc - (w + 1/2)),  e = Lm - I_f;
+ * the pixel is a photometric inlier iff valid, gx^2 + gy^2 >= min_gradient^2 and |e| <= max_intensity_difference.  Then
+ *   a = ((gx fx) / p.z, (gy fy) / p.z, -(((gx fx) p.x + (gy fy) p.y) / (p.z p.z))),  J_I = (p x a, a)   (rotation first),
+ * and with K = photometric_weight J_I and s = photometric_weight e (each one float product) the pixel adds K_a K_b to
+ * JtJ, K_a s to Jtr and e^2 to a sum of its own.  Per-pixel terms are float, the sums double in the same fixed order.
+ * Sums: SMX_TRACK_RGBD_SUMS = 33; [0..30] as SMX_TRACK_SUMS with JtJ and Jtr now the combined ones ([27..30] keep their
+ * geometric meanings), [31] sum e^2, [32] photometric inliers.  Status: the rules and their order are unchanged;
+ * min_inliers and min_inlier_fraction judge the GEOMETRIC inliers, the pivot test runs on the combined matrix, the
+ * finiteness test covers all 33 sums.  (A frame colour alone could track -- no geometric inliers -- is TOO_FEW_INLIERS.)
+ * photometric_weight == 0: neither the colour resolve nor the prepare kernel is launched, no photometric term is added
+ * ([31] = [32] = 0) and the pose, status, counts, information matrix and sums [0..30] of every iteration are bit-identical
+ * to smx_recon_track with the embedded smx_track_params; model_photo_out is then left untouched.
+ * Launches: those of smx_recon_track + 1.  Ordering, stream semantics, "changes no map state" and the argument errors are
+ * those of smx_recon_track; in addition SMX_ERR_INVALID_ARGUMENT (nothing launched) for a colour image of the wrong size
+ * or element size (as far as a descriptor shows the latter: a pitch below 3 x width), a negative or non-finite weight, a non-positive max_intensity_difference or depth step, a negative
+ * min_gradient.  model_photo_out (may be NULL; float4, the object's size) receives P. */
+typedef struct {                 /* smx_track_rgbd_params_default() fills the defaults */
+  smx_track_params icp;
+  float photometric_weight;                 /* metres per unit intensity (0..1 scale); >= 0; default 0.1 */
+  float max_intensity_difference;           /* > 0; default 0.2 */
+  float min_gradient;                       /* >= 0, intensity per pixel; default 0.02 */
+  float gradient_max_relative_depth_step;   /* > 0; default 0.02 */
+} smx_track_rgbd_params;
+typedef struct {
+  smx_track_result icp;                     /* inliers, rms_residual: the geometric ones; information: the combined JtJ */
+  uint32_t photometric_inliers;             /* of the last iteration run */
+  float rms_intensity_residual;             /* intensity units (0..1 scale), last iteration */
+} smx_track_rgbd_result;
+#define SMX_TRACK_RGBD_SUMS 33
+typedef struct {
+  int32_t level, stride, status, reserved;
+  double sums[SMX_TRACK_RGBD_SUMS];
+  double x[6];
+} smx_track_rgbd_iteration;
+/* Defaults: smx_track_params_default() for icp; weight 0.1 (0.02 of intensity noise then weighs like 2 mm of depth
+ * noise); max_intensity_difference 0.2; min_gradient 0.02 (+-2 grey levels of noise give central differences of at most
+ * 2/255 per axis, a magnitude <= 0.011: below the gate); gradient_max_relative_depth_step 0.02. */
+int smx_track_rgbd_params_default(smx_track_rgbd_params* out);
+int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling,
+                         const smx_buffer_desc* depth /*u16*/, const smx_buffer_desc* normals /*float2*/,
+                         const smx_buffer_desc* color /*uchar3*/, const float global_T_pred[12],
+                         const smx_track_rgbd_params* params, smx_track_rgbd_result* result, int32_t result_on_device,
+                         const smx_buffer_desc* model_depth_out /*float, may be NULL*/,
+                         const smx_buffer_desc* model_normal_out /*float4, may be NULL*/,
+                         const smx_buffer_desc* model_photo_out /*float4 P, may be NULL*/);
+/* As smx_recon_debug_track_iterations, for the last smx_recon_track_rgbd call (*count = 0 if the last tracking call was
+ * smx_recon_track). */
+int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
+                                          int32_t* count);
+
 /* ---- candidate lists for the mesher, straight from the device-resident map ----
  * Replaces, for the surfels of one batch (e.g. one changed-surfel delta), the per-surfel octree query at the top of
  * SurfelMeshing::TriangulateSurfel (APP/surfel_meshing.cc:417-425) with the widest radius that function can ask for,

@@ -636,6 +636,18 @@ class CUDASurfelReconstruction {
                                    &params, result, 0, model_depth ? model_depth->ToCUDA().desc() : nullptr,
                                    model_normal ? model_normal->ToCUDA().desc() : nullptr));
   }
+  // Track with a photometric term on top (smx_recon_track_rgbd): `color` is the frame's colour image as Integrate takes it;
+  // model_photo receives P = (L, gx, gy, valid).  Synchronous, like Track; result->icp.status decides as there.
+  void TrackRGBD(cudaStream_t stream, float depth_scaling, const CUDABuffer<u16>& depth, const CUDABuffer<float2_>& normals,
+                 const CUDABuffer<Vec3u8>& color, const float* pred, const smx_track_rgbd_params& params,
+                 smx_track_rgbd_result* result, CUDABuffer<float>* model_depth = nullptr,
+                 CUDABuffer<RenderNormal>* model_normal = nullptr, CUDABuffer<RenderNormal>* model_photo = nullptr) {
+    SMX_SHIM_CHECK(smx_recon_track_rgbd(handle_, stream, depth_scaling, depth.ToCUDA().desc(), normals.ToCUDA().desc(),
+                                        color.ToCUDA().desc(), pred, &params, result, 0,
+                                        model_depth ? model_depth->ToCUDA().desc() : nullptr,
+                                        model_normal ? model_normal->ToCUDA().desc() : nullptr,
+                                        model_photo ? model_photo->ToCUDA().desc() : nullptr));
+  }
   void ExportVertices(cudaStream_t stream, CUDABuffer<float>* position_buffer, CUDABuffer<u8>* color_buffer) {
     SMX_SHIM_CHECK(smx_recon_export_vertices(handle_, stream, position_buffer->ToCUDA().desc(), color_buffer->ToCUDA().desc()));
   }

@@ -105,6 +105,39 @@ class TrackIteration(C.Structure):
                 ("sums", C.c_double * TRACK_SUMS), ("x", C.c_double * 6)]
 
 
+class TrackRGBDParams(C.Structure):
+    """smx_track_rgbd_params: smx_track_params plus the weight and the gates of the photometric term."""
+    _fields_ = [("icp", TrackParams), ("photometric_weight", C.c_float), ("max_intensity_difference", C.c_float),
+                ("min_gradient", C.c_float), ("gradient_max_relative_depth_step", C.c_float)]
+
+    @classmethod
+    def defaults(cls, levels=None, **kw):
+        """smx_track_rgbd_params_default(), then `levels` and any field by name -- the photometric ones, or one of the
+        embedded smx_track_params."""
+        p = cls()
+        check(load().smx_track_rgbd_params_default(C.byref(p)))
+        own = [f for f, _ in cls._fields_ if f != "icp"]
+        p.icp = TrackParams.defaults(levels, **{k: v for k, v in kw.items() if k not in own})
+        for k, v in kw.items():
+            if k in own:
+                setattr(p, k, v)
+        return p
+
+
+class TrackRGBDResult(C.Structure):
+    """smx_track_rgbd_result"""
+    _fields_ = [("icp", TrackResult), ("photometric_inliers", C.c_uint32), ("rms_intensity_residual", C.c_float)]
+
+
+TRACK_RGBD_SUMS = 33   # SMX_TRACK_RGBD_SUMS
+
+
+class TrackRGBDIteration(C.Structure):
+    """smx_track_rgbd_iteration"""
+    _fields_ = [("level", C.c_int32), ("stride", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+                ("sums", C.c_double * TRACK_RGBD_SUMS), ("x", C.c_double * 6)]
+
+
 class MeshParams(C.Structure):
     """smx_mesh_params: thresholds of smx_recon_triangulate (names as in the reference's main.cc)."""
     _fields_ = [("max_angle_between_normals_deg", C.c_float), ("min_triangle_angle_deg", C.c_float),
@@ -183,7 +216,7 @@ EXPORTS = [
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",
-    "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_track_params_default", "smx_recon_track", "smx_recon_debug_track_iterations", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
+    "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_track_params_default", "smx_recon_track", "smx_recon_debug_track_iterations", "smx_track_rgbd_params_default", "smx_recon_track_rgbd", "smx_recon_debug_track_rgbd_iterations", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
     "smx_recon_set_scan_mode", "smx_recon_debug_set_skip", "smx_recon_set_overlap", "smx_recon_integrate_hooks", "smx_recon_integrate_inputs_ready",
     "smx_nn_create", "smx_nn_destroy", "smx_nn_build", "smx_nn_query_batch", "smx_nn_query_self", "smx_nn_set_query_mode", "smx_nn_set_stats_enabled", "smx_nn_get_stats",
     "smx_synth_render_room",

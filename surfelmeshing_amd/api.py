@@ -23,7 +23,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
-                   MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult)
+                   MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
+                   TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
@@ -56,6 +57,21 @@ class TrackOutcome:
     def __repr__(self):
         return "TrackOutcome(%s, %d iterations, %d / %d inliers, rms %.4g m)" % (
             self.status_name, self.iterations_run, self.inliers, self.pixels_with_depth, self.rms_residual)
+
+
+class TrackRGBDOutcome(TrackOutcome):
+    """What CUDASurfelReconstruction.TrackRGBD returns: a TrackOutcome (inliers and rms_residual are the geometric ones,
+    information the combined JtJ) plus photometric_inliers and rms_intensity_residual (0..1 intensity scale)."""
+
+    def __init__(self, res):
+        TrackOutcome.__init__(self, res.icp)
+        self.photometric_inliers = int(res.photometric_inliers)
+        self.rms_intensity_residual = float(res.rms_intensity_residual)
+
+    def __repr__(self):
+        return "TrackRGBDOutcome(%s, %d iterations, %d / %d inliers, rms %.4g m; %d photometric, rms %.4g)" % (
+            self.status_name, self.iterations_run, self.inliers, self.pixels_with_depth, self.rms_residual,
+            self.photometric_inliers, self.rms_intensity_residual)
 
 
 def vis_flags(visualize_last_update_timestamp=False, visualize_creation_timestamp=False, visualize_radii=False,
@@ -749,6 +765,44 @@ class CUDASurfelReconstruction:
         recs = (TrackIteration * 96)()
         n = C.c_int32(0)
         _lib.check(_lib.load().smx_recon_debug_track_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
+        return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
+                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
+
+    def TrackRGBD(self, stream, depth_scaling, depth_buffer, normals_buffer, color_buffer, global_T_pred, params=None,
+                  model_depth=None, model_normal=None, model_photo=None):
+        """Track with a photometric term (smx_recon_track_rgbd): color_buffer is the frame's uchar3 colour image as
+        Integrate takes it, params a TrackRGBDParams (TrackRGBDParams.defaults()), model_photo (float4 CUDABuffer,
+        optional) receives P = (L, gx, gy, valid).  Synchronous; returns a TrackRGBDOutcome.  Changes no map state."""
+        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
+        p = params if params is not None else TrackRGBDParams.defaults()
+        res = TrackRGBDResult()
+        _lib.check(_lib.load().smx_recon_track_rgbd(
+            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer), _d(color_buffer),
+            T.ctypes.data_as(C.c_void_p), C.byref(p), C.byref(res), C.c_int32(0),
+            _d(model_depth) if model_depth is not None else None,
+            _d(model_normal) if model_normal is not None else None,
+            _d(model_photo) if model_photo is not None else None))
+        return TrackRGBDOutcome(res)
+
+    def TrackRGBDAsync(self, stream, depth_scaling, depth_buffer, normals_buffer, color_buffer, global_T_pred, params,
+                       result_buffer, model_depth=None, model_normal=None, model_photo=None):
+        """The same call with the smx_track_rgbd_result left in device memory (result_buffer: a CUDABuffer of at least
+        ctypes.sizeof(TrackRGBDResult) bytes in one row, or a device pointer): nothing waits for the host."""
+        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
+        ptr = result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer)
+        _lib.check(_lib.load().smx_recon_track_rgbd(
+            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer), _d(color_buffer),
+            T.ctypes.data_as(C.c_void_p), C.byref(params), C.c_void_p(ptr), C.c_int32(1),
+            _d(model_depth) if model_depth is not None else None,
+            _d(model_normal) if model_normal is not None else None,
+            _d(model_photo) if model_photo is not None else None))
+
+    def debug_track_rgbd_iterations(self, stream=None):
+        """One dict per iteration of the last TrackRGBD call (smx_recon_debug_track_rgbd_iterations): as
+        debug_track_iterations with 33 sums ([31] sum e^2, [32] photometric inliers)."""
+        recs = (TrackRGBDIteration * 96)()
+        n = C.c_int32(0)
+        _lib.check(_lib.load().smx_recon_debug_track_rgbd_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
         return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
                  "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
 

@@ -592,10 +592,12 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   return SMX_OK;
 }
 
-int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
-                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
-                    const smx_buffer_desc* model_normal_out) {
+// smx_recon_track (q == nullptr: result is an smx_track_result) and smx_recon_track_rgbd (result an smx_track_rgbd_result).
+static int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                      const smx_buffer_desc* normals, const smx_buffer_desc* color, const float global_T_pred[12],
+                      const smx_track_params* params, const smx_track_rgbd_params* q, void* result, int32_t result_on_device,
+                      const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
+                      const smx_buffer_desc* model_photo_out) {
   SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
                 result != nullptr);
   const smx_track_params& p = *params;
@@ -623,6 +625,17 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
   SMX_CHECK_ARG(std::isfinite(p.near_z) && p.near_z > 0 && p.far_z > p.near_z);
   SMX_CHECK_ARG(std::isfinite(p.disc_radius_factor) && p.disc_radius_factor > 0);
   SMX_CHECK_ARG(p.max_splat_extent_in_pixels > 0 && p.max_splat_extent_in_pixels <= 1024);
+  if (q) {
+    // (3-byte elements: any pitch that holds a row, as smx_recon_integrate takes the image)
+    SMX_CHECK_ARG(color != nullptr && color->address && color->width == r->W && color->height == r->H &&
+                  color->pitch >= (size_t)r->W * 3);
+    SMX_CHECK_ARG(!model_photo_out || img_ok(model_photo_out, 16));
+    SMX_CHECK_ARG(std::isfinite(q->photometric_weight) && q->photometric_weight >= 0);
+    SMX_CHECK_ARG(std::isfinite(q->max_intensity_difference) && q->max_intensity_difference > 0);
+    SMX_CHECK_ARG(std::isfinite(q->min_gradient) && q->min_gradient >= 0);
+    SMX_CHECK_ARG(std::isfinite(q->gradient_max_relative_depth_step) && q->gradient_max_relative_depth_step > 0);
+  }
+  const bool photo = q && q->photometric_weight != 0.0f;
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
   const size_t px = (size_t)r->W * r->H;
@@ -635,6 +648,15 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
     r->trk_depth = std::move(depth_img); r->trk_normal = std::move(normal_img);
     r->trk_slabs = std::move(slabs); r->trk_state = std::move(state);
   }
+  if (q && !r->trk_rgbd_state.get()) {   // (likewise)
+    DevBuf<uint32_t> color_img; DevBuf<float4> photo_img; DevBuf<double> slabs; DevBuf<TrackRgbdDev> state;
+    SMX_CALL(color_img.alloc(px, false));
+    SMX_CALL(photo_img.alloc(px, false));
+    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackRgbdSlabStride, false));
+    SMX_CALL(state.alloc(1, false));
+    r->trk_color = std::move(color_img); r->trk_photo = std::move(photo_img);
+    r->trk_rgbd_slabs = std::move(slabs); r->trk_rgbd_state = std::move(state);
+  }
   if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
   // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
   smx_render_params rp;
@@ -644,10 +666,11 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
   rp.near_z = p.near_z; rp.far_z = p.far_z; rp.splat_mode = SMX_SPLAT_DISC;
   rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
   rp.surfel_integration_active_window_size = 2147483647;
-  smx_buffer_desc dd, nd;
+  smx_buffer_desc dd, nd, cd;
   dd.address = r->trk_depth.get(); dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
   nd.address = r->trk_normal.get(); nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
-  SMX_CALL(smx_recon_render(r, s, &rp, &dd, nullptr, &nd, nullptr));
+  cd.address = r->trk_color.get(); cd.height = r->H; cd.width = r->W; cd.pitch = (size_t)r->W * sizeof(uint32_t);
+  SMX_CALL(smx_recon_render(r, s, &rp, &dd, nullptr, &nd, photo ? &cd : nullptr));   // (color_flags 0: the colour row)
   if (model_depth_out)
     SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
                              hipMemcpyDeviceToDevice, st));
@@ -656,14 +679,69 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
                              hipMemcpyDeviceToDevice, st));
   TrackBuffers tb;
   tb.model_depth = r->trk_depth.get(); tb.model_normal = r->trk_normal.get(); tb.slabs = r->trk_slabs.get(); tb.state = r->trk_state.get();
-  SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
-                         result_on_device ? result : nullptr));
+  if (!q) {
+    SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
+                           result_on_device ? (smx_track_result*)result : nullptr));
+  } else {
+    TrackRgbdBuffers rb;
+    rb.icp = tb; rb.model_color = r->trk_color.get(); rb.model_photo = r->trk_photo.get();
+    rb.slabs = r->trk_rgbd_slabs.get(); rb.state = r->trk_rgbd_state.get();
+    SMX_CALL(track_rgbd_enqueue(st, rb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, color,
+                                global_T_pred, *q, result_on_device ? (smx_track_rgbd_result*)result : nullptr));
+    if (photo && model_photo_out) {
+      const size_t row = (size_t)r->W * sizeof(float4);
+      SMX_HIP(hipMemcpy2DAsync(model_photo_out->address, model_photo_out->pitch, r->trk_photo.get(), row, row, (size_t)r->H,
+                               hipMemcpyDeviceToDevice, st));
+    }
+  }
   SMX_HIP(hipEventRecord(r->ev_track, st));
   r->track_busy = true;
+  r->track_last_rgbd = q != nullptr;
   if (!result_on_device) {
-    SMX_HIP(hipMemcpyAsync(result, &r->trk_state.get()->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
+    if (q) SMX_HIP(hipMemcpyAsync(result, &r->trk_rgbd_state.get()->result, sizeof(smx_track_rgbd_result), hipMemcpyDeviceToHost, st));
+    else SMX_HIP(hipMemcpyAsync(result, &r->trk_state.get()->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
+  return SMX_OK;
+}
+
+int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
+                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
+                    const smx_buffer_desc* model_normal_out) {
+  return track_call(r, s, depth_scaling, depth, normals, nullptr, global_T_pred, params, nullptr, result, result_on_device,
+                    model_depth_out, model_normal_out, nullptr);
+}
+
+int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                         const smx_buffer_desc* normals, const smx_buffer_desc* color, const float global_T_pred[12],
+                         const smx_track_rgbd_params* params, smx_track_rgbd_result* result, int32_t result_on_device,
+                         const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
+                         const smx_buffer_desc* model_photo_out) {
+  SMX_CHECK_ARG(params != nullptr);
+  return track_call(r, s, depth_scaling, depth, normals, color, global_T_pred, &params->icp, params, result, result_on_device,
+                    model_depth_out, model_normal_out, model_photo_out);
+}
+
+int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
+                                          int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  *count = 0;
+  if (!r->trk_rgbd_state.get() || !r->track_busy || !r->track_last_rgbd) return SMX_OK;
+  SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
+  int32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  n = std::max(0, std::min(n, (int32_t)kTrackRing));
+  const int32_t m = std::min(n, capacity);
+  if (m > 0) {
+    SMX_HIP(hipMemcpyAsync(records, r->trk_rgbd_state.get()->ring, sizeof(smx_track_rgbd_iteration) * (size_t)m,
+                           hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  *count = n;
   return SMX_OK;
 }
 

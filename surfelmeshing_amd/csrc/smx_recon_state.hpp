@@ -12,6 +12,7 @@
 namespace smx {
 
 struct TrackDev;        // smx_track.hpp
+struct TrackRgbdDev;
 struct MeshWorkspace;   // smx_mesh.hpp
 
 // Attribute ids = the reference's SoA row numbers, APP/cuda_surfel_reconstruction_kernels.cuh:49-78 (the
@@ -312,6 +313,11 @@ struct smx_recon_s {
   smx::DevBuf<smx::TrackDev> trk_state;
   hipEvent_t ev_track;
   bool track_busy;
+  smx::DevBuf<uint32_t> trk_color;        // smx_recon_track_rgbd (allocated by its first call, all four or none): the model colour
+  smx::DevBuf<float4> trk_photo;          // image [H][W] and P = (L, gx, gy, valid) of the last call with a weight, the 33-sum slabs,
+  smx::DevBuf<double> trk_rgbd_slabs;     // the records and the result with colour; ordered by ev_track like the four above
+  smx::DevBuf<smx::TrackRgbdDev> trk_rgbd_state;
+  bool track_last_rgbd;                   // the last tracking call was smx_recon_track_rgbd (whose records trk_rgbd_state holds)
   smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging
 };
 

@@ -39,4 +39,28 @@ int track_enqueue(hipStream_t st, const TrackBuffers& b, int W, int H, float fx,
                   float depth_scaling, const smx_buffer_desc* depth, const smx_buffer_desc* normals,
                   const float global_T_pred[12], const smx_track_params& p, smx_track_result* result_dev);
 
+// ---- smx_recon_track_rgbd: the same schedule with the photometric term ----
+constexpr int kTrackRgbdSlabStride = 40;   // doubles per workgroup slab (SMX_TRACK_RGBD_SUMS of them used)
+
+// What a call with colour keeps beside TrackDev (whose ring and result it fills as well, with the first 31 sums).
+struct TrackRgbdDev {
+  smx_track_rgbd_result result;
+  smx_track_rgbd_iteration ring[kTrackRing];
+};
+
+struct TrackRgbdBuffers {
+  TrackBuffers icp;             // (icp.slabs is not used: the 33 sums have a slab block of their own)
+  const uint32_t* model_color;  // [H][W] dense uchar4, alpha 0 = empty
+  float4* model_photo;          // [H][W] dense (L, gx, gy, valid)
+  double* slabs;                // [kTrackMaxSlabs][kTrackRgbdSlabStride]
+  TrackRgbdDev* state;
+};
+
+// As track_enqueue, with one k_track_photo_prepare launch in front (none if p.photometric_weight == 0, when
+// model_color / model_photo are not touched either).
+int track_rgbd_enqueue(hipStream_t st, const TrackRgbdBuffers& b, int W, int H, float fx, float fy, float cx, float cy,
+                       float depth_scaling, const smx_buffer_desc* depth, const smx_buffer_desc* normals,
+                       const smx_buffer_desc* color, const float global_T_pred[12], const smx_track_rgbd_params& p,
+                       smx_track_rgbd_result* result_dev);
+
 }  // namespace smx

@@ -10,7 +10,7 @@ there to find -- so it does not disturb the images the pipeline integrates.
 import numpy as np
 
 from . import api
-from ._lib import TrackParams
+from ._lib import TrackParams, TrackRGBDParams
 
 _BOTTOM = np.array([[0.0, 0.0, 0.0, 1.0]])
 
@@ -36,11 +36,19 @@ class Tracker:
         pose = tracker.poses[f]
 
     Policy for a bad status (outcome.ok is False): the frame keeps the prediction, its index goes to `lost`, and the next
-    prediction starts from it.  `outcomes` keeps the TrackOutcome of every tracked frame."""
+    prediction starts from it.  `outcomes` keeps the TrackOutcome of every tracked frame.
 
-    def __init__(self, pipeline, params=None):
+    rgbd=True tracks with the photometric term as well (TrackRGBD / smx_recon_track_rgbd, params a TrackRGBDParams): the
+    colour image is the one the pipeline holds for the frame.  The policy is the same."""
+
+    def __init__(self, pipeline, params=None, rgbd=False):
         self.pipeline = pipeline
-        self.params = params if params is not None else TrackParams.defaults()
+        self.rgbd = bool(rgbd)
+        if params is None:
+            params = TrackRGBDParams.defaults() if self.rgbd else TrackParams.defaults()
+        if isinstance(params, TrackRGBDParams) != self.rgbd:
+            raise TypeError("params must be a %s" % ("TrackRGBDParams" if self.rgbd else "TrackParams"))
+        self.params = params
         h, w = pipeline.h, pipeline.w
         self.filtered_A = api.CUDABuffer(h, w, np.uint16)
         self.filtered_B = api.CUDABuffer(h, w, np.uint16)
@@ -90,8 +98,12 @@ class Tracker:
         TrackOutcome.  The pose kept for the frame is outcome.global_T_frame, or the prediction on a bad status."""
         pred = np.asarray(prediction, np.float32).reshape(3, 4) if prediction is not None else self.predict()
         depth, normals = self.preprocess(frame_index)
-        out = self.pipeline.reconstruction.Track(self.pipeline.stream, self.pipeline.pre.depth_scaling, depth, normals,
-                                                 pred, self.params)
+        pl = self.pipeline
+        if self.rgbd:
+            out = pl.reconstruction.TrackRGBD(pl.stream, pl.pre.depth_scaling, depth, normals, pl.color[frame_index], pred,
+                                              self.params)
+        else:
+            out = pl.reconstruction.Track(pl.stream, pl.pre.depth_scaling, depth, normals, pred, self.params)
         self.outcomes[frame_index] = out
         if out.ok:
             pose = out.global_T_frame

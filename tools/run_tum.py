@@ -3,6 +3,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
       python tools/run_tum.py <dataset_folder> [--trajectory groundtruth.txt] [--export_mesh out.obj]
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
                               [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
+                              [--track_rgbd [--track_photometric_weight W]]
                               [--mesh] [--mesh_every N [--mesh_check]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -11,7 +12,8 @@ where the map changed (one line per update: mode, counts, milliseconds); --expor
 after the last frame.  --mesh_check triangulates once more at the end with the full call and fails if the two differ.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
-that is there is used for the first pose and for an error report only.
+that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
+photometric term to the tracking (smx_recon_track_rgbd), --track_photometric_weight sets its weight.
 With --synthetic N it first writes an N-frame synthetic dataset into the folder (the test stream), so that the whole
 path can be exercised without data."""
 import argparse
@@ -58,7 +60,12 @@ def run_tracked(args, video, pipe, n, have_trajectory):
     first = args.start_frame
     truth = {f: np.asarray(video.depth_frame(f).global_T_frame(), np.float64).reshape(3, 4) for f in range(first, n)} \
         if have_trajectory else None
-    tracker = Tracker(pipe)
+    if args.track_rgbd:
+        from surfelmeshing_amd._lib import TrackRGBDParams
+        kw = {} if args.track_photometric_weight is None else {"photometric_weight": args.track_photometric_weight}
+        tracker = Tracker(pipe, TrackRGBDParams.defaults(**kw), rgbd=True)
+    else:
+        tracker = Tracker(pipe)
     uploaded = set()
 
     def need(g):
@@ -145,7 +152,14 @@ def main():
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
+    ap.add_argument("--track_rgbd", action="store_true",
+                    help="track with the photometric term as well (implies --track)")
+    ap.add_argument("--track_photometric_weight", type=float, default=None,
+                    help="with --track_rgbd: metres per unit intensity (default: the library's, 0.1)")
     args = ap.parse_args()
+    if args.track_photometric_weight is not None and not args.track_rgbd:
+        ap.error("--track_photometric_weight needs --track_rgbd")
+    args.track = args.track or args.track_rgbd
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
     from surfelmeshing_amd import api, export, tum, _lib
