@@ -894,6 +894,54 @@ int smx_recon_triangulate_reset(smx_recon r);            /* drops the kept state
  * before the first call. */
 int smx_recon_debug_mesh_update_timings(smx_recon r, float out_ms[6]);
 
+/* ---- a coarser level of detail of a triangle array: vertex clustering (Rossignac and Borrel 1993) ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n) with n =
+ * surfels_size()), of triangles_in (uint32 [n_in][3], slot indices, e.g. the output of smx_recon_triangulate) and of cell_size.
+ * Every quantity is an integer or a float32 expression evaluated as written, one rounding per operation, no contraction.
+ * 1. Live: a slot is live iff !(RadiusSquared < 0) and its smooth position is finite.  A triangle with a corner that is not
+ *    live is dropped and counted in n_not_live (an array gone stale after an integration: not an error).  An index >= n
+ *    anywhere in the input: SMX_ERR_INVALID_ARGUMENT, nothing is written.  U = the slots that occur in the remaining triangles.
+ * 2. Cell: inv = 1.0f / cell_size (one float32 division); c_k = (int32)floorf(x_k * inv) for k = x, y, z.  Every c_k of every
+ *    slot in U must lie in [-2^20, 2^20), otherwise SMX_ERR_INVALID_ARGUMENT (the cell is too small for the extent of the
+ *    map; nothing is written).  key = ((c_x + 2^20) << 42) | ((c_y + 2^20) << 21) | (c_z + 2^20).
+ * 3. Representative: centre_k = ((float)c_k + 0.5f) * cell_size, d_k = x_k - centre_k, d2 = (d_x d_x + d_y d_y) + d_z d_z.
+ *    rep(cell) = the slot of U in the cell with the smallest (float_bits(d2) << 32) | slot: the one nearest to the centre, a
+ *    tie going to the lower slot.  vertex_map[i] = rep(cell(i)) for i in U, 0xFFFFFFFF for every other slot.
+ * 4. Triangles: each remaining triangle becomes (rep p, rep a, rep b), winding kept.  Two equal corners: dropped, counted
+ *    in n_collapsed.  Among triangles with the same set of three corners, in either winding, the earliest in triangles_in
+ *    stays; the others are counted in n_duplicates.
+ * 5. Output: uint32 [T_out][3], each triangle rotated so that its smallest index is first (winding kept), the array
+ *    ascending by (p, a, b): the format of smx_recon_triangulate, over slot indices, so colour, normals, export, old_to_new
+ *    remapping and a further call with a larger cell work on it unchanged.  Two calls give the same bytes.
+ * 6. Not promised: vertex clustering does not keep the surface manifold.  An edge may lie in more than two triangles, and
+ *    a triangle may end up facing against its corners' normals.  No filter is applied.
+ * Calling rules as smx_recon_triangulate: ordered after everything enqueued on the object, synchronous.  on_device says
+ * where triangles_in, triangles_out and vertex_map live (host arrays are staged).  capacity < T_out:
+ * SMX_ERR_INVALID_ARGUMENT, *n_triangles = T_out, nothing written to triangles_out or vertex_map; triangles_out == NULL with
+ * capacity 0 is that count-only form.  n_in == 0 is valid (T_out = 0).  cell_size must be finite and > 0.  triangles_out
+ * must not overlap triangles_in (refused).  vertex_map may be NULL, else it has surfels_size() entries.  stats may be NULL;
+ * it is filled whenever T_out is known.  Changes no map state, delta mark, statistic or stamp, nor the state
+ * smx_recon_triangulate_update keeps.  The workspace belongs to the object, grows on demand and is reused. */
+typedef struct {
+  uint32_t n_in;             /* triangles given */
+  uint32_t n_not_live;       /* of those, dropped because a corner is not live */
+  uint32_t n_used_vertices;  /* distinct live slots that occur in the remaining triangles */
+  uint32_t n_cells;          /* occupied cells = distinct representatives */
+  uint32_t n_collapsed;      /* triangles with two corners in one cell */
+  uint32_t n_duplicates;     /* triangles dropped because an earlier one has the same three corners */
+  uint32_t n_triangles;      /* T_out */
+} smx_decimate_stats;
+int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size,
+                            const uint32_t* triangles_in, uint32_t n_in,
+                            uint32_t* triangles_out, uint32_t capacity,
+                            uint32_t* vertex_map /* may be NULL; surfels_size() entries */,
+                            int32_t on_device, uint32_t* n_triangles, smx_decimate_stats* stats);
+/* Tools: milliseconds the last smx_recon_decimate_mesh call spent in its SMX_DECIMATE_PHASES phases -- clustering (mark,
+ * insert, look up), remapping + duplicates, survivors (count, scan, write), ordering (two sorts, emit) -- by timed events
+ * on the call's stream; a phase a call did not reach reads 0.  capacity >= SMX_DECIMATE_PHASES.  Zeros before the first call. */
+#define SMX_DECIMATE_PHASES 4
+int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- benchmark input generator (not part of the reference's interface) ----
  * Renders one frame of the synthetic room stream into device buffers:
  * depth u16 = round(depth_scaling * z) with sigma = noise_sigma * z^2 noise and coherent 8x8

@@ -585,6 +585,25 @@ class CUDASurfelReconstruction {
     SMX_SHIM_CHECK(rc);
   }
   void ResetTriangulation() { SMX_SHIM_CHECK(smx_recon_triangulate_reset(handle_)); }
+  // Not in the reference: a coarser level of detail of a triangle array by vertex clustering on a grid of cell_size
+  // (smx_recon_decimate_mesh in smx.h).  triangles_in: three slot indices per triangle, as Triangulate returns them;
+  // *triangles_out (not the same vector) receives the result in the same format.  *vertex_map (may be null) receives the
+  // representative of every used slot, 0xFFFFFFFF for the others; stats may be null.  Synchronous.
+  void DecimateMesh(cudaStream_t stream, const std::vector<u32>& triangles_in, float cell_size, std::vector<u32>* triangles_out,
+                    std::vector<u32>* vertex_map = nullptr, smx_decimate_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles_in.size() / 3);
+    u32 count = 0;
+    int rc = smx_recon_decimate_mesh(handle_, stream, cell_size, triangles_in.data(), n_in, nullptr, 0, nullptr, 0, &count, stats);
+    if (rc == SMX_OK || (rc == SMX_ERR_INVALID_ARGUMENT && count > 0)) {   // (the capacity rule: the count came back)
+      triangles_out->resize((size_t)3 * count);
+      if (vertex_map) vertex_map->resize(surfels_size());
+      rc = (count || vertex_map)
+               ? smx_recon_decimate_mesh(handle_, stream, cell_size, triangles_in.data(), n_in, count ? triangles_out->data() : nullptr,
+                                         count, vertex_map && !vertex_map->empty() ? vertex_map->data() : nullptr, 0, &count, stats)
+               : SMX_OK;
+    }
+    SMX_SHIM_CHECK(rc);
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

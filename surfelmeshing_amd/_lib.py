@@ -166,6 +166,15 @@ class MeshUpdateStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mode", "n_changed", "n_dirty", "n_reagreed", "n_kept_triangles")]
 
 
+class DecimateStats(C.Structure):
+    """smx_decimate_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_used_vertices", "n_cells", "n_collapsed", "n_duplicates",
+                                          "n_triangles")]
+
+
+DECIMATE_PHASES = 4   # SMX_DECIMATE_PHASES
+
+
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
     _fields_ = [("frame_index", C.c_uint32), ("surfel_count", C.c_size_t),
@@ -213,6 +222,7 @@ EXPORTS = [
     "smx_recon_build_neighbor_index", "smx_recon_neighbor_candidates", "smx_recon_check_triangles",
     "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings",
     "smx_recon_triangulate_update", "smx_recon_triangulate_reset", "smx_recon_debug_mesh_update_timings", "smx_recon_deform_by_creation_frame",
+    "smx_recon_decimate_mesh", "smx_recon_debug_decimate_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",

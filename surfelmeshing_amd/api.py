@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
-                   MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
+                   DECIMATE_PHASES, DecimateStats, MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
@@ -701,6 +701,38 @@ class CUDASurfelReconstruction:
         out = (C.c_float * 4)()
         _lib.check(_lib.load().smx_recon_debug_mesh_timings(self._h, out))
         return dict(zip(("index_build", "list_query", "star", "agree_write"), [float(v) for v in out]))
+
+    def DecimateMesh(self, stream, triangles, cell_size, return_vertex_map=False):
+        """Not in the reference: a coarser level of detail of `triangles` ([T,3] slot indices, e.g. Triangulate's) by vertex
+        clustering (smx_recon_decimate_mesh): the vertices of a cubic cell of edge cell_size collapse onto the one nearest
+        to the cell's centre, triangles that lose a corner or repeat an earlier one go.  The result is again a triangle array
+        over slot indices in Triangulate's format, so export, colours and a further, coarser call work on it unchanged; it
+        is not kept manifold.  Synchronous.  Returns (triangles [T_out,3] uint32, dict of smx_decimate_stats), and with
+        return_vertex_map also vertex_map [surfels_size()] uint32 (the representative of every used slot, 0xFFFFFFFF for
+        the others)."""
+        tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        L = _lib.load()
+        T, st = C.c_uint32(0), DecimateStats()
+        tin = tri.ctypes.data_as(C.c_void_p) if tri.shape[0] else None
+        rc = L.smx_recon_decimate_mesh(self._h, _sv(stream), C.c_float(cell_size), tin, C.c_uint32(tri.shape[0]), None,
+                                       C.c_uint32(0), None, C.c_int32(0), C.byref(T), C.byref(st))
+        if rc != 0 and not (rc == -1 and T.value > 0):   # (SMX_ERR_INVALID_ARGUMENT with the count: the capacity rule)
+            _lib.check(rc)
+        out = np.zeros((T.value, 3), np.uint32)
+        vmap = np.zeros(self._counts_on(stream)[1], np.uint32) if return_vertex_map else None
+        if T.value or return_vertex_map:
+            _lib.check(L.smx_recon_decimate_mesh(
+                self._h, _sv(stream), C.c_float(cell_size), tin, C.c_uint32(tri.shape[0]),
+                out.ctypes.data_as(C.c_void_p) if T.value else None, C.c_uint32(T.value),
+                vmap.ctypes.data_as(C.c_void_p) if vmap is not None and vmap.size else None, C.c_int32(0), C.byref(T), C.byref(st)))
+        stats = {n: int(getattr(st, n)) for n, _ in DecimateStats._fields_}
+        return (out, stats, vmap) if return_vertex_map else (out, stats)
+
+    def debug_decimate_timings(self):
+        """Milliseconds of the last DecimateMesh call, by phase."""
+        out = (C.c_float * DECIMATE_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_decimate_timings(self._h, out, C.c_int32(DECIMATE_PHASES)))
+        return dict(zip(("cluster", "remap_dedupe", "survivors", "order"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "smx_common.hpp"
+#include "smx_sort.hpp"
 
 using namespace smx;
 
@@ -1202,8 +1203,14 @@ int ensure_queries(smx_nn nn, size_t nq) {
   return SMX_OK;
 }
 
+int bit_length(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+}  // namespace
+
+// (smx_sort.hpp: smx_decimate orders its output with it too)
+size_t smx::radix_sort_workspace_elems(size_t n) { return sort_hist_elems(n) + scan_workspace_elems(sort_hist_elems(n)); }
 // Sorts (keys[0], vals[0]) by the low `bits` bits; returns the index (0 / 1) of the buffers that hold the result.
-int radix_sort(const DevBuf<unsigned long long> (&key_bufs)[2], const DevBuf<uint32_t> (&val_bufs)[2], uint32_t n, int bits,
+int smx::radix_sort(const DevBuf<unsigned long long> (&key_bufs)[2], const DevBuf<uint32_t> (&val_bufs)[2], uint32_t n, int bits,
                uint32_t* hist, hipStream_t st) {
   unsigned long long* const keys[2] = {key_bufs[0].get(), key_bufs[1].get()};
   uint32_t* const vals[2] = {val_bufs[0].get(), val_bufs[1].get()};
@@ -1220,10 +1227,6 @@ int radix_sort(const DevBuf<unsigned long long> (&key_bufs)[2], const DevBuf<uin
   }
   return cur;
 }
-
-int bit_length(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
-
-}  // namespace
 
 extern "C" {
 

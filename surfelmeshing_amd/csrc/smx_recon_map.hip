@@ -14,7 +14,9 @@
 
 #include "smx_recon_state.hpp"
 #include "smx_track.hpp"
+#include "smx_decimate.hpp"
 #include "smx_mesh.hpp"
+#include "smx_sort.hpp"
 
 using namespace smx;
 
@@ -918,6 +920,150 @@ int smx_recon_debug_mesh_update_timings(smx_recon r, float out_ms[6]) {
   SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
   SMX_ON_DEVICE(r->device);
   return mesh_update_phase_ms(r->mesh, out_ms);
+}
+
+// ---- decimation of a triangle array by vertex clustering (include/smx.h; kernels in smx_decimate.hip) ----
+int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size, const uint32_t* triangles_in, uint32_t n_in,
+                            uint32_t* triangles_out, uint32_t capacity, uint32_t* vertex_map, int32_t on_device,
+                            uint32_t* n_triangles, smx_decimate_stats* stats) {
+  SMX_CHECK_ARG(r != nullptr && n_triangles != nullptr);
+  SMX_CHECK_ARG(cell_size > 0.0f && cell_size - cell_size == 0.0f);
+  SMX_CHECK_ARG(triangles_in != nullptr || n_in == 0);
+  SMX_CHECK_ARG(triangles_out != nullptr || capacity == 0);
+  if (n_in > 0 && capacity > 0) {
+    const uintptr_t i0 = (uintptr_t)triangles_in, i1 = i0 + (size_t)n_in * 12, o0 = (uintptr_t)triangles_out, o1 = o0 + (size_t)capacity * 12;
+    if (i0 < o1 && o0 < i1) {
+      set_error("triangles_out overlaps triangles_in");
+      return SMX_ERR_INVALID_ARGUMENT;
+    }
+  }
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  SMX_CALL(join_regularizer(r, st));
+  uint32_t n = 0;
+  SMX_CALL(read_surfel_count(r, st, &n));
+  *n_triangles = 0;
+  if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_in = n_in; }
+  if (!r->ev_dec[0]) for (hipEvent_t& e : r->ev_dec) SMX_HIP(hipEventCreate(&e));
+  r->dec_phases = 0;
+  SMX_HIP(hipEventRecord(r->ev_dec[0], st));
+  int phases = 0;
+  auto stamp = [&]() -> int { SMX_HIP(hipEventRecord(r->ev_dec[++phases], st)); return SMX_OK; };
+  auto finish = [&](int rc) -> int {     // (the stamps are complete before they are published)
+    SMX_HIP(hipStreamSynchronize(st));
+    r->dec_phases = phases;
+    return rc;
+  };
+
+  // ---- workspace of the first two phases; the input on the device
+  const uint32_t cell_entries = dec_table_size((uint32_t)std::min<unsigned long long>(n, 3ull * n_in));
+  const uint32_t dup_entries = dec_table_size(n_in);
+  const int nb = div_up(n_in, kDecBlock);
+  if (!r->dec_counters.get()) SMX_CALL(r->dec_counters.alloc(kDecWords, false));
+  SMX_CALL(r->dec_vmap.reserve(n));
+  if (n_in > 0) {
+    SMX_CALL(r->dec_cells.reserve((size_t)2 * cell_entries));
+    SMX_CALL(r->dec_canon.reserve((size_t)3 * n_in));
+    SMX_CALL(r->dec_own.reserve(n_in));
+    SMX_CALL(r->dec_dup.reserve(dup_entries));
+    SMX_CALL(r->dec_blocks.reserve((size_t)nb));
+  }
+  const uint32_t* din = triangles_in;
+  if (!on_device && n_in > 0) {
+    SMX_CALL(r->dec_in.reserve((size_t)3 * n_in));
+    SMX_HIP(hipMemcpyAsync(r->dec_in.get(), triangles_in, (size_t)n_in * 12, hipMemcpyHostToDevice, st));
+    din = r->dec_in.get();
+  }
+  uint32_t* cnt = r->dec_counters.get();
+  SMX_HIP(hipMemsetAsync(cnt, 0, kDecWords * sizeof(uint32_t), st));
+  uint32_t h[kDecWords];
+  auto read_counters = [&]() -> int {
+    SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+    return SMX_OK;
+  };
+
+  // ---- clustering: U, the cell table, the vertex map.  (An index out of range marks nothing and is read by nothing.)
+  const float inv = 1.0f / cell_size;
+  DecMap map;
+  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
+  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
+  map.smooth = quads + s0; map.smooth_stride = r->S.quad(kGroupS, 1) - s0;
+  map.normal = quads + n0; map.normal_stride = r->S.quad(kGroupN, 1) - n0;
+  map.n = n;
+  DecCell* cells = reinterpret_cast<DecCell*>(r->dec_cells.get());
+  DecTri* canon = reinterpret_cast<DecTri*>(r->dec_canon.get());
+  SMX_CALL(dec_enqueue_cluster(st, map, din, n_in, cell_size, inv, r->dec_vmap.get(), cells, cell_entries, cnt));
+  SMX_CALL(stamp());
+  SMX_CALL(read_counters());
+  if (h[kDecError] & kDecErrIndex) {
+    set_error("triangles_in holds an index >= the %u slots of the map", n);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+  if (h[kDecError] & kDecErrRange) {
+    set_error("cell_size %g is too small for the extent of the map: a cell coordinate is outside [-2^20, 2^20)", (double)cell_size);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+
+  // ---- remap and duplicates; survivors counted and scanned
+  SMX_CALL(dec_enqueue_remap(st, din, n_in, r->dec_vmap.get(), canon, r->dec_own.get(), r->dec_dup.get(), dup_entries, cnt));
+  SMX_CALL(stamp());
+  if (n_in > 0) {
+    SMX_CALL(dec_enqueue_count(st, n_in, r->dec_own.get(), r->dec_dup.get(), r->dec_blocks.get()));
+    enqueue_segment_scan(st, r->dec_blocks.get(), nb, cnt + kDecTotal);
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_CALL(read_counters());
+  const uint32_t T = h[kDecTotal];
+  *n_triangles = T;
+  if (stats) {
+    stats->n_not_live = h[kDecNotLive]; stats->n_used_vertices = h[kDecUsed]; stats->n_cells = h[kDecCells];
+    stats->n_collapsed = h[kDecCollapsed]; stats->n_duplicates = h[kDecAlive] - T; stats->n_triangles = T;
+  }
+  if (capacity < T) {
+    if (triangles_out != nullptr || capacity != 0) set_error("triangles_out holds %u entries, the decimated mesh has %u", capacity, T);
+    else set_error("count only: the decimated mesh has %u triangles", T);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+
+  // ---- the survivors in input order as sort records, ordered by (a, b) and then, stably, by p
+  if (T > 0) {
+    int bits = 1;
+    while (bits < 32 && ((uint32_t)(n - 1) >> bits) != 0) ++bits;
+    for (int k = 0; k < 2; ++k) { SMX_CALL(r->dec_keys[k].reserve(T)); SMX_CALL(r->dec_vals[k].reserve(T)); }
+    SMX_CALL(r->dec_hist.reserve(radix_sort_workspace_elems(T)));
+    SMX_CALL(dec_enqueue_write(st, n_in, r->dec_own.get(), r->dec_dup.get(), r->dec_blocks.get(), canon, bits, r->dec_keys[0].get(),
+                               r->dec_vals[0].get()));
+    SMX_CALL(stamp());
+    int cur = radix_sort(r->dec_keys, r->dec_vals, T, 2 * bits, r->dec_hist.get(), st);
+    SMX_LAUNCH_CHECK();
+    SMX_CALL(dec_enqueue_keys_p(st, T, r->dec_vals[cur].get(), canon, r->dec_keys[0].get(), r->dec_vals[0].get()));
+    cur = radix_sort(r->dec_keys, r->dec_vals, T, bits, r->dec_hist.get(), st);
+    SMX_LAUNCH_CHECK();
+    uint32_t* dst = triangles_out;
+    if (!on_device) {
+      SMX_CALL(r->dec_out.reserve((size_t)3 * T));
+      dst = r->dec_out.get();
+    }
+    SMX_CALL(dec_enqueue_emit(st, T, r->dec_vals[cur].get(), canon, dst));
+    if (!on_device) SMX_HIP(hipMemcpyAsync(triangles_out, dst, (size_t)T * 12, hipMemcpyDeviceToHost, st));
+  } else {
+    SMX_CALL(stamp());
+  }
+  if (vertex_map && n > 0)
+    SMX_HIP(hipMemcpyAsync(vertex_map, r->dec_vmap.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  SMX_CALL(stamp());
+  return finish(SMX_OK);
+}
+
+int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity) {
+  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr && capacity >= SMX_DECIMATE_PHASES);
+  SMX_ON_DEVICE(r->device);
+  for (int i = 0; i < SMX_DECIMATE_PHASES; ++i) {
+    out_ms[i] = 0.0f;
+    if (i < r->dec_phases) SMX_HIP(hipEventElapsedTime(&out_ms[i], r->ev_dec[i], r->ev_dec[i + 1]));
+  }
+  return SMX_OK;
 }
 
 int smx_recon_debug_download_surfels(smx_recon r, smx_stream s, float* rows, uint32_t count) {

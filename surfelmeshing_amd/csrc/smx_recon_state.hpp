@@ -318,7 +318,19 @@ struct smx_recon_s {
   smx::DevBuf<double> trk_rgbd_slabs;     // the records and the result with colour; ordered by ev_track like the four above
   smx::DevBuf<smx::TrackRgbdDev> trk_rgbd_state;
   bool track_last_rgbd;                   // the last tracking call was smx_recon_track_rgbd (whose records trk_rgbd_state holds)
-  smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging
+  smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging  // smx_recon_decimate_mesh (each grows on demand, the call is synchronous, so nothing reads a block that goes)
+  smx::DevBuf<uint32_t> dec_vmap;                  // [n] the vertex map
+  smx::DevBuf<unsigned long long> dec_cells;       // [cell table entries][2]: key, value word (smx::DecCell)
+  smx::DevBuf<uint32_t> dec_canon, dec_own;        // [n_in][3] canonical triples (smx::DecTri); [n_in] each triangle's entry of
+  smx::DevBuf<uint32_t> dec_dup;                   // the table of triangle indices
+  smx::DevBuf<uint32_t> dec_blocks;                // survivors per workgroup, then their offsets
+  smx::DevBuf<unsigned long long> dec_keys[2];     // [T_out] the sort's records
+  smx::DevBuf<uint32_t> dec_vals[2];
+  smx::DevBuf<uint32_t> dec_hist;                  // the sort's workspace
+  smx::DevBuf<uint32_t> dec_in, dec_out;           // staging when the caller's arrays are host memory
+  smx::DevBuf<uint32_t> dec_counters;              // [kDecWords]
+  hipEvent_t ev_dec[5];                            // stamps of the last call (created by the first)
+  int dec_phases;                                  // how many phases of it they bracket
 };
 
 namespace smx {

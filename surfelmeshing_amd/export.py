@@ -90,18 +90,22 @@ def export_vertices(reconstruction, stream=None):
     return p, c
 
 
-def SaveMeshAsOBJ(reconstruction, export_mesh_path, stream=None, triangles=None):
+def SaveMeshAsOBJ(reconstruction, export_mesh_path, stream=None, triangles=None, referenced_only=False):
     """main.cc:128-178.  `triangles` [T,3]: surfel (slot) indices as the mesher holds them; triangles that touch a
     merged surfel are dropped, the rest renumbered to the compacted vertex list.  Without triangles the file holds
-    the coloured vertices only."""
+    the coloured vertices only.  referenced_only (with triangles; for a decimated mesh, which uses few of the surfels):
+    only the vertices a written face uses are written, in slot order, and the faces are renumbered to them."""
     p, c = export_vertices(reconstruction, stream)
     live = ~np.isnan(p[:, 0])                                  # main.cc:152-155
     tri = None
     if triangles is not None:
-        remap = np.cumsum(live) - 1
         t = np.asarray(triangles, np.int64).reshape(-1, 3)
         t = t[np.all((t >= 0) & (t < live.size), axis=1)]
         t = t[np.all(live[t], axis=1)]
+        if referenced_only:
+            live = np.zeros(live.size, bool)
+            live[t] = True
+        remap = np.cumsum(live) - 1
         tri = remap[t]
     return write_obj(export_mesh_path, p[live], c[live], tri)
 

@@ -9,12 +9,17 @@ the map changed:
 
     mesher = meshing.MapMesher(rec)
     for every few frames: triangles, stats, update_stats = mesher.update()
+
+A coarser level of detail of either (smx_recon_decimate_mesh) -- vertex clustering on a grid of cell_size:
+
+    coarse, decimate_stats = meshing.decimate_map_mesh(rec, triangles, 0.05)
 """
 from ._lib import MeshParams as _MeshParamsPOD
 
 UPDATE_STAT_NAMES = ("mode", "n_changed", "n_dirty", "n_reagreed", "n_kept_triangles")
 UPDATE_MODES = ("incremental", "full: no state", "full: parameters differ", "full: fewer slots than kept",
                 "full: dirty fraction above the limit")
+DECIMATE_STAT_NAMES = ("n_in", "n_not_live", "n_used_vertices", "n_cells", "n_collapsed", "n_duplicates", "n_triangles")
 STAT_NAMES = ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")
 
 
@@ -51,9 +56,17 @@ def mesh_map(rec, params=None, stream=None, index=None, cell_size=None):
     return rec.Triangulate(stream, pod, index=index, cell_size=cell_size)
 
 
+def decimate_map_mesh(rec, triangles, cell_size, stream=None):
+    """Decimates `triangles` ([T,3] slot indices of `rec`'s map) by vertex clustering on a grid of cell_size metres.  The
+    result has the format of the input (and may be decimated again with a larger cell); it is not kept manifold.
+    Returns (triangles [T_out,3] uint32, stats dict)."""
+    return rec.DecimateMesh(stream, triangles, cell_size)
+
+
 class MapMesher:
     """Keeps the mesh of `rec`'s map up to date.  Owns the neighbour index; update() returns what mesh_map would return
-    on the map as it stands, plus the update statistics, and keeps the triangles in .triangles / .stats."""
+    on the map as it stands, plus the update statistics, and keeps the triangles in .triangles / .stats.  With a
+    cell_size, update() also decimates the result (.decimated / .decimate_stats) and returns that array as a fourth value."""
 
     def __init__(self, rec, params=None, cell_size=None, full_above_fraction=None):
         from .api import SurfelNeighborIndex
@@ -63,16 +76,22 @@ class MapMesher:
         self._fraction = full_above_fraction
         self._index = SurfelNeighborIndex(rec._device_id)
         self.triangles, self.stats, self.update_stats = None, None, None
+        self.decimated, self.decimate_stats = None, None
 
     @property
     def index(self):
         """The neighbour index, built over the map as of the last update()."""
         return self._index
 
-    def update(self, stream=None):
+    def update(self, stream=None, cell_size=None):
+        """cell_size (of the decimation grid, metres; not the index's): None = no decimation."""
         self.triangles, self.stats, self.update_stats = self._rec.TriangulateUpdate(
             stream, self._pod, index=self._index, cell_size=self._cell_size, full_above_fraction=self._fraction)
-        return self.triangles, self.stats, self.update_stats
+        self.decimated, self.decimate_stats = None, None
+        if cell_size is None:
+            return self.triangles, self.stats, self.update_stats
+        self.decimated, self.decimate_stats = self._rec.DecimateMesh(stream, self.triangles, cell_size)
+        return self.triangles, self.stats, self.update_stats, self.decimated
 
     def timings(self):
         return self._rec.debug_mesh_update_timings()
@@ -81,6 +100,7 @@ class MapMesher:
         """Drops the kept state (and its device memory); the next update() runs the full path."""
         self._rec.ResetTriangulation()
         self.triangles, self.stats, self.update_stats = None, None, None
+        self.decimated, self.decimate_stats = None, None
 
     def close(self):
         if self._index is not None:

@@ -3,7 +3,8 @@
 Every file of build.SOURCES is compiled device-only to gfx950 assembly in both trees (the flags of tools/isa_regs.sh).  Per
 kernel: the descriptor's registers, LDS and scratch, and the instruction stream with comments and directives dropped,
 basic-block labels renumbered and symbol names demangled without "(anonymous namespace)::" and "smx::" (the method of
-profiles/recon_split_isa.txt).  Prints one line per kernel and the number that differ; needs no GPU."""
+profiles/recon_split_isa.txt).  Prints one line per kernel and the number that differ; needs no GPU.  A source file the old
+tree does not have yet is compiled in the new tree alone and its kernels are listed as "new"."""
 import os
 import re
 import shutil
@@ -60,13 +61,19 @@ def main(old, new):
     jobs = []
     for src in SOURCES:
         outs = [os.path.join(tmp, "%s_%s.s" % (tag, src)) for tag in ("old", "new")]
-        jobs.append((src, outs, [compile_to_asm(root, src, out) for root, out in zip((old, new), outs)]))
+        have = [os.path.exists(os.path.join(root, "surfelmeshing_amd", "csrc", src)) for root in (old, new)]
+        jobs.append((src, outs, [compile_to_asm(root, src, out) if h else None for root, out, h in zip((old, new), outs, have)]))
     print("%-70s %-18s %5s %5s %6s %7s %7s  %s" % ("kernel", "file", "vgpr", "sgpr", "lds", "scratch", "instrs", "verdict"))
     total = differ = 0
     for src, outs, procs in jobs:
-        if any(p.wait() != 0 for p in procs):
+        if any(p is not None and p.wait() != 0 for p in procs) or procs[1] is None:
             raise SystemExit("hipcc failed on " + src)
-        ko, kn = kernels(outs[0]), kernels(outs[1])
+        kn = kernels(outs[1])
+        if procs[0] is None:
+            for name, pretty in zip(kn, demangle(list(kn)) if kn else []):
+                print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (re.sub(r"\(.*$", "", pretty)[:70], src, *kn[name][0], kn[name][2], "new"))
+            continue
+        ko = kernels(outs[0])
         if list(ko) != list(kn):
             raise SystemExit("%s: the two trees do not have the same kernels: %s" % (src, sorted(set(ko) ^ set(kn))))
         for name, pretty in zip(kn, demangle(list(kn)) if kn else []):

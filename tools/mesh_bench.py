@@ -3,6 +3,7 @@ tools/compact_bench.py grows).
 
     python tools/mesh_bench.py [--reps 5] [--target 5000000] [--json OUT]
     python tools/mesh_bench.py --update [--target 5000000] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --decimate CELL[,CELL...] [--target 5000000] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -14,7 +15,12 @@ same process: one update after 1, 4 and 16 more integrated frames, then a sweep 
 live slots change (the surfels of the most recent creation frames are moved by 1 mm through
 smx_recon_deform_by_creation_frame: a coherent part of the map, as a frame's changes are).  The update is timed as the
 application calls it: one call with a device buffer that is large enough.  Every update is compared with the full call's
-bytes.  The sweep runs with full_above_fraction = 1, so that the incremental path is what is measured at every point."""
+bytes.  The sweep runs with full_above_fraction = 1, so that the incremental path is what is measured at every point.
+
+--decimate measures smx_recon_decimate_mesh on the same map's full mesh for every cell size given (metres):
+medians of --reps calls with device arrays that are large enough, whole calls by device events and the four phases by the
+library's own (smx_recon_debug_decimate_timings), triangles and vertices in and out, bytes by decimate_traffic_bytes below
+against the HBM peak, and the full triangulation re-measured in the same process beside it."""
 import argparse
 import json
 import os
@@ -29,6 +35,7 @@ ap.add_argument("--target", type=int, default=5_000_000)
 ap.add_argument("--json", default=None)
 ap.add_argument("--update", action="store_true")
 ap.add_argument("--txt", default=None)
+ap.add_argument("--decimate", default=None, help="comma-separated cell sizes in metres")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 
@@ -51,6 +58,125 @@ def traffic_bytes(n, live, k, triangles):
     rings = (64 + 4) * n * (1 + 3)
     scan = 4 * n * 2 + 8 * (n // 256 + 1)
     return lists + records + rings + scan + 12 * triangles
+
+
+HBM_PEAK = 8.0e12   # bytes/s (MI355X spec)
+DECIMATE_PHASES = ("cluster", "remap_dedupe", "survivors", "order")
+
+
+def _table_size(entries):
+    s = 64
+    while s < 2 * entries:
+        s *= 2
+    return s
+
+
+def decimate_traffic_bytes(n, st):
+    """HBM bytes of one smx_recon_decimate_mesh call over n slots, by phase, from its statistics.  Gathers are counted once
+    per distinct target (a lower bound: neighbouring triangles share corners and mostly hit in cache), an atomic as a read
+    and a write of its entry; the host round trips between the phases move a few words."""
+    n_in, used, T = st["n_in"], st["n_used_vertices"], st["n_triangles"]
+    alive = T + st["n_duplicates"]
+    bits = max(1, int(n - 1).bit_length())
+    cluster = (4 * n + 16 * _table_size(min(n, 3 * n_in))      # vmap and the cell table reset
+               + 12 * n_in + 32 * used + 4 * used               # mark: the input, S and N records of the corners, U
+               + 4 * n + 16 * used + 2 * 32 * used + 4 * used   # insert: vmap, S records, CAS + min on a 16-byte entry, vmap
+               + 4 * n + 16 * used + 4 * used)                  # look up
+    remap = (4 * _table_size(n_in) + 12 * n_in + 4 * used + 12 * n_in        # reset; the input, vmap gathers, canonical triples
+             + 12 * n_in + 8 * alive + 12 * st["n_duplicates"] + 4 * n_in)  # duplicates: triples, the entry, the resident's triple, own
+    survivors = 2 * (4 * n_in + 4 * alive) + 8 * (n_in // 256 + 1) + 12 * T + 12 * T
+    passes = -(-2 * bits // 8) + -(-bits // 8)
+    order = passes * 32 * T + (4 + 12 + 12) * T + (4 + 12 + 12) * T          # per pass: keys twice, values, both written
+    return dict(zip(DECIMATE_PHASES, (cluster, remap, survivors, order)))
+
+
+def decimate_main():
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    cells = [float(c) for c in args.decimate.split(",")]
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    rows = rec.debug_download_surfels()
+    spacing = float(np.median(np.sqrt(rows[7][rows[7] >= 0])))
+    del rows
+    say("# grown in %.1f s: %d slots, %d live; median surfel radius %.4f m" % (time.time() - t0, n, live, spacing))
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout, dmap = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, n, np.uint32)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def full():
+        T, st = C.c_uint32(0), _lib.MeshStats()
+        _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                           C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+        return T.value
+
+    def decimate(cell, n_in):
+        T, st = C.c_uint32(0), _lib.DecimateStats()
+        _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(n_in),
+                                             C.c_void_p(dout.ToCUDA().address), C.c_uint32(cap), C.c_void_p(dmap.ToCUDA().address),
+                                             C.c_int32(1), C.byref(T), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in _lib.DecimateStats._fields_}
+    t_full, ph_full = [], []
+    for _ in range(args.reps + 1):
+        ms, T_in = timed(full)
+        t_full.append(ms)
+        ph_full.append(sum(rec.debug_mesh_timings().values()))
+    full_ms, full_events_ms = float(np.median(t_full[1:])), float(np.median(ph_full[1:]))
+    say("full triangulation, re-measured here: %d triangles, one call %.2f ms (%.2f ms by the library's events)" % (T_in, full_ms, full_events_ms))
+    out_rows = []
+    for cell in cells:
+        t, phs, st, first = [], [], None, None
+        for _ in range(args.reps + 1):
+            ms, st = timed(lambda: decimate(cell, T_in))
+            t.append(ms)
+            phs.append(rec.debug_decimate_timings())
+            head = dout.Download()[0][:3 * min(st["n_triangles"], 100000)].tobytes()
+            first = head if first is None else first
+            assert head == first, "two calls gave different bytes"
+        med = float(np.median(t[1:]))                       # (the first call allocates the workspace)
+        ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in DECIMATE_PHASES}
+        b = decimate_traffic_bytes(n, st)
+        tot = sum(b.values())
+        say("cell %.4f m (%.1f radii): %d -> %d triangles, %d -> %d vertices (%d collapsed, %d duplicates) | call %.2f ms (min %.2f, "
+            "max %.2f) = %.2f x the full triangulation | %s | model %.2f GB -> %.2f TB/s = %.0f %% of the %.1f TB/s HBM peak (%s)" % (
+                cell, cell / spacing, st["n_in"], st["n_triangles"], st["n_used_vertices"], st["n_cells"], st["n_collapsed"],
+                st["n_duplicates"], med, min(t[1:]), max(t[1:]), med / full_ms,
+                " ".join("%s %.2f" % (k, ph[k]) for k in DECIMATE_PHASES), tot / 1e9, tot / (med * 1e-3) / 1e12,
+                100.0 * tot / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12,
+                " ".join("%s %.0f %%" % (k, 100.0 * b[k] / (max(ph[k], 1e-6) * 1e-3) / HBM_PEAK) for k in DECIMATE_PHASES)))
+        out_rows.append({"cell_size": cell, "cell_in_median_radii": cell / spacing, "reps": len(t) - 1, "call_ms": med, "call_ms_all": t[1:],
+                         "phases_ms": ph, "stats": st, "traffic_model_bytes": b, "fraction_of_hbm_peak": tot / (med * 1e-3) / HBM_PEAK,
+                         "ratio_to_full_triangulation": med / full_ms})
+    res = {"metric": "decimate_mesh_ms", "slots": n, "live": live, "median_surfel_radius_m": spacing, "triangles_in": T_in,
+           "full_triangulation_ms": full_ms, "full_triangulation_events_ms": full_events_ms, "rows": out_rows}
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    if args.txt:
+        with open(args.txt, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    for b in (dtri, dout, dmap):
+        b.close()
+    nn.close()
 
 
 UPDATE_PHASES = ("diff", "index_builds", "reverse_test", "subset_lists", "stars", "agree_merge")
@@ -215,4 +341,4 @@ def main():
 
 
 if __name__ == "__main__":
-    update_main() if args.update else main()
+    decimate_main() if args.decimate else update_main() if args.update else main()

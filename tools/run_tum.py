@@ -4,12 +4,14 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
                               [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
                               [--track_rgbd [--track_photometric_weight W]]
-                              [--mesh] [--mesh_every N [--mesh_check]] ...
+                              [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
 With --mesh_every N the mesh follows the map instead: every N integrated frames smx_recon_triangulate_update recomputes it
 where the map changed (one line per update: mode, counts, milliseconds); --export_mesh then writes the last update, made
 after the last frame.  --mesh_check triangulates once more at the end with the full call and fails if the two differ.
+--mesh_decimate METRES (with --mesh or --mesh_every) decimates the final mesh by vertex clustering on a grid of that cell
+size (smx_recon_decimate_mesh) before --export_mesh, which then writes only the vertices the coarse mesh uses.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
@@ -149,6 +151,9 @@ def main():
                     help="keep the mesh up to date: update it every N integrated frames and after the last one (0 = never)")
     ap.add_argument("--mesh_check", action="store_true",
                     help="with --mesh_every: compare the last update with one full triangulation, exit 1 if they differ")
+    ap.add_argument("--mesh_decimate", type=float, default=None, metavar="METRES",
+                    help="with --mesh or --mesh_every: decimate the final mesh by vertex clustering with this cell size; "
+                         "--export_mesh then writes the decimated mesh and only the vertices it uses")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -160,6 +165,10 @@ def main():
     if args.track_photometric_weight is not None and not args.track_rgbd:
         ap.error("--track_photometric_weight needs --track_rgbd")
     args.track = args.track or args.track_rgbd
+    if args.mesh_decimate is not None and not (args.mesh or args.mesh_every > 0):
+        ap.error("--mesh_decimate needs --mesh or --mesh_every")
+    if args.mesh_decimate is not None and not args.mesh_decimate > 0:
+        ap.error("--mesh_decimate needs a cell size > 0")
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
     from surfelmeshing_amd import api, export, tum, _lib
@@ -269,8 +278,14 @@ def main():
         triangles, mesh_stats = meshing.mesh_map(rec)
         print("%d triangles in %.1f ms; %s" % (triangles.shape[0], 1e3 * (time.time() - t1),
                                               ", ".join("%s %d" % (k, mesh_stats[k]) for k in meshing.STAT_NAMES)))
+    if args.mesh_decimate is not None:
+        from surfelmeshing_amd import meshing
+        t1 = time.time()
+        triangles, dst = meshing.decimate_map_mesh(rec, triangles, args.mesh_decimate)
+        print("decimated at %g m in %.1f ms: %s" % (args.mesh_decimate, 1e3 * (time.time() - t1),
+                                                    ", ".join("%s %d" % (k, dst[k]) for k in meshing.DECIMATE_STAT_NAMES)))
     if args.export_mesh:
-        export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles)
+        export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles, referenced_only=args.mesh_decimate is not None)
         print("Wrote %s." % args.export_mesh)
     if args.export_point_cloud:
         export.SavePointCloudAsPLY(rec, args.export_point_cloud, export_colors=True)
