@@ -763,80 +763,68 @@ class CUDASurfelReconstruction:
         _lib.check(_lib.load().smx_recon_render(self._h, _sv(stream), C.byref(params) if params is not None else None,
                                                 opt(depth), opt(index), opt(normal), opt(color)))
 
+    def _track(self, fn, stream, depth_scaling, images, global_T_pred, params, result, model_images):
+        """smx_recon_track / smx_recon_track_rgbd (fn): the frame's `images`, then pose, params and result, then the
+        optional model images.  result: a ctypes struct to fill (synchronous) or a CUDABuffer / device pointer."""
+        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
+        on_device = not isinstance(result, C.Structure)
+        if on_device:
+            result = C.c_void_p(result.ToCUDA().address if isinstance(result, CUDABuffer) else int(result))
+        _lib.check(fn(self._h, _sv(stream), C.c_float(depth_scaling), *[_d(b) for b in images], T.ctypes.data_as(C.c_void_p),
+                      C.byref(params), result if on_device else C.byref(result), C.c_int32(on_device),
+                      *[_d(b) if b is not None else None for b in model_images]))
+        return result
+
     def Track(self, stream, depth_scaling, depth_buffer, normals_buffer, global_T_pred, params=None, model_depth=None,
               model_normal=None):
         """Not in the reference: frame-to-model ICP of a preprocessed frame (depth u16, normals float2, as Integrate
         takes them) against the map rendered at the predicted pose (smx_recon_track).  params: a TrackParams
         (TrackParams.defaults()).  model_depth / model_normal (float / float4 CUDABuffer, optional) receive the model
         images.  Synchronous; returns a TrackOutcome.  Changes no map state."""
-        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
-        p = params if params is not None else TrackParams.defaults()
-        res = TrackResult()
-        _lib.check(_lib.load().smx_recon_track(
-            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer),
-            T.ctypes.data_as(C.c_void_p), C.byref(p), C.byref(res), C.c_int32(0),
-            _d(model_depth) if model_depth is not None else None,
-            _d(model_normal) if model_normal is not None else None))
-        return TrackOutcome(res)
+        return TrackOutcome(self._track(_lib.load().smx_recon_track, stream, depth_scaling, (depth_buffer, normals_buffer),
+                                        global_T_pred, params if params is not None else TrackParams.defaults(),
+                                        TrackResult(), (model_depth, model_normal)))
 
     def TrackAsync(self, stream, depth_scaling, depth_buffer, normals_buffer, global_T_pred, params, result_buffer,
                    model_depth=None, model_normal=None):
         """The same call with the smx_track_result left in device memory (result_buffer: a CUDABuffer of at least
         ctypes.sizeof(TrackResult) bytes in one row, or a device pointer): nothing waits for the host."""
-        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
-        ptr = result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer)
-        _lib.check(_lib.load().smx_recon_track(
-            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer),
-            T.ctypes.data_as(C.c_void_p), C.byref(params), C.c_void_p(ptr), C.c_int32(1),
-            _d(model_depth) if model_depth is not None else None,
-            _d(model_normal) if model_normal is not None else None))
-
-    def debug_track_iterations(self, stream=None):
-        """One dict per iteration of the last Track call (smx_recon_debug_track_iterations): level, stride, status,
-        sums (31 float64: JtJ upper triangle, Jtr, sum r^2, inliers, pixels with depth, associated), x (6)."""
-        recs = (TrackIteration * 96)()
-        n = C.c_int32(0)
-        _lib.check(_lib.load().smx_recon_debug_track_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
-        return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
-                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
+        self._track(_lib.load().smx_recon_track, stream, depth_scaling, (depth_buffer, normals_buffer), global_T_pred, params,
+                    result_buffer, (model_depth, model_normal))
 
     def TrackRGBD(self, stream, depth_scaling, depth_buffer, normals_buffer, color_buffer, global_T_pred, params=None,
                   model_depth=None, model_normal=None, model_photo=None):
         """Track with a photometric term (smx_recon_track_rgbd): color_buffer is the frame's uchar3 colour image as
         Integrate takes it, params a TrackRGBDParams (TrackRGBDParams.defaults()), model_photo (float4 CUDABuffer,
         optional) receives P = (L, gx, gy, valid).  Synchronous; returns a TrackRGBDOutcome.  Changes no map state."""
-        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
-        p = params if params is not None else TrackRGBDParams.defaults()
-        res = TrackRGBDResult()
-        _lib.check(_lib.load().smx_recon_track_rgbd(
-            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer), _d(color_buffer),
-            T.ctypes.data_as(C.c_void_p), C.byref(p), C.byref(res), C.c_int32(0),
-            _d(model_depth) if model_depth is not None else None,
-            _d(model_normal) if model_normal is not None else None,
-            _d(model_photo) if model_photo is not None else None))
-        return TrackRGBDOutcome(res)
+        return TrackRGBDOutcome(self._track(_lib.load().smx_recon_track_rgbd, stream, depth_scaling,
+                                            (depth_buffer, normals_buffer, color_buffer), global_T_pred,
+                                            params if params is not None else TrackRGBDParams.defaults(), TrackRGBDResult(),
+                                            (model_depth, model_normal, model_photo)))
 
     def TrackRGBDAsync(self, stream, depth_scaling, depth_buffer, normals_buffer, color_buffer, global_T_pred, params,
                        result_buffer, model_depth=None, model_normal=None, model_photo=None):
         """The same call with the smx_track_rgbd_result left in device memory (result_buffer: a CUDABuffer of at least
         ctypes.sizeof(TrackRGBDResult) bytes in one row, or a device pointer): nothing waits for the host."""
-        T = np.ascontiguousarray(np.asarray(global_T_pred, np.float32).reshape(12))
-        ptr = result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer)
-        _lib.check(_lib.load().smx_recon_track_rgbd(
-            self._h, _sv(stream), C.c_float(depth_scaling), _d(depth_buffer), _d(normals_buffer), _d(color_buffer),
-            T.ctypes.data_as(C.c_void_p), C.byref(params), C.c_void_p(ptr), C.c_int32(1),
-            _d(model_depth) if model_depth is not None else None,
-            _d(model_normal) if model_normal is not None else None,
-            _d(model_photo) if model_photo is not None else None))
+        self._track(_lib.load().smx_recon_track_rgbd, stream, depth_scaling, (depth_buffer, normals_buffer, color_buffer),
+                    global_T_pred, params, result_buffer, (model_depth, model_normal, model_photo))
+
+    def _track_iterations(self, fn, record_type, stream):
+        recs = (record_type * 96)()
+        n = C.c_int32(0)
+        _lib.check(fn(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
+        return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
+                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
+
+    def debug_track_iterations(self, stream=None):
+        """One dict per iteration of the last Track call (smx_recon_debug_track_iterations): level, stride, status,
+        sums (31 float64: JtJ upper triangle, Jtr, sum r^2, inliers, pixels with depth, associated), x (6)."""
+        return self._track_iterations(_lib.load().smx_recon_debug_track_iterations, TrackIteration, stream)
 
     def debug_track_rgbd_iterations(self, stream=None):
         """One dict per iteration of the last TrackRGBD call (smx_recon_debug_track_rgbd_iterations): as
         debug_track_iterations with 33 sums ([31] sum e^2, [32] photometric inliers)."""
-        recs = (TrackRGBDIteration * 96)()
-        n = C.c_int32(0)
-        _lib.check(_lib.load().smx_recon_debug_track_rgbd_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
-        return [{"level": r.level, "stride": r.stride, "status": r.status, "sums": np.array(r.sums, np.float64),
-                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
+        return self._track_iterations(_lib.load().smx_recon_debug_track_rgbd_iterations, TrackRGBDIteration, stream)
 
     def ExportVertices(self, stream, position_buffer, color_buffer):
         _lib.check(_lib.load().smx_recon_export_vertices(self._h, _sv(stream), _d(position_buffer), _d(color_buffer)))

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "smx_recon_state.hpp"
 #include "smx_track.hpp"
@@ -594,11 +595,13 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   return SMX_OK;
 }
 
-// smx_recon_track (q == nullptr: result is an smx_track_result) and smx_recon_track_rgbd (result an smx_track_rgbd_result).
+// smx_recon_track (q, color, result_rgbd and model_photo_out null) and smx_recon_track_rgbd (p = &q->icp, result =
+// &result_rgbd->icp).
 static int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                      const smx_buffer_desc* normals, const smx_buffer_desc* color, const float global_T_pred[12],
-                      const smx_track_params* params, const smx_track_rgbd_params* q, void* result, int32_t result_on_device,
-                      const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
+                      const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
+                      smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
+                      const smx_buffer_desc* model_normal_out, const smx_buffer_desc* color,
+                      const smx_track_rgbd_params* q, smx_track_rgbd_result* result_rgbd,
                       const smx_buffer_desc* model_photo_out) {
   SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
                 result != nullptr);
@@ -645,19 +648,16 @@ static int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_
     DevBuf<float> depth_img; DevBuf<float4> normal_img; DevBuf<double> slabs; DevBuf<TrackDev> state;
     SMX_CALL(depth_img.alloc(px, false));
     SMX_CALL(normal_img.alloc(px, false));
-    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackSlabStride, false));
+    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackRgbdSlabStride, false));
     SMX_CALL(state.alloc(1, false));
     r->trk_depth = std::move(depth_img); r->trk_normal = std::move(normal_img);
     r->trk_slabs = std::move(slabs); r->trk_state = std::move(state);
   }
-  if (q && !r->trk_rgbd_state.get()) {   // (likewise)
-    DevBuf<uint32_t> color_img; DevBuf<float4> photo_img; DevBuf<double> slabs; DevBuf<TrackRgbdDev> state;
+  if (q && !r->trk_photo.get()) {   // (both or none, likewise)
+    DevBuf<uint32_t> color_img; DevBuf<float4> photo_img;
     SMX_CALL(color_img.alloc(px, false));
     SMX_CALL(photo_img.alloc(px, false));
-    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackRgbdSlabStride, false));
-    SMX_CALL(state.alloc(1, false));
     r->trk_color = std::move(color_img); r->trk_photo = std::move(photo_img);
-    r->trk_rgbd_slabs = std::move(slabs); r->trk_rgbd_state = std::move(state);
   }
   if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
   // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
@@ -681,27 +681,21 @@ static int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_
                              hipMemcpyDeviceToDevice, st));
   TrackBuffers tb;
   tb.model_depth = r->trk_depth.get(); tb.model_normal = r->trk_normal.get(); tb.slabs = r->trk_slabs.get(); tb.state = r->trk_state.get();
-  if (!q) {
-    SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
-                           result_on_device ? (smx_track_result*)result : nullptr));
-  } else {
-    TrackRgbdBuffers rb;
-    rb.icp = tb; rb.model_color = r->trk_color.get(); rb.model_photo = r->trk_photo.get();
-    rb.slabs = r->trk_rgbd_slabs.get(); rb.state = r->trk_rgbd_state.get();
-    SMX_CALL(track_rgbd_enqueue(st, rb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, color,
-                                global_T_pred, *q, result_on_device ? (smx_track_rgbd_result*)result : nullptr));
-    if (photo && model_photo_out) {
-      const size_t row = (size_t)r->W * sizeof(float4);
-      SMX_HIP(hipMemcpy2DAsync(model_photo_out->address, model_photo_out->pitch, r->trk_photo.get(), row, row, (size_t)r->H,
-                               hipMemcpyDeviceToDevice, st));
-    }
+  tb.model_color = r->trk_color.get(); tb.model_photo = r->trk_photo.get();
+  SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
+                         result_on_device && !q ? result : nullptr, color, q, result_on_device ? result_rgbd : nullptr));
+  if (photo && model_photo_out) {
+    const size_t row = (size_t)r->W * sizeof(float4);
+    SMX_HIP(hipMemcpy2DAsync(model_photo_out->address, model_photo_out->pitch, r->trk_photo.get(), row, row, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
   }
   SMX_HIP(hipEventRecord(r->ev_track, st));
   r->track_busy = true;
   r->track_last_rgbd = q != nullptr;
   if (!result_on_device) {
-    if (q) SMX_HIP(hipMemcpyAsync(result, &r->trk_rgbd_state.get()->result, sizeof(smx_track_rgbd_result), hipMemcpyDeviceToHost, st));
-    else SMX_HIP(hipMemcpyAsync(result, &r->trk_state.get()->result, sizeof(smx_track_result), hipMemcpyDeviceToHost, st));
+    const smx_track_rgbd_result* res = &r->trk_state.get()->result;
+    if (q) SMX_HIP(hipMemcpyAsync(result_rgbd, res, sizeof(*res), hipMemcpyDeviceToHost, st));
+    else SMX_HIP(hipMemcpyAsync(result, &res->icp, sizeof(res->icp), hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
   return SMX_OK;
@@ -711,8 +705,8 @@ int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_bu
                     const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
                     smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
                     const smx_buffer_desc* model_normal_out) {
-  return track_call(r, s, depth_scaling, depth, normals, nullptr, global_T_pred, params, nullptr, result, result_on_device,
-                    model_depth_out, model_normal_out, nullptr);
+  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, params, result, result_on_device, model_depth_out,
+                    model_normal_out, nullptr, nullptr, nullptr, nullptr);
 }
 
 int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
@@ -721,35 +715,12 @@ int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling, const s
                          const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
                          const smx_buffer_desc* model_photo_out) {
   SMX_CHECK_ARG(params != nullptr);
-  return track_call(r, s, depth_scaling, depth, normals, color, global_T_pred, &params->icp, params, result, result_on_device,
-                    model_depth_out, model_normal_out, model_photo_out);
+  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, &params->icp, result ? &result->icp : nullptr,
+                    result_on_device, model_depth_out, model_normal_out, color, params, result, model_photo_out);
 }
 
-int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
-                                          int32_t* count) {
-  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  *count = 0;
-  if (!r->trk_rgbd_state.get() || !r->track_busy || !r->track_last_rgbd) return SMX_OK;
-  SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
-  int32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  n = std::max(0, std::min(n, (int32_t)kTrackRing));
-  const int32_t m = std::min(n, capacity);
-  if (m > 0) {
-    SMX_HIP(hipMemcpyAsync(records, r->trk_rgbd_state.get()->ring, sizeof(smx_track_rgbd_iteration) * (size_t)m,
-                           hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  *count = n;
-  return SMX_OK;
-}
-
-int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
-                                     int32_t* count) {
-  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+// The records of the last tracking call, the first *count of them (at most kTrackRing) copied into recs.
+static int track_records(smx_recon r, smx_stream s, smx_track_rgbd_iteration* recs, int32_t* count) {
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
   *count = 0;
@@ -759,12 +730,38 @@ int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iterat
   SMX_HIP(hipMemcpyAsync(&n, &r->trk_state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   n = std::max(0, std::min(n, (int32_t)kTrackRing));
-  const int32_t m = std::min(n, capacity);
-  if (m > 0) {
-    SMX_HIP(hipMemcpyAsync(records, r->trk_state.get()->ring, sizeof(smx_track_iteration) * (size_t)m, hipMemcpyDeviceToHost, st));
+  if (n > 0) {
+    SMX_HIP(hipMemcpyAsync(recs, r->trk_state.get()->ring, sizeof(smx_track_rgbd_iteration) * (size_t)n, hipMemcpyDeviceToHost, st));
     SMX_HIP(hipStreamSynchronize(st));
   }
   *count = n;
+  return SMX_OK;
+}
+
+int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
+                                          int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  *count = 0;
+  if (!r->track_last_rgbd) return SMX_OK;
+  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
+  SMX_CALL(track_records(r, s, recs.data(), count));
+  std::copy_n(recs.begin(), std::min(*count, capacity), records);
+  return SMX_OK;
+}
+
+// (the same records without their last two sums, which a call without colour leaves 0)
+int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
+                                     int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
+  SMX_CALL(track_records(r, s, recs.data(), count));
+  for (int32_t i = 0; i < std::min(*count, capacity); ++i) {
+    const smx_track_rgbd_iteration& f = recs[i];
+    smx_track_iteration& t = records[i];
+    t.level = f.level; t.stride = f.stride; t.status = f.status; t.reserved = f.reserved;
+    std::copy_n(f.sums, SMX_TRACK_SUMS, t.sums);
+    std::copy_n(f.x, 6, t.x);
+  }
   return SMX_OK;
 }
 

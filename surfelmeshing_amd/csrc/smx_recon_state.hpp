@@ -12,7 +12,6 @@
 namespace smx {
 
 struct TrackDev;        // smx_track.hpp
-struct TrackRgbdDev;
 struct MeshWorkspace;   // smx_mesh.hpp
 
 // Attribute ids = the reference's SoA row numbers, APP/cuda_surfel_reconstruction_kernels.cuh:49-78 (the
@@ -307,17 +306,15 @@ struct smx_recon_s {
   smx::DevBuf<unsigned long long> zbuf;   // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
   hipEvent_t ev_render;                   // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
   bool render_busy;
-  smx::DevBuf<float> trk_depth;         // smx_recon_track (allocated by its first call, all four or none): the model images [H][W]
-  smx::DevBuf<float4> trk_normal;       // of the last call, the reduce kernel's per-workgroup partial sums, the call's device state,
-  smx::DevBuf<double> trk_slabs;        // and the mark after the last call's kernels (the next call, on whatever stream, waits for it)
-  smx::DevBuf<smx::TrackDev> trk_state;
+  smx::DevBuf<float> trk_depth;         // smx_recon_track / _rgbd (allocated by the first call of either, all four or none): the model
+  smx::DevBuf<float4> trk_normal;       // images [H][W] of the last call, the reduce kernel's per-workgroup partial sums, the call's
+  smx::DevBuf<double> trk_slabs;        // device state (records and result of either kind), and the mark after the last call's kernels
+  smx::DevBuf<smx::TrackDev> trk_state; // (the next call, on whatever stream, waits for it)
   hipEvent_t ev_track;
   bool track_busy;
-  smx::DevBuf<uint32_t> trk_color;        // smx_recon_track_rgbd (allocated by its first call, all four or none): the model colour
-  smx::DevBuf<float4> trk_photo;          // image [H][W] and P = (L, gx, gy, valid) of the last call with a weight, the 33-sum slabs,
-  smx::DevBuf<double> trk_rgbd_slabs;     // the records and the result with colour; ordered by ev_track like the four above
-  smx::DevBuf<smx::TrackRgbdDev> trk_rgbd_state;
-  bool track_last_rgbd;                   // the last tracking call was smx_recon_track_rgbd (whose records trk_rgbd_state holds)
+  smx::DevBuf<uint32_t> trk_color;      // smx_recon_track_rgbd (allocated by its first call, both or none): the model colour image
+  smx::DevBuf<float4> trk_photo;        // [H][W] and P = (L, gx, gy, valid) of the last call with a weight
+  bool track_last_rgbd;                 // the last tracking call was smx_recon_track_rgbd
   smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging  // smx_recon_decimate_mesh (each grows on demand, the call is synchronous, so nothing reads a block that goes)
   smx::DevBuf<uint32_t> dec_vmap;                  // [n] the vertex map
   smx::DevBuf<unsigned long long> dec_cells;       // [cell table entries][2]: key, value word (smx::DecCell)

@@ -124,7 +124,7 @@ def sized(smx, request):
     return _grown(smx, w, h, obstacle_until=8)
 
 
-@pytest.mark.parametrize("stride", [1, 2, 4])
+@pytest.mark.parametrize("stride", [1, 2, 4, 8])
 def test_one_iteration_matches_the_restatement(smx, sized, stride):
     """From the identity (record 0) and from a perturbed T_rel (record 1: the pose the first iteration left) of a
     (stride, 1), (stride, 1) schedule, for predictions 1, 3 and 5 frames old."""

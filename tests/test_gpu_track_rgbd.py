@@ -100,7 +100,7 @@ def test_model_photo_is_the_restatement_of_the_gpus_own_renders(smx, sized):
 
 
 # ---- 2. one iteration ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("stride", [1, 2, 4])
+@pytest.mark.parametrize("stride", [1, 2, 4, 8])
 def test_one_iteration_matches_the_restatement(smx, sized, stride):
     """From the identity (record 0) and from a perturbed T_rel (record 1) of a (stride, 1), (stride, 1) schedule, for
     predictions 1, 3 and 5 frames old: all 33 sums."""

@@ -1,7 +1,8 @@
-"""The arithmetic of smx_track.hip without a GPU: the body of k_track_reduce and the solve / exponential code are plain
-C++, so this test compiles them for the host (one lane per workgroup, cross-lane shifts that add nothing, the project's
--ffp-contract=off) and compares them with the float64 restatement of tests/track_ref.py on the oracle's map -- the same
-comparison tests/test_gpu_track.py makes on the device, with the same derived bound."""
+"""The arithmetic of smx_track.hip without a GPU: smx_track.hpp holds the per-pixel work, the accumulation order, the solve
+and the exponential as plain inline functions, so this test compiles them for the host with the project's
+-ffp-contract=off, drives them the way k_track_reduce / k_track_solve do (one lane that visits every sampled pixel in index
+order, so the cross-lane sums have nothing to add) and compares them with the float64 restatement of tests/track_ref.py on
+the oracle's map -- the same comparison tests/test_gpu_track.py makes on the device, with the same derived bound."""
 import ctypes as C
 import os
 import subprocess
@@ -16,77 +17,96 @@ from test_track_api import oracle_map
 SRC = os.path.join(ROOT, "surfelmeshing_amd", "csrc")
 U = 2.0 ** -24
 
-PRELUDE = r'''
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-#include "smx.h"
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __shared__ static
-#define __syncthreads()
-#define __launch_bounds__(x)
-struct float2 { float x, y; };
-struct float4 { float x, y, z, w; };
-struct Idx { unsigned x; };
-static Idx blockIdx{0}, threadIdx{0}, gridDim{1};
-template <typename T> static T __shfl_down(T, int, int) { return T(0); }   // (the other lanes hold nothing)
-constexpr int kTrackRing = 96, kTrackBlock = 1, kTrackSlabStride = 32;   // (one lane visits every pixel)
-enum { kSumRR = 27, kSumInliers = 28, kSumPixels = 29, kSumAssociated = 30 };
-template <typename T> struct Img {
-  T* address; int32_t height; int32_t width; size_t pitch;
-  T& operator()(int y, int x) const {
-    return *reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(address) + (size_t)y * pitch + (size_t)x * sizeof(T)); }
-};
-'''
-
 HARNESS = r'''
-extern "C" void host_reduce(int stride, int W, int H, float fx, float fy, float cx, float cy, float ds, float maxd2,
-                            float cosang, uint16_t* depth, float* normals, const float* D, const float* M, const float* Tf,
-                            double* slab) {
-  static TrackDev st; st.status = 0; st.converged_level = -1;
-  for (int i = 0; i < 12; ++i) st.Tf[i] = Tf[i];
-  TrackK k; k.W = W; k.H = H; const int s = stride;
-  k.sw = W > s / 2 ? (W - s / 2 + s - 1) / s : 0; k.sh = H > s / 2 ? (H - s / 2 + s - 1) / s : 0;
-  k.fx = fx; k.fy = fy; k.cx = cx; k.cy = cy; k.depth_scaling = ds; k.max_distance_sq = maxd2; k.cos_max_angle = cosang;
-  Img<uint16_t> d{depth, H, W, (size_t)W * 2}; Img<float2> n{(float2*)normals, H, W, (size_t)W * 8};
-  // lane 0 visits every pixel and leaves the sums in the (static) LDS row; run as lane j, the kernel stores entry j
-  for (unsigned j = 0; j < SMX_TRACK_SUMS; ++j) {
-    threadIdx.x = j;
-    if (s == 1) k_track_reduce<1>(k, d, n, D, (const float4*)M, &st, 0, slab);
-    else if (s == 2) k_track_reduce<2>(k, d, n, D, (const float4*)M, &st, 0, slab);
-    else if (s == 4) k_track_reduce<4>(k, d, n, D, (const float4*)M, &st, 0, slab);
-    else k_track_reduce<8>(k, d, n, D, (const float4*)M, &st, 0, slab);
+#define SMX_TRACK_HOST_ONLY 1
+#include "smx_track.hpp"
+using namespace smx;
+
+// One reduce launch as a single lane: slab = the 28 float sums, the three counts, sum e^2, the photometric inliers.  As
+// track_enqueue, weight 0 (or no colour at all) runs the instantiation without the photometric term.
+template <bool kPhoto>
+static void reduce(const TrackK& k, const TrackPhotoK& ph, int stride, const float* T, const uint16_t* depth,
+                   const float2* normals, const unsigned char* color, const float* D, const float4* M, const float4* P,
+                   double* slab) {
+  double acc[28] = {0.0}, acc_ee = 0.0;
+  uint32_t n_in = 0, n_px = 0, n_as = 0, n_ph = 0;
+  for (int i = 0; i < k.sw * k.sh; ++i) {
+    const int sy = i / k.sw, sx = i - sy * k.sw;
+    const int x = stride / 2 + sx * stride, y = stride / 2 + sy * stride;
+    const size_t at = (size_t)y * k.W + x;
+    track_pixel<kPhoto>(k, ph, T, x, y, depth[at], normals + at, kPhoto ? color + 3 * at : nullptr, D, M, P, acc, acc_ee,
+                        n_in, n_px, n_as, n_ph);
   }
+  for (int e = 0; e < 28; ++e) slab[e] = acc[e];
+  slab[kSumInliers] = n_in; slab[kSumPixels] = n_px; slab[kSumAssociated] = n_as;
+  if (kPhoto) { slab[kSumEE] = acc_ee; slab[kSumPhotoInliers] = n_ph; }
+}
+extern "C" void host_reduce(int stride, int W, int H, float fx, float fy, float cx, float cy, float ds, float maxd2,
+                            float cosang, float weight, float maxe, float ming2, const uint16_t* depth, const float* normals,
+                            const unsigned char* color, const float* D, const float* M, const float* P, const float* Tf,
+                            double* slab) {
+  TrackK k; k.W = W; k.H = H; k.sw = track_samples(W, stride); k.sh = track_samples(H, stride);
+  k.fx = fx; k.fy = fy; k.cx = cx; k.cy = cy; k.depth_scaling = ds; k.max_distance_sq = maxd2; k.cos_max_angle = cosang;
+  TrackPhotoK ph; ph.weight = weight; ph.max_intensity_difference = maxe; ph.min_gradient_sq = ming2;
+  if (weight != 0.0f) reduce<true>(k, ph, stride, Tf, depth, (const float2*)normals, color, D, (const float4*)M, (const float4*)P, slab);
+  else reduce<false>(k, ph, stride, Tf, depth, (const float2*)normals, nullptr, D, (const float4*)M, nullptr, slab);
+}
+extern "C" void host_prepare(int W, int H, float step, const float* D, const uint32_t* Cm, float* P) {
+  for (long long i = 0; i < (long long)W * H; ++i) ((float4*)P)[i] = track_photo_pixel(W, H, step, D, Cm, i);
+}
+static TrackSolveK solve_k(int photo, int min_inliers, double pivot, double cr, double ct) {
+  TrackSolveK k; k.level = 0; k.stride = 1; k.n_slabs = 1; k.final_launch = 1; k.min_inliers = min_inliers; k.photo = photo;
+  k.min_inlier_fraction = 0; k.min_pivot_ratio = pivot; k.convergence_rotation = cr; k.convergence_translation = ct;
+  for (int i = 0; i < 12; ++i) k.pred[i] = (i == 0 || i == 5 || i == 10) ? 1.0 : 0.0;
+  return k;
 }
 extern "C" int host_solve(const double* S, int min_inliers, double pivot, double cr, double ct, const float* Tf_in,
                           double* x, double* Tout) {
-  static TrackDev st; TrackSolveK k; k.min_inliers = min_inliers; k.min_inlier_fraction = 0; k.min_pivot_ratio = pivot;
-  k.convergence_rotation = cr; k.convergence_translation = ct;
+  static TrackDev st;
+  const TrackSolveK k = solve_k(0, min_inliers, pivot, cr, ct);
   for (int i = 0; i < 12; ++i) { st.Tf[i] = Tf_in[i]; st.T_rel[i] = Tf_in[i]; }
   const int s = track_solve_one(S, k, &st, x);
   for (int i = 0; i < 12; ++i) Tout[i] = st.T_rel[i];
   return s;
 }
+// Lane 0 of one k_track_solve launch with colour (the final one of a call) on one slab; returns the status, fills the
+// record and the result.
+extern "C" int host_solve_rgbd(const double* slab, int min_inliers, double pivot, double cr, double ct, const float* Tf_in,
+                               smx_track_rgbd_iteration* rec, smx_track_rgbd_result* res) {
+  static TrackDev st;
+  st.status = 0; st.converged_level = -1; st.iterations_run = 0;
+  for (int i = 0; i < 12; ++i) { st.Tf[i] = Tf_in[i]; st.T_rel[i] = Tf_in[i]; st.T_prev[i] = Tf_in[i]; }
+  const TrackSolveK k = solve_k(1, min_inliers, pivot, cr, ct);
+  double S[SMX_TRACK_RGBD_SUMS];
+  for (int i = 0; i < SMX_TRACK_RGBD_SUMS; ++i) S[i] = 0.0 + slab[i];
+  track_solve_step(S, k, &st);
+  track_finish(k, &st);
+  *rec = st.ring[0]; *res = st.result;
+  return st.status;
+}
 '''
 
 
 def _host_library(tmp_path):
-    hip = open(os.path.join(SRC, "smx_track.hip")).read()
-    hpp = open(os.path.join(SRC, "smx_track.hpp")).read()
-    state = hpp[hpp.index("struct TrackDev {"):hpp.index("struct TrackBuffers")]
-    kernels = hip[hip.index("struct TrackK {"):hip.index("__global__ void __launch_bounds__(64)")]
-    kernels = kernels.replace("kTrackBlock / 64", "1")      # (one wavefront row of LDS)
-    assert "k_track_reduce" in kernels and "track_solve_one" in kernels and "se3_exp" in kernels
     src = tmp_path / "track_host.cpp"
-    src.write_text(PRELUDE + state + kernels + HARNESS)
+    src.write_text(HARNESS)
     lib = tmp_path / "libtrack_host.so"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
-                        str(src), "-o", str(lib)], capture_output=True, text=True)
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", SRC,
+                        "-I", os.path.join(ROOT, "include"), str(src), "-o", str(lib)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return C.CDLL(str(lib))
+
+
+def host_reduce(L, s, stride, gates, Tf, depth, normals, D, M, photo=None):
+    """The 40-double slab of one reduce launch on the host; photo = (weight, max_intensity_difference, min_gradient_sq,
+    color, P) or None for the geometric kernel."""
+    weight, maxe, ming2, color, P = photo if photo is not None else (0.0, 0.0, 0.0, None, None)
+    slab = np.zeros(40)
+    L.host_reduce(stride, s.width, s.height, C.c_float(s.fx), C.c_float(s.fy), C.c_float(s.cx), C.c_float(s.cy),
+                  C.c_float(s.depth_scaling), C.c_float(gates[0]), C.c_float(gates[1]), C.c_float(weight), C.c_float(maxe),
+                  C.c_float(ming2), _ptr(depth), _ptr(normals), _ptr(color) if color is not None else None, _ptr(D), _ptr(M),
+                  _ptr(P) if P is not None else None, _ptr(Tf), _ptr(slab))
+    return slab
 
 
 def _sum_bounds(inliers, flagged, B, max_distance):
@@ -101,6 +121,14 @@ def _sum_bounds(inliers, flagged, B, max_distance):
     out[21:27] = inliers * 64 * U * B * c + 2 * flagged * c * max_distance
     out[27] = inliers * 64 * U * B * max_distance + 2 * flagged * max_distance ** 2
     return out
+
+
+# Per stride: the inlier floor under which the comparison would mean little, the floor of photometric inliers (for
+# tests/test_track_rgbd_kernel_host.py), and the min_inliers the solve is asked with.  Stride 8 leaves 20 x 15 samples of the
+# 160x120 frame, a quarter of stride 4's, and the restatement finds 23 to 132 inliers among them: too few for the default
+# min_inliers of 50, so stride 8 runs with the floors tests/test_gpu_track.py and tests/test_gpu_track_rgbd.py use for all
+# their strides (min_inliers = 10, inliers >= min_inliers, photometric inliers > 0).
+FLOORS = {1: (90, 20, 50), 2: (90, 20, 50), 4: (90, 20, 50), 8: (10, 0, 10)}
 
 
 def _ptr(a):
@@ -123,20 +151,18 @@ def test_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_path):
         normals = np.ascontiguousarray(np.asarray(po.normals).reshape(s.height, s.width, 2), np.float32)
         T1 = tr.se3_exp([0.001, 0.027 * (g - 11), 0.0005, 0.003, -0.002, 0.004])
         for T in (tr.IDENTITY, T1):
-            for stride in (1, 2, 4):
+            for stride in (1, 2, 4, 8):
                 _, _, _, inl, pix, mg = tr.iteration(D, M, depth, normals, intr, T, stride, p.gates(), s.depth_scaling)
-                slab = np.zeros(32)
                 Tf = np.ascontiguousarray(T, np.float32)
-                L.host_reduce(stride, s.width, s.height, C.c_float(s.fx), C.c_float(s.fy), C.c_float(s.cx),
-                              C.c_float(s.cy), C.c_float(s.depth_scaling), C.c_float(g2), C.c_float(ca), _ptr(depth),
-                              _ptr(normals), _ptr(D), _ptr(M), _ptr(Tf), _ptr(slab))
-                assert inl >= 90 and mg["flagged"] <= 0.01 * pix
+                slab = host_reduce(L, s, stride, (g2, ca), Tf, depth, normals, D, M)
+                assert inl >= FLOORS[stride][0] and mg["flagged"] <= 0.01 * pix
                 assert slab[tr.S_PIXELS] == pix
                 assert abs(slab[tr.S_ASSOCIATED] - mg["associated"]) <= mg["flagged"]
                 assert abs(slab[tr.S_INLIERS] - inl) <= mg["flagged"]
                 bound = _sum_bounds(inl, mg["flagged"], max(mg["p_max"], 1.0), p.max_distance)
                 assert np.all(np.abs(slab[:28] - mg["sums"][:28]) <= bound), (g, stride)
                 # the solve: status, twist and new pose against the restatement's, from the same sums
+                p.min_inliers = FLOORS[stride][2]
                 status, x, Tn = tr.solve(mg["sums"], T, p)
                 S = (C.c_double * 31)(*mg["sums"])
                 xo, To = (C.c_double * 6)(), (C.c_double * 12)()

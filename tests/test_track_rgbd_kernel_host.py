@@ -1,88 +1,19 @@
-"""The arithmetic of the kernels of smx_recon_track_rgbd without a GPU, in the manner of tests/test_track_kernel_host.py:
-k_track_photo_prepare, the body of k_track_reduce_rgbd and k_track_solve_rgbd are plain C++, compiled here for the host
-(one lane per workgroup, cross-lane shifts that add nothing, -ffp-contract=off).  The prepare output must equal the float32
-restatement of tests/track_rgbd_ref.py bit for bit; the 33 sums stay within the bound derived there and in
+"""The arithmetic of the kernels of smx_recon_track_rgbd without a GPU, in the manner of tests/test_track_kernel_host.py and
+through its host library: track_photo_pixel, track_pixel<true> and the solve with colour, the inline functions of
+smx_track.hpp that k_track_photo_prepare, k_track_reduce_rgbd and k_track_solve call.  The prepare output must equal the
+float32 restatement of tests/track_rgbd_ref.py bit for bit; the 33 sums stay within the bound derived there and in
 tests/test_gpu_track.py -- the comparison tests/test_gpu_track_rgbd.py makes on the device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import track_ref as tr
 import track_rgbd_ref as trr
 import viz_ref as vr
-from common import ROOT, small_stream
+from common import small_stream
 from test_track_api import oracle_map
-from test_track_kernel_host import PRELUDE, _ptr, _sum_bounds
+from test_track_kernel_host import FLOORS, _host_library, _ptr, _sum_bounds, host_reduce
 from test_track_rgbd_api import frame_color
-
-SRC = os.path.join(ROOT, "surfelmeshing_amd", "csrc")
-
-PRELUDE_RGBD = PRELUDE + r'''
-struct uchar3 { unsigned char x, y, z; };
-static inline float4 make_float4(float x, float y, float z, float w) { float4 v; v.x = x; v.y = y; v.z = z; v.w = w; return v; }
-'''
-
-HARNESS = r'''
-extern "C" void host_prepare(int W, int H, float step, const float* D, const uint32_t* Cm, float* P) {
-  threadIdx.x = 0;
-  for (unsigned i = 0; i < (unsigned)(W * H); ++i) { blockIdx.x = i; k_track_photo_prepare(W, H, step, D, Cm, (float4*)P); }
-  blockIdx.x = 0;
-}
-extern "C" void host_reduce_rgbd(int stride, int W, int H, float fx, float fy, float cx, float cy, float ds, float maxd2,
-                                 float cosang, float weight, float maxe, float ming2, uint16_t* depth, float* normals,
-                                 unsigned char* color, const float* D, const float* M, const float* P, const float* Tf,
-                                 double* slab) {
-  static TrackDev st; st.status = 0; st.converged_level = -1;
-  for (int i = 0; i < 12; ++i) st.Tf[i] = Tf[i];
-  TrackK k; k.W = W; k.H = H; const int s = stride;
-  k.sw = W > s / 2 ? (W - s / 2 + s - 1) / s : 0; k.sh = H > s / 2 ? (H - s / 2 + s - 1) / s : 0;
-  k.fx = fx; k.fy = fy; k.cx = cx; k.cy = cy; k.depth_scaling = ds; k.max_distance_sq = maxd2; k.cos_max_angle = cosang;
-  TrackPhotoK ph; ph.weight = weight; ph.max_intensity_difference = maxe; ph.min_gradient_sq = ming2;
-  Img<uint16_t> d{depth, H, W, (size_t)W * 2}; Img<float2> n{(float2*)normals, H, W, (size_t)W * 8};
-  Img<uchar3> c{(uchar3*)color, H, W, (size_t)W * 3};
-  for (unsigned j = 0; j < SMX_TRACK_RGBD_SUMS; ++j) {   // (as lane j the kernel stores entry j of what lane 0 left in LDS)
-    threadIdx.x = j;
-    if (s == 1) k_track_reduce_rgbd<1>(k, ph, d, n, c, D, (const float4*)M, (const float4*)P, &st, 0, slab);
-    else if (s == 2) k_track_reduce_rgbd<2>(k, ph, d, n, c, D, (const float4*)M, (const float4*)P, &st, 0, slab);
-    else if (s == 4) k_track_reduce_rgbd<4>(k, ph, d, n, c, D, (const float4*)M, (const float4*)P, &st, 0, slab);
-    else k_track_reduce_rgbd<8>(k, ph, d, n, c, D, (const float4*)M, (const float4*)P, &st, 0, slab);
-  }
-  threadIdx.x = 0;
-}
-// One k_track_solve_rgbd launch (the final one of a call) on one slab; returns the status, fills the record and the result.
-extern "C" int host_solve_rgbd(const double* slab, int min_inliers, double pivot, double cr, double ct, const float* Tf_in,
-                               smx_track_rgbd_iteration* rec, smx_track_rgbd_result* res) {
-  static TrackDev st; static TrackRgbdDev rst;
-  st.status = 0; st.converged_level = -1; st.iterations_run = 0;
-  for (int i = 0; i < 12; ++i) { st.Tf[i] = Tf_in[i]; st.T_rel[i] = Tf_in[i]; st.T_prev[i] = Tf_in[i]; }
-  TrackSolveK k; k.level = 0; k.stride = 1; k.n_slabs = 1; k.final_launch = 1; k.min_inliers = min_inliers;
-  k.min_inlier_fraction = 0; k.min_pivot_ratio = pivot; k.convergence_rotation = cr; k.convergence_translation = ct;
-  for (int i = 0; i < 12; ++i) k.pred[i] = (i == 0 || i == 5 || i == 10) ? 1.0 : 0.0;
-  for (int j = SMX_TRACK_RGBD_SUMS - 1; j >= 0; --j) { threadIdx.x = (unsigned)j; k_track_solve_rgbd(k, slab, &st, &rst, res); }
-  *rec = rst.ring[0];
-  return st.status;
-}
-'''
-
-
-def _host_library(tmp_path):
-    hip = open(os.path.join(SRC, "smx_track.hip")).read()
-    hpp = open(os.path.join(SRC, "smx_track.hpp")).read()
-    state = hpp[hpp.index("struct TrackDev {"):hpp.index("struct TrackBuffers")]
-    state += hpp[hpp.index("constexpr int kTrackRgbdSlabStride"):hpp.index("struct TrackRgbdBuffers")]
-    kernels = hip[hip.index("struct TrackK {"):hip.index("template <int STRIDE>\nvoid launch_reduce_rgbd")]
-    kernels = kernels.replace("kTrackBlock / 64", "1")      # (one wavefront row of LDS)
-    for name in ("k_track_photo_prepare", "k_track_reduce_rgbd", "k_track_solve_rgbd", "track_solve_one"):
-        assert name in kernels, name
-    src = tmp_path / "track_rgbd_host.cpp"
-    src.write_text(PRELUDE_RGBD + state + kernels + HARNESS)
-    lib = tmp_path / "libtrack_rgbd_host.so"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
-                        str(src), "-o", str(lib)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return C.CDLL(str(lib))
 
 
 def test_rgbd_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_path):
@@ -110,21 +41,17 @@ def test_rgbd_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_pat
         color = frame_color(s, g)
         T1 = tr.se3_exp([0.001, 0.027 * (g - 11), 0.0005, 0.003, -0.002, 0.004])
         for T in (tr.IDENTITY, T1):
-            for stride in (1, 2, 4):
+            for stride in (8, 1, 2, 4):   # (4 last: the checks after the loops go on from its slabs)
                 Tf = np.ascontiguousarray(T, np.float32)
 
                 def reduce(weight, photo):
-                    slab = np.zeros(40)
-                    L.host_reduce_rgbd(stride, s.width, s.height, C.c_float(s.fx), C.c_float(s.fy), C.c_float(s.cx),
-                                       C.c_float(s.cy), C.c_float(s.depth_scaling), C.c_float(g2), C.c_float(ca),
-                                       C.c_float(weight), C.c_float(p.max_intensity_difference),
-                                       C.c_float(p.min_gradient_sq()), _ptr(depth), _ptr(normals), _ptr(color), _ptr(D),
-                                       _ptr(M), _ptr(P) if photo else None, _ptr(Tf), _ptr(slab))
-                    return slab
+                    return host_reduce(L, s, stride, (g2, ca), Tf, depth, normals, D, M,
+                                       (weight, p.max_intensity_difference, p.min_gradient_sq(), color, P if photo else None))
                 want, mg = trr.iteration(D, M, P, depth, normals, color, intr, T, stride, p, s.depth_scaling)
                 slab = reduce(p.photometric_weight, True)
                 pix, fl = want[tr.S_PIXELS], mg["flagged"]
-                assert fl <= 0.01 * pix and slab[tr.S_PIXELS] == pix and mg["photo"]["inliers"] > 20
+                assert fl <= 0.01 * pix and slab[tr.S_PIXELS] == pix and mg["photo"]["inliers"] > FLOORS[stride][1]
+                assert want[tr.S_INLIERS] >= FLOORS[stride][2]
                 for e in (tr.S_ASSOCIATED, tr.S_INLIERS, trr.S_PHOTO_INLIERS):
                     assert abs(slab[e] - want[e]) <= fl, (g, stride, e)
                 diff, bound = trr.compare_sums(slab, want, mg, p, _sum_bounds)
@@ -133,6 +60,7 @@ def test_rgbd_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_pat
                 geo = reduce(0.0, False)
                 assert np.all(geo[31:33] == 0) and np.any(np.abs(geo[:28] - want[:28]) > bound[:28])
                 # the solve: status, twist, record and result from the kernel's own sums against the restatement's solve
+                p.min_inliers = FLOORS[stride][2]
                 status, x, Tn = trr.solve(slab[:33], T, p)
                 rec, res = TrackRGBDIteration(), TrackRGBDResult()
                 st = L.host_solve_rgbd(_ptr(slab), p.min_inliers, C.c_double(p.min_pivot_ratio),
@@ -144,7 +72,7 @@ def test_rgbd_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_pat
                 assert np.allclose(np.array(res.icp.global_T_frame).reshape(3, 4), Tn, rtol=0, atol=1e-6)
                 assert res.photometric_inliers == slab[32] and res.icp.inliers == slab[tr.S_INLIERS]
                 assert abs(res.rms_intensity_residual - np.sqrt(slab[31] / slab[32])) < 1e-6
-    # weight 0 (P == nullptr) leaves the geometric sums: the restatement's, within the geometric bound alone
+    # weight 0 (the kernel without the term) leaves the geometric sums: the restatement's, within the geometric bound alone
     _, _, _, inl, pix, mg0 = tr.iteration(D, M, depth, normals, intr, T1, 4, p.gates(), s.depth_scaling)
     assert np.all(np.abs(geo[:28] - mg0["sums"][:28]) <= _sum_bounds(inl, mg0["flagged"], max(mg0["p_max"], 1.0), p.max_distance))
     # a non-finite photometric sum is NOT_FINITE before anything is solved

@@ -1,10 +1,13 @@
-"""python tools/isa_compare.py <old tree> <new tree>: is the device code of two checkouts the same, kernel by kernel?
+"""python tools/isa_compare.py <old tree> <new tree> [old=new ...]: is the device code of two checkouts the same, kernel by kernel?
 
 Every file of build.SOURCES is compiled device-only to gfx950 assembly in both trees (the flags of tools/isa_regs.sh).  Per
 kernel: the descriptor's registers, LDS and scratch, and the instruction stream with comments and directives dropped,
 basic-block labels renumbered and symbol names demangled without "(anonymous namespace)::" and "smx::" (the method of
 profiles/recon_split_isa.txt).  Prints one line per kernel and the number that differ; needs no GPU.  A source file the old
-tree does not have yet is compiled in the new tree alone and its kernels are listed as "new"."""
+tree does not have yet is compiled in the new tree alone and its kernels are listed as "new".  Kernels are matched by that
+demangled name without its parameter list, so a parameter type that moved between namespaces is no rename; a kernel that
+was renamed or folded into another is matched through an `old=new` argument (k_track_solve_rgbd=k_track_solve), and where
+the new tree differs both trees' figures are printed."""
 import os
 import re
 import shutil
@@ -56,7 +59,11 @@ def kernels(path):
     return res
 
 
-def main(old, new):
+def by_plain_name(k):
+    return {re.sub(r"\(.*$", "", p).replace("void ", ""): k[n] for n, p in zip(k, demangle(list(k)) if k else [])}
+
+
+def main(old, new, renames):
     tmp = tempfile.mkdtemp(prefix="isa_compare_")
     jobs = []
     for src in SOURCES:
@@ -74,17 +81,20 @@ def main(old, new):
                 print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (re.sub(r"\(.*$", "", pretty)[:70], src, *kn[name][0], kn[name][2], "new"))
             continue
         ko = kernels(outs[0])
-        if list(ko) != list(kn):
+        ko, kn = by_plain_name(ko), by_plain_name(kn)
+        pairs = [(o, renames.get(o, o)) for o in ko]
+        if any(n not in kn for _, n in pairs) or set(kn) - {n for _, n in pairs}:
             raise SystemExit("%s: the two trees do not have the same kernels: %s" % (src, sorted(set(ko) ^ set(kn))))
-        for name, pretty in zip(kn, demangle(list(kn)) if kn else []):
-            same = ko[name][:2] == kn[name][:2]
+        for o, n in pairs:
+            same = ko[o][:2] == kn[n][:2]
             total, differ = total + 1, differ + (not same)
-            print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (re.sub(r"\(.*$", "", pretty)[:70], src, *kn[name][0], kn[name][2],
-                                                          "identical" if same else "DIFFERS"))
+            if not same:
+                print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % ((o + " (old tree)")[:70], src, *ko[o][0], ko[o][2], ""))
+            print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (n[:70], src, *kn[n][0], kn[n][2], "identical" if same else "DIFFERS"))
     shutil.rmtree(tmp)
     print("%d kernels, %d differ" % (total, differ))
     return 1 if differ else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])))
+    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2]), dict(a.split("=") for a in sys.argv[3:])))
