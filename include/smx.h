@@ -942,6 +942,90 @@ int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size,
 #define SMX_DECIMATE_PHASES 4
 int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
+ * OpenGL) ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the
+ * colour of smx_recon_update_visualization_buffers reads; slots [0, n) with n = surfels_size()), of `triangles` (uint32
+ * [n_triangles][3], slot indices: the format smx_recon_triangulate and smx_recon_decimate_mesh write) and of p.  Camera,
+ * size, near_z / far_z, color_flags, frame_index and the window are those of smx_render_params (pixel-corner convention).
+ * Every floating-point quantity below is a DOUBLE expression evaluated as written, one rounding per operation, no
+ * contraction; division and square root are correctly rounded.  Everything that decides coverage is an integer.
+ * Vertex.  L = camera_T_global, inverted on the host in double as in smx_recon_render.  For slot i with smooth position
+ *    (px, py, pz): c.k = L[4k] px + L[4k+1] py + L[4k+2] pz + L[4k+3], summed left to right; u = fx c.x / c.z + cx,
+ *    v = fy c.y / c.z + cy; snapped to 1/256 pixel: X = (int64)floor(u * 256.0 + 0.5), Y likewise.
+ * Triangle t = (a, b, c), in this order:
+ * 1. An index >= n: counted in n_out_of_range, never dereferenced, not drawn (not an error).
+ * 2. A corner that is not live (!(RadiusSquared < 0) and a finite smooth position, as in smx_recon_triangulate): n_not_live.
+ * 3. A corner with !(near_z < c.z && c.z < far_z) or !(fabs(u) < 1048576.0 && fabs(v) < 1048576.0): n_clipped.
+ * 4. A = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) in int64 (every product stays below 2^59).  A == 0: n_degenerate.
+ * 5. Front-facing iff A < 0 (x right, y down, z forward: sign(A) = sign(a_c . n) for n = (b - a) x (c - a)).  With
+ *    cull_back_faces a triangle with A > 0 is dropped and counted in n_culled.
+ * 6. Pixel box x0 = ceil((min X - 128) / 256), x1 = floor((max X - 128) / 256) in integer arithmetic, y likewise, both
+ *    clamped to the image.  Empty: not drawn.  Otherwise n_drawn, and n_large as well iff (x1 - x0 + 1)(y1 - y0 + 1) >
+ *    SMX_MESH_RENDER_LARGE_PIXELS (which only chooses the kernel that walks the box).
+ * Coverage of pixel (x, y), centre P = (256 x + 128, 256 y + 128).  s = sign(A); w0 = s E(b, c, P), w1 = s E(c, a, P),
+ *    w2 = s E(a, b, P) with E(p, q, P) = (Xq - Xp)(Py - Yp) - (Yq - Yp)(Px - Xp) in int64.  Covered iff for every edge
+ *    w_k > 0, or w_k == 0 and, with d = s (q - p), d.y < 0 || (d.y == 0 && d.x > 0).  Two triangles of one facing that
+ *    share an edge traverse it in opposite directions, so a centre exactly on the edge belongs to exactly one of them.
+ * Depth, perspective-correct: l_k = (double)w_k / (double)|A|; invz = (l0 / za + l1 / zb) + l2 / zc with z = the corners'
+ *    c.z; Z = 1.0 / invz; depth = (float)Z.
+ * Z-test: every pixel keeps the minimum of (float_bits(depth) << 32) | t, t = the triangle's position in `triangles` (a
+ *    tie goes to the earlier triangle): the result does not depend on scheduling, two calls give the same bytes.
+ * Outputs (each may be NULL; otherwise exactly height x width with the element size given, any pitch):
+ *   depth  float   the winner's depth, 0 where no triangle covers the pixel
+ *   index  u32     the winner's t, 0xFFFFFFFF where empty
+ *   normal float4  with m_k = (l_k / z_k) * Z and n_k = the corner's normal rotated by L's rotation (in double, summed left
+ *                  to right): SMX_MESH_NORMAL_VERTEX takes N = (m0 n_a + m1 n_b) + m2 n_c per component, SMX_MESH_NORMAL_FACE
+ *                  g = (b_c - a_c) x (c_c - a_c) on the camera-space corners (g.x = e.y f.z - e.z f.y and cyclic), negated
+ *                  if (g.x a.x + g.y a.y) + g.z a.z > 0, so that it faces the camera.  len2 = (Nx Nx + Ny Ny) + Nz Nz; the
+ *                  output is (float)(N / sqrt(len2)), zeros if !(len2 > 0); w = 0; zeros where empty
+ *   color  uchar4  per channel min(255, floor(((m0 C_a + m1 C_b) + m2 C_c) + 0.5)) over the bytes of the corners' vertex-
+ *                  buffer colours (color_flags); alpha 255; (0, 0, 0, 0) where empty
+ * Not promised: there is no near-plane clipping -- a triangle with a corner outside (near_z, far_z) is dropped whole, so
+ *   a surface that passes through the near plane shows a ragged hole there.  No anti-aliasing.  A vertex-clustered mesh
+ *   may hold triangles that face against their corners' normals; cull_back_faces drops them.
+ * Calling rules: enqueued on s behind the pipelined regulariser and behind the previous smx_recon_render / _render_mesh /
+ *   tracking call (the z-buffer is the object's, shared with them, and grows on demand; growing a workspace waits for the
+ *   device).  on_device says where `triangles` lives; a host array is staged first.  With on_device != 0 and stats ==
+ *   NULL nothing waits on the host; a non-NULL stats makes the call synchronise s and read the counters back.
+ *   n_triangles == 0 is valid and gives empty images; at most 2^31 - 1 triangles.  Invalid sizes, parameters, modes or descriptors, or triangles ==
+ *   NULL with n_triangles > 0: SMX_ERR_INVALID_ARGUMENT with nothing launched.  Changes no map state, delta mark,
+ *   statistic or stamp, nor the state smx_recon_triangulate_update keeps. */
+enum { SMX_MESH_NORMAL_VERTEX = 0, SMX_MESH_NORMAL_FACE = 1 };
+#define SMX_MESH_RENDER_LARGE_PIXELS 256
+typedef struct {
+  int32_t width, height;
+  float fx, fy, cx, cy;                    /* pixel-corner convention */
+  float global_T_camera[12];               /* row-major 3x4 */
+  float near_z, far_z;                     /* 0 < near_z < far_z */
+  int32_t color_flags;                     /* SMX_VIS_* */
+  uint32_t frame_index;                    /* for the age colours */
+  int32_t surfel_integration_active_window_size;
+  int32_t cull_back_faces;                 /* 0 / 1 */
+  int32_t normal_mode;                     /* SMX_MESH_NORMAL_* */
+} smx_mesh_render_params;
+typedef struct {
+  uint32_t n_in;             /* triangles given */
+  uint32_t n_out_of_range;   /* of those, with an index >= surfels_size() */
+  uint32_t n_not_live;       /* with a corner that is not live */
+  uint32_t n_clipped;        /* with a corner outside (near_z, far_z) or projecting beyond +-2^20 pixels */
+  uint32_t n_degenerate;     /* with A == 0 */
+  uint32_t n_culled;         /* back-facing, with cull_back_faces */
+  uint32_t n_drawn;          /* with a non-empty pixel box (the rest: off the image, or between pixel centres) */
+  uint32_t n_large;          /* of n_drawn, with a box above SMX_MESH_RENDER_LARGE_PIXELS */
+  uint32_t n_covered_pixels; /* pixels of the image some triangle covers */
+} smx_mesh_render_stats;
+/* width = height = 0 (to be set), near_z 0.05, far_z 1000, identity pose, the colour row, no culling, vertex normals */
+int smx_mesh_render_params_default(smx_mesh_render_params* out);
+int smx_recon_render_mesh(smx_recon r, smx_stream s, const smx_mesh_render_params* p,
+                          const uint32_t* triangles, uint32_t n_triangles, int32_t on_device,
+                          const smx_buffer_desc* depth, const smx_buffer_desc* index,
+                          const smx_buffer_desc* normal, const smx_buffer_desc* color,
+                          smx_mesh_render_stats* stats /* may be NULL */);
+/* Tools: milliseconds the last smx_recon_render_mesh call spent in k_mrast_small (with the clears before it),
+ * k_mrast_large and k_mrast_resolve, by timed events on the call's stream.  Zeros before the first call. */
+int smx_recon_debug_mesh_render_timings(smx_recon r, float out_ms[3]);
+
 /* ---- benchmark input generator (not part of the reference's interface) ----
  * Renders one frame of the synthetic room stream into device buffers:
  * depth u16 = round(depth_scaling * z) with sigma = noise_sigma * z^2 noise and coherent 8x8

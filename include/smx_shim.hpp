@@ -645,6 +645,17 @@ class CUDASurfelReconstruction {
                                     index ? index->ToCUDA().desc() : nullptr, normal ? normal->ToCUDA().desc() : nullptr,
                                     color ? color->ToCUDA().desc() : nullptr));
   }
+  // Not in the reference: a triangle array over the map (three slot indices per triangle, as Triangulate and DecimateMesh
+  // return them) rasterised into the same images (smx_recon_render_mesh in smx.h); index holds the triangle's position in
+  // the array.  The host array is staged; stats may be null, and the call waits for the device only if it is not.
+  void RenderMesh(cudaStream_t stream, const smx_mesh_render_params& params, const std::vector<u32>& triangles,
+                  CUDABuffer<float>* depth, CUDABuffer<u32>* index, CUDABuffer<RenderNormal>* normal, CUDABuffer<RenderColor>* color,
+                  smx_mesh_render_stats* stats = nullptr) {
+    SMX_SHIM_CHECK(smx_recon_render_mesh(handle_, stream, &params, triangles.empty() ? nullptr : triangles.data(),
+                                         (u32)(triangles.size() / 3), 0, depth ? depth->ToCUDA().desc() : nullptr,
+                                         index ? index->ToCUDA().desc() : nullptr, normal ? normal->ToCUDA().desc() : nullptr,
+                                         color ? color->ToCUDA().desc() : nullptr, stats));
+  }
   // Not in the reference: frame-to-model ICP of a preprocessed frame against the map rendered at the predicted pose
   // (smx_recon_track; `pred` = 12 row-major floats of global_T_frame as predicted).  Synchronous: *result is filled on
   // return; result->status >= SMX_TRACK_TOO_FEW_INLIERS means that the caller keeps its prediction.

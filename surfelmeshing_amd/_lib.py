@@ -175,6 +175,34 @@ class DecimateStats(C.Structure):
 DECIMATE_PHASES = 4   # SMX_DECIMATE_PHASES
 
 
+class MeshRenderParams(C.Structure):
+    """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("global_T_camera", C.c_float * 12),
+                ("near_z", C.c_float), ("far_z", C.c_float),
+                ("color_flags", C.c_int32), ("frame_index", C.c_uint32),
+                ("surfel_integration_active_window_size", C.c_int32),
+                ("cull_back_faces", C.c_int32), ("normal_mode", C.c_int32)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """smx_mesh_render_params_default(), then any field by name."""
+        p = cls()
+        check(load().smx_mesh_render_params_default(C.byref(p)))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+class MeshRenderStats(C.Structure):
+    """smx_mesh_render_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_in", "n_out_of_range", "n_not_live", "n_clipped", "n_degenerate", "n_culled",
+                                          "n_drawn", "n_large", "n_covered_pixels")]
+
+
 class SurfelBuffersCPU(C.Structure):
     """smx_surfel_buffers_cpu == CUDASurfelBuffersCPU (APP/cuda_surfels_cpu.h:40-74)."""
     _fields_ = [("frame_index", C.c_uint32), ("surfel_count", C.c_size_t),
@@ -223,6 +251,7 @@ EXPORTS = [
     "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings",
     "smx_recon_triangulate_update", "smx_recon_triangulate_reset", "smx_recon_debug_mesh_update_timings", "smx_recon_deform_by_creation_frame",
     "smx_recon_decimate_mesh", "smx_recon_debug_decimate_timings",
+    "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
-                   DECIMATE_PHASES, DecimateStats, MeshParams, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
+                   DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
@@ -32,6 +32,9 @@ kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:7
 # smx.h: colour modes of the viewer buffers and the render, splat shapes of the render
 SMX_VIS_LAST_UPDATE, SMX_VIS_CREATION, SMX_VIS_RADII, SMX_VIS_NORMALS = 1, 2, 4, 8
 SMX_SPLAT_SQUARE, SMX_SPLAT_DISC = 0, 1
+# smx.h: where the mesh render takes its normals from; the box size above which a triangle goes to the tiled kernel
+SMX_MESH_NORMAL_VERTEX, SMX_MESH_NORMAL_FACE = 0, 1
+SMX_MESH_RENDER_LARGE_PIXELS = 256
 # smx.h: outcome of smx_recon_track (>= SMX_TRACK_TOO_FEW_INLIERS: nothing usable was solved)
 SMX_TRACK_OK, SMX_TRACK_CONVERGED, SMX_TRACK_TOO_FEW_INLIERS, SMX_TRACK_DEGENERATE, SMX_TRACK_NOT_FINITE = range(5)
 TRACK_STATUS_NAMES = ("OK", "CONVERGED", "TOO_FEW_INLIERS", "DEGENERATE", "NOT_FINITE")
@@ -92,6 +95,17 @@ def make_render_params(width, height, fx, fy, cx, cy, global_T_camera, near_z=0.
                         far_z, int(splat_mode), splat_half_extent_in_pixels, disc_radius_factor,
                         max_splat_extent_in_pixels, int(color_flags), int(frame_index) & 0xFFFFFFFF,
                         int(surfel_integration_active_window_size))
+
+
+def make_mesh_render_params(width, height, fx, fy, cx, cy, global_T_camera, near_z=0.05, far_z=1000.0, color_flags=0,
+                            frame_index=0, surfel_integration_active_window_size=2147483647, cull_back_faces=False,
+                            normal_mode=SMX_MESH_NORMAL_VERTEX):
+    """An smx_mesh_render_params.  Defaults: the depth range of make_render_params, the surfels' own colours, both faces
+    drawn, normals interpolated from the corners."""
+    T = np.asarray(global_T_camera, np.float32).reshape(12)
+    return MeshRenderParams(int(width), int(height), fx, fy, cx, cy, (C.c_float * 12)(*[float(v) for v in T]), near_z, far_z,
+                            int(color_flags), int(frame_index) & 0xFFFFFFFF, int(surfel_integration_active_window_size),
+                            int(cull_back_faces), int(normal_mode))
 
 
 def _slots_of(buf, slot_bytes):
@@ -762,6 +776,32 @@ class CUDASurfelReconstruction:
             return _d(b) if b is not None else None
         _lib.check(_lib.load().smx_recon_render(self._h, _sv(stream), C.byref(params) if params is not None else None,
                                                 opt(depth), opt(index), opt(normal), opt(color)))
+
+    def RenderMesh(self, stream, params, triangles, depth=None, index=None, normal=None, color=None, return_stats=False):
+        """Not in the reference: rasterises a triangle array over the map (smx_recon_render_mesh) into height x width device
+        images -- depth float, index uint32 (the triangle's position in the array), normal float4, color uchar4 (CUDABuffer
+        or BufferDesc; None = not wanted).  triangles: [T,3] slot indices as a numpy array (staged), or a (device address,
+        count) pair.  params: an smx_mesh_render_params (make_mesh_render_params).  Enqueued on `stream`; with a device
+        array and without return_stats nothing waits on the host.  return_stats: synchronises and returns the dict of
+        smx_mesh_render_stats."""
+        def opt(b):
+            return _d(b) if b is not None else None
+        if isinstance(triangles, tuple):
+            ptr, count, on_device = C.c_void_p(int(triangles[0])) if triangles[1] else None, int(triangles[1]), 1
+        else:
+            tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+            ptr, count, on_device = tri.ctypes.data_as(C.c_void_p) if tri.shape[0] else None, tri.shape[0], 0
+        st = MeshRenderStats() if return_stats else None
+        _lib.check(_lib.load().smx_recon_render_mesh(self._h, _sv(stream), C.byref(params) if params is not None else None, ptr,
+                                                     C.c_uint32(count), C.c_int32(on_device), opt(depth), opt(index), opt(normal),
+                                                     opt(color), C.byref(st) if return_stats else None))
+        return {n: int(getattr(st, n)) for n, _ in MeshRenderStats._fields_} if return_stats else None
+
+    def debug_mesh_render_timings(self):
+        """Milliseconds of the last RenderMesh call: k_mrast_small (with the clears), k_mrast_large, k_mrast_resolve."""
+        out = (C.c_float * 3)()
+        _lib.check(_lib.load().smx_recon_debug_mesh_render_timings(self._h, out))
+        return dict(zip(("small", "large", "resolve"), [float(v) for v in out]))
 
     def _track(self, fn, stream, depth_scaling, images, global_T_pred, params, result, model_images):
         """smx_recon_track / smx_recon_track_rgbd (fn): the frame's `images`, then pose, params and result, then the

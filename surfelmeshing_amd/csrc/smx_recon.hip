@@ -3020,6 +3020,7 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_track) (void)hipEventDestroy(r->ev_track);
   mesh_workspace_destroy(r->mesh);
   for (hipEvent_t e : r->ev_dec) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : r->ev_mr) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
   if (r->prof_ev) { for (int i = 0; i < 2 * r->prof_cap; ++i) (void)hipEventDestroy(r->prof_ev[i]); delete[] r->prof_ev; }

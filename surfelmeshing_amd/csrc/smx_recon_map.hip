@@ -167,41 +167,7 @@ k_export(Surfels S, float* __restrict__ pos, uint8_t* __restrict__ col, const De
 }
 
 // ---- viewer buffers (UpdateVisualizationBuffers) and headless rendering (smx_recon_render) ----
-struct VisColor { uint32_t frame; int window; int flags; };
-
-// float -> u8 for the colour conversions below: the reference converts values in [0, 256) (truncation); outside that
-// range its conversion is undefined, here it saturates (NaN -> 0)
-__device__ __forceinline__ uint32_t vis_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f); }
-__device__ __forceinline__ uint32_t vis_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
-
-// The colour word of UpdateSurfelVertexBufferCUDAKernel (kernels.cu:306-349) for one slot, flags in the reference
-// template's precedence (smx.h SMX_VIS_*).  Shared by the vertex buffer and the render's colour image.
-__device__ __forceinline__ uint32_t vis_color(const Surfels& S, uint32_t i, const VisColor& vc) {
-  if (vc.flags & (SMX_VIS_LAST_UPDATE | SMX_VIS_CREATION)) {
-    const bool creation = (vc.flags & SMX_VIS_CREATION) != 0;
-    const int age = (int)(vc.frame - (creation ? S.u(kCreationStamp, i) : S.u(kLastUpdateStamp, i)));
-    const int max_age = creation ? 3000 : vc.window;
-    if (age < 1) return vis_rgb(255, 80, 80);
-    if (age > max_age) return vis_rgb(40, 40, 255);
-    float blend = (float)(age - 1) * 1.0f / (float)(max_age - 1);
-    blend = fminf(1.0f, fmaxf(0.0f, blend));
-    const uint32_t intensity = (255u - vis_u8(255.99f * blend)) & 255u;
-    return vis_rgb(intensity, intensity, intensity);
-  }
-  if (vc.flags & SMX_VIS_RADII) {
-    const float radius = sqrtf(S.f(kRadiusSq, i));
-    float blend = (radius - 0.0005f) / (0.01f - 0.0005f);
-    blend = fminf(1.0f, fmaxf(0.0f, blend));
-    const uint32_t red = vis_u8(255.99f * blend);
-    return vis_rgb(red, 255u - red, 80u);
-  }
-  if (vc.flags & SMX_VIS_NORMALS) {
-    const float4 n = *S.group(kGroupN, i);
-    return vis_rgb(vis_u8(255.99f / 2.0f * (n.x + 1.0f)), vis_u8(255.99f / 2.0f * (n.y + 1.0f)),
-                   vis_u8(255.99f / 2.0f * (n.z + 1.0f)));
-  }
-  return S.u(kColor, i);
-}
+// (VisColor and vis_color, shared with the mesh rasteriser: smx_recon_state.hpp)
 
 // The three fill kernels of UpdateVisualizationBuffers (kernels.cu:278-351, 434-449, 498-514) in one pass over the
 // slots; each buffer stops at its own capacity.  (The reference writes vertex components one float at a time; one

@@ -201,6 +201,43 @@ struct SegWork {
   uint32_t* count;       // [0] survivors, [1] copies; zeroed for the next call by k_assoc_tiles
 };
 
+// ---- the colour of a slot in the viewer buffers, the splat render and the mesh render ----
+struct VisColor { uint32_t frame; int window; int flags; };
+
+// float -> u8 for the colour conversions below: the reference converts values in [0, 256) (truncation); outside that
+// range its conversion is undefined, here it saturates (NaN -> 0)
+__device__ __forceinline__ uint32_t vis_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f); }
+__device__ __forceinline__ uint32_t vis_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
+
+// The colour word of UpdateSurfelVertexBufferCUDAKernel (kernels.cu:306-349) for one slot, flags in the reference
+// template's precedence (smx.h SMX_VIS_*).  Shared by the vertex buffer and the render's colour image.
+__device__ __forceinline__ uint32_t vis_color(const Surfels& S, uint32_t i, const VisColor& vc) {
+  if (vc.flags & (SMX_VIS_LAST_UPDATE | SMX_VIS_CREATION)) {
+    const bool creation = (vc.flags & SMX_VIS_CREATION) != 0;
+    const int age = (int)(vc.frame - (creation ? S.u(kCreationStamp, i) : S.u(kLastUpdateStamp, i)));
+    const int max_age = creation ? 3000 : vc.window;
+    if (age < 1) return vis_rgb(255, 80, 80);
+    if (age > max_age) return vis_rgb(40, 40, 255);
+    float blend = (float)(age - 1) * 1.0f / (float)(max_age - 1);
+    blend = fminf(1.0f, fmaxf(0.0f, blend));
+    const uint32_t intensity = (255u - vis_u8(255.99f * blend)) & 255u;
+    return vis_rgb(intensity, intensity, intensity);
+  }
+  if (vc.flags & SMX_VIS_RADII) {
+    const float radius = sqrtf(S.f(kRadiusSq, i));
+    float blend = (radius - 0.0005f) / (0.01f - 0.0005f);
+    blend = fminf(1.0f, fmaxf(0.0f, blend));
+    const uint32_t red = vis_u8(255.99f * blend);
+    return vis_rgb(red, 255u - red, 80u);
+  }
+  if (vc.flags & SMX_VIS_NORMALS) {
+    const float4 n = *S.group(kGroupN, i);
+    return vis_rgb(vis_u8(255.99f / 2.0f * (n.x + 1.0f)), vis_u8(255.99f / 2.0f * (n.y + 1.0f)),
+                   vis_u8(255.99f / 2.0f * (n.z + 1.0f)));
+  }
+  return S.u(kColor, i);
+}
+
 }  // namespace smx
 
 // Created value-initialised (everything zero / empty).  `mem` owns the blocks smx_recon_create allocates -- the pointers
@@ -328,6 +365,12 @@ struct smx_recon_s {
   smx::DevBuf<uint32_t> dec_counters;              // [kDecWords]
   hipEvent_t ev_dec[5];                            // stamps of the last call (created by the first)
   int dec_phases;                                  // how many phases of it they bracket
+  // smx_recon_render_mesh (each grows on demand, behind the render event: see the call)
+  smx::DevBuf<uint32_t> mr_list;                   // [n_triangles] the triangles k_mrast_large walks
+  smx::DevBuf<uint32_t> mr_counters;               // [kMrWords] the verdict counts, the covered pixels, the list's length
+  smx::DevBuf<uint32_t> mr_in;                     // staging when the caller's array is host memory
+  hipEvent_t ev_mr[4];                             // stamps around the last call's three kernels (created by the first)
+  bool mr_timed;                                   // they bracket a complete call
 };
 
 namespace smx {

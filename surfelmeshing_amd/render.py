@@ -1,7 +1,9 @@
-"""Headless views of the device-resident surfel map (smx_recon_render): images from any camera, as numpy arrays.
+"""Headless views of the device-resident surfel map, as splats (smx_recon_render) or through a triangle array
+(smx_recon_render_mesh): images from any camera, as numpy arrays.
 
     img = render_view(rec, 640, 480, 525.0, 525.0, 320.0, 240.0, pose, splat_mode="disc")
     img["depth"], img["index"], img["normal"], img["color"]
+    img = render_mesh_view(rec, triangles, 640, 480, 525.0, 525.0, 320.0, 240.0, pose)
 
 Cameras follow the project's conventions: intrinsics in the pixel-corner convention, poses global_T_camera as
 row-major 3x4 with the camera's x right, y down, z forward.
@@ -13,6 +15,7 @@ from . import api
 _SPLAT = {"square": api.SMX_SPLAT_SQUARE, "disc": api.SMX_SPLAT_DISC}
 _COLOR = {"color": 0, "last_update": api.SMX_VIS_LAST_UPDATE, "creation": api.SMX_VIS_CREATION,
           "radii": api.SMX_VIS_RADII, "normals": api.SMX_VIS_NORMALS}
+_NORMALS = {"vertex": api.SMX_MESH_NORMAL_VERTEX, "face": api.SMX_MESH_NORMAL_FACE}
 _OUTPUTS = {"depth": (np.float32, 1), "index": (np.uint32, 1), "normal": (np.float32, 4), "color": (np.uint8, 4)}
 
 
@@ -45,6 +48,28 @@ def render_view(rec, width, height, fx, fy, cx, cy, global_T_camera, splat_mode=
     bufs = {name: api.CUDABuffer(int(height), int(width), *_OUTPUTS[name]) for name in outputs}
     try:
         rec.Render(stream, params, **bufs)
+        out = {name: b.DownloadAsync(stream) for name, b in bufs.items()}
+        api.StreamSynchronize(stream)
+    finally:
+        for b in bufs.values():
+            b.close()
+    return out
+
+
+def render_mesh_view(rec, triangles, width, height, fx, fy, cx, cy, global_T_camera, color="color", normal_mode="vertex",
+                     cull_back_faces=False, outputs=("depth", "index", "normal", "color"), stream=None, **opts):
+    """Draws `triangles` ([T,3] slot indices of `rec`: the output of Triangulate, TriangulateUpdate or DecimateMesh) and
+    returns {name: array} in the shapes of render_view; index holds the triangle's position in the array.  normal_mode
+    "vertex" (interpolated from the corners' normals) / "face" (or SMX_MESH_NORMAL_*), color as in render_view; further
+    options are the fields of smx_mesh_render_params (near_z, far_z, frame_index,
+    surfel_integration_active_window_size).  Synchronises `stream`."""
+    mode = _NORMALS[normal_mode] if isinstance(normal_mode, str) else int(normal_mode)
+    flags = _COLOR[color] if isinstance(color, str) else int(color)
+    params = api.make_mesh_render_params(width, height, fx, fy, cx, cy, global_T_camera, color_flags=flags,
+                                         cull_back_faces=cull_back_faces, normal_mode=mode, **opts)
+    bufs = {name: api.CUDABuffer(int(height), int(width), *_OUTPUTS[name]) for name in outputs}
+    try:
+        rec.RenderMesh(stream, params, triangles, **bufs)
         out = {name: b.DownloadAsync(stream) for name, b in bufs.items()}
         api.StreamSynchronize(stream)
     finally:

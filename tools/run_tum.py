@@ -4,7 +4,8 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--export_point_cloud out.ply] [--max_surfel_count N] [--pyramid_level L]
                               [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
                               [--track_rgbd [--track_photometric_weight W]]
-                              [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES] ...
+                              [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
+                              [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
 With --mesh_every N the mesh follows the map instead: every N integrated frames smx_recon_triangulate_update recomputes it
@@ -12,6 +13,9 @@ where the map changed (one line per update: mode, counts, milliseconds); --expor
 after the last frame.  --mesh_check triangulates once more at the end with the full call and fails if the two differ.
 --mesh_decimate METRES (with --mesh or --mesh_every) decimates the final mesh by vertex clustering on a grid of that cell
 size (smx_recon_decimate_mesh) before --export_mesh, which then writes only the vertices the coarse mesh uses.
+--render_source mesh (with --mesh or --mesh_every) makes --render_dir / --render_every / --render_overview draw the current
+mesh with smx_recon_render_mesh instead of splats: the kept array of --mesh_every as of its last update, otherwise a
+triangulation of the map as it stands, decimated first if --mesh_decimate is given.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
@@ -27,13 +31,17 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import numpy as np  # noqa: E402
 
 
-def write_render(args, rec, cam, global_T_camera, frame_index, name):
-    """One headless render of the map (surfelmeshing_amd.render) as an RGB PNG."""
+def write_render(args, rec, cam, global_T_camera, frame_index, name, triangles=None):
+    """One headless render of the map (surfelmeshing_amd.render) as an RGB PNG: splats, or `triangles` if given."""
     from surfelmeshing_amd import render, tum
     fx, fy, cx, cy = cam.parameters()
-    img = render.render_view(rec, cam.width(), cam.height(), fx, fy, cx, cy, global_T_camera,
-                             splat_mode=args.render_splat, color=args.render_color, outputs=("color",),
-                             frame_index=frame_index)
+    if triangles is None:
+        img = render.render_view(rec, cam.width(), cam.height(), fx, fy, cx, cy, global_T_camera,
+                                 splat_mode=args.render_splat, color=args.render_color, outputs=("color",),
+                                 frame_index=frame_index)
+    else:
+        img = render.render_mesh_view(rec, triangles, cam.width(), cam.height(), fx, fy, cx, cy, global_T_camera,
+                                      color=args.render_color, outputs=("color",), frame_index=frame_index)
     os.makedirs(args.render_dir, exist_ok=True)
     tum.write_png(os.path.join(args.render_dir, name), np.ascontiguousarray(img["color"][:, :, :3]))
 
@@ -119,7 +127,7 @@ def run_tracked(args, video, pipe, n, have_trajectory):
     return len(integrated)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset_folder")
     ap.add_argument("--trajectory", default="groundtruth.txt")
@@ -145,6 +153,8 @@ def main():
     ap.add_argument("--render_color", choices=("color", "last_update", "creation", "radii", "normals"), default="color")
     ap.add_argument("--render_overview", action="store_true",
                     help="at the end, render one view from outside the map's bounds looking at its centre")
+    ap.add_argument("--render_source", choices=("splats", "mesh"), default="splats",
+                    help="what the renders draw: the surfels as splats, or the current mesh (needs --mesh or --mesh_every)")
     ap.add_argument("--mesh", action="store_true",
                     help="triangulate the final map on the device; --export_mesh then writes the faces as well")
     ap.add_argument("--mesh_every", type=int, default=0,
@@ -161,7 +171,7 @@ def main():
                     help="track with the photometric term as well (implies --track)")
     ap.add_argument("--track_photometric_weight", type=float, default=None,
                     help="with --track_rgbd: metres per unit intensity (default: the library's, 0.1)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.track_photometric_weight is not None and not args.track_rgbd:
         ap.error("--track_photometric_weight needs --track_rgbd")
     args.track = args.track or args.track_rgbd
@@ -169,6 +179,13 @@ def main():
         ap.error("--mesh_decimate needs --mesh or --mesh_every")
     if args.mesh_decimate is not None and not args.mesh_decimate > 0:
         ap.error("--mesh_decimate needs a cell size > 0")
+    if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
+        ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch  # noqa: F401  (libsmx binds to the HIP runtime torch loaded)
     from surfelmeshing_amd import api, export, tum, _lib
@@ -217,6 +234,19 @@ def main():
               "(device phases %.2f ms)" % (frames_done, meshing.UPDATE_MODES[us["mode"]], us["n_changed"], us["n_dirty"],
                                            us["n_reagreed"], us["n_kept_triangles"], tri.shape[0], 1e3 * (time.time() - t),
                                            sum(ph.values())), flush=True)
+
+    def current_mesh():
+        """What --render_source mesh draws: the kept array (as of its last update), or a triangulation of the map as it stands."""
+        from surfelmeshing_amd import meshing
+        if mesher is not None:
+            if mesher.triangles is None:
+                mesher.update()
+            tri = mesher.triangles
+        else:
+            tri, _ = meshing.mesh_map(pipe.reconstruction)
+        if args.mesh_decimate is not None:
+            tri, _ = meshing.decimate_map_mesh(pipe.reconstruction, tri, args.mesh_decimate)
+        return tri
     uploaded = set()
     t0 = time.time()
     done = 0
@@ -247,7 +277,8 @@ def main():
         if mesher is not None and done % args.mesh_every == 0:
             update_mesh(done)
         if args.render_dir and args.render_every > 0 and done % args.render_every == 0:
-            write_render(args, pipe.reconstruction, cam, G, f, "render_%06d.png" % f)
+            write_render(args, pipe.reconstruction, cam, G, f, "render_%06d.png" % f,
+                         current_mesh() if args.render_source == "mesh" else None)
         old = f - half - 1                                                                      # main.cc:1226-1240
         if old in uploaded:
             pipe.release(old)
@@ -258,7 +289,7 @@ def main():
         done, dt, done / max(dt, 1e-9), rec.surfels_size(), rec.surfels_size() - rec.surfel_count()))
     if compactions:
         print("%d compactions removed %d merged slots" % (compactions, removed))
-    if args.render_dir and args.render_overview:
+    if args.render_dir and args.render_overview and args.render_source == "splats":
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png")
     triangles = None
     if mesher is not None:
@@ -284,6 +315,8 @@ def main():
         triangles, dst = meshing.decimate_map_mesh(rec, triangles, args.mesh_decimate)
         print("decimated at %g m in %.1f ms: %s" % (args.mesh_decimate, 1e3 * (time.time() - t1),
                                                     ", ".join("%s %d" % (k, dst[k]) for k in meshing.DECIMATE_STAT_NAMES)))
+    if args.render_dir and args.render_overview and args.render_source == "mesh":      # (the final mesh, decimated if asked)
+        write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png", triangles)
     if args.export_mesh:
         export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles, referenced_only=args.mesh_decimate is not None)
         print("Wrote %s." % args.export_mesh)
