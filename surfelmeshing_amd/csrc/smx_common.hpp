@@ -173,6 +173,91 @@ class DevBuf {
   size_t bytes_ = 0;
 };
 
+// Several buffers that exist together or not at all: (buffer, elements) pairs, allocated in the order given into
+// temporaries and moved in only when every allocation succeeded.  A failure leaves every buffer as it was.
+inline int alloc_all() { return SMX_OK; }
+template <typename T, typename... Rest>
+int alloc_all(DevBuf<T>& buf, size_t count, Rest&&... rest) {
+  DevBuf<T> fresh;
+  SMX_CALL(fresh.alloc(count, false));
+  SMX_CALL(alloc_all(rest...));
+  buf = std::move(fresh);
+  return SMX_OK;
+}
+
+// The caller's array may be host memory: *dev is src itself where that is device memory (or empty), else `buf`, grown to
+// hold it, with the copy enqueued on st.  Whoever owns buf keeps it alive until that copy and its readers are done.
+template <typename T>
+int stage_in(DevBuf<T>& buf, const T* src, size_t count, bool on_device, hipStream_t st, const T** dev) {
+  *dev = src;
+  if (on_device || count == 0) return SMX_OK;
+  SMX_CALL(buf.reserve(count));
+  SMX_HIP(hipMemcpyAsync(buf.get(), src, count * sizeof(T), hipMemcpyHostToDevice, st));
+  *dev = buf.get();
+  return SMX_OK;
+}
+
+// ---- events: two owners ---------------------------------------------------------------------------------------------
+// The mark behind the last user's work on a workspace that the next user, on whatever stream, must not overtake.  The
+// event is created by the first record and destroyed with the owner.
+class StreamMark {
+ public:
+  StreamMark() = default;
+  StreamMark(const StreamMark&) = delete;
+  ~StreamMark() { if (ev_) (void)hipEventDestroy(ev_); }
+  bool busy() const { return busy_; }
+  void clear() { busy_ = false; }   // (for a caller that has just synchronised the device)
+  int wait(hipStream_t st) const {
+    if (busy_) SMX_HIP(hipStreamWaitEvent(st, ev_, 0));
+    return SMX_OK;
+  }
+  int record(hipStream_t st) {
+    if (!ev_) SMX_HIP(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+    SMX_HIP(hipEventRecord(ev_, st));
+    busy_ = true;
+    return SMX_OK;
+  }
+
+ private:
+  hipEvent_t ev_ = nullptr;
+  bool busy_ = false;
+};
+
+// N + 1 timing events around the N phases of a call, created by the first begin.  Only published phases are read: a
+// call that fails between two stamps leaves zeros, not the time between the stamps of two calls.
+template <int N>
+class PhaseStamps {
+ public:
+  PhaseStamps() = default;
+  PhaseStamps(const PhaseStamps&) = delete;
+  ~PhaseStamps() { for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e); }
+  int begin(hipStream_t st) {
+    for (hipEvent_t& e : ev_) if (!e) SMX_HIP(hipEventCreate(&e));
+    published_ = marked_ = 0;
+    SMX_HIP(hipEventRecord(ev_[0], st));
+    return SMX_OK;
+  }
+  int mark(hipStream_t st) {   // (the end of the next phase; a call site that marks more than N per begin is refused)
+    if (marked_ >= N) { set_error("PhaseStamps<%d>: mark %d after one begin", N, marked_ + 1); return SMX_ERR_UNSUPPORTED; }
+    SMX_HIP(hipEventRecord(ev_[++marked_], st));
+    return SMX_OK;
+  }
+  void publish() { published_ = marked_; }   // (the phases marked so far may be read)
+  int elapsed_ms(float* out, int n) const {  // (waits for the closing stamp of each published phase)
+    for (int i = 0; i < n; ++i) {
+      out[i] = 0.0f;
+      if (i >= published_) continue;
+      SMX_HIP(hipEventSynchronize(ev_[i + 1]));
+      SMX_HIP(hipEventElapsedTime(&out[i], ev_[i], ev_[i + 1]));
+    }
+    return SMX_OK;
+  }
+
+ private:
+  hipEvent_t ev_[N + 1] = {};
+  int marked_ = 0, published_ = 0;
+};
+
 // The fixed blocks of an object, recorded as they are allocated and given back together.  The pointers go to plain
 // members and to the structs that kernels take by value (views: they own nothing).
 class DevBlocks {

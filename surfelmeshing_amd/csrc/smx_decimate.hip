@@ -14,7 +14,11 @@
 // only decreases towards the minimum over the cell; an entry of the triangle table only ever holds triangles of one corner
 // set and decreases towards the earliest of them.  A kernel reads with plain loads only what an EARLIER kernel wrote;
 // within a kernel, lanes meet through the atomics' return values alone.
-#include "smx_decimate.hpp"
+//
+// smx_recon_decimate_mesh itself is at the end of the file: it owns the order of the phases, the workspace (DecimateWork,
+// smx_decimate.hpp) and the three reads of the counters.
+#include "smx_recon_state.hpp"
+#include "smx_sort.hpp"
 
 namespace smx {
 
@@ -187,59 +191,161 @@ k_dec_emit(uint32_t m, const uint32_t* __restrict__ vals, const DecTri* __restri
 inline unsigned blocks_for(uint32_t n) { return (unsigned)div_up(n, kBlock); }
 
 }  // namespace
-
-int dec_enqueue_cluster(hipStream_t st, const DecMap& map, const uint32_t* tri_in, uint32_t n_in, float cell_size, float inv,
-                        uint32_t* vmap, DecCell* table, uint32_t table_size, uint32_t* counters) {
-  if (map.n > 0) SMX_HIP(hipMemsetAsync(vmap, 0xFF, (size_t)map.n * sizeof(uint32_t), st));
-  if (n_in == 0) return SMX_OK;
-  hipLaunchKernelGGL(k_dec_mark, dim3(blocks_for(n_in)), dim3(kBlock), 0, st, map, tri_in, n_in, vmap, counters);
-  if (map.n > 0) {      // (an empty map: every index is out of range, which k_dec_mark has just said)
-    SMX_HIP(hipMemsetAsync(table, 0xFF, (size_t)table_size * sizeof(DecCell), st));
-    hipLaunchKernelGGL(k_dec_insert, dim3(blocks_for(map.n)), dim3(kBlock), 0, st, map, cell_size, inv, vmap, table, table_size - 1, counters);
-    hipLaunchKernelGGL(k_dec_lookup, dim3(blocks_for(map.n)), dim3(kBlock), 0, st, map.n, vmap, table);
-  }
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int dec_enqueue_remap(hipStream_t st, const uint32_t* tri_in, uint32_t n_in, const uint32_t* vmap, DecTri* canon, uint32_t* own,
-                      uint32_t* dup_table, uint32_t table_size, uint32_t* counters) {
-  if (n_in == 0) return SMX_OK;
-  SMX_HIP(hipMemsetAsync(dup_table, 0xFF, (size_t)table_size * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_dec_remap, dim3(blocks_for(n_in)), dim3(kBlock), 0, st, tri_in, n_in, vmap, canon, counters);
-  hipLaunchKernelGGL(k_dec_dups, dim3(blocks_for(n_in)), dim3(kBlock), 0, st, n_in, canon, own, dup_table, table_size - 1);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int dec_enqueue_count(hipStream_t st, uint32_t n_in, const uint32_t* own, const uint32_t* dup_table, uint32_t* block_sums) {
-  if (n_in == 0) return SMX_OK;
-  hipLaunchKernelGGL(k_dec_count, dim3(blocks_for(n_in)), dim3(kBlock), 0, st, n_in, own, dup_table, block_sums);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int dec_enqueue_write(hipStream_t st, uint32_t n_in, const uint32_t* own, const uint32_t* dup_table, const uint32_t* block_off,
-                      const DecTri* canon, int bits, unsigned long long* keys, uint32_t* vals) {
-  if (n_in == 0) return SMX_OK;
-  hipLaunchKernelGGL(k_dec_write, dim3(blocks_for(n_in)), dim3(kBlock), 0, st, n_in, own, dup_table, block_off, canon, bits, keys, vals);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int dec_enqueue_keys_p(hipStream_t st, uint32_t m, const uint32_t* vals_in, const DecTri* canon, unsigned long long* keys_out,
-                       uint32_t* vals_out) {
-  if (m == 0) return SMX_OK;
-  hipLaunchKernelGGL(k_dec_keys_p, dim3(blocks_for(m)), dim3(kBlock), 0, st, m, vals_in, canon, keys_out, vals_out);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
-int dec_enqueue_emit(hipStream_t st, uint32_t m, const uint32_t* vals, const DecTri* canon, uint32_t* out) {
-  if (m == 0) return SMX_OK;
-  hipLaunchKernelGGL(k_dec_emit, dim3(blocks_for(m)), dim3(kBlock), 0, st, m, vals, canon, out);
-  SMX_LAUNCH_CHECK();
-  return SMX_OK;
-}
-
 }  // namespace smx
+
+using namespace smx;
+
+extern "C" {
+
+int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size, const uint32_t* triangles_in, uint32_t n_in,
+                            uint32_t* triangles_out, uint32_t capacity, uint32_t* vertex_map, int32_t on_device,
+                            uint32_t* n_triangles, smx_decimate_stats* stats) {
+  SMX_CHECK_ARG(r != nullptr && n_triangles != nullptr);
+  SMX_CHECK_ARG(cell_size > 0.0f && cell_size - cell_size == 0.0f);
+  SMX_CHECK_ARG(triangles_in != nullptr || n_in == 0);
+  SMX_CHECK_ARG(triangles_out != nullptr || capacity == 0);
+  if (n_in > 0 && capacity > 0) {
+    const uintptr_t i0 = (uintptr_t)triangles_in, i1 = i0 + (size_t)n_in * 12, o0 = (uintptr_t)triangles_out, o1 = o0 + (size_t)capacity * 12;
+    if (i0 < o1 && o0 < i1) {
+      set_error("triangles_out overlaps triangles_in");
+      return SMX_ERR_INVALID_ARGUMENT;
+    }
+  }
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  SMX_CALL(join_regularizer(r, st));
+  uint32_t n = 0;
+  SMX_CALL(read_surfel_count(r, st, &n));
+  *n_triangles = 0;
+  if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_in = n_in; }
+  DecimateWork& w = r->decimate;
+  SMX_CALL(w.stamps.begin(st));
+  // Every way out below that has marked a phase goes through finish: it publishes exactly the phases marked so far, which
+  // is what a refused call's getter returns (1 after a bad index or range, 2 after the capacity rule, 4 after a full call).
+  auto finish = [&](int rc) -> int {     // (the stamps are complete before they are published)
+    SMX_HIP(hipStreamSynchronize(st));
+    w.stamps.publish();
+    return rc;
+  };
+
+  // ---- workspace of the first two phases; the input on the device
+  const uint32_t cell_entries = dec_table_size((uint32_t)std::min<unsigned long long>(n, 3ull * n_in));
+  const uint32_t dup_entries = dec_table_size(n_in);
+  const int nb = div_up(n_in, kDecBlock);
+  if (!w.counters.get()) SMX_CALL(w.counters.alloc(kDecWords, false));
+  SMX_CALL(w.vmap.reserve(n));
+  if (n_in > 0) {
+    SMX_CALL(w.cells.reserve((size_t)2 * cell_entries));
+    SMX_CALL(w.canon.reserve((size_t)3 * n_in));
+    SMX_CALL(w.own.reserve(n_in));
+    SMX_CALL(w.dup.reserve(dup_entries));
+    SMX_CALL(w.blocks.reserve((size_t)nb));
+  }
+  const uint32_t* din = nullptr;
+  SMX_CALL(stage_in(w.in, triangles_in, (size_t)3 * n_in, on_device != 0, st, &din));
+  uint32_t* cnt = w.counters.get();
+  SMX_HIP(hipMemsetAsync(cnt, 0, kDecWords * sizeof(uint32_t), st));
+  uint32_t h[kDecWords];
+  auto read_counters = [&]() -> int {
+    SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+    return SMX_OK;
+  };
+
+  // ---- clustering: U, the cell table, the vertex map.  (An index out of range marks nothing and is read by nothing.)
+  const float inv = 1.0f / cell_size;
+  const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
+  const DecMap map{sv.p, sv.stride, nv.p, nv.stride, n};
+  DecCell* cells = reinterpret_cast<DecCell*>(w.cells.get());   // (dec_table_size(min(n, 3 n_in)) entries)
+  DecTri* canon = reinterpret_cast<DecTri*>(w.canon.get());
+  uint32_t* vmap = w.vmap.get();                                // (ends as the contract's vertex_map)
+  const dim3 b(kDecBlock), g_in(nb), g_map(blocks_for(n));
+  if (n > 0) SMX_HIP(hipMemsetAsync(vmap, 0xFF, (size_t)n * sizeof(uint32_t), st));
+  if (n_in > 0) {
+    hipLaunchKernelGGL(k_dec_mark, g_in, b, 0, st, map, din, n_in, vmap, cnt);
+    if (n > 0) {      // (an empty map: every index is out of range, which k_dec_mark has just said)
+      SMX_HIP(hipMemsetAsync(cells, 0xFF, (size_t)cell_entries * sizeof(DecCell), st));
+      hipLaunchKernelGGL(k_dec_insert, g_map, b, 0, st, map, cell_size, inv, vmap, cells, cell_entries - 1, cnt);
+      hipLaunchKernelGGL(k_dec_lookup, g_map, b, 0, st, n, vmap, cells);
+    }
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_CALL(w.stamps.mark(st));
+  SMX_CALL(read_counters());
+  if (h[kDecError] & kDecErrIndex) {
+    set_error("triangles_in holds an index >= the %u slots of the map", n);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+  if (h[kDecError] & kDecErrRange) {
+    set_error("cell_size %g is too small for the extent of the map: a cell coordinate is outside [-2^20, 2^20)", (double)cell_size);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+
+  // ---- remap and duplicates: canon gets the canonical triples (p = kDecNoSlot: dropped), own each triangle's entry of the
+  // table dup, which ends holding the earliest triangle of each corner set; survivors counted and scanned
+  if (n_in > 0) {
+    SMX_HIP(hipMemsetAsync(w.dup.get(), 0xFF, (size_t)dup_entries * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_dec_remap, g_in, b, 0, st, din, n_in, vmap, canon, cnt);
+    hipLaunchKernelGGL(k_dec_dups, g_in, b, 0, st, n_in, canon, w.own.get(), w.dup.get(), dup_entries - 1);
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_CALL(w.stamps.mark(st));
+  if (n_in > 0) {
+    hipLaunchKernelGGL(k_dec_count, g_in, b, 0, st, n_in, w.own.get(), w.dup.get(), w.blocks.get());
+    enqueue_segment_scan(st, w.blocks.get(), nb, cnt + kDecTotal);   // (survivors per workgroup -> their offsets, and the total)
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_CALL(read_counters());
+  const uint32_t T = h[kDecTotal];
+  *n_triangles = T;
+  if (stats) {
+    stats->n_not_live = h[kDecNotLive]; stats->n_used_vertices = h[kDecUsed]; stats->n_cells = h[kDecCells];
+    stats->n_collapsed = h[kDecCollapsed]; stats->n_duplicates = h[kDecAlive] - T; stats->n_triangles = T;
+  }
+  if (capacity < T) {
+    if (triangles_out != nullptr || capacity != 0) set_error("triangles_out holds %u entries, the decimated mesh has %u", capacity, T);
+    else set_error("count only: the decimated mesh has %u triangles", T);
+    return finish(SMX_ERR_INVALID_ARGUMENT);
+  }
+
+  // ---- the survivors in input order as sort records, ordered by (a, b) and then, stably, by p
+  if (T > 0) {
+    int bits = 1;
+    while (bits < 32 && ((uint32_t)(n - 1) >> bits) != 0) ++bits;
+    for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(T)); SMX_CALL(w.vals[k].reserve(T)); }
+    SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(T)));
+    const dim3 gt(blocks_for(T));
+    // (keys[j] = (a << bits) | b, vals[j] = the triangle's index in canon)
+    hipLaunchKernelGGL(k_dec_write, g_in, b, 0, st, n_in, w.own.get(), w.dup.get(), w.blocks.get(), canon, bits, w.keys[0].get(),
+                       w.vals[0].get());
+    SMX_LAUNCH_CHECK();
+    SMX_CALL(w.stamps.mark(st));
+    int cur = radix_sort(w.keys, w.vals, T, 2 * bits, w.hist.get(), st);
+    // (between the two stable sorts: keys[j] = p of triangle vals[j]; after them out[j] = canon[vals[j]])
+    hipLaunchKernelGGL(k_dec_keys_p, gt, b, 0, st, T, w.vals[cur].get(), canon, w.keys[0].get(), w.vals[0].get());
+    cur = radix_sort(w.keys, w.vals, T, bits, w.hist.get(), st);
+    SMX_LAUNCH_CHECK();
+    uint32_t* dst = triangles_out;
+    if (!on_device) {
+      SMX_CALL(w.out.reserve((size_t)3 * T));
+      dst = w.out.get();
+    }
+    hipLaunchKernelGGL(k_dec_emit, gt, b, 0, st, T, w.vals[cur].get(), canon, dst);
+    SMX_LAUNCH_CHECK();
+    if (!on_device) SMX_HIP(hipMemcpyAsync(triangles_out, dst, (size_t)T * 12, hipMemcpyDeviceToHost, st));
+  } else {
+    SMX_CALL(w.stamps.mark(st));
+  }
+  if (vertex_map && n > 0)
+    SMX_HIP(hipMemcpyAsync(vertex_map, vmap, (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  SMX_CALL(w.stamps.mark(st));
+  return finish(SMX_OK);
+}
+
+int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity) {
+  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr && capacity >= SMX_DECIMATE_PHASES);
+  SMX_ON_DEVICE(r->device);
+  return r->decimate.stamps.elapsed_ms(out_ms, SMX_DECIMATE_PHASES);
+}
+
+}  // extern "C"

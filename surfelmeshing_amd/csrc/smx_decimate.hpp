@@ -3,7 +3,7 @@
 // Part 1: the arithmetic of the contract as plain inline functions (cell coordinate with its range check, cell key, centre,
 // squared distance to the centre, the 64-bit value word, the canonical rotation of a triple).  smx_decimate.hip calls them
 // from its kernels; a test compiles this part alone for the host (SMX_DECIMATE_HOST_ONLY) and walks the same passes.
-// Part 2: what smx_recon_map.hip (owner of the map and of the workspace) needs of smx_decimate.hip (owner of the kernels).
+// Part 2: the device-side records and the workspace the object keeps for the call (kernels and glue: smx_decimate.hip).
 #pragma once
 
 #include <stdint.h>
@@ -108,26 +108,23 @@ struct DecMap {
   uint32_t n;
 };
 
-// All of them enqueue on st and return; the buffers are the caller's.  `counters` holds kDecWords zeroed words.
-// Phase 1 (clustering): vmap [n] ends as the contract's vertex_map; table must hold dec_table_size(min(n, 3 n_in)) entries.
-int dec_enqueue_cluster(hipStream_t st, const DecMap& map, const uint32_t* tri_in, uint32_t n_in, float cell_size, float inv,
-                        uint32_t* vmap, DecCell* table, uint32_t table_size, uint32_t* counters);
-// Phase 2 (remap and duplicates): canon [n_in] gets the canonical triples (p = kDecNoSlot: dropped), own [n_in] each
-// triangle's entry of dup_table (dec_table_size(n_in) entries), which ends holding the earliest triangle of each corner set.
-int dec_enqueue_remap(hipStream_t st, const uint32_t* tri_in, uint32_t n_in, const uint32_t* vmap, DecTri* canon, uint32_t* own,
-                      uint32_t* dup_table, uint32_t table_size, uint32_t* counters);
-// Phase 3 (survivors): their number per workgroup of kDecBlock triangles to block_sums [div_up(n_in, kDecBlock)]; the caller
-// scans them in place (enqueue_segment_scan, the total to counters[kDecTotal]) ...
-constexpr int kDecBlock = 256;
-int dec_enqueue_count(hipStream_t st, uint32_t n_in, const uint32_t* own, const uint32_t* dup_table, uint32_t* block_sums);
-// ... and then their list in input order, as sort records: keys[j] = (a << bits) | b, vals[j] = the triangle's index in canon.
-int dec_enqueue_write(hipStream_t st, uint32_t n_in, const uint32_t* own, const uint32_t* dup_table, const uint32_t* block_off,
-                      const DecTri* canon, int bits, unsigned long long* keys, uint32_t* vals);
-// Phase 4 (order): between the two stable sorts keys_out[j] = p of triangle vals_in[j], vals_out[j] = vals_in[j] ...
-int dec_enqueue_keys_p(hipStream_t st, uint32_t m, const uint32_t* vals_in, const DecTri* canon, unsigned long long* keys_out,
-                       uint32_t* vals_out);
-// ... and after them out[j] = canon[vals[j]].
-int dec_enqueue_emit(hipStream_t st, uint32_t m, const uint32_t* vals, const DecTri* canon, uint32_t* out);
+constexpr int kDecBlock = 256;                              // triangles (or slots) per workgroup of every kernel
+
+// The workspace, a member of smx_recon_s.  Each buffer grows on demand; the call is synchronous, so nothing
+// reads a block that goes.
+struct DecimateWork {
+  DevBuf<uint32_t> vmap;                   // [n] the vertex map
+  DevBuf<unsigned long long> cells;        // [cell table entries][2]: key, value word (DecCell)
+  DevBuf<uint32_t> canon, own;             // [n_in][3] canonical triples (DecTri); [n_in] each triangle's entry of
+  DevBuf<uint32_t> dup;                    // the table of triangle indices
+  DevBuf<uint32_t> blocks;                 // survivors per workgroup, then their offsets
+  DevBuf<unsigned long long> keys[2];      // [T_out] the sort's records
+  DevBuf<uint32_t> vals[2];
+  DevBuf<uint32_t> hist;                   // the sort's workspace
+  DevBuf<uint32_t> in, out;                // staging when the caller's arrays are host memory
+  DevBuf<uint32_t> counters;               // [kDecWords]
+  PhaseStamps<SMX_DECIMATE_PHASES> stamps; // of the last call; a refused call publishes the phases it completed
+};
 #endif
 
 }  // namespace smx

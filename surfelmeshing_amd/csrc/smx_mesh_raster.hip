@@ -11,10 +11,7 @@
 //
 // The three kernels call the same inline functions, so set-up, coverage and depth have the same bits wherever they are
 // evaluated; the z-buffer keeps the minimum key per pixel, so neither the order of the lanes nor that of the list shows.
-#include <cmath>
-
 #include "smx_recon_state.hpp"
-#include "smx_mesh_raster.hpp"
 
 using namespace smx;
 
@@ -150,17 +147,6 @@ k_mrast_resolve(Surfels S, MrCam cam, VisColor vc, const uint32_t* __restrict__ 
   if ((threadIdx.x & 63) == 0 && covered) atomicAdd(&counters[kMrCovered], covered);
 }
 
-bool desc_ok(const smx_buffer_desc* d, const smx_mesh_render_params* p, size_t elem) {   // (the rules of smx_recon_render)
-  return !d || (d->address && d->width == p->width && d->height == p->height && d->pitch >= (size_t)p->width * elem &&
-                d->pitch % elem == 0 && (uintptr_t)d->address % elem == 0);
-}
-template <typename T>
-Img<T> img_or_null(const smx_buffer_desc* d) {
-  if (d) return as_img<T>(d);
-  Img<T> i; i.address = nullptr; i.height = 0; i.width = 0; i.pitch = 0;
-  return i;
-}
-
 }  // namespace
 
 int smx_mesh_render_params_default(smx_mesh_render_params* out) {
@@ -176,70 +162,54 @@ int smx_recon_render_mesh(smx_recon r, smx_stream s, const smx_mesh_render_param
                           int32_t on_device, const smx_buffer_desc* depth, const smx_buffer_desc* index,
                           const smx_buffer_desc* normal, const smx_buffer_desc* color, smx_mesh_render_stats* stats) {
   SMX_CHECK_ARG(r != nullptr && p != nullptr);
-  SMX_CHECK_ARG(p->width > 0 && p->height > 0 && p->width <= 16384 && p->height <= 16384);
-  SMX_CHECK_ARG(std::isfinite(p->fx) && std::isfinite(p->fy) && p->fx > 0 && p->fy > 0 && std::isfinite(p->cx) && std::isfinite(p->cy));
-  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(p->global_T_camera[k]));
-  SMX_CHECK_ARG(std::isfinite(p->near_z) && p->near_z > 0 && p->far_z > p->near_z);
-  SMX_CHECK_ARG((p->color_flags & ~15) == 0);
+  SMX_CALL(check_view(*p));
   SMX_CHECK_ARG(p->cull_back_faces == 0 || p->cull_back_faces == 1);
   SMX_CHECK_ARG(p->normal_mode == SMX_MESH_NORMAL_VERTEX || p->normal_mode == SMX_MESH_NORMAL_FACE);
   SMX_CHECK_ARG(triangles != nullptr || n_triangles == 0);
   SMX_CHECK_ARG(n_triangles <= 0x7FFFFFFFu);   // (the grid-stride loops count in 32 bits)
-  SMX_CHECK_ARG(desc_ok(depth, p, 4) && desc_ok(index, p, 4) && desc_ok(normal, p, 16) && desc_ok(color, p, 4));
+  const int W = p->width, H = p->height;
+  SMX_CHECK_ARG(image_desc_ok_or_null(depth, W, H, 4) && image_desc_ok_or_null(index, W, H, 4) &&
+                image_desc_ok_or_null(normal, W, H, 16) && image_desc_ok_or_null(color, W, H, 4));
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
-  SMX_CALL(join_regularizer(r, st));
-  const size_t px = (size_t)p->width * p->height;
-  const bool stage = !on_device && n_triangles > 0;
-  // a workspace that has to grow: the previous render (of either kind, on whatever stream) may still be using the old block
-  if (r->zbuf.capacity() < px || r->mr_list.capacity() < n_triangles || !r->mr_counters.get() ||
-      (stage && r->mr_in.capacity() < (size_t)3 * n_triangles)) {
-    if (r->render_busy) SMX_HIP(hipDeviceSynchronize());
-    r->render_busy = false;
-    if (r->zbuf.capacity() < px) SMX_CALL(r->zbuf.alloc(px, false));
-    SMX_CALL(r->mr_list.reserve(n_triangles));
-    if (stage) SMX_CALL(r->mr_in.reserve((size_t)3 * n_triangles));
-    if (!r->mr_counters.get()) SMX_CALL(r->mr_counters.alloc(kMrWords, false));
-  }
-  if (!r->ev_mr[0]) for (hipEvent_t& e : r->ev_mr) SMX_HIP(hipEventCreate(&e));
-  if (r->render_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_render, 0));   // (the previous render's resolve, on any stream)
+  const size_t px = (size_t)W * H;
+  RenderWork& w = r->render;
+  const size_t staged = on_device ? 0 : (size_t)3 * n_triangles;
+  SMX_CALL(render_begin(r, st, px, w.list.capacity() < n_triangles || w.in.capacity() < staged || !w.counters.get()));
+  SMX_CALL(w.list.reserve(n_triangles));   // (no-ops unless render_begin was told of them: behind its synchronisation)
+  SMX_CALL(w.in.reserve(staged));
+  if (!w.counters.get()) SMX_CALL(w.counters.alloc(kMrWords, false));
   MrCam cam;
   mr_invert_pose(p->global_T_camera, cam.L);
   cam.fx = p->fx; cam.fy = p->fy; cam.cx = p->cx; cam.cy = p->cy; cam.near_z = p->near_z; cam.far_z = p->far_z;   // (floats widened)
-  cam.W = p->width; cam.H = p->height; cam.cull_back_faces = p->cull_back_faces; cam.normal_mode = p->normal_mode;
+  cam.W = W; cam.H = H; cam.cull_back_faces = p->cull_back_faces; cam.normal_mode = p->normal_mode;
   VisColor vc;
   vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
-  const uint32_t* tri = triangles;
-  r->mr_timed = false;
-  SMX_HIP(hipEventRecord(r->ev_mr[0], st));
-  if (stage) {
-    SMX_HIP(hipMemcpyAsync(r->mr_in.get(), triangles, (size_t)n_triangles * 12, hipMemcpyHostToDevice, st));
-    tri = r->mr_in.get();
-  }
-  uint32_t* cnt = r->mr_counters.get();
+  const uint32_t* tri = nullptr;
+  SMX_CALL(w.stamps.begin(st));
+  SMX_CALL(stage_in(w.in, triangles, (size_t)3 * n_triangles, on_device != 0, st, &tri));   // (there is room: no allocation)
+  uint32_t* cnt = w.counters.get();
+  unsigned long long* zbuf = w.zbuf.get();
   SMX_HIP(hipMemsetAsync(cnt, 0, kMrWords * sizeof(uint32_t), st));
-  SMX_HIP(hipMemsetAsync(r->zbuf.get(), 0xFF, px * sizeof(unsigned long long), st));
+  SMX_HIP(hipMemsetAsync(zbuf, 0xFF, px * sizeof(unsigned long long), st));
   if (n_triangles > 0) {
     const int blocks = std::min(div_up(n_triangles, kBlock), 8 * r->cu_count);
-    hipLaunchKernelGGL(k_mrast_small, dim3(blocks), dim3(kBlock), 0, st, r->S, cam, tri, n_triangles, r->zbuf.get(), r->mr_list.get(),
-                       cnt, r->st);
+    hipLaunchKernelGGL(k_mrast_small, dim3(blocks), dim3(kBlock), 0, st, r->S, cam, tri, n_triangles, zbuf, w.list.get(), cnt, r->st);
   }
-  SMX_HIP(hipEventRecord(r->ev_mr[1], st));
+  SMX_CALL(w.stamps.mark(st));
   if (n_triangles > 0) {
     // (a wavefront per listed triangle; the list's length is only known on the device)
     const int blocks = std::min(div_up(n_triangles, kBlock / 64), 8 * r->cu_count);
-    hipLaunchKernelGGL(k_mrast_large, dim3(blocks), dim3(kBlock), 0, st, r->S, cam, tri, n_triangles, r->zbuf.get(), r->mr_list.get(),
-                       cnt, r->st);
+    hipLaunchKernelGGL(k_mrast_large, dim3(blocks), dim3(kBlock), 0, st, r->S, cam, tri, n_triangles, zbuf, w.list.get(), cnt, r->st);
   }
-  SMX_HIP(hipEventRecord(r->ev_mr[2], st));
-  hipLaunchKernelGGL(k_mrast_resolve, dim3(div_up(p->width, 64), div_up(p->height, 4)), dim3(kBlock), 0, st, r->S, cam, vc, tri,
-                     r->zbuf.get(), img_or_null<float>(depth), img_or_null<uint32_t>(index), img_or_null<float4>(normal),
+  SMX_CALL(w.stamps.mark(st));
+  hipLaunchKernelGGL(k_mrast_resolve, dim3(div_up(W, 64), div_up(H, 4)), dim3(kBlock), 0, st, r->S, cam, vc, tri,
+                     zbuf, img_or_null<float>(depth), img_or_null<uint32_t>(index), img_or_null<float4>(normal),
                      img_or_null<uint32_t>(color), cnt);
   SMX_LAUNCH_CHECK();
-  SMX_HIP(hipEventRecord(r->ev_mr[3], st));
-  SMX_HIP(hipEventRecord(r->ev_render, st));
-  r->render_busy = true;
-  r->mr_timed = true;
+  SMX_CALL(w.stamps.mark(st));
+  SMX_CALL(render_end(r, st));
+  w.stamps.publish();
   if (stats) {
     uint32_t h[kMrWords];
     SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -254,12 +224,5 @@ int smx_recon_render_mesh(smx_recon r, smx_stream s, const smx_mesh_render_param
 int smx_recon_debug_mesh_render_timings(smx_recon r, float out_ms[3]) {
   SMX_CHECK_ARG(r != nullptr && out_ms != nullptr);
   SMX_ON_DEVICE(r->device);
-  for (int i = 0; i < 3; ++i) {
-    out_ms[i] = 0.0f;
-    if (r->mr_timed) {
-      SMX_HIP(hipEventSynchronize(r->ev_mr[i + 1]));
-      SMX_HIP(hipEventElapsedTime(&out_ms[i], r->ev_mr[i], r->ev_mr[i + 1]));
-    }
-  }
-  return SMX_OK;
+  return r->render.stamps.elapsed_ms(out_ms, 3);
 }

@@ -2776,12 +2776,6 @@ int enqueue_regularize(smx_recon r, hipStream_t st, uint32_t frame, float rf, fl
   return SMX_OK;
 }
 
-int ensure_staging(smx_recon r, size_t floats) {
-  if (r->staging.capacity() >= floats) return SMX_OK;
-  if (r->staging.get()) SMX_HIP(hipDeviceSynchronize());   // (earlier users may still be reading the old block)
-  return r->staging.alloc(floats, false);
-}
-
 // (for the create functions, whose failure paths have to release what exists so far instead of returning on the spot)
 int hip_rc(hipError_t e, const char* what) {
   if (e == hipSuccess) return SMX_OK;
@@ -2791,7 +2785,7 @@ int hip_rc(hipError_t e, const char* what) {
 
 }  // namespace
 
-// ---- host helpers shared with smx_recon_map.hip (declared in smx_recon_state.hpp) ----
+// ---- host helpers shared with the map services' files (declared in smx_recon_state.hpp) ----
 namespace smx {
 
 int join_regularizer(smx_recon r, hipStream_t st) {
@@ -2817,14 +2811,13 @@ void enqueue_segment_scan(hipStream_t st, uint32_t* seg_count, int nseg, uint32_
 }
 
 int acquire_staging(smx_recon r, hipStream_t st, size_t floats) {
-  if (r->staging_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_staging, 0));
-  return ensure_staging(r, floats);
+  DevBuf<float>& buf = r->staging.buf;
+  SMX_CALL(r->staging.mark.wait(st));
+  if (buf.capacity() >= floats) return SMX_OK;
+  if (buf.get()) SMX_HIP(hipDeviceSynchronize());   // (earlier users may still be reading the old block)
+  return buf.alloc(floats, false);
 }
-int release_staging(smx_recon r, hipStream_t st) {
-  SMX_HIP(hipEventRecord(r->ev_staging, st));
-  r->staging_busy = true;
-  return SMX_OK;
-}
+int release_staging(smx_recon r, hipStream_t st) { return r->staging.mark.record(st); }
 
 // After surfel attributes were changed from outside the frame loop (state upload, deformation): drop the work
 // lists and segment boxes (count 0 = no box, the segment is scanned) and rebuild the flag table -- its detach bits
@@ -2986,9 +2979,6 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_front, evf), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_upd, evf), "hipEventCreateWithFlags"));
   SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_reg, evf), "hipEventCreateWithFlags"));
-  SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_staging, hipEventDisableTiming), "hipEventCreateWithFlags"));
-  SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_render, hipEventDisableTiming), "hipEventCreateWithFlags"));
-  SMX_TRY(hip_rc(hipEventCreateWithFlags(&r->ev_track, hipEventDisableTiming), "hipEventCreateWithFlags"));
   r->overlap_enabled = 1;
   r->prof_slot = -1;
   r->timing_enabled = 4;   // (GetTimings is served by the stage stamps: on from the first call, like the reference's events)
@@ -3015,16 +3005,11 @@ int smx_recon_destroy(smx_recon r) {
   if (r->ev_front) (void)hipEventDestroy(r->ev_front);
   if (r->ev_upd) (void)hipEventDestroy(r->ev_upd);
   if (r->ev_reg) (void)hipEventDestroy(r->ev_reg);
-  if (r->ev_staging) (void)hipEventDestroy(r->ev_staging);
-  if (r->ev_render) (void)hipEventDestroy(r->ev_render);
-  if (r->ev_track) (void)hipEventDestroy(r->ev_track);
   mesh_workspace_destroy(r->mesh);
-  for (hipEvent_t e : r->ev_dec) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : r->ev_mr) if (e) (void)hipEventDestroy(e);
   for (int i = 0; i < 14; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   for (int i = 0; i < 2 * 16; ++i) if (r->kev[i]) (void)hipEventDestroy(r->kev[i]);
   if (r->prof_ev) { for (int i = 0; i < 2 * r->prof_cap; ++i) (void)hipEventDestroy(r->prof_ev[i]); delete[] r->prof_ev; }
-  delete r;   // (mem and the DevBuf members give their blocks back)
+  delete r;   // (mem and the services' workspaces give their blocks and events back)
   return SMX_OK;
 }
 
@@ -3622,13 +3607,13 @@ int smx_recon_transfer_changed_to_cpu(smx_recon r, smx_stream s, uint32_t frame_
   SMX_CHECK_ARG(d->surfel_index && d->x && d->y && d->z && d->radius_squared && d->normal_x && d->normal_y &&
                 d->normal_z && d->last_update_stamp);
   SMX_CALL(acquire_staging(r, st, (size_t)9 * total));
-  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg.get(), r->staging.get(), total,
+  hipLaunchKernelGGL(k_delta_gather, dim3(r->nseg), dim3(kBlock), 0, st, r->S, r->L.dirty8, r->delta_seg.get(), r->staging.buf.get(), total,
                      r->st);
   SMX_LAUNCH_CHECK();
   void* dst[9] = {d->surfel_index, d->x, d->y, d->z, d->radius_squared, d->normal_x, d->normal_y, d->normal_z,
                   d->last_update_stamp};
   for (int k = 0; k < 9; ++k)
-    SMX_HIP(hipMemcpyAsync(dst[k], r->staging.get() + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(dst[k], r->staging.buf.get() + (size_t)k * total, (size_t)total * 4, hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   return SMX_OK;
 }

@@ -1,23 +1,19 @@
 // smx_recon_map.hip -- map services of the surfel reconstruction object: the entry points that are called outside the
 // frame loop and only read or rewrite the finished map, and their gfx950 kernels.
 //
-// TransferAllToCPU, ExportVertices, the viewer buffers and headless rendering, the glue of smx_recon_track /
-// _triangulate / _triangulate_update, the mesher's candidate lists and triangle tests, map compaction, the
-// loop-closure deformation and the debug row upload / download.  The frame loop itself (Integrate, Regularize, their
-// kernels, the timing readers, and the changed-surfel delta whose marks those kernels write) is smx_recon.hip; what
-// the two share is smx_recon_state.hpp.
+// TransferAllToCPU, ExportVertices, the viewer buffers, the splat render (and the front end it shares with the mesh
+// render, smx_render.hpp), the glue of smx_recon_triangulate / _triangulate_update, the mesher's candidate lists and
+// triangle tests, map compaction, the loop-closure deformation and the debug row upload / download.  Tracking, decimation
+// and the mesh render are with their kernels (smx_track.hip, smx_decimate.hip, smx_mesh_raster.hip).  The frame loop itself
+// (Integrate, Regularize, their kernels, the timing readers, and the changed-surfel delta whose marks those kernels write)
+// is smx_recon.hip; what they all share is smx_recon_state.hpp.
 #include <math.h>
-#include <cmath>
 #include <string.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "smx_recon_state.hpp"
-#include "smx_track.hpp"
-#include "smx_decimate.hpp"
 #include "smx_mesh.hpp"
-#include "smx_sort.hpp"
 
 using namespace smx;
 
@@ -292,17 +288,6 @@ k_render_resolve(Surfels S, RenderCtx rc, VisColor vc, const unsigned long long*
   if (color.address) color(y, x) = empty ? 0u : ((vis_color(S, slot, vc) & 0x00FFFFFFu) | 0xFF000000u);
 }
 
-bool render_desc_ok(const smx_buffer_desc* d, const smx_render_params* p, size_t elem) {
-  return !d || (d->address && d->width == p->width && d->height == p->height && d->pitch >= (size_t)p->width * elem &&
-                d->pitch % elem == 0 && (uintptr_t)d->address % elem == 0);
-}
-template <typename T>
-Img<T> render_img(const smx_buffer_desc* d) {
-  if (d) return as_img<T>(d);
-  Img<T> i; i.address = nullptr; i.height = 0; i.width = 0; i.pitch = 0;
-  return i;
-}
-
 // Candidate lists for the mesher: the rows the neighbour index is built from (smooth position,
 // NaN for merged slots so that the index leaves them out) and the per-query (position, radius^2) of a list of slots.
 __global__ void __launch_bounds__(kBlock)
@@ -438,6 +423,19 @@ struct DevTemp {
 
 }  // namespace
 
+// ---- the render front end (smx_render.hpp) ----
+int smx::render_begin(smx_recon r, hipStream_t st, size_t px, bool caller_grows) {
+  SMX_CALL(join_regularizer(r, st));
+  RenderWork& w = r->render;
+  if (w.zbuf.capacity() < px || caller_grows) {
+    if (w.mark.busy()) SMX_HIP(hipDeviceSynchronize());
+    w.mark.clear();
+    if (w.zbuf.capacity() < px) SMX_CALL(w.zbuf.alloc(px, false));
+  }
+  return w.mark.wait(st);
+}
+int smx::render_end(smx_recon r, hipStream_t st) { return r->render.mark.record(st); }
+
 extern "C" {
 
 int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_index, smx_surfel_buffers_cpu* buf) {
@@ -457,7 +455,7 @@ int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_inde
   rl.n = 8;
   const int want[8] = {kSmoothX, kSmoothY, kSmoothZ, kRadiusSq, kNormalX, kNormalY, kNormalZ, kLastUpdateStamp};
   for (int k = 0; k < 8; ++k) rl.rows[k] = want[k];
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging.get(), n);
+  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rl, r->staging.buf.get(), n);
   SMX_LAUNCH_CHECK();
   struct { int row; void* dst; } rows[8] = {
       {kSmoothX, buf->surfel_x_buffer}, {kSmoothY, buf->surfel_y_buffer}, {kSmoothZ, buf->surfel_z_buffer},
@@ -467,7 +465,7 @@ int smx_recon_transfer_all_to_cpu(smx_recon r, smx_stream s, uint32_t frame_inde
   int k = 0;
   for (auto& q : rows) {
     SMX_CHECK_ARG(q.dst != nullptr);
-    SMX_HIP(hipMemcpyAsync(q.dst, r->staging.get() + (size_t)k * n, bytes, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(q.dst, r->staging.buf.get() + (size_t)k * n, bytes, hipMemcpyDeviceToHost, st));
     ++k;
   }
   return release_staging(r, st);  // (the copies are still in flight: the caller synchronises, main.cc:1266-1267)
@@ -513,222 +511,35 @@ int smx_recon_update_visualization_buffers(smx_recon r, smx_stream s, uint32_t f
 int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, const smx_buffer_desc* depth,
                      const smx_buffer_desc* index, const smx_buffer_desc* normal, const smx_buffer_desc* color) {
   SMX_CHECK_ARG(r != nullptr && p != nullptr);
-  SMX_CHECK_ARG(p->width > 0 && p->height > 0 && p->width <= 16384 && p->height <= 16384);
-  SMX_CHECK_ARG(std::isfinite(p->fx) && std::isfinite(p->fy) && p->fx > 0 && p->fy > 0 && std::isfinite(p->cx) && std::isfinite(p->cy));
-  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(p->global_T_camera[k]));
-  SMX_CHECK_ARG(std::isfinite(p->near_z) && p->near_z > 0 && p->far_z > p->near_z);
+  SMX_CALL(check_view(*p));
   SMX_CHECK_ARG(p->splat_mode == SMX_SPLAT_SQUARE || p->splat_mode == SMX_SPLAT_DISC);
   // (a splat's pixel rectangle is bounded by these: at most (2 x 1024 + 1)^2 pixels for one thread)
   SMX_CHECK_ARG(p->splat_half_extent_in_pixels >= 0 && p->splat_half_extent_in_pixels <= 1024);
   SMX_CHECK_ARG(p->max_splat_extent_in_pixels > 0 && p->max_splat_extent_in_pixels <= 1024);
   SMX_CHECK_ARG(std::isfinite(p->disc_radius_factor) && p->disc_radius_factor > 0);
-  SMX_CHECK_ARG((p->color_flags & ~15) == 0);
-  SMX_CHECK_ARG(render_desc_ok(depth, p, 4) && render_desc_ok(index, p, 4) && render_desc_ok(normal, p, 16) &&
-                render_desc_ok(color, p, 4));
+  const int W = p->width, H = p->height;
+  SMX_CHECK_ARG(image_desc_ok_or_null(depth, W, H, 4) && image_desc_ok_or_null(index, W, H, 4) &&
+                image_desc_ok_or_null(normal, W, H, 16) && image_desc_ok_or_null(color, W, H, 4));
   SMX_ON_DEVICE(r->device);
   hipStream_t st = (hipStream_t)s;
-  SMX_CALL(join_regularizer(r, st));
-  const size_t px = (size_t)p->width * p->height;
-  if (r->zbuf.capacity() < px) {
-    if (r->zbuf.get()) SMX_HIP(hipDeviceSynchronize());   // (the previous render may still be using the old block)
-    r->render_busy = false;
-    SMX_CALL(r->zbuf.alloc(px, false));
-  }
-  if (r->render_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_render, 0));   // (the previous render's resolve, on any stream)
+  const size_t px = (size_t)W * H;
+  SMX_CALL(render_begin(r, st, px));
+  unsigned long long* zbuf = r->render.zbuf.get();
   RenderCtx rc;
-  {
-    const float* m = p->global_T_camera;
-    for (int i = 0; i < 3; ++i) {   // R^T, -(R^T t)
-      for (int k = 0; k < 3; ++k) rc.L[4 * i + k] = m[4 * k + i];
-      rc.L[4 * i + 3] = -(rc.L[4 * i + 0] * m[3] + rc.L[4 * i + 1] * m[7] + rc.L[4 * i + 2] * m[11]);
-    }
-    rc.Lf = se3_inverse(m);
-  }
+  mr_invert_pose(p->global_T_camera, rc.L);
+  rc.Lf = se3_inverse(p->global_T_camera);
   rc.fx = p->fx; rc.fy = p->fy; rc.cx = p->cx; rc.cy = p->cy; rc.near_z = p->near_z; rc.far_z = p->far_z;
   rc.half_extent = p->splat_half_extent_in_pixels;
   rc.disc_factor = p->disc_radius_factor; rc.max_extent = p->max_splat_extent_in_pixels; rc.f_max = std::max(p->fx, p->fy);  // (float fields widened to double)
-  rc.W = p->width; rc.H = p->height; rc.mode = p->splat_mode;
+  rc.W = W; rc.H = H; rc.mode = p->splat_mode;
   VisColor vc;
   vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
-  SMX_HIP(hipMemsetAsync(r->zbuf.get(), 0xFF, px * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, r->zbuf.get(), r->st);
-  hipLaunchKernelGGL(k_render_resolve, dim3(div_up(p->width, 64), div_up(p->height, 4)), dim3(kBlock), 0, st, r->S, rc, vc,
-                     r->zbuf.get(), render_img<float>(depth), render_img<uint32_t>(index), render_img<float4>(normal),
-                     render_img<uint32_t>(color));
+  SMX_HIP(hipMemsetAsync(zbuf, 0xFF, px * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_render_splat, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, rc, zbuf, r->st);
+  hipLaunchKernelGGL(k_render_resolve, dim3(div_up(W, 64), div_up(H, 4)), dim3(kBlock), 0, st, r->S, rc, vc, zbuf,
+                     img_or_null<float>(depth), img_or_null<uint32_t>(index), img_or_null<float4>(normal), img_or_null<uint32_t>(color));
   SMX_LAUNCH_CHECK();
-  SMX_HIP(hipEventRecord(r->ev_render, st));
-  r->render_busy = true;
-  return SMX_OK;
-}
-
-// smx_recon_track (q, color, result_rgbd and model_photo_out null) and smx_recon_track_rgbd (p = &q->icp, result =
-// &result_rgbd->icp).
-static int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                      const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
-                      smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
-                      const smx_buffer_desc* model_normal_out, const smx_buffer_desc* color,
-                      const smx_track_rgbd_params* q, smx_track_rgbd_result* result_rgbd,
-                      const smx_buffer_desc* model_photo_out) {
-  SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
-                result != nullptr);
-  const smx_track_params& p = *params;
-  SMX_CHECK_ARG(std::isfinite(depth_scaling) && depth_scaling > 0);
-  auto img_ok = [&](const smx_buffer_desc* d, size_t elem) {
-    return d->address && d->width == r->W && d->height == r->H && d->pitch >= (size_t)r->W * elem && d->pitch % elem == 0 &&
-           (uintptr_t)d->address % elem == 0;
-  };
-  SMX_CHECK_ARG(img_ok(depth, 2) && img_ok(normals, 8));
-  SMX_CHECK_ARG(!model_depth_out || img_ok(model_depth_out, 4));
-  SMX_CHECK_ARG(!model_normal_out || img_ok(model_normal_out, 16));
-  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(global_T_pred[k]));
-  int levels_used = 0;
-  for (int l = 0; l < kTrackLevels; ++l) {
-    SMX_CHECK_ARG(p.level_iterations[l] >= 0 && p.level_iterations[l] <= kTrackMaxIterationsPerLevel);
-    if (p.level_iterations[l] == 0) continue;
-    ++levels_used;
-    SMX_CHECK_ARG(p.level_stride[l] == 1 || p.level_stride[l] == 2 || p.level_stride[l] == 4 || p.level_stride[l] == 8);
-  }
-  SMX_CHECK_ARG(levels_used > 0);
-  SMX_CHECK_ARG(std::isfinite(p.max_distance) && p.max_distance > 0);
-  SMX_CHECK_ARG(p.max_normal_angle_deg > 0 && p.max_normal_angle_deg <= 180.0f);
-  SMX_CHECK_ARG(p.convergence_rotation >= 0 && p.convergence_translation >= 0 && p.min_inliers >= 0);
-  SMX_CHECK_ARG(p.min_inlier_fraction >= 0 && p.min_inlier_fraction <= 1 && p.min_pivot_ratio >= 0);
-  SMX_CHECK_ARG(std::isfinite(p.near_z) && p.near_z > 0 && p.far_z > p.near_z);
-  SMX_CHECK_ARG(std::isfinite(p.disc_radius_factor) && p.disc_radius_factor > 0);
-  SMX_CHECK_ARG(p.max_splat_extent_in_pixels > 0 && p.max_splat_extent_in_pixels <= 1024);
-  if (q) {
-    // (3-byte elements: any pitch that holds a row, as smx_recon_integrate takes the image)
-    SMX_CHECK_ARG(color != nullptr && color->address && color->width == r->W && color->height == r->H &&
-                  color->pitch >= (size_t)r->W * 3);
-    SMX_CHECK_ARG(!model_photo_out || img_ok(model_photo_out, 16));
-    SMX_CHECK_ARG(std::isfinite(q->photometric_weight) && q->photometric_weight >= 0);
-    SMX_CHECK_ARG(std::isfinite(q->max_intensity_difference) && q->max_intensity_difference > 0);
-    SMX_CHECK_ARG(std::isfinite(q->min_gradient) && q->min_gradient >= 0);
-    SMX_CHECK_ARG(std::isfinite(q->gradient_max_relative_depth_step) && q->gradient_max_relative_depth_step > 0);
-  }
-  const bool photo = q && q->photometric_weight != 0.0f;
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  const size_t px = (size_t)r->W * r->H;
-  if (!r->trk_state.get()) {   // (all four or none: a call that fails here leaves nothing behind for the next one to trip over)
-    DevBuf<float> depth_img; DevBuf<float4> normal_img; DevBuf<double> slabs; DevBuf<TrackDev> state;
-    SMX_CALL(depth_img.alloc(px, false));
-    SMX_CALL(normal_img.alloc(px, false));
-    SMX_CALL(slabs.alloc((size_t)kTrackMaxSlabs * kTrackRgbdSlabStride, false));
-    SMX_CALL(state.alloc(1, false));
-    r->trk_depth = std::move(depth_img); r->trk_normal = std::move(normal_img);
-    r->trk_slabs = std::move(slabs); r->trk_state = std::move(state);
-  }
-  if (q && !r->trk_photo.get()) {   // (both or none, likewise)
-    DevBuf<uint32_t> color_img; DevBuf<float4> photo_img;
-    SMX_CALL(color_img.alloc(px, false));
-    SMX_CALL(photo_img.alloc(px, false));
-    r->trk_color = std::move(color_img); r->trk_photo = std::move(photo_img);
-  }
-  if (r->track_busy) SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));   // (the previous call's kernels, on any stream)
-  // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
-  smx_render_params rp;
-  memset(&rp, 0, sizeof(rp));
-  rp.width = r->W; rp.height = r->H; rp.fx = r->fx; rp.fy = r->fy; rp.cx = r->cx; rp.cy = r->cy;
-  for (int k = 0; k < 12; ++k) rp.global_T_camera[k] = global_T_pred[k];
-  rp.near_z = p.near_z; rp.far_z = p.far_z; rp.splat_mode = SMX_SPLAT_DISC;
-  rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
-  rp.surfel_integration_active_window_size = 2147483647;
-  smx_buffer_desc dd, nd, cd;
-  dd.address = r->trk_depth.get(); dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
-  nd.address = r->trk_normal.get(); nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
-  cd.address = r->trk_color.get(); cd.height = r->H; cd.width = r->W; cd.pitch = (size_t)r->W * sizeof(uint32_t);
-  SMX_CALL(smx_recon_render(r, s, &rp, &dd, nullptr, &nd, photo ? &cd : nullptr));   // (color_flags 0: the colour row)
-  if (model_depth_out)
-    SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
-                             hipMemcpyDeviceToDevice, st));
-  if (model_normal_out)
-    SMX_HIP(hipMemcpy2DAsync(model_normal_out->address, model_normal_out->pitch, nd.address, nd.pitch, nd.pitch, (size_t)r->H,
-                             hipMemcpyDeviceToDevice, st));
-  TrackBuffers tb;
-  tb.model_depth = r->trk_depth.get(); tb.model_normal = r->trk_normal.get(); tb.slabs = r->trk_slabs.get(); tb.state = r->trk_state.get();
-  tb.model_color = r->trk_color.get(); tb.model_photo = r->trk_photo.get();
-  SMX_CALL(track_enqueue(st, tb, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
-                         result_on_device && !q ? result : nullptr, color, q, result_on_device ? result_rgbd : nullptr));
-  if (photo && model_photo_out) {
-    const size_t row = (size_t)r->W * sizeof(float4);
-    SMX_HIP(hipMemcpy2DAsync(model_photo_out->address, model_photo_out->pitch, r->trk_photo.get(), row, row, (size_t)r->H,
-                             hipMemcpyDeviceToDevice, st));
-  }
-  SMX_HIP(hipEventRecord(r->ev_track, st));
-  r->track_busy = true;
-  r->track_last_rgbd = q != nullptr;
-  if (!result_on_device) {
-    const smx_track_rgbd_result* res = &r->trk_state.get()->result;
-    if (q) SMX_HIP(hipMemcpyAsync(result_rgbd, res, sizeof(*res), hipMemcpyDeviceToHost, st));
-    else SMX_HIP(hipMemcpyAsync(result, &res->icp, sizeof(res->icp), hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  return SMX_OK;
-}
-
-int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
-                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
-                    const smx_buffer_desc* model_normal_out) {
-  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, params, result, result_on_device, model_depth_out,
-                    model_normal_out, nullptr, nullptr, nullptr, nullptr);
-}
-
-int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
-                         const smx_buffer_desc* normals, const smx_buffer_desc* color, const float global_T_pred[12],
-                         const smx_track_rgbd_params* params, smx_track_rgbd_result* result, int32_t result_on_device,
-                         const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
-                         const smx_buffer_desc* model_photo_out) {
-  SMX_CHECK_ARG(params != nullptr);
-  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, &params->icp, result ? &result->icp : nullptr,
-                    result_on_device, model_depth_out, model_normal_out, color, params, result, model_photo_out);
-}
-
-// The records of the last tracking call, the first *count of them (at most kTrackRing) copied into recs.
-static int track_records(smx_recon r, smx_stream s, smx_track_rgbd_iteration* recs, int32_t* count) {
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  *count = 0;
-  if (!r->trk_state.get() || !r->track_busy) return SMX_OK;
-  SMX_HIP(hipStreamWaitEvent(st, r->ev_track, 0));
-  int32_t n = 0;
-  SMX_HIP(hipMemcpyAsync(&n, &r->trk_state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
-  SMX_HIP(hipStreamSynchronize(st));
-  n = std::max(0, std::min(n, (int32_t)kTrackRing));
-  if (n > 0) {
-    SMX_HIP(hipMemcpyAsync(recs, r->trk_state.get()->ring, sizeof(smx_track_rgbd_iteration) * (size_t)n, hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-  }
-  *count = n;
-  return SMX_OK;
-}
-
-int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
-                                          int32_t* count) {
-  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
-  *count = 0;
-  if (!r->track_last_rgbd) return SMX_OK;
-  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
-  SMX_CALL(track_records(r, s, recs.data(), count));
-  std::copy_n(recs.begin(), std::min(*count, capacity), records);
-  return SMX_OK;
-}
-
-// (the same records without their last two sums, which a call without colour leaves 0)
-int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
-                                     int32_t* count) {
-  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
-  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
-  SMX_CALL(track_records(r, s, recs.data(), count));
-  for (int32_t i = 0; i < std::min(*count, capacity); ++i) {
-    const smx_track_rgbd_iteration& f = recs[i];
-    smx_track_iteration& t = records[i];
-    t.level = f.level; t.stride = f.stride; t.status = f.status; t.reserved = f.reserved;
-    std::copy_n(f.sums, SMX_TRACK_SUMS, t.sums);
-    std::copy_n(f.x, 6, t.x);
-  }
-  return SMX_OK;
+  return render_end(r, st);
 }
 
 int smx_recon_build_neighbor_index(smx_recon r, smx_stream s, smx_nn nn, float cell_size) {
@@ -740,9 +551,9 @@ int smx_recon_build_neighbor_index(smx_recon r, smx_stream s, smx_nn nn, float c
   SMX_CALL(read_surfel_count(r, st, &n));
   if (n == 0) return smx_nn_build(nn, s, nullptr, nullptr, nullptr, 0, cell_size, 1);
   SMX_CALL(acquire_staging(r, st, (size_t)3 * n));
-  hipLaunchKernelGGL(k_index_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, r->staging.get(), n);
+  hipLaunchKernelGGL(k_index_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, r->staging.buf.get(), n);
   SMX_LAUNCH_CHECK();
-  SMX_CALL(smx_nn_build(nn, s, r->staging.get(), r->staging.get() + n, r->staging.get() + (size_t)2 * n, n, cell_size, 1));
+  SMX_CALL(smx_nn_build(nn, s, r->staging.buf.get(), r->staging.buf.get() + n, r->staging.buf.get() + (size_t)2 * n, n, cell_size, 1));
   return release_staging(r, st);
 }
 
@@ -758,30 +569,27 @@ int smx_recon_neighbor_candidates(smx_recon r, smx_stream s, smx_nn nn, const ui
   SMX_CALL(join_regularizer(r, st));
   // workspace owned by the object, grown only when a batch is larger than any before it (then, and only then, the
   // device is synchronised: earlier batches may still be reading the old buffers)
-  if (n_indices > r->cand_slots.capacity()) {   // (cand_slots is allocated last: its capacity stands for both)
+  CandidateWork& w = r->candidates;
+  if (n_indices > w.slots.capacity()) {
     SMX_HIP(hipDeviceSynchronize());
-    r->cand_slots.reset();
+    w.q.reset(); w.slots.reset();   // (first, so that the old and the new pair never exist together)
     const size_t cap = (size_t)n_indices + n_indices / 8 + 1024;
-    SMX_CALL(r->cand_q.alloc(4 * cap, false));
-    SMX_CALL(r->cand_slots.alloc(cap, false));
+    SMX_CALL(alloc_all(w.q, 4 * cap, w.slots, cap));
   }
   const uint8_t* dstate = state;
-  const uint32_t* dslots = surfel_indices;
-  if (!inputs_on_device) {
-    SMX_HIP(hipMemcpyAsync(r->cand_slots.get(), surfel_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, st));
-    dslots = r->cand_slots.get();
-    if (state) {
-      uint32_t n = 0;
-      SMX_CALL(read_surfel_count(r, st, &n));
-      if (n > r->cand_state.capacity()) {
-        SMX_HIP(hipDeviceSynchronize());
-        SMX_CALL(r->cand_state.alloc((size_t)r->S.pitch, false));
-      }
-      if (n > 0) SMX_HIP(hipMemcpyAsync(r->cand_state.get(), state, n, hipMemcpyHostToDevice, st));
-      dstate = r->cand_state.get();
+  const uint32_t* dslots = nullptr;
+  SMX_CALL(stage_in(w.slots, surfel_indices, n_indices, inputs_on_device != 0, st, &dslots));   // (there is room: no allocation)
+  if (!inputs_on_device && state) {
+    uint32_t n = 0;
+    SMX_CALL(read_surfel_count(r, st, &n));
+    if (n > w.state.capacity()) {
+      SMX_HIP(hipDeviceSynchronize());
+      SMX_CALL(w.state.alloc((size_t)r->S.pitch, false));
     }
+    if (n > 0) SMX_HIP(hipMemcpyAsync(w.state.get(), state, n, hipMemcpyHostToDevice, st));
+    dstate = w.state.get();
   }
-  float* q = r->cand_q.get();
+  float* q = w.q.get();
   const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_indices + kBlock - 1) / kBlock, 4096);
   hipLaunchKernelGGL(k_candidate_queries, dim3(blocks), dim3(kBlock), 0, st, r->S, dslots, n_indices, r->st,
                      radius_factor_squared, q);
@@ -800,14 +608,12 @@ int smx_recon_check_triangles(smx_recon r, smx_stream s, const uint32_t* triangl
   SMX_CALL(join_regularizer(r, st));
   DevTemp<uint32_t> dtri(st);
   DevTemp<uint8_t> dflags(st);
-  if (!on_device) {
-    SMX_CALL(dtri.alloc((size_t)n_triangles * 3));
-    SMX_CALL(dflags.alloc(n_triangles));
-    SMX_HIP(hipMemcpyAsync(dtri.get(), triangles, (size_t)n_triangles * 12, hipMemcpyHostToDevice, st));
-  }
+  const uint32_t* tri = nullptr;
+  SMX_CALL(stage_in(dtri.buf, triangles, (size_t)n_triangles * 3, on_device != 0, st, &tri));
+  if (!on_device) SMX_CALL(dflags.alloc(n_triangles));
   const unsigned blocks = (unsigned)std::min<size_t>(((size_t)n_triangles + kBlock - 1) / kBlock, 8192);
-  hipLaunchKernelGGL(k_check_triangles, dim3(blocks), dim3(kBlock), 0, st, r->S, on_device ? triangles : dtri.get(),
-                     n_triangles, r->st, long_edge_total_factor_squared, on_device ? flags : dflags.get());
+  hipLaunchKernelGGL(k_check_triangles, dim3(blocks), dim3(kBlock), 0, st, r->S, tri, n_triangles, r->st,
+                     long_edge_total_factor_squared, on_device ? flags : dflags.get());
   SMX_LAUNCH_CHECK();
   if (!on_device) {
     SMX_HIP(hipMemcpyAsync(flags, dflags.get(), n_triangles, hipMemcpyDeviceToHost, st));
@@ -831,10 +637,9 @@ int smx_recon_triangulate(smx_recon r, smx_stream s, smx_nn nn, float cell_size,
   SMX_CALL(smx_recon_build_neighbor_index(r, s, nn, cell_size));
   uint32_t n = 0;
   SMX_CALL(read_surfel_count(r, st, &n));
-  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
-  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
-  return mesh_triangulate(r->mesh, st, nn, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0, r->S.quad(kGroupN, 1) - n0, n,
-                          *p, triangles, capacity, on_device, n_triangles, stats);
+  const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
+  return mesh_triangulate(r->mesh, st, nn, sv.p, sv.stride, nv.p, nv.stride, n, *p, triangles, capacity, on_device, n_triangles,
+                          stats);
 }
 
 int smx_recon_debug_mesh_timings(smx_recon r, float out_ms[4]) {
@@ -865,11 +670,10 @@ int smx_recon_triangulate_update(smx_recon r, smx_stream s, smx_nn nn, float cel
   SMX_CALL(join_regularizer(r, st));
   uint32_t n = 0;
   SMX_CALL(read_surfel_count(r, st, &n));
-  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
-  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
-  return mesh_triangulate_update(r->mesh, r->device, st, nn, cell_size, quads + s0, r->S.quad(kGroupS, 1) - s0, quads + n0,
-                                 r->S.quad(kGroupN, 1) - n0, n, *p, full_above_fraction, mesh_subset_lists, r, triangles,
-                                 capacity, on_device, n_triangles, stats, update_stats);
+  const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
+  return mesh_triangulate_update(r->mesh, r->device, st, nn, cell_size, sv.p, sv.stride, nv.p, nv.stride, n, *p,
+                                 full_above_fraction, mesh_subset_lists, r, triangles, capacity, on_device, n_triangles, stats,
+                                 update_stats);
 }
 
 int smx_recon_triangulate_reset(smx_recon r) {
@@ -885,158 +689,14 @@ int smx_recon_debug_mesh_update_timings(smx_recon r, float out_ms[6]) {
   return mesh_update_phase_ms(r->mesh, out_ms);
 }
 
-// ---- decimation of a triangle array by vertex clustering (include/smx.h; kernels in smx_decimate.hip) ----
-int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size, const uint32_t* triangles_in, uint32_t n_in,
-                            uint32_t* triangles_out, uint32_t capacity, uint32_t* vertex_map, int32_t on_device,
-                            uint32_t* n_triangles, smx_decimate_stats* stats) {
-  SMX_CHECK_ARG(r != nullptr && n_triangles != nullptr);
-  SMX_CHECK_ARG(cell_size > 0.0f && cell_size - cell_size == 0.0f);
-  SMX_CHECK_ARG(triangles_in != nullptr || n_in == 0);
-  SMX_CHECK_ARG(triangles_out != nullptr || capacity == 0);
-  if (n_in > 0 && capacity > 0) {
-    const uintptr_t i0 = (uintptr_t)triangles_in, i1 = i0 + (size_t)n_in * 12, o0 = (uintptr_t)triangles_out, o1 = o0 + (size_t)capacity * 12;
-    if (i0 < o1 && o0 < i1) {
-      set_error("triangles_out overlaps triangles_in");
-      return SMX_ERR_INVALID_ARGUMENT;
-    }
-  }
-  SMX_ON_DEVICE(r->device);
-  hipStream_t st = (hipStream_t)s;
-  SMX_CALL(join_regularizer(r, st));
-  uint32_t n = 0;
-  SMX_CALL(read_surfel_count(r, st, &n));
-  *n_triangles = 0;
-  if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_in = n_in; }
-  if (!r->ev_dec[0]) for (hipEvent_t& e : r->ev_dec) SMX_HIP(hipEventCreate(&e));
-  r->dec_phases = 0;
-  SMX_HIP(hipEventRecord(r->ev_dec[0], st));
-  int phases = 0;
-  auto stamp = [&]() -> int { SMX_HIP(hipEventRecord(r->ev_dec[++phases], st)); return SMX_OK; };
-  auto finish = [&](int rc) -> int {     // (the stamps are complete before they are published)
-    SMX_HIP(hipStreamSynchronize(st));
-    r->dec_phases = phases;
-    return rc;
-  };
-
-  // ---- workspace of the first two phases; the input on the device
-  const uint32_t cell_entries = dec_table_size((uint32_t)std::min<unsigned long long>(n, 3ull * n_in));
-  const uint32_t dup_entries = dec_table_size(n_in);
-  const int nb = div_up(n_in, kDecBlock);
-  if (!r->dec_counters.get()) SMX_CALL(r->dec_counters.alloc(kDecWords, false));
-  SMX_CALL(r->dec_vmap.reserve(n));
-  if (n_in > 0) {
-    SMX_CALL(r->dec_cells.reserve((size_t)2 * cell_entries));
-    SMX_CALL(r->dec_canon.reserve((size_t)3 * n_in));
-    SMX_CALL(r->dec_own.reserve(n_in));
-    SMX_CALL(r->dec_dup.reserve(dup_entries));
-    SMX_CALL(r->dec_blocks.reserve((size_t)nb));
-  }
-  const uint32_t* din = triangles_in;
-  if (!on_device && n_in > 0) {
-    SMX_CALL(r->dec_in.reserve((size_t)3 * n_in));
-    SMX_HIP(hipMemcpyAsync(r->dec_in.get(), triangles_in, (size_t)n_in * 12, hipMemcpyHostToDevice, st));
-    din = r->dec_in.get();
-  }
-  uint32_t* cnt = r->dec_counters.get();
-  SMX_HIP(hipMemsetAsync(cnt, 0, kDecWords * sizeof(uint32_t), st));
-  uint32_t h[kDecWords];
-  auto read_counters = [&]() -> int {
-    SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-    return SMX_OK;
-  };
-
-  // ---- clustering: U, the cell table, the vertex map.  (An index out of range marks nothing and is read by nothing.)
-  const float inv = 1.0f / cell_size;
-  DecMap map;
-  const float4* quads = reinterpret_cast<const float4*>(r->S.base);
-  const size_t s0 = r->S.quad(kGroupS, 0), n0 = r->S.quad(kGroupN, 0);
-  map.smooth = quads + s0; map.smooth_stride = r->S.quad(kGroupS, 1) - s0;
-  map.normal = quads + n0; map.normal_stride = r->S.quad(kGroupN, 1) - n0;
-  map.n = n;
-  DecCell* cells = reinterpret_cast<DecCell*>(r->dec_cells.get());
-  DecTri* canon = reinterpret_cast<DecTri*>(r->dec_canon.get());
-  SMX_CALL(dec_enqueue_cluster(st, map, din, n_in, cell_size, inv, r->dec_vmap.get(), cells, cell_entries, cnt));
-  SMX_CALL(stamp());
-  SMX_CALL(read_counters());
-  if (h[kDecError] & kDecErrIndex) {
-    set_error("triangles_in holds an index >= the %u slots of the map", n);
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-  if (h[kDecError] & kDecErrRange) {
-    set_error("cell_size %g is too small for the extent of the map: a cell coordinate is outside [-2^20, 2^20)", (double)cell_size);
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-
-  // ---- remap and duplicates; survivors counted and scanned
-  SMX_CALL(dec_enqueue_remap(st, din, n_in, r->dec_vmap.get(), canon, r->dec_own.get(), r->dec_dup.get(), dup_entries, cnt));
-  SMX_CALL(stamp());
-  if (n_in > 0) {
-    SMX_CALL(dec_enqueue_count(st, n_in, r->dec_own.get(), r->dec_dup.get(), r->dec_blocks.get()));
-    enqueue_segment_scan(st, r->dec_blocks.get(), nb, cnt + kDecTotal);
-    SMX_LAUNCH_CHECK();
-  }
-  SMX_CALL(read_counters());
-  const uint32_t T = h[kDecTotal];
-  *n_triangles = T;
-  if (stats) {
-    stats->n_not_live = h[kDecNotLive]; stats->n_used_vertices = h[kDecUsed]; stats->n_cells = h[kDecCells];
-    stats->n_collapsed = h[kDecCollapsed]; stats->n_duplicates = h[kDecAlive] - T; stats->n_triangles = T;
-  }
-  if (capacity < T) {
-    if (triangles_out != nullptr || capacity != 0) set_error("triangles_out holds %u entries, the decimated mesh has %u", capacity, T);
-    else set_error("count only: the decimated mesh has %u triangles", T);
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-
-  // ---- the survivors in input order as sort records, ordered by (a, b) and then, stably, by p
-  if (T > 0) {
-    int bits = 1;
-    while (bits < 32 && ((uint32_t)(n - 1) >> bits) != 0) ++bits;
-    for (int k = 0; k < 2; ++k) { SMX_CALL(r->dec_keys[k].reserve(T)); SMX_CALL(r->dec_vals[k].reserve(T)); }
-    SMX_CALL(r->dec_hist.reserve(radix_sort_workspace_elems(T)));
-    SMX_CALL(dec_enqueue_write(st, n_in, r->dec_own.get(), r->dec_dup.get(), r->dec_blocks.get(), canon, bits, r->dec_keys[0].get(),
-                               r->dec_vals[0].get()));
-    SMX_CALL(stamp());
-    int cur = radix_sort(r->dec_keys, r->dec_vals, T, 2 * bits, r->dec_hist.get(), st);
-    SMX_LAUNCH_CHECK();
-    SMX_CALL(dec_enqueue_keys_p(st, T, r->dec_vals[cur].get(), canon, r->dec_keys[0].get(), r->dec_vals[0].get()));
-    cur = radix_sort(r->dec_keys, r->dec_vals, T, bits, r->dec_hist.get(), st);
-    SMX_LAUNCH_CHECK();
-    uint32_t* dst = triangles_out;
-    if (!on_device) {
-      SMX_CALL(r->dec_out.reserve((size_t)3 * T));
-      dst = r->dec_out.get();
-    }
-    SMX_CALL(dec_enqueue_emit(st, T, r->dec_vals[cur].get(), canon, dst));
-    if (!on_device) SMX_HIP(hipMemcpyAsync(triangles_out, dst, (size_t)T * 12, hipMemcpyDeviceToHost, st));
-  } else {
-    SMX_CALL(stamp());
-  }
-  if (vertex_map && n > 0)
-    SMX_HIP(hipMemcpyAsync(vertex_map, r->dec_vmap.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  SMX_CALL(stamp());
-  return finish(SMX_OK);
-}
-
-int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity) {
-  SMX_CHECK_ARG(r != nullptr && out_ms != nullptr && capacity >= SMX_DECIMATE_PHASES);
-  SMX_ON_DEVICE(r->device);
-  for (int i = 0; i < SMX_DECIMATE_PHASES; ++i) {
-    out_ms[i] = 0.0f;
-    if (i < r->dec_phases) SMX_HIP(hipEventElapsedTime(&out_ms[i], r->ev_dec[i], r->ev_dec[i + 1]));
-  }
-  return SMX_OK;
-}
-
 int smx_recon_debug_download_surfels(smx_recon r, smx_stream s, float* rows, uint32_t count) {
   SMX_CHECK_ARG(r != nullptr && rows != nullptr && count <= r->max_surfels);
   SMX_ON_DEVICE(r->device);
   if (count == 0) return SMX_OK;
   SMX_CALL(join_regularizer(r, (hipStream_t)s));
   SMX_CALL(acquire_staging(r, (hipStream_t)s, (size_t)kRows * count));
-  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S, all_rows(), r->staging.get(), count);
-  SMX_HIP(hipMemcpyAsync(rows, r->staging.get(), (size_t)kRows * count * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
+  hipLaunchKernelGGL(k_pack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, (hipStream_t)s, r->S, all_rows(), r->staging.buf.get(), count);
+  SMX_HIP(hipMemcpyAsync(rows, r->staging.buf.get(), (size_t)kRows * count * 4, hipMemcpyDeviceToHost, (hipStream_t)s));
   SMX_HIP(hipStreamSynchronize((hipStream_t)s));
   return SMX_OK;
 }
@@ -1048,8 +708,8 @@ int smx_recon_debug_upload_surfels(smx_recon r, smx_stream s, const float* rows,
   hipStream_t st = (hipStream_t)s;
   if (count) {
     SMX_CALL(acquire_staging(r, st, (size_t)kRows * count));
-    SMX_HIP(hipMemcpyAsync(r->staging.get(), rows, (size_t)kRows * count * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_unpack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, all_rows(), r->staging.get(), count);
+    SMX_HIP(hipMemcpyAsync(r->staging.buf.get(), rows, (size_t)kRows * count * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_unpack_rows, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, all_rows(), r->staging.buf.get(), count);
   }
   DevState h;
   memset(&h, 0, sizeof(h));
@@ -1074,27 +734,24 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
     set_error("old_to_new holds %u entries, the map has %u slots", capacity, n);
     return SMX_ERR_INVALID_ARGUMENT;
   }
-  if (!r->cmp_out.get()) {   // (allocated last: it stands for all three)
-    SMX_CALL(r->cmp_map.alloc(r->S.pitch, false));
-    SMX_CALL(r->cmp_seg.alloc((size_t)r->nseg, false));
-    SMX_CALL(r->cmp_out.alloc(2, false));
-  }
-  SMX_HIP(hipMemsetAsync(r->cmp_out.get(), 0, 2 * sizeof(uint32_t), st));
+  CompactWork& w = r->compact;
+  if (!w.out.get()) SMX_CALL(alloc_all(w.map, r->S.pitch, w.seg, (size_t)r->nseg, w.out, 2));
+  SMX_HIP(hipMemsetAsync(w.out.get(), 0, 2 * sizeof(uint32_t), st));
   const dim3 b(kBlock);
   if (n) {
     const int nseg_used = div_up((long long)n, kSeg);
     // (merge_flag -- one byte per slot, reset below -- holds the keep bits: a byte per four slots)
-    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, r->cmp_seg.get());
-    enqueue_segment_scan(st, r->cmp_seg.get(), nseg_used, r->cmp_out.get());
-    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, r->cmp_seg.get(), n, r->cmp_map.get());
+    hipLaunchKernelGGL(k_compact_count, dim3(nseg_used), b, 0, st, r->S, n, r->merge_flag, w.seg.get());
+    enqueue_segment_scan(st, w.seg.get(), nseg_used, w.out.get());
+    hipLaunchKernelGGL(k_compact_map, dim3(nseg_used), b, 0, st, r->merge_flag, w.seg.get(), n, w.map.get());
     SMX_LAUNCH_CHECK();
     SMX_CALL(acquire_staging(r, st, (size_t)4 * n));
-    float4* tmp = reinterpret_cast<float4*>(r->staging.get());
+    float4* tmp = reinterpret_cast<float4*>(r->staging.buf.get());
     const int groups[5] = {kGroupP, kGroupS, kGroupN, kGroupC, kGroupT};
     for (int g : groups) {
-      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map.get(), n, tmp, r->cmp_out.get() + 1);
-      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, r->cmp_map.get(), n, tmp, r->cmp_out.get() + 1);
-      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, r->cmp_out.get());
+      if (g == kGroupT) hipLaunchKernelGGL(k_compact_scatter<true>, dim3(nseg_used), b, 0, st, r->S, g, w.map.get(), n, tmp, w.out.get() + 1);
+      else hipLaunchKernelGGL(k_compact_scatter<false>, dim3(nseg_used), b, 0, st, r->S, g, w.map.get(), n, tmp, w.out.get() + 1);
+      hipLaunchKernelGGL(k_compact_copy, dim3(r->grid_surfels), b, 0, st, r->S, g, tmp, w.out.get());
     }
     SMX_LAUNCH_CHECK();
     SMX_CALL(release_staging(r, st));
@@ -1111,10 +768,10 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
   //    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
   // The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
   // has been read again, and reading a segment resets its streak).
-  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, r->cmp_out.get());
+  hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, w.out.get());
   SMX_CALL(reset_accumulators(r, st));
   if (r->L.dirty8)
-    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), r->cmp_out.get());
+    hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), w.out.get());
   SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
   SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
   SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
@@ -1124,9 +781,9 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
   uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
   SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
   if (old_to_new && n)
-    SMX_HIP(hipMemcpyAsync(old_to_new, r->cmp_map.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipMemcpyAsync(old_to_new, w.map.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   uint32_t out[2] = {0, 0};
-  SMX_HIP(hipMemcpyAsync(out, r->cmp_out.get(), sizeof(out), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipMemcpyAsync(out, w.out.get(), sizeof(out), hipMemcpyDeviceToHost, st));
   SMX_HIP(hipStreamSynchronize(st));
   if (new_size) *new_size = out[0];
   if (links_dropped) *links_dropped = out[1];
@@ -1142,16 +799,11 @@ int smx_recon_deform_by_creation_frame(smx_recon r, smx_stream s, const float* f
   SMX_CALL(join_regularizer(r, st));
   DevTemp<float> dT(st);
   DevTemp<uint8_t> dre(st);
-  if (!inputs_on_device) {
-    SMX_CALL(dT.alloc((size_t)n_frames * 12));
-    SMX_HIP(hipMemcpyAsync(dT.get(), frame_T, (size_t)n_frames * 48, hipMemcpyHostToDevice, st));
-    if (reactivate) {
-      SMX_CALL(dre.alloc(n_frames));
-      SMX_HIP(hipMemcpyAsync(dre.get(), reactivate, n_frames, hipMemcpyHostToDevice, st));
-    }
-  }
-  hipLaunchKernelGGL(k_deform_by_creation_frame, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S,
-                     inputs_on_device ? frame_T : dT.get(), n_frames, inputs_on_device ? reactivate : dre.get(), frame_index,
+  const float* T = nullptr;
+  const uint8_t* re = nullptr;
+  SMX_CALL(stage_in(dT.buf, frame_T, (size_t)n_frames * 12, inputs_on_device != 0, st, &T));
+  SMX_CALL(stage_in(dre.buf, reactivate, reactivate ? n_frames : 0, inputs_on_device != 0, st, &re));
+  hipLaunchKernelGGL(k_deform_by_creation_frame, dim3(r->grid_surfels), dim3(kBlock), 0, st, r->S, T, n_frames, re, frame_index,
                      r->L.dirty8, r->st);
   SMX_LAUNCH_CHECK();
   // positions and stamps changed behind the work lists, segment boxes and the flag table

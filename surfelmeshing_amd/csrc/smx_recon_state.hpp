@@ -1,17 +1,21 @@
-// smx_recon_state.hpp -- the surfel reconstruction object as its two translation units see it (internal).
+// smx_recon_state.hpp -- the surfel reconstruction object as its translation units see it (internal).
 //
 // smx_recon.hip holds the frame loop (Integrate / Regularize, their kernels, the changed-surfel delta),
 // smx_recon_map.hip the map services that read or rewrite the finished map outside of it (row transfers, export,
-// rendering, tracking and meshing glue, compaction, deformation).  This header is what both need: the attribute
-// layout, the plain structs that are members of smx_recon_s, the object itself, and the few host helpers every
-// entry point starts with.  Kernels stay in anonymous namespaces of the two .hip files.
+// viewer buffers, the splat render, neighbour and meshing glue, compaction, deformation); tracking, decimation and the
+// mesh render live with their kernels in smx_track.hip, smx_decimate.hip and smx_mesh_raster.hip.  This header is what
+// they all need: the attribute layout, the plain structs that are members of smx_recon_s, the object itself -- the
+// frame loop's state, then one workspace per service, each defined in the service's own header -- and the few host
+// helpers every entry point starts with.  Kernels stay in anonymous namespaces of the .hip files.
 #pragma once
 
 #include "smx_common.hpp"
+#include "smx_decimate.hpp"
+#include "smx_render.hpp"
+#include "smx_track.hpp"
 
 namespace smx {
 
-struct TrackDev;        // smx_track.hpp
 struct MeshWorkspace;   // smx_mesh.hpp
 
 // Attribute ids = the reference's SoA row numbers, APP/cuda_surfel_reconstruction_kernels.cuh:49-78 (the
@@ -77,6 +81,9 @@ struct Surfels {
   __device__ __forceinline__ float4* group(int g, uint32_t i) const { return reinterpret_cast<float4*>(base) + quad(g, i); }
   __device__ __forceinline__ void set_neighbors(uint32_t i, const uint4& t) const { *reinterpret_cast<uint4*>(group(kGroupT, i)) = t; }
   __device__ __forceinline__ void set_neighbor(uint32_t i, int q, uint32_t v) const { u(kNeighbor0 + q, i) = v; }
+  // a group for the code that does not know this layout (the mesher, decimation): slot i's record is p[i * stride]
+  struct View { const float4* p; size_t stride; };
+  View view(int g) const { return View{reinterpret_cast<const float4*>(base) + quad(g, 0), quad(g, 1) - quad(g, 0)}; }
 };
 
 // The association images of a frame (built per image tile by k_assoc_tiles).
@@ -238,11 +245,23 @@ __device__ __forceinline__ uint32_t vis_color(const Surfels& S, uint32_t i, cons
   return S.u(kColor, i);
 }
 
+// ---- workspaces of the services in smx_recon_map.hip (allocated by the first call that needs them) ----
+// Row-layout staging for the boundary conversions (TransferAllToCPU, the delta hand-off, debug rows, compaction).  The mark
+// is recorded after the last enqueued read: TransferAllToCPU returns with its row downloads in flight, and the next user
+// may come on another stream.
+struct StagingWork { DevBuf<float> buf; StreamMark mark; };
+// smx_recon_compact, all or none: old_to_new [pitch], per-segment counts / offsets [nseg], [0] = new count, [1] = links dropped
+struct CompactWork { DevBuf<uint32_t> map, seg, out; };
+// smx_recon_neighbor_candidates: queries [4][capacity] and staged slots [capacity], both or none; a host array's state bytes
+struct CandidateWork { DevBuf<float> q; DevBuf<uint32_t> slots; DevBuf<uint8_t> state; };
+
 }  // namespace smx
 
-// Created value-initialised (everything zero / empty).  `mem` owns the blocks smx_recon_create allocates -- the pointers
-// in S, L, fb, sc, tb, sw, bb and the plain pointer members below are views of them -- and every buffer a service
-// allocates on demand is a DevBuf.
+// Created value-initialised (everything zero / empty) and deleted as a whole: `mem` owns the blocks smx_recon_create
+// allocates -- the pointers in S, L, fb, sc, tb, sw, bb and the plain pointer members below are views of them -- every
+// buffer a service allocates on demand is a DevBuf, and every event a service creates belongs to a StreamMark or a
+// PhaseStamps of its workspace.  The frame loop's own events and stream are created and destroyed by smx_recon_create /
+// _destroy.
 struct smx_recon_s {
   smx::DevBlocks mem;
   int device;               // the HIP device the object lives on (every entry point runs on it)
@@ -311,10 +330,6 @@ struct smx_recon_s {
   smx::DevBuf<uint8_t> dirty;         // delta tracking: the block behind L.dirty8 while it is on
   smx::DevBuf<uint32_t> delta_seg;    // delta hand-off: per-segment counts / offsets, and the total
   smx::DevBuf<uint32_t> delta_total;
-  smx::DevBuf<float> staging;    // row-layout staging for the boundary conversions (TransferAllToCPU, debug rows)
-  smx::DevBuf<float> cand_q; smx::DevBuf<uint32_t> cand_slots; smx::DevBuf<uint8_t> cand_state;   // workspace of smx_recon_neighbor_candidates
-  hipEvent_t ev_staging;  // recorded after the last enqueued read of `staging`: TransferAllToCPU returns with its
-  bool staging_busy;      // row downloads in flight, and the next user may come on another stream
   int grid_surfels;  // persistent grid for the grid-stride all-slot kernels
   int grid_list;     // persistent grid of the chunked list kernels
   int grid_acc;      // ... of the edge kernel (512-lane workgroups)
@@ -337,52 +352,27 @@ struct smx_recon_s {
   uint8_t* flags_buf[2];    // the flag table is double-buffered by frame (L.flags8 = the current frame's)
   bool have_frame;          // an Integrate call has been made since creation / the last state upload
   uint32_t last_frame;      // its frame_index: the segment culling of pass A presumes that it never decreases
-  smx::DevBuf<uint32_t> cmp_map;   // smx_recon_compact (allocated by its first call): old_to_new [pitch], per-segment counts /
-  smx::DevBuf<uint32_t> cmp_seg;   // offsets [nseg], and [0] = new count, [1] = links dropped
-  smx::DevBuf<uint32_t> cmp_out;
-  smx::DevBuf<unsigned long long> zbuf;   // smx_recon_render: the z-buffer (grows on demand) and the mark after the last render's
-  hipEvent_t ev_render;                   // resolve (the next render, on whatever stream, waits for it before clearing the buffer)
-  bool render_busy;
-  smx::DevBuf<float> trk_depth;         // smx_recon_track / _rgbd (allocated by the first call of either, all four or none): the model
-  smx::DevBuf<float4> trk_normal;       // images [H][W] of the last call, the reduce kernel's per-workgroup partial sums, the call's
-  smx::DevBuf<double> trk_slabs;        // device state (records and result of either kind), and the mark after the last call's kernels
-  smx::DevBuf<smx::TrackDev> trk_state; // (the next call, on whatever stream, waits for it)
-  hipEvent_t ev_track;
-  bool track_busy;
-  smx::DevBuf<uint32_t> trk_color;      // smx_recon_track_rgbd (allocated by its first call, both or none): the model colour image
-  smx::DevBuf<float4> trk_photo;        // [H][W] and P = (L, gx, gy, valid) of the last call with a weight
-  bool track_last_rgbd;                 // the last tracking call was smx_recon_track_rgbd
-  smx::MeshWorkspace* mesh;      // smx_recon_triangulate (created by its first call): lists, rings, counts, output staging  // smx_recon_decimate_mesh (each grows on demand, the call is synchronous, so nothing reads a block that goes)
-  smx::DevBuf<uint32_t> dec_vmap;                  // [n] the vertex map
-  smx::DevBuf<unsigned long long> dec_cells;       // [cell table entries][2]: key, value word (smx::DecCell)
-  smx::DevBuf<uint32_t> dec_canon, dec_own;        // [n_in][3] canonical triples (smx::DecTri); [n_in] each triangle's entry of
-  smx::DevBuf<uint32_t> dec_dup;                   // the table of triangle indices
-  smx::DevBuf<uint32_t> dec_blocks;                // survivors per workgroup, then their offsets
-  smx::DevBuf<unsigned long long> dec_keys[2];     // [T_out] the sort's records
-  smx::DevBuf<uint32_t> dec_vals[2];
-  smx::DevBuf<uint32_t> dec_hist;                  // the sort's workspace
-  smx::DevBuf<uint32_t> dec_in, dec_out;           // staging when the caller's arrays are host memory
-  smx::DevBuf<uint32_t> dec_counters;              // [kDecWords]
-  hipEvent_t ev_dec[5];                            // stamps of the last call (created by the first)
-  int dec_phases;                                  // how many phases of it they bracket
-  // smx_recon_render_mesh (each grows on demand, behind the render event: see the call)
-  smx::DevBuf<uint32_t> mr_list;                   // [n_triangles] the triangles k_mrast_large walks
-  smx::DevBuf<uint32_t> mr_counters;               // [kMrWords] the verdict counts, the covered pixels, the list's length
-  smx::DevBuf<uint32_t> mr_in;                     // staging when the caller's array is host memory
-  hipEvent_t ev_mr[4];                             // stamps around the last call's three kernels (created by the first)
-  bool mr_timed;                                   // they bracket a complete call
+  // ---- the map services: one workspace each, reached by the service's own file only ----
+  smx::StagingWork staging;       // smx_recon_map.hip and the delta hand-off
+  smx::RenderWork render;         // smx_recon_render and smx_recon_render_mesh (and, through the first, tracking)
+  smx::TrackWork track;           // smx_recon_track / _rgbd
+  smx::DecimateWork decimate;     // smx_recon_decimate_mesh
+  smx::CompactWork compact;       // smx_recon_compact
+  smx::CandidateWork candidates;  // smx_recon_neighbor_candidates
+  smx::MeshWorkspace* mesh;       // smx_recon_triangulate / _update (created by the first call): lists, rings, counts, output staging
 };
 
 namespace smx {
 
-// ---- host helpers shared by the two files (defined in smx_recon.hip) ----------------------------------------------
+// ---- host helpers shared by the object's files (defined in smx_recon.hip) -----------------------------------------
 // Orders stream st after the regulariser that may still run on the internal stream.
 int join_regularizer(smx_recon r, hipStream_t st);
 // The slot count (merged slots included), read back on st; returns with st synchronised.
 int read_surfel_count(smx_recon r, hipStream_t st, uint32_t* n);
 // Exclusive scan in place of per-segment counts, the total to *total_out (k_delta_scan: the delta hand-off and compaction).
 void enqueue_segment_scan(hipStream_t st, uint32_t* seg_count, int nseg, uint32_t* total_out);
-// Every user of the shared staging buffer first orders its stream after the previous user's last read.
+// Every user of the shared staging buffer first orders its stream after the previous user's last read (and gets room
+// for `floats`), and leaves its mark after its own.
 int acquire_staging(smx_recon r, hipStream_t st, size_t floats);
 int release_staging(smx_recon r, hipStream_t st);
 // After surfel attributes were changed from outside the frame loop (state upload, compaction, deformation).

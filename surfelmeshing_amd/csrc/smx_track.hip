@@ -15,9 +15,14 @@
 //
 // Nothing is cleared between iterations: every slab is rewritten by its workgroup, the grid is fixed per level.  A kernel
 // that finds a bad status (or its level converged) returns at once; nothing waits on the device.
-#include "smx_track.hpp"
-
+//
+// The entry points are at the end of the file: track_call validates, allocates the workspace (TrackWork, smx_track.hpp),
+// renders the model images with smx_recon_render and enqueues the schedule.
 #include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "smx_recon_state.hpp"
 
 namespace smx {
 namespace {
@@ -135,14 +140,14 @@ k_track_photo_prepare(int W, int H, float max_relative_step, const float* __rest
 
 template <int STRIDE>
 void launch_reduce(hipStream_t st, int grid, const TrackK& k, const TrackPhotoK* ph, const smx_buffer_desc* depth,
-                   const smx_buffer_desc* normals, const smx_buffer_desc* color, const TrackBuffers& b, int level) {
+                   const smx_buffer_desc* normals, const smx_buffer_desc* color, const TrackWork& b, int level) {
   if (ph)
     hipLaunchKernelGGL(k_track_reduce_rgbd<STRIDE>, dim3(grid), dim3(kTrackBlock), 0, st, k, *ph, as_img<uint16_t>(depth),
-                       as_img<float2>(normals), as_img<uchar3>(color), b.model_depth, b.model_normal, b.model_photo,
-                       b.state, level, b.slabs);
+                       as_img<float2>(normals), as_img<uchar3>(color), b.depth.get(), b.normal.get(), b.photo.get(),
+                       b.state.get(), level, b.slabs.get());
   else
     hipLaunchKernelGGL(k_track_reduce<STRIDE>, dim3(grid), dim3(kTrackBlock), 0, st, k, as_img<uint16_t>(depth),
-                       as_img<float2>(normals), b.model_depth, b.model_normal, b.state, level, b.slabs);
+                       as_img<float2>(normals), b.depth.get(), b.normal.get(), b.state.get(), level, b.slabs.get());
 }
 
 // The constants of one level of the schedule: the reduce kernel's, the solve kernel's, the grid.
@@ -169,18 +174,20 @@ TrackLevel track_level(int l, int W, int H, float fx, float fy, float cx, float 
   return t;
 }
 
-}  // namespace
-
-int track_enqueue(hipStream_t st, const TrackBuffers& b, int W, int H, float fx, float fy, float cx, float cy,
+// Enqueues begin + every (reduce, solve) pair of the schedule on st; the last solve launch writes b.state->result and, where
+// not null, *result_dev (its .icp) / *result_rgbd_dev (all of it).  q is null for smx_recon_track; with one, p is q->icp,
+// color the frame's image, and a weight other than 0 puts one k_track_photo_prepare launch in front and the photometric
+// term into the sums (at weight 0 b.color / b.photo are not touched).  Arguments are validated by the caller.
+int track_enqueue(hipStream_t st, const TrackWork& b, int W, int H, float fx, float fy, float cx, float cy,
                   float depth_scaling, const smx_buffer_desc* depth, const smx_buffer_desc* normals,
                   const float global_T_pred[12], const smx_track_params& p, smx_track_result* result_dev,
                   const smx_buffer_desc* color, const smx_track_rgbd_params* q, smx_track_rgbd_result* result_rgbd_dev) {
-  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(1), 0, st, b.state);
+  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(1), 0, st, b.state.get());
   const bool photo = q && q->photometric_weight != 0.0f;
   TrackPhotoK ph;
   if (photo) {
     hipLaunchKernelGGL(k_track_photo_prepare, dim3((unsigned)div_up((long long)W * H, kTrackBlock)), dim3(kTrackBlock), 0, st,
-                       W, H, q->gradient_max_relative_depth_step, b.model_depth, b.model_color, b.model_photo);
+                       W, H, q->gradient_max_relative_depth_step, b.depth.get(), b.color.get(), b.photo.get());
     ph.weight = q->photometric_weight; ph.max_intensity_difference = q->max_intensity_difference;
     ph.min_gradient_sq = q->min_gradient * q->min_gradient;
   }
@@ -199,7 +206,7 @@ int track_enqueue(hipStream_t st, const TrackBuffers& b, int W, int H, float fx,
       }
       const bool last = l == last_level && it == iters - 1;
       t.sk.final_launch = last ? 1 : 0;
-      hipLaunchKernelGGL(k_track_solve, dim3(1), dim3(64), 0, st, t.sk, b.slabs, b.state, last ? result_dev : nullptr,
+      hipLaunchKernelGGL(k_track_solve, dim3(1), dim3(64), 0, st, t.sk, b.slabs.get(), b.state.get(), last ? result_dev : nullptr,
                          last ? result_rgbd_dev : nullptr);
     }
   }
@@ -207,9 +214,120 @@ int track_enqueue(hipStream_t st, const TrackBuffers& b, int W, int H, float fx,
   return SMX_OK;
 }
 
+// smx_recon_track (q, color, result_rgbd and model_photo_out null) and smx_recon_track_rgbd (p = &q->icp, result =
+// &result_rgbd->icp).
+int track_call(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+               const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
+               smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
+               const smx_buffer_desc* model_normal_out, const smx_buffer_desc* color,
+               const smx_track_rgbd_params* q, smx_track_rgbd_result* result_rgbd,
+               const smx_buffer_desc* model_photo_out) {
+  SMX_CHECK_ARG(r != nullptr && depth != nullptr && normals != nullptr && global_T_pred != nullptr && params != nullptr &&
+                result != nullptr);
+  const smx_track_params& p = *params;
+  SMX_CHECK_ARG(std::isfinite(depth_scaling) && depth_scaling > 0);
+  SMX_CHECK_ARG(image_desc_ok(depth, r->W, r->H, 2) && image_desc_ok(normals, r->W, r->H, 8));
+  SMX_CHECK_ARG(image_desc_ok_or_null(model_depth_out, r->W, r->H, 4) && image_desc_ok_or_null(model_normal_out, r->W, r->H, 16));
+  for (int k = 0; k < 12; ++k) SMX_CHECK_ARG(std::isfinite(global_T_pred[k]));
+  int levels_used = 0;
+  for (int l = 0; l < kTrackLevels; ++l) {
+    SMX_CHECK_ARG(p.level_iterations[l] >= 0 && p.level_iterations[l] <= kTrackMaxIterationsPerLevel);
+    if (p.level_iterations[l] == 0) continue;
+    ++levels_used;
+    SMX_CHECK_ARG(p.level_stride[l] == 1 || p.level_stride[l] == 2 || p.level_stride[l] == 4 || p.level_stride[l] == 8);
+  }
+  SMX_CHECK_ARG(levels_used > 0);
+  SMX_CHECK_ARG(std::isfinite(p.max_distance) && p.max_distance > 0);
+  SMX_CHECK_ARG(p.max_normal_angle_deg > 0 && p.max_normal_angle_deg <= 180.0f);
+  SMX_CHECK_ARG(p.convergence_rotation >= 0 && p.convergence_translation >= 0 && p.min_inliers >= 0);
+  SMX_CHECK_ARG(p.min_inlier_fraction >= 0 && p.min_inlier_fraction <= 1 && p.min_pivot_ratio >= 0);
+  SMX_CHECK_ARG(std::isfinite(p.near_z) && p.near_z > 0 && p.far_z > p.near_z);
+  SMX_CHECK_ARG(std::isfinite(p.disc_radius_factor) && p.disc_radius_factor > 0);
+  SMX_CHECK_ARG(p.max_splat_extent_in_pixels > 0 && p.max_splat_extent_in_pixels <= 1024);
+  if (q) {
+    // (3-byte elements: any pitch that holds a row, as smx_recon_integrate takes the image)
+    SMX_CHECK_ARG(color != nullptr && color->address && color->width == r->W && color->height == r->H &&
+                  color->pitch >= (size_t)r->W * 3);
+    SMX_CHECK_ARG(image_desc_ok_or_null(model_photo_out, r->W, r->H, 16));
+    SMX_CHECK_ARG(std::isfinite(q->photometric_weight) && q->photometric_weight >= 0);
+    SMX_CHECK_ARG(std::isfinite(q->max_intensity_difference) && q->max_intensity_difference > 0);
+    SMX_CHECK_ARG(std::isfinite(q->min_gradient) && q->min_gradient >= 0);
+    SMX_CHECK_ARG(std::isfinite(q->gradient_max_relative_depth_step) && q->gradient_max_relative_depth_step > 0);
+  }
+  const bool photo = q && q->photometric_weight != 0.0f;
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  const size_t px = (size_t)r->W * r->H;
+  TrackWork& w = r->track;
+  // (all or none: a call that fails here leaves nothing behind for the next one to trip over)
+  if (!w.state.get()) SMX_CALL(alloc_all(w.depth, px, w.normal, px, w.slabs, (size_t)kTrackMaxSlabs * kTrackRgbdSlabStride, w.state, 1));
+  if (q && !w.photo.get()) SMX_CALL(alloc_all(w.color, px, w.photo, px));
+  SMX_CALL(w.mark.wait(st));   // (the previous call's kernels, on any stream)
+  // the model images: smx_recon_render itself (it orders st behind the pipelined regulariser and the previous render)
+  smx_render_params rp;
+  memset(&rp, 0, sizeof(rp));
+  rp.width = r->W; rp.height = r->H; rp.fx = r->fx; rp.fy = r->fy; rp.cx = r->cx; rp.cy = r->cy;
+  for (int k = 0; k < 12; ++k) rp.global_T_camera[k] = global_T_pred[k];
+  rp.near_z = p.near_z; rp.far_z = p.far_z; rp.splat_mode = SMX_SPLAT_DISC;
+  rp.disc_radius_factor = p.disc_radius_factor; rp.max_splat_extent_in_pixels = p.max_splat_extent_in_pixels;
+  rp.surfel_integration_active_window_size = 2147483647;
+  smx_buffer_desc dd, nd, cd;
+  dd.address = w.depth.get(); dd.height = r->H; dd.width = r->W; dd.pitch = (size_t)r->W * sizeof(float);
+  nd.address = w.normal.get(); nd.height = r->H; nd.width = r->W; nd.pitch = (size_t)r->W * sizeof(float4);
+  cd.address = w.color.get(); cd.height = r->H; cd.width = r->W; cd.pitch = (size_t)r->W * sizeof(uint32_t);
+  SMX_CALL(smx_recon_render(r, s, &rp, &dd, nullptr, &nd, photo ? &cd : nullptr));   // (color_flags 0: the colour row)
+  if (model_depth_out)
+    SMX_HIP(hipMemcpy2DAsync(model_depth_out->address, model_depth_out->pitch, dd.address, dd.pitch, dd.pitch, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
+  if (model_normal_out)
+    SMX_HIP(hipMemcpy2DAsync(model_normal_out->address, model_normal_out->pitch, nd.address, nd.pitch, nd.pitch, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
+  SMX_CALL(track_enqueue(st, w, r->W, r->H, r->fx, r->fy, r->cx, r->cy, depth_scaling, depth, normals, global_T_pred, p,
+                         result_on_device && !q ? result : nullptr, color, q, result_on_device ? result_rgbd : nullptr));
+  if (photo && model_photo_out) {
+    const size_t row = (size_t)r->W * sizeof(float4);
+    SMX_HIP(hipMemcpy2DAsync(model_photo_out->address, model_photo_out->pitch, w.photo.get(), row, row, (size_t)r->H,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  SMX_CALL(w.mark.record(st));
+  w.last_rgbd = q != nullptr;
+  if (!result_on_device) {
+    const smx_track_rgbd_result* res = &w.state.get()->result;
+    if (q) SMX_HIP(hipMemcpyAsync(result_rgbd, res, sizeof(*res), hipMemcpyDeviceToHost, st));
+    else SMX_HIP(hipMemcpyAsync(result, &res->icp, sizeof(res->icp), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  return SMX_OK;
+}
+
+// The records of the last tracking call, the first *count of them (at most kTrackRing) copied into recs.
+int track_records(smx_recon r, smx_stream s, smx_track_rgbd_iteration* recs, int32_t* count) {
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  *count = 0;
+  const TrackWork& w = r->track;
+  if (!w.state.get() || !w.mark.busy()) return SMX_OK;
+  SMX_CALL(w.mark.wait(st));
+  int32_t n = 0;
+  SMX_HIP(hipMemcpyAsync(&n, &w.state.get()->iterations_run, sizeof(n), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  n = std::max(0, std::min(n, (int32_t)kTrackRing));
+  if (n > 0) {
+    SMX_HIP(hipMemcpyAsync(recs, w.state.get()->ring, sizeof(smx_track_rgbd_iteration) * (size_t)n, hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+  }
+  *count = n;
+  return SMX_OK;
+}
+
+}  // namespace
 }  // namespace smx
 
-extern "C" int smx_track_params_default(smx_track_params* out) {
+using namespace smx;
+
+extern "C" {
+
+int smx_track_params_default(smx_track_params* out) {
   SMX_CHECK_ARG(out != nullptr);
   const int32_t stride[3] = {4, 2, 1}, iters[3] = {4, 5, 10};
   for (int l = 0; l < 3; ++l) { out->level_stride[l] = stride[l]; out->level_iterations[l] = iters[l]; }
@@ -220,10 +338,57 @@ extern "C" int smx_track_params_default(smx_track_params* out) {
   return SMX_OK;
 }
 
-extern "C" int smx_track_rgbd_params_default(smx_track_rgbd_params* out) {
+int smx_track_rgbd_params_default(smx_track_rgbd_params* out) {
   SMX_CHECK_ARG(out != nullptr);
   SMX_CALL(smx_track_params_default(&out->icp));
   out->photometric_weight = 0.1f; out->max_intensity_difference = 0.2f;
   out->min_gradient = 0.02f; out->gradient_max_relative_depth_step = 0.02f;
   return SMX_OK;
 }
+
+int smx_recon_track(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                    const smx_buffer_desc* normals, const float global_T_pred[12], const smx_track_params* params,
+                    smx_track_result* result, int32_t result_on_device, const smx_buffer_desc* model_depth_out,
+                    const smx_buffer_desc* model_normal_out) {
+  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, params, result, result_on_device, model_depth_out,
+                    model_normal_out, nullptr, nullptr, nullptr, nullptr);
+}
+
+int smx_recon_track_rgbd(smx_recon r, smx_stream s, float depth_scaling, const smx_buffer_desc* depth,
+                         const smx_buffer_desc* normals, const smx_buffer_desc* color, const float global_T_pred[12],
+                         const smx_track_rgbd_params* params, smx_track_rgbd_result* result, int32_t result_on_device,
+                         const smx_buffer_desc* model_depth_out, const smx_buffer_desc* model_normal_out,
+                         const smx_buffer_desc* model_photo_out) {
+  SMX_CHECK_ARG(params != nullptr);
+  return track_call(r, s, depth_scaling, depth, normals, global_T_pred, &params->icp, result ? &result->icp : nullptr,
+                    result_on_device, model_depth_out, model_normal_out, color, params, result, model_photo_out);
+}
+
+int smx_recon_debug_track_rgbd_iterations(smx_recon r, smx_stream s, smx_track_rgbd_iteration* records, int32_t capacity,
+                                          int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  *count = 0;
+  if (!r->track.last_rgbd) return SMX_OK;
+  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
+  SMX_CALL(track_records(r, s, recs.data(), count));
+  std::copy_n(recs.begin(), std::min(*count, capacity), records);
+  return SMX_OK;
+}
+
+// (the same records without their last two sums, which a call without colour leaves 0)
+int smx_recon_debug_track_iterations(smx_recon r, smx_stream s, smx_track_iteration* records, int32_t capacity,
+                                     int32_t* count) {
+  SMX_CHECK_ARG(r != nullptr && count != nullptr && capacity >= 0 && (capacity == 0 || records != nullptr));
+  std::vector<smx_track_rgbd_iteration> recs(kTrackRing);
+  SMX_CALL(track_records(r, s, recs.data(), count));
+  for (int32_t i = 0; i < std::min(*count, capacity); ++i) {
+    const smx_track_rgbd_iteration& f = recs[i];
+    smx_track_iteration& t = records[i];
+    t.level = f.level; t.stride = f.stride; t.status = f.status; t.reserved = f.reserved;
+    std::copy_n(f.sums, SMX_TRACK_SUMS, t.sums);
+    std::copy_n(f.x, 6, t.x);
+  }
+  return SMX_OK;
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 // Part 1: the arithmetic as plain inline functions -- one sampled pixel's contribution to the sums (with and without the
 // photometric term), the prepare kernel's pixel, the solve, the SE(3) exponential, the end of a call.  smx_track.hip calls
 // them from its kernels; a test compiles this part alone for the host (SMX_TRACK_HOST_ONLY) and runs the same functions.
-// Part 2: what smx_recon_map.hip needs of smx_track.hip (the buffers and the one entry point).
+// Part 2: the constants of the slabs and the workspace the object keeps for the calls (their glue is in smx_track.hip).
 #pragma once
 
 #include <math.h>
@@ -309,24 +309,21 @@ constexpr int kTrackSlabStride = 32;       // doubles per workgroup slab without
 constexpr int kTrackRgbdSlabStride = 40;   // ... with it (33 used)
 constexpr int kTrackMaxSlabs = 256;        // workgroups of the reduce kernel, at most
 
-// The object (smx_recon_s) owns the buffers; smx_track.hip owns the kernels and enqueues all iterations of a call.
-struct TrackBuffers {
-  const float* model_depth;     // [H][W] dense
-  const float4* model_normal;   // [H][W] dense
-  double* slabs;                // kTrackMaxSlabs * kTrackRgbdSlabStride doubles (either stride fits)
-  TrackDev* state;
-  const uint32_t* model_color;  // [H][W] dense uchar4, alpha 0 = empty; this and the next: calls with colour only
-  float4* model_photo;          // [H][W] dense (L, gx, gy, valid)
+// The workspace of the two calls, a member of smx_recon_s; allocated by the first call that needs each part.
+struct TrackWork {
+  // smx_recon_track / _rgbd, all four or none: the model images [H][W] of the last call, the reduce kernel's per-workgroup
+  // partial sums (kTrackMaxSlabs * kTrackRgbdSlabStride doubles: either stride fits), the call's device state
+  DevBuf<float> depth;
+  DevBuf<float4> normal;
+  DevBuf<double> slabs;
+  DevBuf<TrackDev> state;
+  // smx_recon_track_rgbd, both or none: the model colour image [H][W] (uchar4, alpha 0 = empty) and P = (L, gx, gy, valid)
+  // of the last call with a weight
+  DevBuf<uint32_t> color;
+  DevBuf<float4> photo;
+  StreamMark mark;          // behind the last call's kernels (the next call, on whatever stream, waits for it)
+  bool last_rgbd = false;   // the last call was smx_recon_track_rgbd
 };
-
-// Enqueues begin + every (reduce, solve) pair of the schedule on st; the last solve launch writes b.state->result and, where
-// not null, *result_dev (its .icp) / *result_rgbd_dev (all of it).  q is null for smx_recon_track; with one, p is q->icp,
-// color the frame's image, and a weight other than 0 puts one k_track_photo_prepare launch in front and the photometric
-// term into the sums (at weight 0 model_color / model_photo are not touched).  Arguments are validated by the caller.
-int track_enqueue(hipStream_t st, const TrackBuffers& b, int W, int H, float fx, float fy, float cx, float cy,
-                  float depth_scaling, const smx_buffer_desc* depth, const smx_buffer_desc* normals,
-                  const float global_T_pred[12], const smx_track_params& p, smx_track_result* result_dev,
-                  const smx_buffer_desc* color, const smx_track_rgbd_params* q, smx_track_rgbd_result* result_rgbd_dev);
 #endif
 
 }  // namespace smx
