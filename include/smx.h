@@ -942,6 +942,72 @@ int smx_recon_decimate_mesh(smx_recon r, smx_stream s, float cell_size,
 #define SMX_DECIMATE_PHASES 4
 int smx_recon_debug_decimate_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- the connected pieces of a triangle array: label them, measure them, drop the small ones ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n) with n =
+ * surfels_size()), of triangles_in (uint32 [n_in][3], slot indices, in ANY order: the output of smx_recon_triangulate, of
+ * smx_recon_decimate_mesh, or any other array over the map) and of p.  Every quantity is an integer or a float32 expression
+ * evaluated as written, one rounding per operation, no contraction.
+ * 1. Live and range, as smx_recon_decimate_mesh step 1: a triangle with a corner that is not live (!(RadiusSquared < 0) and a
+ *    finite smooth position) is dropped and counted in n_not_live.  An index >= n anywhere in the input:
+ *    SMX_ERR_INVALID_ARGUMENT, nothing is written.  U = the slots that occur in the remaining triangles.
+ * 2. Components: the graph on U with an edge for every side of every remaining triangle; a component is a connected component
+ *    of that graph.  This is connectivity through shared VERTICES: two triangles that touch in one corner only are one piece
+ *    (a surfel is one point of the surface; an edge-connectivity rule would split a fan at its hub).  label(i) = the smallest
+ *    slot index in i's component.  vertex_labels[i] = label(i) for i in U, 0xFFFFFFFF for every other slot.  A triangle
+ *    belongs to the component of its corners.
+ * 3. Measures of a component: n_vertices and n_triangles (integer counts); the box of its vertices' smooth positions, per
+ *    coordinate the minimum and the maximum under the total order of k(f) = bits(f) ^ ((bits(f) >> 31) ? 0xFFFFFFFF :
+ *    0x80000000), so -0 < +0 and the stored bytes are those of the winning input.  d_k = hi_k - lo_k, diag2 = (d_x d_x +
+ *    d_y d_y) + d_z d_z.
+ * 4. Kept: a component passes iff n_triangles >= min_triangles and diag2 >= min_diagonal * min_diagonal (one float32 product).
+ *    With keep_largest = K > 0 the passing components are ranked by (n_triangles descending, label ascending) and the first K
+ *    are kept; with K = 0 all that pass are.
+ * 5. Output: triangles_out = the subsequence of triangles_in whose component is kept, input order and each triangle's three
+ *    words unchanged (so an array in smx_recon_triangulate's order stays in it).  The table holds every component, kept or
+ *    not, ascending by label.  Two calls give the same bytes in all three outputs.
+ * 6. Not done: no hole is filled, no edge is made manifold, non-manifold edges are not reported.
+ * Calling rules as smx_recon_decimate_mesh: ordered after everything enqueued on the object, synchronous.  on_device says
+ * where triangles_in, triangles_out, vertex_labels and components live (host arrays are staged).  capacity < T_out, or
+ * components != NULL and component_capacity < n_components: SMX_ERR_INVALID_ARGUMENT, *n_triangles = T_out and *n_components
+ * are both reported, nothing is written to any output; triangles_out == NULL with capacity 0 is that count-only form.
+ * n_in == 0 is valid.  min_diagonal must be finite and >= 0.  triangles_out must not overlap triangles_in (refused).
+ * vertex_labels may be NULL, else it has surfels_size() entries; components may be NULL (component_capacity is then ignored).
+ * stats may be NULL; it is filled whenever the counts are known.  Changes no map state, delta mark, statistic or stamp, nor
+ * the state smx_recon_triangulate_update keeps.  The workspace belongs to the object, grows on demand and is reused. */
+typedef struct {
+  uint32_t min_triangles;   /* keep a component only if it has at least this many triangles; 0 = no test */
+  float    min_diagonal;    /* ... and its bounding-box diagonal is at least this long (map units); 0 = no test */
+  uint32_t keep_largest;    /* of the components that pass, keep only this many largest; 0 = all */
+} smx_components_params;
+typedef struct {            /* 40 bytes, one per component, table ascending by label */
+  uint32_t label;           /* smallest slot index in the component */
+  uint32_t n_vertices, n_triangles;
+  uint32_t kept;            /* 0 / 1 */
+  float    lo[3], hi[3];    /* bounding box of the smooth positions */
+} smx_mesh_component;
+typedef struct {
+  uint32_t n_in;                /* triangles given */
+  uint32_t n_not_live;          /* of those, dropped because a corner is not live */
+  uint32_t n_used_vertices;     /* |U| */
+  uint32_t n_components;
+  uint32_t n_kept_components;
+  uint32_t n_largest_triangles; /* triangle count of the largest component, kept or not; 0 if there is none */
+  uint32_t n_triangles;         /* T_out */
+} smx_components_stats;
+int smx_components_params_default(smx_components_params* out);   /* 0, 0.0f, 0: labels only, everything kept */
+int smx_recon_mesh_components(smx_recon r, smx_stream s, const smx_components_params* p,
+                              const uint32_t* triangles_in, uint32_t n_in,
+                              uint32_t* triangles_out, uint32_t capacity,
+                              uint32_t* vertex_labels /* may be NULL; surfels_size() entries */,
+                              smx_mesh_component* components /* may be NULL */, uint32_t component_capacity,
+                              int32_t on_device, uint32_t* n_triangles, uint32_t* n_components,
+                              smx_components_stats* stats);
+/* Tools: milliseconds the last smx_recon_mesh_components call spent in its SMX_COMPONENTS_PHASES phases -- mark + link,
+ * flatten + number, measure (+ rank), write (count, scan, triangles, labels, table) -- by timed events on the call's
+ * stream; a phase a call did not reach reads 0.  capacity >= SMX_COMPONENTS_PHASES.  Zeros before the first call. */
+#define SMX_COMPONENTS_PHASES 4
+int smx_recon_debug_components_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the

@@ -604,6 +604,30 @@ class CUDASurfelReconstruction {
     }
     SMX_SHIM_CHECK(rc);
   }
+  // Not in the reference: the connected pieces of a triangle array (through shared vertices), measured, and the array
+  // without the pieces that fail params (smx_recon_mesh_components in smx.h).  *triangles_out (not the same vector) receives
+  // the kept triangles in input order.  *vertex_labels (may be null) receives the smallest slot of every used slot's piece,
+  // 0xFFFFFFFF for the others; *components (may be null) the table of all pieces; stats may be null.  Synchronous.
+  void MeshComponents(cudaStream_t stream, const std::vector<u32>& triangles_in, const smx_components_params& params,
+                      std::vector<u32>* triangles_out, std::vector<u32>* vertex_labels = nullptr,
+                      std::vector<smx_mesh_component>* components = nullptr, smx_components_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles_in.size() / 3);
+    u32 count = 0, pieces = 0;
+    int rc = smx_recon_mesh_components(handle_, stream, &params, triangles_in.data(), n_in, nullptr, 0, nullptr, nullptr, 0, 0,
+                                       &count, &pieces, stats);
+    if (rc == SMX_OK || (rc == SMX_ERR_INVALID_ARGUMENT && count > 0)) {   // (the capacity rule: the counts came back)
+      triangles_out->resize((size_t)3 * count);
+      if (vertex_labels) vertex_labels->resize(surfels_size());
+      if (components) components->resize(pieces);
+      const bool labels = vertex_labels && !vertex_labels->empty(), table = components && !components->empty();
+      rc = (count || labels || table)
+               ? smx_recon_mesh_components(handle_, stream, &params, triangles_in.data(), n_in, count ? triangles_out->data() : nullptr,
+                                           count, labels ? vertex_labels->data() : nullptr, table ? components->data() : nullptr,
+                                           table ? pieces : 0, 0, &count, &pieces, stats)
+               : SMX_OK;
+    }
+    SMX_SHIM_CHECK(rc);
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

@@ -175,6 +175,26 @@ class DecimateStats(C.Structure):
 DECIMATE_PHASES = 4   # SMX_DECIMATE_PHASES
 
 
+class ComponentsParams(C.Structure):
+    """smx_components_params: the thresholds of smx_recon_mesh_components."""
+    _fields_ = [("min_triangles", C.c_uint32), ("min_diagonal", C.c_float), ("keep_largest", C.c_uint32)]
+
+
+class MeshComponent(C.Structure):
+    """smx_mesh_component: one row of the component table."""
+    _fields_ = [("label", C.c_uint32), ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("kept", C.c_uint32),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+class ComponentsStats(C.Structure):
+    """smx_components_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_used_vertices", "n_components", "n_kept_components",
+                                          "n_largest_triangles", "n_triangles")]
+
+
+COMPONENTS_PHASES = 4   # SMX_COMPONENTS_PHASES
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -251,6 +271,7 @@ EXPORTS = [
     "smx_mesh_params_default", "smx_recon_triangulate", "smx_recon_debug_mesh_timings",
     "smx_recon_triangulate_update", "smx_recon_triangulate_reset", "smx_recon_debug_mesh_update_timings", "smx_recon_deform_by_creation_frame",
     "smx_recon_decimate_mesh", "smx_recon_debug_decimate_timings",
+    "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

@@ -23,10 +23,27 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
+                   COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
 kInvalidSurfelIndex = 0xFFFFFFFF  # APP/surfel.h (Surfel::kInvalidIndex)
+# smx_mesh_component as a numpy record: what MeshComponents(return_components=True) returns
+COMPONENT_DTYPE = np.dtype([("label", "<u4"), ("n_vertices", "<u4"), ("n_triangles", "<u4"), ("kept", "<u4"),
+                            ("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
+
+
+def components_params(min_triangles=0, min_diagonal=0.0, keep_largest=0):
+    """The thresholds of MeshComponents as smx_components_params; ValueError on what the library would refuse (and on what
+    a uint32 cannot hold), before anything is called."""
+    for name, v in (("min_triangles", min_triangles), ("keep_largest", keep_largest)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError("%s must be an integer within 0 .. 2^32 - 1" % name)
+    d = float(min_diagonal)
+    if not (d >= 0.0 and d != float("inf")):
+        raise ValueError("min_diagonal must be finite and >= 0")
+    return ComponentsParams(int(min_triangles), d, int(keep_largest))
+
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
 
 # smx.h: colour modes of the viewer buffers and the render, splat shapes of the render
@@ -747,6 +764,54 @@ class CUDASurfelReconstruction:
         out = (C.c_float * DECIMATE_PHASES)()
         _lib.check(_lib.load().smx_recon_debug_decimate_timings(self._h, out, C.c_int32(DECIMATE_PHASES)))
         return dict(zip(("cluster", "remap_dedupe", "survivors", "order"), [float(v) for v in out]))
+
+    def MeshComponents(self, stream, triangles, min_triangles=0, min_diagonal=0.0, keep_largest=0, return_labels=False,
+                       return_components=False):
+        """Not in the reference: the connected pieces of `triangles` ([T,3] slot indices in any order, e.g. Triangulate's or
+        DecimateMesh's) labelled, measured and filtered on the device (smx_recon_mesh_components).  Pieces are connected
+        through shared vertices; a piece is kept if it has at least min_triangles triangles and a bounding-box diagonal of
+        at least min_diagonal, and with keep_largest = K > 0 only the K largest of those.  The result is the subsequence of
+        the input whose piece is kept: same order, same format.  Synchronous.  Returns (triangles [T_out,3] uint32, dict of
+        smx_components_stats), then with return_labels vertex_labels [surfels_size()] uint32 (the smallest slot of every
+        used slot's piece, 0xFFFFFFFF for the others), then with return_components the table of all pieces, ascending by
+        label, as a structured array of COMPONENT_DTYPE."""
+        p = components_params(min_triangles, min_diagonal, keep_largest)
+        tri = np.ascontiguousarray(triangles, np.uint32)
+        if tri.size % 3:
+            raise ValueError("triangles must hold three indices per triangle")
+        tri = tri.reshape(-1, 3)
+        L = _lib.load()
+        T, nc, st = C.c_uint32(0), C.c_uint32(0), ComponentsStats()
+        tin = tri.ctypes.data_as(C.c_void_p) if tri.shape[0] else None
+
+        def call(out, labels, table):
+            return L.smx_recon_mesh_components(
+                self._h, _sv(stream), C.byref(p), tin, C.c_uint32(tri.shape[0]),
+                out.ctypes.data_as(C.c_void_p) if out is not None and out.size else None,
+                C.c_uint32(0 if out is None else out.shape[0]),
+                labels.ctypes.data_as(C.c_void_p) if labels is not None and labels.size else None,
+                table.ctypes.data_as(C.c_void_p) if table is not None and table.size else None,
+                C.c_uint32(0 if table is None else table.shape[0]), C.c_int32(0), C.byref(T), C.byref(nc), C.byref(st))
+        rc = call(None, None, None)
+        if rc != 0 and not (rc == -1 and T.value > 0):   # (SMX_ERR_INVALID_ARGUMENT with the counts: the capacity rule)
+            _lib.check(rc)
+        out = np.zeros((T.value, 3), np.uint32)
+        labels = np.zeros(self._counts_on(stream)[1], np.uint32) if return_labels else None
+        table = np.zeros(nc.value, COMPONENT_DTYPE) if return_components else None
+        if T.value or (labels is not None and labels.size) or (table is not None and table.size):
+            _lib.check(call(out, labels, table))
+        ret = (out, {n: int(getattr(st, n)) for n, _ in ComponentsStats._fields_})
+        if return_labels:
+            ret += (labels,)
+        if return_components:
+            ret += (table,)
+        return ret
+
+    def debug_components_timings(self):
+        """Milliseconds of the last MeshComponents call, by phase."""
+        out = (C.c_float * COMPONENTS_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_components_timings(self._h, out, C.c_int32(COMPONENTS_PHASES)))
+        return dict(zip(("mark_link", "flatten_number", "measure", "write"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

@@ -13,6 +13,10 @@ the map changed:
 A coarser level of detail of either (smx_recon_decimate_mesh) -- vertex clustering on a grid of cell_size:
 
     coarse, decimate_stats = meshing.decimate_map_mesh(rec, triangles, 0.05)
+
+Without its small pieces (smx_recon_mesh_components) -- connected components through shared vertices:
+
+    clean, component_stats = meshing.clean_map_mesh(rec, triangles, min_triangles=20, min_diagonal=0.05)
 """
 from ._lib import MeshParams as _MeshParamsPOD
 
@@ -20,6 +24,9 @@ UPDATE_STAT_NAMES = ("mode", "n_changed", "n_dirty", "n_reagreed", "n_kept_trian
 UPDATE_MODES = ("incremental", "full: no state", "full: parameters differ", "full: fewer slots than kept",
                 "full: dirty fraction above the limit")
 DECIMATE_STAT_NAMES = ("n_in", "n_not_live", "n_used_vertices", "n_cells", "n_collapsed", "n_duplicates", "n_triangles")
+COMPONENTS_STAT_NAMES = ("n_in", "n_not_live", "n_used_vertices", "n_components", "n_kept_components", "n_largest_triangles",
+                         "n_triangles")
+CLEAN_KEYS = ("min_triangles", "min_diagonal", "keep_largest")
 STAT_NAMES = ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")
 
 
@@ -63,10 +70,35 @@ def decimate_map_mesh(rec, triangles, cell_size, stream=None):
     return rec.DecimateMesh(stream, triangles, cell_size)
 
 
+def clean_options(clean):
+    """`clean` of MapMesher.update as keyword arguments of clean_map_mesh: None, or a dict with keys out of CLEAN_KEYS whose
+    values the library would take (checked here, before anything runs)."""
+    if clean is None:
+        return None
+    from .api import components_params
+    unknown = sorted(set(clean) - set(CLEAN_KEYS))
+    if unknown:
+        raise ValueError("clean: unknown key(s) %s (known: %s)" % (", ".join(map(str, unknown)), ", ".join(CLEAN_KEYS)))
+    components_params(**clean)
+    return dict(clean)
+
+
+def clean_map_mesh(rec, triangles, min_triangles=0, min_diagonal=0.0, keep_largest=0, stream=None, return_labels=False,
+                   return_components=False):
+    """Removes the small connected pieces of `triangles` ([T,3] slot indices of `rec`'s map): a piece stays if it has at
+    least min_triangles triangles and a bounding-box diagonal of at least min_diagonal metres, and with keep_largest = K > 0
+    only the K largest of those.  The result is a subsequence of the input.  Returns (triangles [T_out,3] uint32, stats
+    dict[, labels][, component table])."""
+    from .api import components_params
+    components_params(min_triangles, min_diagonal, keep_largest)
+    return rec.MeshComponents(stream, triangles, min_triangles, min_diagonal, keep_largest, return_labels, return_components)
+
+
 class MapMesher:
     """Keeps the mesh of `rec`'s map up to date.  Owns the neighbour index; update() returns what mesh_map would return
     on the map as it stands, plus the update statistics, and keeps the triangles in .triangles / .stats.  With a
-    cell_size, update() also decimates the result (.decimated / .decimate_stats) and returns that array as a fourth value."""
+    cell_size, update() also decimates the result (.decimated / .decimate_stats) and returns that array as a fourth value.
+    With clean, the small pieces are removed first (.cleaned / .clean_stats): cleaning is applied before cell_size."""
 
     def __init__(self, rec, params=None, cell_size=None, full_above_fraction=None):
         from .api import SurfelNeighborIndex
@@ -77,20 +109,31 @@ class MapMesher:
         self._index = SurfelNeighborIndex(rec._device_id)
         self.triangles, self.stats, self.update_stats = None, None, None
         self.decimated, self.decimate_stats = None, None
+        self.cleaned, self.clean_stats = None, None
 
     @property
     def index(self):
         """The neighbour index, built over the map as of the last update()."""
         return self._index
 
-    def update(self, stream=None, cell_size=None):
-        """cell_size (of the decimation grid, metres; not the index's): None = no decimation."""
+    def update(self, stream=None, cell_size=None, clean=None):
+        """cell_size (of the decimation grid, metres; not the index's): None = no decimation.  clean: None, or a dict of
+        clean_map_mesh's thresholds (CLEAN_KEYS); the cleaned array (.cleaned / .clean_stats) is what gets decimated, and
+        without a cell_size it is returned as the fourth value."""
+        options = clean_options(clean)
         self.triangles, self.stats, self.update_stats = self._rec.TriangulateUpdate(
             stream, self._pod, index=self._index, cell_size=self._cell_size, full_above_fraction=self._fraction)
         self.decimated, self.decimate_stats = None, None
+        self.cleaned, self.clean_stats = None, None
+        source = self.triangles
+        if options is not None:
+            self.cleaned, self.clean_stats = self._rec.MeshComponents(stream, self.triangles, **options)
+            source = self.cleaned
         if cell_size is None:
-            return self.triangles, self.stats, self.update_stats
-        self.decimated, self.decimate_stats = self._rec.DecimateMesh(stream, self.triangles, cell_size)
+            if options is None:
+                return self.triangles, self.stats, self.update_stats
+            return self.triangles, self.stats, self.update_stats, self.cleaned
+        self.decimated, self.decimate_stats = self._rec.DecimateMesh(stream, source, cell_size)
         return self.triangles, self.stats, self.update_stats, self.decimated
 
     def timings(self):
@@ -101,6 +144,7 @@ class MapMesher:
         self._rec.ResetTriangulation()
         self.triangles, self.stats, self.update_stats = None, None, None
         self.decimated, self.decimate_stats = None, None
+        self.cleaned, self.clean_stats = None, None
 
     def close(self):
         if self._index is not None:

@@ -4,6 +4,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py [--reps 5] [--target 5000000] [--json OUT]
     python tools/mesh_bench.py --update [--target 5000000] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --decimate CELL[,CELL...] [--target 5000000] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --components [--decimate CELL[,CELL...]] [--compare_json OTHER.json] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -20,7 +21,16 @@ bytes.  The sweep runs with full_above_fraction = 1, so that the incremental pat
 --decimate measures smx_recon_decimate_mesh on the same map's full mesh for every cell size given (metres):
 medians of --reps calls with device arrays that are large enough, whole calls by device events and the four phases by the
 library's own (smx_recon_debug_decimate_timings), triangles and vertices in and out, bytes by decimate_traffic_bytes below
-against the HBM peak, and the full triangulation re-measured in the same process beside it."""
+against the HBM peak, and the full triangulation re-measured in the same process beside it.
+
+--components measures smx_recon_mesh_components on the same map's full mesh and, with --decimate, on each
+decimated mesh: medians of --reps calls with device arrays that are large enough, once with the default parameters (labels
+and table only, everything kept) and once with min_triangles = 10; whole calls by device events and the four phases by the
+library's own (smx_recon_debug_components_timings); bytes by components_traffic_bytes below against the HBM peak; the
+histogram of component sizes (1, 2-9, 10-99, ..., and the largest); the full triangulation re-measured beside it.  Writes
+profiles/components_bench.{txt,json} unless --txt / --json say otherwise.  --compare_json names the JSON another build of
+the library wrote with the same command on the same box (SMX_LIB_PATH, tools/build_variant.sh): its per-phase times are
+printed beside this build's, row by row -- the A/B of the measure phase with and without wave aggregation."""
 import argparse
 import json
 import os
@@ -36,6 +46,9 @@ ap.add_argument("--json", default=None)
 ap.add_argument("--update", action="store_true")
 ap.add_argument("--txt", default=None)
 ap.add_argument("--decimate", default=None, help="comma-separated cell sizes in metres")
+ap.add_argument("--components", action="store_true")
+ap.add_argument("--compare_json", default=None, help="with --components: the JSON of another build's run, printed beside this one")
+ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
 
@@ -175,6 +188,167 @@ def decimate_main():
         with open(args.txt, "w") as f:
             f.write("\n".join(lines) + "\n")
     for b in (dtri, dout, dmap):
+        b.close()
+    nn.close()
+
+
+COMPONENTS_PHASES = ("mark_link", "flatten_number", "measure", "write")
+
+
+def components_traffic_bytes(n, st, labels_out=True, table_out=True):
+    """HBM bytes of one smx_recon_mesh_components call over n slots, by phase, from its statistics.  Gathers are counted once
+    per distinct target (a lower bound: neighbouring triangles share corners and mostly hit in cache); a find is counted as
+    two loads of parent per corner (the word and its parent: a lower bound, the trees are shallow once halved), a hook or a
+    halving as a read and a write of one word; the aggregated atomics of the measure phase are a few words per wavefront and
+    not counted.  The two reads of the counters move a few words."""
+    n_in, used, C, T = st["n_in"], st["n_used_vertices"], st["n_components"], st["n_triangles"]
+    rem = n_in - st["n_not_live"]
+    mark_link = (4 * n + 12 * n_in + 32 * used + 4 * used + 4 * n_in       # reset; mark: the input, S and N of the corners, roots, tcomp
+                 + 12 * n_in + 4 * n_in + 2 * 4 * 3 * rem + 8 * used)      # link: the input, tcomp, the finds, one hook per slot
+    flatten = 4 * n + 2 * 4 * used + 4 * n + 8 * (n // 256 + 1) + 4 * n + 4 * C   # flatten: parent, finds, label; scan; number: label, roots
+    measure = (4 * n + 4 * used + 16 * used                                # vertices: label, dense number, S record
+               + 4 * n_in + 4 * rem + 4 * rem + 4 * rem + 4 * rem          # triangles: tcomp, first corner, its label, dense number, tcomp
+               + 32 * C + 32 * C + 40 * C)                                 # accumulators reset and read, the table
+    write = (2 * (4 * n_in + 4 * rem) + 8 * (n_in // 256 + 1) + 12 * T + 12 * T   # count and write: tcomp, kept; the triangles in and out
+             + (8 * n if labels_out else 0) + (80 * C if table_out else 0))
+    return dict(zip(COMPONENTS_PHASES, (mark_link, flatten, measure, write)))
+
+
+def size_histogram(n_triangles):
+    """Component sizes in triangles: how many components in 1, 2-9, 10-99, ..., and the largest."""
+    sizes = np.asarray(n_triangles, np.int64)
+    rows, lo = [], 1
+    if sizes.size:
+        rows.append(("1", int(np.sum(sizes == 1)), int(sizes[sizes == 1].sum())))
+        lo = 2
+        while lo <= int(sizes.max()):
+            hi = 10 if lo == 2 else lo * 10
+            sel = (sizes >= lo) & (sizes < hi)
+            rows.append(("%d-%d" % (lo, hi - 1), int(sel.sum()), int(sizes[sel].sum())))
+            lo = hi
+    return rows, int(sizes.max()) if sizes.size else 0
+
+
+def components_main():
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    cells = [float(c) for c in args.decimate.split(",")] if args.decimate else []
+    other = json.load(open(args.compare_json)) if args.compare_json else None
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# %s; grown in %.1f s: %d slots, %d live" % (args.label, time.time() - t0, n, live))
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, ddec, dout, dlab = (api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32),
+                              api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, n, np.uint32))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def full():
+        T, st = C.c_uint32(0), _lib.MeshStats()
+        _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                           C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+        return T.value
+
+    def components(src, n_in, prm, dtab, tab_cap):
+        T, nc, st = C.c_uint32(0), C.c_uint32(0), _lib.ComponentsStats()
+        rc = L.smx_recon_mesh_components(rec._h, None, C.byref(prm), C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(cap), C.c_void_p(dlab.ToCUDA().address),
+                                         C.c_void_p(dtab.ToCUDA().address) if dtab is not None else None, C.c_uint32(tab_cap),
+                                         C.c_int32(1), C.byref(T), C.byref(nc), C.byref(st))
+        _lib.check(rc)
+        return {k: int(getattr(st, k)) for k, _ in _lib.ComponentsStats._fields_}
+    t_full = []
+    for _ in range(args.reps + 1):
+        ms, T_in = timed(full)
+        t_full.append(ms)
+    full_ms = float(np.median(t_full[1:]))
+    say("full triangulation, re-measured here: %d triangles, one call %.2f ms" % (T_in, full_ms))
+    inputs = [("full mesh", dtri, T_in)]
+    out_rows = []
+    for cell in cells:
+        T, st = C.c_uint32(0), _lib.DecimateStats()
+        _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                             C.c_void_p(ddec.ToCUDA().address), C.c_uint32(cap), None, C.c_int32(1), C.byref(T), C.byref(st)))
+        coarse = api.CUDABuffer(1, 3 * max(T.value, 1), np.uint32)           # (an array of its own: ddec is reused by the next cell)
+        coarse.Upload(np.ascontiguousarray(ddec.Download()[:, :3 * max(T.value, 1)]))
+        inputs.append(("decimated at %g m" % cell, coarse, T.value))
+    for what, src, n_in in inputs:
+        first = components(src, n_in, _lib.ComponentsParams(0, 0.0, 0), None, 0)          # (allocates; tells the table's size)
+        Cn = first["n_components"]
+        dtab = api.CUDABuffer(1, 10 * max(Cn, 1), np.uint32)
+        for prm_name, prm in (("default", _lib.ComponentsParams(0, 0.0, 0)), ("min_triangles 10", _lib.ComponentsParams(10, 0.0, 0))):
+            t, phs, st, head0 = [], [], None, None
+            for _ in range(args.reps + 1):
+                ms, st = timed(lambda: components(src, n_in, prm, dtab, Cn))
+                t.append(ms)
+                phs.append(rec.debug_components_timings())
+                head = dout.Download()[0][:3 * min(st["n_triangles"], 100000)].tobytes() + dtab.Download()[0].tobytes()
+                head0 = head if head0 is None else head0
+                assert head == head0, "two calls gave different bytes"
+            med = float(np.median(t[1:]))
+            ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in COMPONENTS_PHASES}
+            b = components_traffic_bytes(n, st)
+            tot = sum(b.values())
+            say("%s, %s: %d -> %d triangles, %d used vertices, %d components (%d kept, the largest has %d triangles) | call %.2f ms "
+                "(min %.2f, max %.2f) = %.3f x the full triangulation | %s | model %.2f GB -> %.2f TB/s = %.0f %% of the %.1f TB/s "
+                "HBM peak (%s)" % (
+                    what, prm_name, st["n_in"], st["n_triangles"], st["n_used_vertices"], st["n_components"], st["n_kept_components"],
+                    st["n_largest_triangles"], med, min(t[1:]), max(t[1:]), med / full_ms,
+                    " ".join("%s %.3f" % (k, ph[k]) for k in COMPONENTS_PHASES), tot / 1e9, tot / (med * 1e-3) / 1e12,
+                    100.0 * tot / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12,
+                    " ".join("%s %.0f %%" % (k, 100.0 * b[k] / (max(ph[k], 1e-6) * 1e-3) / HBM_PEAK) for k in COMPONENTS_PHASES)))
+            row = {"input": what, "params": prm_name, "reps": len(t) - 1, "call_ms": med, "call_ms_all": t[1:], "phases_ms": ph,
+                   "phases_ms_all": phs[1:], "stats": st, "traffic_model_bytes": b, "fraction_of_hbm_peak": tot / (med * 1e-3) / HBM_PEAK,
+                   "ratio_to_full_triangulation": med / full_ms}
+            if other is not None:
+                theirs = [r for r in other["rows"] if r["input"] == what and r["params"] == prm_name]
+                if theirs and theirs[0]["stats"] == st:
+                    o = theirs[0]
+                    say("    %s on the same box: call %.2f ms | %s | measure phase %.3f ms here against %.3f ms there (all: %s | %s)" % (
+                        other["label"], o["call_ms"], " ".join("%s %.3f" % (k, o["phases_ms"][k]) for k in COMPONENTS_PHASES),
+                        ph["measure"], o["phases_ms"]["measure"], " ".join("%.3f" % q["measure"] for q in phs[1:]),
+                        " ".join("%.3f" % q["measure"] for q in o["phases_ms_all"])))
+                    row["compared_with"] = {"label": other["label"], "call_ms": o["call_ms"], "phases_ms": o["phases_ms"],
+                                            "phases_ms_all": o["phases_ms_all"]}
+                else:
+                    say("    %s: no row with the same input and statistics" % other["label"])
+            if prm_name == "default":
+                table = dtab.Download()[0][:10 * Cn].view(api.COMPONENT_DTYPE)
+                hist, largest = size_histogram(table["n_triangles"])
+                say("    component sizes in triangles (components / their triangles): %s; the largest has %d = %.2f %% of the mesh" % (
+                    ", ".join("%s: %d / %d" % h for h in hist), largest, 100.0 * largest / max(st["n_in"] - st["n_not_live"], 1)))
+                row["size_histogram"] = [{"triangles": h[0], "components": h[1], "triangles_in_them": h[2]} for h in hist]
+                row["largest_component_triangles"] = largest
+            out_rows.append(row)
+        dtab.close()
+    res = {"metric": "mesh_components_ms", "label": args.label, "slots": n, "live": live, "triangles_in": T_in,
+           "full_triangulation_ms": full_ms, "rows": out_rows}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(args.json or os.path.join(ROOT, "profiles", "components_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "components_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    for what, src, _ in inputs[1:]:
+        src.close()
+    for b in (dtri, ddec, dout, dlab):
         b.close()
     nn.close()
 
@@ -341,4 +515,4 @@ def main():
 
 
 if __name__ == "__main__":
-    decimate_main() if args.decimate else update_main() if args.update else main()
+    components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -5,6 +5,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--compact_every N] [--compact_at_fill F] [--track [--track_write_trajectory FILE]]
                               [--track_rgbd [--track_photometric_weight W]]
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
+                              [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -13,9 +14,13 @@ where the map changed (one line per update: mode, counts, milliseconds); --expor
 after the last frame.  --mesh_check triangulates once more at the end with the full call and fails if the two differ.
 --mesh_decimate METRES (with --mesh or --mesh_every) decimates the final mesh by vertex clustering on a grid of that cell
 size (smx_recon_decimate_mesh) before --export_mesh, which then writes only the vertices the coarse mesh uses.
+--mesh_min_component TRIANGLES, --mesh_min_extent METRES and --mesh_keep_largest K (each with --mesh or --mesh_every) remove
+the small connected pieces of the final mesh (smx_recon_mesh_components): a piece stays if it has at least that many
+triangles and a bounding-box diagonal of at least that length, and of those only the K largest.  Cleaning is applied before
+--mesh_decimate; --export_mesh then writes only the vertices the remaining mesh uses.
 --render_source mesh (with --mesh or --mesh_every) makes --render_dir / --render_every / --render_overview draw the current
 mesh with smx_recon_render_mesh instead of splats: the kept array of --mesh_every as of its last update, otherwise a
-triangulation of the map as it stands, decimated first if --mesh_decimate is given.
+triangulation of the map as it stands, cleaned and decimated first if those flags are given.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
@@ -164,6 +169,12 @@ def parse_args(argv=None):
     ap.add_argument("--mesh_decimate", type=float, default=None, metavar="METRES",
                     help="with --mesh or --mesh_every: decimate the final mesh by vertex clustering with this cell size; "
                          "--export_mesh then writes the decimated mesh and only the vertices it uses")
+    ap.add_argument("--mesh_min_component", type=int, default=None, metavar="TRIANGLES",
+                    help="with --mesh or --mesh_every: drop the connected pieces of the final mesh with fewer triangles")
+    ap.add_argument("--mesh_min_extent", type=float, default=None, metavar="METRES",
+                    help="with --mesh or --mesh_every: drop the connected pieces whose bounding-box diagonal is shorter")
+    ap.add_argument("--mesh_keep_largest", type=int, default=None, metavar="K",
+                    help="with --mesh or --mesh_every: keep only the K largest connected pieces (of those that pass the other two)")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -179,6 +190,20 @@ def parse_args(argv=None):
         ap.error("--mesh_decimate needs --mesh or --mesh_every")
     if args.mesh_decimate is not None and not args.mesh_decimate > 0:
         ap.error("--mesh_decimate needs a cell size > 0")
+    for flag, value in (("--mesh_min_component", args.mesh_min_component), ("--mesh_min_extent", args.mesh_min_extent),
+                        ("--mesh_keep_largest", args.mesh_keep_largest)):
+        if value is not None and not (args.mesh or args.mesh_every > 0):
+            ap.error("%s needs --mesh or --mesh_every" % flag)
+    if args.mesh_min_component is not None and not 0 <= args.mesh_min_component <= 0xFFFFFFFF:
+        ap.error("--mesh_min_component needs a triangle count >= 0")
+    if args.mesh_min_extent is not None and not 0 <= args.mesh_min_extent < float("inf"):
+        ap.error("--mesh_min_extent needs a finite length >= 0")
+    if args.mesh_keep_largest is not None and not 1 <= args.mesh_keep_largest <= 0xFFFFFFFF:
+        ap.error("--mesh_keep_largest needs a count >= 1")
+    args.mesh_clean = None
+    if any(v is not None for v in (args.mesh_min_component, args.mesh_min_extent, args.mesh_keep_largest)):
+        args.mesh_clean = dict(min_triangles=args.mesh_min_component or 0, min_diagonal=args.mesh_min_extent or 0.0,
+                               keep_largest=args.mesh_keep_largest or 0)
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
     return args
@@ -244,6 +269,8 @@ def main():
             tri = mesher.triangles
         else:
             tri, _ = meshing.mesh_map(pipe.reconstruction)
+        if args.mesh_clean is not None:
+            tri, _ = meshing.clean_map_mesh(pipe.reconstruction, tri, **args.mesh_clean)
         if args.mesh_decimate is not None:
             tri, _ = meshing.decimate_map_mesh(pipe.reconstruction, tri, args.mesh_decimate)
         return tri
@@ -309,6 +336,14 @@ def main():
         triangles, mesh_stats = meshing.mesh_map(rec)
         print("%d triangles in %.1f ms; %s" % (triangles.shape[0], 1e3 * (time.time() - t1),
                                               ", ".join("%s %d" % (k, mesh_stats[k]) for k in meshing.STAT_NAMES)))
+    if args.mesh_clean is not None:
+        from surfelmeshing_amd import meshing
+        t1 = time.time()
+        n_before = triangles.shape[0]
+        triangles, cst = meshing.clean_map_mesh(rec, triangles, **args.mesh_clean)
+        print("cleaned in %.1f ms: components %d in / %d kept (the largest has %d triangles), triangles %d in / %d out" % (
+            1e3 * (time.time() - t1), cst["n_components"], cst["n_kept_components"], cst["n_largest_triangles"], n_before,
+            triangles.shape[0]))
     if args.mesh_decimate is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
@@ -318,7 +353,7 @@ def main():
     if args.render_dir and args.render_overview and args.render_source == "mesh":      # (the final mesh, decimated if asked)
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png", triangles)
     if args.export_mesh:
-        export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles, referenced_only=args.mesh_decimate is not None)
+        export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles, referenced_only=args.mesh_decimate is not None or args.mesh_clean is not None)
         print("Wrote %s." % args.export_mesh)
     if args.export_point_cloud:
         export.SavePointCloudAsPLY(rec, args.export_point_cloud, export_colors=True)
