@@ -1008,6 +1008,97 @@ int smx_recon_mesh_components(smx_recon r, smx_stream s, const smx_components_pa
 #define SMX_COMPONENTS_PHASES 4
 int smx_recon_debug_components_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- small holes of a triangle array closed by fans, and the report of its edges ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, slots [0, n) with
+ * n = surfels_size()), of triangles_in (uint32 [n_in][3], slot indices, in ANY order) and of p.  Every quantity is an integer or
+ * a float32 expression evaluated as written, one rounding per operation, no contraction; division and square root are
+ * correctly rounded.
+ * 1. Live and range, as smx_recon_decimate_mesh and smx_recon_mesh_components step 1: a triangle with a corner that is not live
+ *    (!(RadiusSquared < 0) and a finite smooth position) is dropped and counted in n_not_live.  An index >= n anywhere in the
+ *    input: SMX_ERR_INVALID_ARGUMENT, nothing is written.  The surviving triangles are R.
+ * 2. Half-edges: triangle (p, a, b) of R has the half-edges p->a, a->b and b->p.  For an unordered pair {u, v}, f = the number
+ *    of triangles of R with the half-edge min->max, g = the number with max->min (a half-edge u->u of a triangle with a repeated
+ *    corner counts in f).  The pair is INTERIOR iff f = g = 1, BOUNDARY iff f + g = 1, and NON-MANIFOLD otherwise (three or
+ *    more triangles, or two in the same direction): counted in n_nonmanifold_edges and never boundary.  n_edges = the pairs with
+ *    f + g > 0.  Every boundary half-edge u->v defines the GAP v->u, the half-edge a filling triangle has to supply.
+ * 3. Simple vertices and loops: out(w) = the gaps that leave w, in(w) = the gaps that enter it.  w is SIMPLE iff out(w) = in(w)
+ *    = 1, and then next(w) is the head of its one outgoing gap.  Every other vertex with out + in > 0 is counted in
+ *    n_pinched_vertices (two holes touch there, or a non-manifold fan does).  A LOOP of length L is a cycle w_0 -> next(w_0) =
+ *    w_1 -> ... -> w_{L-1} -> w_0 of simple vertices; w_0 is its smallest slot, the loop's label.  The loops with 3 <= L <=
+ *    max_hole_edges are LISTED.  Longer loops (the outer rim of a sheet is one) and chains that run into a vertex that is not
+ *    simple are left alone; they appear in n_boundary_edges only.
+ * 4. The fill of a listed loop is a fan from the best apex.  With pos = the smooth positions, d = pos[other] - pos[w_i] and
+ *    d2 = (d_x d_x + d_y d_y) + d_z d_z: cost(i) = sum over k = 2 .. L-2, in this order, accumulated from 0.0f, of d2(w_i,
+ *    w_{(i+k) mod L}).  The apex is the i with the smallest (float_bits(cost(i)) << 32) | w_i (for L = 3 every cost is 0 and
+ *    the apex is the label).  Fan triangles: (w_i, w_{(i+k) mod L}, w_{(i+k+1) mod L}) for k = 1 .. L-2.  A loop is filled whole
+ *    or not at all; its status is the first of these that applies:
+ *      SMX_HOLE_DIAGONAL  a fan diagonal {w_i, w_{(i+k) mod L}}, 2 <= k <= L-2, is a pair of R with f + g > 0 already (so an
+ *                         input whose pairs are all interior or boundary stays that way);
+ *      SMX_HOLE_FILTER    some fan triangle (P, A, B), in the order above, does not get the value 1 from the triangle filter of
+ *                         smx_recon_triangulate (interior angles within [min_triangle_angle_deg, max_triangle_angle_deg] by
+ *                         their float32 cosines, the limits' cosines formed as (float)cos((double)deg * pi / 180); the
+ *                         triangle's normal (A - P) x (B - P) agreeing in sign with the sum of the three corner normals and
+ *                         with each of them).  "The other winding" is a rejection: that refuses the outer boundary of an
+ *                         island and the back of an isolated triangle;
+ *      SMX_HOLE_FILLED    otherwise: its L - 2 fan triangles are the loop's new triangles.
+ * 5. Output: triangles_out = R in input order, every word unchanged, then the new triangles, each rotated so that its smallest
+ *    index is first (winding kept), ascending by (p, a, b).  *n_kept = |R| is the split point, *n_triangles = T_out = |R| +
+ *    n_new_triangles.  holes (optional) gets one row per listed loop, filled or not, ascending by label; *n_holes = their
+ *    number.  Two calls give the same bytes in both outputs.
+ * 6. Consequences: the vertices of different loops are disjoint.  If every pair of the input is interior or boundary, so is
+ *    every pair of the output.  Each filled loop removes exactly L boundary edges.  A second call on the output fills nothing
+ *    and returns its input.  A hole made by deleting one interior triangle of a triangulation comes back as that triangle.
+ * 7. Not done: holes that touch in a vertex; holes longer than max_hole_edges; any triangulation better than a fan; no vertex
+ *    is ever made.  The array as a whole is not in (p, a, b) order: a caller who needs that passes it through
+ *    smx_recon_decimate_mesh or sorts it.
+ * Parameters: 3 <= max_hole_edges <= SMX_FILL_MAX_HOLE_EDGES; the angles finite with 0 <= min < max <= 180; n_in <= 2^28.
+ * Anything else: SMX_ERR_INVALID_ARGUMENT with nothing launched.
+ * Calling rules as smx_recon_mesh_components: ordered after everything enqueued on the object, synchronous.  on_device says where
+ * triangles_in, triangles_out and holes live (host arrays are staged).  capacity < T_out, or holes != NULL and hole_capacity <
+ * n_listed_loops: SMX_ERR_INVALID_ARGUMENT, *n_triangles, *n_kept and *n_holes are all reported, nothing is written to any
+ * output; triangles_out == NULL with capacity 0 is that count-only form.  n_in == 0 is valid.  triangles_out must not overlap
+ * triangles_in (refused).  holes may be NULL (hole_capacity is then ignored).  stats may be NULL; it is filled whenever the
+ * counts are known.  Changes no map state, delta mark, statistic or stamp, nor the state smx_recon_triangulate_update keeps.
+ * The workspace belongs to the object, grows on demand and is reused. */
+#define SMX_FILL_MAX_HOLE_EDGES 32
+enum { SMX_HOLE_FILLED = 1, SMX_HOLE_DIAGONAL = 2, SMX_HOLE_FILTER = 3 };
+typedef struct {
+  uint32_t max_hole_edges;          /* loops of 3 .. this many edges are listed */
+  float    min_triangle_angle_deg;  /* the triangle filter's limits, as in smx_mesh_params */
+  float    max_triangle_angle_deg;
+} smx_fill_params;
+typedef struct {            /* 12 bytes, one per listed loop, table ascending by label */
+  uint32_t label;           /* smallest slot index on the loop */
+  uint32_t n_edges;         /* L */
+  uint32_t status;          /* SMX_HOLE_* */
+} smx_mesh_hole;
+typedef struct {
+  uint32_t n_in;                /* triangles given */
+  uint32_t n_not_live;          /* of those, dropped because a corner is not live */
+  uint32_t n_edges;             /* unordered pairs with f + g > 0 */
+  uint32_t n_boundary_edges;    /* of those, with f + g = 1 (before the fill) */
+  uint32_t n_nonmanifold_edges; /* neither interior nor boundary */
+  uint32_t n_pinched_vertices;  /* out + in > 0 and not simple */
+  uint32_t n_listed_loops;
+  uint32_t n_filled_loops;
+  uint32_t n_rejected_diagonal;
+  uint32_t n_rejected_filter;
+  uint32_t n_new_triangles;
+  uint32_t n_triangles;         /* T_out */
+} smx_fill_stats;
+int smx_fill_params_default(smx_fill_params* out);   /* 8, 10.0f, 170.0f */
+int smx_recon_fill_holes(smx_recon r, smx_stream s, const smx_fill_params* p,
+                         const uint32_t* triangles_in, uint32_t n_in,
+                         uint32_t* triangles_out, uint32_t capacity,
+                         smx_mesh_hole* holes /* may be NULL */, uint32_t hole_capacity,
+                         int32_t on_device, uint32_t* n_triangles, uint32_t* n_kept, uint32_t* n_holes,
+                         smx_fill_stats* stats);
+/* Tools: milliseconds the last smx_recon_fill_holes call spent in its SMX_FILL_PHASES phases -- edges (mark, insert,
+ * classify), loops (walk, scan, list), fill (apex, tests, the new run's order), write (R, the new run, the table) -- by timed
+ * events on the call's stream; a phase a call did not reach reads 0.  capacity >= SMX_FILL_PHASES.  Zeros before the first call. */
+#define SMX_FILL_PHASES 4
+int smx_recon_debug_fill_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the

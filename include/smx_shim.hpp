@@ -628,6 +628,28 @@ class CUDASurfelReconstruction {
     }
     SMX_SHIM_CHECK(rc);
   }
+  // Not in the reference: the small holes of a triangle array closed by fans (smx_recon_fill_holes in smx.h).  *triangles_out
+  // (not the same vector) receives the live input triangles in input order, then the new ones; *n_kept (may be null) where
+  // the new run starts; *holes (may be null) the table of the listed loops, filled or not; stats may be null.  Synchronous.
+  void FillHoles(cudaStream_t stream, const std::vector<u32>& triangles_in, const smx_fill_params& params,
+                 std::vector<u32>* triangles_out, u32* n_kept = nullptr, std::vector<smx_mesh_hole>* holes = nullptr,
+                 smx_fill_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles_in.size() / 3);
+    u32 count = 0, kept = 0, listed = 0;
+    int rc = smx_recon_fill_holes(handle_, stream, &params, triangles_in.data(), n_in, nullptr, 0, nullptr, 0, 0, &count, &kept, &listed,
+                                  stats);
+    if (rc == SMX_OK || (rc == SMX_ERR_INVALID_ARGUMENT && count > 0)) {   // (the capacity rule: the counts came back)
+      triangles_out->resize((size_t)3 * count);
+      if (holes) holes->resize(listed);
+      const bool table = holes && !holes->empty();
+      rc = (count || table)
+               ? smx_recon_fill_holes(handle_, stream, &params, triangles_in.data(), n_in, count ? triangles_out->data() : nullptr, count,
+                                      table ? holes->data() : nullptr, table ? listed : 0, 0, &count, &kept, &listed, stats)
+               : SMX_OK;
+    }
+    SMX_SHIM_CHECK(rc);
+    if (n_kept) *n_kept = kept;
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

@@ -195,6 +195,27 @@ class ComponentsStats(C.Structure):
 COMPONENTS_PHASES = 4   # SMX_COMPONENTS_PHASES
 
 
+class FillParams(C.Structure):
+    """smx_fill_params: the longest loop smx_recon_fill_holes lists, and the limits of the triangle filter."""
+    _fields_ = [("max_hole_edges", C.c_uint32), ("min_triangle_angle_deg", C.c_float), ("max_triangle_angle_deg", C.c_float)]
+
+
+class MeshHole(C.Structure):
+    """smx_mesh_hole: one row of the table of listed loops."""
+    _fields_ = [("label", C.c_uint32), ("n_edges", C.c_uint32), ("status", C.c_uint32)]
+
+
+class FillStats(C.Structure):
+    """smx_fill_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_edges", "n_boundary_edges", "n_nonmanifold_edges",
+                                          "n_pinched_vertices", "n_listed_loops", "n_filled_loops", "n_rejected_diagonal",
+                                          "n_rejected_filter", "n_new_triangles", "n_triangles")]
+
+
+FILL_PHASES = 4             # SMX_FILL_PHASES
+FILL_MAX_HOLE_EDGES = 32    # SMX_FILL_MAX_HOLE_EDGES
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -272,6 +293,7 @@ EXPORTS = [
     "smx_recon_triangulate_update", "smx_recon_triangulate_reset", "smx_recon_debug_mesh_update_timings", "smx_recon_deform_by_creation_frame",
     "smx_recon_decimate_mesh", "smx_recon_debug_decimate_timings",
     "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
+    "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

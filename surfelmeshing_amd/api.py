@@ -24,6 +24,7 @@ import numpy as np
 from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
                    COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
+                   FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -43,6 +44,22 @@ def components_params(min_triangles=0, min_diagonal=0.0, keep_largest=0):
     if not (d >= 0.0 and d != float("inf")):
         raise ValueError("min_diagonal must be finite and >= 0")
     return ComponentsParams(int(min_triangles), d, int(keep_largest))
+
+
+# smx_mesh_hole as a numpy record: what FillHoles(return_holes=True) returns; its status values
+HOLE_DTYPE = np.dtype([("label", "<u4"), ("n_edges", "<u4"), ("status", "<u4")])
+SMX_HOLE_FILLED, SMX_HOLE_DIAGONAL, SMX_HOLE_FILTER = 1, 2, 3
+
+
+def fill_params(max_hole_edges=8, min_triangle_angle_deg=10.0, max_triangle_angle_deg=170.0):
+    """The parameters of FillHoles as smx_fill_params; ValueError on what the library would refuse, before anything is
+    called."""
+    if isinstance(max_hole_edges, bool) or int(max_hole_edges) != max_hole_edges or not 3 <= int(max_hole_edges) <= FILL_MAX_HOLE_EDGES:
+        raise ValueError("max_hole_edges must be an integer within 3 .. %d" % FILL_MAX_HOLE_EDGES)
+    lo, hi = float(np.float32(min_triangle_angle_deg)), float(np.float32(max_triangle_angle_deg))
+    if not (lo - lo == 0.0 and hi - hi == 0.0 and 0.0 <= lo < hi <= 180.0):
+        raise ValueError("the triangle angles must be finite with 0 <= min < max <= 180")
+    return FillParams(int(max_hole_edges), lo, hi)
 
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
 
@@ -812,6 +829,50 @@ class CUDASurfelReconstruction:
         out = (C.c_float * COMPONENTS_PHASES)()
         _lib.check(_lib.load().smx_recon_debug_components_timings(self._h, out, C.c_int32(COMPONENTS_PHASES)))
         return dict(zip(("mark_link", "flatten_number", "measure", "write"), [float(v) for v in out]))
+
+    def FillHoles(self, stream, triangles, max_hole_edges=8, min_triangle_angle_deg=10.0, max_triangle_angle_deg=170.0,
+                  return_holes=False):
+        """Not in the reference: the small holes of `triangles` ([T,3] slot indices in any order, e.g. Triangulate's or
+        MeshComponents') closed on the device (smx_recon_fill_holes).  A hole is a closed loop of 3 .. max_hole_edges
+        boundary edges through vertices no other hole touches; it is closed by a fan from the vertex with the shortest
+        diagonals, whole or not at all: not if a diagonal of the fan is an edge of the mesh already, and not if a fan
+        triangle fails Triangulate's triangle filter with the two angle limits given.  The result is the live triangles of
+        the input, in input order, followed by the new ones (each starting at its smallest index, ascending); no vertex is
+        made.  Synchronous.  Returns (triangles [T_out,3] uint32, dict of smx_fill_stats plus n_kept = where the new run
+        starts), then with return_holes the table of the listed loops, filled or not, ascending by label, as a structured
+        array of HOLE_DTYPE."""
+        p = fill_params(max_hole_edges, min_triangle_angle_deg, max_triangle_angle_deg)
+        tri = np.ascontiguousarray(triangles, np.uint32)
+        if tri.size % 3:
+            raise ValueError("triangles must hold three indices per triangle")
+        tri = tri.reshape(-1, 3)
+        L = _lib.load()
+        T, kept, nh, st = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), FillStats()
+        tin = tri.ctypes.data_as(C.c_void_p) if tri.shape[0] else None
+
+        def call(out, table):
+            return L.smx_recon_fill_holes(
+                self._h, _sv(stream), C.byref(p), tin, C.c_uint32(tri.shape[0]),
+                out.ctypes.data_as(C.c_void_p) if out is not None and out.size else None,
+                C.c_uint32(0 if out is None else out.shape[0]),
+                table.ctypes.data_as(C.c_void_p) if table is not None and table.size else None,
+                C.c_uint32(0 if table is None else table.shape[0]), C.c_int32(0), C.byref(T), C.byref(kept), C.byref(nh), C.byref(st))
+        rc = call(None, None)
+        if rc != 0 and not (rc == -1 and T.value > 0):   # (SMX_ERR_INVALID_ARGUMENT with the counts: the capacity rule)
+            _lib.check(rc)
+        out = np.zeros((T.value, 3), np.uint32)
+        table = np.zeros(nh.value, HOLE_DTYPE) if return_holes else None
+        if T.value or (table is not None and table.size):
+            _lib.check(call(out, table))
+        stats = {n: int(getattr(st, n)) for n, _ in FillStats._fields_}
+        stats["n_kept"] = int(kept.value)
+        return (out, stats, table) if return_holes else (out, stats)
+
+    def debug_fill_timings(self):
+        """Milliseconds of the last FillHoles call, by phase."""
+        out = (C.c_float * FILL_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_fill_timings(self._h, out, C.c_int32(FILL_PHASES)))
+        return dict(zip(("edges", "loops", "fill", "write"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

@@ -17,6 +17,13 @@ A coarser level of detail of either (smx_recon_decimate_mesh) -- v
 Without its small pieces (smx_recon_mesh_components) -- connected components through shared vertices:
 
     clean, component_stats = meshing.clean_map_mesh(rec, triangles, min_triangles=20, min_diagonal=0.05)
+
+With its small holes closed (smx_recon_fill_holes) -- fans over boundary loops of at most max_hole_edges edges:
+
+    filled, fill_stats = meshing.fill_map_mesh(rec, clean, max_hole_edges=8)
+
+The order of the chain is clean -> fill -> decimate: cleaning first, so that no hole of a piece that goes is filled, and
+decimation last, because it does not keep the mesh manifold and puts the whole array back into (p, a, b) order.
 """
 from ._lib import MeshParams as _MeshParamsPOD
 
@@ -27,6 +34,9 @@ DECIMATE_STAT_NAMES = ("n_in", "n_not_live", "n_used_vertices", "n_cells", "n_co
 COMPONENTS_STAT_NAMES = ("n_in", "n_not_live", "n_used_vertices", "n_components", "n_kept_components", "n_largest_triangles",
                          "n_triangles")
 CLEAN_KEYS = ("min_triangles", "min_diagonal", "keep_largest")
+FILL_STAT_NAMES = ("n_in", "n_not_live", "n_edges", "n_boundary_edges", "n_nonmanifold_edges", "n_pinched_vertices", "n_listed_loops",
+                   "n_filled_loops", "n_rejected_diagonal", "n_rejected_filter", "n_new_triangles", "n_triangles")
+FILL_KEYS = ("max_hole_edges", "min_triangle_angle_deg", "max_triangle_angle_deg")
 STAT_NAMES = ("n_live", "n_star_triangles", "n_triangles", "star_overflow", "truncated_lists")
 
 
@@ -94,11 +104,36 @@ def clean_map_mesh(rec, triangles, min_triangles=0, min_diagonal=0.0, keep_large
     return rec.MeshComponents(stream, triangles, min_triangles, min_diagonal, keep_largest, return_labels, return_components)
 
 
+def fill_options(fill):
+    """`fill` of MapMesher.update as keyword arguments of fill_map_mesh: None, or a dict with keys out of FILL_KEYS whose
+    values the library would take (checked here, before anything runs)."""
+    if fill is None:
+        return None
+    from .api import fill_params
+    unknown = sorted(set(fill) - set(FILL_KEYS))
+    if unknown:
+        raise ValueError("fill: unknown key(s) %s (known: %s)" % (", ".join(map(str, unknown)), ", ".join(FILL_KEYS)))
+    fill_params(**fill)
+    return dict(fill)
+
+
+def fill_map_mesh(rec, triangles, max_hole_edges=8, min_triangle_angle_deg=10.0, max_triangle_angle_deg=170.0, stream=None,
+                  return_holes=False):
+    """Closes the small holes of `triangles` ([T,3] slot indices of `rec`'s map): every closed loop of 3 .. max_hole_edges
+    boundary edges that touches no other hole gets a fan of new triangles, unless a diagonal of the fan exists already or a
+    fan triangle fails the triangulation's triangle filter at the two angle limits.  The result is the live input triangles
+    in input order, then the new ones.  Returns (triangles [T_out,3] uint32, stats dict[, table of the listed loops])."""
+    from .api import fill_params
+    fill_params(max_hole_edges, min_triangle_angle_deg, max_triangle_angle_deg)
+    return rec.FillHoles(stream, triangles, max_hole_edges, min_triangle_angle_deg, max_triangle_angle_deg, return_holes)
+
+
 class MapMesher:
     """Keeps the mesh of `rec`'s map up to date.  Owns the neighbour index; update() returns what mesh_map would return
     on the map as it stands, plus the update statistics, and keeps the triangles in .triangles / .stats.  With a
     cell_size, update() also decimates the result (.decimated / .decimate_stats) and returns that array as a fourth value.
-    With clean, the small pieces are removed first (.cleaned / .clean_stats): cleaning is applied before cell_size."""
+    With clean, the small pieces are removed first (.cleaned / .clean_stats): cleaning is applied before cell_size.
+    With fill, the small holes are closed (.filled / .fill_stats).  The order is clean -> fill -> decimate."""
 
     def __init__(self, rec, params=None, cell_size=None, full_above_fraction=None):
         from .api import SurfelNeighborIndex
@@ -110,29 +145,37 @@ class MapMesher:
         self.triangles, self.stats, self.update_stats = None, None, None
         self.decimated, self.decimate_stats = None, None
         self.cleaned, self.clean_stats = None, None
+        self.filled, self.fill_stats = None, None
 
     @property
     def index(self):
         """The neighbour index, built over the map as of the last update()."""
         return self._index
 
-    def update(self, stream=None, cell_size=None, clean=None):
+    def update(self, stream=None, cell_size=None, clean=None, fill=None):
         """cell_size (of the decimation grid, metres; not the index's): None = no decimation.  clean: None, or a dict of
         clean_map_mesh's thresholds (CLEAN_KEYS); the cleaned array (.cleaned / .clean_stats) is what gets decimated, and
-        without a cell_size it is returned as the fourth value."""
+        without a cell_size it is returned as the fourth value.  fill: None, or a dict of fill_map_mesh's parameters
+        (FILL_KEYS); the order is clean -> fill -> decimate, each step takes the array of the one before, and the fourth
+        value is the array of the last step that ran (.filled / .fill_stats keep the filled one)."""
         options = clean_options(clean)
+        filling = fill_options(fill)
         self.triangles, self.stats, self.update_stats = self._rec.TriangulateUpdate(
             stream, self._pod, index=self._index, cell_size=self._cell_size, full_above_fraction=self._fraction)
         self.decimated, self.decimate_stats = None, None
         self.cleaned, self.clean_stats = None, None
+        self.filled, self.fill_stats = None, None
         source = self.triangles
         if options is not None:
             self.cleaned, self.clean_stats = self._rec.MeshComponents(stream, self.triangles, **options)
             source = self.cleaned
+        if filling is not None:
+            self.filled, self.fill_stats = self._rec.FillHoles(stream, source, **filling)
+            source = self.filled
         if cell_size is None:
-            if options is None:
+            if options is None and filling is None:
                 return self.triangles, self.stats, self.update_stats
-            return self.triangles, self.stats, self.update_stats, self.cleaned
+            return self.triangles, self.stats, self.update_stats, source
         self.decimated, self.decimate_stats = self._rec.DecimateMesh(stream, source, cell_size)
         return self.triangles, self.stats, self.update_stats, self.decimated
 
@@ -145,6 +188,7 @@ class MapMesher:
         self.triangles, self.stats, self.update_stats = None, None, None
         self.decimated, self.decimate_stats = None, None
         self.cleaned, self.clean_stats = None, None
+        self.filled, self.fill_stats = None, None
 
     def close(self):
         if self._index is not None:

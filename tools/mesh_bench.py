@@ -5,6 +5,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --update [--target 5000000] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --decimate CELL[,CELL...] [--target 5000000] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --components [--decimate CELL[,CELL...]] [--compare_json OTHER.json] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --fill [EDGES] [--decimate CELL[,CELL...]] [--small_target N] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -30,7 +31,15 @@ library's own (smx_recon_debug_components_timings); bytes by components_traffic_
 histogram of component sizes (1, 2-9, 10-99, ..., and the largest); the full triangulation re-measured beside it.  Writes
 profiles/components_bench.{txt,json} unless --txt / --json say otherwise.  --compare_json names the JSON another build of
 the library wrote with the same command on the same box (SMX_LIB_PATH, tools/build_variant.sh): its per-phase times are
-printed beside this build's, row by row -- the A/B of the measure phase with and without wave aggregation."""
+printed beside this build's, row by row -- the A/B of the measure phase with and without wave aggregation.
+
+--fill [EDGES] measures smx_recon_fill_holes with max_hole_edges = EDGES (default 8) on the same map's full mesh
+and, with --decimate, on each decimated mesh, then on the full mesh of a second, small map (the same stream at 160 x 120 grown
+to --small_target live surfels, where the mesh has far more holes per triangle): medians of --reps calls with device arrays
+that are large enough, whole calls by device events and the four phases by the library's own (smx_recon_debug_fill_timings);
+every count of smx_fill_stats; the histogram of the listed loops' lengths; bytes by fill_traffic_bytes below against the HBM
+peak; the full triangulation re-measured beside it.  Writes profiles/fill_bench.{txt,json} unless --txt / --json say
+otherwise."""
 import argparse
 import json
 import os
@@ -48,6 +57,8 @@ ap.add_argument("--txt", default=None)
 ap.add_argument("--decimate", default=None, help="comma-separated cell sizes in metres")
 ap.add_argument("--components", action="store_true")
 ap.add_argument("--compare_json", default=None, help="with --components: the JSON of another build's run, printed beside this one")
+ap.add_argument("--fill", type=int, nargs="?", const=8, default=None, metavar="EDGES", help="measure smx_recon_fill_holes with this max_hole_edges")
+ap.add_argument("--small_target", type=int, default=50_000, help="with --fill: live surfels of the second, 160 x 120 map (0 = none)")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -353,6 +364,140 @@ def components_main():
     nn.close()
 
 
+FILL_PHASES = ("edges", "loops", "fill", "write")
+
+
+def fill_traffic_bytes(n, st, max_hole_edges):
+    """HBM bytes of one smx_recon_fill_holes call over n slots, by phase, from its statistics.  Gathers are counted once per
+    distinct target (a lower bound), an insert as a read and a write of the 16-byte entry it ends at (the probes before it are
+    not counted), an atomic on out / in as a read and a write of its word; the two reads of the counters move a few words."""
+    n_in, T = st["n_in"], st["n_triangles"]
+    rem = n_in - st["n_not_live"]
+    used = st["n_edges"] * 2 // 3 + 1                      # about the vertices of a mesh with that many edges (V ~ E / 3 ... E / 1.5)
+    entries = _table_size(3 * n_in)
+    edges = (16 * entries + 8 * n                          # the table and out / in reset
+             + 12 * n_in + 32 * used + 4 * n_in            # the input, S and N of the corners, the keep flags
+             + 2 * 16 * 3 * rem                            # three inserts per triangle of R
+             + 8 * (n_in // 256 + 1)                       # the scan
+             + 16 * entries + (8 + 8 + 4) * st["n_boundary_edges"])   # classify: every entry read; out, in, next of a boundary pair
+    loops = 8 * n + 4 * n + (8 + 4) * st["n_boundary_edges"] + 8 * (n // 256 + 1) + 4 * n + 12 * st["n_listed_loops"]
+    new = st["n_new_triangles"]
+    bits = max(1, int(n - 1).bit_length())
+    passes = -(-2 * bits // 8) + -(-bits // 8)
+    fill = st["n_listed_loops"] * (12 + max_hole_edges * (4 + 32) + 16 * max_hole_edges + 4) + 12 * new + passes * 32 * new + 2 * 28 * new
+    write = 2 * 4 * n_in + 12 * rem + 12 * rem + 12 * new + 12 * new + 12 * st["n_listed_loops"]
+    return dict(zip(FILL_PHASES, (edges, loops, fill, write)))
+
+
+def fill_main():
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines, out_rows, maps = [], [], []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    cells = [float(c) for c in args.decimate.split(",")] if args.decimate else []
+    prm = api.fill_params(args.fill)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def one_map(name, width, height, target, cells):
+        wl = bench.Workload(api, width, height, target, target + target // 10 + 20000, 0x5EED0001, 0.0)
+        t0 = time.time()
+        wl.grow(False)
+        rec = wl.pipe.reconstruction
+        n, live = rec.surfels_size(), rec.surfel_count()
+        say("# %s: %d x %d, grown in %.1f s: %d slots, %d live" % (name, width, height, time.time() - t0, n, live))
+        nn = api.SurfelNeighborIndex()
+        p = _lib.MeshParams.defaults()
+        cap = 3 * n
+        dtri, ddec, dout = (api.CUDABuffer(1, 3 * cap, np.uint32) for _ in range(3))
+
+        def full():
+            T, st = C.c_uint32(0), _lib.MeshStats()
+            _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                               C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+            return T.value
+
+        def fill(src, n_in, dtab, tab_cap):
+            T, kept, nh, st = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), _lib.FillStats()
+            _lib.check(L.smx_recon_fill_holes(rec._h, None, C.byref(prm), C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in),
+                                              C.c_void_p(dout.ToCUDA().address), C.c_uint32(cap),
+                                              C.c_void_p(dtab.ToCUDA().address) if dtab is not None else None, C.c_uint32(tab_cap),
+                                              C.c_int32(1), C.byref(T), C.byref(kept), C.byref(nh), C.byref(st)))
+            return {k: int(getattr(st, k)) for k, _ in _lib.FillStats._fields_}
+        t_full = []
+        for _ in range(args.reps + 1):
+            ms, T_in = timed(full)
+            t_full.append(ms)
+        full_ms = float(np.median(t_full[1:]))
+        say("%s: full triangulation, re-measured here: %d triangles, one call %.2f ms" % (name, T_in, full_ms))
+        inputs = [("full mesh", dtri, T_in)]
+        for cell in cells:
+            T, st = C.c_uint32(0), _lib.DecimateStats()
+            _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                                 C.c_void_p(ddec.ToCUDA().address), C.c_uint32(cap), None, C.c_int32(1), C.byref(T), C.byref(st)))
+            coarse = api.CUDABuffer(1, 3 * max(T.value, 1), np.uint32)
+            coarse.Upload(np.ascontiguousarray(ddec.Download()[:, :3 * max(T.value, 1)]))
+            inputs.append(("decimated at %g m" % cell, coarse, T.value))
+        for what, src, n_in in inputs:
+            H = fill(src, n_in, None, 0)["n_listed_loops"]             # (allocates; tells the table's size)
+            dtab = api.CUDABuffer(1, 3 * max(H, 1), np.uint32)
+            t, phs, st, head0 = [], [], None, None
+            for _ in range(args.reps + 1):
+                ms, st = timed(lambda: fill(src, n_in, dtab, H))
+                t.append(ms)
+                phs.append(rec.debug_fill_timings())
+                new = dout.Download()[0][3 * (st["n_triangles"] - st["n_new_triangles"]):3 * st["n_triangles"]]
+                head = new[:300000].tobytes() + dtab.Download()[0].tobytes()
+                head0 = head if head0 is None else head0
+                assert head == head0, "two calls gave different bytes"
+            med = float(np.median(t[1:]))
+            ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in FILL_PHASES}
+            b = fill_traffic_bytes(n, st, args.fill)
+            tot = sum(b.values())
+            say("%s, %s, max_hole_edges %d: %s | call %.2f ms (min %.2f, max %.2f) = %.3f x the full triangulation | %s | model %.2f GB -> "
+                "%.2f TB/s = %.0f %% of the %.1f TB/s HBM peak (%s)" % (
+                    name, what, args.fill, " ".join("%s %d" % (k, st[k]) for k, _ in _lib.FillStats._fields_), med, min(t[1:]), max(t[1:]),
+                    med / full_ms, " ".join("%s %.3f" % (k, ph[k]) for k in FILL_PHASES), tot / 1e9, tot / (med * 1e-3) / 1e12,
+                    100.0 * tot / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12,
+                    " ".join("%s %.0f %%" % (k, 100.0 * b[k] / (max(ph[k], 1e-6) * 1e-3) / HBM_PEAK) for k in FILL_PHASES)))
+            table = dtab.Download()[0][:3 * H].view(api.HOLE_DTYPE)
+            hist = np.bincount(table["n_edges"], minlength=args.fill + 1)[3:].tolist()
+            by_status = np.bincount(table["status"], minlength=4)[1:4].tolist()
+            say("    listed loops by length 3 .. %d: %s; filled / diagonal / filter: %s; boundary edges left %d of %d" % (
+                args.fill, hist, by_status, st["n_boundary_edges"] - int(table["n_edges"][table["status"] == 1].sum()), st["n_boundary_edges"]))
+            out_rows.append({"map": name, "input": what, "max_hole_edges": args.fill, "reps": len(t) - 1, "call_ms": med, "call_ms_all": t[1:],
+                             "phases_ms": ph, "phases_ms_all": phs[1:], "stats": st, "loop_length_histogram_from_3": hist,
+                             "loops_filled_diagonal_filter": by_status, "traffic_model_bytes": b,
+                             "fraction_of_hbm_peak": tot / (med * 1e-3) / HBM_PEAK, "ratio_to_full_triangulation": med / full_ms})
+            dtab.close()
+        maps.append({"map": name, "width": width, "height": height, "slots": n, "live": live, "triangles_in": T_in, "full_triangulation_ms": full_ms})
+        for _, src, _ in inputs[1:]:
+            src.close()
+        for buf in (dtri, ddec, dout):
+            buf.close()
+        nn.close()
+    one_map("C2", 640, 480, args.target, cells)
+    if args.small_target > 0:
+        one_map("small", 160, 120, args.small_target, [])
+    res = {"metric": "mesh_fill_holes_ms", "label": args.label, "maps": maps, "rows": out_rows}
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(args.json or os.path.join(ROOT, "profiles", "fill_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "fill_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 UPDATE_PHASES = ("diff", "index_builds", "reverse_test", "subset_lists", "stars", "agree_merge")
 
 
@@ -515,4 +660,4 @@ def main():
 
 
 if __name__ == "__main__":
-    components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -6,6 +6,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--track_rgbd [--track_photometric_weight W]]
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
+                              [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -18,9 +19,12 @@ size (smx_recon_decimate_mesh) before --export_mesh, which then writes only the 
 the small connected pieces of the final mesh (smx_recon_mesh_components): a piece stays if it has at least that many
 triangles and a bounding-box diagonal of at least that length, and of those only the K largest.  Cleaning is applied before
 --mesh_decimate; --export_mesh then writes only the vertices the remaining mesh uses.
+--mesh_fill_holes EDGES (with --mesh or --mesh_every; 0 = off) closes the holes of the final mesh that have at most that many
+edges (smx_recon_fill_holes), after cleaning and before --mesh_decimate; --mesh_fill_min_angle / --mesh_fill_max_angle are the
+limits of the triangle filter the new triangles have to pass (default 10 / 170 degrees).  The statistics line is printed.
 --render_source mesh (with --mesh or --mesh_every) makes --render_dir / --render_every / --render_overview draw the current
 mesh with smx_recon_render_mesh instead of splats: the kept array of --mesh_every as of its last update, otherwise a
-triangulation of the map as it stands, cleaned and decimated first if those flags are given.
+triangulation of the map as it stands, cleaned, filled and decimated first if those flags are given.
 With --track the folder needs no trajectory: every frame is tracked against the map (frame-to-model ICP) `half` frames
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
@@ -175,6 +179,12 @@ def parse_args(argv=None):
                     help="with --mesh or --mesh_every: drop the connected pieces whose bounding-box diagonal is shorter")
     ap.add_argument("--mesh_keep_largest", type=int, default=None, metavar="K",
                     help="with --mesh or --mesh_every: keep only the K largest connected pieces (of those that pass the other two)")
+    ap.add_argument("--mesh_fill_holes", type=int, default=0, metavar="EDGES",
+                    help="with --mesh or --mesh_every: close the holes of the final mesh with at most this many edges (3 .. 32; 0 = off)")
+    ap.add_argument("--mesh_fill_min_angle", type=float, default=None, metavar="DEG",
+                    help="with --mesh_fill_holes: smallest interior angle a new triangle may have (default 10)")
+    ap.add_argument("--mesh_fill_max_angle", type=float, default=None, metavar="DEG",
+                    help="with --mesh_fill_holes: largest interior angle a new triangle may have (default 170)")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -204,6 +214,19 @@ def parse_args(argv=None):
     if any(v is not None for v in (args.mesh_min_component, args.mesh_min_extent, args.mesh_keep_largest)):
         args.mesh_clean = dict(min_triangles=args.mesh_min_component or 0, min_diagonal=args.mesh_min_extent or 0.0,
                                keep_largest=args.mesh_keep_largest or 0)
+    args.mesh_fill = None
+    if args.mesh_fill_holes != 0:
+        if not (args.mesh or args.mesh_every > 0):
+            ap.error("--mesh_fill_holes needs --mesh or --mesh_every")
+        if not 3 <= args.mesh_fill_holes <= 32:
+            ap.error("--mesh_fill_holes needs an edge count within 3 .. 32 (0 = off)")
+        lo = 10.0 if args.mesh_fill_min_angle is None else args.mesh_fill_min_angle
+        hi = 170.0 if args.mesh_fill_max_angle is None else args.mesh_fill_max_angle
+        if not 0.0 <= lo < hi <= 180.0:
+            ap.error("--mesh_fill_min_angle / --mesh_fill_max_angle need 0 <= min < max <= 180")
+        args.mesh_fill = dict(max_hole_edges=args.mesh_fill_holes, min_triangle_angle_deg=lo, max_triangle_angle_deg=hi)
+    elif args.mesh_fill_min_angle is not None or args.mesh_fill_max_angle is not None:
+        ap.error("--mesh_fill_min_angle / --mesh_fill_max_angle need --mesh_fill_holes")
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
     return args
@@ -271,6 +294,8 @@ def main():
             tri, _ = meshing.mesh_map(pipe.reconstruction)
         if args.mesh_clean is not None:
             tri, _ = meshing.clean_map_mesh(pipe.reconstruction, tri, **args.mesh_clean)
+        if args.mesh_fill is not None:
+            tri, _ = meshing.fill_map_mesh(pipe.reconstruction, tri, **args.mesh_fill)
         if args.mesh_decimate is not None:
             tri, _ = meshing.decimate_map_mesh(pipe.reconstruction, tri, args.mesh_decimate)
         return tri
@@ -344,6 +369,12 @@ def main():
         print("cleaned in %.1f ms: components %d in / %d kept (the largest has %d triangles), triangles %d in / %d out" % (
             1e3 * (time.time() - t1), cst["n_components"], cst["n_kept_components"], cst["n_largest_triangles"], n_before,
             triangles.shape[0]))
+    if args.mesh_fill is not None:
+        from surfelmeshing_amd import meshing
+        t1 = time.time()
+        triangles, fst = meshing.fill_map_mesh(rec, triangles, **args.mesh_fill)
+        print("holes of up to %d edges filled in %.1f ms: %s" % (args.mesh_fill["max_hole_edges"], 1e3 * (time.time() - t1),
+                                                                 ", ".join("%s %d" % (k, fst[k]) for k in meshing.FILL_STAT_NAMES)))
     if args.mesh_decimate is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
