@@ -1099,6 +1099,101 @@ int smx_recon_fill_holes(smx_recon r, smx_stream s, const smx_fill_params* p,
 #define SMX_FILL_PHASES 4
 int smx_recon_debug_fill_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- the distance from points to a triangle array: closest triangle, distance, closest point ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n) with n =
+ * surfels_size()), of `triangles` (uint32 [n_in][3], slot indices, in ANY order), of `points` (float [n_points][3]) and of p.
+ * Every quantity is an integer or a float32 expression evaluated as written, one rounding per operation, no contraction; division
+ * and square root are correctly rounded.  Throughout dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z, and cross(u, v) = (u_y v_z -
+ * u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x).  A scalar times a vector is three products, a sum of vectors three sums.
+ * 1. Live, range and shape.  An index >= n anywhere in `triangles`: SMX_ERR_INVALID_ARGUMENT, nothing is written.  A triangle
+ *    with a corner that is not live (!(RadiusSquared < 0) and a finite smooth position, as smx_recon_decimate_mesh step 1) is
+ *    dropped and counted in n_not_live; of the rest, one with a repeated index is dropped and counted in n_repeated; of the rest,
+ *    one with a corner coordinate of magnitude > SMX_DIST_MAX_COORD is dropped and counted in n_out_of_range.  The survivors are
+ *    R; each keeps t, its position in the input.
+ * 2. Points.  A point with a non-finite coordinate or one of magnitude > SMX_DIST_MAX_COORD is BAD, counted in n_bad_points,
+ *    and its outputs are those of "none" below.
+ * 3. The closest point Q of P on (A, B, C), the corners of a triangle of R in input order: Ericson's regions in this order,
+ *    first match wins:
+ *      ab = B-A; ac = C-A; ap = P-A;  d1 = dot(ab,ap); d2 = dot(ac,ap)
+ *      if d1 <= 0 and d2 <= 0:                 Q = A
+ *      bp = P-B; d3 = dot(ab,bp); d4 = dot(ac,bp)
+ *      if d3 >= 0 and d4 <= d3:                Q = B
+ *      vc = d1*d4 - d3*d2
+ *      if vc <= 0 and d1 >= 0 and d3 <= 0:     v = d1/(d1-d3);  Q = A + v*ab
+ *      cp = P-C; d5 = dot(ab,cp); d6 = dot(ac,cp)
+ *      if d6 >= 0 and d5 <= d6:                Q = C
+ *      vb = d5*d2 - d1*d6
+ *      if vb <= 0 and d2 >= 0 and d6 <= 0:     w = d2/(d2-d6);  Q = A + w*ac
+ *      va = d3*d6 - d5*d4
+ *      if va <= 0 and (d4-d3) >= 0 and (d5-d6) >= 0:
+ *                                              w = (d4-d3)/((d4-d3)+(d5-d6));  Q = B + w*(C-B)
+ *      else: s = (va+vb)+vc; v = vb/s; w = vc/s
+ *            v = v < 0 ? 0 : (v > 1 ? 1 : v);  lim = 1 - v;  w = w < 0 ? 0 : (w > lim ? lim : w)
+ *            Q = (A + v*ab) + w*ac
+ *      e = P-Q;  dist2 = dot(e,e)
+ *    (Exact arithmetic reaches the last branch only with va, vb, vc > 0; float32 may not, so v and w are held to the triangle:
+ *    Q then lies in the hull of A, B, C in every branch, which is what lets a grid find every candidate.  The comparisons keep a
+ *    NaN a NaN.)
+ *    The triangle is a CANDIDATE for P iff dist2 <= max_distance*max_distance (one float32 product).  A NaN dist2 (coincident
+ *    or collinear corners) therefore never is.
+ * 4. The answer for P: the candidate with the smallest key (float_bits(dist2) << 32) | t -- the distance decides, then the
+ *    smallest input position.  nearest = t, distance = sqrt(dist2), closest = Q.  With signed_distance, distance is negated iff
+ *    dot(e, cross(ab, ac)) < 0.  With no candidate, or for a BAD point: nearest = 0xFFFFFFFF, distance = +infinity, closest =
+ *    (NaN, NaN, NaN).  The answer is the minimum over ALL of R: it does not depend on cell_size, on the search structure or on
+ *    the schedule.  Two calls give the same bytes.
+ * 5. smx_distance_stats: the counts of steps 1 and 2; n_matched = the points with a candidate; max_dist2_bits = the largest
+ *    matched dist2 as its bits (0 if none); histogram: a matched point counts in bin min(31, (uint32)((|distance| * 32.0f) /
+ *    max_distance)).  n_wide, n_entries, n_cells describe the search structure: a uniform grid with c = max(cell_size, 1.125f *
+ *    max_distance), the cell of a coordinate x is (int32)floorf(x / c), a triangle of R is entered in every cell of the box
+ *    from the cell of its per-axis minimum to the cell of its per-axis maximum unless that box has more than
+ *    SMX_DIST_WIDE_CELLS cells, in which case it goes on the wide list every query tests in full.  n_entries = the (cell,
+ *    triangle) entries, n_cells = the occupied cells.  With cell_size == 0 the library takes max(1.125f * max_distance, the mean
+ *    over R of the largest of the three extents of a triangle's box) for c; these three and cell_size_used are defined exactly
+ *    only when cell_size > 0 is given.
+ * 6. Not done: no BVH; no mesh-to-mesh Hausdorff distance in one call (the caller samples one mesh and swaps roles); no
+ *    distance to an analytic surface.
+ * Parameters: max_distance finite with 1e-3f <= max_distance <= 16.0f; cell_size 0 or finite and > 0; signed_distance 0 or 1;
+ * n_in <= 2^28 and n_points <= 2^28.  Anything else: SMX_ERR_INVALID_ARGUMENT with nothing launched.  A cell_size so far below
+ * the triangles' size that the grid would hold more than 2^30 entries is refused after the mark phase, nothing written.
+ * Calling rules as smx_recon_mesh_components: ordered after everything enqueued on the object, synchronous.  on_device says where
+ * triangles, points, nearest, distance and closest live (host arrays are staged).  n_in == 0 is valid (every point is "none"),
+ * and so is n_points == 0.  closest may be NULL.  The outputs must not overlap the inputs (refused).  stats may be NULL.
+ * Changes no map state, delta mark, statistic or stamp, nor the state smx_recon_triangulate_update keeps.  The workspace
+ * belongs to the object, grows on demand, is reused and is freed with the object. */
+#define SMX_DIST_MAX_COORD 64.0f
+#define SMX_DIST_WIDE_CELLS 64
+#define SMX_DIST_BINS 32
+typedef struct {
+  float   max_distance;      /* triangles farther than this are no candidates */
+  float   cell_size;         /* 0: the library chooses */
+  int32_t signed_distance;   /* 0 / 1 */
+} smx_distance_params;
+typedef struct {
+  uint32_t n_in;                      /* triangles given */
+  uint32_t n_not_live;                /* of those, dropped because a corner is not live */
+  uint32_t n_repeated;                /* of the rest, with a repeated index */
+  uint32_t n_out_of_range;            /* of the rest, with a coordinate beyond SMX_DIST_MAX_COORD */
+  uint32_t n_points;
+  uint32_t n_bad_points;
+  uint32_t n_matched;
+  uint32_t max_dist2_bits;
+  uint32_t histogram[SMX_DIST_BINS];
+  uint32_t n_wide, n_entries, n_cells;
+  float    cell_size_used;
+} smx_distance_stats;
+int smx_distance_params_default(smx_distance_params* out);   /* 0.05f, 0.0f, 0 */
+int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params* p,
+                            const uint32_t* triangles, uint32_t n_in,
+                            const float* points /* [n_points][3] */, uint32_t n_points,
+                            uint32_t* nearest /* [n_points] */, float* distance /* [n_points] */,
+                            float* closest /* [n_points][3], may be NULL */,
+                            int32_t on_device, smx_distance_stats* stats /* may be NULL */);
+/* Tools: milliseconds the last smx_recon_mesh_distance call spent in its SMX_DIST_PHASES phases -- mark (classes, c, boxes,
+ * the wide list, scan), index (entries, sort, records, cell table), query (the points' sort, the walk), stats -- by timed events
+ * on the call's stream; a phase a call did not reach reads 0.  capacity >= SMX_DIST_PHASES.  Zeros before the first call. */
+#define SMX_DIST_PHASES 4
+int smx_recon_debug_distance_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the

@@ -650,6 +650,20 @@ class CUDASurfelReconstruction {
     SMX_SHIM_CHECK(rc);
     if (n_kept) *n_kept = kept;
   }
+  // Not in the reference: for every point (x, y, z triples) its closest triangle of `triangles` within params.max_distance
+  // (smx_recon_mesh_distance in smx.h).  *nearest gets the triangle's position in the array or 0xFFFFFFFF, *distance the distance
+  // or +infinity, *closest (may be null) the closest point or NaNs; stats may be null.  Synchronous.
+  void MeshDistance(cudaStream_t stream, const std::vector<u32>& triangles, const std::vector<float>& points,
+                    const smx_distance_params& params, std::vector<u32>* nearest, std::vector<float>* distance,
+                    std::vector<float>* closest = nullptr, smx_distance_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles.size() / 3), n_points = (u32)(points.size() / 3);
+    nearest->resize(n_points);
+    distance->resize(n_points);
+    if (closest) closest->resize((size_t)3 * n_points);
+    SMX_SHIM_CHECK(smx_recon_mesh_distance(handle_, stream, &params, n_in ? triangles.data() : nullptr, n_in,
+                                           n_points ? points.data() : nullptr, n_points, n_points ? nearest->data() : nullptr,
+                                           n_points ? distance->data() : nullptr, closest && n_points ? closest->data() : nullptr, 0, stats));
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

@@ -216,6 +216,25 @@ FILL_PHASES = 4             # SMX_FILL_PHASES
 FILL_MAX_HOLE_EDGES = 32    # SMX_FILL_MAX_HOLE_EDGES
 
 
+class DistanceParams(C.Structure):
+    """smx_distance_params: the search radius, the grid's cell (0: the library chooses) and the sign switch."""
+    _fields_ = [("max_distance", C.c_float), ("cell_size", C.c_float), ("signed_distance", C.c_int32)]
+
+
+DIST_PHASES = 4             # SMX_DIST_PHASES
+DIST_BINS = 32              # SMX_DIST_BINS
+DIST_MAX_COORD = 64.0       # SMX_DIST_MAX_COORD
+DIST_WIDE_CELLS = 64        # SMX_DIST_WIDE_CELLS
+DIST_MARGIN = 1.125         # the grid's cell is at least this many max_distance (smx.h step 5)
+
+
+class DistanceStats(C.Structure):
+    """smx_distance_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_points", "n_bad_points",
+                                           "n_matched", "max_dist2_bits")] + [("histogram", C.c_uint32 * DIST_BINS)] +
+                [(n, C.c_uint32) for n in ("n_wide", "n_entries", "n_cells")] + [("cell_size_used", C.c_float)])
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -294,6 +313,7 @@ EXPORTS = [
     "smx_recon_decimate_mesh", "smx_recon_debug_decimate_timings",
     "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
     "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
+    "smx_distance_params_default", "smx_recon_mesh_distance", "smx_recon_debug_distance_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

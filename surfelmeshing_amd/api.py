@@ -25,6 +25,7 @@ from . import _lib
 from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBuffersCPU, ReconStats,  # noqa: F401
                    COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
                    FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
+                   DIST_BINS, DIST_PHASES, DistanceParams, DistanceStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -60,6 +61,35 @@ def fill_params(max_hole_edges=8, min_triangle_angle_deg=10.0, max_triangle_angl
     if not (lo - lo == 0.0 and hi - hi == 0.0 and 0.0 <= lo < hi <= 180.0):
         raise ValueError("the triangle angles must be finite with 0 <= min < max <= 180")
     return FillParams(int(max_hole_edges), lo, hi)
+
+
+def distance_params(max_distance, cell_size=0.0, signed=False):
+    """The parameters of MeshDistance as smx_distance_params; ValueError on what the library would refuse, before anything
+    is called."""
+    m, c = float(np.float32(max_distance)), float(np.float32(cell_size))
+    if not (m - m == 0.0 and float(np.float32(1e-3)) <= m <= 16.0):
+        raise ValueError("max_distance must be finite within 1e-3 .. 16")
+    if not (c - c == 0.0 and c >= 0.0):
+        raise ValueError("cell_size must be 0 (the library chooses) or finite and > 0")
+    if signed not in (False, True, 0, 1):
+        raise ValueError("signed must be a bool")
+    return DistanceParams(m, c, int(bool(signed)))
+
+
+def distance_stats_dict(st):
+    """smx_distance_stats as a dict: integers, histogram a list of DIST_BINS integers, cell_size_used a float."""
+    d = {n: int(getattr(st, n)) for n, _ in DistanceStats._fields_ if n not in ("histogram", "cell_size_used")}
+    d["histogram"] = [int(v) for v in st.histogram]
+    d["cell_size_used"] = float(st.cell_size_used)
+    return d
+
+
+def _device_address(a):
+    """The device address of a device tensor (anything with is_cuda / data_ptr), None for everything else."""
+    if getattr(a, "is_cuda", False) and hasattr(a, "data_ptr"):
+        return int(a.data_ptr())
+    return None
+
 
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
 
@@ -873,6 +903,56 @@ class CUDASurfelReconstruction:
         out = (C.c_float * FILL_PHASES)()
         _lib.check(_lib.load().smx_recon_debug_fill_timings(self._h, out, C.c_int32(FILL_PHASES)))
         return dict(zip(("edges", "loops", "fill", "write"), [float(v) for v in out]))
+
+    def MeshDistance(self, stream, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False):
+        """Not in the reference: for every point of `points` ([P,3] float32) the closest point on `triangles` ([T,3] slot
+        indices in any order, e.g. Triangulate's, DecimateMesh's, MeshComponents' or FillHoles') over the map's smooth
+        positions (smx_recon_mesh_distance).  Only triangles within max_distance count; the answer is exactly the minimum over
+        all of them (ties go to the earlier triangle) whatever cell_size the search grid uses (0: the library chooses).
+        Synchronous.  Both arrays are numpy arrays, or both are contiguous device tensors (uint32 / int32 and float32); the
+        results then are device tensors too (nearest a torch.uint32 tensor).  Returns (nearest [P] uint32 with 0xFFFFFFFF for "none", distance [P] float32
+        with +inf for "none" -- negative behind the triangle if signed --, then with return_closest closest [P,3] float32,
+        then the dict of smx_distance_stats)."""
+        p = distance_params(max_distance, cell_size, signed)
+        L = _lib.load()
+        st = DistanceStats()
+        dev = _device_address(triangles) is not None or _device_address(points) is not None
+        if dev:
+            import torch
+            if _device_address(triangles) is None or _device_address(points) is None:
+                raise ValueError("triangles and points must both be device tensors, or both host arrays")
+            if not (triangles.is_contiguous() and points.is_contiguous() and triangles.element_size() == 4 and
+                    points.dtype == torch.float32 and triangles.numel() % 3 == 0 and points.numel() % 3 == 0):
+                raise ValueError("device tensors must be contiguous: [T,3] 32-bit integers and [P,3] float32")
+            n_in, n_points = triangles.numel() // 3, points.numel() // 3
+            nearest = torch.empty(n_points, dtype=torch.uint32, device=points.device)
+            distance = torch.empty(n_points, dtype=torch.float32, device=points.device)
+            closest = torch.empty((n_points, 3), dtype=torch.float32, device=points.device) if return_closest else None
+            tin, pin = triangles.data_ptr() if n_in else None, points.data_ptr() if n_points else None
+            outs = [a.data_ptr() if a is not None and n_points else None for a in (nearest, distance, closest)]
+            torch.cuda.current_stream(points.device).synchronize()      # (the tensors' producers; the call runs on `stream`)
+        else:
+            tri = np.ascontiguousarray(triangles, np.uint32)
+            pts = np.ascontiguousarray(points, np.float32)
+            if tri.size % 3 or pts.size % 3:
+                raise ValueError("triangles and points must hold three values per row")
+            n_in, n_points = tri.size // 3, pts.size // 3
+            nearest, distance = np.zeros(n_points, np.uint32), np.zeros(n_points, np.float32)
+            closest = np.zeros((n_points, 3), np.float32) if return_closest else None
+            tin, pin = tri.ctypes.data if n_in else None, pts.ctypes.data if n_points else None
+            outs = [a.ctypes.data if a is not None and n_points else None for a in (nearest, distance, closest)]
+        _lib.check(L.smx_recon_mesh_distance(self._h, _sv(stream), C.byref(p), C.c_void_p(tin), C.c_uint32(n_in), C.c_void_p(pin),
+                                             C.c_uint32(n_points), C.c_void_p(outs[0]), C.c_void_p(outs[1]), C.c_void_p(outs[2]),
+                                             C.c_int32(1 if dev else 0), C.byref(st)))
+        stats = distance_stats_dict(st)
+        stats["max_distance"] = float(p.max_distance)      # (what the histogram's bins are fractions of)
+        return (nearest, distance, closest, stats) if return_closest else (nearest, distance, stats)
+
+    def debug_distance_timings(self):
+        """Milliseconds of the last MeshDistance call, by phase."""
+        out = (C.c_float * DIST_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_distance_timings(self._h, out, C.c_int32(DIST_PHASES)))
+        return dict(zip(("mark", "index", "query", "stats"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

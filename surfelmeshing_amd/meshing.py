@@ -22,6 +22,13 @@ With its small holes closed (smx_recon_fill_holes) -- fans over bo
 
     filled, fill_stats = meshing.fill_map_mesh(rec, clean, max_hole_edges=8)
 
+How far points lie from any of these arrays (smx_recon_mesh_distance) -- the exact closest triangle within
+max_distance, and what a decimation moved:
+
+    nearest, distance, stats = meshing.mesh_distance(rec, triangles, points, max_distance=0.05)
+    print(meshing.distance_summary(distance, stats))
+    print(meshing.decimation_error(rec, triangles, coarse, max_distance=0.1)[0])
+
 The order of the chain is clean -> fill -> decimate: cleaning first, so that no hole of a piece that goes is filled, and
 decimation last, because it does not keep the mesh manifold and puts the whole array back into (p, a, b) order.
 """
@@ -194,3 +201,64 @@ class MapMesher:
         if self._index is not None:
             self._index.close()
             self._index = None
+
+
+def mesh_distance(rec, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False, stream=None):
+    """For every point its closest triangle of `triangles` within max_distance, on the device: (nearest, distance[, closest],
+    stats) as CUDASurfelReconstruction.MeshDistance returns them.  ValueError on parameters the library would refuse."""
+    from .api import distance_params
+    distance_params(max_distance, cell_size, signed)
+    return rec.MeshDistance(stream, triangles, points, max_distance, cell_size, signed, return_closest)
+
+
+def distance_summary(distance, stats):
+    """What one MeshDistance call says in a few numbers: the matched fraction (of all points), mean, rms and maximum of
+    |distance| over the matched points (float64 sums over the returned array), and the upper edges of the histogram bins that
+    hold the 50 / 90 / 99 % points of the matched ones, in metres (None without a match).  `distance` may be a device tensor."""
+    import numpy as np
+    d = np.asarray(distance.cpu() if hasattr(distance, "cpu") else distance, np.float64).reshape(-1)
+    m = np.abs(d[np.isfinite(d)])
+    n_points, n_matched = int(stats["n_points"]), int(stats["n_matched"])
+    if m.size != n_matched or d.size != n_points:
+        raise ValueError("distance and stats are not of one call: %d finite of %d entries, %d matched of %d points"
+                         % (m.size, d.size, n_matched, n_points))
+    out = dict(n_points=n_points, n_matched=n_matched, matched_fraction=n_matched / n_points if n_points else 0.0,
+               mean=float(m.mean()) if m.size else None, rms=float(np.sqrt((m * m).mean())) if m.size else None,
+               max=float(m.max()) if m.size else None)
+    hist = np.asarray(stats["histogram"], np.int64)
+    max_distance = stats.get("max_distance")
+    cum = np.cumsum(hist)
+    for q in (50, 90, 99):
+        # the first bin at which the running count reaches q % of the matched points
+        b = int(np.searchsorted(cum, -(-q * n_matched // 100))) if n_matched else None
+        out["bin%d" % q] = b
+        out["p%d_below" % q] = None if b is None or max_distance is None else (b + 1) * float(max_distance) / hist.size
+    return out
+
+
+def format_distance_summary(summary):
+    """distance_summary as one line."""
+    if not summary["n_matched"]:
+        return "0 of %d points matched" % summary["n_points"]
+    mm = lambda v: "n/a" if v is None else "%.2f mm" % (1000.0 * v)     # noqa: E731
+    return ("%d of %d points matched (%.1f %%): mean %s, rms %s, max %s; 50 / 90 / 99 %% below %s / %s / %s" % (
+        summary["n_matched"], summary["n_points"], 100.0 * summary["matched_fraction"], mm(summary["mean"]), mm(summary["rms"]),
+        mm(summary["max"]), mm(summary["p50_below"]), mm(summary["p90_below"]), mm(summary["p99_below"])))
+
+
+def map_positions(rec, slots=None, stream=None):
+    """The smooth positions (rows 3-5) of the map's slots, or of `slots` only, as [m, 3] float32 on the host (NaN rows for merged
+    slots): the three rows through ExportVertices, not the whole map."""
+    import numpy as np
+    from . import export
+    pos = np.ascontiguousarray(export.export_vertices(rec, stream)[0], np.float32)
+    return pos if slots is None else pos[np.asarray(slots, np.int64)]
+
+
+def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None):
+    """How far a decimation moved the surface: the points are the positions of the vertices `fine` uses (ascending by slot),
+    measured against `coarse`.  Returns (distance_summary, nearest, distance, stats)."""
+    import numpy as np
+    used = np.unique(np.ascontiguousarray(fine, np.uint32))
+    nearest, distance, stats = mesh_distance(rec, coarse, map_positions(rec, used, stream), max_distance, cell_size, stream=stream)
+    return distance_summary(distance, stats), nearest, distance, stats

@@ -97,6 +97,14 @@ class SyntheticStream:
         hit = o[None, None, :] + best_t[..., None] * d
         return best_t, hit
 
+    def surface_points(self, f, stride=1):
+        """The noise-free hit points of frame f at every stride-th pixel (rows and columns), those with a finite hit, as
+        [m, 3] float32 in the global frame: the ground truth a reconstruction of the stream is measured against."""
+        z, hit = self._raycast(f)
+        stride = int(stride)
+        z, hit = z[::stride, ::stride], hit[::stride, ::stride]
+        return np.ascontiguousarray(hit[np.isfinite(z)], np.float32)
+
     def frame(self, f):
         """Returns (depth u16 [H,W], colour u8 [H,W,3]) of frame f."""
         z, hit = self._raycast(f)

@@ -6,6 +6,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --decimate CELL[,CELL...] [--target 5000000] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --components [--decimate CELL[,CELL...]] [--compare_json OTHER.json] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --fill [EDGES] [--decimate CELL[,CELL...]] [--small_target N] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --distance METRES[,METRES...] [--decimate CELL[,CELL...]] [--points N] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -39,7 +40,16 @@ to --small_target live surfels, where the mesh has far more holes per triangle):
 that are large enough, whole calls by device events and the four phases by the library's own (smx_recon_debug_fill_timings);
 every count of smx_fill_stats; the histogram of the listed loops' lengths; bytes by fill_traffic_bytes below against the HBM
 peak; the full triangulation re-measured beside it.  Writes profiles/fill_bench.{txt,json} unless --txt / --json say
-otherwise."""
+otherwise.
+
+--distance METRES[,METRES...] measures smx_recon_mesh_distance for every max_distance given: --points (default
+1 M) points of synth.room_surface_points (the C5 points: on the room's nominal walls with the relief, 30 mm BEHIND the surface
+the stream shows, whose raycast offsets the relief inward by 0.03 m -- so the distances measure that offset, a query load with
+a known answer, not a reconstruction error; run_tum.py --mesh_eval measures the error) against the same map's full mesh and, with --decimate, against each decimated mesh: medians of --reps calls with device
+arrays, whole calls by device events and the four phases by the library's own (smx_recon_debug_distance_timings); points/s;
+every count of smx_distance_stats and the summary line of meshing.distance_summary; bytes by distance_traffic_bytes below
+against the HBM peak, the query phase's share on its own; the full triangulation re-measured beside it.  Writes
+profiles/distance_bench.{txt,json} unless --txt / --json say otherwise."""
 import argparse
 import json
 import os
@@ -59,6 +69,8 @@ ap.add_argument("--components", action="store_true")
 ap.add_argument("--compare_json", default=None, help="with --components: the JSON of another build's run, printed beside this one")
 ap.add_argument("--fill", type=int, nargs="?", const=8, default=None, metavar="EDGES", help="measure smx_recon_fill_holes with this max_hole_edges")
 ap.add_argument("--small_target", type=int, default=50_000, help="with --fill: live surfels of the second, 160 x 120 map (0 = none)")
+ap.add_argument("--distance", default=None, metavar="METRES[,METRES...]", help="measure smx_recon_mesh_distance at these max_distance values")
+ap.add_argument("--points", type=int, default=1_000_000, help="with --distance: query points on the analytic room surface")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -501,6 +513,128 @@ def fill_main():
 UPDATE_PHASES = ("diff", "index_builds", "reverse_test", "subset_lists", "stars", "agree_merge")
 
 
+DIST_PHASES = ("mark", "index", "query", "stats")
+
+
+def distance_traffic_bytes(n, n_in, n_points, st):
+    """HBM bytes of one smx_recon_mesh_distance call, by phase, from its statistics: a lower bound.  Gathers are counted once per
+    distinct target, a sort pass as its keys and values read twice and written once, an atomic as a read and a write of its
+    entry; the query as every record and every occupied table entry read ONCE (lanes of one cell share them, neighbouring cells
+    mostly hit in cache) plus the points and the outputs; the wide list once per wavefront."""
+    E, Wd, P = st["n_entries"], st["n_wide"], n_points
+    corners = min(n, 3 * n_in)
+    mark = 2 * 12 * n_in + 2 * 32 * corners + 2 * 4 * n_in + 4 * Wd + 8 * (n_in // 256 + 1)
+    index = (12 * n_in + 16 * corners + 12 * E                     # entries: the input, S records, keys and values
+             + 8 * 36 * E                                          # eight sort passes
+             + 4 * E + 12 * E + 16 * corners + 48 * (E + Wd)       # records
+             + 16 * _table_size(E) + 8 * E + 32 * st["n_cells"])   # the table: reset, keys read, head and tail claims
+    query = (12 * P + 12 * P + 8 * 36 * P                          # the points' keys and their sort
+             + 4 * P + 12 * P + 16 * st["n_cells"] + 48 * E + 48 * Wd * (P // 64 + 1)
+             + 36 * st["n_matched"] + 28 * P)                      # the winner's corners; key, nearest, distance, closest
+    stats = 12 * P + 8 * P
+    return dict(zip(DIST_PHASES, (mark, index, query, stats)))
+
+
+def distance_main():
+    import ctypes as C
+    from surfelmeshing_amd import meshing, synth
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    maxes = [float(c) for c in args.distance.split(",")]
+    cells = [float(c) for c in args.decimate.split(",")] if args.decimate else []
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    pts = np.ascontiguousarray(synth.room_surface_points(args.points)[0], np.float32)
+    P = pts.shape[0]
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    dpts, dnear, ddist = api.CUDABuffer(1, 3 * P, np.float32), api.CUDABuffer(1, P, np.uint32), api.CUDABuffer(1, P, np.float32)
+    dpts.Upload(pts.reshape(1, -1))
+    say("# %d query points of synth.room_surface_points: the nominal walls, 30 mm behind the surface the stream shows" % P)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def full():
+        T, st = C.c_uint32(0), _lib.MeshStats()
+        _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                           C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+        return T.value
+
+    def distance(src, n_in, max_distance):
+        prm, st = api.distance_params(max_distance), _lib.DistanceStats()
+        _lib.check(L.smx_recon_mesh_distance(rec._h, None, C.byref(prm), C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in),
+                                             C.c_void_p(dpts.ToCUDA().address), C.c_uint32(P), C.c_void_p(dnear.ToCUDA().address),
+                                             C.c_void_p(ddist.ToCUDA().address), None, C.c_int32(1), C.byref(st)))
+        return api.distance_stats_dict(st)
+    t_full = []
+    for _ in range(args.reps + 1):
+        ms, T_in = timed(full)
+        t_full.append(ms)
+    full_ms = float(np.median(t_full[1:]))
+    say("full triangulation, re-measured here: %d triangles, one call %.2f ms" % (T_in, full_ms))
+    inputs = [("full mesh", dtri, T_in)]
+    for cell in cells:
+        T, st = C.c_uint32(0), _lib.DecimateStats()
+        buf = api.CUDABuffer(1, 3 * max(1, T_in), np.uint32) if len(inputs) > 1 else dout
+        _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                             C.c_void_p(buf.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(T), C.byref(st)))
+        inputs.append(("decimated at %g m" % cell, buf, T.value))
+    out_rows = []
+    for what, src, n_in in inputs:
+        for md in maxes:
+            t, phs, st, first = [], [], None, None
+            for _ in range(args.reps + 1):
+                ms, st = timed(lambda: distance(src, n_in, md))
+                t.append(ms)
+                phs.append(rec.debug_distance_timings())
+                head = dnear.Download()[0][:100000].tobytes() + ddist.Download()[0][:100000].tobytes()
+                first = head if first is None else first
+                assert head == first, "two calls gave different bytes"
+            med = float(np.median(t[1:]))                       # (the first call allocates the workspace)
+            ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in DIST_PHASES}
+            b = distance_traffic_bytes(n, n_in, P, st)
+            tot = sum(b.values())
+            st["max_distance"] = md
+            summary = meshing.distance_summary(ddist.Download()[0], st)
+            say("%s, max_distance %g m: %d triangles (%d not live, %d repeated, %d out of range), cell %.4f m, %d entries in %d cells, %d wide | "
+                "call %.2f ms (min %.2f, max %.2f) = %.2f x the full triangulation, %.2f M points/s | %s | model %.2f GB -> %.0f %% of the "
+                "%.1f TB/s HBM peak (%s) | %s" % (
+                    what, md, n_in, st["n_not_live"], st["n_repeated"], st["n_out_of_range"], st["cell_size_used"], st["n_entries"], st["n_cells"],
+                    st["n_wide"], med, min(t[1:]), max(t[1:]), med / full_ms, P / (med * 1e-3) / 1e6,
+                    " ".join("%s %.2f" % (k, ph[k]) for k in DIST_PHASES), tot / 1e9, 100.0 * tot / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12,
+                    " ".join("%s %.0f %%" % (k, 100.0 * b[k] / (max(ph[k], 1e-6) * 1e-3) / HBM_PEAK) for k in DIST_PHASES),
+                    meshing.format_distance_summary(summary)))
+            out_rows.append({"input": what, "max_distance": md, "triangles_in": n_in, "points": P, "reps": len(t) - 1, "call_ms": med,
+                             "call_ms_all": t[1:], "phases_ms": ph, "points_per_s": P / (med * 1e-3), "stats": st, "summary": summary,
+                             "traffic_model_bytes": b, "fraction_of_hbm_peak": tot / (med * 1e-3) / HBM_PEAK,
+                             "query_fraction_of_hbm_peak": b["query"] / (max(ph["query"], 1e-6) * 1e-3) / HBM_PEAK,
+                             "ratio_to_full_triangulation": med / full_ms})
+    res = {"metric": "mesh_distance_ms", "slots": n, "live": live, "triangles_in": T_in, "full_triangulation_ms": full_ms, "rows": out_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "distance_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "distance_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 def update_main():
     import ctypes as C
     _lib.require_gpu()
@@ -660,4 +794,4 @@ def main():
 
 
 if __name__ == "__main__":
-    fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -7,6 +7,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
+                              [--mesh_eval METRES]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -22,6 +23,10 @@ triangles and a bounding-box diagonal of at least that length, and of those only
 --mesh_fill_holes EDGES (with --mesh or --mesh_every; 0 = off) closes the holes of the final mesh that have at most that many
 edges (smx_recon_fill_holes), after cleaning and before --mesh_decimate; --mesh_fill_min_angle / --mesh_fill_max_angle are the
 limits of the triangle filter the new triangles have to pass (default 10 / 170 degrees).  The statistics line is printed.
+--mesh_eval METRES (with --mesh or --mesh_every) measures point-to-mesh distances up to METRES with smx_recon_mesh_distance and
+prints one summary line per measurement: with --synthetic the noise-free surface points of the integrated frames (every 8th
+pixel) against the final mesh -- with --track that is what the tracker's drift does to the surface --, with --mesh_decimate the
+fine mesh's vertices against the decimated one.  Without --synthetic and without --mesh_decimate the flag is refused.
 --render_source mesh (with --mesh or --mesh_every) makes --render_dir / --render_every / --render_overview draw the current
 mesh with smx_recon_render_mesh instead of splats: the kept array of --mesh_every as of its last update, otherwise a
 triangulation of the map as it stands, cleaned, filled and decimated first if those flags are given.
@@ -185,6 +190,10 @@ def parse_args(argv=None):
                     help="with --mesh_fill_holes: smallest interior angle a new triangle may have (default 10)")
     ap.add_argument("--mesh_fill_max_angle", type=float, default=None, metavar="DEG",
                     help="with --mesh_fill_holes: largest interior angle a new triangle may have (default 170)")
+    ap.add_argument("--mesh_eval", type=float, default=None, metavar="METRES",
+                    help="with --mesh or --mesh_every: measure point-to-mesh distances up to this far (smx_recon_mesh_distance): with "
+                         "--synthetic the noise-free surface points of the integrated frames (every 8th pixel) against the final "
+                         "mesh, with --mesh_decimate also the fine mesh's vertices against the decimated one")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -227,6 +236,14 @@ def parse_args(argv=None):
         args.mesh_fill = dict(max_hole_edges=args.mesh_fill_holes, min_triangle_angle_deg=lo, max_triangle_angle_deg=hi)
     elif args.mesh_fill_min_angle is not None or args.mesh_fill_max_angle is not None:
         ap.error("--mesh_fill_min_angle / --mesh_fill_max_angle need --mesh_fill_holes")
+    if args.mesh_eval is not None:
+        if not (args.mesh or args.mesh_every > 0):
+            ap.error("--mesh_eval needs --mesh or --mesh_every")
+        if not (args.synthetic or args.mesh_decimate is not None):
+            ap.error("--mesh_eval has nothing to measure against: it needs --synthetic (the ground-truth surface) or --mesh_decimate "
+                     "(the fine mesh's vertices)")
+        if not 1e-3 <= args.mesh_eval <= 16.0:
+            ap.error("--mesh_eval needs a distance within 0.001 .. 16 metres")
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
     return args
@@ -378,9 +395,22 @@ def main():
     if args.mesh_decimate is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
+        fine = triangles
         triangles, dst = meshing.decimate_map_mesh(rec, triangles, args.mesh_decimate)
         print("decimated at %g m in %.1f ms: %s" % (args.mesh_decimate, 1e3 * (time.time() - t1),
                                                     ", ".join("%s %d" % (k, dst[k]) for k in meshing.DECIMATE_STAT_NAMES)))
+    if args.mesh_eval is not None:
+        from surfelmeshing_amd import meshing
+        if args.mesh_decimate is not None:
+            summary = meshing.decimation_error(rec, fine, triangles, args.mesh_eval)[0]
+            print("decimation error within %g m, fine vertices to the coarse mesh: %s" % (args.mesh_eval, meshing.format_distance_summary(summary)))
+        if args.synthetic:
+            half_ = args.outlier_filtering_frame_count // 2
+            truth = np.concatenate([s.surface_points(f, 8) for f in range(args.start_frame + half_, n - half_)] or [np.zeros((0, 3), np.float32)])
+            _, distance, dstats = meshing.mesh_distance(rec, triangles, truth, args.mesh_eval)
+            print("surface error within %g m, ground truth of %d frames to the mesh (%s poses): %s" % (
+                args.mesh_eval, max(0, n - 2 * half_ - args.start_frame), "tracked" if args.track else "true",
+                meshing.format_distance_summary(meshing.distance_summary(distance, dstats))))
     if args.render_dir and args.render_overview and args.render_source == "mesh":      # (the final mesh, decimated if asked)
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png", triangles)
     if args.export_mesh:
