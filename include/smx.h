@@ -1194,6 +1194,93 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
 #define SMX_DIST_PHASES 4
 int smx_recon_debug_distance_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- rays against a triangle array: the first triangle hit, the ray parameter, the barycentrics ----
+ * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n) with n =
+ * surfels_size()), of `triangles` (uint32 [n_in][3], slot indices, in ANY order), of `rays` (float [n_rays][6]: the origin O,
+ * then the direction D) and of p.  Every quantity is an integer or a float32 expression evaluated as written, one rounding per
+ * operation, no contraction; division is correctly rounded; dot and cross as in smx_recon_mesh_distance above.
+ * 1. Triangles.  R and the counts n_not_live, n_repeated and n_out_of_range exactly as smx_recon_mesh_distance step 1; an
+ *    index >= n anywhere in `triangles`: SMX_ERR_INVALID_ARGUMENT, nothing is written.  Each triangle of R keeps i, its
+ *    position in the input, and its corners A, B, C in input order.
+ * 2. Rays.  D is not normalised: t is in units of |D|, so the segment from P to Q is O = P, D = Q - P, t_max = 1.  A ray is
+ *    BAD if a coordinate of O or D is not finite, if |O_k| > SMX_DIST_MAX_COORD, if |D_k| > SMX_RAY_MAX_DIR for some k, or if
+ *    max_k |D_k| < SMX_RAY_MIN_DIR.  A BAD ray is counted in n_bad_rays and its outputs are those of "none" below.
+ * 3. Candidate.  For the ray (O, D) and the triangle (A, B, C) of R:
+ *      e1 = B-A; e2 = C-A; p = cross(D, e2); det = dot(e1, p)
+ *      not a candidate unless det > 0 or det < 0        (a NaN or zero det never is)
+ *      cull == 1: only det > 0  (front: smx_recon_triangulate's winding seen from its normal side);  cull == 2: only det < 0
+ *      inv = 1.0f / det; s = O-A; u = dot(s, p) * inv; q = cross(s, e1); v = dot(D, q) * inv
+ *      w = u + v; t = dot(e2, q) * inv
+ *      candidate iff u >= 0 and v >= 0 and w <= 1 and t >= t_min and t <= t_max and, for each axis k,
+ *        H_k = O_k + t * D_k   (a product, then a sum)
+ *        min3(A_k, B_k, C_k) - SMX_RAY_BOX_SLACK <= H_k <= max3(A_k, B_k, C_k) + SMX_RAY_BOX_SLACK
+ *    with min3(a, b, c) = (m = a < b ? a : b; m < c ? m : c) and max3 alike.  The last condition is part of the definition on
+ *    purpose, like the clamp of v and w in smx_recon_mesh_distance: float32 Moeller-Trumbore on a sliver can place a "hit"
+ *    anywhere along the ray; such a hit is none, and that is what lets a grid find every candidate.
+ * 4. The answer for a ray: the candidate with the smallest key (float_bits(t + 0.0f) << 32) | i -- the nearest, then the
+ *    smallest input position.  hit = i, t = t + 0.0f, uv = (u, v).  With no candidate, or for a BAD ray: hit = 0xFFFFFFFF,
+ *    t = +infinity, uv = (NaN, NaN).  The answer is the minimum over ALL of R: it does not depend on cell_size, on the search
+ *    structure or on the schedule.  Two calls give the same bytes.
+ * 5. smx_raycast_stats: the counts of steps 1 and 2; n_hit = the rays with a candidate, n_front_hits = those whose winner has
+ *    det > 0; max_t_bits = the largest winning t as its bits (0 if none).  n_wide, n_entries, n_cells describe the search
+ *    structure: a uniform grid with c = max(cell_size, SMX_RAY_MIN_CELL); the cell of a coordinate x is (int32)floorf(x / c); a
+ *    triangle of R is entered in every cell from the cell of min3 - SMX_RAY_BOX_SLACK to the cell of max3 +
+ *    SMX_RAY_BOX_SLACK per axis (the expressions of step 3; the cell function is monotone, so the cell of H of any candidate is
+ *    one of them) unless that box has more than SMX_DIST_WIDE_CELLS cells, in which case it goes on the wide list every ray
+ *    tests in full.  With cell_size == 0 the library takes max(SMX_RAY_MIN_CELL, the mean over R of the largest of the three
+ *    extents of a triangle's box) for c; these three and cell_size_used are defined exactly only when cell_size > 0 is given.
+ *    n_layers, n_lookups, n_pair_tests say what the traversal did (layers of the dominant axis walked, cell look-ups, ray-
+ *    triangle tests); they are sums of per-wavefront counts, equal between two calls with the same inputs, and defined by the
+ *    implementation only.
+ * 6. Not done: not watertight -- a ray aimed exactly at a shared edge or vertex may slip between two triangles, or hit the
+ *    later one; no index is kept between calls; no ray packets; no BVH.
+ * Parameters: t_min and t_max finite with 0 <= t_min <= t_max <= SMX_RAY_MAX_T; cell_size 0 or finite and > 0; cull 0, 1 or 2;
+ * n_in <= 2^28 and n_rays <= 2^28.  Anything else: SMX_ERR_INVALID_ARGUMENT with nothing launched.  A cell_size so far below
+ * the triangles' size that the grid would hold more than 2^30 entries is refused after the mark phase, nothing written.
+ * Calling rules as smx_recon_mesh_distance: ordered after everything enqueued on the object, synchronous.  on_device says where
+ * triangles, rays, hit, t and uv live (host arrays are staged).  n_in == 0 is valid (every ray is "none"), and so is
+ * n_rays == 0.  uv may be NULL.  The outputs must not overlap the inputs (refused).  stats may be NULL.  Every allocation
+ * happens before the first write to an output.  Changes no map state, delta mark, statistic or stamp, nor the state
+ * smx_recon_triangulate_update keeps.  The workspace belongs to the object, grows on demand, is reused and is freed with the
+ * object. */
+#define SMX_RAY_MAX_DIR 1024.0f
+#define SMX_RAY_MIN_DIR 0.0009765625f      /* 2^-10 */
+#define SMX_RAY_MAX_T 1048576.0f           /* 2^20 */
+#define SMX_RAY_BOX_SLACK 0.000244140625f  /* 2^-12 m */
+#define SMX_RAY_MIN_CELL 0.001953125f      /* 2^-9 m */
+typedef struct {
+  float   t_min, t_max;      /* candidates have t_min <= t <= t_max */
+  float   cell_size;         /* 0: the library chooses */
+  int32_t cull;              /* 0: both sides, 1: front faces only (det > 0), 2: back faces only */
+} smx_raycast_params;
+typedef struct {
+  uint32_t n_in;                      /* triangles given */
+  uint32_t n_not_live;                /* of those, dropped because a corner is not live */
+  uint32_t n_repeated;                /* of the rest, with a repeated index */
+  uint32_t n_out_of_range;            /* of the rest, with a coordinate beyond SMX_DIST_MAX_COORD */
+  uint32_t n_rays;
+  uint32_t n_bad_rays;
+  uint32_t n_hit;
+  uint32_t n_front_hits;
+  uint32_t max_t_bits;
+  uint32_t n_wide, n_entries, n_cells;
+  float    cell_size_used;
+  uint32_t reserved;
+  uint64_t n_layers, n_lookups, n_pair_tests;
+} smx_raycast_stats;
+int smx_raycast_params_default(smx_raycast_params* out);   /* 0.0f, SMX_RAY_MAX_T, 0.0f, 0 */
+int smx_recon_raycast_mesh(smx_recon r, smx_stream s, const smx_raycast_params* p,
+                           const uint32_t* triangles, uint32_t n_in,
+                           const float* rays /* [n_rays][6] */, uint32_t n_rays,
+                           uint32_t* hit /* [n_rays] */, float* t /* [n_rays] */,
+                           float* uv /* [n_rays][2], may be NULL */,
+                           int32_t on_device, smx_raycast_stats* stats /* may be NULL */);
+/* Tools: milliseconds the last smx_recon_raycast_mesh call spent in its SMX_RAY_PHASES phases -- mark (classes, c, boxes, the
+ * wide list, the occupied box, scan), index (entries, sort, records, cell table), cast, stats -- by timed events on the call's
+ * stream; a phase a call did not reach reads 0.  capacity >= SMX_RAY_PHASES.  Zeros before the first call. */
+#define SMX_RAY_PHASES 4
+int smx_recon_debug_raycast_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the

@@ -664,6 +664,20 @@ class CUDASurfelReconstruction {
                                            n_points ? points.data() : nullptr, n_points, n_points ? nearest->data() : nullptr,
                                            n_points ? distance->data() : nullptr, closest && n_points ? closest->data() : nullptr, 0, stats));
   }
+  // Not in the reference: for every ray (origin, then direction: six floats) the first triangle of `triangles` it hits within
+  // [params.t_min, params.t_max] (smx_recon_raycast_mesh in smx.h).  *hit gets the triangle's position in the array or
+  // 0xFFFFFFFF, *t the ray parameter or +infinity, *uv (may be null) the barycentrics or NaNs; stats may be null.  Synchronous.
+  void RaycastMesh(cudaStream_t stream, const std::vector<u32>& triangles, const std::vector<float>& rays,
+                   const smx_raycast_params& params, std::vector<u32>* hit, std::vector<float>* t,
+                   std::vector<float>* uv = nullptr, smx_raycast_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles.size() / 3), n_rays = (u32)(rays.size() / 6);
+    hit->resize(n_rays);
+    t->resize(n_rays);
+    if (uv) uv->resize((size_t)2 * n_rays);
+    SMX_SHIM_CHECK(smx_recon_raycast_mesh(handle_, stream, &params, n_in ? triangles.data() : nullptr, n_in,
+                                          n_rays ? rays.data() : nullptr, n_rays, n_rays ? hit->data() : nullptr,
+                                          n_rays ? t->data() : nullptr, uv && n_rays ? uv->data() : nullptr, 0, stats));
+  }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.
   void CheckTrianglesForRemeshing(cudaStream_t stream, const u32* triangle_indices, u32 count,

@@ -235,6 +235,27 @@ class DistanceStats(C.Structure):
                 [(n, C.c_uint32) for n in ("n_wide", "n_entries", "n_cells")] + [("cell_size_used", C.c_float)])
 
 
+class RaycastParams(C.Structure):
+    """smx_raycast_params: the range of the ray parameter, the grid's cell (0: the library chooses) and the culling mode."""
+    _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("cell_size", C.c_float), ("cull", C.c_int32)]
+
+
+RAY_PHASES = 4              # SMX_RAY_PHASES
+RAY_MAX_DIR = 1024.0        # SMX_RAY_MAX_DIR
+RAY_MIN_DIR = 2.0 ** -10    # SMX_RAY_MIN_DIR
+RAY_MAX_T = 2.0 ** 20       # SMX_RAY_MAX_T
+RAY_BOX_SLACK = 2.0 ** -12  # SMX_RAY_BOX_SLACK
+RAY_MIN_CELL = 2.0 ** -9    # SMX_RAY_MIN_CELL
+
+
+class RaycastStats(C.Structure):
+    """smx_raycast_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_rays", "n_bad_rays", "n_hit",
+                                           "n_front_hits", "max_t_bits", "n_wide", "n_entries", "n_cells")] +
+                [("cell_size_used", C.c_float), ("reserved", C.c_uint32)] +
+                [(n, C.c_uint64) for n in ("n_layers", "n_lookups", "n_pair_tests")])
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -314,6 +335,7 @@ EXPORTS = [
     "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
     "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
     "smx_distance_params_default", "smx_recon_mesh_distance", "smx_recon_debug_distance_timings",
+    "smx_raycast_params_default", "smx_recon_raycast_mesh", "smx_recon_debug_raycast_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

@@ -26,6 +26,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
                    FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
                    DIST_BINS, DIST_PHASES, DistanceParams, DistanceStats,
+                   RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -80,6 +81,26 @@ def distance_stats_dict(st):
     """smx_distance_stats as a dict: integers, histogram a list of DIST_BINS integers, cell_size_used a float."""
     d = {n: int(getattr(st, n)) for n, _ in DistanceStats._fields_ if n not in ("histogram", "cell_size_used")}
     d["histogram"] = [int(v) for v in st.histogram]
+    d["cell_size_used"] = float(st.cell_size_used)
+    return d
+
+
+def raycast_params(t_min=0.0, t_max=RAY_MAX_T, cell_size=0.0, cull=0):
+    """The parameters of RaycastMesh as smx_raycast_params; ValueError on what the library would refuse, before anything is
+    called."""
+    t0, t1, c = float(np.float32(t_min)), float(np.float32(t_max)), float(np.float32(cell_size))
+    if not (t0 - t0 == 0.0 and t1 - t1 == 0.0 and 0.0 <= t0 <= t1 <= RAY_MAX_T):
+        raise ValueError("t_min and t_max must be finite with 0 <= t_min <= t_max <= 2^20")
+    if not (c - c == 0.0 and c >= 0.0):
+        raise ValueError("cell_size must be 0 (the library chooses) or finite and > 0")
+    if cull not in (0, 1, 2) or isinstance(cull, bool):
+        raise ValueError("cull must be 0 (both sides), 1 (front faces only) or 2 (back faces only)")
+    return RaycastParams(t0, t1, c, int(cull))
+
+
+def raycast_stats_dict(st):
+    """smx_raycast_stats as a dict: integers, cell_size_used a float."""
+    d = {n: int(getattr(st, n)) for n, _ in RaycastStats._fields_ if n not in ("reserved", "cell_size_used")}
     d["cell_size_used"] = float(st.cell_size_used)
     return d
 
@@ -953,6 +974,55 @@ class CUDASurfelReconstruction:
         out = (C.c_float * DIST_PHASES)()
         _lib.check(_lib.load().smx_recon_debug_distance_timings(self._h, out, C.c_int32(DIST_PHASES)))
         return dict(zip(("mark", "index", "query", "stats"), [float(v) for v in out]))
+
+    def RaycastMesh(self, stream, triangles, rays, t_min=0.0, t_max=RAY_MAX_T, cell_size=0.0, cull=0, return_uv=False):
+        """Not in the reference: for every ray of `rays` ([P,6] float32: origin, then direction, not normalised) the first
+        triangle of `triangles` ([T,3] slot indices in any order, e.g. Triangulate's, DecimateMesh's, MeshComponents' or
+        FillHoles') over the map's smooth positions it hits with t_min <= t <= t_max (smx_recon_raycast_mesh).  The answer is
+        exactly the minimum over all triangles (ties go to the earlier triangle) whatever cell_size the search grid uses (0:
+        the library chooses); cull 1 keeps front faces only, 2 back faces only.  Synchronous.  Both arrays are numpy arrays,
+        or both are contiguous device tensors (uint32 / int32 and float32); the results then are device tensors too (hit a
+        torch.uint32 tensor).  Returns (hit [P] uint32 with 0xFFFFFFFF for "none", t [P] float32 with +inf for "none", then
+        with return_uv uv [P,2] float32, then the dict of smx_raycast_stats)."""
+        p = raycast_params(t_min, t_max, cell_size, cull)
+        L = _lib.load()
+        st = RaycastStats()
+        dev = _device_address(triangles) is not None or _device_address(rays) is not None
+        if dev:
+            import torch
+            if _device_address(triangles) is None or _device_address(rays) is None:
+                raise ValueError("triangles and rays must both be device tensors, or both host arrays")
+            if not (triangles.is_contiguous() and rays.is_contiguous() and triangles.element_size() == 4 and
+                    rays.dtype == torch.float32 and triangles.numel() % 3 == 0 and rays.numel() % 6 == 0):
+                raise ValueError("device tensors must be contiguous: [T,3] 32-bit integers and [P,6] float32")
+            n_in, n_rays = triangles.numel() // 3, rays.numel() // 6
+            hit = torch.empty(n_rays, dtype=torch.uint32, device=rays.device)
+            t = torch.empty(n_rays, dtype=torch.float32, device=rays.device)
+            uv = torch.empty((n_rays, 2), dtype=torch.float32, device=rays.device) if return_uv else None
+            tin, rin = triangles.data_ptr() if n_in else None, rays.data_ptr() if n_rays else None
+            outs = [a.data_ptr() if a is not None and n_rays else None for a in (hit, t, uv)]
+            torch.cuda.current_stream(rays.device).synchronize()      # (the tensors' producers; the call runs on `stream`)
+        else:
+            tri = np.ascontiguousarray(triangles, np.uint32)
+            ry = np.ascontiguousarray(rays, np.float32)
+            if tri.size % 3 or ry.size % 6:
+                raise ValueError("triangles must hold three values per row and rays six")
+            n_in, n_rays = tri.size // 3, ry.size // 6
+            hit, t = np.zeros(n_rays, np.uint32), np.zeros(n_rays, np.float32)
+            uv = np.zeros((n_rays, 2), np.float32) if return_uv else None
+            tin, rin = tri.ctypes.data if n_in else None, ry.ctypes.data if n_rays else None
+            outs = [a.ctypes.data if a is not None and n_rays else None for a in (hit, t, uv)]
+        _lib.check(L.smx_recon_raycast_mesh(self._h, _sv(stream), C.byref(p), C.c_void_p(tin), C.c_uint32(n_in), C.c_void_p(rin),
+                                            C.c_uint32(n_rays), C.c_void_p(outs[0]), C.c_void_p(outs[1]), C.c_void_p(outs[2]),
+                                            C.c_int32(1 if dev else 0), C.byref(st)))
+        stats = raycast_stats_dict(st)
+        return (hit, t, uv, stats) if return_uv else (hit, t, stats)
+
+    def debug_raycast_timings(self):
+        """Milliseconds of the last RaycastMesh call, by phase."""
+        out = (C.c_float * RAY_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_raycast_timings(self._h, out, C.c_int32(RAY_PHASES)))
+        return dict(zip(("mark", "index", "cast", "stats"), [float(v) for v in out]))
 
     def UpdateVisualizationBuffers(self, stream, frame_index, latest_triangulated_frame_index, latest_mesh_surfel_count,
                                    surfel_integration_active_window_size, visualize_last_update_timestamp=False,

@@ -29,6 +29,13 @@ max_distance, and what a decimation moved:
     print(meshing.distance_summary(distance, stats))
     print(meshing.decimation_error(rec, triangles, coarse, max_distance=0.1)[0])
 
+What a ray hits first on any of these arrays (smx_recon_raycast_mesh) -- any set of rays, a pinhole camera's, or
+the segments from the vertices to a camera (visibility):
+
+    hit, t, stats = meshing.cast_rays(rec, triangles, origins, directions)
+    o, d = meshing.camera_rays(fx, fy, cx, cy, width, height, global_T_camera)
+    slots, visible = meshing.vertex_visibility(rec, triangles, camera_centre)
+
 The order of the chain is clean -> fill -> decimate: cleaning first, so that no hole of a piece that goes is filled, and
 decimation last, because it does not keep the mesh manifold and puts the whole array back into (p, a, b) order.
 """
@@ -262,3 +269,44 @@ def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None
     used = np.unique(np.ascontiguousarray(fine, np.uint32))
     nearest, distance, stats = mesh_distance(rec, coarse, map_positions(rec, used, stream), max_distance, cell_size, stream=stream)
     return distance_summary(distance, stats), nearest, distance, stats
+
+
+def cast_rays(rec, triangles, origins, directions, t_min=0.0, t_max=2.0 ** 20, cull=0, cell_size=0.0, return_uv=False, stream=None):
+    """For every ray (origins [P,3], directions [P,3], not normalised: t is in units of |direction|) the first triangle of
+    `triangles` it hits with t_min <= t <= t_max, on the device: (hit, t[, uv], stats) as CUDASurfelReconstruction.RaycastMesh
+    returns them.  ValueError on parameters the library would refuse."""
+    import numpy as np
+    from .api import raycast_params
+    raycast_params(t_min, t_max, cell_size, cull)
+    o, d = np.asarray(origins, np.float32), np.asarray(directions, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be [P, 3]")
+    return rec.RaycastMesh(stream, triangles, np.ascontiguousarray(np.concatenate([o, d], axis=1)), t_min, t_max, cell_size, cull, return_uv)
+
+
+def camera_rays(fx, fy, cx, cy, width, height, global_T_camera):
+    """The rays of a pinhole camera in the pixel-corner convention of smx_recon_render, row by row: (origins, directions), both
+    [height * width, 3] float32.  The direction of pixel (x, y) is R ((x + 1/2 - cx) / fx, (y + 1/2 - cy) / fy, 1) with
+    global_T_camera = (R | centre), so t is the camera depth of the hit."""
+    import numpy as np
+    T = np.asarray(global_T_camera, np.float64).reshape(3, 4)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or not (fx > 0 and fy > 0):
+        raise ValueError("width, height, fx and fy must be positive")
+    x, y = np.meshgrid(np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64))
+    local = np.stack([(x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, np.ones_like(x)], axis=-1).reshape(-1, 3)
+    d = (local @ T[:, :3].T).astype(np.float32)
+    o = np.broadcast_to(T[:, 3].astype(np.float32), d.shape).copy()
+    return o, d
+
+
+def vertex_visibility(rec, triangles, camera_centre, t_min=2.0 ** -10, cell_size=0.0, stream=None):
+    """Which of the vertices `triangles` uses are seen from camera_centre: the segment from each used vertex (ascending by
+    slot) to the camera is cast with t in [t_min, 1], and a vertex is visible iff its segment hits nothing.  t_min keeps the
+    triangles around the vertex itself out.  Returns (slots [m] uint32, visible [m] bool, stats)."""
+    import numpy as np
+    used = np.unique(np.ascontiguousarray(triangles, np.uint32))
+    c = np.asarray(camera_centre, np.float32).reshape(3)
+    v = map_positions(rec, used, stream)
+    hit, t, stats = cast_rays(rec, triangles, v, c[None, :] - v, t_min, 1.0, 0, cell_size, stream=stream)
+    return used, hit == np.uint32(0xFFFFFFFF), stats

@@ -7,6 +7,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --components [--decimate CELL[,CELL...]] [--compare_json OTHER.json] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --fill [EDGES] [--decimate CELL[,CELL...]] [--small_target N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --distance METRES[,METRES...] [--decimate CELL[,CELL...]] [--points N] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -49,7 +50,15 @@ a known answer, not a reconstruction error; run_tum.py --mesh_eval measures the 
 arrays, whole calls by device events and the four phases by the library's own (smx_recon_debug_distance_timings); points/s;
 every count of smx_distance_stats and the summary line of meshing.distance_summary; bytes by distance_traffic_bytes below
 against the HBM peak, the query phase's share on its own; the full triangulation re-measured beside it.  Writes
-profiles/distance_bench.{txt,json} unless --txt / --json say otherwise."""
+profiles/distance_bench.{txt,json} unless --txt / --json say otherwise.
+
+--raycast WxH measures smx_recon_raycast_mesh: the W x H camera rays (meshing.camera_rays) of the bench pose --
+the pose of the first frame after the growth, render_bench.py's capture pose -- against the same map's full mesh and against the
+mesh decimated at 0.05 m: medians of --reps calls with device arrays, whole calls by device events and the four phases by the
+library's own (smx_recon_debug_raycast_timings); rays/s; every count of smx_raycast_stats; layers, look-ups and pair tests per
+ray; the index rebuild's share (mark + index) of the call; and smx_recon_render_mesh of the same pose, size and mesh measured
+beside it, with the share of pixels whose index equals the rasteriser's.  Writes profiles/raycast_bench.{txt,json} unless --txt
+/ --json say otherwise."""
 import argparse
 import json
 import os
@@ -71,6 +80,7 @@ ap.add_argument("--fill", type=int, nargs="?", const=8, default=None, metavar="E
 ap.add_argument("--small_target", type=int, default=50_000, help="with --fill: live surfels of the second, 160 x 120 map (0 = none)")
 ap.add_argument("--distance", default=None, metavar="METRES[,METRES...]", help="measure smx_recon_mesh_distance at these max_distance values")
 ap.add_argument("--points", type=int, default=1_000_000, help="with --distance: query points on the analytic room surface")
+ap.add_argument("--raycast", default=None, metavar="WxH", help="measure smx_recon_raycast_mesh with the camera rays of the bench pose")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -748,6 +758,104 @@ def update_main():
     sys.exit(0 if ok else 1)
 
 
+RAY_PHASES = ("mark", "index", "cast", "stats")
+
+
+def raycast_main():
+    import ctypes as C
+    from surfelmeshing_amd import meshing
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    W, H = (int(v) for v in args.raycast.lower().split("x"))
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    g_end, _ = wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    pose = wl.plan(g_end + 10, 4)[3]
+    fx, fy, cx, cy = (wl.fx * W / 640.0, wl.fy * H / 480.0, wl.cx * W / 640.0, wl.cy * H / 480.0)
+    o, d = meshing.camera_rays(fx, fy, cx, cy, W, H, pose)
+    P = o.shape[0]
+    drays, dhit, dt = api.CUDABuffer(1, 6 * P, np.float32), api.CUDABuffer(1, P, np.uint32), api.CUDABuffer(1, P, np.float32)
+    drays.Upload(np.ascontiguousarray(np.concatenate([o, d], axis=1)).reshape(1, -1))
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    bufs = {"depth": api.CUDABuffer(H, W, np.float32), "index": api.CUDABuffer(H, W, np.uint32)}
+    say("# %d x %d camera rays of the bench pose" % (W, H))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    T, st = C.c_uint32(0), _lib.MeshStats()
+    _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                       C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+    T_in = T.value
+    T, dst = C.c_uint32(0), _lib.DecimateStats()
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(0.05), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(T), C.byref(dst)))
+
+    def cast(src, n_in):
+        prm, st = api.raycast_params(), _lib.RaycastStats()
+        _lib.check(L.smx_recon_raycast_mesh(rec._h, None, C.byref(prm), C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in),
+                                            C.c_void_p(drays.ToCUDA().address), C.c_uint32(P), C.c_void_p(dhit.ToCUDA().address),
+                                            C.c_void_p(dt.ToCUDA().address), None, C.c_int32(1), C.byref(st)))
+        return api.raycast_stats_dict(st)
+    out_rows = []
+    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at 0.05 m", dout, T.value)):
+        t, phs, st, first = [], [], None, None
+        for _ in range(args.reps + 1):
+            ms, st2 = timed(lambda: cast(src, n_in))
+            t.append(ms)
+            phs.append(rec.debug_raycast_timings())
+            head = dhit.Download()[0].tobytes() + dt.Download()[0].tobytes()
+            first, st = (head, st2) if first is None else (first, st)
+            assert head == first and st2 == st, "two calls gave different bytes"
+        med = float(np.median(t[1:]))                       # (the first call allocates the workspace)
+        ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in RAY_PHASES}
+        prm = api.make_mesh_render_params(W, H, fx, fy, cx, cy, pose)
+        where = (src.ToCUDA().address, n_in)
+        r_ms = []
+        for _ in range(args.reps + 1):
+            r_ms.append(timed(lambda: rec.RenderMesh(None, prm, where, **bufs))[0])
+        raster = float(np.median(r_ms[1:]))
+        same = float((bufs["index"].Download().reshape(-1) == dhit.Download()[0]).mean())
+        rays_ok = max(1, P - st["n_bad_rays"])
+        say("%s: %d triangles (%d not live, %d repeated, %d out of range), cell %.4f m, %d entries in %d cells, %d wide | call %.2f ms "
+            "(min %.2f, max %.2f), %.2f M rays/s | %s | index rebuild (mark + index) %.0f %% of the call | %d of %d rays hit (%d front) | per "
+            "ray: %.1f layers, %.1f look-ups, %.1f pair tests | smx_recon_render_mesh of the same pose %.2f ms; %.2f %% of the pixels "
+            "have the same index" % (
+                what, n_in, st["n_not_live"], st["n_repeated"], st["n_out_of_range"], st["cell_size_used"], st["n_entries"], st["n_cells"],
+                st["n_wide"], med, min(t[1:]), max(t[1:]), P / (med * 1e-3) / 1e6, " ".join("%s %.2f" % (k, ph[k]) for k in RAY_PHASES),
+                100.0 * (ph["mark"] + ph["index"]) / max(sum(ph.values()), 1e-9), st["n_hit"], P, st["n_front_hits"],
+                st["n_layers"] / rays_ok, st["n_lookups"] / rays_ok, st["n_pair_tests"] / rays_ok, raster, 100.0 * same))
+        out_rows.append({"input": what, "triangles_in": n_in, "rays": P, "width": W, "height": H, "reps": len(t) - 1, "call_ms": med,
+                         "call_ms_all": t[1:], "phases_ms": ph, "rays_per_s": P / (med * 1e-3), "stats": st,
+                         "index_rebuild_share": (ph["mark"] + ph["index"]) / max(sum(ph.values()), 1e-9),
+                         "layers_per_ray": st["n_layers"] / rays_ok, "lookups_per_ray": st["n_lookups"] / rays_ok,
+                         "pair_tests_per_ray": st["n_pair_tests"] / rays_ok, "render_mesh_ms": raster, "render_mesh_ms_all": r_ms[1:],
+                         "same_index_share": same})
+    res = {"metric": "mesh_raycast_ms", "slots": n, "live": live, "triangles_in": T_in, "rows": out_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "raycast_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "raycast_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 def main():
     _lib.require_gpu()
     wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
@@ -794,4 +902,4 @@ def main():
 
 
 if __name__ == "__main__":
-    distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    raycast_main() if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -7,7 +7,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
-                              [--mesh_eval METRES]
+                              [--mesh_eval METRES] [--mesh_eval_rays]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -194,6 +194,10 @@ def parse_args(argv=None):
                     help="with --mesh or --mesh_every: measure point-to-mesh distances up to this far (smx_recon_mesh_distance): with "
                          "--synthetic the noise-free surface points of the integrated frames (every 8th pixel) against the final "
                          "mesh, with --mesh_decimate also the fine mesh's vertices against the decimated one")
+    ap.add_argument("--mesh_eval_rays", action="store_true",
+                    help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
+                         "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
+                         "mean and rms of |hit range - true range|: accuracy and completeness along the sensor's own rays")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -244,9 +248,22 @@ def parse_args(argv=None):
                      "(the fine mesh's vertices)")
         if not 1e-3 <= args.mesh_eval <= 16.0:
             ap.error("--mesh_eval needs a distance within 0.001 .. 16 metres")
+    if args.mesh_eval_rays and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
+        ap.error("--mesh_eval_rays needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
     return args
+
+
+def format_ray_eval(hit, t, d, frame):
+    """The line of --mesh_eval_rays: rays to the true surface points (direction d = point - camera, so t = 1 at the truth)."""
+    has = np.asarray(hit) != np.uint32(0xFFFFFFFF)
+    rng = np.linalg.norm(np.asarray(d, np.float64), axis=1)
+    err = np.abs(np.asarray(t, np.float64)[has] * rng[has] - rng[has])
+    if not has.size or not has.any():
+        return "surface error along the rays of frame %d: 0 of %d rays hit the mesh" % (frame, has.size)
+    return "surface error along the rays of frame %d: %d of %d rays hit the mesh (%.1f %%): mean %.2f mm, rms %.2f mm" % (
+        frame, int(has.sum()), has.size, 100.0 * has.mean(), 1e3 * err.mean(), 1e3 * np.sqrt((err * err).mean()))
 
 
 def main():
@@ -411,6 +428,15 @@ def main():
             print("surface error within %g m, ground truth of %d frames to the mesh (%s poses): %s" % (
                 args.mesh_eval, max(0, n - 2 * half_ - args.start_frame), "tracked" if args.track else "true",
                 meshing.format_distance_summary(meshing.distance_summary(distance, dstats))))
+    if args.mesh_eval_rays:
+        from surfelmeshing_amd import meshing
+        half_ = args.outlier_filtering_frame_count // 2
+        last = n - half_ - 1                                             # (the last frame the loop above integrated, if any)
+        truth = s.surface_points(last, 8) if last >= args.start_frame + half_ else np.zeros((0, 3), np.float32)
+        centre = s.pose64(max(last, 0))[1].astype(np.float32)
+        d = truth - centre[None, :]
+        hit, t, rstats = meshing.cast_rays(rec, triangles, np.broadcast_to(centre, d.shape), d, 0.0, 2.0)
+        print(format_ray_eval(hit, t, d, last))
     if args.render_dir and args.render_overview and args.render_source == "mesh":      # (the final mesh, decimated if asked)
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png", triangles)
     if args.export_mesh:
