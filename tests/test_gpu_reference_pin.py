@@ -99,6 +99,76 @@ def test_integrate_matches_the_reference_kernels_at_640x480(ref):
     _integrate_pin(ref, {}, 640, 480, list(range(4, 12)), 700000)
 
 
+def _pin_one_call(rr, recon, images, g, pose, params, depth_scaling, max_stray_pixels, surfels_per_stray_pixel=8):
+    """One Integrate on both sides from the same state: `recon` (the oracle's map, advanced by the call) and the
+    reference's kernels in `rr`, which first receives that state.  images = (depth, normals, radius, color); the oracle
+    blends `depth` in place.  Returns the race outcomes applied, the replacements and the stray blended-depth pixels."""
+    depth, normals, radius, color = images
+    n0 = recon.surfels_size
+    # same state, same preprocessed frame on both sides
+    rr.upload_surfels(recon.surfels()[:, :n0].copy(), recon.merge_count)
+    depth_r = depth.copy()
+    rr.integrate(g, depth_scaling, depth_r, normals, radius, color, pose, params)
+    sr = rr.scratch()
+    sup_r, conf_r = np.ascontiguousarray(sr["supporting"]), np.ascontiguousarray(sr["conflicting"])
+    orc.set_race_overrides(sup_r, conf_r)
+    try:
+        recon.integrate(g, depth_scaling, depth, normals, radius, color, pose, params)
+        ovr = orc.race_override_stats()
+    finally:
+        orc.set_race_overrides(None, None)
+    # every race outcome of the reference run is one the oracle considers legal
+    assert ovr["rejected_supporting"] == 0 and ovr["rejected_conflicting"] == 0, (g, ovr)
+    cr, st = rr.counts(), recon.stats()
+    n = recon.surfels_size
+    assert (n, recon.merge_count, st["n_new"]) == (cr["surfels_size"], cr["merge_count"], cr["n_new"]), g
+    so = recon.scratch()
+    assert np.array_equal(so["supporting"], sr["supporting"]) and np.array_equal(so["conflicting"], sr["conflicting"])
+    assert np.array_equal(so["support_counts"], sr["support_counts"])
+    assert np.array_equal(so["first_depth"].view(np.uint32), sr["first_depth"].view(np.uint32))
+    # blended depth: the reference's float atomicAdd depth sums depend on scheduling -> a stray LSB
+    dd = depth.astype(np.int32) - depth_r.astype(np.int32)
+    stray = int(np.count_nonzero(dd))
+    print("pin call %d: %d stray blended-depth pixels, %d overrides" % (g, stray, ovr["applied_supporting"] + ovr["applied_conflicting"]))
+    assert np.abs(dd).max() <= 1 and stray <= max_stray_pixels, (g, stray)
+    So, Sr = recon.surfels()[:, :n], rr.surfels(n)
+    for row in INT_ROWS:
+        assert np.array_equal(So[row].view(np.uint32), Sr[row].view(np.uint32)), (g, row)
+    for row in FLOAT_ROWS:
+        a, b = So[row], Sr[row]
+        neq = a.view(np.uint32) != b.view(np.uint32)
+        if row in SMOOTH_ROWS:
+            # regulariser: float atomicAdd order in the reference, 2^-22 m fixed point in the oracle
+            # (a few ulp at metres; surfels fed by a stray blended depth follow it)
+            off = np.abs(a - b) > 5e-6
+            if off.any():
+                print("pin call %d row %d: %d beyond 5e-6 m, max %g m" % (g, row, off.sum(), np.abs(a - b).max()))
+            assert off.sum() <= surfels_per_stray_pixel * stray and np.abs(a - b).max() <= 1.01 / depth_scaling, \
+                (g, row, off.sum(), np.abs(a - b).max())
+        else:
+            # (the few surfels that integrated one of the stray blended depths: several surfels share a pixel)
+            if neq.any():
+                print("pin call %d row %d: %d unequal" % (g, row, neq.sum()))
+            assert neq.sum() <= surfels_per_stray_pixel * stray, (g, row, neq.sum())
+            if neq.any():   # one depth unit is 1 / depth_scaling = 0.2 mm
+                assert np.abs(a - b)[neq].max() <= 1.01 / depth_scaling, (g, row, np.abs(a - b)[neq].max())
+    return {"applied": ovr["applied_supporting"] + ovr["applied_conflicting"], "n_replaced": st["n_replaced"], "stray": stray}
+
+
+def _pin_regularize(rr, recon, frame, weight, radius_factor, window):
+    """A standalone Regularize (cc:322-337) on both sides from the same state."""
+    n = recon.surfels_size
+    rr.upload_surfels(recon.surfels()[:, :n].copy(), recon.merge_count)
+    recon.regularize(frame, weight, radius_factor, window)
+    rr.regularize(frame, weight, radius_factor, window)
+    So, Sr = recon.surfels()[:, :n], rr.surfels(n)
+    for row in INT_ROWS + [r for r in FLOAT_ROWS if r not in SMOOTH_ROWS]:
+        assert np.array_equal(So[row].view(np.uint32), Sr[row].view(np.uint32)), row
+    for row in SMOOTH_ROWS:
+        assert np.abs(So[row] - Sr[row]).max() <= 5e-6
+    return So
+
+
 def _integrate_pin(ref, kw, w, h, frames, cap):
     scale = (w * h) // (160 * 120)                # pixel count relative to the small case: bounds on counts scale with it
     s = small_stream(w, h, obstacle_until=10)     # vanishing obstacle: conflicts, replacements, merges
@@ -112,61 +182,12 @@ def _integrate_pin(ref, kw, w, h, frames, cap):
     applied = merges = replaced = stray_depth = 0
     for g in frames:
         po.preprocess(g, s.outlier_frames(g), s.others_TR_reference(g))
-        n0 = po.recon.surfels_size
-        # same state, same preprocessed frame on both sides
-        rr.upload_surfels(po.recon.surfels()[:, :n0].copy(), po.recon.merge_count)
-        depth_r = po.depth_final.copy()
-        rr.integrate(g, pre.depth_scaling, depth_r, po.normals, po.radius, po.color[g], s.pose(g), params)
-        sr = rr.scratch()
-        sup_r, conf_r = np.ascontiguousarray(sr["supporting"]), np.ascontiguousarray(sr["conflicting"])
-        orc.set_race_overrides(sup_r, conf_r)
-        try:
-            po.integrate(g, s.pose(g))
-            ovr = orc.race_override_stats()
-        finally:
-            orc.set_race_overrides(None, None)
-        # every race outcome of the reference run is one the oracle considers legal
-        assert ovr["rejected_supporting"] == 0 and ovr["rejected_conflicting"] == 0, (g, ovr)
-        applied += ovr["applied_supporting"] + ovr["applied_conflicting"]
-        cr, st = rr.counts(), po.recon.stats()
-        n = po.recon.surfels_size
-        assert (n, po.recon.merge_count, st["n_new"]) == (cr["surfels_size"], cr["merge_count"], cr["n_new"]), g
-        merges, replaced = po.recon.merge_count, replaced + st["n_replaced"]
-        so = po.recon.scratch()
-        assert np.array_equal(so["supporting"], sr["supporting"]) and np.array_equal(so["conflicting"], sr["conflicting"])
-        assert np.array_equal(so["support_counts"], sr["support_counts"])
-        assert np.array_equal(so["first_depth"].view(np.uint32), sr["first_depth"].view(np.uint32))
-        # blended depth: the reference's float atomicAdd depth sums depend on scheduling -> a stray LSB
-        dd = po.depth_final.astype(np.int32) - depth_r.astype(np.int32)
-        assert np.abs(dd).max() <= 1 and np.count_nonzero(dd) <= 6 * scale, (g, np.count_nonzero(dd))
-        stray_depth += np.count_nonzero(dd)
-        So, Sr = po.recon.surfels()[:, :n], rr.surfels(n)
-        for row in INT_ROWS:
-            assert np.array_equal(So[row].view(np.uint32), Sr[row].view(np.uint32)), (g, row)
-        for row in FLOAT_ROWS:
-            a, b = So[row], Sr[row]
-            neq = a.view(np.uint32) != b.view(np.uint32)
-            if row in SMOOTH_ROWS:
-                # regulariser: float atomicAdd order in the reference, 2^-22 m fixed point in the oracle
-                # (a few ulp at metres; surfels fed by a stray blended depth follow it)
-                off = np.abs(a - b) > 5e-6
-                assert off.sum() <= 8 * np.count_nonzero(dd) and np.abs(a - b).max() <= 1.01 / pre.depth_scaling, \
-                    (g, row, off.sum(), np.abs(a - b).max())
-            else:
-                # (the few surfels that integrated one of the stray blended depths: several surfels share a pixel)
-                assert neq.sum() <= 8 * np.count_nonzero(dd), (g, row, neq.sum())
-                if neq.any():   # one depth unit is 1 / depth_scaling = 0.2 mm
-                    assert np.abs(a - b)[neq].max() <= 1.01 / pre.depth_scaling, (g, row, np.abs(a - b)[neq].max())
+        got = _pin_one_call(rr, po.recon, (po.depth_final, po.normals, po.radius, po.color[g]), g, s.pose(g), params,
+                            pre.depth_scaling, max_stray_pixels=6 * scale)
+        applied += got["applied"]
+        merges, replaced, stray_depth = po.recon.merge_count, replaced + got["n_replaced"], stray_depth + got["stray"]
     # the extra regulariser iteration (Regularize, cc:322-337) and ExportVertices on the final common state
-    n = po.recon.surfels_size
-    rr.upload_surfels(po.recon.surfels()[:, :n].copy(), po.recon.merge_count)
-    po.recon.regularize(frames[-1], 6.0, 1.8, 12)
-    rr.regularize(frames[-1], 6.0, 1.8, 12)
-    So, Sr = po.recon.surfels()[:, :n], rr.surfels(n)
-    for row in INT_ROWS + [r for r in FLOAT_ROWS if r not in SMOOTH_ROWS]:
-        assert np.array_equal(So[row].view(np.uint32), Sr[row].view(np.uint32)), row
-    for row in SMOOTH_ROWS:
-        assert np.abs(So[row] - Sr[row]).max() <= 5e-6
+    So = _pin_regularize(rr, po.recon, frames[-1], 6.0, 1.8, 12)
     rr.upload_surfels(So.copy(), po.recon.merge_count)
     pos_o, col_o = po.recon.export_vertices()
     pos_r, col_r = rr.export_vertices()
@@ -175,6 +196,36 @@ def _integrate_pin(ref, kw, w, h, frames, cap):
     assert po.recon.surfels_size > 12000 * scale * len(frames) // 20 and applied > 1000
     if not kw and len(frames) >= 20:
         assert merges > 50 and replaced > 50 and stray_depth <= 25 * scale, (merges, replaced, stray_depth)
+
+
+def test_integrate_matches_the_reference_kernels_on_decision_maps(ref):
+    """The crafted map of tests/decision_maps.py (both sides of the twelve decisions no stream reaches, see
+    tests/test_decision_maps.py) on the reference's own kernels: every Integrate of the scenario and its standalone
+    Regularize, each from the oracle's state, with the per-call assertions of the stream legs, count caps included
+    (each call prints its stray blended-depth pixels and the race outcomes it took over from the reference's run)."""
+    import decision_maps as dm
+    sc = dm.build()
+    fx, fy, cx, cy = sc.camera
+    recon = orc.Recon(sc.capacity, dm.W, dm.H, fx, fy, cx, cy)
+    recon.surfels()[:, :sc.count] = sc.rows
+    recon.set_counts(sc.count, sc.merge_count)
+    rr = ref.Recon(sc.capacity, dm.W, dm.H, fx, fy, cx, cy)
+    applied = 0
+    for c in sc.calls:
+        if c.kind == "regularize":
+            _pin_regularize(rr, recon, c.frame, c.weight, c.radius_factor, c.window)
+            continue
+        got = _pin_one_call(rr, recon, (c.depth.copy(), c.normals, c.radius, c.color), c.frame, c.pose, c.params,
+                            c.depth_scaling, max_stray_pixels=6)
+        applied += got["applied"]
+    n = recon.surfels_size
+    rr.upload_surfels(recon.surfels()[:, :n].copy(), recon.merge_count)
+    pos_o, col_o = recon.export_vertices()
+    pos_r, col_r = rr.export_vertices()
+    assert np.array_equal(pos_o.view(np.uint32), pos_r.view(np.uint32)) and np.array_equal(col_o, col_r)
+    rr.close()
+    recon.close()
+    assert n > 40000 and applied > 100, (n, applied)
 
 
 def test_first_frame_without_any_race_is_identical(ref):
