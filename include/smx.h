@@ -1281,6 +1281,77 @@ int smx_recon_raycast_mesh(smx_recon r, smx_stream s, const smx_raycast_params* 
 #define SMX_RAY_PHASES 4
 int smx_recon_debug_raycast_timings(smx_recon r, float* out_ms, int32_t capacity);
 
+/* ---- a ray-casting scene: the search structure of smx_recon_raycast_mesh built once, cast against many times ----
+ * smx_rayscene is a SNAPSHOT of a triangle array over the map together with its search structure.  After a build a cast reads
+ * neither the map nor the caller's triangle array: its answer is what smx_recon_raycast_mesh gives on the map as it stood at
+ * the build, with the same triangles and cell size, and stays so through later smx_recon_integrate, smx_recon_compact and
+ * smx_recon_deform_by_creation_frame calls and after smx_recon_destroy of the object it was built from.  hit stays "position
+ * in the array given at the build".  There is nothing that could go stale, hence no generation counter.
+ * Build (smx_recon_build_rayscene).  Steps 1 and 5 of smx_recon_raycast_mesh unchanged: the classes, R, c, the inflated boxes,
+ *    the wide list, the occupied cell box, the entries, the packed corner records in the sorted order, the cell table;
+ *    smx_rayscene_stats holds step 1's counts and step 5's structure words with the same meaning.  Refused like that call: an
+ *    index >= n, more than 2^30 entries, cell_size not 0 or finite and > 0, n_in > 2^28, triangles == NULL with n_in > 0; also
+ *    occupancy outside -1 .. 7, and a scene and an object on different devices.  Ordered after everything enqueued on r,
+ *    synchronous; changes in r only what smx_recon_raycast_mesh changes (its workspace holds the sort's buffers).  Building
+ *    into a scene that holds a build replaces it.  A scene never built, or whose last build was refused or failed for any
+ *    reason (an allocation included), is EMPTY: it holds no records, table or grid and refuses every cast.
+ *    n_in == 0 is a valid build (every ray answers "none").
+ * Occupancy bit grid.  It spans the occupied cell box [lo, hi] of the structure.  With k = occupancy - 1 a block is 2^k cells
+ *    per axis: the block of cell x on an axis is (x - lo) >> k, an axis has ((hi - lo) >> k) + 1 blocks, the bit number of
+ *    block (bx, by, bz) is (bz * nby + by) * nbx + bx in 64 bits, and a bit is set iff some cell of its block has an entry in
+ *    the cell table.  At most 2^31 bits (256 MiB).  occupancy -1: no grid.  1 + k with 0 <= k <= 6: that block size; one that
+ *    does not fit is refused after the mark phase and leaves the scene empty.  0: the library chooses -- the smallest k in
+ *    0 .. 6 that fits, none if none fits or nothing was entered (DESIGN.md 5m has the measurement behind it); occupancy_log2
+ *    of the stats says what was taken, -1 for none.  occupancy_bytes = the grid's size, n_blocks_set = its set bits (counted from
+ *    the bits), device_bytes = the device memory the scene holds after the build (records, table, grid, counters).
+ * Cast (smx_rayscene_cast).  p->cell_size must be 0; t_min, t_max, cull, BAD rays, the key, the outputs and the overlap rule
+ *    are exactly those of smx_recon_raycast_mesh, and hit, t and uv are byte for byte what that call writes.  The traversal
+ *    and its exit rule are that call's; the grid is a filter in front of the cell table's look-up and nothing else: a clear
+ *    bit means "no run", a set bit goes on to the table.  smx_rayscene_cast_stats: n_layers and n_pair_tests equal that call's
+ *    at the same c; without a grid n_bit_tests == 0 and n_lookups equals that call's; with one n_bit_tests equals that call's
+ *    n_lookups and n_lookups counts only the table look-ups still made; n_lookup_misses = those that found no run (0 at
+ *    k == 0), so n_lookups - n_lookup_misses does not depend on the occupancy setting.  Synchronous.  on_device says where
+ *    rays, hit, t and uv live.  n_rays == 0 is valid; uv and stats may be NULL; rays must not overlap an output (refused).  A
+ *    cast on an empty scene: SMX_ERR_INVALID_ARGUMENT.  A refused cast writes nothing; every allocation (ray staging, the
+ *    per-ray keys and work words) happens before the first write to an output.  One caller thread per scene.  A cast does
+ *    not touch r.
+ * All scene memory is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation.
+ * Not done: a kept index for smx_recon_mesh_distance; incremental updates of a scene; ray packets; a BVH; watertightness; an
+ * enqueue-only cast without host synchronisation. */
+typedef struct smx_rayscene_s* smx_rayscene;
+typedef struct {
+  float   cell_size;         /* as smx_raycast_params.cell_size; 0: the library chooses */
+  int32_t occupancy;         /* -1: no bit grid, 0: the library chooses, 1 + k: a bit per block of 2^k cells per axis (k <= 6) */
+} smx_rayscene_params;
+typedef struct {
+  uint32_t n_in, n_not_live, n_repeated, n_out_of_range;   /* as smx_raycast_stats */
+  uint32_t n_wide, n_entries, n_cells;
+  float    cell_size_used;
+  int32_t  occupancy_log2;            /* k of the grid built, -1: none */
+  uint32_t n_blocks_set;              /* set bits of the grid */
+  uint64_t occupancy_bytes;           /* the grid's size */
+  uint64_t device_bytes;              /* device memory the scene holds after the build */
+} smx_rayscene_stats;
+typedef struct {
+  uint32_t n_rays, n_bad_rays, n_hit, n_front_hits, max_t_bits, reserved;
+  uint64_t n_layers, n_bit_tests, n_lookups, n_lookup_misses, n_pair_tests;
+} smx_rayscene_cast_stats;
+int smx_rayscene_create(int32_t device_id /* -1: the current device */, smx_rayscene* out);
+int smx_rayscene_destroy(smx_rayscene sc);
+int smx_rayscene_params_default(smx_rayscene_params* out);   /* 0.0f, 0 */
+int smx_recon_build_rayscene(smx_recon r, smx_stream s, smx_rayscene sc, const smx_rayscene_params* p,
+                             const uint32_t* triangles, uint32_t n_in, int32_t on_device,
+                             smx_rayscene_stats* stats /* may be NULL */);
+int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p,
+                      const float* rays /* [n_rays][6] */, uint32_t n_rays,
+                      uint32_t* hit /* [n_rays] */, float* t /* [n_rays] */, float* uv /* [n_rays][2], may be NULL */,
+                      int32_t on_device, smx_rayscene_cast_stats* stats /* may be NULL */);
+/* Tools: milliseconds of the last build's phases mark, index, occupancy (grid clear, bits, their count), then of the last
+ * cast's phases cast, stats, by timed events on the calls' streams; a phase not reached reads 0.  capacity >=
+ * SMX_RAYSCENE_PHASES. */
+#define SMX_RAYSCENE_PHASES 5
+int smx_rayscene_debug_timings(smx_rayscene sc, float* out_ms, int32_t capacity);
+
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, normal rows 8-10, the rows the

@@ -462,6 +462,36 @@ struct MeshParams : smx_mesh_params {
   MeshParams() { SMX_SHIM_CHECK(smx_mesh_params_default(this)); }
 };
 
+// Not in the reference: a ray-casting scene (smx_rayscene in smx.h) -- a snapshot of a triangle array over the map with its search
+// structure, built once by CUDASurfelReconstruction::BuildRayScene and cast against many times; it outlives the map it was built
+// from.  stats() are those of the last build.
+class RayScene {
+ public:
+  explicit RayScene(int device_id = -1) {
+    SMX_SHIM_CHECK(smx_rayscene_create(device_id, &handle_));
+  }
+  RayScene(const RayScene&) = delete;
+  RayScene& operator=(const RayScene&) = delete;
+  ~RayScene() { SMX_SHIM_CHECK(smx_rayscene_destroy(handle_)); }
+  // *hit, *t and *uv (may be null) as CUDASurfelReconstruction::RaycastMesh fills them; params.cell_size must be 0.  Synchronous.
+  void Cast(cudaStream_t stream, const std::vector<float>& rays, const smx_raycast_params& params, std::vector<u32>* hit,
+            std::vector<float>* t, std::vector<float>* uv = nullptr, smx_rayscene_cast_stats* stats = nullptr) {
+    const u32 n_rays = (u32)(rays.size() / 6);
+    hit->resize(n_rays);
+    t->resize(n_rays);
+    if (uv) uv->resize((size_t)2 * n_rays);
+    SMX_SHIM_CHECK(smx_rayscene_cast(handle_, stream, &params, n_rays ? rays.data() : nullptr, n_rays, n_rays ? hit->data() : nullptr,
+                                     n_rays ? t->data() : nullptr, uv && n_rays ? uv->data() : nullptr, 0, stats));
+  }
+  const smx_rayscene_stats& stats() const { return stats_; }
+  smx_rayscene handle() const { return handle_; }
+
+ private:
+  friend class CUDASurfelReconstruction;
+  smx_rayscene handle_ = nullptr;
+  smx_rayscene_stats stats_{};
+};
+
 class CUDASurfelReconstruction {
  public:
   // The three cudaGraphicsResource_t arguments and the render window of the reference's constructor are
@@ -677,6 +707,17 @@ class CUDASurfelReconstruction {
     SMX_SHIM_CHECK(smx_recon_raycast_mesh(handle_, stream, &params, n_in ? triangles.data() : nullptr, n_in,
                                           n_rays ? rays.data() : nullptr, n_rays, n_rays ? hit->data() : nullptr,
                                           n_rays ? t->data() : nullptr, uv && n_rays ? uv->data() : nullptr, 0, stats));
+  }
+  // Not in the reference: (re)builds `scene` from `triangles` over the map as it stands (smx_recon_build_rayscene in smx.h);
+  // cell_size 0 and occupancy 0 leave both choices to the library.  Synchronous.  A refused build leaves the scene empty.
+  void BuildRayScene(cudaStream_t stream, const std::vector<u32>& triangles, RayScene* scene, float cell_size = 0.0f,
+                     int occupancy = 0) {
+    smx_rayscene_params p;
+    SMX_SHIM_CHECK(smx_rayscene_params_default(&p));
+    p.cell_size = cell_size;
+    p.occupancy = occupancy;
+    const u32 n_in = (u32)(triangles.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_build_rayscene(handle_, stream, scene->handle_, &p, n_in ? triangles.data() : nullptr, n_in, 0, &scene->stats_));
   }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.

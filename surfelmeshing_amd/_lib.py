@@ -256,6 +256,29 @@ class RaycastStats(C.Structure):
                 [(n, C.c_uint64) for n in ("n_layers", "n_lookups", "n_pair_tests")])
 
 
+class RaySceneParams(C.Structure):
+    """smx_rayscene_params: the grid's cell (0: the library chooses) and the occupancy bit grid (-1 none, 0 the library chooses,
+    1 + k: a bit per block of 2^k cells per axis)."""
+    _fields_ = [("cell_size", C.c_float), ("occupancy", C.c_int32)]
+
+
+RAYSCENE_PHASES = 5         # SMX_RAYSCENE_PHASES
+RAYSCENE_MAX_LOG2 = 6       # the largest k of an occupancy block
+
+
+class RaySceneStats(C.Structure):
+    """smx_rayscene_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_wide", "n_entries", "n_cells")] +
+                [("cell_size_used", C.c_float), ("occupancy_log2", C.c_int32), ("n_blocks_set", C.c_uint32),
+                 ("occupancy_bytes", C.c_uint64), ("device_bytes", C.c_uint64)])
+
+
+class RaySceneCastStats(C.Structure):
+    """smx_rayscene_cast_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_rays", "n_bad_rays", "n_hit", "n_front_hits", "max_t_bits", "reserved")] +
+                [(n, C.c_uint64) for n in ("n_layers", "n_bit_tests", "n_lookups", "n_lookup_misses", "n_pair_tests")])
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -336,6 +359,8 @@ EXPORTS = [
     "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
     "smx_distance_params_default", "smx_recon_mesh_distance", "smx_recon_debug_distance_timings",
     "smx_raycast_params_default", "smx_recon_raycast_mesh", "smx_recon_debug_raycast_timings",
+    "smx_rayscene_create", "smx_rayscene_destroy", "smx_rayscene_params_default", "smx_recon_build_rayscene", "smx_rayscene_cast",
+    "smx_rayscene_debug_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

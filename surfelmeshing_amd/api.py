@@ -27,6 +27,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
                    DIST_BINS, DIST_PHASES, DistanceParams, DistanceStats,
                    RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
+                   RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -103,6 +104,98 @@ def raycast_stats_dict(st):
     d = {n: int(getattr(st, n)) for n, _ in RaycastStats._fields_ if n not in ("reserved", "cell_size_used")}
     d["cell_size_used"] = float(st.cell_size_used)
     return d
+
+
+def rayscene_params(cell_size=0.0, occupancy=0):
+    """The parameters of BuildRayScene as smx_rayscene_params; ValueError on what the library would refuse, before anything
+    is called."""
+    c = float(np.float32(cell_size))
+    if not (c - c == 0.0 and c >= 0.0):
+        raise ValueError("cell_size must be 0 (the library chooses) or finite and > 0")
+    if isinstance(occupancy, bool) or not isinstance(occupancy, (int, np.integer)) or not -1 <= int(occupancy) <= 1 + RAYSCENE_MAX_LOG2:
+        raise ValueError("occupancy must be -1 (no bit grid), 0 (the library chooses) or 1 + k with 0 <= k <= %d" % RAYSCENE_MAX_LOG2)
+    return RaySceneParams(c, int(occupancy))
+
+
+def rayscene_stats_dict(st):
+    """smx_rayscene_stats or smx_rayscene_cast_stats as a dict: integers, cell_size_used a float."""
+    d = {n: int(getattr(st, n)) for n, _ in st._fields_ if n not in ("reserved", "cell_size_used")}
+    if hasattr(st, "cell_size_used"):
+        d["cell_size_used"] = float(st.cell_size_used)
+    return d
+
+
+class RayScene:
+    """Not in the reference: a snapshot of a triangle array over the map with its search structure (smx_rayscene), built once
+    by CUDASurfelReconstruction.BuildRayScene and cast against many times.  After the build a cast reads neither the map nor
+    the triangle array: it answers what RaycastMesh answered on the map as it stood at the build, through later Integrate,
+    Compact and deformation calls and after the reconstruction object is gone.  .stats is the dict of smx_rayscene_stats of
+    the build.  close() frees the device memory; the object is a context manager."""
+
+    def __init__(self, device_id=-1):
+        self._h = C.c_void_p()
+        self.stats = None
+        _lib.check(_lib.load().smx_rayscene_create(C.c_int32(device_id), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().smx_rayscene_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def Cast(self, stream, rays, t_min=0.0, t_max=RAY_MAX_T, cull=0, return_uv=False):
+        """For every ray of `rays` ([P,6] float32: origin, then direction, not normalised) what RaycastMesh returns for the
+        triangles and the map of the build (smx_rayscene_cast): byte for byte the same hit, t and uv.  Synchronous.  rays is
+        a numpy array or a contiguous float32 device tensor; the results then are device tensors too.  Returns (hit, t, then
+        with return_uv uv, then the dict of smx_rayscene_cast_stats)."""
+        p = raycast_params(t_min, t_max, 0.0, cull)
+        if not getattr(self, "_h", None):
+            raise ValueError("the scene is closed")
+        L = _lib.load()
+        st = RaySceneCastStats()
+        dev = _device_address(rays) is not None
+        if dev:
+            import torch
+            if not (rays.is_contiguous() and rays.dtype == torch.float32 and rays.numel() % 6 == 0):
+                raise ValueError("a device tensor of rays must be contiguous [P,6] float32")
+            n_rays = rays.numel() // 6
+            hit = torch.empty(n_rays, dtype=torch.uint32, device=rays.device)
+            t = torch.empty(n_rays, dtype=torch.float32, device=rays.device)
+            uv = torch.empty((n_rays, 2), dtype=torch.float32, device=rays.device) if return_uv else None
+            rin = rays.data_ptr() if n_rays else None
+            outs = [a.data_ptr() if a is not None and n_rays else None for a in (hit, t, uv)]
+            torch.cuda.current_stream(rays.device).synchronize()      # (the tensor's producers; the call runs on `stream`)
+        else:
+            ry = np.ascontiguousarray(rays, np.float32)
+            if ry.size % 6:
+                raise ValueError("rays must hold six values per row")
+            n_rays = ry.size // 6
+            hit, t = np.zeros(n_rays, np.uint32), np.zeros(n_rays, np.float32)
+            uv = np.zeros((n_rays, 2), np.float32) if return_uv else None
+            rin = ry.ctypes.data if n_rays else None
+            outs = [a.ctypes.data if a is not None and n_rays else None for a in (hit, t, uv)]
+        _lib.check(L.smx_rayscene_cast(self._h, _sv(stream), C.byref(p), C.c_void_p(rin), C.c_uint32(n_rays), C.c_void_p(outs[0]),
+                                       C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_int32(1 if dev else 0), C.byref(st)))
+        stats = rayscene_stats_dict(st)
+        return (hit, t, uv, stats) if return_uv else (hit, t, stats)
+
+    def debug_timings(self):
+        """Milliseconds of the last build (mark, index, occupancy) and of the last cast (cast, stats)."""
+        out = (C.c_float * RAYSCENE_PHASES)()
+        _lib.check(_lib.load().smx_rayscene_debug_timings(self._h, out, C.c_int32(RAYSCENE_PHASES)))
+        return dict(zip(("mark", "index", "occupancy", "cast", "stats"), [float(v) for v in out]))
 
 
 def _device_address(a):
@@ -1017,6 +1110,40 @@ class CUDASurfelReconstruction:
                                             C.c_int32(1 if dev else 0), C.byref(st)))
         stats = raycast_stats_dict(st)
         return (hit, t, uv, stats) if return_uv else (hit, t, stats)
+
+    def BuildRayScene(self, stream, triangles, cell_size=0.0, occupancy=0, scene=None):
+        """Not in the reference: a RayScene of `triangles` ([T,3] slot indices, a numpy array or a contiguous 32-bit device
+        tensor) over the map as it stands (smx_recon_build_rayscene).  cell_size as in RaycastMesh; occupancy -1: no occupancy
+        bit grid, 0: the library chooses, 1 + k: a bit per block of 2^k cells per axis.  Synchronous.  scene: an existing
+        RayScene to rebuild in place.  A refused build leaves the scene empty (and closes a scene made here)."""
+        p = rayscene_params(cell_size, occupancy)
+        dev = _device_address(triangles) is not None
+        if dev:
+            if not (triangles.is_contiguous() and triangles.element_size() == 4 and triangles.numel() % 3 == 0):
+                raise ValueError("a device tensor of triangles must be contiguous [T,3] 32-bit integers")
+            n_in = triangles.numel() // 3
+            tin = triangles.data_ptr() if n_in else None
+            import torch
+            torch.cuda.current_stream(triangles.device).synchronize()      # (the tensor's producers; the call runs on `stream`)
+        else:
+            tri = np.ascontiguousarray(triangles, np.uint32)
+            if tri.size % 3:
+                raise ValueError("triangles must hold three values per row")
+            n_in = tri.size // 3
+            tin = tri.ctypes.data if n_in else None
+        own = scene is None
+        sc = RayScene() if own else scene
+        st = RaySceneStats()
+        try:
+            _lib.check(_lib.load().smx_recon_build_rayscene(self._h, _sv(stream), sc._h, C.byref(p), C.c_void_p(tin), C.c_uint32(n_in),
+                                                            C.c_int32(1 if dev else 0), C.byref(st)))
+        except Exception:
+            sc.stats = None
+            if own:
+                sc.close()
+            raise
+        sc.stats = rayscene_stats_dict(st)
+        return sc
 
     def debug_raycast_timings(self):
         """Milliseconds of the last RaycastMesh call, by phase."""

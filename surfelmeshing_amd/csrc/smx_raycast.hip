@@ -20,7 +20,8 @@
 // and one integer maximum.
 //
 // smx_recon_raycast_mesh itself is at the end of the file: it owns the order of the phases, the workspace (RaycastWork,
-// smx_raycast.hpp) and the two reads of the counters.
+// smx_raycast.hpp) and the two reads of the counters.  The mark and the index phase are ray_enqueue_mark and ray_enqueue_index,
+// which smx_recon_build_rayscene (smx_rayscene.hip) calls too, with a scene's records and table in place of the workspace's.
 #include <cmath>
 
 #include "smx_recon_state.hpp"
@@ -31,51 +32,6 @@ namespace smx {
 namespace {
 
 constexpr int kRBlock = kRayBlock;
-
-struct RayDeviceTable {
-  DistCell* e;
-  __device__ __forceinline__ unsigned long long key(uint32_t h) const { return e[h].key; }
-  __device__ __forceinline__ unsigned long long value(uint32_t h) const { return e[h].value; }
-  __device__ __forceinline__ unsigned long long claim(uint32_t h, unsigned long long expected, unsigned long long desired) const {
-    return atomicCAS(&e[h].key, expected, desired);
-  }
-  __device__ __forceinline__ void bump(uint32_t h, unsigned long long inc) const { atomicAdd(&e[h].value, inc); }
-};
-
-struct RayDeviceRecs {
-  const DistRec* r;
-  __device__ __forceinline__ void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* i) const {
-    const DistRec x = r[j];
-    *A = DistVec{x.a.x, x.a.y, x.a.z}; *B = DistVec{x.b.x, x.b.y, x.b.z}; *C = DistVec{x.c.x, x.c.y, x.c.z};
-    *i = __float_as_uint(x.a.w);
-  }
-};
-
-// one atomic per wavefront: the number of its lanes with `pred`
-__device__ __forceinline__ void ray_wave_count(uint32_t* counter, bool pred) {
-  const unsigned long long m = __ballot(pred);
-  if (m != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)m) - 1)) atomicAdd(counter, (uint32_t)__popcll(m));
-}
-__device__ __forceinline__ unsigned long long ray_wave_min(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ unsigned long long ray_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ int32_t ray_wave_imin(int32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int32_t ray_wave_imax(int32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
-  return v;
-}
 
 __device__ __forceinline__ DistVec ray_pos(const DistMap& map, uint32_t i) {
   const float4 s = map.smooth[(size_t)i * map.smooth_stride];
@@ -217,11 +173,6 @@ k_ray_table(const unsigned long long* __restrict__ keys, uint32_t n_entries, Dis
   ray_wave_count(&cnt[kRayCells], head);
 }
 
-__device__ __forceinline__ void ray_load(const float* rays, uint32_t p, DistVec* O, DistVec* D) {
-  const float* r = rays + 6 * (size_t)p;
-  *O = DistVec{r[0], r[1], r[2]}; *D = DistVec{r[3], r[4], r[5]};
-}
-
 // A wavefront per ray.  Everything that steers a loop (the ray, its axes, the layer count, the ballots, the broadcast
 // rectangles and runs, the folded minimum) is uniform over the wavefront; a lane's own state is its layer's rectangle, one
 // 64-bit key and three counts.  No LDS, no barrier.
@@ -332,16 +283,50 @@ k_ray_stats(uint32_t n_rays, const unsigned long long* __restrict__ best, const 
   if (bits) atomicMax(&cnt[kRayMaxBits], bits);              // (bits of non-negative floats order as the floats do)
 }
 
-inline unsigned ray_blocks(uint32_t n) { return (unsigned)div_up(n, kRBlock); }
-inline bool ray_finite_f(float v) { return v - v == 0.0f; }
-inline bool ray_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-inline unsigned long long ray_word64(const uint32_t* h, int lo) { return ((unsigned long long)h[lo + 1] << 32) | h[lo]; }
+}  // namespace
 
-}  // extern "C"
+int ray_enqueue_mark(RaycastWork& w, const DistMap& map, const uint32_t* din, uint32_t n_in, float cell_size, uint32_t* cnt, hipStream_t st) {
+  const int nb = div_up(n_in, kRayBlock);
+  const dim3 b(kRayBlock), g_in(nb);
+  if (n_in > 0) hipLaunchKernelGGL(k_ray_classify, g_in, b, 0, st, map, din, n_in, w.mark.get(), cnt);
+  hipLaunchKernelGGL(k_ray_cell, dim3(1), dim3(64), 0, st, cell_size, cnt);
+  if (n_in > 0) {
+    hipLaunchKernelGGL(k_ray_mark, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.wide_t.get(), w.blocks.get(), cnt);
+    enqueue_segment_scan(st, w.blocks.get(), nb, cnt + kRayEntries);
+  }
+  SMX_LAUNCH_CHECK();
+  return SMX_OK;
+}
+
+int ray_enqueue_index(RaycastWork& w, const DistMap& map, const uint32_t* din, uint32_t n_in, uint32_t E, uint32_t Wd, uint32_t* cnt,
+                      DevBuf<float>& recs_buf, DevBuf<float>& wide_buf, DevBuf<unsigned long long>& table_buf, uint32_t* mask_out,
+                      const unsigned long long** sorted_keys, hipStream_t st) {
+  const dim3 b(kRayBlock), g_in(div_up(n_in, kRayBlock));
+  const uint32_t entries = dec_table_size(E), mask = entries - 1;
+  for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(E)); SMX_CALL(w.vals[k].reserve(E)); }
+  SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(E)));
+  SMX_CALL(recs_buf.reserve((size_t)E * 12));
+  SMX_CALL(wide_buf.reserve((size_t)Wd * 12));
+  SMX_CALL(table_buf.reserve((size_t)2 * entries));
+  DistCell* table = reinterpret_cast<DistCell*>(table_buf.get());
+  DistRec* recs = reinterpret_cast<DistRec*>(recs_buf.get());
+  DistRec* wide_recs = reinterpret_cast<DistRec*>(wide_buf.get());
+  *mask_out = mask;
+  *sorted_keys = nullptr;
+  SMX_HIP(hipMemsetAsync(table, 0, (size_t)entries * sizeof(DistCell), st));
+  if (E > 0) {
+    hipLaunchKernelGGL(k_ray_entries, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.blocks.get(), cnt, E, w.keys[0].get(), w.vals[0].get());
+    SMX_LAUNCH_CHECK();
+    const int cur = radix_sort(w.keys, w.vals, E, 63, w.hist.get(), st);
+    hipLaunchKernelGGL(k_ray_records, dim3(ray_blocks(E)), b, 0, st, map, din, w.vals[cur].get(), E, recs);
+    hipLaunchKernelGGL(k_ray_table, dim3(ray_blocks(E)), b, 0, st, w.keys[cur].get(), E, table, mask, cnt);
+    *sorted_keys = w.keys[cur].get();
+  }
+  if (Wd > 0) hipLaunchKernelGGL(k_ray_records, dim3(ray_blocks(Wd)), b, 0, st, map, din, w.wide_t.get(), Wd, wide_recs);
+  SMX_LAUNCH_CHECK();
+  return SMX_OK;
+}
+
 }  // namespace smx
 
 using namespace smx;
@@ -424,14 +409,8 @@ int smx_recon_raycast_mesh(smx_recon r, smx_stream s, const smx_raycast_params* 
   // ---- mark
   const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
   const DistMap map{sv.p, sv.stride, nv.p, nv.stride, n};
-  const dim3 b(kRayBlock), g_in(nb);
-  if (n_in > 0) hipLaunchKernelGGL(k_ray_classify, g_in, b, 0, st, map, din, n_in, w.mark.get(), cnt);
-  hipLaunchKernelGGL(k_ray_cell, dim3(1), dim3(64), 0, st, p->cell_size, cnt);
-  if (n_in > 0) {
-    hipLaunchKernelGGL(k_ray_mark, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.wide_t.get(), w.blocks.get(), cnt);
-    enqueue_segment_scan(st, w.blocks.get(), nb, cnt + kRayEntries);
-  }
-  SMX_LAUNCH_CHECK();
+  const dim3 b(kRayBlock);
+  SMX_CALL(ray_enqueue_mark(w, map, din, n_in, p->cell_size, cnt, st));
   SMX_CALL(w.stamps.mark(st));
   SMX_CALL(read_counters());
   if (h[kRayError] != 0) {
@@ -445,25 +424,12 @@ int smx_recon_raycast_mesh(smx_recon r, smx_stream s, const smx_raycast_params* 
   const uint32_t E = h[kRayEntries], Wd = h[kRayNWide];
 
   // ---- index (every allocation of the call lies before the first write to an output)
-  const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(E)); SMX_CALL(w.vals[k].reserve(E)); }
-  SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(E)));
-  SMX_CALL(w.recs.reserve((size_t)E * 12));
-  SMX_CALL(w.wide_recs.reserve((size_t)Wd * 12));
-  SMX_CALL(w.table.reserve((size_t)2 * entries));
-  DistCell* table = reinterpret_cast<DistCell*>(w.table.get());
-  DistRec* recs = reinterpret_cast<DistRec*>(w.recs.get());
-  DistRec* wide_recs = reinterpret_cast<DistRec*>(w.wide_recs.get());
-  SMX_HIP(hipMemsetAsync(table, 0, (size_t)entries * sizeof(DistCell), st));
-  if (E > 0) {
-    hipLaunchKernelGGL(k_ray_entries, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.blocks.get(), cnt, E, w.keys[0].get(), w.vals[0].get());
-    SMX_LAUNCH_CHECK();
-    const int cur = radix_sort(w.keys, w.vals, E, 63, w.hist.get(), st);
-    hipLaunchKernelGGL(k_ray_records, dim3(ray_blocks(E)), b, 0, st, map, din, w.vals[cur].get(), E, recs);
-    hipLaunchKernelGGL(k_ray_table, dim3(ray_blocks(E)), b, 0, st, w.keys[cur].get(), E, table, mask, cnt);
-  }
-  if (Wd > 0) hipLaunchKernelGGL(k_ray_records, dim3(ray_blocks(Wd)), b, 0, st, map, din, w.wide_t.get(), Wd, wide_recs);
-  SMX_LAUNCH_CHECK();
+  uint32_t mask = 0;
+  const unsigned long long* sorted_keys = nullptr;
+  SMX_CALL(ray_enqueue_index(w, map, din, n_in, E, Wd, cnt, w.recs, w.wide_recs, w.table, &mask, &sorted_keys, st));
+  const DistCell* table = reinterpret_cast<const DistCell*>(w.table.get());
+  const DistRec* recs = reinterpret_cast<const DistRec*>(w.recs.get());
+  const DistRec* wide_recs = reinterpret_cast<const DistRec*>(w.wide_recs.get());
   SMX_CALL(w.stamps.mark(st));
 
   // ---- cast

@@ -252,6 +252,75 @@ struct RaycastWork {
   DevBuf<uint32_t> counters;               // [kRayWords]
   PhaseStamps<SMX_RAY_PHASES> stamps;      // of the last call; a refused call publishes the phases it completed
 };
+
+// ---- what smx_raycast.hip and smx_rayscene.hip share: how a kernel reads the table and the records, the wave folds ----------
+struct RayDeviceTable {
+  DistCell* e;
+  __device__ __forceinline__ unsigned long long key(uint32_t h) const { return e[h].key; }
+  __device__ __forceinline__ unsigned long long value(uint32_t h) const { return e[h].value; }
+  __device__ __forceinline__ unsigned long long claim(uint32_t h, unsigned long long expected, unsigned long long desired) const {
+    return atomicCAS(&e[h].key, expected, desired);
+  }
+  __device__ __forceinline__ void bump(uint32_t h, unsigned long long inc) const { atomicAdd(&e[h].value, inc); }
+};
+
+struct RayDeviceRecs {
+  const DistRec* r;
+  __device__ __forceinline__ void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* i) const {
+    const DistRec x = r[j];
+    *A = DistVec{x.a.x, x.a.y, x.a.z}; *B = DistVec{x.b.x, x.b.y, x.b.z}; *C = DistVec{x.c.x, x.c.y, x.c.z};
+    *i = __float_as_uint(x.a.w);
+  }
+};
+
+// one atomic per wavefront: the number of its lanes with `pred`
+__device__ __forceinline__ void ray_wave_count(uint32_t* counter, bool pred) {
+  const unsigned long long m = __ballot(pred);
+  if (m != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)m) - 1)) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+__device__ __forceinline__ unsigned long long ray_wave_min(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ unsigned long long ray_wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ int32_t ray_wave_imin(int32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int32_t ray_wave_imax(int32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ void ray_load(const float* rays, uint32_t p, DistVec* O, DistVec* D) {
+  const float* r = rays + 6 * (size_t)p;
+  *O = DistVec{r[0], r[1], r[2]}; *D = DistVec{r[3], r[4], r[5]};
+}
+
+inline unsigned ray_blocks(uint32_t n) { return (unsigned)div_up(n, kRayBlock); }
+inline bool ray_finite_f(float v) { return v - v == 0.0f; }
+inline bool ray_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+inline unsigned long long ray_word64(const uint32_t* h, int lo) { return ((unsigned long long)h[lo + 1] << 32) | h[lo]; }
+
+// The mark and the index phase of smx_recon_raycast_mesh, enqueued on st (smx_raycast.hip).  The caller has reserved w.mark,
+// w.blocks ([div_up(n_in, kRayBlock)]) and w.wide_t for n_in and zeroed the kRayWords words of cnt; din is device memory.
+// Between the two it reads cnt back: kRayError, the 64-bit entry count, E = [kRayEntries] and Wd = [kRayNWide].
+int ray_enqueue_mark(RaycastWork& w, const DistMap& map, const uint32_t* din, uint32_t n_in, float cell_size, uint32_t* cnt, hipStream_t st);
+// Reserves the sort's buffers in w, then recs, wide_recs and table (the caller's: the workspace's own, or a scene's), in the
+// order the call always has; *sorted_keys = the E sorted cell keys, in w until its next use.
+int ray_enqueue_index(RaycastWork& w, const DistMap& map, const uint32_t* din, uint32_t n_in, uint32_t E, uint32_t Wd, uint32_t* cnt,
+                      DevBuf<float>& recs, DevBuf<float>& wide_recs, DevBuf<unsigned long long>& table, uint32_t* mask,
+                      const unsigned long long** sorted_keys, hipStream_t st);
 #endif
 
 }  // namespace smx

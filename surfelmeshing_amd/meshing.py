@@ -271,17 +271,31 @@ def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None
     return distance_summary(distance, stats), nearest, distance, stats
 
 
-def cast_rays(rec, triangles, origins, directions, t_min=0.0, t_max=2.0 ** 20, cull=0, cell_size=0.0, return_uv=False, stream=None):
+def build_ray_scene(rec, triangles, cell_size=0.0, occupancy=0, stream=None):
+    """A RayScene of `triangles` over the map as it stands (CUDASurfelReconstruction.BuildRayScene): build it once, then pass it
+    as scene= to cast_rays, vertex_visibility or render.raycast_mesh_view as often as needed.  It is a snapshot: later changes
+    of the map do not reach it.  ValueError on parameters the library would refuse."""
+    from .api import rayscene_params
+    rayscene_params(cell_size, occupancy)
+    return rec.BuildRayScene(stream, triangles, cell_size, occupancy)
+
+
+def cast_rays(rec, triangles, origins, directions, t_min=0.0, t_max=2.0 ** 20, cull=0, cell_size=0.0, return_uv=False, stream=None,
+              scene=None):
     """For every ray (origins [P,3], directions [P,3], not normalised: t is in units of |direction|) the first triangle of
     `triangles` it hits with t_min <= t <= t_max, on the device: (hit, t[, uv], stats) as CUDASurfelReconstruction.RaycastMesh
-    returns them.  ValueError on parameters the library would refuse."""
+    returns them.  With scene (build_ray_scene) the rays are cast against that scene instead: rec, triangles and cell_size
+    are not used, and the statistics are those of RayScene.Cast.  ValueError on parameters the library would refuse."""
     import numpy as np
     from .api import raycast_params
     raycast_params(t_min, t_max, cell_size, cull)
     o, d = np.asarray(origins, np.float32), np.asarray(directions, np.float32)
     if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
         raise ValueError("origins and directions must both be [P, 3]")
-    return rec.RaycastMesh(stream, triangles, np.ascontiguousarray(np.concatenate([o, d], axis=1)), t_min, t_max, cell_size, cull, return_uv)
+    rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+    if scene is not None:
+        return scene.Cast(stream, rays, t_min, t_max, cull, return_uv)
+    return rec.RaycastMesh(stream, triangles, rays, t_min, t_max, cell_size, cull, return_uv)
 
 
 def camera_rays(fx, fy, cx, cy, width, height, global_T_camera):
@@ -300,13 +314,14 @@ def camera_rays(fx, fy, cx, cy, width, height, global_T_camera):
     return o, d
 
 
-def vertex_visibility(rec, triangles, camera_centre, t_min=2.0 ** -10, cell_size=0.0, stream=None):
+def vertex_visibility(rec, triangles, camera_centre, t_min=2.0 ** -10, cell_size=0.0, stream=None, scene=None):
     """Which of the vertices `triangles` uses are seen from camera_centre: the segment from each used vertex (ascending by
     slot) to the camera is cast with t in [t_min, 1], and a vertex is visible iff its segment hits nothing.  t_min keeps the
-    triangles around the vertex itself out.  Returns (slots [m] uint32, visible [m] bool, stats)."""
+    triangles around the vertex itself out.  scene: a RayScene of `triangles` (build_ray_scene) to cast against, for one camera
+    after another.  Returns (slots [m] uint32, visible [m] bool, stats)."""
     import numpy as np
     used = np.unique(np.ascontiguousarray(triangles, np.uint32))
     c = np.asarray(camera_centre, np.float32).reshape(3)
     v = map_positions(rec, used, stream)
-    hit, t, stats = cast_rays(rec, triangles, v, c[None, :] - v, t_min, 1.0, 0, cell_size, stream=stream)
+    hit, t, stats = cast_rays(rec, triangles, v, c[None, :] - v, t_min, 1.0, 0, cell_size, stream=stream, scene=scene)
     return used, hit == np.uint32(0xFFFFFFFF), stats

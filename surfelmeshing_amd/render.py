@@ -80,14 +80,15 @@ def render_mesh_view(rec, triangles, width, height, fx, fy, cx, cy, global_T_cam
 
 
 def raycast_mesh_view(rec, triangles, width, height, fx, fy, cx, cy, global_T_camera, cull_back_faces=False, near_z=0.0,
-                      far_z=2.0 ** 20, cell_size=0.0, stream=None):
+                      far_z=2.0 ** 20, cell_size=0.0, stream=None, scene=None):
     """The depth and index images of `triangles` by ray casting (smx_recon_raycast_mesh) instead of rasterising: {"depth":
     float32 [H, W] (0 = empty), "index": uint32 [H, W] (0xFFFFFFFF = empty)}, the sizes and dtypes render_mesh_view gives.
     One ray per pixel centre (meshing.camera_rays), so depth is the ray parameter t = the camera depth of the hit.  There is no
     near plane to clip against: it also works for a camera whose plane cuts triangles.  Different arithmetic from the
-    rasteriser, so the two images agree on most pixels, not on all."""
+    rasteriser, so the two images agree on most pixels, not on all.  scene: a RayScene of `triangles` (meshing.build_ray_scene)
+    to cast against, for one pose after another."""
     from . import meshing
     o, d = meshing.camera_rays(fx, fy, cx, cy, width, height, global_T_camera)
-    hit, t, _ = meshing.cast_rays(rec, triangles, o, d, near_z, far_z, 1 if cull_back_faces else 0, cell_size, stream=stream)
+    hit, t, _ = meshing.cast_rays(rec, triangles, o, d, near_z, far_z, 1 if cull_back_faces else 0, cell_size, stream=stream, scene=scene)
     depth = np.where(hit != np.uint32(0xFFFFFFFF), t, np.float32(0.0)).astype(np.float32)
     return {"depth": depth.reshape(int(height), int(width)), "index": hit.reshape(int(height), int(width))}

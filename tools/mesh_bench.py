@@ -8,6 +8,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --fill [EDGES] [--decimate CELL[,CELL...]] [--small_target N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --distance METRES[,METRES...] [--decimate CELL[,CELL...]] [--points N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --raycast WxH --scene [--decimate METRES] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -58,7 +59,16 @@ mesh decimated at 0.05 m: medians of --reps calls with device arrays, whole call
 library's own (smx_recon_debug_raycast_timings); rays/s; every count of smx_raycast_stats; layers, look-ups and pair tests per
 ray; the index rebuild's share (mark + index) of the call; and smx_recon_render_mesh of the same pose, size and mesh measured
 beside it, with the share of pixels whose index equals the rasteriser's.  Writes profiles/raycast_bench.{txt,json} unless --txt
-/ --json say otherwise."""
+/ --json say otherwise.
+
+--raycast WxH --scene measures smx_rayscene on the same rays and the same two meshes (the decimated one at the
+first --decimate cell, 0.05 m by default), everything in one process: smx_recon_raycast_mesh re-measured first (its call, its
+phases, and the min and max of its cast + stats over the repetitions: the spread every comparison allows); then for occupancy
+-1, 0 and every explicit block size that fits: the build by phase (smx_rayscene_debug_timings, medians of --reps rebuilds), the
+grid's size and set bits, the scene's device memory, cast + stats as the median, min and max of --reps casts with device
+arrays, and the five work counters per ray; the bytes of every cast are compared with the call's.  The last two lines say whether
+a cast without a grid stays within the call's cast + stats plus the spread, and whether the smallest grid that fits pays by the
+rule of DESIGN.md 5m.  Writes profiles/rayscene_bench.{txt,json} unless --txt / --json say otherwise."""
 import argparse
 import json
 import os
@@ -81,6 +91,8 @@ ap.add_argument("--small_target", type=int, default=50_000, help="with --fill: l
 ap.add_argument("--distance", default=None, metavar="METRES[,METRES...]", help="measure smx_recon_mesh_distance at these max_distance values")
 ap.add_argument("--points", type=int, default=1_000_000, help="with --distance: query points on the analytic room surface")
 ap.add_argument("--raycast", default=None, metavar="WxH", help="measure smx_recon_raycast_mesh with the camera rays of the bench pose")
+ap.add_argument("--scene", action="store_true", help="with --raycast: measure smx_rayscene (build by phase, cast for every occupancy setting) "
+                                                      "beside smx_recon_raycast_mesh, on the full mesh and the one decimated at the first --decimate cell")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -761,17 +773,15 @@ def update_main():
 RAY_PHASES = ("mark", "index", "cast", "stats")
 
 
-def raycast_main():
+def raycast_inputs(say):
+    """What --raycast and --raycast --scene measure on: the grown map, its mesh and the decimated one on the device, the camera
+    rays of the bench pose on the device, and an event timer."""
     import ctypes as C
+    from types import SimpleNamespace
     from surfelmeshing_amd import meshing
-    _lib.require_gpu()
     L = _lib.load()
-    lines = []
-
-    def say(text):
-        print(text, flush=True)
-        lines.append(text)
     W, H = (int(v) for v in args.raycast.lower().split("x"))
+    DEC = float(args.decimate.split(",")[0]) if args.decimate else 0.05
     wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
     t0 = time.time()
     g_end, _ = wl.grow(False)
@@ -805,8 +815,26 @@ def raycast_main():
                                        C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
     T_in = T.value
     T, dst = C.c_uint32(0), _lib.DecimateStats()
-    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(0.05), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(DEC), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
                                          C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(T), C.byref(dst)))
+
+    return SimpleNamespace(W=W, H=H, wl=wl, rec=rec, n=n, live=live, pose=pose, fx=fx, fy=fy, cx=cx, cy=cy, P=P, drays=drays, dhit=dhit, dt=dt,
+                           nn=nn, dtri=dtri, dout=dout, bufs=bufs, timed=timed, T_in=T_in, T_dec=T.value, dec_cell=DEC)
+
+
+def raycast_main():
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    q = raycast_inputs(say)
+    W, H, rec, n, live, pose, fx, fy, cx, cy, P = q.W, q.H, q.rec, q.n, q.live, q.pose, q.fx, q.fy, q.cx, q.cy, q.P
+    drays, dhit, dt, nn, dtri, dout, bufs, timed, T_in = q.drays, q.dhit, q.dt, q.nn, q.dtri, q.dout, q.bufs, q.timed, q.T_in
+    T = C.c_uint32(q.T_dec)
 
     def cast(src, n_in):
         prm, st = api.raycast_params(), _lib.RaycastStats()
@@ -815,7 +843,7 @@ def raycast_main():
                                             C.c_void_p(dt.ToCUDA().address), None, C.c_int32(1), C.byref(st)))
         return api.raycast_stats_dict(st)
     out_rows = []
-    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at 0.05 m", dout, T.value)):
+    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at %g m" % q.dec_cell, dout, T.value)):
         t, phs, st, first = [], [], None, None
         for _ in range(args.reps + 1):
             ms, st2 = timed(lambda: cast(src, n_in))
@@ -854,6 +882,130 @@ def raycast_main():
     with open(args.txt or os.path.join(ROOT, "profiles", "raycast_bench.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     nn.close()
+
+
+SCENE_PHASES = ("mark", "index", "occupancy", "cast", "stats")
+SCENE_WORK = ("n_layers", "n_bit_tests", "n_lookups", "n_lookup_misses", "n_pair_tests")
+
+
+def rayscene_main():
+    """--raycast WxH --scene: smx_rayscene beside smx_recon_raycast_mesh in one process."""
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    q = raycast_inputs(say)
+    rec, P, timed = q.rec, q.P, q.timed
+    rays, hit, t = (C.c_void_p(b.ToCUDA().address) for b in (q.drays, q.dhit, q.dt))
+    prm = api.raycast_params()
+
+    def answer():
+        return q.dhit.Download()[0].tobytes() + q.dt.Download()[0].tobytes()
+
+    def spread(v):
+        return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+    out_rows = []
+    for what, src, n_in in (("full mesh", q.dtri, q.T_in), ("decimated at %g m" % q.dec_cell, q.dout, q.T_dec)):
+        tri = C.c_void_p(src.ToCUDA().address)
+        # the existing call, re-measured here
+        calls, phs, st = [], [], _lib.RaycastStats()
+        for _ in range(args.reps + 1):
+            calls.append(timed(lambda: _lib.check(L.smx_recon_raycast_mesh(rec._h, None, C.byref(prm), tri, C.c_uint32(n_in), rays, C.c_uint32(P),
+                                                                            hit, t, None, C.c_int32(1), C.byref(st))))[0])
+            phs.append(rec.debug_raycast_timings())
+        want, base = answer(), api.raycast_stats_dict(st)
+        base_cast = spread([ph["cast"] + ph["stats"] for ph in phs[1:]])          # (the first call allocates the workspace)
+        base_ph = {k: float(np.median([ph[k] for ph in phs[1:]])) for k in RAY_PHASES}
+        tol = base_cast["max"] - base_cast["min"]
+        rays_ok = max(1, P - base["n_bad_rays"])
+        say("%s: %d triangles, cell %.4f m, %d entries in %d cells, %d wide | smx_recon_raycast_mesh %.2f ms (%s); its cast + stats %.3f ms "
+            "(min %.3f, max %.3f: spread %.3f) | per ray %.1f layers, %.1f look-ups, %.1f pair tests" % (
+                what, n_in, base["cell_size_used"], base["n_entries"], base["n_cells"], base["n_wide"], float(np.median(calls[1:])),
+                " ".join("%s %.2f" % (k, base_ph[k]) for k in RAY_PHASES), base_cast["median"], base_cast["min"], base_cast["max"], tol,
+                base["n_layers"] / rays_ok, base["n_lookups"] / rays_ok, base["n_pair_tests"] / rays_ok))
+        settings = []
+        for occ in [-1, 0] + list(range(1, 2 + _lib.RAYSCENE_MAX_LOG2)):
+            try:
+                scene = rec.BuildRayScene(None, _DeviceArray(src, 3 * n_in), 0.0, occ)
+            except _lib.SmxError:
+                say("  occupancy %2d: does not fit 2^31 bits" % occ)
+                continue
+            build = []
+            for _ in range(args.reps):
+                rec.BuildRayScene(None, _DeviceArray(src, 3 * n_in), 0.0, occ, scene=scene)
+                build.append(scene.debug_timings())
+            bst = scene.stats
+            cst, casts, whole, cast_only = _lib.RaySceneCastStats(), [], [], []
+            for _ in range(args.reps + 1):
+                whole.append(timed(lambda: _lib.check(L.smx_rayscene_cast(scene._h, None, C.byref(prm), rays, C.c_uint32(P), hit, t, None, C.c_int32(1),
+                                                                           C.byref(cst))))[0])
+                ph = scene.debug_timings()
+                casts.append(ph["cast"] + ph["stats"])
+                cast_only.append(ph["cast"])
+            assert answer() == want, "the scene's bytes differ from smx_recon_raycast_mesh's"
+            cs = api.rayscene_stats_dict(cst)
+            assert cs["n_layers"] == base["n_layers"] and cs["n_pair_tests"] == base["n_pair_tests"] and cs["n_hit"] == base["n_hit"]
+            c = spread(casts[1:])
+            bph = {k: float(np.median([b[k] for b in build])) for k in SCENE_PHASES[:3]}
+            say("  occupancy %2d: k %2d, grid %.1f MiB with %d blocks set, scene %.1f MiB | build %s | cast + stats %.3f ms (min %.3f, max %.3f) = "
+                "%.2f x the call's (cast %.3f, stats %.3f); the whole cast call by device events %.3f ms | per ray %s" % (
+                    occ, bst["occupancy_log2"], bst["occupancy_bytes"] / 2.0 ** 20, bst["n_blocks_set"], bst["device_bytes"] / 2.0 ** 20,
+                    " ".join("%s %.2f" % (k, bph[k]) for k in SCENE_PHASES[:3]), c["median"], c["min"], c["max"],
+                    c["median"] / max(base_cast["median"], 1e-9), float(np.median(cast_only[1:])), c["median"] - float(np.median(cast_only[1:])),
+                    float(np.median(whole[1:])), ", ".join("%s %.1f" % (k[2:], cs[k] / rays_ok) for k in SCENE_WORK)))
+            settings.append({"occupancy": occ, "build_stats": bst, "build_phases_ms": bph, "cast_ms": c, "cast_ms_all": casts[1:], "cast_phase_ms": float(np.median(cast_only[1:])), "cast_call_ms": float(np.median(whole[1:])), "cast_call_ms_all": whole[1:], "cast_stats": cs})
+            scene.close()
+        out_rows.append({"input": what, "triangles_in": n_in, "rays": P, "reps": args.reps, "raycast_mesh_call_ms": float(np.median(calls[1:])),
+                         "raycast_mesh_phases_ms": base_ph, "raycast_mesh_cast_ms": base_cast, "spread_ms": tol, "raycast_mesh_stats": base,
+                         "settings": settings})
+    # what the contract asks of occupancy 0, on these numbers
+    def cast_of(row, pick):
+        c = [s_ for s_ in row["settings"] if pick(s_)]
+        return min(c, key=lambda s_: s_["build_stats"]["occupancy_log2"])["cast_ms"]["median"] if c else None
+    full, dec = out_rows
+    none_f, none_d = (cast_of(r, lambda s_: s_["occupancy"] == -1) for r in (full, dec))
+    grid_f, grid_d = (cast_of(r, lambda s_: s_["occupancy"] > 0) for r in (full, dec))
+    same = none_f <= full["raycast_mesh_cast_ms"]["median"] + full["spread_ms"] and none_d <= dec["raycast_mesh_cast_ms"]["median"] + dec["spread_ms"]
+    pays = grid_f is not None and grid_d is not None and grid_f < none_f - full["spread_ms"] and grid_d <= none_d + dec["spread_ms"]
+    say("a scene cast without a grid costs no more than the call's cast + stats within the spread: %s (full %.3f vs %.3f + %.3f, decimated %.3f vs "
+        "%.3f + %.3f)" % (same, none_f, full["raycast_mesh_cast_ms"]["median"], full["spread_ms"], none_d, dec["raycast_mesh_cast_ms"]["median"],
+                          dec["spread_ms"]))
+    say("the smallest grid that fits pays (faster than none on the full mesh by more than the spread, not slower beyond it on the decimated): %s "
+        "(full %s vs %.3f, decimated %s vs %.3f)" % (pays, "%.3f" % grid_f if grid_f is not None else "-", none_f, "%.3f" % grid_d if grid_d is not None else "-", none_d))
+    res = {"metric": "rayscene_cast_ms", "slots": q.n, "live": q.live, "rows": out_rows, "no_grid_within_spread": bool(same), "grid_pays": bool(pays)}
+    with open(args.json or os.path.join(ROOT, "profiles", "rayscene_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "rayscene_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    q.nn.close()
+
+
+class _DeviceArray:
+    """A CUDABuffer's first 32-bit `count` elements in the shape api.BuildRayScene takes a device tensor in."""
+    is_cuda = True
+
+    def __init__(self, buf, count):
+        self._address, self._count = buf.ToCUDA().address, int(count)
+
+    def data_ptr(self):
+        return self._address
+
+    def is_contiguous(self):
+        return True
+
+    def element_size(self):
+        return 4
+
+    def numel(self):
+        return self._count
+
+    @property
+    def device(self):
+        return torch.device("cuda", torch.cuda.current_device())
 
 
 def main():
@@ -902,4 +1054,4 @@ def main():
 
 
 if __name__ == "__main__":
-    raycast_main() if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

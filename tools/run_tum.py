@@ -7,7 +7,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
-                              [--mesh_eval METRES] [--mesh_eval_rays]
+                              [--mesh_eval METRES] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -198,6 +198,9 @@ def parse_args(argv=None):
                     help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
                          "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
                          "mean and rms of |hit range - true range|: accuracy and completeness along the sensor's own rays")
+    ap.add_argument("--mesh_eval_rays_frames", type=int, default=0, metavar="N",
+                    help="with --synthetic N --mesh: build one ray-casting scene (smx_rayscene) of the final mesh and cast the rays of "
+                         "--mesh_eval_rays for each of the last N integrated frames against it: one line per frame and a total")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -250,20 +253,25 @@ def parse_args(argv=None):
             ap.error("--mesh_eval needs a distance within 0.001 .. 16 metres")
     if args.mesh_eval_rays and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_rays needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
+    if args.mesh_eval_rays_frames < 0:
+        ap.error("--mesh_eval_rays_frames needs a frame count >= 0")
+    if args.mesh_eval_rays_frames and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
+        ap.error("--mesh_eval_rays_frames needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
     return args
 
 
-def format_ray_eval(hit, t, d, frame):
-    """The line of --mesh_eval_rays: rays to the true surface points (direction d = point - camera, so t = 1 at the truth)."""
+def format_ray_eval(hit, t, d, frame, head="surface error along the rays"):
+    """The line of --mesh_eval_rays: rays to the true surface points (direction d = point - camera, so t = 1 at the truth).
+    --mesh_eval_rays_frames prints the same figures per frame under the head "scene rays"."""
     has = np.asarray(hit) != np.uint32(0xFFFFFFFF)
     rng = np.linalg.norm(np.asarray(d, np.float64), axis=1)
     err = np.abs(np.asarray(t, np.float64)[has] * rng[has] - rng[has])
     if not has.size or not has.any():
-        return "surface error along the rays of frame %d: 0 of %d rays hit the mesh" % (frame, has.size)
-    return "surface error along the rays of frame %d: %d of %d rays hit the mesh (%.1f %%): mean %.2f mm, rms %.2f mm" % (
-        frame, int(has.sum()), has.size, 100.0 * has.mean(), 1e3 * err.mean(), 1e3 * np.sqrt((err * err).mean()))
+        return "%s of frame %d: 0 of %d rays hit the mesh" % (head, frame, has.size)
+    return "%s of frame %d: %d of %d rays hit the mesh (%.1f %%): mean %.2f mm, rms %.2f mm" % (
+        head, frame, int(has.sum()), has.size, 100.0 * has.mean(), 1e3 * err.mean(), 1e3 * np.sqrt((err * err).mean()))
 
 
 def main():
@@ -437,6 +445,23 @@ def main():
         d = truth - centre[None, :]
         hit, t, rstats = meshing.cast_rays(rec, triangles, np.broadcast_to(centre, d.shape), d, 0.0, 2.0)
         print(format_ray_eval(hit, t, d, last))
+    if args.mesh_eval_rays_frames:
+        from surfelmeshing_amd import meshing
+        half_ = args.outlier_filtering_frame_count // 2
+        last = n - half_ - 1
+        frames = [f for f in range(last - args.mesh_eval_rays_frames + 1, last + 1) if f >= args.start_frame + half_]
+        t1 = time.time()
+        n_hit = n_rays = 0
+        with meshing.build_ray_scene(rec, triangles) as scene:
+            built = time.time()
+            for f in frames:
+                centre = s.pose64(f)[1].astype(np.float32)
+                d = s.surface_points(f, 8) - centre[None, :]
+                hit, t, _ = meshing.cast_rays(rec, triangles, np.broadcast_to(centre, d.shape), d, 0.0, 2.0, scene=scene)
+                print(format_ray_eval(hit, t, d, f, "scene rays"))
+                n_hit, n_rays = n_hit + int(np.sum(hit != np.uint32(0xFFFFFFFF))), n_rays + hit.size
+        print("scene rays of %d frames: %d of %d rays hit the mesh; one scene of %d triangles built in %.1f ms, cast in %.1f ms" % (
+            len(frames), n_hit, n_rays, triangles.shape[0], 1e3 * (built - t1), 1e3 * (time.time() - built)))
     if args.render_dir and args.render_overview and args.render_source == "mesh":      # (the final mesh, decimated if asked)
         write_render(args, rec, cam, overview_pose(rec), n, "render_overview.png", triangles)
     if args.export_mesh:
