@@ -289,8 +289,6 @@ k_cc_write(const uint32_t* __restrict__ tri_in, uint32_t n_in, const uint32_t* _
   }
 }
 
-inline unsigned blocks_for(uint32_t n) { return (unsigned)div_up(n, kBlock); }
-
 }  // namespace
 }  // namespace smx
 

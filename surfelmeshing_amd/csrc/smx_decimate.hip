@@ -188,8 +188,6 @@ k_dec_emit(uint32_t m, const uint32_t* __restrict__ vals, const DecTri* __restri
   out[3 * (size_t)j] = c.p; out[3 * (size_t)j + 1] = c.a; out[3 * (size_t)j + 2] = c.b;
 }
 
-inline unsigned blocks_for(uint32_t n) { return (unsigned)div_up(n, kBlock); }
-
 }  // namespace
 }  // namespace smx
 

@@ -1,13 +1,9 @@
 // smx_distance.hip -- the kernels of smx_recon_mesh_distance (gfx950): for each of many points the closest point on a triangle
 // array over the surfel map, exactly the minimum over all triangles (the contract is in include/smx.h, its
-// arithmetic, the cell functions and the table operations in smx_distance.hpp).
+// distance arithmetic in smx_distance.hpp, the cell functions and the table operations in smx_trigrid.hpp).
 //
-//   mark:   k_dist_classify (a lane per triangle: range check, step 1's classes, the extents summed per wavefront in fixed
-//           point) -> k_dist_cell (one lane: c) -> k_dist_mark (a lane per triangle of R: its box, the entry count or the wide
-//           list by ballot compaction, entries counted per workgroup) -> enqueue_segment_scan
-//   index:  k_dist_entries ((cell key, t) per cell of every box) -> the stable radix sort of smx_nn.hip -> k_dist_records (the
-//           packed corner records in the sorted order, and the wide list's) -> k_dist_table (the head and the tail of every
-//           run add its bounds to the cell's entry of an open-addressing table)
+//   mark:   tg_enqueue_mark of smx_trigrid.hip with the boxes as they are and c >= 1.125 max_distance
+//   index:  tg_enqueue_index of smx_trigrid.hip, its sort buffers sized for the points' keys too
 //   query:  k_dist_point_keys -> the same sort -> k_dist_query (a workgroup per tile of 256 points in cell order = a run of
 //           occupied query cells: per cell 27 look-ups, the neighbour cells' packed records staged in LDS in chunks, the lanes
 //           dealt out as walkers over the staged records with one 64-bit key each and an integer LDS minimum per point; the
@@ -19,7 +15,7 @@
 // maximum; c itself may depend on the order of nothing either (an integer sum), though the result would not care.
 //
 // smx_recon_mesh_distance itself is at the end of the file: it owns the order of the phases, the workspace (DistanceWork,
-// smx_distance.hpp) and the two reads of the counters.
+// smx_distance.hpp) and the second read of the counters (the first is tg_read_counts).
 #include <cmath>
 
 #include "smx_recon_state.hpp"
@@ -32,154 +28,8 @@ namespace {
 constexpr int kDBlock = kDistBlock;
 constexpr unsigned long long kDistBadCell = 0x7FFFFFFFFFFFFFFFull;   // the sort key of a BAD point: behind every cell
 
-struct DistDeviceTable {
-  DistCell* e;
-  __device__ __forceinline__ unsigned long long key(uint32_t h) const { return e[h].key; }
-  __device__ __forceinline__ unsigned long long value(uint32_t h) const { return e[h].value; }
-  __device__ __forceinline__ unsigned long long claim(uint32_t h, unsigned long long expected, unsigned long long desired) const {
-    return atomicCAS(&e[h].key, expected, desired);
-  }
-  __device__ __forceinline__ void bump(uint32_t h, unsigned long long inc) const { atomicAdd(&e[h].value, inc); }
-};
-
-struct DistDeviceRecs {
-  const DistRec* r;
-  __device__ __forceinline__ void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* t) const {
-    const DistRec x = r[j];
-    *A = DistVec{x.a.x, x.a.y, x.a.z}; *B = DistVec{x.b.x, x.b.y, x.b.z}; *C = DistVec{x.c.x, x.c.y, x.c.z};
-    *t = __float_as_uint(x.a.w);
-  }
-};
-
-// one atomic per wavefront: the number of its lanes with `pred`
-__device__ __forceinline__ void dist_wave_count(uint32_t* counter, bool pred) {
-  const unsigned long long m = __ballot(pred);
-  if (m != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)m) - 1)) atomicAdd(counter, (uint32_t)__popcll(m));
-}
-
-__device__ __forceinline__ DistVec dist_pos(const DistMap& map, uint32_t i) {
-  const float4 s = map.smooth[(size_t)i * map.smooth_stride];
-  return DistVec{s.x, s.y, s.z};
-}
-__device__ __forceinline__ bool dist_live(const DistMap& map, uint32_t i, const DistVec& p) {
-  return dec_live(p.x, p.y, p.z, map.normal[(size_t)i * map.normal_stride].w);
-}
-__device__ __forceinline__ float dist_cell_of(const uint32_t* cnt) { return __uint_as_float(cnt[kDistCellBits]); }
-
-// mark[t] = 1 for a triangle of R, else 0.  (A triangle with an index out of range reads nothing; the call is refused.)
-__global__ void __launch_bounds__(kDBlock)
-k_dist_classify(DistMap map, const uint32_t* __restrict__ tri, uint32_t n_in, uint32_t* __restrict__ mark, uint32_t* __restrict__ cnt) {
-  const uint32_t t = blockIdx.x * kDBlock + threadIdx.x;
-  uint32_t cls = 0xFFu;
-  unsigned long long extent = 0;
-  bool bad_index = false;
-  if (t < n_in) {
-    const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-    if (i0 >= map.n || i1 >= map.n || i2 >= map.n) {
-      bad_index = true;
-    } else {
-      const DistVec a = dist_pos(map, i0), b = dist_pos(map, i1), c = dist_pos(map, i2);
-      cls = dist_classify(i0, i1, i2, dist_live(map, i0, a), dist_live(map, i1, b), dist_live(map, i2, c), a, b, c);
-      if (cls == kDistInR) extent = (unsigned long long)(dist_extent(a, b, c) * 1048576.0f);     // (at most 128 m: 2^27)
-    }
-    mark[t] = cls == kDistInR ? 1u : 0u;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) extent += __shfl_xor(extent, off);
-  if ((threadIdx.x & 63) == 0 && extent != 0) atomicAdd(reinterpret_cast<unsigned long long*>(cnt + kDistExtentLo), extent);
-  if (__ballot(bad_index) != 0 && (threadIdx.x & 63) == 0) atomicOr(&cnt[kDistError], 1u);     // (one per wavefront)
-  dist_wave_count(&cnt[kDistNotLive], cls == kDistDropNotLive);
-  dist_wave_count(&cnt[kDistRepeated], cls == kDistDropRepeated);
-  dist_wave_count(&cnt[kDistRange], cls == kDistDropRange);
-  dist_wave_count(&cnt[kDistInRCount], cls == kDistInR);
-}
-
-__global__ void k_dist_cell(float cell_size, float max_distance, uint32_t* cnt) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  float given = cell_size;
-  if (!(cell_size > 0.0f)) {
-    const unsigned long long sum = *reinterpret_cast<const unsigned long long*>(cnt + kDistExtentLo);
-    const uint32_t r = cnt[kDistInRCount];
-    given = r != 0 ? (float)((double)sum / (double)r * (1.0 / 1048576.0)) : 0.0f;
-  }
-  cnt[kDistCellBits] = __float_as_uint(dist_cell_size(given, max_distance));
-}
-
-__device__ __forceinline__ DistBox dist_box_of(const DistMap& map, const uint32_t* tri, uint32_t t, float cell) {
-  const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-  return dist_box(dist_pos(map, i0), dist_pos(map, i1), dist_pos(map, i2), cell);
-}
-
-// mark[t]: 1 -> the entry count of the triangle or kDistWide.  wide_t has n_in entries.
-__global__ void __launch_bounds__(kDBlock)
-k_dist_mark(DistMap map, const uint32_t* __restrict__ tri, uint32_t n_in, uint32_t* __restrict__ mark, uint32_t* __restrict__ wide_t,
-            uint32_t* __restrict__ block_sums, uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t wave_tot[kDBlock / 64];
-  const uint32_t t = blockIdx.x * kDBlock + threadIdx.x;
-  const float cell = dist_cell_of(cnt);
-  uint32_t word = 0;
-  if (t < n_in && mark[t] != 0) {
-    word = dist_mark(dist_box_of(map, tri, t, cell));
-    mark[t] = word;
-  }
-  const bool wide = word == kDistWide;
-  const unsigned long long m = __ballot(wide);
-  if (m != 0) {
-    const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)(__ffsll((long long)m) - 1);
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&cnt[kDistNWide], (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, (int)leader);
-    if (wide) wide_t[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = t;      // (at most n_in wide triangles in all)
-  }
-  uint32_t total;
-  (void)block_excl_scan(wide ? 0u : word, wave_tot, total);
-  if (threadIdx.x == 0) {
-    block_sums[blockIdx.x] = total;
-    if (total != 0) atomicAdd(reinterpret_cast<unsigned long long*>(cnt + kDistEntries64Lo), (unsigned long long)total);
-  }
-}
-
-__global__ void __launch_bounds__(kDBlock)
-k_dist_entries(DistMap map, const uint32_t* __restrict__ tri, uint32_t n_in, const uint32_t* __restrict__ mark,
-               const uint32_t* __restrict__ block_off, const uint32_t* __restrict__ cnt, uint32_t n_entries,
-               unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
-  __shared__ uint32_t wave_tot[kDBlock / 64];
-  const uint32_t t = blockIdx.x * kDBlock + threadIdx.x;
-  uint32_t count = t < n_in ? mark[t] : 0u;
-  if (count == kDistWide) count = 0;
-  uint32_t total;
-  const uint32_t off = block_off[blockIdx.x] + block_excl_scan(count, wave_tot, total);
-  if (count == 0 || off + count > n_entries) return;         // (the second never holds: off + count <= the scan's total)
-  const DistBox box = dist_box_of(map, tri, t, dist_cell_of(cnt));
-  for (uint32_t j = 0; j < count; ++j) { keys[off + j] = dist_box_key(box, j); vals[off + j] = t; }
-}
-
-// recs[j] = the corners of triangle list[j]
-__global__ void __launch_bounds__(kDBlock)
-k_dist_records(DistMap map, const uint32_t* __restrict__ tri, const uint32_t* __restrict__ list, uint32_t m, DistRec* __restrict__ recs) {
-  const uint32_t j = blockIdx.x * kDBlock + threadIdx.x;
-  if (j >= m) return;
-  const uint32_t t = list[j];
-  const DistVec a = dist_pos(map, tri[3 * (size_t)t]), b = dist_pos(map, tri[3 * (size_t)t + 1]), c = dist_pos(map, tri[3 * (size_t)t + 2]);
-  DistRec r;
-  r.a = make_float4(a.x, a.y, a.z, __uint_as_float(t)); r.b = make_float4(b.x, b.y, b.z, 0.0f); r.c = make_float4(c.x, c.y, c.z, 0.0f);
-  recs[j] = r;
-}
-
-// the table is all zeros before: empty
-__global__ void __launch_bounds__(kDBlock)
-k_dist_table(const unsigned long long* __restrict__ keys, uint32_t n_entries, DistCell* table, uint32_t mask, uint32_t* __restrict__ cnt) {
-  const uint32_t j = blockIdx.x * kDBlock + threadIdx.x;
-  bool head = false;
-  if (j < n_entries) {
-    DistDeviceTable tab{table};
-    head = dist_table_entry(tab, mask, keys, n_entries, j);
-  }
-  dist_wave_count(&cnt[kDistCells], head);
-}
-
-__device__ __forceinline__ DistVec dist_point(const float* points, uint32_t p) {
-  return DistVec{points[3 * (size_t)p], points[3 * (size_t)p + 1], points[3 * (size_t)p + 2]};
+__device__ __forceinline__ TgVec dist_point(const float* points, uint32_t p) {
+  return TgVec{points[3 * (size_t)p], points[3 * (size_t)p + 1], points[3 * (size_t)p + 2]};
 }
 
 // a BAD point gets the largest 63-bit key: it sorts behind every cell, and its lanes walk nothing
@@ -188,9 +38,9 @@ k_dist_point_keys(const float* __restrict__ points, uint32_t n_points, const uin
                   uint32_t* __restrict__ vals) {
   const uint32_t p = blockIdx.x * kDBlock + threadIdx.x;
   if (p >= n_points) return;
-  const DistVec P = dist_point(points, p);
-  const float cell = dist_cell_of(cnt);
-  keys[p] = dist_point_ok(P) ? dec_cell_key(dist_cell(P.x, cell), dist_cell(P.y, cell), dist_cell(P.z, cell)) : kDistBadCell;
+  const TgVec P = dist_point(points, p);
+  const float cell = tg_cell_of(cnt);
+  keys[p] = tg_point_ok(P) ? dec_cell_key(tg_cell(P.x, cell), tg_cell(P.y, cell), tg_cell(P.z, cell)) : kDistBadCell;
   vals[p] = p;
 }
 
@@ -199,9 +49,9 @@ constexpr uint32_t kDistChunk = 2 * kDBlock;                                // r
 // the staged chunk: three 16-byte reads per record, the same address for the lanes that share a record (a broadcast)
 struct DistLdsRecs {
   const float4 *a, *b, *c;
-  __device__ __forceinline__ void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* t) const {
+  __device__ __forceinline__ void load(uint32_t j, TgVec* A, TgVec* B, TgVec* C, uint32_t* t) const {
     const float4 x = a[j], y = b[j], z = c[j];
-    *A = DistVec{x.x, x.y, x.z}; *B = DistVec{y.x, y.y, y.z}; *C = DistVec{z.x, z.y, z.z};
+    *A = TgVec{x.x, x.y, x.z}; *B = TgVec{y.x, y.y, y.z}; *C = TgVec{z.x, z.y, z.z};
     *t = __float_as_uint(x.w);
   }
 };
@@ -220,38 +70,38 @@ __device__ __forceinline__ void dist_stage_and_walk(const DistStage& st, const S
   const uint32_t tid = threadIdx.x;
   const uint32_t walkers = na != 0 ? kDBlock / na : 0u, mine = na != 0 ? tid % na : 0u, q = na != 0 ? tid / na : 0u;
   const bool walking = na != 0 && q < walkers;
-  DistVec P{0.0f, 0.0f, 0.0f};
-  if (walking) P = DistVec{st.px[pos + mine], st.py[pos + mine], st.pz[pos + mine]};
-  unsigned long long best = kDistNone;
+  TgVec P{0.0f, 0.0f, 0.0f};
+  if (walking) P = TgVec{st.px[pos + mine], st.py[pos + mine], st.pz[pos + mine]};
+  unsigned long long best = kTgNone;
   for (uint32_t base = 0; base < total; base += kDistChunk) {
     const uint32_t m = total - base < kDistChunk ? total - base : kDistChunk;
     const bool h0 = tid < m, h1 = tid + kDBlock < m;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 a0 = zero, b0 = zero, c0 = zero, a1 = zero, b1 = zero, c1 = zero;
-    if (h0) { const DistRec* r = src(base + tid); a0 = r->a; b0 = r->b; c0 = r->c; }
-    if (h1) { const DistRec* r = src(base + tid + kDBlock); a1 = r->a; b1 = r->b; c1 = r->c; }
+    if (h0) { const TgRec* r = src(base + tid); a0 = r->a; b0 = r->b; c0 = r->c; }
+    if (h1) { const TgRec* r = src(base + tid + kDBlock); a1 = r->a; b1 = r->b; c1 = r->c; }
     if (h0) { st.a[tid] = a0; st.b[tid] = b0; st.c[tid] = c0; }
     if (h1) { st.a[tid + kDBlock] = a1; st.b[tid + kDBlock] = b1; st.c[tid + kDBlock] = c1; }
     __syncthreads();
     if (walking) best = dist_walk(DistLdsRecs{st.a, st.b, st.c}, q, m, P, max2, best, walkers);
     __syncthreads();
   }
-  if (walking && best != kDistNone) atomicMin(&st.best[pos + mine], best);
+  if (walking && best != kTgNone) atomicMin(&st.best[pos + mine], best);
 }
 
 // the 27 neighbour runs of a cell as one sequence of records
 struct DistCellSrc {
-  const DistRec* recs;
+  const TgRec* recs;
   const uint32_t *first, *off;        // LDS: [27] first record of the run, [28] offsets of the runs in the sequence
-  __device__ __forceinline__ const DistRec* operator()(uint32_t g) const {
+  __device__ __forceinline__ const TgRec* operator()(uint32_t g) const {
     uint32_t k = 0;
     while (k < 26 && g >= off[k + 1]) ++k;
     return recs + first[k] + (g - off[k]);
   }
 };
 struct DistWideSrc {
-  const DistRec* recs;
-  __device__ __forceinline__ const DistRec* operator()(uint32_t g) const { return recs + g; }
+  const TgRec* recs;
+  __device__ __forceinline__ const TgRec* operator()(uint32_t g) const { return recs + g; }
 };
 
 // A workgroup per tile of 256 points in cell order = a run of occupied query cells.  Cell after cell: 27 lanes look the
@@ -259,9 +109,9 @@ struct DistWideSrc {
 // points of that cell; the wide list is staged the same way behind the cells, for all points of the tile.  (A cell whose points
 // straddle two tiles is staged by both.)  Then every lane writes the answer of its own point to the point's place in the input.
 __global__ void __launch_bounds__(kDBlock)
-k_dist_query(DistMap map, const uint32_t* __restrict__ tri, const float* __restrict__ points, uint32_t n_points,
-             const unsigned long long* __restrict__ cell_keys, const uint32_t* __restrict__ order, const DistCell* __restrict__ table,
-             uint32_t mask, const DistRec* __restrict__ recs, const DistRec* __restrict__ wide_recs, uint32_t n_wide,
+k_dist_query(TgMap map, const uint32_t* __restrict__ tri, const float* __restrict__ points, uint32_t n_points,
+             const unsigned long long* __restrict__ cell_keys, const uint32_t* __restrict__ order, const TgCell* __restrict__ table,
+             uint32_t mask, const TgRec* __restrict__ recs, const TgRec* __restrict__ wide_recs, uint32_t n_wide,
              const uint32_t* __restrict__ cnt, float max2, int signed_distance, uint32_t* __restrict__ nearest, float* __restrict__ distance,
              float* __restrict__ closest, unsigned long long* __restrict__ best_out) {
   __shared__ float4 s_a[kDistChunk], s_b[kDistChunk], s_c[kDistChunk];
@@ -271,23 +121,23 @@ k_dist_query(DistMap map, const uint32_t* __restrict__ tri, const float* __restr
   const uint32_t tid = threadIdx.x, j = blockIdx.x * kDBlock + tid;
   const bool in = j < n_points;
   const uint32_t p = in ? order[j] : 0u;
-  const DistVec P = in ? dist_point(points, p) : DistVec{0.0f, 0.0f, 0.0f};
+  const TgVec P = in ? dist_point(points, p) : TgVec{0.0f, 0.0f, 0.0f};
   const unsigned long long my_cell = in ? cell_keys[j] : kDistBadCell;
-  s_key[tid] = my_cell; s_best[tid] = kDistNone;
+  s_key[tid] = my_cell; s_best[tid] = kTgNone;
   s_px[tid] = P.x; s_py[tid] = P.y; s_pz[tid] = P.z;
   // the keys ascend, so the good points of the tile are its first n_good lanes
   const uint32_t n_good = (uint32_t)__syncthreads_count(my_cell != kDistBadCell);
-  const float cell = dist_cell_of(cnt);
+  const float cell = tg_cell_of(cnt);
   const DistStage st{s_a, s_b, s_c, s_best, s_px, s_py, s_pz};
   uint32_t pos = 0;
   while (pos < n_good) {
     const unsigned long long cur = s_key[pos];
     const uint32_t na = (uint32_t)__syncthreads_count(my_cell == cur);       // (the lanes [pos, pos + na))
     if (tid < 27) {
-      const DistDeviceTable tab{const_cast<DistCell*>(table)};
+      const TgDeviceTable tab{const_cast<TgCell*>(table)};
       uint32_t first = 0, end = 0;
-      const bool found = dist_table_find(tab, mask, dist_neighbour_key(dist_cell(s_px[pos], cell), dist_cell(s_py[pos], cell),
-                                                                      dist_cell(s_pz[pos], cell), tid), &first, &end);
+      const bool found = tg_table_find(tab, mask, dist_neighbour_key(tg_cell(s_px[pos], cell), tg_cell(s_py[pos], cell),
+                                                                      tg_cell(s_pz[pos], cell), tid), &first, &end);
       s_first[tid] = first; s_count[tid] = found ? end - first : 0u;
     }
     __syncthreads();
@@ -306,13 +156,13 @@ k_dist_query(DistMap map, const uint32_t* __restrict__ tri, const float* __restr
   const unsigned long long key = s_best[tid];
   uint32_t t = kInvalid;
   float d = __builtin_inff();
-  DistVec Q{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
-  if (key != kDistNone) {
+  TgVec Q{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+  if (key != kTgNone) {
     t = (uint32_t)key;
-    const DistVec A = dist_pos(map, tri[3 * (size_t)t]), B = dist_pos(map, tri[3 * (size_t)t + 1]), C = dist_pos(map, tri[3 * (size_t)t + 2]);
+    const TgVec A = tg_pos(map, tri[3 * (size_t)t]), B = tg_pos(map, tri[3 * (size_t)t + 1]), C = tg_pos(map, tri[3 * (size_t)t + 2]);
     uint32_t region;
     Q = dist_closest(P, A, B, C, &region);
-    d = sqrtf(dist_key_dist2(key));
+    d = sqrtf(tg_key_float(key));
     if (signed_distance && dist_negative(P, Q, A, B, C)) d = -d;
   }
   best_out[p] = key;
@@ -328,26 +178,18 @@ k_dist_stats(const float* __restrict__ points, uint32_t n_points, const unsigned
   bool bad = false, matched = false;
   uint32_t bits = 0, bin = kDistBins;
   if (p < n_points) {
-    bad = !dist_point_ok(dist_point(points, p));
+    bad = !tg_point_ok(dist_point(points, p));
     const unsigned long long key = best[p];
-    matched = key != kDistNone;
-    if (matched) { bits = (uint32_t)(key >> 32); bin = dist_bin(sqrtf(dist_key_dist2(key)), max_distance); }
+    matched = key != kTgNone;
+    if (matched) { bits = (uint32_t)(key >> 32); bin = dist_bin(sqrtf(tg_key_float(key)), max_distance); }
   }
-  dist_wave_count(&cnt[kDistBadPoints], bad);
-  dist_wave_count(&cnt[kDistMatched], matched);
+  wave_count(&cnt[kDistBadPoints], bad);
+  wave_count(&cnt[kDistMatched], matched);
   if (__ballot(matched) == 0) return;                        // (uniform over the wavefront)
-  for (uint32_t b = 0; b < kDistBins; ++b) dist_wave_count(&cnt[kDistHist + b], bin == b);
+  for (uint32_t b = 0; b < kDistBins; ++b) wave_count(&cnt[kDistHist + b], bin == b);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)bits, off); bits = o > bits ? o : bits; }
   if ((threadIdx.x & 63) == 0) atomicMax(&cnt[kDistMaxBits], bits);    // (bits of non-negative floats order as the floats do)
-}
-
-inline unsigned dist_blocks(uint32_t n) { return (unsigned)div_up(n, kDBlock); }
-inline bool dist_finite_f(float v) { return v - v == 0.0f; }
-inline bool dist_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 }  // namespace
@@ -367,8 +209,8 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
                             const float* points, uint32_t n_points, uint32_t* nearest, float* distance, float* closest,
                             int32_t on_device, smx_distance_stats* stats) {
   SMX_CHECK_ARG(r != nullptr && p != nullptr);
-  SMX_CHECK_ARG(dist_finite_f(p->max_distance) && p->max_distance >= 1e-3f && p->max_distance <= 16.0f);
-  SMX_CHECK_ARG(dist_finite_f(p->cell_size) && p->cell_size >= 0.0f);
+  SMX_CHECK_ARG(finite_f(p->max_distance) && p->max_distance >= 1e-3f && p->max_distance <= 16.0f);
+  SMX_CHECK_ARG(finite_f(p->cell_size) && p->cell_size >= 0.0f);
   SMX_CHECK_ARG(p->signed_distance == 0 || p->signed_distance == 1);
   SMX_CHECK_ARG(n_in <= (1u << 28) && n_points <= (1u << 28));
   SMX_CHECK_ARG(triangles != nullptr || n_in == 0);
@@ -380,7 +222,7 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
     const size_t out_bytes[3] = {(size_t)n_points * 4, (size_t)n_points * 4, (size_t)n_points * 12};
     for (int i = 0; i < 2; ++i)
       for (int o = 0; o < 3; ++o)
-        if (dist_overlap(ins[i], in_bytes[i], outs[o], out_bytes[o])) {
+        if (ranges_overlap(ins[i], in_bytes[i], outs[o], out_bytes[o])) {
           set_error("an output of smx_recon_mesh_distance overlaps %s", i == 0 ? "triangles" : "points");
           return SMX_ERR_INVALID_ARGUMENT;
         }
@@ -400,12 +242,9 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
   };
 
   // ---- workspace of the first phase; the inputs on the device; the outputs' staging
-  const int nb = div_up(n_in, kDistBlock);
   const bool dev = on_device != 0;
   if (!w.counters.get()) SMX_CALL(w.counters.alloc(kDistWords, false));
-  SMX_CALL(w.mark.reserve(n_in));
-  SMX_CALL(w.blocks.reserve((size_t)nb));
-  SMX_CALL(w.wide_t.reserve(n_in));
+  SMX_CALL(w.grid.reserve_mark(n_in));
   SMX_CALL(w.best.reserve(n_points));
   const uint32_t* din = nullptr;
   const float* dpts = nullptr;
@@ -423,65 +262,31 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
   uint32_t* cnt = w.counters.get();
   SMX_HIP(hipMemsetAsync(cnt, 0, kDistWords * sizeof(uint32_t), st));
   uint32_t h[kDistWords];
-  auto read_counters = [&]() -> int {
-    SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-    return SMX_OK;
-  };
 
   // ---- mark
   const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
-  const DistMap map{sv.p, sv.stride, nv.p, nv.stride, n};
-  const dim3 b(kDistBlock), g_in(nb);
-  if (n_in > 0) hipLaunchKernelGGL(k_dist_classify, g_in, b, 0, st, map, din, n_in, w.mark.get(), cnt);
-  hipLaunchKernelGGL(k_dist_cell, dim3(1), dim3(64), 0, st, p->cell_size, p->max_distance, cnt);
-  if (n_in > 0) {
-    hipLaunchKernelGGL(k_dist_mark, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.wide_t.get(), w.blocks.get(), cnt);
-    enqueue_segment_scan(st, w.blocks.get(), nb, cnt + kDistEntries);
-  }
-  SMX_LAUNCH_CHECK();
+  const TgMap map{sv.p, sv.stride, nv.p, nv.stride, n};
+  const dim3 b(kDistBlock);
+  SMX_CALL(tg_enqueue_mark(w.grid, TgBoxes::kExact, map, din, n_in, p->cell_size, kDistMargin * p->max_distance, cnt, st));
   SMX_CALL(w.stamps.mark(st));
-  SMX_CALL(read_counters());
-  if (h[kDistError] != 0) {
-    set_error("triangles holds an index >= the %u slots of the map", n);
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-  if ((((unsigned long long)h[kDistEntries64Hi] << 32) | h[kDistEntries64Lo]) > (1ull << 30)) {
-    set_error("more than 2^30 (cell, triangle) entries: choose a larger cell_size");
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-  const uint32_t E = h[kDistEntries], Wd = h[kDistNWide];
+  uint32_t E = 0, Wd = 0;
+  if (const int rc = tg_read_counts(cnt, h, kDistWords, n, st, &E, &Wd)) return finish(rc);
 
-  // ---- index (every allocation of the call lies before the first write to an output)
-  const uint32_t sort_n = E > n_points ? E : n_points;
-  const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(sort_n)); SMX_CALL(w.vals[k].reserve(sort_n)); }
-  SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(sort_n)));
-  SMX_CALL(w.recs.reserve((size_t)E * 12));
-  SMX_CALL(w.wide_recs.reserve((size_t)Wd * 12));
-  SMX_CALL(w.table.reserve((size_t)2 * entries));
-  DistCell* table = reinterpret_cast<DistCell*>(w.table.get());
-  DistRec* recs = reinterpret_cast<DistRec*>(w.recs.get());
-  DistRec* wide_recs = reinterpret_cast<DistRec*>(w.wide_recs.get());
-  SMX_HIP(hipMemsetAsync(table, 0, (size_t)entries * sizeof(DistCell), st));
-  if (E > 0) {
-    hipLaunchKernelGGL(k_dist_entries, g_in, b, 0, st, map, din, n_in, w.mark.get(), w.blocks.get(), cnt, E, w.keys[0].get(), w.vals[0].get());
-    SMX_LAUNCH_CHECK();
-    const int cur = radix_sort(w.keys, w.vals, E, 63, w.hist.get(), st);
-    hipLaunchKernelGGL(k_dist_records, dim3(dist_blocks(E)), b, 0, st, map, din, w.vals[cur].get(), E, recs);
-    hipLaunchKernelGGL(k_dist_table, dim3(dist_blocks(E)), b, 0, st, w.keys[cur].get(), E, table, mask, cnt);
-  }
-  if (Wd > 0) hipLaunchKernelGGL(k_dist_records, dim3(dist_blocks(Wd)), b, 0, st, map, din, w.wide_t.get(), Wd, wide_recs);
-  SMX_LAUNCH_CHECK();
+  // ---- index (every allocation of the call lies before the first write to an output; the sort's buffers hold the points' keys too)
+  uint32_t mask = 0;
+  SMX_CALL(tg_enqueue_index(w.grid, TgBoxes::kExact, map, din, n_in, E, Wd, n_points, cnt, w.recs, w.wide_recs, w.table, &mask, nullptr, st));
+  const TgCell* table = reinterpret_cast<const TgCell*>(w.table.get());
+  const TgRec* recs = reinterpret_cast<const TgRec*>(w.recs.get());
+  const TgRec* wide_recs = reinterpret_cast<const TgRec*>(w.wide_recs.get());
   SMX_CALL(w.stamps.mark(st));
 
   // ---- query
   if (n_points > 0) {
-    const dim3 g_pts(dist_blocks(n_points));
-    hipLaunchKernelGGL(k_dist_point_keys, g_pts, b, 0, st, dpts, n_points, cnt, w.keys[0].get(), w.vals[0].get());
+    const dim3 g_pts(blocks_for(n_points));
+    hipLaunchKernelGGL(k_dist_point_keys, g_pts, b, 0, st, dpts, n_points, cnt, w.grid.keys[0].get(), w.grid.vals[0].get());
     SMX_LAUNCH_CHECK();
-    const int cur = radix_sort(w.keys, w.vals, n_points, 63, w.hist.get(), st);
-    hipLaunchKernelGGL(k_dist_query, g_pts, b, 0, st, map, din, dpts, n_points, w.keys[cur].get(), w.vals[cur].get(), table, mask, recs, wide_recs, Wd, cnt,
+    const int cur = radix_sort(w.grid.keys, w.grid.vals, n_points, 63, w.grid.hist.get(), st);
+    hipLaunchKernelGGL(k_dist_query, g_pts, b, 0, st, map, din, dpts, n_points, w.grid.keys[cur].get(), w.grid.vals[cur].get(), table, mask, recs, wide_recs, Wd, cnt,
                        p->max_distance * p->max_distance, (int)p->signed_distance, d_nearest, d_distance, d_closest, w.best.get());
     SMX_LAUNCH_CHECK();
   }
@@ -489,7 +294,7 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
 
   // ---- stats
   if (n_points > 0) {
-    hipLaunchKernelGGL(k_dist_stats, dim3(dist_blocks(n_points)), b, 0, st, dpts, n_points, w.best.get(), p->max_distance, cnt);
+    hipLaunchKernelGGL(k_dist_stats, dim3(blocks_for(n_points)), b, 0, st, dpts, n_points, w.best.get(), p->max_distance, cnt);
     SMX_LAUNCH_CHECK();
     if (!dev) {
       SMX_HIP(hipMemcpyAsync(nearest, d_nearest, (size_t)n_points * 4, hipMemcpyDeviceToHost, st));
@@ -497,13 +302,14 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
       if (closest) SMX_HIP(hipMemcpyAsync(closest, d_closest, (size_t)n_points * 12, hipMemcpyDeviceToHost, st));
     }
   }
-  SMX_CALL(read_counters());
+  SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
   if (stats) {
-    stats->n_not_live = h[kDistNotLive]; stats->n_repeated = h[kDistRepeated]; stats->n_out_of_range = h[kDistRange];
+    stats->n_not_live = h[kTgNotLive]; stats->n_repeated = h[kTgRepeated]; stats->n_out_of_range = h[kTgRange];
     stats->n_bad_points = h[kDistBadPoints]; stats->n_matched = h[kDistMatched]; stats->max_dist2_bits = h[kDistMaxBits];
     for (uint32_t k = 0; k < kDistBins; ++k) stats->histogram[k] = h[kDistHist + k];
-    stats->n_wide = Wd; stats->n_entries = E; stats->n_cells = h[kDistCells];
-    memcpy(&stats->cell_size_used, &h[kDistCellBits], sizeof(float));
+    stats->n_wide = Wd; stats->n_entries = E; stats->n_cells = h[kTgCells];
+    memcpy(&stats->cell_size_used, &h[kTgCellBits], sizeof(float));
   }
   SMX_CALL(w.stamps.mark(st));
   return finish(SMX_OK);

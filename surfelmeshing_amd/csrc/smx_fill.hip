@@ -253,10 +253,6 @@ k_fill_write(const uint32_t* __restrict__ tri_in, uint32_t n_in, const uint32_t*
   }
 }
 
-inline unsigned blocks_for(uint32_t n) { return (unsigned)div_up(n, kBlock); }
-
-inline bool finite_f(float v) { return v - v == 0.0f; }
-
 }  // namespace
 }  // namespace smx
 

@@ -2,9 +2,10 @@
 // occupancy bit grid in front of its cell table (the contract is in include/smx.h, the grid's arithmetic and the
 // filtered walk in smx_rayscene.hpp).
 //
-//   build:  ray_enqueue_mark and ray_enqueue_index of smx_raycast.hip, writing the records and the cell table into the scene's
-//           own buffers -> k_scene_occupancy (a lane per sorted entry; the head of a run sets its block's bit, one atomic per
-//           distinct bit of the wavefront) -> k_scene_popcount (the set bits, counted from the bits)
+//   build:  tg_enqueue_mark and tg_enqueue_index of smx_trigrid.hip as smx_recon_raycast_mesh calls them, writing
+//           the records and the cell table into the scene's own buffers -> k_scene_occupancy (a lane per sorted entry; the head
+//           of a run sets its block's bit, one atomic per distinct bit of the wavefront) -> k_scene_popcount (the set bits,
+//           counted from the bits)
 //   cast:   k_scene_cast (k_ray_cast's structure: a wavefront per ray, 64 layers per round, a ballot of the non-empty ones, the
 //           runs dealt to the lanes, a wave minimum of 64-bit keys; the bit test in front of both look-up sites; no read of the
 //           map: the lane that holds the winning key hands its (u, v, det) to lane 0) -> k_scene_stats
@@ -22,15 +23,8 @@ namespace {
 
 // occupancy 0: the smallest block that fits.  DESIGN.md 5m "Measured" holds the numbers behind this: on an MI355X the grid pays.
 constexpr bool kSceneAutoGrid = true;
-constexpr int kSceneBlocksWord = 30;                         // a free word of the kRay counters: the set bits of the grid
 
 struct SceneBox { int32_t lo[3], hi[3]; };
-
-__device__ __forceinline__ uint32_t scene_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
-  return v;
-}
 
 // bits is all zeros before.  At k > 0 the heads of one block lie near each other in the sorted order (z runs fastest in the
 // cell key), so a wavefront issues one atomic per distinct bit, and none where a plain read already sees the bit (a stale
@@ -61,31 +55,31 @@ __global__ void __launch_bounds__(kRayBlock)
 k_scene_popcount(const uint32_t* __restrict__ bits, uint32_t n_words, uint32_t* __restrict__ cnt) {
   uint32_t sum = 0;
   for (uint32_t i = blockIdx.x * kRayBlock + threadIdx.x; i < n_words; i += gridDim.x * kRayBlock) sum += (uint32_t)__popc(bits[i]);
-  sum = scene_wave_sum(sum);
-  if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(&cnt[kSceneBlocksWord], sum);
+  sum = wave_sum(sum);
+  if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(&cnt[kSceneBlocksSet], sum);
 }
 
 // A wavefront per ray, as k_ray_cast: everything that steers a loop is uniform over the wavefront; a lane's own state is its
 // layer's rectangle, one 64-bit key with what it came with, and five counts.  No LDS, no barrier, no read of the map.
 __global__ void __launch_bounds__(kRayBlock)
-k_scene_cast(const float* __restrict__ rays, uint32_t n_rays, const DistCell* __restrict__ table, uint32_t mask, const DistRec* __restrict__ recs,
-             const DistRec* __restrict__ wide_recs, uint32_t n_wide, uint32_t n_entries, SceneGrid grid, const uint32_t* __restrict__ bit_words,
+k_scene_cast(const float* __restrict__ rays, uint32_t n_rays, const TgCell* __restrict__ table, uint32_t mask, const TgRec* __restrict__ recs,
+             const TgRec* __restrict__ wide_recs, uint32_t n_wide, uint32_t n_entries, SceneGrid grid, const uint32_t* __restrict__ bit_words,
              float cell, SceneBox occ, float t_min, float t_max, int cull, uint32_t* __restrict__ hit, float* __restrict__ t_out,
              float* __restrict__ uv, unsigned long long* __restrict__ best_out, uint4* __restrict__ work_out) {
   const uint32_t lane = threadIdx.x & 63, p = blockIdx.x * kRayWaves + (threadIdx.x >> 6);
   if (p >= n_rays) return;                                   // (the whole wavefront)
-  DistVec O, D;
+  TgVec O, D;
   ray_load(rays, p, &O, &D);
   const bool bad = ray_bad(O, D);
-  unsigned long long best = kDistNone;
-  SceneKeep keep{kDistNone, 0.0f, 0.0f, 0.0f};
+  unsigned long long best = kTgNone;
+  SceneKeep keep{kTgNone, 0.0f, 0.0f, 0.0f};
   SceneWork work{0, 0, 0, 0, 0};
   if (!bad) {
-    best = ray_wave_min(scene_walk(RayDeviceRecs{wide_recs}, lane, n_wide, 64, O, D, t_min, t_max, cull, best, &keep, &work.tests));
+    best = wave_min(scene_walk(TgDeviceRecs{wide_recs}, lane, n_wide, 64, O, D, t_min, t_max, cull, best, &keep, &work.tests));
     if (n_entries != 0) {
       const RayAxes r = ray_axes(O, D, occ.lo[0], occ.lo[1], occ.lo[2], occ.hi[0], occ.hi[1], occ.hi[2], cell, t_min, t_max);
-      const RayDeviceTable tab{const_cast<DistCell*>(table)};
-      const RayDeviceRecs cell_recs{recs};
+      const TgDeviceTable tab{const_cast<TgCell*>(table)};
+      const TgDeviceRecs cell_recs{recs};
       const SceneBits bits{bit_words};
       bool stop = false;
       for (uint32_t base = 0; base < r.n_layers && !stop; base += 64) {
@@ -128,25 +122,25 @@ k_scene_cast(const float* __restrict__ rays, uint32_t n_rays, const DistCell* __
               best = scene_walk(cell_recs, f + lane, e, 64, O, D, t_min, t_max, cull, best, &keep, &work.tests);
             }
           }
-          best = ray_wave_min(best);
+          best = wave_min(best);
           if (ray_done(r, cell, best, mk + 1)) { stop = true; break; }
         }
       }
     }
   }
-  const uint32_t n_layers = scene_wave_sum(work.layers), n_bits = scene_wave_sum(work.bit_tests), n_lookups = scene_wave_sum(work.lookups),
-                 n_misses = scene_wave_sum(work.misses), n_tests = scene_wave_sum(work.tests);
+  const uint32_t n_layers = wave_sum(work.layers), n_bits = wave_sum(work.bit_tests), n_lookups = wave_sum(work.lookups),
+                 n_misses = wave_sum(work.misses), n_tests = wave_sum(work.tests);
   // the winner's (u, v, det): from the first lane whose own key is the minimum (it was strictly below that lane's best when it
   // was computed, so the lane kept it, and no smaller key came after)
-  const unsigned long long holders = __ballot(best != kDistNone && keep.own == best);
+  const unsigned long long holders = __ballot(best != kTgNone && keep.own == best);
   const int src = holders != 0 ? __ffsll((long long)holders) - 1 : 0;
   const float wu = __shfl(keep.u, src), wv = __shfl(keep.v, src), wdet = __shfl(keep.det, src);
   if (lane != 0) return;
   uint32_t i = kInvalid, flags = bad ? kRayFlagBad : 0u;
   float t = __builtin_inff(), u = __builtin_nanf(""), v = __builtin_nanf("");
-  if (best != kDistNone) {
+  if (best != kTgNone) {
     i = (uint32_t)best;
-    t = dist_key_dist2(best); u = wu; v = wv;
+    t = tg_key_float(best); u = wu; v = wv;
     flags |= kRayFlagHit | (wdet > 0.0f ? kRayFlagFront : 0u);
   }
   best_out[p] = best;
@@ -170,9 +164,9 @@ k_scene_stats(uint32_t n_rays, const unsigned long long* __restrict__ best, cons
     n_bad += (b.y & kRayFlagBad) != 0; n_hit += (b.y & kRayFlagHit) != 0; n_front += (b.y & kRayFlagFront) != 0;
     if (b.y & kRayFlagHit) { const uint32_t t_bits = (uint32_t)(best[p] >> 32); bits = t_bits > bits ? t_bits : bits; }
   }
-  layers = ray_wave_sum(layers); bit_tests = ray_wave_sum(bit_tests); lookups = ray_wave_sum(lookups); misses = ray_wave_sum(misses);
-  tests = ray_wave_sum(tests);
-  n_bad = scene_wave_sum(n_bad); n_hit = scene_wave_sum(n_hit); n_front = scene_wave_sum(n_front);
+  layers = wave_sum(layers); bit_tests = wave_sum(bit_tests); lookups = wave_sum(lookups); misses = wave_sum(misses);
+  tests = wave_sum(tests);
+  n_bad = wave_sum(n_bad); n_hit = wave_sum(n_hit); n_front = wave_sum(n_front);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)bits, off); bits = o > bits ? o : bits; }
   if ((threadIdx.x & 63) != 0) return;
@@ -200,45 +194,30 @@ unsigned long long scene_bytes(const DevBuf<T>& b) { return (unsigned long long)
 
 int scene_build(smx_recon r, hipStream_t st, smx_rayscene_s* sc, const smx_rayscene_params* p, const uint32_t* triangles, uint32_t n_in,
                 bool dev, uint32_t n, smx_rayscene_stats* stats) {
-  RaycastWork& w = r->raycast;
   SMX_CALL(sc->build_stamps.begin(st));
   auto finish = [&](int rc) -> int {     // (the stamps are complete before they are published)
     SMX_HIP(hipStreamSynchronize(st));
     sc->build_stamps.publish();
     return rc;
   };
-  if (!sc->counters.get()) SMX_CALL(sc->counters.alloc(kRayWords, false));
-  SMX_CALL(w.mark.reserve(n_in));
-  SMX_CALL(w.blocks.reserve((size_t)div_up(n_in, kRayBlock)));
-  SMX_CALL(w.wide_t.reserve(n_in));
+  TgWork& w = r->raycast.grid;
+  if (!sc->counters.get()) SMX_CALL(sc->counters.alloc(kSceneBuildWords, false));
+  SMX_CALL(w.reserve_mark(n_in));
   const uint32_t* din = nullptr;
-  SMX_CALL(stage_in(w.in, triangles, (size_t)3 * n_in, dev, st, &din));
+  SMX_CALL(stage_in(r->raycast.in, triangles, (size_t)3 * n_in, dev, st, &din));
   uint32_t* cnt = sc->counters.get();
-  SMX_HIP(hipMemsetAsync(cnt, 0, kRayWords * sizeof(uint32_t), st));
+  SMX_HIP(hipMemsetAsync(cnt, 0, kSceneBuildWords * sizeof(uint32_t), st));
   uint32_t* h = sc->h;
-  auto read_counters = [&]() -> int {
-    SMX_HIP(hipMemcpyAsync(h, cnt, kRayWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    SMX_HIP(hipStreamSynchronize(st));
-    return SMX_OK;
-  };
 
   // ---- mark
   const Surfels::View sv = r->S.view(kGroupS), nv = r->S.view(kGroupN);
-  const DistMap map{sv.p, sv.stride, nv.p, nv.stride, n};
-  SMX_CALL(ray_enqueue_mark(w, map, din, n_in, p->cell_size, cnt, st));
+  const TgMap map{sv.p, sv.stride, nv.p, nv.stride, n};
+  SMX_CALL(tg_enqueue_mark(w, TgBoxes::kForRays, map, din, n_in, p->cell_size, kRayMinCell, cnt, st));
   SMX_CALL(sc->build_stamps.mark(st));
-  SMX_CALL(read_counters());
-  if (h[kRayError] != 0) {
-    set_error("triangles holds an index >= the %u slots of the map", n);
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-  if (ray_word64(h, kRayEntries64Lo) > (1ull << 30)) {
-    set_error("more than 2^30 (cell, triangle) entries: choose a larger cell_size");
-    return finish(SMX_ERR_INVALID_ARGUMENT);
-  }
-  const uint32_t E = h[kRayEntries], Wd = h[kRayNWide];
+  uint32_t E = 0, Wd = 0;
+  if (const int rc = tg_read_counts(cnt, h, kSceneBuildWords, n, st, &E, &Wd)) return finish(rc);
   int32_t lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) { lo[a] = (int32_t)h[kRayOccLo + a]; hi[a] = (int32_t)h[kRayOccHi + a]; }
+  for (int a = 0; a < 3; ++a) { lo[a] = (int32_t)h[kTgOccLo + a]; hi[a] = (int32_t)h[kTgOccHi + a]; }
   int k = -1;
   if (p->occupancy > 0) {
     k = p->occupancy - 1;
@@ -256,7 +235,7 @@ int scene_build(smx_recon r, hipStream_t st, smx_rayscene_s* sc, const smx_raysc
   // ---- index, into the scene's own records and table
   uint32_t mask = 0;
   const unsigned long long* sorted_keys = nullptr;
-  SMX_CALL(ray_enqueue_index(w, map, din, n_in, E, Wd, cnt, sc->recs, sc->wide_recs, sc->table, &mask, &sorted_keys, st));
+  SMX_CALL(tg_enqueue_index(w, TgBoxes::kForRays, map, din, n_in, E, Wd, 0, cnt, sc->recs, sc->wide_recs, sc->table, &mask, &sorted_keys, st));
   SMX_CALL(sc->build_stamps.mark(st));
 
   // ---- occupancy
@@ -264,20 +243,21 @@ int scene_build(smx_recon r, hipStream_t st, smx_rayscene_s* sc, const smx_raysc
     SMX_CALL(sc->bits.alloc(n_words, false));
     SMX_HIP(hipMemsetAsync(sc->bits.get(), 0, (size_t)std::max<uint32_t>(n_words, 1u) * sizeof(uint32_t), st));
     if (E > 0 && n_words > 0) {
-      hipLaunchKernelGGL(k_scene_occupancy, dim3(ray_blocks(E)), dim3(kRayBlock), 0, st, sorted_keys, E, grid, sc->bits.get());
-      hipLaunchKernelGGL(k_scene_popcount, dim3(std::min<unsigned>(ray_blocks(n_words), 4096u)), dim3(kRayBlock), 0, st, sc->bits.get(), n_words, cnt);
+      hipLaunchKernelGGL(k_scene_occupancy, dim3(blocks_for(E)), dim3(kRayBlock), 0, st, sorted_keys, E, grid, sc->bits.get());
+      hipLaunchKernelGGL(k_scene_popcount, dim3(std::min<unsigned>(blocks_for(n_words), 4096u)), dim3(kRayBlock), 0, st, sc->bits.get(), n_words, cnt);
       SMX_LAUNCH_CHECK();
     }
   }
   SMX_CALL(sc->build_stamps.mark(st));
-  SMX_CALL(read_counters());
+  SMX_HIP(hipMemcpyAsync(h, cnt, kSceneBuildWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
   sc->mask = mask; sc->n_entries = E; sc->n_wide = Wd; sc->grid = grid;
   sc->built = true;
   if (stats) {
-    stats->n_not_live = h[kRayNotLive]; stats->n_repeated = h[kRayRepeated]; stats->n_out_of_range = h[kRayRange];
-    stats->n_wide = Wd; stats->n_entries = E; stats->n_cells = h[kRayCells];
-    memcpy(&stats->cell_size_used, &h[kRayCellBits], sizeof(float));
-    stats->occupancy_log2 = k; stats->n_blocks_set = h[kSceneBlocksWord];
+    stats->n_not_live = h[kTgNotLive]; stats->n_repeated = h[kTgRepeated]; stats->n_out_of_range = h[kTgRange];
+    stats->n_wide = Wd; stats->n_entries = E; stats->n_cells = h[kTgCells];
+    memcpy(&stats->cell_size_used, &h[kTgCellBits], sizeof(float));
+    stats->occupancy_log2 = k; stats->n_blocks_set = h[kSceneBlocksSet];
     stats->occupancy_bytes = (unsigned long long)n_words * sizeof(uint32_t);
     stats->device_bytes = scene_bytes(sc->recs) + scene_bytes(sc->wide_recs) + scene_bytes(sc->table) + scene_bytes(sc->bits) +
                           scene_bytes(sc->counters) + scene_bytes(sc->cast_counters) + scene_bytes(sc->best) + scene_bytes(sc->work) +
@@ -325,7 +305,7 @@ int smx_recon_build_rayscene(smx_recon r, smx_stream s, smx_rayscene sc, const s
   scene_clear(sc);                       // (a refused build leaves the scene empty too; casts are synchronous: nothing reads what goes)
   SMX_CHECK_ARG(r != nullptr && p != nullptr);
   SMX_CHECK_ARG(sc->device == r->device);
-  SMX_CHECK_ARG(ray_finite_f(p->cell_size) && p->cell_size >= 0.0f);
+  SMX_CHECK_ARG(finite_f(p->cell_size) && p->cell_size >= 0.0f);
   SMX_CHECK_ARG(p->occupancy >= -1 && p->occupancy <= 1 + kSceneMaxLog2);
   SMX_CHECK_ARG(n_in <= (1u << 28));
   SMX_CHECK_ARG(triangles != nullptr || n_in == 0);
@@ -345,7 +325,7 @@ int smx_recon_build_rayscene(smx_recon r, smx_stream s, smx_rayscene sc, const s
 int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p, const float* rays, uint32_t n_rays, uint32_t* hit, float* t,
                       float* uv, int32_t on_device, smx_rayscene_cast_stats* stats) {
   SMX_CHECK_ARG(sc != nullptr && p != nullptr);
-  SMX_CHECK_ARG(ray_finite_f(p->t_min) && ray_finite_f(p->t_max) && p->t_min >= 0.0f && p->t_min <= p->t_max && p->t_max <= SMX_RAY_MAX_T);
+  SMX_CHECK_ARG(finite_f(p->t_min) && finite_f(p->t_max) && p->t_min >= 0.0f && p->t_min <= p->t_max && p->t_max <= SMX_RAY_MAX_T);
   SMX_CHECK_ARG(p->cell_size == 0.0f);
   SMX_CHECK_ARG(p->cull == 0 || p->cull == 1 || p->cull == 2);
   SMX_CHECK_ARG(n_rays <= (1u << 28));
@@ -358,7 +338,7 @@ int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p
     const void* outs[3] = {hit, t, uv};
     const size_t out_bytes[3] = {(size_t)n_rays * 4, (size_t)n_rays * 4, (size_t)n_rays * 8};
     for (int o = 0; o < 3; ++o)
-      if (ray_overlap(rays, (size_t)n_rays * 24, outs[o], out_bytes[o])) {
+      if (ranges_overlap(rays, (size_t)n_rays * 24, outs[o], out_bytes[o])) {
         set_error("an output of smx_rayscene_cast overlaps rays");
         return SMX_ERR_INVALID_ARGUMENT;
       }
@@ -395,11 +375,11 @@ int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p
   uint4* work = reinterpret_cast<uint4*>(sc->work.get());
   if (n_rays > 0) {
     float cell;
-    memcpy(&cell, &sc->h[kRayCellBits], sizeof(float));
+    memcpy(&cell, &sc->h[kTgCellBits], sizeof(float));
     SceneBox occ;
-    for (int a = 0; a < 3; ++a) { occ.lo[a] = (int32_t)sc->h[kRayOccLo + a]; occ.hi[a] = (int32_t)sc->h[kRayOccHi + a]; }
-    hipLaunchKernelGGL(k_scene_cast, dim3((unsigned)div_up(n_rays, kRayWaves)), b, 0, st, drays, n_rays, reinterpret_cast<const DistCell*>(sc->table.get()),
-                       sc->mask, reinterpret_cast<const DistRec*>(sc->recs.get()), reinterpret_cast<const DistRec*>(sc->wide_recs.get()), sc->n_wide,
+    for (int a = 0; a < 3; ++a) { occ.lo[a] = (int32_t)sc->h[kTgOccLo + a]; occ.hi[a] = (int32_t)sc->h[kTgOccHi + a]; }
+    hipLaunchKernelGGL(k_scene_cast, dim3((unsigned)div_up(n_rays, kRayWaves)), b, 0, st, drays, n_rays, reinterpret_cast<const TgCell*>(sc->table.get()),
+                       sc->mask, reinterpret_cast<const TgRec*>(sc->recs.get()), reinterpret_cast<const TgRec*>(sc->wide_recs.get()), sc->n_wide,
                        sc->n_entries, sc->grid, sc->bits.get(), cell, occ, p->t_min, p->t_max, (int)p->cull, d_hit, d_t, d_uv, sc->best.get(), work);
     SMX_LAUNCH_CHECK();
   }
@@ -407,7 +387,7 @@ int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p
 
   // ---- stats
   if (n_rays > 0) {
-    hipLaunchKernelGGL(k_scene_stats, dim3(std::min(ray_blocks(n_rays), kSceneStatsBlocks)), b, 0, st, n_rays, sc->best.get(), work, cnt);
+    hipLaunchKernelGGL(k_scene_stats, dim3(std::min(blocks_for(n_rays), kSceneStatsBlocks)), b, 0, st, n_rays, sc->best.get(), work, cnt);
     SMX_LAUNCH_CHECK();
     if (!dev) {
       SMX_HIP(hipMemcpyAsync(hit, d_hit, (size_t)n_rays * 4, hipMemcpyDeviceToHost, st));
@@ -422,9 +402,9 @@ int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p
     memset(stats, 0, sizeof(*stats));
     stats->n_rays = n_rays; stats->n_bad_rays = h[kSceneBadRays]; stats->n_hit = h[kSceneHits]; stats->n_front_hits = h[kSceneFrontHits];
     stats->max_t_bits = h[kSceneMaxTBits];
-    stats->n_layers = ray_word64(h, kSceneLayersLo); stats->n_bit_tests = ray_word64(h, kSceneBitTestsLo);
-    stats->n_lookups = ray_word64(h, kSceneLookupsLo); stats->n_lookup_misses = ray_word64(h, kSceneMissesLo);
-    stats->n_pair_tests = ray_word64(h, kSceneTestsLo);
+    stats->n_layers = word64(h, kSceneLayersLo); stats->n_bit_tests = word64(h, kSceneBitTestsLo);
+    stats->n_lookups = word64(h, kSceneLookupsLo); stats->n_lookup_misses = word64(h, kSceneMissesLo);
+    stats->n_pair_tests = word64(h, kSceneTestsLo);
   }
   SMX_CALL(sc->cast_stamps.mark(st));
   return finish(SMX_OK);

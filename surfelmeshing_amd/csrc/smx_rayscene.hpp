@@ -86,7 +86,7 @@ SMX_RAY_FN bool scene_find(const SceneGrid& g, const Bits& bits, const Tab& tab,
     if (!scene_bit_of(g, x, y, z, &bit) || !bits.test(bit)) return false;
   }
   ++w->lookups;
-  const bool found = dist_table_find(tab, mask, dec_cell_key(x, y, z), first, end);
+  const bool found = tg_table_find(tab, mask, dec_cell_key(x, y, z), first, end);
   if (!found) ++w->misses;
   return found;
 }
@@ -95,10 +95,10 @@ SMX_RAY_FN bool scene_find(const SceneGrid& g, const Bits& bits, const Tab& tab,
 // by the same expressions.
 struct SceneKeep { unsigned long long own; float u, v, det; };
 template <class Recs>
-SMX_RAY_FN unsigned long long scene_walk(const Recs& recs, uint32_t first, uint32_t end, uint32_t stride, const DistVec& O, const DistVec& D,
+SMX_RAY_FN unsigned long long scene_walk(const Recs& recs, uint32_t first, uint32_t end, uint32_t stride, const TgVec& O, const TgVec& D,
                                          float t_min, float t_max, int cull, unsigned long long best, SceneKeep* keep, uint32_t* tests) {
   for (uint32_t j = first; j < end; j += stride) {
-    DistVec A, B, C;
+    TgVec A, B, C;
     uint32_t i;
     RayHit h{0.0f, 0.0f, 0.0f, 0.0f};
     recs.load(j, &A, &B, &C, &i);
@@ -112,9 +112,9 @@ SMX_RAY_FN unsigned long long scene_walk(const Recs& recs, uint32_t first, uint3
 // cell looked up in the table.
 template <class Bits, class Tab, class Recs, class Seen>
 SMX_RAY_FN unsigned long long scene_cast_one(const SceneGrid& g, const Bits& bits, const Tab& tab, uint32_t mask, const Recs& cell_recs,
-                                             const Recs& wide_recs, uint32_t n_wide, const RayAxes& r, const DistVec& O, const DistVec& D, float cell,
+                                             const Recs& wide_recs, uint32_t n_wide, const RayAxes& r, const TgVec& O, const TgVec& D, float cell,
                                              float t_min, float t_max, int cull, bool early_exit, Seen& seen, SceneKeep* keep, SceneWork* work) {
-  unsigned long long best = scene_walk(wide_recs, 0, n_wide, 1, O, D, t_min, t_max, cull, kDistNone, keep, &work->tests);
+  unsigned long long best = scene_walk(wide_recs, 0, n_wide, 1, O, D, t_min, t_max, cull, kTgNone, keep, &work->tests);
   for (uint32_t m = 0; m < r.n_layers; ++m) {
     if (early_exit && ray_done(r, cell, best, m)) break;
     const RayRect q = ray_layer_rect(r, cell, t_min, t_max, m);
@@ -135,7 +135,9 @@ SMX_RAY_FN unsigned long long scene_cast_one(const SceneGrid& g, const Bits& bit
 
 #if !defined(SMX_RAYSCENE_HOST_ONLY)
 // ---- part 2 ----------------------------------------------------------------------------------------------------------
-// the words of a cast's counters (the build's are the kRay words of smx_raycast.hpp, kept as the build left them)
+// the words of the build's counters behind the grid's (kept as the build left them), and the words of a cast's counters
+enum : int { kSceneBlocksSet = kTgWords, kSceneBuildWords = 32 };      // the set bits of the occupancy grid; device_bytes counts 32 words
+static_assert(kSceneBlocksSet < kSceneBuildWords, "the build's counters");
 enum : int { kSceneBadRays = 0, kSceneHits, kSceneFrontHits, kSceneMaxTBits, kSceneLayersLo, kSceneLayersHi, kSceneBitTestsLo, kSceneBitTestsHi,
              kSceneLookupsLo, kSceneLookupsHi, kSceneMissesLo, kSceneMissesHi, kSceneTestsLo, kSceneTestsHi, kSceneWords = 16 };
 enum : uint32_t { kSceneWorkWords = 8 };                    // per ray: layers, bit tests, look-ups, misses, pair tests, flags, -, -
@@ -154,11 +156,11 @@ struct smx_rayscene_s {
   int device = 0;
   bool built = false;
   // the build's
-  smx::DevBuf<float> recs, wide_recs;              // [n_entries] / [n_wide] DistRec
-  smx::DevBuf<unsigned long long> table;           // [mask + 1][2] DistCell
+  smx::DevBuf<float> recs, wide_recs;              // [n_entries] / [n_wide] TgRec
+  smx::DevBuf<unsigned long long> table;           // [mask + 1][2] TgCell
   smx::DevBuf<uint32_t> bits;                      // the occupancy grid, 32 bits a word
-  smx::DevBuf<uint32_t> counters;                  // [kRayWords] as the build left them: c, the occupied box
-  uint32_t h[smx::kRayWords] = {};                 // ... and on the host
+  smx::DevBuf<uint32_t> counters;                  // [kSceneBuildWords] as the build left them: c, the occupied box
+  uint32_t h[smx::kSceneBuildWords] = {};          // ... and on the host
   uint32_t mask = 0, n_entries = 0, n_wide = 0;
   smx::SceneGrid grid{{0, 0, 0}, {0, 0, 0}, -1};
   // a cast's

@@ -102,6 +102,16 @@ struct Scratch {
 
 constexpr int kBlock = 256;
 
+// ---- what the glue of every map service asks ----
+inline unsigned blocks_for(uint32_t n) { return (unsigned)div_up(n, kBlock); }
+inline bool finite_f(float v) { return v - v == 0.0f; }
+inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+inline unsigned long long word64(const uint32_t* h, int lo) { return ((unsigned long long)h[lo + 1] << 32) | h[lo]; }   // a (lo, hi) pair
+
 // Work lists are SEGMENTED: the slots [s*kSeg, (s+1)*kSeg) are scanned by one workgroup, which writes the
 // indices it selects to list[s*kSeg ...] (ascending) and their number to seg[s].  No global counter, no
 // atomics, and the list order is deterministic.
@@ -199,6 +209,38 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* wav
     total += wave_tot[w];
   }
   return wave_off + incl - mine;
+}
+
+// ---- folds over a wavefront (wave64 shuffles) ----
+// one atomic per wavefront: the number of its lanes with `pred`
+__device__ __forceinline__ void wave_count(uint32_t* counter, bool pred) {
+  const unsigned long long m = __ballot(pred);
+  if (m != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)m) - 1)) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int32_t wave_imin(int32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o < v ? o : v; }
+  return v;
+}
+__device__ __forceinline__ int32_t wave_imax(int32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int32_t o = __shfl_xor(v, off); v = o > v ? o : v; }
+  return v;
 }
 
 // The maps of the multi-launch blend fallback (kernels.cc:165-166).

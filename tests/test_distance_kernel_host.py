@@ -40,10 +40,10 @@ struct Tab {                         // one lane at a time: the operations on pl
   }
   void bump(uint32_t h, unsigned long long inc) const { e[h].value += inc; }
 };
-struct Rec { DistVec a, b, c; uint32_t t; };
+struct Rec { TgVec a, b, c; uint32_t t; };
 struct Recs {
   const Rec* r;
-  void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
+  void load(uint32_t j, TgVec* A, TgVec* B, TgVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
 };
 
 static std::vector<uint32_t> lanes(uint32_t count, uint32_t order) {
@@ -61,9 +61,9 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
                          float cell_size, int is_signed, uint32_t order, uint32_t* nearest, float* distance, float* closest, uint32_t* stats) {
   for (int k = 0; k < WORDS; ++k) stats[k] = 0;
   stats[N_IN] = n_in; stats[N_POINTS] = n_points;
-  auto pos = [&](uint32_t i) { return DistVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
+  auto pos = [&](uint32_t i) { return TgVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
   auto live = [&](uint32_t i) { return dec_live(S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2], S[4 * (size_t)i + 3]); };
-  auto point = [&](uint32_t p) { return DistVec{pts[3 * (size_t)p], pts[3 * (size_t)p + 1], pts[3 * (size_t)p + 2]}; };
+  auto point = [&](uint32_t p) { return TgVec{pts[3 * (size_t)p], pts[3 * (size_t)p + 1], pts[3 * (size_t)p + 2]}; };
   // k_dist_classify, k_dist_cell
   std::vector<uint32_t> mark(n_in, 0);
   unsigned long long extent = 0;
@@ -71,12 +71,12 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
   for (uint32_t t : lanes(n_in, order)) {
     const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
     if (i0 >= n || i1 >= n || i2 >= n) return -1;
-    const DistVec a = pos(i0), b = pos(i1), c = pos(i2);
-    const uint32_t cls = dist_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
-    if (cls == kDistDropNotLive) ++stats[N_NOT_LIVE];
-    if (cls == kDistDropRepeated) ++stats[N_REPEATED];
-    if (cls == kDistDropRange) ++stats[N_RANGE];
-    if (cls == kDistInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(dist_extent(a, b, c) * 1048576.0f); }
+    const TgVec a = pos(i0), b = pos(i1), c = pos(i2);
+    const uint32_t cls = tg_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
+    if (cls == kTgDropNotLive) ++stats[N_NOT_LIVE];
+    if (cls == kTgDropRepeated) ++stats[N_REPEATED];
+    if (cls == kTgDropRange) ++stats[N_RANGE];
+    if (cls == kTgInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(tg_extent(a, b, c) * 1048576.0f); }
   }
   float given = cell_size;
   if (!(cell_size > 0.0f)) given = in_r != 0 ? (float)((double)extent / (double)in_r * (1.0 / 1048576.0)) : 0.0f;
@@ -84,24 +84,24 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
   __builtin_memcpy(&stats[CELL], &cell, 4);
   // k_dist_mark: the wide list in arrival order; the scan
   std::vector<uint32_t> wide_t;
-  auto box_of = [&](uint32_t t) { return dist_box(pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), cell); };
+  auto box_of = [&](uint32_t t) { return tg_box(pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), cell); };
   for (uint32_t t : lanes(n_in, order)) {
     if (mark[t] == 0) continue;
-    mark[t] = dist_mark(box_of(t));
-    if (mark[t] == kDistWide) wide_t.push_back(t);
+    mark[t] = tg_mark(box_of(t));
+    if (mark[t] == kTgWide) wide_t.push_back(t);
   }
   std::vector<uint32_t> off(n_in + 1, 0);
-  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kDistWide ? 0u : mark[t]);
+  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kTgWide ? 0u : mark[t]);
   const uint32_t E = off[n_in];
   stats[N_WIDE] = (uint32_t)wide_t.size(); stats[N_ENTRIES] = E;
   // k_dist_entries, the stable sort, k_dist_records
   std::vector<unsigned long long> keys(E);
   std::vector<uint32_t> vals(E);
   for (uint32_t t : lanes(n_in, order)) {
-    const uint32_t count = mark[t] == kDistWide ? 0u : mark[t];
+    const uint32_t count = mark[t] == kTgWide ? 0u : mark[t];
     if (count == 0) continue;
-    const DistBox box = box_of(t);
-    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = dist_box_key(box, j); vals[off[t] + j] = t; }
+    const TgBox box = box_of(t);
+    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = tg_box_key(box, j); vals[off[t] + j] = t; }
   }
   std::vector<uint32_t> perm(E);
   std::iota(perm.begin(), perm.end(), 0u);
@@ -113,26 +113,26 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
   for (size_t j = 0; j < wide_t.size(); ++j) wide_recs[j] = rec_of(wide_t[j]);
   // k_dist_table
   const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  std::vector<Entry> table(entries, Entry{kDistEmpty, 0});
+  std::vector<Entry> table(entries, Entry{kTgEmpty, 0});
   Tab tab{table.data()};
-  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += dist_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
+  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += tg_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
   // k_dist_query, k_dist_stats
   const float max2 = max_distance * max_distance;
   const Recs cell_recs{recs.data()}, wrecs{wide_recs.data()};
   for (uint32_t p : lanes(n_points, order)) {
-    const DistVec P = point(p);
-    unsigned long long key = kDistNone;
-    if (dist_point_ok(P)) key = dist_query(tab, mask, cell_recs, wrecs, (uint32_t)wide_t.size(), P, cell, max2);
+    const TgVec P = point(p);
+    unsigned long long key = kTgNone;
+    if (tg_point_ok(P)) key = dist_query(tab, mask, cell_recs, wrecs, (uint32_t)wide_t.size(), P, cell, max2);
     else ++stats[N_BAD];
     uint32_t t = 0xFFFFFFFFu;
     float d = INFINITY;
-    DistVec Q{NAN, NAN, NAN};
-    if (key != kDistNone) {
+    TgVec Q{NAN, NAN, NAN};
+    if (key != kTgNone) {
       t = (uint32_t)key;
-      const DistVec A = pos(tri[3 * (size_t)t]), B = pos(tri[3 * (size_t)t + 1]), C = pos(tri[3 * (size_t)t + 2]);
+      const TgVec A = pos(tri[3 * (size_t)t]), B = pos(tri[3 * (size_t)t + 1]), C = pos(tri[3 * (size_t)t + 2]);
       uint32_t region;
       Q = dist_closest(P, A, B, C, &region);
-      d = sqrtf(dist_key_dist2(key));
+      d = sqrtf(tg_key_float(key));
       ++stats[N_MATCHED];
       ++stats[HIST + dist_bin(d, max_distance)];
       stats[MAX_BITS] = std::max(stats[MAX_BITS], (uint32_t)(key >> 32));

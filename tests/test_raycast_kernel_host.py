@@ -44,10 +44,10 @@ struct Tab {                         // one lane at a time: the operations on pl
   }
   void bump(uint32_t h, unsigned long long inc) const { e[h].value += inc; }
 };
-struct Rec { DistVec a, b, c; uint32_t t; };
+struct Rec { TgVec a, b, c; uint32_t t; };
 struct Recs {
   const Rec* r;
-  void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
+  void load(uint32_t j, TgVec* A, TgVec* B, TgVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
 };
 struct Unseen { void operator()(unsigned long long) const {} };
 struct SeenSet { std::unordered_set<unsigned long long>* s; void operator()(unsigned long long k) const { s->insert(k); } };
@@ -69,7 +69,7 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
                         uint32_t* stats) {
   for (int k = 0; k < WORDS; ++k) stats[k] = 0;
   stats[N_IN] = n_in; stats[N_RAYS] = n_rays;
-  auto pos = [&](uint32_t i) { return DistVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
+  auto pos = [&](uint32_t i) { return TgVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
   auto live = [&](uint32_t i) { return dec_live(S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2], S[4 * (size_t)i + 3]); };
   // k_ray_classify, k_ray_cell
   std::vector<uint32_t> mark(n_in, 0);
@@ -78,12 +78,12 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
   for (uint32_t t : lanes(n_in, order)) {
     const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
     if (i0 >= n || i1 >= n || i2 >= n) return -1;
-    const DistVec a = pos(i0), b = pos(i1), c = pos(i2);
-    const uint32_t cls = dist_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
-    if (cls == kDistDropNotLive) ++stats[N_NOT_LIVE];
-    if (cls == kDistDropRepeated) ++stats[N_REPEATED];
-    if (cls == kDistDropRange) ++stats[N_RANGE];
-    if (cls == kDistInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(dist_extent(a, b, c) * 1048576.0f); }
+    const TgVec a = pos(i0), b = pos(i1), c = pos(i2);
+    const uint32_t cls = tg_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
+    if (cls == kTgDropNotLive) ++stats[N_NOT_LIVE];
+    if (cls == kTgDropRepeated) ++stats[N_REPEATED];
+    if (cls == kTgDropRange) ++stats[N_RANGE];
+    if (cls == kTgInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(tg_extent(a, b, c) * 1048576.0f); }
   }
   float given = cell_size;
   if (!(cell_size > 0.0f)) given = in_r != 0 ? (float)((double)extent / (double)in_r * (1.0 / 1048576.0)) : 0.0f;
@@ -95,23 +95,23 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
   auto box_of = [&](uint32_t t) { return ray_box(pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), cell); };
   for (uint32_t t : lanes(n_in, order)) {
     if (mark[t] == 0) continue;
-    const DistBox box = box_of(t);
-    mark[t] = dist_mark(box);
-    if (mark[t] == kDistWide) { wide_t.push_back(t); continue; }
+    const TgBox box = box_of(t);
+    mark[t] = tg_mark(box);
+    if (mark[t] == kTgWide) { wide_t.push_back(t); continue; }
     for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], box.lo[k]); hi[k] = std::max(hi[k], box.hi[k]); }
   }
   std::vector<uint32_t> off(n_in + 1, 0);
-  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kDistWide ? 0u : mark[t]);
+  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kTgWide ? 0u : mark[t]);
   const uint32_t E = off[n_in];
   stats[N_WIDE] = (uint32_t)wide_t.size(); stats[N_ENTRIES] = E;
   // k_ray_entries, the stable sort, k_ray_records
   std::vector<unsigned long long> keys(E);
   std::vector<uint32_t> vals(E);
   for (uint32_t t : lanes(n_in, order)) {
-    const uint32_t count = mark[t] == kDistWide ? 0u : mark[t];
+    const uint32_t count = mark[t] == kTgWide ? 0u : mark[t];
     if (count == 0) continue;
-    const DistBox box = box_of(t);
-    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = dist_box_key(box, j); vals[off[t] + j] = t; }
+    const TgBox box = box_of(t);
+    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = tg_box_key(box, j); vals[off[t] + j] = t; }
   }
   std::vector<uint32_t> perm(E);
   std::iota(perm.begin(), perm.end(), 0u);
@@ -123,16 +123,16 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
   for (size_t j = 0; j < wide_t.size(); ++j) wide_recs[j] = rec_of(wide_t[j]);
   // k_ray_table
   const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  std::vector<Entry> table(entries, Entry{kDistEmpty, 0});
+  std::vector<Entry> table(entries, Entry{kTgEmpty, 0});
   Tab tab{table.data()};
-  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += dist_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
+  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += tg_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
   // k_ray_cast, k_ray_stats
   const Recs cell_recs{recs.data()}, wrecs{wide_recs.data()};
   uint32_t at_pair = 0;
   for (uint32_t p = 0; p < n_rays; ++p) {
     const float* r = rays + 6 * (size_t)p;
-    const DistVec O{r[0], r[1], r[2]}, D{r[3], r[4], r[5]};
-    unsigned long long key = kDistNone;
+    const TgVec O{r[0], r[1], r[2]}, D{r[3], r[4], r[5]};
+    unsigned long long key = kTgNone;
     if (ray_bad(O, D)) {
       ++stats[N_BAD];
     } else {
@@ -148,10 +148,10 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
       stats[LAYERS] += work.layers; stats[LOOKUPS] += work.lookups; stats[LAYERS_FULL] += full.layers; stats[LOOKUPS_FULL] += full.lookups;
       for (; at_pair < n_pairs && pairs[2 * (size_t)at_pair] == p; ++at_pair) {
         const uint32_t i = pairs[2 * (size_t)at_pair + 1];
-        bool found = mark[i] == kDistWide;
+        bool found = mark[i] == kTgWide;
         if (!found && mark[i] != 0) {
-          const DistBox box = box_of(i);
-          for (uint32_t j = 0; j < mark[i] && !found; ++j) found = cells.count(dist_box_key(box, j)) != 0;
+          const TgBox box = box_of(i);
+          for (uint32_t j = 0; j < mark[i] && !found; ++j) found = cells.count(tg_box_key(box, j)) != 0;
         }
         if (!found) ++stats[PAIRS_MISSED];
       }
@@ -159,12 +159,12 @@ static int host_raycast(uint32_t n, const float* S, const uint32_t* tri, uint32_
     for (; at_pair < n_pairs && pairs[2 * (size_t)at_pair] == p; ++at_pair) ++stats[PAIRS_MISSED];      // (a candidate of a BAD ray)
     uint32_t i = 0xFFFFFFFFu;
     float t = INFINITY, u = NAN, v = NAN;
-    if (key != kDistNone) {
+    if (key != kTgNone) {
       i = (uint32_t)key;
       RayHit h{0, 0, 0, 0};
       const unsigned long long again = ray_key(O, D, pos(tri[3 * (size_t)i]), pos(tri[3 * (size_t)i + 1]), pos(tri[3 * (size_t)i + 2]), i, t_min, t_max, cull, &h);
       if (again != key) ++stats[EXIT_DIFFERS];
-      t = dist_key_dist2(key); u = h.u; v = h.v;
+      t = tg_key_float(key); u = h.u; v = h.v;
       ++stats[N_HIT];
       if (h.det > 0.0f) ++stats[N_FRONT];
       stats[MAX_BITS] = std::max(stats[MAX_BITS], (uint32_t)(key >> 32));

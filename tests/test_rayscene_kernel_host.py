@@ -47,10 +47,10 @@ struct Tab {                         // one lane at a time: the operations on pl
   }
   void bump(uint32_t h, unsigned long long inc) const { e[h].value += inc; }
 };
-struct Rec { DistVec a, b, c; uint32_t t; };
+struct Rec { TgVec a, b, c; uint32_t t; };
 struct Recs {
   const Rec* r;
-  void load(uint32_t j, DistVec* A, DistVec* B, DistVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
+  void load(uint32_t j, TgVec* A, TgVec* B, TgVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
 };
 struct Bits {
   const std::vector<uint32_t>* w;
@@ -77,7 +77,7 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
                       float* uv, uint32_t* stats) {
   for (int k = 0; k < WORDS; ++k) stats[k] = 0;
   stats[N_IN] = n_in; stats[N_RAYS] = n_rays;
-  auto pos = [&](uint32_t i) { return DistVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
+  auto pos = [&](uint32_t i) { return TgVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
   auto live = [&](uint32_t i) { return dec_live(S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2], S[4 * (size_t)i + 3]); };
   // ---- mark and index, as the build shares them with smx_recon_raycast_mesh
   std::vector<uint32_t> mark(n_in, 0);
@@ -86,12 +86,12 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
   for (uint32_t t : lanes(n_in, order)) {
     const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
     if (i0 >= n || i1 >= n || i2 >= n) return -1;
-    const DistVec a = pos(i0), b = pos(i1), c = pos(i2);
-    const uint32_t cls = dist_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
-    if (cls == kDistDropNotLive) ++stats[N_NOT_LIVE];
-    if (cls == kDistDropRepeated) ++stats[N_REPEATED];
-    if (cls == kDistDropRange) ++stats[N_RANGE];
-    if (cls == kDistInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(dist_extent(a, b, c) * 1048576.0f); }
+    const TgVec a = pos(i0), b = pos(i1), c = pos(i2);
+    const uint32_t cls = tg_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
+    if (cls == kTgDropNotLive) ++stats[N_NOT_LIVE];
+    if (cls == kTgDropRepeated) ++stats[N_REPEATED];
+    if (cls == kTgDropRange) ++stats[N_RANGE];
+    if (cls == kTgInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(tg_extent(a, b, c) * 1048576.0f); }
   }
   float given = cell_size;
   if (!(cell_size > 0.0f)) given = in_r != 0 ? (float)((double)extent / (double)in_r * (1.0 / 1048576.0)) : 0.0f;
@@ -102,22 +102,22 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
   auto box_of = [&](uint32_t t) { return ray_box(pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), cell); };
   for (uint32_t t : lanes(n_in, order)) {
     if (mark[t] == 0) continue;
-    const DistBox box = box_of(t);
-    mark[t] = dist_mark(box);
-    if (mark[t] == kDistWide) { wide_t.push_back(t); continue; }
+    const TgBox box = box_of(t);
+    mark[t] = tg_mark(box);
+    if (mark[t] == kTgWide) { wide_t.push_back(t); continue; }
     for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], box.lo[k]); hi[k] = std::max(hi[k], box.hi[k]); }
   }
   std::vector<uint32_t> off(n_in + 1, 0);
-  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kDistWide ? 0u : mark[t]);
+  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kTgWide ? 0u : mark[t]);
   const uint32_t E = off[n_in];
   stats[N_WIDE] = (uint32_t)wide_t.size(); stats[N_ENTRIES] = E;
   std::vector<unsigned long long> keys(E);
   std::vector<uint32_t> vals(E);
   for (uint32_t t : lanes(n_in, order)) {
-    const uint32_t count = mark[t] == kDistWide ? 0u : mark[t];
+    const uint32_t count = mark[t] == kTgWide ? 0u : mark[t];
     if (count == 0) continue;
-    const DistBox box = box_of(t);
-    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = dist_box_key(box, j); vals[off[t] + j] = t; }
+    const TgBox box = box_of(t);
+    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = tg_box_key(box, j); vals[off[t] + j] = t; }
   }
   std::vector<uint32_t> perm(E);
   std::iota(perm.begin(), perm.end(), 0u);
@@ -128,9 +128,9 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
   for (uint32_t j = 0; j < E; ++j) { skeys[j] = keys[perm[j]]; recs[j] = rec_of(vals[perm[j]]); }
   for (size_t j = 0; j < wide_t.size(); ++j) wide_recs[j] = rec_of(wide_t[j]);
   const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  std::vector<Entry> table(entries, Entry{kDistEmpty, 0});
+  std::vector<Entry> table(entries, Entry{kTgEmpty, 0});
   Tab tab{table.data()};
-  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += dist_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
+  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += tg_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
   // ---- the occupancy grid: k_scene_occupancy a lane at a time, k_scene_popcount
   int k = -1;
   if (occupancy > 0) { k = occupancy - 1; if (!scene_grid_fits(lo, hi, k)) return -3; }
@@ -167,15 +167,15 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
   uint32_t at_pair = 0;
   for (uint32_t p = 0; p < n_rays; ++p) {
     const float* r = rays + 6 * (size_t)p;
-    const DistVec O{r[0], r[1], r[2]}, D{r[3], r[4], r[5]};
-    unsigned long long key = kDistNone;
-    SceneKeep keep{kDistNone, 0.0f, 0.0f, 0.0f};
+    const TgVec O{r[0], r[1], r[2]}, D{r[3], r[4], r[5]};
+    unsigned long long key = kTgNone;
+    SceneKeep keep{kTgNone, 0.0f, 0.0f, 0.0f};
     if (ray_bad(O, D)) {
       ++stats[N_BAD];
     } else {
       SceneWork work{0, 0, 0, 0, 0}, full{0, 0, 0, 0, 0};
       RayWork base{0, 0, 0}, base_full{0, 0, 0};
-      SceneKeep keep_full{kDistNone, 0.0f, 0.0f, 0.0f};
+      SceneKeep keep_full{kTgNone, 0.0f, 0.0f, 0.0f};
       RayAxes ax = ray_axes(O, D, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], cell, t_min, t_max);
       if (E == 0) ax.n_layers = 0;
       Unseen unseen;
@@ -188,7 +188,7 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
       const unsigned long long plain_all = ray_cast_one(tab, mask, cell_recs, wrecs, (uint32_t)wide_t.size(), ax, O, D, cell, t_min, t_max, cull, false,
                                                         unseen, &base_full);
       if (all != key || plain != key || plain_all != key) ++stats[EXIT_DIFFERS];
-      if (key != kDistNone && (keep.own != key || keep_full.own != key || keep.u != keep_full.u || keep.v != keep_full.v)) ++stats[EXIT_DIFFERS];
+      if (key != kTgNone && (keep.own != key || keep_full.own != key || keep.u != keep_full.u || keep.v != keep_full.v)) ++stats[EXIT_DIFFERS];
       // the contract's relations, with the exit on and off
       const SceneWork* sw[2] = {&work, &full};
       const RayWork* bw[2] = {&base, &base_full};
@@ -202,10 +202,10 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
       stats[TESTS] += work.tests; stats[FOUND] += work.lookups - work.misses; stats[BASE_LOOKUPS] += base.lookups;
       for (; at_pair < n_pairs && pairs[2 * (size_t)at_pair] == p; ++at_pair) {
         const uint32_t i = pairs[2 * (size_t)at_pair + 1];
-        bool found = mark[i] == kDistWide;
+        bool found = mark[i] == kTgWide;
         if (!found && mark[i] != 0) {
-          const DistBox box = box_of(i);
-          for (uint32_t j = 0; j < mark[i] && !found; ++j) found = cells.count(dist_box_key(box, j)) != 0;
+          const TgBox box = box_of(i);
+          for (uint32_t j = 0; j < mark[i] && !found; ++j) found = cells.count(tg_box_key(box, j)) != 0;
         }
         if (!found) ++stats[PAIRS_MISSED];
       }
@@ -213,9 +213,9 @@ static int host_scene(uint32_t n, const float* S, const uint32_t* tri, uint32_t 
     for (; at_pair < n_pairs && pairs[2 * (size_t)at_pair] == p; ++at_pair) ++stats[PAIRS_MISSED];      // (a candidate of a BAD ray)
     uint32_t i = 0xFFFFFFFFu;
     float t = INFINITY, u = NAN, v = NAN;
-    if (key != kDistNone) {                       // as lane 0 of k_scene_cast: from what the walk kept, no read of the map
+    if (key != kTgNone) {                       // as lane 0 of k_scene_cast: from what the walk kept, no read of the map
       i = (uint32_t)key;
-      t = dist_key_dist2(key); u = keep.u; v = keep.v;
+      t = tg_key_float(key); u = keep.u; v = keep.v;
       ++stats[N_HIT];
       if (keep.det > 0.0f) ++stats[N_FRONT];
       stats[MAX_BITS] = std::max(stats[MAX_BITS], (uint32_t)(key >> 32));
