@@ -1150,8 +1150,8 @@ int smx_recon_debug_fill_timings(smx_recon r, float* out_ms, int32_t capacity);
  *    triangle) entries, n_cells = the occupied cells.  With cell_size == 0 the library takes max(1.125f * max_distance, the mean
  *    over R of the largest of the three extents of a triangle's box) for c; these three and cell_size_used are defined exactly
  *    only when cell_size > 0 is given.
- * 6. Not done: no BVH; no mesh-to-mesh Hausdorff distance in one call (the caller samples one mesh and swaps roles); no
- *    distance to an analytic surface.
+ * 6. Not done: no BVH; no distance to an analytic surface.  (The distance between two meshes, both ways in one call, is
+ *    smx_recon_compare_meshes below, on the samples of smx_recon_sample_mesh.)
  * Parameters: max_distance finite with 1e-3f <= max_distance <= 16.0f; cell_size 0 or finite and > 0; signed_distance 0 or 1;
  * n_in <= 2^28 and n_points <= 2^28.  Anything else: SMX_ERR_INVALID_ARGUMENT with nothing launched.  A cell_size so far below
  * the triangles' size that the grid would hold more than 2^30 entries is refused after the mark phase, nothing written.
@@ -1193,6 +1193,101 @@ int smx_recon_mesh_distance(smx_recon r, smx_stream s, const smx_distance_params
  * on the call's stream; a phase a call did not reach reads 0.  capacity >= SMX_DIST_PHASES.  Zeros before the first call. */
 #define SMX_DIST_PHASES 4
 int smx_recon_debug_distance_timings(smx_recon r, float* out_ms, int32_t capacity);
+
+/* ---- points on a triangle array in proportion to area, and the distance between two triangle arrays ----
+ * smx_recon_sample_mesh is a pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n)
+ * with n = surfels_size()), of `triangles` (uint32 [n_in][3], slot indices, in ANY order), of n_samples and of seed.  Every
+ * quantity is an integer or a float32 expression evaluated as written, one rounding per operation, no contraction; sqrtf and
+ * division are correctly rounded; dot and cross as in smx_recon_mesh_distance above.
+ * 1. Triangles.  R and the counts n_not_live, n_repeated and n_out_of_range exactly as smx_recon_mesh_distance step 1; an
+ *    index >= n anywhere in `triangles`: SMX_ERR_INVALID_ARGUMENT, nothing is written.  Each triangle of R keeps t, its position
+ *    in the input, and its corners A, B, C in input order.
+ * 2. Weight.  ab = B-A; ac = C-A; N = cross(ab, ac); a = sqrtf(dot(N, N)) (twice the area);
+ *    q_t = a > 0 ? (uint64)(a * 1073741824.0f) : 0 -- the product by 2^30 is exact, the conversion truncates, the unit is
+ *    2^-30 m^2, and with the corners within SMX_DIST_MAX_COORD q_t < 2^46.  A triangle outside R has q_t = 0.  n_zero_weight
+ *    counts the triangles of R with q_t == 0.
+ * 3. Prefix and total.  C_t = sat(sum of q_t' over t' < t) in input order, W = sat(sum over all t), sat(x) = min(x, 2^62).
+ *    (min(2^62, a + b) is associative on [0, 2^62], so a parallel scan gives exactly this.)  W == 2^62:
+ *    SMX_ERR_INVALID_ARGUMENT ("total area too large") after the weights phase, nothing is written.
+ * 4. Random words.  mix(x) on uint32, every operation wrapping: x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B;
+ *    x ^= x >> 16.  r_j(k) = mix(mix(3k + j) ^ seed) for j = 0, 1, 2.
+ * 5. Strata.  S = W / n_samples (integer division).  If W < n_samples every sample is "none" (so with W == 0 or an empty R).
+ *    Otherwise u_k = k*S + floor(S * r_0(k) / 2^32), all of it in integers: the high 64 bits of S * (r_0 << 32), or
+ *    (S >> 32) * r_0 + (((S & 0xFFFFFFFF) * r_0) >> 32).  So k*S <= u_k < (k+1)*S <= W: sample k is drawn from stratum k of the
+ *    total weight.  The last W - n_samples*S units (fewer than n_samples of 2^-30 m^2) are never drawn.
+ * 6. Triangle.  t is the triangle with C_t <= u_k < C_t + q_t.  It exists, has q_t > 0 and does not decrease with k: the
+ *    output is in the order of the input triangles.
+ * 7. Point.  v = (float)(r_1 >> 8) * 2^-24; w = (float)(r_2 >> 8) * 2^-24; if v + w > 1.0f: v = 1.0f - v; w = 1.0f - w (both
+ *    exact).  P = (A + v*ab) + w*ac, the interior expression of smx_recon_mesh_distance.  Normal: (N_x / a, N_y / a, N_z / a).
+ * 8. Outputs: points [n_samples][3], tri [n_samples] = t, bary [n_samples][2] = (v, w) (may be NULL), normals [n_samples][3]
+ *    (may be NULL).  A "none" sample has tri = 0xFFFFFFFF and NaN everywhere else.
+ * 9. smx_sample_stats: the counts of steps 1 and 2; n_samples; n_none; total_weight = W and stride = S; n_triangles_hit = the
+ *    samples that are not "none" whose tri differs from the sample's before (the first one counts).
+ * Not done: no colours interpolated onto the samples; no blue-noise or Poisson-disc spacing.
+ * Parameters: n_in <= 2^28 and n_samples <= 2^28, anything else SMX_ERR_INVALID_ARGUMENT with nothing launched; n_in == 0 and
+ * n_samples == 0 are valid.  Calling rules as smx_recon_mesh_distance: ordered after everything enqueued on the object,
+ * synchronous.  on_device says where triangles, points, tri, bary and normals live (host arrays are staged).  An output that
+ * overlaps `triangles` is refused.  Every allocation of the call lies before the first write to an output.  stats may be NULL.
+ * Changes no map state, delta mark, statistic or stamp, nor the state smx_recon_triangulate_update keeps.  Two calls give the
+ * same bytes.  The workspace belongs to the object, grows on demand, is reused and is freed with the object. */
+typedef struct {
+  uint32_t n_in;                      /* triangles given */
+  uint32_t n_not_live;                /* of those, dropped because a corner is not live */
+  uint32_t n_repeated;                /* of the rest, with a repeated index */
+  uint32_t n_out_of_range;            /* of the rest, with a coordinate beyond SMX_DIST_MAX_COORD */
+  uint32_t n_zero_weight;             /* of R, with q_t == 0 */
+  uint32_t n_samples;
+  uint32_t n_none;
+  uint32_t n_triangles_hit;
+  uint64_t total_weight;              /* W, in units of 2^-30 m^2 (twice the area) */
+  uint64_t stride;                    /* S */
+} smx_sample_stats;
+int smx_recon_sample_mesh(smx_recon r, smx_stream s, const uint32_t* triangles, uint32_t n_in, uint32_t n_samples, uint32_t seed,
+                          float* points /* [n_samples][3] */, uint32_t* tri /* [n_samples] */,
+                          float* bary /* [n_samples][2], may be NULL */, float* normals /* [n_samples][3], may be NULL */,
+                          int32_t on_device, smx_sample_stats* stats /* may be NULL */);
+/* Tools: milliseconds the last smx_recon_sample_mesh call spent in its SMX_SAMPLE_PHASES phases -- weights (classes, q_t, the
+ * sums inside a block), scan (the blocks' prefix, W, the read-back), draw -- by timed events on the call's stream; a phase a call
+ * did not reach reads 0 (a refused call publishes the weights only).  capacity >= SMX_SAMPLE_PHASES.  Zeros before the first call. */
+#define SMX_SAMPLE_PHASES 3
+int smx_recon_debug_sample_timings(smx_recon r, float* out_ms, int32_t capacity);
+
+/* smx_recon_compare_meshes: both one-sided surface distances between two triangle arrays A and B over the map, in one call.
+ * Side A->B is BY DEFINITION smx_recon_sample_mesh(A, n_samples, seed) followed by smx_recon_mesh_distance(B, those points,
+ * max_distance, cell_size, unsigned); a "none" sample is a NaN point, so the distance's n_bad_points counts it.  Side B->A swaps
+ * the roles of A and B and uses the same seed.  Per side `out` holds the smx_sample_stats, the smx_distance_stats and three
+ * exact sums over the matched samples: with d_q = (uint32)(distance * 1048576.0f) (at most 2^24, the unit is 2^-20 m) sum_d =
+ * the uint64 sum of d_q, sum_sq_lo and sum_sq_hi = the uint64 sums of (d_q*d_q) & 0xFFFFFFFF and of (d_q*d_q) >> 32; no word
+ * can overflow at 2^28 samples, and the sum of the squares is sum_sq_hi * 2^32 + sum_sq_lo.  directions: 1 = A->B only, 2 =
+ * B->A only, 3 = both; a side not asked for is all zeros.  The samples stay in the call's workspace: nothing per sample crosses
+ * to the host.  The parameter limits are those of the two calls it is made of (and directions 1 .. 3); a refusal by either half
+ * is the call's refusal, and `out` is zeroed.  The two halves run as the calls themselves do -- each side builds the grid of
+ * the mesh it measures against anew -- and publish their own timings (smx_recon_debug_sample_timings, _distance_timings: those
+ * of the last side).  Calling rules as smx_recon_sample_mesh; on_device says where both triangle arrays live.
+ * Not done: no kept index, so each side rebuilds the grid; no distance to an analytic surface. */
+typedef struct {
+  float    max_distance;     /* as smx_distance_params */
+  float    cell_size;        /* 0: the library chooses */
+  uint32_t n_samples;        /* per side */
+  uint32_t seed;
+  int32_t  directions;       /* 1: A->B, 2: B->A, 3: both */
+} smx_compare_params;
+typedef struct {
+  smx_sample_stats   sample;
+  smx_distance_stats distance;
+  uint64_t sum_d, sum_sq_lo, sum_sq_hi;
+} smx_compare_side;
+typedef struct {
+  smx_compare_side a_to_b, b_to_a;
+} smx_compare_stats;
+int smx_recon_compare_meshes(smx_recon r, smx_stream s, const smx_compare_params* p,
+                             const uint32_t* triangles_a, uint32_t n_a, const uint32_t* triangles_b, uint32_t n_b,
+                             int32_t on_device, smx_compare_stats* out);
+/* Tools: milliseconds the last smx_recon_compare_meshes call spent in its SMX_COMPARE_PHASES phases -- sample, distance, sums
+ * of side A->B, then of side B->A -- by timed events on the call's stream; a side not asked for reads 0.  capacity >=
+ * SMX_COMPARE_PHASES.  Zeros before the first call. */
+#define SMX_COMPARE_PHASES 6
+int smx_recon_debug_compare_timings(smx_recon r, float* out_ms, int32_t capacity);
 
 /* ---- rays against a triangle array: the first triangle hit, the ray parameter, the barycentrics ----
  * A pure function of the map as it stands (smooth position rows 3-5, RadiusSquared row 7, slots [0, n) with n =

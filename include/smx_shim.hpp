@@ -694,6 +694,30 @@ class CUDASurfelReconstruction {
                                            n_points ? points.data() : nullptr, n_points, n_points ? nearest->data() : nullptr,
                                            n_points ? distance->data() : nullptr, closest && n_points ? closest->data() : nullptr, 0, stats));
   }
+  // Not in the reference: n_samples points on `triangles`, drawn in proportion to area and stratified over the total area, in the
+  // order of the triangles (smx_recon_sample_mesh in smx.h).  *points gets x, y, z triples, *tri the triangle's position in the
+  // array or 0xFFFFFFFF, *bary (may be null) the pairs (v, w), *normals (may be null) the unit normals; stats may be null.
+  // Synchronous.
+  void SampleMesh(cudaStream_t stream, const std::vector<u32>& triangles, u32 n_samples, u32 seed, std::vector<float>* points,
+                  std::vector<u32>* tri, std::vector<float>* bary = nullptr, std::vector<float>* normals = nullptr,
+                  smx_sample_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles.size() / 3);
+    points->resize((size_t)3 * n_samples);
+    tri->resize(n_samples);
+    if (bary) bary->resize((size_t)2 * n_samples);
+    if (normals) normals->resize((size_t)3 * n_samples);
+    SMX_SHIM_CHECK(smx_recon_sample_mesh(handle_, stream, n_in ? triangles.data() : nullptr, n_in, n_samples, seed,
+                                         n_samples ? points->data() : nullptr, n_samples ? tri->data() : nullptr,
+                                         bary && n_samples ? bary->data() : nullptr, normals && n_samples ? normals->data() : nullptr, 0, stats));
+  }
+  // Not in the reference: both one-sided surface distances between two triangle arrays over the map, on params.n_samples
+  // samples per side that never leave the device (smx_recon_compare_meshes in smx.h).  Synchronous.
+  void CompareMeshes(cudaStream_t stream, const std::vector<u32>& triangles_a, const std::vector<u32>& triangles_b,
+                     const smx_compare_params& params, smx_compare_stats* out) {
+    const u32 n_a = (u32)(triangles_a.size() / 3), n_b = (u32)(triangles_b.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_compare_meshes(handle_, stream, &params, n_a ? triangles_a.data() : nullptr, n_a,
+                                            n_b ? triangles_b.data() : nullptr, n_b, 0, out));
+  }
   // Not in the reference: for every ray (origin, then direction: six floats) the first triangle of `triangles` it hits within
   // [params.t_min, params.t_max] (smx_recon_raycast_mesh in smx.h).  *hit gets the triangle's position in the array or
   // 0xFFFFFFFF, *t the ray parameter or +infinity, *uv (may be null) the barycentrics or NaNs; stats may be null.  Synchronous.

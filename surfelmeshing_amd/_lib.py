@@ -235,6 +235,37 @@ class DistanceStats(C.Structure):
                 [(n, C.c_uint32) for n in ("n_wide", "n_entries", "n_cells")] + [("cell_size_used", C.c_float)])
 
 
+class SampleStats(C.Structure):
+    """smx_sample_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_zero_weight", "n_samples", "n_none",
+                                           "n_triangles_hit")] + [("total_weight", C.c_uint64), ("stride", C.c_uint64)])
+
+
+SAMPLE_PHASES = 3           # SMX_SAMPLE_PHASES
+SAMPLE_MAX = 1 << 28        # the most triangles and the most samples of one call
+
+
+class CompareParams(C.Structure):
+    """smx_compare_params: the search radius and the grid's cell of the distance half, the samples per side and their seed, and
+    which sides to measure (1: A->B, 2: B->A, 3: both)."""
+    _fields_ = [("max_distance", C.c_float), ("cell_size", C.c_float), ("n_samples", C.c_uint32), ("seed", C.c_uint32),
+                ("directions", C.c_int32)]
+
+
+class CompareSide(C.Structure):
+    """smx_compare_side"""
+    _fields_ = [("sample", SampleStats), ("distance", DistanceStats), ("sum_d", C.c_uint64), ("sum_sq_lo", C.c_uint64),
+                ("sum_sq_hi", C.c_uint64)]
+
+
+class CompareStats(C.Structure):
+    """smx_compare_stats"""
+    _fields_ = [("a_to_b", CompareSide), ("b_to_a", CompareSide)]
+
+
+COMPARE_PHASES = 6          # SMX_COMPARE_PHASES
+
+
 class RaycastParams(C.Structure):
     """smx_raycast_params: the range of the ray parameter, the grid's cell (0: the library chooses) and the culling mode."""
     _fields_ = [("t_min", C.c_float), ("t_max", C.c_float), ("cell_size", C.c_float), ("cull", C.c_int32)]
@@ -358,6 +389,7 @@ EXPORTS = [
     "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
     "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
     "smx_distance_params_default", "smx_recon_mesh_distance", "smx_recon_debug_distance_timings",
+    "smx_recon_sample_mesh", "smx_recon_debug_sample_timings", "smx_recon_compare_meshes", "smx_recon_debug_compare_timings",
     "smx_raycast_params_default", "smx_recon_raycast_mesh", "smx_recon_debug_raycast_timings",
     "smx_rayscene_create", "smx_rayscene_destroy", "smx_rayscene_params_default", "smx_recon_build_rayscene", "smx_rayscene_cast",
     "smx_rayscene_debug_timings",

@@ -26,6 +26,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
                    FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
                    DIST_BINS, DIST_PHASES, DistanceParams, DistanceStats,
+                   COMPARE_PHASES, SAMPLE_MAX, SAMPLE_PHASES, CompareParams, CompareStats, SampleStats,
                    RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
                    RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
@@ -84,6 +85,45 @@ def distance_stats_dict(st):
     d["histogram"] = [int(v) for v in st.histogram]
     d["cell_size_used"] = float(st.cell_size_used)
     return d
+
+
+def sample_params(n_samples, seed=0):
+    """(n_samples, seed) of SampleMesh as integers; ValueError on what the library would refuse (and on what a uint32 cannot
+    hold), before anything is called."""
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or not 0 <= int(n_samples) <= SAMPLE_MAX:
+        raise ValueError("n_samples must be an integer within 0 .. 2^28")
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) <= 0xFFFFFFFF:
+        raise ValueError("seed must be an integer within 0 .. 2^32 - 1")
+    return int(n_samples), int(seed)
+
+
+def sample_stats_dict(st):
+    """smx_sample_stats as a dict of integers."""
+    return {n: int(getattr(st, n)) for n, _ in SampleStats._fields_}
+
+
+def compare_params(max_distance, n_samples, seed=0, cell_size=0.0, directions=3):
+    """The parameters of CompareMeshes as smx_compare_params; ValueError on what the library would refuse, before anything is
+    called."""
+    d = distance_params(max_distance, cell_size)
+    n, sd = sample_params(n_samples, seed)
+    if isinstance(directions, bool) or directions not in (1, 2, 3):
+        raise ValueError("directions must be 1 (A to B), 2 (B to A) or 3 (both)")
+    return CompareParams(d.max_distance, d.cell_size, n, sd, int(directions))
+
+
+def compare_stats_dict(st, max_distance=None):
+    """smx_compare_stats as {"a_to_b": side, "b_to_a": side}; a side: {"sample": dict, "distance": dict, "sum_d", "sum_sq_lo",
+    "sum_sq_hi": integers}.  max_distance goes into each distance dict (what the histogram's bins are fractions of)."""
+    out = {}
+    for name in ("a_to_b", "b_to_a"):
+        side = getattr(st, name)
+        dist = distance_stats_dict(side.distance)
+        if max_distance is not None:
+            dist["max_distance"] = float(max_distance)
+        out[name] = dict(sample=sample_stats_dict(side.sample), distance=dist, sum_d=int(side.sum_d), sum_sq_lo=int(side.sum_sq_lo),
+                         sum_sq_hi=int(side.sum_sq_hi))
+    return out
 
 
 def raycast_params(t_min=0.0, t_max=RAY_MAX_T, cell_size=0.0, cull=0):
@@ -1067,6 +1107,83 @@ class CUDASurfelReconstruction:
         out = (C.c_float * DIST_PHASES)()
         _lib.check(_lib.load().smx_recon_debug_distance_timings(self._h, out, C.c_int32(DIST_PHASES)))
         return dict(zip(("mark", "index", "query", "stats"), [float(v) for v in out]))
+
+    def SampleMesh(self, stream, triangles, n_samples, seed=0, return_bary=False, return_normals=False):
+        """Not in the reference: n_samples points on `triangles` ([T,3] slot indices in any order) over the map's smooth
+        positions, drawn in proportion to area, one per stratum of the total area, in the order of the triangles
+        (smx_recon_sample_mesh).  A pure function of the map, the array, n_samples and seed.  Synchronous.  `triangles` is a
+        numpy array or a contiguous device tensor (uint32 / int32); the results then are device tensors too.  Returns (points
+        [n,3] float32, tri [n] uint32 with 0xFFFFFFFF for "none", then with return_bary bary [n,2] float32, then with
+        return_normals normals [n,3] float32, then the dict of smx_sample_stats)."""
+        n, sd = sample_params(n_samples, seed)
+        st = SampleStats()
+        dev = _device_address(triangles) is not None
+        if dev:
+            import torch
+            if not (triangles.is_contiguous() and triangles.element_size() == 4 and triangles.numel() % 3 == 0):
+                raise ValueError("a device tensor must be contiguous: [T,3] 32-bit integers")
+            n_in = triangles.numel() // 3
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=triangles.device)      # noqa: E731
+            points, tri = new((n, 3), torch.float32), new(n, torch.uint32)
+            bary = new((n, 2), torch.float32) if return_bary else None
+            normals = new((n, 3), torch.float32) if return_normals else None
+            tin = triangles.data_ptr() if n_in else None
+            outs = [a.data_ptr() if a is not None and n else None for a in (points, tri, bary, normals)]
+            torch.cuda.current_stream(triangles.device).synchronize()      # (the tensor's producers; the call runs on `stream`)
+        else:
+            t = np.ascontiguousarray(triangles, np.uint32)
+            if t.size % 3:
+                raise ValueError("triangles must hold three values per row")
+            n_in = t.size // 3
+            points, tri = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+            bary = np.zeros((n, 2), np.float32) if return_bary else None
+            normals = np.zeros((n, 3), np.float32) if return_normals else None
+            tin = t.ctypes.data if n_in else None
+            outs = [a.ctypes.data if a is not None and n else None for a in (points, tri, bary, normals)]
+        _lib.check(_lib.load().smx_recon_sample_mesh(self._h, _sv(stream), C.c_void_p(tin), C.c_uint32(n_in), C.c_uint32(n), C.c_uint32(sd),
+                                                     C.c_void_p(outs[0]), C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_void_p(outs[3]),
+                                                     C.c_int32(1 if dev else 0), C.byref(st)))
+        return tuple([points, tri] + ([bary] if return_bary else []) + ([normals] if return_normals else []) + [sample_stats_dict(st)])
+
+    def debug_sample_timings(self):
+        """Milliseconds of the last SampleMesh call, by phase."""
+        out = (C.c_float * SAMPLE_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_sample_timings(self._h, out, C.c_int32(SAMPLE_PHASES)))
+        return dict(zip(("weights", "scan", "draw"), [float(v) for v in out]))
+
+    def CompareMeshes(self, stream, a, b, max_distance, n_samples, seed=0, cell_size=0.0, directions=3):
+        """Not in the reference: both one-sided surface distances between the triangle arrays a and b ([T,3] slot indices) over
+        the map (smx_recon_compare_meshes): per side n_samples points drawn on one array as SampleMesh draws them, measured
+        against the other as MeshDistance measures them, within max_distance.  The samples stay on the device.  Synchronous.
+        Both arrays are numpy arrays, or both are contiguous device tensors.  Returns the dict of compare_stats_dict."""
+        p = compare_params(max_distance, n_samples, seed, cell_size, directions)
+        st = CompareStats()
+        dev = _device_address(a) is not None or _device_address(b) is not None
+        if dev:
+            import torch
+            if _device_address(a) is None or _device_address(b) is None:
+                raise ValueError("a and b must both be device tensors, or both host arrays")
+            if not all(t.is_contiguous() and t.element_size() == 4 and t.numel() % 3 == 0 for t in (a, b)):
+                raise ValueError("device tensors must be contiguous: [T,3] 32-bit integers")
+            n_a, n_b = a.numel() // 3, b.numel() // 3
+            pa, pb = a.data_ptr() if n_a else None, b.data_ptr() if n_b else None
+            torch.cuda.current_stream(a.device).synchronize()
+        else:
+            ta, tb = np.ascontiguousarray(a, np.uint32), np.ascontiguousarray(b, np.uint32)
+            if ta.size % 3 or tb.size % 3:
+                raise ValueError("a and b must hold three values per row")
+            n_a, n_b = ta.size // 3, tb.size // 3
+            pa, pb = ta.ctypes.data if n_a else None, tb.ctypes.data if n_b else None
+        _lib.check(_lib.load().smx_recon_compare_meshes(self._h, _sv(stream), C.byref(p), C.c_void_p(pa), C.c_uint32(n_a), C.c_void_p(pb),
+                                                        C.c_uint32(n_b), C.c_int32(1 if dev else 0), C.byref(st)))
+        return compare_stats_dict(st, p.max_distance)
+
+    def debug_compare_timings(self):
+        """Milliseconds of the last CompareMeshes call, by phase and side."""
+        out = (C.c_float * COMPARE_PHASES)()
+        _lib.check(_lib.load().smx_recon_debug_compare_timings(self._h, out, C.c_int32(COMPARE_PHASES)))
+        names = ("a_to_b.sample", "a_to_b.distance", "a_to_b.sums", "b_to_a.sample", "b_to_a.distance", "b_to_a.sums")
+        return dict(zip(names, [float(v) for v in out]))
 
     def RaycastMesh(self, stream, triangles, rays, t_min=0.0, t_max=RAY_MAX_T, cell_size=0.0, cull=0, return_uv=False):
         """Not in the reference: for every ray of `rays` ([P,6] float32: origin, then direction, not normalised) the first

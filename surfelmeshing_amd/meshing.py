@@ -271,6 +271,87 @@ def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None
     return distance_summary(distance, stats), nearest, distance, stats
 
 
+def sample_mesh(rec, triangles, n_samples, seed=0, return_bary=False, return_normals=False, stream=None):
+    """n_samples points on `triangles`, drawn on the device in proportion to area and stratified over the total area: (points,
+    tri[, bary][, normals], stats) as CUDASurfelReconstruction.SampleMesh returns them.  With return_normals this is the
+    uniform-density point cloud of the mesh.  ValueError on parameters the library would refuse."""
+    from .api import sample_params
+    sample_params(n_samples, seed)
+    return rec.SampleMesh(stream, triangles, n_samples, seed, return_bary, return_normals)
+
+
+def compare_meshes(rec, a, b, max_distance, n_samples, seed=0, cell_size=0.0, directions=3, stream=None):
+    """Both one-sided surface distances between the triangle arrays a and b, on the device: the dict
+    CUDASurfelReconstruction.CompareMeshes returns (comparison_summary reads it).  ValueError on parameters the library would
+    refuse."""
+    from .api import compare_params
+    compare_params(max_distance, n_samples, seed, cell_size, directions)
+    return rec.CompareMeshes(stream, a, b, max_distance, n_samples, seed, cell_size, directions)
+
+
+def _side_summary(side):
+    """One side of compare_meshes in a few numbers, all from its integer words: the distances in units of 2^-20 m."""
+    import math
+    import struct
+    dist, n_samples = side["distance"], int(side["sample"]["n_samples"])
+    n_matched = int(dist["n_matched"])
+    unit = 2.0 ** -20
+    out = dict(n_samples=n_samples, n_none=int(side["sample"]["n_none"]), n_matched=n_matched,
+               matched_fraction=n_matched / n_samples if n_samples else 0.0, mean=None, rms=None, max=None)
+    if n_matched:
+        square_sum = (int(side["sum_sq_hi"]) << 32) + int(side["sum_sq_lo"])          # (a Python integer: it may pass 2^64)
+        out["mean"] = int(side["sum_d"]) / n_matched * unit
+        out["rms"] = math.sqrt(square_sum / n_matched) * unit
+        out["max"] = math.sqrt(struct.unpack("<f", struct.pack("<I", int(dist["max_dist2_bits"])))[0])
+    hist, max_distance = [int(v) for v in dist["histogram"]], dist.get("max_distance")
+    for q in (50, 90, 99):
+        b = None
+        if n_matched:
+            need, run = -(-q * n_matched // 100), 0
+            for b, count in enumerate(hist):
+                run += count
+                if run >= need:
+                    break
+        out["bin%d" % q] = b
+        out["p%d_below" % q] = None if b is None or max_distance is None else (b + 1) * float(max_distance) / len(hist)
+    return out
+
+
+def comparison_summary(stats):
+    """What one compare_meshes call says: per side ("a_to_b", "b_to_a"; None for a side not asked for) the matched fraction of
+    the samples, mean, rms and maximum of the matched distances from the integer words, and the upper edges of the histogram
+    bins that hold the 50 / 90 / 99 % points as distance_summary gives them; "hausdorff" = the larger one-sided maximum (None
+    without a match), and "hausdorff_is_lower_bound" = True whenever a side has samples without a match (their distance is
+    beyond max_distance, or they are "none")."""
+    out = {}
+    for name in ("a_to_b", "b_to_a"):
+        side = stats[name]
+        out[name] = _side_summary(side) if int(side["sample"]["n_samples"]) or int(side["sample"]["n_in"]) else None
+    sides = [s for s in (out["a_to_b"], out["b_to_a"]) if s is not None]
+    maxima = [s["max"] for s in sides if s["max"] is not None]
+    out["hausdorff"] = max(maxima) if maxima else None
+    out["hausdorff_is_lower_bound"] = any(s["n_matched"] < s["n_samples"] for s in sides)
+    return out
+
+
+def format_mesh_comparison(summary, names=("A", "B")):
+    """comparison_summary as a few lines."""
+    mm = lambda v: "n/a" if v is None else "%.3f mm" % (1000.0 * v)     # noqa: E731
+    lines = []
+    for key, (x, y) in (("a_to_b", (names[0], names[1])), ("b_to_a", (names[1], names[0]))):
+        s = summary[key]
+        if s is None:
+            continue
+        if not s["n_matched"]:
+            lines.append("%s -> %s: 0 of %d samples matched" % (x, y, s["n_samples"]))
+            continue
+        lines.append("%s -> %s: %d of %d samples matched (%.1f %%): mean %s, rms %s, max %s; 50 / 90 / 99 %% below %s / %s / %s" % (
+            x, y, s["n_matched"], s["n_samples"], 100.0 * s["matched_fraction"], mm(s["mean"]), mm(s["rms"]), mm(s["max"]),
+            mm(s["p50_below"]), mm(s["p90_below"]), mm(s["p99_below"])))
+    lines.append("Hausdorff distance %s %s" % (">=" if summary["hausdorff_is_lower_bound"] else "=", mm(summary["hausdorff"])))
+    return "\n".join(lines)
+
+
 def build_ray_scene(rec, triangles, cell_size=0.0, occupancy=0, stream=None):
     """A RayScene of `triangles` over the map as it stands (CUDASurfelReconstruction.BuildRayScene): build it once, then pass it
     as scene= to cast_rays, vertex_visibility or render.raycast_mesh_view as often as needed.  It is a snapshot: later changes

@@ -68,7 +68,13 @@ phases, and the min and max of its cast + stats over the repetitions: the spread
 grid's size and set bits, the scene's device memory, cast + stats as the median, min and max of --reps casts with device
 arrays, and the five work counters per ray; the bytes of every cast are compared with the call's.  The last two lines say whether
 a cast without a grid stays within the call's cast + stats plus the spread, and whether the smallest grid that fits pays by the
-rule of DESIGN.md 5m.  Writes profiles/rayscene_bench.{txt,json} unless --txt / --json say otherwise."""
+rule of DESIGN.md 5m.  Writes profiles/rayscene_bench.{txt,json} unless --txt / --json say otherwise.
+
+--sample N[,N...] measures smx_recon_sample_mesh on the full mesh of the same map and on its decimation at each
+--decimate cell size, for every sample count given; --compare N measures smx_recon_compare_meshes, the full mesh against each
+decimated one with N samples per side within --compare_distance.  Per call and per phase by the library's events; a traffic
+model against the HBM peak; the full triangulation re-measured beside it.  Writes profiles/sample_bench.{txt,json} unless --txt /
+--json say otherwise."""
 import argparse
 import json
 import os
@@ -90,6 +96,9 @@ ap.add_argument("--fill", type=int, nargs="?", const=8, default=None, metavar="E
 ap.add_argument("--small_target", type=int, default=50_000, help="with --fill: live surfels of the second, 160 x 120 map (0 = none)")
 ap.add_argument("--distance", default=None, metavar="METRES[,METRES...]", help="measure smx_recon_mesh_distance at these max_distance values")
 ap.add_argument("--points", type=int, default=1_000_000, help="with --distance: query points on the analytic room surface")
+ap.add_argument("--sample", default=None, metavar="N[,N...]", help="measure smx_recon_sample_mesh at these sample counts")
+ap.add_argument("--compare", type=int, default=0, metavar="N", help="measure smx_recon_compare_meshes, full mesh against each --decimate mesh, N samples per side")
+ap.add_argument("--compare_distance", type=float, default=0.05, metavar="METRES", help="with --compare: max_distance")
 ap.add_argument("--raycast", default=None, metavar="WxH", help="measure smx_recon_raycast_mesh with the camera rays of the bench pose")
 ap.add_argument("--scene", action="store_true", help="with --raycast: measure smx_rayscene (build by phase, cast for every occupancy setting) "
                                                       "beside smx_recon_raycast_mesh, on the full mesh and the one decimated at the first --decimate cell")
@@ -657,6 +666,142 @@ def distance_main():
     nn.close()
 
 
+SAMPLE_PHASES = ("weights", "scan", "draw")
+COMPARE_PHASES = ("a_to_b.sample", "a_to_b.distance", "a_to_b.sums", "b_to_a.sample", "b_to_a.distance", "b_to_a.sums")
+
+
+def sample_traffic_bytes(n, n_in, n_samples, st, bary=True, normals=True):
+    """HBM bytes of one smx_recon_sample_mesh call, by phase, from its statistics: a lower bound.  Gathers are counted once per
+    distinct target (the S and the N record of a corner in the weights, the S record in the draw); the draw reads the blocks'
+    offsets once, one 64-byte line of the in-block sums and the index triple per triangle hit, and writes the outputs."""
+    nb = n_in // 256 + 1
+    weights = 12 * n_in + 32 * min(n, 3 * n_in) + 8 * n_in + 8 * nb
+    scan = 16 * nb
+    hit = st["n_triangles_hit"]
+    draw = 8 * nb + (64 + 12) * hit + 16 * min(n, 3 * hit) + (12 + 4 + (8 if bary else 0) + (12 if normals else 0)) * n_samples
+    return dict(zip(SAMPLE_PHASES, (weights, scan, draw)))
+
+
+def sample_main():
+    import ctypes as C
+    from surfelmeshing_amd import meshing
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    counts = [int(c) for c in args.sample.split(",")] if args.sample else []
+    cells = [float(c) for c in args.decimate.split(",")] if args.decimate else []
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri = api.CUDABuffer(1, 3 * cap, np.uint32)
+    P = max(counts + [1])
+    dpts, dti, dbary, dnrm = (api.CUDABuffer(1, k * P, np.float32 if k != 1 else np.uint32) for k in (3, 1, 2, 3))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def full():
+        T, st = C.c_uint32(0), _lib.MeshStats()
+        _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address),
+                                           C.c_uint32(cap), C.c_int32(1), C.byref(T), C.byref(st)))
+        return T.value
+
+    def sample(src, n_in, count):
+        st = _lib.SampleStats()
+        _lib.check(L.smx_recon_sample_mesh(rec._h, None, C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in), C.c_uint32(count), C.c_uint32(0),
+                                           C.c_void_p(dpts.ToCUDA().address), C.c_void_p(dti.ToCUDA().address), C.c_void_p(dbary.ToCUDA().address),
+                                           C.c_void_p(dnrm.ToCUDA().address), C.c_int32(1), C.byref(st)))
+        return api.sample_stats_dict(st)
+
+    def compare(a, n_a, b, n_b):
+        prm, st = api.compare_params(args.compare_distance, args.compare), _lib.CompareStats()
+        _lib.check(L.smx_recon_compare_meshes(rec._h, None, C.byref(prm), C.c_void_p(a.ToCUDA().address), C.c_uint32(n_a),
+                                              C.c_void_p(b.ToCUDA().address), C.c_uint32(n_b), C.c_int32(1), C.byref(st)))
+        return api.compare_stats_dict(st, args.compare_distance)
+    t_full = []
+    for _ in range(args.reps + 1):
+        ms, T_in = timed(full)
+        t_full.append(ms)
+    full_ms = float(np.median(t_full[1:]))
+    say("full triangulation, re-measured here: %d triangles, one call %.2f ms" % (T_in, full_ms))
+    inputs = [("full mesh", dtri, T_in)]
+    for cell in cells:
+        T, st = C.c_uint32(0), _lib.DecimateStats()
+        buf = api.CUDABuffer(1, 3 * max(1, T_in), np.uint32)
+        _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                             C.c_void_p(buf.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(T), C.byref(st)))
+        inputs.append(("decimated at %g m" % cell, buf, T.value))
+    sample_rows, compare_rows = [], []
+    for what, src, n_in in inputs:
+        for count in counts:
+            t, phs, st, first = [], [], None, None
+            for _ in range(args.reps + 1):
+                ms, st = timed(lambda: sample(src, n_in, count))
+                t.append(ms)
+                phs.append(rec.debug_sample_timings())
+                head = dpts.Download()[0][:100000].tobytes() + dti.Download()[0][:100000].tobytes()
+                first = head if first is None else first
+                assert head == first, "two calls gave different bytes"
+            med = float(np.median(t[1:]))                       # (the first call allocates the workspace)
+            ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in SAMPLE_PHASES}
+            b = sample_traffic_bytes(n, n_in, count, st)
+            tot = sum(b.values())
+            say("sample %s, %d samples: %d triangles (%d not live, %d repeated, %d out of range, %d of zero weight), W 2^%.2f, %d none, %d "
+                "triangles hit | call %.2f ms (min %.2f, max %.2f) = %.3f x the full triangulation, %.1f M samples/s | %s | model %.3f GB -> "
+                "%.0f %% of the %.1f TB/s HBM peak (%s)" % (
+                    what, count, n_in, st["n_not_live"], st["n_repeated"], st["n_out_of_range"], st["n_zero_weight"],
+                    np.log2(max(st["total_weight"], 1)), st["n_none"], st["n_triangles_hit"], med, min(t[1:]), max(t[1:]), med / full_ms,
+                    count / (med * 1e-3) / 1e6, " ".join("%s %.3f" % (k, ph[k]) for k in SAMPLE_PHASES), tot / 1e9,
+                    100.0 * tot / (med * 1e-3) / HBM_PEAK, HBM_PEAK / 1e12,
+                    " ".join("%s %.0f %%" % (k, 100.0 * b[k] / (max(ph[k], 1e-6) * 1e-3) / HBM_PEAK) for k in SAMPLE_PHASES)))
+            sample_rows.append({"input": what, "samples": count, "triangles_in": n_in, "reps": len(t) - 1, "call_ms": med, "call_ms_all": t[1:],
+                                "phases_ms": ph, "samples_per_s": count / (med * 1e-3), "stats": st, "traffic_model_bytes": b,
+                                "fraction_of_hbm_peak": tot / (med * 1e-3) / HBM_PEAK, "ratio_to_full_triangulation": med / full_ms})
+    if args.compare:
+        for what, src, n_in in inputs[1:]:
+            t, phs, st, first = [], [], None, None
+            for _ in range(args.reps + 1):
+                ms, st = timed(lambda: compare(dtri, T_in, src, n_in))
+                t.append(ms)
+                phs.append(rec.debug_compare_timings())
+                first = st if first is None else first
+                assert st == first, "two calls gave different statistics"
+            med = float(np.median(t[1:]))
+            ph = {k: float(np.median([q[k] for q in phs[1:]])) for k in COMPARE_PHASES}
+            summary = meshing.comparison_summary(st)
+            say("compare full mesh (%d triangles) with %s (%d triangles), %d samples per side within %g m | call %.2f ms (min %.2f, max %.2f) "
+                "= %.2f x the full triangulation | %s" % (T_in, what, n_in, args.compare, args.compare_distance, med, min(t[1:]), max(t[1:]),
+                                                         med / full_ms, " ".join("%s %.2f" % (k, ph[k]) for k in COMPARE_PHASES)))
+            for line in meshing.format_mesh_comparison(summary, ("full", "decimated")).split("\n"):
+                say("  " + line)
+            compare_rows.append({"a": "full mesh", "b": what, "triangles_a": T_in, "triangles_b": n_in, "samples": args.compare,
+                                 "max_distance": args.compare_distance, "reps": len(t) - 1, "call_ms": med, "call_ms_all": t[1:], "phases_ms": ph,
+                                 "stats": st, "summary": summary, "ratio_to_full_triangulation": med / full_ms})
+    res = {"metric": "sample_mesh_ms", "slots": n, "live": live, "triangles_in": T_in, "full_triangulation_ms": full_ms,
+           "sample_rows": sample_rows, "compare_rows": compare_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "sample_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "sample_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 def update_main():
     import ctypes as C
     _lib.require_gpu()
@@ -1054,4 +1199,4 @@ def main():
 
 
 if __name__ == "__main__":
-    (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -8,6 +8,8 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
                               [--mesh_eval METRES] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
+                              [--mesh_compare_samples N [--mesh_compare_distance METRES]]
+                              [--export_mesh_samples FILE.ply --mesh_samples N]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
@@ -27,6 +29,9 @@ limits of the triangle filter the new triangles have to pass (default 10 / 170 d
 prints one summary line per measurement: with --synthetic the noise-free surface points of the integrated frames (every 8th
 pixel) against the final mesh -- with --track that is what the tracker's drift does to the surface --, with --mesh_decimate the
 fine mesh's vertices against the decimated one.  Without --synthetic and without --mesh_decimate the flag is refused.
+--mesh_compare_samples N prints, for every stage of the chain that was asked for (cleaning, hole filling, decimation), the
+two-sided surface error between the mesh before and after it on N area-weighted samples per side (smx_recon_compare_meshes).
+--export_mesh_samples FILE.ply with --mesh_samples N writes N such samples of the final mesh with the face normals.
 --render_source mesh (with --mesh or --mesh_every) makes --render_dir / --render_every / --render_overview draw the current
 mesh with smx_recon_render_mesh instead of splats: the kept array of --mesh_every as of its last update, otherwise a
 triangulation of the map as it stands, cleaned, filled and decimated first if those flags are given.
@@ -201,6 +206,15 @@ def parse_args(argv=None):
     ap.add_argument("--mesh_eval_rays_frames", type=int, default=0, metavar="N",
                     help="with --synthetic N --mesh: build one ray-casting scene (smx_rayscene) of the final mesh and cast the rays of "
                          "--mesh_eval_rays for each of the last N integrated frames against it: one line per frame and a total")
+    ap.add_argument("--mesh_compare_samples", type=int, default=0, metavar="N",
+                    help="with --mesh_decimate, --mesh_fill_holes or the cleaning flags: print the two-sided surface error between "
+                         "the mesh before and after each such stage, on N area-weighted samples per side (smx_recon_compare_meshes)")
+    ap.add_argument("--mesh_compare_distance", type=float, default=0.05, metavar="METRES",
+                    help="with --mesh_compare_samples: how far a sample may lie from the other mesh and still match (default 0.05)")
+    ap.add_argument("--export_mesh_samples", metavar="FILE.ply",
+                    help="with --mesh or --mesh_every and --mesh_samples N: write N area-weighted samples of the final mesh, with the "
+                         "face normals, as a point cloud of uniform density (smx_recon_sample_mesh)")
+    ap.add_argument("--mesh_samples", type=int, default=0, metavar="N", help="the number of samples of --export_mesh_samples")
     ap.add_argument("--track", action="store_true",
                     help="track the camera against the map instead of reading the poses from the trajectory file")
     ap.add_argument("--track_write_trajectory", help="with --track: write the poses of the integrated frames (TUM format)")
@@ -259,7 +273,30 @@ def parse_args(argv=None):
         ap.error("--mesh_eval_rays_frames needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.render_source == "mesh" and not (args.mesh or args.mesh_every > 0):
         ap.error("--render_source mesh needs a mesh to draw: add --mesh or --mesh_every")
+    if not 0 <= args.mesh_compare_samples <= 1 << 28:
+        ap.error("--mesh_compare_samples needs a count within 0 .. 2^28")
+    if args.mesh_compare_samples:
+        if not (args.mesh or args.mesh_every > 0):
+            ap.error("--mesh_compare_samples needs --mesh or --mesh_every")
+        if args.mesh_decimate is None and args.mesh_fill is None and args.mesh_clean is None:
+            ap.error("--mesh_compare_samples has no two meshes to compare: it needs --mesh_decimate, --mesh_fill_holes or a cleaning flag")
+        if not 1e-3 <= args.mesh_compare_distance <= 16.0:
+            ap.error("--mesh_compare_distance needs a distance within 0.001 .. 16 metres")
+    if not 0 <= args.mesh_samples <= 1 << 28:
+        ap.error("--mesh_samples needs a count within 0 .. 2^28")
+    if bool(args.export_mesh_samples) != bool(args.mesh_samples):
+        ap.error("--export_mesh_samples FILE.ply and --mesh_samples N go together")
+    if args.export_mesh_samples and not (args.mesh or args.mesh_every > 0):
+        ap.error("--export_mesh_samples needs --mesh or --mesh_every")
     return args
+
+
+def print_mesh_comparison(args, rec, stage, before, after):
+    """The lines of --mesh_compare_samples for one stage of the mesh chain."""
+    from surfelmeshing_amd import meshing
+    stats = meshing.compare_meshes(rec, before, after, args.mesh_compare_distance, args.mesh_compare_samples)
+    print("surface error of %s within %g m, %d samples per side:" % (stage, args.mesh_compare_distance, args.mesh_compare_samples))
+    print(meshing.format_mesh_comparison(meshing.comparison_summary(stats), ("before", "after")))
 
 
 def format_ray_eval(hit, t, d, frame, head="surface error along the rays"):
@@ -406,17 +443,22 @@ def main():
     if args.mesh_clean is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
-        n_before = triangles.shape[0]
+        n_before, before = triangles.shape[0], triangles
         triangles, cst = meshing.clean_map_mesh(rec, triangles, **args.mesh_clean)
         print("cleaned in %.1f ms: components %d in / %d kept (the largest has %d triangles), triangles %d in / %d out" % (
             1e3 * (time.time() - t1), cst["n_components"], cst["n_kept_components"], cst["n_largest_triangles"], n_before,
             triangles.shape[0]))
+        if args.mesh_compare_samples:
+            print_mesh_comparison(args, rec, "the cleaning", before, triangles)
     if args.mesh_fill is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
+        before = triangles
         triangles, fst = meshing.fill_map_mesh(rec, triangles, **args.mesh_fill)
         print("holes of up to %d edges filled in %.1f ms: %s" % (args.mesh_fill["max_hole_edges"], 1e3 * (time.time() - t1),
                                                                  ", ".join("%s %d" % (k, fst[k]) for k in meshing.FILL_STAT_NAMES)))
+        if args.mesh_compare_samples:
+            print_mesh_comparison(args, rec, "the hole filling", before, triangles)
     if args.mesh_decimate is not None:
         from surfelmeshing_amd import meshing
         t1 = time.time()
@@ -424,6 +466,8 @@ def main():
         triangles, dst = meshing.decimate_map_mesh(rec, triangles, args.mesh_decimate)
         print("decimated at %g m in %.1f ms: %s" % (args.mesh_decimate, 1e3 * (time.time() - t1),
                                                     ", ".join("%s %d" % (k, dst[k]) for k in meshing.DECIMATE_STAT_NAMES)))
+        if args.mesh_compare_samples:
+            print_mesh_comparison(args, rec, "the decimation", fine, triangles)
     if args.mesh_eval is not None:
         from surfelmeshing_amd import meshing
         if args.mesh_decimate is not None:
@@ -467,6 +511,12 @@ def main():
     if args.export_mesh:
         export.SaveMeshAsOBJ(rec, args.export_mesh, triangles=triangles, referenced_only=args.mesh_decimate is not None or args.mesh_clean is not None)
         print("Wrote %s." % args.export_mesh)
+    if args.export_mesh_samples:
+        from surfelmeshing_amd import meshing
+        points, tri_of, normals, sst = meshing.sample_mesh(rec, triangles, args.mesh_samples, return_normals=True)
+        keep = tri_of != np.uint32(0xFFFFFFFF)
+        export.write_ply(args.export_mesh_samples, points[keep], normals=normals[keep])
+        print("Wrote %s: %d samples of %d triangles (%d hit)." % (args.export_mesh_samples, int(keep.sum()), triangles.shape[0], sst["n_triangles_hit"]))
     if args.export_point_cloud:
         export.SavePointCloudAsPLY(rec, args.export_point_cloud, export_colors=True)
         print("Wrote %s." % args.export_point_cloud)
