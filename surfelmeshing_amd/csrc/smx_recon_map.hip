@@ -14,6 +14,7 @@
 
 #include "smx_recon_state.hpp"
 #include "smx_mesh.hpp"
+#include "smx_splat.hpp"
 
 using namespace smx;
 
@@ -195,15 +196,6 @@ k_vis_fill(Surfels S, VisColor vc, uint32_t latest_triangulated, uint32_t latest
   }
 }
 
-struct RenderCtx {
-  double L[12];   // camera_T_global (inverted on the host in double precision)
-  Mat34 Lf;       // ... rounded to float: the rotation part is exact (a transpose), used for the normal image
-  double fx, fy, cx, cy, near_z, far_z;
-  double half_extent;   // square mode
-  double disc_factor, max_extent, f_max;   // disc mode (f_max = max(fx, fy))
-  int W, H, mode;
-};
-
 // z-test: the smaller (depth bits, slot) key wins; a plain load first, so that a hidden splat costs no atomic
 __device__ __forceinline__ void render_zmin(unsigned long long* p, unsigned long long key) {
   if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
@@ -214,51 +206,33 @@ __device__ __forceinline__ void render_zmin(unsigned long long* p, unsigned long
 // The geometry is evaluated in double precision: neighbouring discs of one surface meet a pixel's ray at depths only
 // 1e-6 apart, and a float evaluation would order them by its rounding errors; the key then holds the depth as a float.
 __global__ void __launch_bounds__(kBlock)
-k_render_splat(Surfels S, RenderCtx rc, unsigned long long* __restrict__ zbuf, const DevState* st) {
+k_render_splat(Surfels S, SplatCam rc, unsigned long long* __restrict__ zbuf, const DevState* st) {
   const uint32_t N = st->surfel_count;
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < N; i += gridDim.x * kBlock) {
     const float4 nr = *S.group(kGroupN, i);
-    if (!(nr.w >= 0.0f)) continue;                       // merged
+    if (!sp_live(nr.w)) continue;                        // merged
     const float4 sp = *S.group(kGroupS, i);
-    const double* L = rc.L;
-    const double px = sp.x, py = sp.y, pz = sp.z;
-    const double cz = L[8] * px + L[9] * py + L[10] * pz + L[11];
-    if (!(cz > rc.near_z && cz < rc.far_z)) continue;
-    const double cx = L[0] * px + L[1] * py + L[2] * pz + L[3], cy = L[4] * px + L[5] * py + L[6] * pz + L[7];
-    const double u = rc.fx * cx / cz + rc.cx, v = rc.fy * cy / cz + rc.cy;
-    if (!(fabs(u) < 1e8 && fabs(v) < 1e8)) continue;   // (far outside any image; keeps the conversions below defined)
-    double e = rc.half_extent, rho = 0.0;
-    if (rc.mode == SMX_SPLAT_DISC) {
-      rho = rc.disc_factor * sqrt((double)nr.w);
-      const double dz = cz - rho;
-      e = dz <= rc.near_z ? rc.max_extent : fmin(rc.max_extent, 2.0 * rc.f_max * rho / dz);
-    }
-    // pixels whose centre x + 1/2 lies within e of u: u - e - 1/2 <= x <= u + e - 1/2 (square mode, h = 0: floor(u))
-    const bool point = rc.mode == SMX_SPLAT_SQUARE && e == 0.0;
-    const double x0f = point ? floor(u) : ceil(u - e - 0.5), x1f = point ? floor(u) : floor(u + e - 0.5);
-    const double y0f = point ? floor(v) : ceil(v - e - 0.5), y1f = point ? floor(v) : floor(v + e - 0.5);
-    const int x0 = (int)fmax(x0f, 0.0), x1 = (int)fmin(x1f, (double)(rc.W - 1));
-    const int y0 = (int)fmax(y0f, 0.0), y1 = (int)fmin(y1f, (double)(rc.H - 1));
+    const double cz = sp_depth(rc, sp.x, sp.y, sp.z);
+    if (!sp_in_range(rc, cz)) continue;
+    SplatSlot s;
+    if (!sp_project(rc, sp.x, sp.y, sp.z, cz, &s)) continue;   // (far outside any image)
+    sp_extent(rc, nr.w, &s);
+    sp_rect(rc, &s);
     if (rc.mode == SMX_SPLAT_SQUARE) {
-      const unsigned long long key = ((unsigned long long)__float_as_uint((float)cz) << 32) | i;
-      for (int y = y0; y <= y1; ++y)
-        for (int x = x0; x <= x1; ++x) render_zmin(&zbuf[(size_t)y * rc.W + x], key);
+      const unsigned long long key = sp_key(cz, i);
+      for (int y = s.y0; y <= s.y1; ++y)
+        for (int x = s.x0; x <= s.x1; ++x) render_zmin(&zbuf[(size_t)y * rc.W + x], key);
     } else {
-      const double nx = L[0] * nr.x + L[1] * nr.y + L[2] * nr.z, ny = L[4] * nr.x + L[5] * nr.y + L[6] * nr.z;
-      const double nz = L[8] * nr.x + L[9] * nr.y + L[10] * nr.z;
-      const double n_dot_c = nx * cx + ny * cy + nz * cz;
-      const double rho2 = rho * rho;
-      for (int y = y0; y <= y1; ++y) {
-        const double dy = ((double)y + 0.5 - rc.cy) / rc.fy;
-        for (int x = x0; x <= x1; ++x) {
-          const double dx = ((double)x + 0.5 - rc.cx) / rc.fx;
-          const double n_dot_d = nx * dx + ny * dy + nz;
-          if (fabs(n_dot_d) < 1e-4) continue;
-          const double t = n_dot_c / n_dot_d;
-          if (!(t > rc.near_z)) continue;
-          const double ex = t * dx - cx, ey = t * dy - cy, ez = t - cz;
-          if (ex * ex + ey * ey + ez * ez <= rho2)
-            render_zmin(&zbuf[(size_t)y * rc.W + x], ((unsigned long long)__float_as_uint((float)t) << 32) | i);
+      const SplatDisc d = sp_disc(rc, s, nr.x, nr.y, nr.z);
+      for (int y = s.y0; y <= s.y1; ++y) {
+        const double dy = sp_ray_y(rc, y);
+        for (int x = s.x0; x <= s.x1; ++x) {
+          const double dx = sp_ray_x(rc, x);
+          const double n_dot_d = sp_n_dot_d(d, dx, dy);
+          if (sp_edge_on(n_dot_d)) continue;
+          const double t = sp_plane_depth(d, n_dot_d);
+          if (!sp_in_front(rc, t)) continue;
+          if (sp_within_disc(s, d, t, dx, dy)) render_zmin(&zbuf[(size_t)y * rc.W + x], sp_key(t, i));
         }
       }
     }
@@ -267,21 +241,22 @@ k_render_splat(Surfels S, RenderCtx rc, unsigned long long* __restrict__ zbuf, c
 
 // One thread per pixel: decode the key, gather only the winner's records.
 __global__ void __launch_bounds__(kBlock)
-k_render_resolve(Surfels S, RenderCtx rc, VisColor vc, const unsigned long long* __restrict__ zbuf,
+k_render_resolve(Surfels S, SplatCam rc, VisColor vc, const unsigned long long* __restrict__ zbuf,
                  Img<float> depth, Img<uint32_t> index, Img<float4> normal, Img<uint32_t> color) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= rc.W || y >= rc.H) return;
   const unsigned long long key = zbuf[(size_t)y * rc.W + x];
-  const bool empty = key == ~0ull;
-  const uint32_t slot = empty ? kInvalid : (uint32_t)key;
-  if (depth.address) depth(y, x) = empty ? 0.0f : __uint_as_float((uint32_t)(key >> 32));
+  const bool empty = sp_key_empty(key);
+  const uint32_t slot = sp_key_slot(key);
+  if (depth.address) depth(y, x) = sp_key_depth(key);
   if (index.address) index(y, x) = slot;
   if (normal.address) {
     float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (!empty) {
       const float4 nr = *S.group(kGroupN, slot);
-      const Vec3 n = rotate(rc.Lf, Vec3{nr.x, nr.y, nr.z});
-      o = make_float4(n.x, n.y, n.z, 0.0f);
+      float n[3];
+      sp_rotate_normal(rc.Lf, nr.x, nr.y, nr.z, n);
+      o = make_float4(n[0], n[1], n[2], 0.0f);
     }
     normal(y, x) = o;
   }
@@ -525,13 +500,8 @@ int smx_recon_render(smx_recon r, smx_stream s, const smx_render_params* p, cons
   const size_t px = (size_t)W * H;
   SMX_CALL(render_begin(r, st, px));
   unsigned long long* zbuf = r->render.zbuf.get();
-  RenderCtx rc;
-  mr_invert_pose(p->global_T_camera, rc.L);
-  rc.Lf = se3_inverse(p->global_T_camera);
-  rc.fx = p->fx; rc.fy = p->fy; rc.cx = p->cx; rc.cy = p->cy; rc.near_z = p->near_z; rc.far_z = p->far_z;
-  rc.half_extent = p->splat_half_extent_in_pixels;
-  rc.disc_factor = p->disc_radius_factor; rc.max_extent = p->max_splat_extent_in_pixels; rc.f_max = std::max(p->fx, p->fy);  // (float fields widened to double)
-  rc.W = W; rc.H = H; rc.mode = p->splat_mode;
+  SplatCam rc;
+  sp_make_cam(*p, &rc);   // (float fields widened to double)
   VisColor vc;
   vc.frame = p->frame_index; vc.window = p->surfel_integration_active_window_size; vc.flags = p->color_flags;
   SMX_HIP(hipMemsetAsync(zbuf, 0xFF, px * sizeof(unsigned long long), st));

@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import splat_ref as sp
 import viz_ref as vr
 from common import ROOT, assert_surfels_match, run_both, small_stream
 from test_gpu_parity import _compare_state, _pipes
@@ -129,6 +130,11 @@ def test_render_matches_the_reference(smx, grown, mode, h, size):
         rel = np.abs(got["depth"][same] - ref["depth"][same]) / ref["depth"][same]
         assert rel.max() <= 1e-5, rel.max()
         _check_invariants(got, rows, T, vr.VIS_RADII, 15, INT_MAX)
+        # ... and bit for bit against the exact model: no tolerance, no pixel excused
+        exact = sp.render(rows, n, w, hh, fx, fy, cx, cy, T, mode=sp.DISC if mode == "disc" else sp.SQUARE, half_extent=h,
+                          color_flags=vr.VIS_RADII, frame_index=15)
+        for k in sp.IMAGES:
+            assert np.ascontiguousarray(got[k]).tobytes() == np.ascontiguousarray(exact[k]).tobytes(), (k, T)
 
 
 def _check_invariants(got, rows, T, flags, frame, window):
