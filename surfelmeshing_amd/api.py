@@ -1618,7 +1618,9 @@ class SurfelNeighborIndex:
         return cnt, d2, idx
 
     def set_query_mode(self, mode):
-        """A/B switch (results identical): 0 = LDS-staged brick tiles, 1 = one wavefront per query through L1 / L2."""
+        """A/B switch (results identical): 2 = one lane per query, the tile kernel for what it marks (k_query_lanes; the
+        default), 0 = one wavefront per query over LDS-staged brick tiles (k_query_tiles alone), 1 = one wavefront per query
+        through L1 / L2 (k_query_stream; the self-query entry point has no such kernel and runs mode 0 there)."""
         _lib.check(_lib.load().smx_nn_set_query_mode(self._h, C.c_int32(mode)))
 
     def set_stats_enabled(self, enabled, stream=None):
