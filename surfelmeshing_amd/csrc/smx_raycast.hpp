@@ -1,11 +1,14 @@
-// smx_raycast.hpp -- rays against a triangle array over the map (smx_recon_raycast_mesh).
+// smx_raycast.hpp -- rays against a triangle array over the map: the one traversal of smx_recon_raycast_mesh and
+// of a kept scene (smx_rayscene).
 //
 // Part 1: the arithmetic of the contract and the traversal as plain inline functions (the BAD test of a ray, the candidate test
 // of step 3 with its key, the inflated box of a triangle, the saturating cell function, the dominant axis and its layers, the t
-// interval and the cell rectangle of one layer, the exit test, the walk of one ray).  smx_raycast.hip calls them from its
-// kernels; a test compiles this part alone for the host (SMX_RAYCAST_HOST_ONLY) and walks the same passes with plain words.
+// interval and the cell rectangle of one layer, the exit test, the look-up of a cell behind an optional occupancy bit grid, the
+// walk of a run of records that keeps the winner's (u, v, det), the walk of one ray).  smx_raycast.hip calls them from its
+// kernels; the ray host tests compile this part alone for the host (SMX_RAYCAST_HOST_ONLY) and walk the same passes with plain words.
 // The classes of step 1, the cell key, the cell table and the packed records are the triangle grid's (smx_trigrid.hpp).
-// Part 2: the counter words and the workspace the object keeps for the call (kernels and glue: smx_raycast.hip).
+// Part 2: the counter words, an index a cast can read, a cast's workspace and the host functions of a cast, and the workspace
+// the object keeps for the one-shot call (kernels and glue: smx_raycast.hip).
 #pragma once
 
 #include <stdint.h>
@@ -159,11 +162,11 @@ SMX_RAY_FN RayRect ray_layer_rect(const RayAxes& r, float cell, float t_min, flo
 SMX_RAY_FN uint32_t ray_rect_cells(const RayRect& q) {
   return (q.b0 > q.b1 || q.c0 > q.c1) ? 0u : ((uint32_t)(q.b1 - q.b0) + 1u) * ((uint32_t)(q.c1 - q.c0) + 1u);
 }
-// cell number j (0 <= j < ray_rect_cells) of layer m's rectangle, b fastest, as the key of the cell table
-SMX_RAY_FN unsigned long long ray_rect_key(const RayAxes& r, const RayRect& q, uint32_t m, uint32_t j) {
+// cell number j (0 <= j < ray_rect_cells) of layer m's rectangle, b fastest
+SMX_RAY_FN void ray_rect_cell(const RayAxes& r, const RayRect& q, uint32_t m, uint32_t j, int32_t* x, int32_t* y, int32_t* z) {
   const uint32_t nb = (uint32_t)(q.b1 - q.b0) + 1u;
   const int32_t a = r.first + r.sgn * (int32_t)m, b = q.b0 + (int32_t)(j % nb), c = q.c0 + (int32_t)(j / nb);
-  return r.axis == 0 ? dec_cell_key(a, b, c) : (r.axis == 1 ? dec_cell_key(b, a, c) : dec_cell_key(b, c, a));
+  if (r.axis == 0) { *x = a; *y = b; *z = c; } else if (r.axis == 1) { *x = b; *y = a; *z = c; } else { *x = b; *y = c; *z = a; }
 }
 // After layer m: may the walk stop?  Yes once the layer of H_a(t_best) lies strictly before layer m + 1: every candidate not
 // yet met has its H in a later layer, so by monotonicity a larger t and a larger key.
@@ -173,17 +176,49 @@ SMX_RAY_FN bool ray_done(const RayAxes& r, float cell, unsigned long long best, 
   return at < 0 || (uint32_t)at < next_layer;
 }
 
-// The smallest key over records [first, end), stepping by `stride` (the lanes of a wavefront share a run).
+// ---- the occupancy bit grid in front of the cell table (built by a scene, smx_rayscene.hpp) ---------------------------------
+// It spans the occupied cell box from lo on; a block is 2^k cells per axis.  k < 0: no grid, and every cell goes to the table.
+// nb = 0 on every axis: the box is empty, and so is the grid.
+struct RayGrid { int32_t lo[3]; uint32_t nb[3]; int32_t k; };
+// The bit number of the block of cell (x, y, z); false for a cell outside the box (the traversal asks about none: ray_axes and
+// ray_span clamp to the occupied box).
+SMX_RAY_FN bool ray_grid_bit(const RayGrid& g, int32_t x, int32_t y, int32_t z, unsigned long long* bit) {
+  const uint32_t bx = (uint32_t)(x - g.lo[0]) >> g.k, by = (uint32_t)(y - g.lo[1]) >> g.k, bz = (uint32_t)(z - g.lo[2]) >> g.k;
+  if (x < g.lo[0] || y < g.lo[1] || z < g.lo[2] || bx >= g.nb[0] || by >= g.nb[1] || bz >= g.nb[2]) return false;
+  *bit = ((unsigned long long)bz * g.nb[1] + by) * g.nb[0] + bx;
+  return true;
+}
+struct RayWork { uint32_t layers, bit_tests, lookups, misses, tests; };
+// The look-up of one cell: with a grid a clear bit is "no run" and a set bit goes on to the table; without one the table is
+// asked at once.  Bits: bool test(unsigned long long bit).
+template <class Bits, class Tab>
+SMX_RAY_FN bool ray_find(const RayGrid& g, const Bits& bits, const Tab& tab, uint32_t mask, int32_t x, int32_t y, int32_t z, uint32_t* first,
+                         uint32_t* end, RayWork* w) {
+  if (g.k >= 0) {
+    unsigned long long bit;
+    ++w->bit_tests;
+    if (!ray_grid_bit(g, x, y, z, &bit) || !bits.test(bit)) return false;
+  }
+  ++w->lookups;
+  const bool found = tg_table_find(tab, mask, dec_cell_key(x, y, z), first, end);
+  if (!found) ++w->misses;
+  return found;
+}
+
+// The smallest key over records [first, end), stepping by `stride` (the lanes of a wavefront share a run), and what the lane's
+// own smallest key came with: a cast reads no map, so the winner's (u, v) and the sign of det are taken from the lane that
+// computed the winning key.  Any lane with that key computed it from the same three corners by the same expressions.
+struct RayKeep { unsigned long long own; float u, v, det; };
 template <class Recs>
 SMX_RAY_FN unsigned long long ray_walk(const Recs& recs, uint32_t first, uint32_t end, uint32_t stride, const TgVec& O, const TgVec& D,
-                                       float t_min, float t_max, int cull, unsigned long long best, uint32_t* tests) {
+                                       float t_min, float t_max, int cull, unsigned long long best, RayKeep* keep, uint32_t* tests) {
   for (uint32_t j = first; j < end; j += stride) {
     TgVec A, B, C;
     uint32_t i;
-    RayHit h;
+    RayHit h{0.0f, 0.0f, 0.0f, 0.0f};
     recs.load(j, &A, &B, &C, &i);
     const unsigned long long key = ray_key(O, D, A, B, C, i, t_min, t_max, cull, &h);
-    best = key < best ? key : best;
+    if (key < best) { best = key; keep->own = key; keep->u = h.u; keep->v = h.v; keep->det = h.det; }
     ++*tests;
   }
   return best;
@@ -191,24 +226,25 @@ SMX_RAY_FN unsigned long long ray_walk(const Recs& recs, uint32_t first, uint32_
 
 // One ray's view of the cast: the wide list, then layer after layer.  k_ray_cast makes the same look-ups 64 layers at a time and
 // walks the same records with its lanes sharing a run; the host walk calls this as it stands.  Seen: void operator()(cell key)
-// for every cell looked up (the tests' completeness check); early_exit = false walks every layer.
-struct RayWork { uint32_t layers, lookups, tests; };
-template <class Tab, class Recs, class Seen>
-SMX_RAY_FN unsigned long long ray_cast_one(const Tab& tab, uint32_t mask, const Recs& cell_recs, const Recs& wide_recs, uint32_t n_wide,
-                                           const RayAxes& r, const TgVec& O, const TgVec& D, float cell, float t_min, float t_max, int cull,
-                                           bool early_exit, Seen& seen, RayWork* work) {
-  unsigned long long best = ray_walk(wide_recs, 0, n_wide, 1, O, D, t_min, t_max, cull, kTgNone, &work->tests);
+// for every cell looked up in the table (the tests' completeness check); early_exit = false walks every layer.
+template <class Bits, class Tab, class Recs, class Seen>
+SMX_RAY_FN unsigned long long ray_cast_one(const RayGrid& g, const Bits& bits, const Tab& tab, uint32_t mask, const Recs& cell_recs,
+                                           const Recs& wide_recs, uint32_t n_wide, const RayAxes& r, const TgVec& O, const TgVec& D, float cell,
+                                           float t_min, float t_max, int cull, bool early_exit, Seen& seen, RayKeep* keep, RayWork* work) {
+  unsigned long long best = ray_walk(wide_recs, 0, n_wide, 1, O, D, t_min, t_max, cull, kTgNone, keep, &work->tests);
   for (uint32_t m = 0; m < r.n_layers; ++m) {
     if (early_exit && ray_done(r, cell, best, m)) break;
     const RayRect q = ray_layer_rect(r, cell, t_min, t_max, m);
     const uint32_t cells = ray_rect_cells(q);
     ++work->layers;
     for (uint32_t j = 0; j < cells; ++j) {
-      const unsigned long long key = ray_rect_key(r, q, m, j);
+      int32_t x, y, z;
       uint32_t first, end;
-      seen(key);
-      ++work->lookups;
-      if (tg_table_find(tab, mask, key, &first, &end)) best = ray_walk(cell_recs, first, end, 1, O, D, t_min, t_max, cull, best, &work->tests);
+      ray_rect_cell(r, q, m, j, &x, &y, &z);
+      const uint32_t before = work->lookups;
+      const bool found = ray_find(g, bits, tab, mask, x, y, z, &first, &end, work);
+      if (work->lookups != before) seen(dec_cell_key(x, y, z));
+      if (found) best = ray_walk(cell_recs, first, end, 1, O, D, t_min, t_max, cull, best, keep, &work->tests);
     }
   }
   return best;
@@ -216,28 +252,73 @@ SMX_RAY_FN unsigned long long ray_cast_one(const Tab& tab, uint32_t mask, const 
 
 #if !defined(SMX_RAYCAST_HOST_ONLY)
 // ---- part 2 ----------------------------------------------------------------------------------------------------------
-// the words of the device counters behind the grid's; the 64-bit words as (lo, hi) pairs.  k_ray_stats adds to the four counts
-// and to the three sums from every wavefront: they sit in different 64-byte blocks, as atomics on one block queue behind each
-// other.
-enum : int { kRayBadRays = kTgWords, kRayHits, kRayFrontHits, kRayMaxBits, kRayLayersLo = (kRayMaxBits / 16 + 1) * 16, kRayLayersHi, kRayLookupsLo, kRayLookupsHi,
-             kRayTestsLo, kRayTestsHi, kRayWords };
-static_assert(kRayMaxBits < kRayLayersLo && kRayLayersLo % 16 == 0, "the counts, then the sums in a block of their own");
+// the words of a cast's counters, a block of their own; the 64-bit words as (lo, hi) pairs
+enum : int { kRayBadRays = 0, kRayHits, kRayFrontHits, kRayMaxBits, kRayLayersLo, kRayLayersHi, kRayBitTestsLo, kRayBitTestsHi, kRayLookupsLo,
+             kRayLookupsHi, kRayMissesLo, kRayMissesHi, kRayTestsLo, kRayTestsHi, kRayWords = 16 };
+enum : uint32_t { kRayWorkWords = 8 };                      // per ray: layers, bit tests, look-ups, misses, pair tests, flags, -, -
 
-constexpr int kRayBlock = 256;                               // rays per workgroup of k_ray_stats (k_ray_cast: 4 rays)
+constexpr int kRayBlock = 256;                               // lanes per workgroup of the ray kernels (k_ray_cast: 4 rays)
 constexpr int kRayWaves = kRayBlock / 64;
 
-// The workspace, a member of smx_recon_s.  Each buffer grows on demand; the call is synchronous, so nothing
-// reads a block that goes.  smx_recon_build_rayscene builds with `grid` and `in` too, into a scene's records and table.
-struct RaycastWork {
-  TgWork grid;                             // the build's
-  DevBuf<float> recs, wide_recs;           // [n_entries] / [n_wide] TgRec, the first in the sorted order
-  DevBuf<unsigned long long> table;        // [table entries][2] TgCell
+struct RayBits {
+  const uint32_t* w;
+  __device__ __forceinline__ bool test(unsigned long long bit) const { return (w[bit >> 5] >> (uint32_t)(bit & 31u)) & 1u; }
+};
+struct RayBox { int32_t lo[3], hi[3]; };                     // the occupied cell box (lo > hi: no cell is occupied)
+
+// An index a cast can read: views, it owns nothing.  The one-shot call fills it from its workspace, a scene from what it keeps.
+struct RayIndex {
+  const TgCell* table; uint32_t mask;
+  const TgRec* recs; const TgRec* wide_recs;
+  uint32_t n_entries, n_wide;
+  float cell; RayBox occ;
+  RayGrid grid; const uint32_t* bits;      // grid.k < 0: none, and bits is not read
+  const uint32_t* built;                   // the build's counter words on the device where the index was built for this cast alone
+};
+// cell and the occupied box of an index from the build's counter words as tg_read_counts brought them to the host
+inline void ray_index_read(RayIndex* ix, const uint32_t* h) {
+  memcpy(&ix->cell, &h[kTgCellBits], sizeof(float));
+  for (int a = 0; a < 3; ++a) { ix->occ.lo[a] = (int32_t)h[kTgOccLo + a]; ix->occ.hi[a] = (int32_t)h[kTgOccHi + a]; }
+}
+
+// What a cast needs beside an index.  Each buffer grows on demand; a cast is synchronous, so nothing reads a block that goes.
+struct RayCastWork {
   DevBuf<unsigned long long> best;         // [n_rays] the winning key of every ray
-  DevBuf<uint32_t> work;                   // [n_rays][4] layers, look-ups, pair tests, flags of every ray
-  DevBuf<uint32_t> in;                     // staging when the caller's arrays are host memory
-  DevBuf<float> rays, out_t, out_uv;
+  DevBuf<uint32_t> work;                   // [n_rays][kRayWorkWords]
+  DevBuf<float> rays, out_t, out_uv;       // staging when the caller's arrays are host memory
   DevBuf<uint32_t> out_hit;
   DevBuf<uint32_t> counters;               // [kRayWords]
+  unsigned long long bytes() const;        // device memory held
+};
+// The device side of a cast's arrays: the caller's own, or the staging.
+struct RayCastArrays { const float* rays; uint32_t* hit; float* t; float* uv; };
+
+// A cast in four steps, which smx_recon_raycast_mesh and smx_rayscene_cast take in this order behind their argument checks, with
+// what is their own between them (smx_raycast.hip).  First the overlap check, without touching any object; `fn` names the caller
+// and `what` the input in the text.
+int ray_cast_overlap(const char* fn, const char* what, const void* in, size_t in_bytes, uint32_t n_rays, const uint32_t* hit, const float* t,
+                     const float* uv);
+// Every reservation of the cast, the rays staged in, the counters zeroed: nothing is allocated after it.
+int ray_cast_stage(RayCastWork& w, const float* rays, uint32_t n_rays, uint32_t* hit, float* t, float* uv, bool on_device, hipStream_t st,
+                   RayCastArrays* d);
+// The cast kernel: the thin one over the build's counter words where ix.built is set, the one that takes the grid, c and the
+// box by value otherwise.  The caller stamps the end of its cast phase behind it.
+int ray_cast_launch(RayCastWork& w, const RayIndex& ix, const smx_raycast_params* p, const RayCastArrays& d, uint32_t n_rays, hipStream_t st);
+// The stats kernel, the copy-back of staged outputs, the counter read-back and the fill of *out; with built_cells the cell count
+// of ix.built comes to the host in the same wait.  Returns after the stream has been waited for; the caller stamps the end of
+// its stats phase.
+int ray_cast_finish(RayCastWork& w, const RayIndex& ix, const RayCastArrays& d, uint32_t n_rays, uint32_t* hit, float* t, float* uv, bool on_device,
+                    hipStream_t st, smx_rayscene_cast_stats* out, uint32_t* built_cells = nullptr);
+
+// The workspace of smx_recon_raycast_mesh, a member of smx_recon_s.  smx_recon_build_rayscene builds with `grid`
+// and `in` too, into a scene's records and table.
+struct RaycastWork {
+  TgWork grid;                             // the build's
+  DevBuf<uint32_t> in;                     // staging when the caller's triangles are host memory
+  DevBuf<uint32_t> counters;               // [kTgWords] the build's
+  DevBuf<float> recs, wide_recs;           // [n_entries] / [n_wide] TgRec, the first in the sorted order
+  DevBuf<unsigned long long> table;        // [table entries][2] TgCell
+  RayCastWork cast;
   PhaseStamps<SMX_RAY_PHASES> stamps;      // of the last call; a refused call publishes the phases it completed
 };
 

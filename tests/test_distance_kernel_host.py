@@ -6,54 +6,18 @@ own main: it reads a case file and writes a result file) and walks mark, index, 
 forwards, backwards and in a seeded shuffled order -- with plain words behind the table operations.  Every output byte and
 every statistic has to equal the brute-force model of tests/distance_ref.py, as on the device.  The same program is also
 built with -fsanitize=address,undefined and run directly."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import distance_ref as dr
-from common import ROOT
-
-SRC = os.path.join(ROOT, "surfelmeshing_amd", "csrc")
+import ray_host
 
 PROGRAM = r'''
 #define SMX_DISTANCE_HOST_ONLY 1
 #include "smx_distance.hpp"
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <numeric>
-#include <random>
-#include <vector>
-using namespace smx;
-
-struct Entry { unsigned long long key, value; };
-struct Tab {                         // one lane at a time: the operations on plain words
-  Entry* e;
-  unsigned long long key(uint32_t h) const { return e[h].key; }
-  unsigned long long value(uint32_t h) const { return e[h].value; }
-  unsigned long long claim(uint32_t h, unsigned long long expected, unsigned long long desired) const {
-    const unsigned long long old = e[h].key;
-    if (old == expected) e[h].key = desired;
-    return old;
-  }
-  void bump(uint32_t h, unsigned long long inc) const { e[h].value += inc; }
-};
-struct Rec { TgVec a, b, c; uint32_t t; };
-struct Recs {
-  const Rec* r;
-  void load(uint32_t j, TgVec* A, TgVec* B, TgVec* C, uint32_t* t) const { *A = r[j].a; *B = r[j].b; *C = r[j].c; *t = r[j].t; }
-};
-
-static std::vector<uint32_t> lanes(uint32_t count, uint32_t order) {
-  std::vector<uint32_t> l(count);
-  std::iota(l.begin(), l.end(), 0u);
-  if (order == 1) std::reverse(l.begin(), l.end());
-  if (order > 1) { std::mt19937 g(order); std::shuffle(l.begin(), l.end(), g); }
-  return l;
-}
-
+''' + ray_host.GRID_BUILD + r'''
 enum { N_IN = 0, N_NOT_LIVE, N_REPEATED, N_RANGE, N_POINTS, N_BAD, N_MATCHED, MAX_BITS, HIST, N_WIDE = HIST + 32, N_ENTRIES, N_CELLS, CELL, WORDS };
 
 // Returns 0, or -1 (an index out of range).
@@ -62,63 +26,20 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
   for (int k = 0; k < WORDS; ++k) stats[k] = 0;
   stats[N_IN] = n_in; stats[N_POINTS] = n_points;
   auto pos = [&](uint32_t i) { return TgVec{S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2]}; };
-  auto live = [&](uint32_t i) { return dec_live(S[4 * (size_t)i], S[4 * (size_t)i + 1], S[4 * (size_t)i + 2], S[4 * (size_t)i + 3]); };
   auto point = [&](uint32_t p) { return TgVec{pts[3 * (size_t)p], pts[3 * (size_t)p + 1], pts[3 * (size_t)p + 2]}; };
-  // k_dist_classify, k_dist_cell
-  std::vector<uint32_t> mark(n_in, 0);
-  unsigned long long extent = 0;
-  uint32_t in_r = 0;
-  for (uint32_t t : lanes(n_in, order)) {
-    const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-    if (i0 >= n || i1 >= n || i2 >= n) return -1;
-    const TgVec a = pos(i0), b = pos(i1), c = pos(i2);
-    const uint32_t cls = tg_classify(i0, i1, i2, live(i0), live(i1), live(i2), a, b, c);
-    if (cls == kTgDropNotLive) ++stats[N_NOT_LIVE];
-    if (cls == kTgDropRepeated) ++stats[N_REPEATED];
-    if (cls == kTgDropRange) ++stats[N_RANGE];
-    if (cls == kTgInR) { mark[t] = 1; ++in_r; extent += (unsigned long long)(tg_extent(a, b, c) * 1048576.0f); }
-  }
-  float given = cell_size;
-  if (!(cell_size > 0.0f)) given = in_r != 0 ? (float)((double)extent / (double)in_r * (1.0 / 1048576.0)) : 0.0f;
-  const float cell = dist_cell_size(given, max_distance);
+  // mark and index: the exact boxes, c >= 1.125 max_distance
+  HostGrid g;
+  if (host_tg_build(n, S, tri, n_in, cell_size, order, [&](float given) { return dist_cell_size(given, max_distance); }, tg_box, &g) != 0) return -1;
+  const float cell = g.cell;
+  const uint32_t mask = g.mask;
+  const Tab tab = g.tab();
+  const std::vector<uint32_t>& wide_t = g.wide_t;
+  stats[N_NOT_LIVE] = g.n_not_live; stats[N_REPEATED] = g.n_repeated; stats[N_RANGE] = g.n_range;
+  stats[N_WIDE] = (uint32_t)wide_t.size(); stats[N_ENTRIES] = g.E; stats[N_CELLS] = g.n_cells;
   __builtin_memcpy(&stats[CELL], &cell, 4);
-  // k_dist_mark: the wide list in arrival order; the scan
-  std::vector<uint32_t> wide_t;
-  auto box_of = [&](uint32_t t) { return tg_box(pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), cell); };
-  for (uint32_t t : lanes(n_in, order)) {
-    if (mark[t] == 0) continue;
-    mark[t] = tg_mark(box_of(t));
-    if (mark[t] == kTgWide) wide_t.push_back(t);
-  }
-  std::vector<uint32_t> off(n_in + 1, 0);
-  for (uint32_t t = 0; t < n_in; ++t) off[t + 1] = off[t] + (mark[t] == kTgWide ? 0u : mark[t]);
-  const uint32_t E = off[n_in];
-  stats[N_WIDE] = (uint32_t)wide_t.size(); stats[N_ENTRIES] = E;
-  // k_dist_entries, the stable sort, k_dist_records
-  std::vector<unsigned long long> keys(E);
-  std::vector<uint32_t> vals(E);
-  for (uint32_t t : lanes(n_in, order)) {
-    const uint32_t count = mark[t] == kTgWide ? 0u : mark[t];
-    if (count == 0) continue;
-    const TgBox box = box_of(t);
-    for (uint32_t j = 0; j < count; ++j) { keys[off[t] + j] = tg_box_key(box, j); vals[off[t] + j] = t; }
-  }
-  std::vector<uint32_t> perm(E);
-  std::iota(perm.begin(), perm.end(), 0u);
-  std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return keys[x] < keys[y]; });
-  std::vector<unsigned long long> skeys(E);
-  std::vector<Rec> recs(E), wide_recs(wide_t.size());
-  auto rec_of = [&](uint32_t t) { return Rec{pos(tri[3 * (size_t)t]), pos(tri[3 * (size_t)t + 1]), pos(tri[3 * (size_t)t + 2]), t}; };
-  for (uint32_t j = 0; j < E; ++j) { skeys[j] = keys[perm[j]]; recs[j] = rec_of(vals[perm[j]]); }
-  for (size_t j = 0; j < wide_t.size(); ++j) wide_recs[j] = rec_of(wide_t[j]);
-  // k_dist_table
-  const uint32_t entries = dec_table_size(E), mask = entries - 1;
-  std::vector<Entry> table(entries, Entry{kTgEmpty, 0});
-  Tab tab{table.data()};
-  for (uint32_t j : lanes(E, order)) stats[N_CELLS] += tg_table_entry(tab, mask, skeys.data(), E, j) ? 1u : 0u;
   // k_dist_query, k_dist_stats
   const float max2 = max_distance * max_distance;
-  const Recs cell_recs{recs.data()}, wrecs{wide_recs.data()};
+  const Recs cell_recs{g.recs.data()}, wrecs{g.wide_recs.data()};
   for (uint32_t p : lanes(n_points, order)) {
     const TgVec P = point(p);
     unsigned long long key = kTgNone;
@@ -143,9 +64,6 @@ static int host_distance(uint32_t n, const float* S, const uint32_t* tri, uint32
   }
   return 0;
 }
-
-template <class T> static bool get(FILE* f, T* p, size_t count) { return count == 0 || fread(p, sizeof(T), count, f) == count; }
-template <class T> static void put(FILE* f, const T* p, size_t count) { if (count) fwrite(p, sizeof(T), count, f); }
 
 // case file: u32 n, n_in, n_points, signed, n_orders; f32 max_distance, cell_size; u32 orders[]; f32 S[n][4]; u32 tri[n_in][3];
 //            f32 points[n_points][3]
@@ -181,16 +99,6 @@ ORDERS = (0, 1, 7)      # forwards, backwards, shuffled with seed 7
 WORDS = 8 + 32 + 4
 
 
-def _build(d, flags, name):
-    src = d / "distance_host.cpp"
-    src.write_text(PROGRAM)
-    exe = d / name
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall"] + flags + ["-I", SRC, "-I", os.path.join(ROOT, "include"),
-                        str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return str(exe)
-
-
 @pytest.fixture(scope="module")
 def work(tmp_path_factory):
     return tmp_path_factory.mktemp("distance_host")
@@ -198,12 +106,12 @@ def work(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def program(work):
-    return _build(work, [], "distance_host")
+    return ray_host.build(work, PROGRAM, [], "distance_host")
 
 
 @pytest.fixture(scope="module")
 def sanitized(work):
-    return _build(work, ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "distance_host_san")
+    return ray_host.build(work, PROGRAM, ray_host.SANITIZE, "distance_host_san")
 
 
 def host_distance(exe, work, pos, r2, tri, points, max_distance, cell_size=0.0, signed=False):

@@ -1,13 +1,15 @@
-"""python tools/isa_compare.py <old tree> <new tree> [old=new ...]: is the device code of two checkouts the same, kernel by kernel?
+"""python tools/isa_compare.py <old tree> <new tree> [old=new ...] [-gone ...]: is the device code of two checkouts the same, kernel by kernel?
 
 Every file of build.SOURCES is compiled device-only to gfx950 assembly in both trees (the flags of tools/isa_regs.sh).  Per
 kernel: the descriptor's registers, LDS and scratch, and the instruction stream with comments and directives dropped,
 basic-block labels renumbered and symbol names demangled without "(anonymous namespace)::" and "smx::" (the method of
 profiles/recon_split_isa.txt).  Prints one line per kernel and the number that differ; needs no GPU.  A source file the old
 tree does not have yet is compiled in the new tree alone and its kernels are listed as "new".  Kernels are matched by that
-demangled name without its parameter list, so a parameter type that moved between namespaces is no rename; a kernel that
-was renamed or folded into another is matched through an `old=new` argument (k_track_solve_rgbd=k_track_solve), and where
-the new tree differs both trees' figures are printed."""
+demangled name without its parameter list, across the files, so a parameter type that moved between namespaces is no rename and
+a kernel that moved to another file is found there ("was ... in ..."); a kernel that was renamed or folded into another is
+matched through an `old=new` argument (k_track_solve_rgbd=k_track_solve); where the new tree differs both trees' figures are
+printed, and a kernel of the old tree that the new one no longer has is listed as "gone": it has to be named by a `-name`
+argument, or the comparison fails ("GONE"), so that no kernel vanishes by accident."""
 import os
 import re
 import shutil
@@ -63,7 +65,7 @@ def by_plain_name(k):
     return {re.sub(r"\(.*$", "", p).replace("void ", ""): k[n] for n, p in zip(k, demangle(list(k)) if k else [])}
 
 
-def main(old, new, renames):
+def main(old, new, renames, may_go):
     tmp = tempfile.mkdtemp(prefix="isa_compare_")
     jobs = []
     for src in SOURCES:
@@ -71,30 +73,35 @@ def main(old, new, renames):
         have = [os.path.exists(os.path.join(root, "surfelmeshing_amd", "csrc", src)) for root in (old, new)]
         jobs.append((src, outs, [compile_to_asm(root, src, out) if h else None for root, out, h in zip((old, new), outs, have)]))
     print("%-70s %-18s %5s %5s %6s %7s %7s  %s" % ("kernel", "file", "vgpr", "sgpr", "lds", "scratch", "instrs", "verdict"))
-    total = differ = 0
+    was, now = {}, []                       # old: plain name -> (file, kernel); new: (plain name, file, kernel) in file order
     for src, outs, procs in jobs:
         if any(p is not None and p.wait() != 0 for p in procs) or procs[1] is None:
             raise SystemExit("hipcc failed on " + src)
-        kn = kernels(outs[1])
-        if procs[0] is None:
-            for name, pretty in zip(kn, demangle(list(kn)) if kn else []):
-                print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (re.sub(r"\(.*$", "", pretty)[:70], src, *kn[name][0], kn[name][2], "new"))
+        if procs[0] is not None:
+            was.update({name: (src, k) for name, k in by_plain_name(kernels(outs[0])).items()})
+        now += [(name, src, k) for name, k in by_plain_name(kernels(outs[1])).items()]
+    back = {n: o for o, n in renames.items()}
+    total, differ, row = len(was), 0, "%-70s %-18s %5d %5d %6d %7d %7d  %s"
+    for n, src, k in now:
+        o = back.get(n, n)
+        if o not in was:
+            print(row % (n[:70], src, *k[0], k[2], "new"))
             continue
-        ko = kernels(outs[0])
-        ko, kn = by_plain_name(ko), by_plain_name(kn)
-        pairs = [(o, renames.get(o, o)) for o in ko]
-        if any(n not in kn for _, n in pairs) or set(kn) - {n for _, n in pairs}:
-            raise SystemExit("%s: the two trees do not have the same kernels: %s" % (src, sorted(set(ko) ^ set(kn))))
-        for o, n in pairs:
-            same = ko[o][:2] == kn[n][:2]
-            total, differ = total + 1, differ + (not same)
-            if not same:
-                print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % ((o + " (old tree)")[:70], src, *ko[o][0], ko[o][2], ""))
-            print("%-70s %-18s %5d %5d %6d %7d %7d  %s" % (n[:70], src, *kn[n][0], kn[n][2], "identical" if same else "DIFFERS"))
+        old_src, ko = was.pop(o)
+        same = ko[:2] == k[:2]
+        differ += not same
+        moved = ", was %s in %s" % (o, old_src) if (o, old_src) != (n, src) else ""
+        if not same:
+            print(row % ((o + " (old tree)")[:70], old_src, *ko[0], ko[2], ""))
+        print(row % (n[:70], src, *k[0], k[2], ("identical" if same else "DIFFERS") + moved))
+    lost = [o for o in was if o not in may_go]
+    for o, (old_src, ko) in was.items():
+        print(row % ((o + " (old tree)")[:70], old_src, *ko[0], ko[2], "GONE" if o in lost else "gone"))
     shutil.rmtree(tmp)
-    print("%d kernels, %d differ" % (total, differ))
-    return 1 if differ else 0
+    print("%d kernels of the old tree, %d differ, %d gone (%d not named)" % (total, differ, len(was), len(lost)))
+    return 1 if differ or lost else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2]), dict(a.split("=") for a in sys.argv[3:])))
+    sys.exit(main(os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2]), dict(a.split("=") for a in sys.argv[3:] if not a.startswith("-")),
+                  {a[1:] for a in sys.argv[3:] if a.startswith("-")}))
