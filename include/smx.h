@@ -1264,7 +1264,8 @@ int smx_recon_debug_sample_timings(smx_recon r, float* out_ms, int32_t capacity)
  * is the call's refusal, and `out` is zeroed.  The two halves run as the calls themselves do -- each side builds the grid of
  * the mesh it measures against anew -- and publish their own timings (smx_recon_debug_sample_timings, _distance_timings: those
  * of the last side).  Calling rules as smx_recon_sample_mesh; on_device says where both triangle arrays live.
- * Not done: no kept index, so each side rebuilds the grid; no distance to an analytic surface. */
+ * This call keeps no index, so each side rebuilds the grid; one side against a kept index is smx_recon_compare_to_distscene
+ * below.  Not done: no distance to an analytic surface. */
 typedef struct {
   float    max_distance;     /* as smx_distance_params */
   float    cell_size;        /* 0: the library chooses */
@@ -1411,7 +1412,7 @@ int smx_recon_debug_raycast_timings(smx_recon r, float* out_ms, int32_t capacity
  *    per-ray keys and work words) happens before the first write to an output.  One caller thread per scene.  A cast does
  *    not touch r.
  * All scene memory is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation.
- * Not done: a kept index for smx_recon_mesh_distance; incremental updates of a scene; ray packets; a BVH; watertightness; an
+ * (The kept index of smx_recon_mesh_distance is smx_distscene below.)  Not done: incremental updates of a scene; ray packets; a BVH; watertightness; an
  * enqueue-only cast without host synchronisation. */
 typedef struct smx_rayscene_s* smx_rayscene;
 typedef struct {
@@ -1446,6 +1447,78 @@ int smx_rayscene_cast(smx_rayscene sc, smx_stream s, const smx_raycast_params* p
  * SMX_RAYSCENE_PHASES. */
 #define SMX_RAYSCENE_PHASES 5
 int smx_rayscene_debug_timings(smx_rayscene sc, float* out_ms, int32_t capacity);
+
+/* ---- a distance scene: the search structure of smx_recon_mesh_distance built once, queried many times ----
+ * smx_distscene is a SNAPSHOT of a triangle array over the map together with its search structure, for one distance bound.
+ * After a build a query reads neither the map nor the caller's triangle array: its answer is what smx_recon_mesh_distance
+ * gives on the map as it stood at the build, with the same triangles, and stays so through later smx_recon_integrate,
+ * smx_recon_compact and smx_recon_deform_by_creation_frame calls, through a smx_recon_debug_upload_surfels that moves or kills
+ * slots, and after smx_recon_destroy of the object it was built from.  nearest stays "position in the array given at the
+ * build".  There is nothing that could go stale, hence no generation counter.
+ * Build (smx_recon_build_distscene).  Steps 1 and 5 of smx_recon_mesh_distance unchanged: the classes, R, the exact boxes, the
+ *    wide list, the entries, the packed corner records in the sorted order, the cell table, with c = max(cell_size, 1.125f *
+ *    max_distance), or at cell_size == 0 the library's choice of that call; smx_distscene_stats holds step 1's counts and step
+ *    5's structure words with the same meaning, and max_distance = the bound.  Behind them first_rec: per input triangle t of R
+ *    the smallest position among the records that hold t, a position in the cell records, or a position in the wide list with
+ *    the top bit set (a triangle is in cells or on the wide list, never both); 0xFFFFFFFF outside R.  Refused like that call:
+ *    an index >= n, more than 2^30 entries, max_distance outside 1e-3f .. 16.0f, cell_size not 0 or finite and > 0, n_in >
+ *    2^28, triangles == NULL with n_in > 0; also a scene and an object on different devices.  Ordered after everything enqueued
+ *    on r, synchronous; changes in r only what smx_recon_mesh_distance changes (its workspace holds the sort's buffers).
+ *    Building into a scene that holds a build replaces it.  A scene never built, or whose last build was refused or failed for
+ *    any reason (an allocation included), is EMPTY: it holds no records, table or first_rec and refuses every query.  n_in == 0
+ *    is a valid build (every point answers "none").  device_bytes = the device memory the scene holds after the build (records,
+ *    table, first_rec, counters, and the query workspace as it stands).
+ * Query (smx_distscene_query).  p->cell_size must be 0; p->max_distance = q must lie in 1e-3f .. the scene's max_distance, a
+ *    larger one is SMX_ERR_INVALID_ARGUMENT with nothing written.  A smaller one needs no new structure: the 27 cells around a
+ *    point's own hold every candidate as soon as c >= 1.125f * q, and float32 multiplication is monotone.  signed_distance, BAD
+ *    points, the key, the outputs and the overlap rule are exactly those of smx_recon_mesh_distance: nearest, distance, closest
+ *    and every word of smx_distance_stats are byte for byte what that call writes on the map as it stood at the build with the
+ *    same triangles, max_distance = q and cell_size = the scene's cell_size_used (both sides then have the same c, so n_wide,
+ *    n_entries and n_cells agree too).  The winner's closest point and sign are recomputed from the corners its first record
+ *    holds: the float32 words the map held.  Synchronous.  on_device says where points, nearest, distance and closest live.
+ *    n_points == 0 is valid; closest and stats may be NULL; points must not overlap an output (refused).  A query on an empty
+ *    scene: SMX_ERR_INVALID_ARGUMENT.  A refused query writes nothing; every allocation (point staging, the points' sort
+ *    buffers, the per-point keys) happens before the first write to an output.  One caller thread per scene.  A query does not
+ *    touch r.
+ * smx_recon_compare_to_distscene is BY DEFINITION smx_recon_sample_mesh(triangles, n_samples, seed) on r's map as it stands,
+ *    then smx_distscene_query of those points (max_distance, unsigned, closest NULL), then the three exact sums of
+ *    smx_recon_compare_meshes.  While the map is unchanged since the build, `out` equals the a_to_b side of
+ *    smx_recon_compare_meshes with A = triangles, B = the scene's triangles, cell_size = the scene's cell_size_used and
+ *    directions 1.  The samples never leave the device.  r and sc on different devices: refused.  A refusal by either half is the
+ *    call's refusal, and `out` is zeroed.  on_device says where triangles lives.
+ * All scene memory is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation.
+ * Not done: incremental updates of a scene; an index shared with a smx_rayscene (their boxes differ); a BVH; an enqueue-only
+ * query without host synchronisation; point-to-mesh registration on top of the scene. */
+typedef struct smx_distscene_s* smx_distscene;
+typedef struct {
+  float max_distance;        /* the bound: a query asks for this much or less */
+  float cell_size;           /* as smx_distance_params.cell_size; 0: the library chooses */
+} smx_distscene_params;
+typedef struct {
+  uint32_t n_in, n_not_live, n_repeated, n_out_of_range;   /* as smx_distance_stats */
+  uint32_t n_wide, n_entries, n_cells;
+  float    cell_size_used;
+  float    max_distance;              /* the bound of the build */
+  uint64_t device_bytes;              /* device memory the scene holds after the build */
+} smx_distscene_stats;
+int smx_distscene_create(int32_t device_id /* -1: the current device */, smx_distscene* out);
+int smx_distscene_destroy(smx_distscene sc);
+int smx_distscene_params_default(smx_distscene_params* out);   /* 0.05f, 0.0f */
+int smx_recon_build_distscene(smx_recon r, smx_stream s, smx_distscene sc, const smx_distscene_params* p,
+                              const uint32_t* triangles, uint32_t n_in, int32_t on_device,
+                              smx_distscene_stats* stats /* may be NULL */);
+int smx_distscene_query(smx_distscene sc, smx_stream s, const smx_distance_params* p,
+                        const float* points /* [n_points][3] */, uint32_t n_points,
+                        uint32_t* nearest /* [n_points] */, float* distance /* [n_points] */,
+                        float* closest /* [n_points][3], may be NULL */,
+                        int32_t on_device, smx_distance_stats* stats /* may be NULL */);
+int smx_recon_compare_to_distscene(smx_recon r, smx_stream s, smx_distscene sc, float max_distance, uint32_t n_samples, uint32_t seed,
+                                   const uint32_t* triangles, uint32_t n_in, int32_t on_device, smx_compare_side* out);
+/* Tools: milliseconds of the last build's phases mark, index, first (first_rec), then of the last query's phases query (the
+ * points' sort, the walk), stats, by timed events on the calls' streams; a phase not reached reads 0.  capacity >=
+ * SMX_DISTSCENE_PHASES. */
+#define SMX_DISTSCENE_PHASES 5
+int smx_distscene_debug_timings(smx_distscene sc, float* out_ms, int32_t capacity);
 
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----

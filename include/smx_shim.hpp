@@ -492,6 +492,39 @@ class RayScene {
   smx_rayscene_stats stats_{};
 };
 
+// Not in the reference: a snapshot of a triangle array over the map with the search structure of
+// CUDASurfelReconstruction::MeshDistance (smx_distscene in smx.h), built once by CUDASurfelReconstruction::BuildDistanceScene
+// for one bound on max_distance and queried many times; it outlives the map it was built from.  stats() are those of the last
+// build.
+class DistanceScene {
+ public:
+  explicit DistanceScene(int device_id = -1) {
+    SMX_SHIM_CHECK(smx_distscene_create(device_id, &handle_));
+  }
+  DistanceScene(const DistanceScene&) = delete;
+  DistanceScene& operator=(const DistanceScene&) = delete;
+  ~DistanceScene() { SMX_SHIM_CHECK(smx_distscene_destroy(handle_)); }
+  // *nearest, *distance and *closest (may be null) as CUDASurfelReconstruction::MeshDistance fills them; params.cell_size must
+  // be 0 and params.max_distance at most the bound of the build.  Synchronous.
+  void Query(cudaStream_t stream, const std::vector<float>& points, const smx_distance_params& params, std::vector<u32>* nearest,
+             std::vector<float>* distance, std::vector<float>* closest = nullptr, smx_distance_stats* stats = nullptr) {
+    const u32 n_points = (u32)(points.size() / 3);
+    nearest->resize(n_points);
+    distance->resize(n_points);
+    if (closest) closest->resize((size_t)3 * n_points);
+    SMX_SHIM_CHECK(smx_distscene_query(handle_, stream, &params, n_points ? points.data() : nullptr, n_points,
+                                       n_points ? nearest->data() : nullptr, n_points ? distance->data() : nullptr,
+                                       closest && n_points ? closest->data() : nullptr, 0, stats));
+  }
+  const smx_distscene_stats& stats() const { return stats_; }
+  smx_distscene handle() const { return handle_; }
+
+ private:
+  friend class CUDASurfelReconstruction;
+  smx_distscene handle_ = nullptr;
+  smx_distscene_stats stats_{};
+};
+
 class CUDASurfelReconstruction {
  public:
   // The three cudaGraphicsResource_t arguments and the render window of the reference's constructor are
@@ -742,6 +775,26 @@ class CUDASurfelReconstruction {
     p.occupancy = occupancy;
     const u32 n_in = (u32)(triangles.size() / 3);
     SMX_SHIM_CHECK(smx_recon_build_rayscene(handle_, stream, scene->handle_, &p, n_in ? triangles.data() : nullptr, n_in, 0, &scene->stats_));
+  }
+  // Not in the reference: (re)builds `scene` from `triangles` over the map as it stands, for queries within max_distance
+  // (smx_recon_build_distscene in smx.h); cell_size 0 leaves the cell to the library.  Synchronous.  A refused build leaves the
+  // scene empty.
+  void BuildDistanceScene(cudaStream_t stream, const std::vector<u32>& triangles, DistanceScene* scene, float max_distance,
+                          float cell_size = 0.0f) {
+    smx_distscene_params p;
+    SMX_SHIM_CHECK(smx_distscene_params_default(&p));
+    p.max_distance = max_distance;
+    p.cell_size = cell_size;
+    const u32 n_in = (u32)(triangles.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_build_distscene(handle_, stream, scene->handle_, &p, n_in ? triangles.data() : nullptr, n_in, 0, &scene->stats_));
+  }
+  // Not in the reference: n_samples points drawn on `triangles` over the map as it stands, measured against `scene` within
+  // max_distance (smx_recon_compare_to_distscene in smx.h): one side of CompareMeshes without a rebuild of the other mesh's index.
+  void CompareToDistanceScene(cudaStream_t stream, const std::vector<u32>& triangles, const DistanceScene& scene, float max_distance,
+                              u32 n_samples, u32 seed, smx_compare_side* out) {
+    const u32 n_in = (u32)(triangles.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_compare_to_distscene(handle_, stream, scene.handle_, max_distance, n_samples, seed,
+                                                  n_in ? triangles.data() : nullptr, n_in, 0, out));
   }
   // Not in the reference: the per-triangle tests of SurfelMeshing::CheckRemeshing
   // (APP/surfel_meshing.cc:590-650) for `count` triangles (3 surfel indices each) against the device map; flag bits in smx.h.

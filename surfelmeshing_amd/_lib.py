@@ -310,6 +310,20 @@ class RaySceneCastStats(C.Structure):
                 [(n, C.c_uint64) for n in ("n_layers", "n_bit_tests", "n_lookups", "n_lookup_misses", "n_pair_tests")])
 
 
+class DistSceneParams(C.Structure):
+    """smx_distscene_params: the bound on a query's max_distance and the grid's cell (0: the library chooses)."""
+    _fields_ = [("max_distance", C.c_float), ("cell_size", C.c_float)]
+
+
+DISTSCENE_PHASES = 5        # SMX_DISTSCENE_PHASES
+
+
+class DistSceneStats(C.Structure):
+    """smx_distscene_stats"""
+    _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_wide", "n_entries", "n_cells")] +
+                [("cell_size_used", C.c_float), ("max_distance", C.c_float), ("device_bytes", C.c_uint64)])
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -393,6 +407,8 @@ EXPORTS = [
     "smx_raycast_params_default", "smx_recon_raycast_mesh", "smx_recon_debug_raycast_timings",
     "smx_rayscene_create", "smx_rayscene_destroy", "smx_rayscene_params_default", "smx_recon_build_rayscene", "smx_rayscene_cast",
     "smx_rayscene_debug_timings",
+    "smx_distscene_create", "smx_distscene_destroy", "smx_distscene_params_default", "smx_recon_build_distscene", "smx_distscene_query",
+    "smx_recon_compare_to_distscene", "smx_distscene_debug_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

@@ -29,6 +29,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    COMPARE_PHASES, SAMPLE_MAX, SAMPLE_PHASES, CompareParams, CompareStats, SampleStats,
                    RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
                    RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
+                   DISTSCENE_PHASES, CompareSide, DistSceneParams, DistSceneStats,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -238,11 +239,145 @@ class RayScene:
         return dict(zip(("mark", "index", "occupancy", "cast", "stats"), [float(v) for v in out]))
 
 
+def distscene_params(max_distance, cell_size=0.0):
+    """The parameters of BuildDistanceScene as smx_distscene_params; ValueError on what the library would refuse, before
+    anything is called."""
+    d = distance_params(max_distance, cell_size)
+    return DistSceneParams(d.max_distance, d.cell_size)
+
+
+def distscene_stats_dict(st):
+    """smx_distscene_stats as a dict: integers, cell_size_used and max_distance floats."""
+    d = {n: int(getattr(st, n)) for n, _ in DistSceneStats._fields_ if n not in ("cell_size_used", "max_distance")}
+    d["cell_size_used"], d["max_distance"] = float(st.cell_size_used), float(st.max_distance)
+    return d
+
+
+def distscene_check_query(scene, max_distance):
+    """ValueError if `scene` is closed, holds no build, or was built for less than max_distance: what the library would refuse
+    of a query, before anything is called."""
+    if not getattr(scene, "_h", None):
+        raise ValueError("the scene is closed")
+    if not getattr(scene, "stats", None):
+        raise ValueError("the scene holds no build")
+    if np.float32(max_distance) > np.float32(scene.stats["max_distance"]):
+        raise ValueError("max_distance %g is above the %g the scene was built for" % (max_distance, scene.stats["max_distance"]))
+
+
+def compare_side_dict(side, max_distance=None):
+    """smx_compare_side as a dict, as one side of compare_stats_dict."""
+    dist = distance_stats_dict(side.distance)
+    if max_distance is not None:
+        dist["max_distance"] = float(max_distance)
+    return dict(sample=sample_stats_dict(side.sample), distance=dist, sum_d=int(side.sum_d), sum_sq_lo=int(side.sum_sq_lo),
+                sum_sq_hi=int(side.sum_sq_hi))
+
+
+class DistanceScene:
+    """Not in the reference: a snapshot of a triangle array over the map with the search structure of MeshDistance
+    (smx_distscene), built once by CUDASurfelReconstruction.BuildDistanceScene for one bound on max_distance and queried many
+    times.  After the build a query reads neither the map nor the triangle array: it answers what MeshDistance answered on the
+    map as it stood at the build, through later Integrate, Compact and deformation calls and after the reconstruction object
+    is gone.  .stats is the dict of smx_distscene_stats of the build.  close() frees the device memory; the object is a context
+    manager."""
+
+    def __init__(self, device_id=-1):
+        self._h = C.c_void_p()
+        self.stats = None
+        _lib.check(_lib.load().smx_distscene_create(C.c_int32(device_id), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().smx_distscene_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def device_bytes(self):
+        """Device memory the scene held after its build (smx_distscene_stats.device_bytes); 0 for a scene without a build."""
+        return self.stats["device_bytes"] if self.stats else 0
+
+    def Query(self, stream, points, max_distance=None, signed=False, return_closest=False):
+        """For every point of `points` ([P,3] float32) what MeshDistance returns for the triangles and the map of the build
+        (smx_distscene_query): byte for byte the same nearest, distance, closest and statistics.  max_distance: at most the
+        bound of the build (None: the bound).  Synchronous.  points is a numpy array or a contiguous float32 device tensor; the
+        results then are device tensors too.  Returns (nearest, distance, then with return_closest closest, then the dict of
+        smx_distance_stats)."""
+        if max_distance is None:
+            if not getattr(self, "stats", None):
+                raise ValueError("the scene holds no build")
+            max_distance = self.stats["max_distance"]
+        p = distance_params(max_distance, 0.0, signed)
+        distscene_check_query(self, p.max_distance)
+        st = DistanceStats()
+        dev = _device_address(points) is not None
+        if dev:
+            import torch
+            if not (points.is_contiguous() and points.dtype == torch.float32 and points.numel() % 3 == 0):
+                raise ValueError("a device tensor of points must be contiguous [P,3] float32")
+            n_points = points.numel() // 3
+            nearest = torch.empty(n_points, dtype=torch.uint32, device=points.device)
+            distance = torch.empty(n_points, dtype=torch.float32, device=points.device)
+            closest = torch.empty((n_points, 3), dtype=torch.float32, device=points.device) if return_closest else None
+            pin = points.data_ptr() if n_points else None
+            outs = [a.data_ptr() if a is not None and n_points else None for a in (nearest, distance, closest)]
+            torch.cuda.current_stream(points.device).synchronize()      # (the tensor's producers; the call runs on `stream`)
+        else:
+            pts = np.ascontiguousarray(points, np.float32)
+            if pts.size % 3:
+                raise ValueError("points must hold three values per row")
+            n_points = pts.size // 3
+            nearest, distance = np.zeros(n_points, np.uint32), np.zeros(n_points, np.float32)
+            closest = np.zeros((n_points, 3), np.float32) if return_closest else None
+            pin = pts.ctypes.data if n_points else None
+            outs = [a.ctypes.data if a is not None and n_points else None for a in (nearest, distance, closest)]
+        _lib.check(_lib.load().smx_distscene_query(self._h, _sv(stream), C.byref(p), C.c_void_p(pin), C.c_uint32(n_points), C.c_void_p(outs[0]),
+                                                   C.c_void_p(outs[1]), C.c_void_p(outs[2]), C.c_int32(1 if dev else 0), C.byref(st)))
+        stats = distance_stats_dict(st)
+        stats["max_distance"] = float(p.max_distance)      # (what the histogram's bins are fractions of)
+        return (nearest, distance, closest, stats) if return_closest else (nearest, distance, stats)
+
+    def debug_timings(self):
+        """Milliseconds of the last build (mark, index, first) and of the last query (query, stats)."""
+        out = (C.c_float * DISTSCENE_PHASES)()
+        _lib.check(_lib.load().smx_distscene_debug_timings(self._h, out, C.c_int32(DISTSCENE_PHASES)))
+        return dict(zip(("mark", "index", "first", "query", "stats"), [float(v) for v in out]))
+
+
 def _device_address(a):
     """The device address of a device tensor (anything with is_cuda / data_ptr), None for everything else."""
     if getattr(a, "is_cuda", False) and hasattr(a, "data_ptr"):
         return int(a.data_ptr())
     return None
+
+
+def _triangles_arg(triangles):
+    """A triangle array for the library: (n_in, address or None, on_device, the object that keeps the address alive).
+    ValueError on what is not [T,3] 32-bit integers."""
+    if _device_address(triangles) is not None:
+        if not (triangles.is_contiguous() and triangles.element_size() == 4 and triangles.numel() % 3 == 0):
+            raise ValueError("a device tensor of triangles must be contiguous [T,3] 32-bit integers")
+        import torch
+        n_in = triangles.numel() // 3
+        torch.cuda.current_stream(triangles.device).synchronize()      # (the tensor's producers; the call runs on its own stream)
+        return n_in, (triangles.data_ptr() if n_in else None), True, triangles
+    tri = np.ascontiguousarray(triangles, np.uint32)
+    if tri.size % 3:
+        raise ValueError("triangles must hold three values per row")
+    n_in = tri.size // 3
+    return n_in, (tri.ctypes.data if n_in else None), False, tri
 
 
 kSurfelAttributeCount = 25        # APP/cuda_surfel_reconstruction_kernels.cuh:76
@@ -1261,6 +1396,42 @@ class CUDASurfelReconstruction:
             raise
         sc.stats = rayscene_stats_dict(st)
         return sc
+
+    def BuildDistanceScene(self, stream, triangles, max_distance, cell_size=0.0, scene=None):
+        """Not in the reference: a DistanceScene of `triangles` ([T,3] slot indices, a numpy array or a contiguous 32-bit device
+        tensor) over the map as it stands (smx_recon_build_distscene).  max_distance is the bound on what a query may ask for;
+        cell_size as in MeshDistance.  Synchronous.  scene: an existing DistanceScene to rebuild in place.  A refused build
+        leaves the scene empty (and closes a scene made here)."""
+        p = distscene_params(max_distance, cell_size)
+        n_in, tin, dev, _keep = _triangles_arg(triangles)
+        own = scene is None
+        sc = DistanceScene() if own else scene
+        st = DistSceneStats()
+        try:
+            _lib.check(_lib.load().smx_recon_build_distscene(self._h, _sv(stream), sc._h, C.byref(p), C.c_void_p(tin), C.c_uint32(n_in),
+                                                             C.c_int32(1 if dev else 0), C.byref(st)))
+        except Exception:
+            sc.stats = None
+            if own:
+                sc.close()
+            raise
+        sc.stats = distscene_stats_dict(st)
+        return sc
+
+    def CompareToDistanceScene(self, stream, triangles, scene, max_distance, n_samples, seed=0):
+        """Not in the reference: n_samples points drawn on `triangles` over the map as it stands as SampleMesh draws them,
+        measured against `scene` as DistanceScene.Query measures them, unsigned, within max_distance (at most the scene's bound)
+        (smx_recon_compare_to_distscene).  While the map is unchanged since the scene's build this is the a_to_b side of
+        CompareMeshes(triangles, the scene's triangles, directions=1, cell_size=the scene's cell_size_used).  The samples stay
+        on the device.  Synchronous.  Returns one side of compare_stats_dict."""
+        d = distance_params(max_distance)
+        n, sd = sample_params(n_samples, seed)
+        distscene_check_query(scene, d.max_distance)
+        n_in, tin, dev, _keep = _triangles_arg(triangles)
+        side = CompareSide()
+        _lib.check(_lib.load().smx_recon_compare_to_distscene(self._h, _sv(stream), scene._h, C.c_float(d.max_distance), C.c_uint32(n), C.c_uint32(sd),
+                                                              C.c_void_p(tin), C.c_uint32(n_in), C.c_int32(1 if dev else 0), C.byref(side)))
+        return compare_side_dict(side, d.max_distance)
 
     def debug_raycast_timings(self):
         """Milliseconds of the last RaycastMesh call, by phase."""

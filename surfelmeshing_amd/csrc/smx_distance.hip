@@ -14,11 +14,16 @@
 // and the set is the candidates of ALL of R whatever c is; the counters are integer sums and one integer
 // maximum; c itself may depend on the order of nothing either (an integer sum), though the result would not care.
 //
+// One query body serves two kernels: k_dist_query for the call, which re-reads the winner's corners from the map, and
+// k_dscene_query for a kept scene (smx_distscene.hip), which reads them from a record of the winner.
+// dist_scene_query, behind the kernels, is the host side of a scene's query: the query and stats phases on a kept index.
+//
 // smx_recon_mesh_distance itself is at the end of the file: it owns the order of the phases, the workspace (DistanceWork,
 // smx_distance.hpp) and the second read of the counters (the first is tg_read_counts).
 #include <cmath>
 
 #include "smx_recon_state.hpp"
+#include "smx_distscene.hpp"
 #include "smx_sort.hpp"
 
 namespace smx {
@@ -104,16 +109,37 @@ struct DistWideSrc {
   __device__ __forceinline__ const TgRec* operator()(uint32_t g) const { return recs + g; }
 };
 
+// Where the winner's corners come from.  The call re-reads them through the caller's triangle array from the map; a kept scene
+// reads any record of the winner (first_rec names one): the same float32 words, so the same Q and the same sign.
+struct DistCornersFromMap {
+  TgMap map;
+  const uint32_t* tri;
+  __device__ __forceinline__ void load(uint32_t t, TgVec* A, TgVec* B, TgVec* C) const {
+    *A = tg_pos(map, tri[3 * (size_t)t]); *B = tg_pos(map, tri[3 * (size_t)t + 1]); *C = tg_pos(map, tri[3 * (size_t)t + 2]);
+  }
+};
+struct DistCornersFromRecs {
+  const uint32_t* first_rec;
+  const TgRec *recs, *wide_recs;
+  __device__ __forceinline__ void load(uint32_t t, TgVec* A, TgVec* B, TgVec* C) const {
+    uint32_t held;
+    const uint32_t word = first_rec[t];                      // (t came out of a record, so it has one; if not: NaN, which shows)
+    *A = *B = *C = TgVec{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+    if (word != kDsceneNoRec) dscene_winner(word, TgDeviceRecs{recs}, TgDeviceRecs{wide_recs}, A, B, C, &held);
+  }
+};
+
 // A workgroup per tile of 256 points in cell order = a run of occupied query cells.  Cell after cell: 27 lanes look the
 // neighbour cells up, the workgroup stages their packed records in LDS in chunks and the lanes walk the staged records for the
 // points of that cell; the wide list is staged the same way behind the cells, for all points of the tile.  (A cell whose points
 // straddle two tiles is staged by both.)  Then every lane writes the answer of its own point to the point's place in the input.
-__global__ void __launch_bounds__(kDBlock)
-k_dist_query(TgMap map, const uint32_t* __restrict__ tri, const float* __restrict__ points, uint32_t n_points,
-             const unsigned long long* __restrict__ cell_keys, const uint32_t* __restrict__ order, const TgCell* __restrict__ table,
-             uint32_t mask, const TgRec* __restrict__ recs, const TgRec* __restrict__ wide_recs, uint32_t n_wide,
-             const uint32_t* __restrict__ cnt, float max2, int signed_distance, uint32_t* __restrict__ nearest, float* __restrict__ distance,
-             float* __restrict__ closest, unsigned long long* __restrict__ best_out) {
+// One body for the two kernels below.
+template <class Corners>
+__device__ __forceinline__ void
+dist_query_tile(const Corners& corners, const float* __restrict__ points, uint32_t n_points, const unsigned long long* __restrict__ cell_keys,
+                const uint32_t* __restrict__ order, const TgCell* __restrict__ table, uint32_t mask, const TgRec* __restrict__ recs,
+                const TgRec* __restrict__ wide_recs, uint32_t n_wide, const uint32_t* __restrict__ cnt, float max2, int signed_distance,
+                uint32_t* __restrict__ nearest, float* __restrict__ distance, float* __restrict__ closest, unsigned long long* __restrict__ best_out) {
   __shared__ float4 s_a[kDistChunk], s_b[kDistChunk], s_c[kDistChunk];
   __shared__ unsigned long long s_key[kDBlock], s_best[kDBlock];
   __shared__ float s_px[kDBlock], s_py[kDBlock], s_pz[kDBlock];
@@ -159,7 +185,8 @@ k_dist_query(TgMap map, const uint32_t* __restrict__ tri, const float* __restric
   TgVec Q{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
   if (key != kTgNone) {
     t = (uint32_t)key;
-    const TgVec A = tg_pos(map, tri[3 * (size_t)t]), B = tg_pos(map, tri[3 * (size_t)t + 1]), C = tg_pos(map, tri[3 * (size_t)t + 2]);
+    TgVec A, B, C;
+    corners.load(t, &A, &B, &C);
     uint32_t region;
     Q = dist_closest(P, A, B, C, &region);
     d = sqrtf(tg_key_float(key));
@@ -169,6 +196,27 @@ k_dist_query(TgMap map, const uint32_t* __restrict__ tri, const float* __restric
   nearest[p] = t;
   distance[p] = d;
   if (closest) { closest[3 * (size_t)p] = Q.x; closest[3 * (size_t)p + 1] = Q.y; closest[3 * (size_t)p + 2] = Q.z; }
+}
+
+// The two kernels over it: the call's, and a kept scene's (smx_distscene), which reads neither the map nor the
+// caller's triangle array.
+__global__ void __launch_bounds__(kDBlock)
+k_dist_query(TgMap map, const uint32_t* __restrict__ tri, const float* __restrict__ points, uint32_t n_points,
+             const unsigned long long* __restrict__ cell_keys, const uint32_t* __restrict__ order, const TgCell* __restrict__ table,
+             uint32_t mask, const TgRec* __restrict__ recs, const TgRec* __restrict__ wide_recs, uint32_t n_wide,
+             const uint32_t* __restrict__ cnt, float max2, int signed_distance, uint32_t* __restrict__ nearest, float* __restrict__ distance,
+             float* __restrict__ closest, unsigned long long* __restrict__ best_out) {
+  dist_query_tile(DistCornersFromMap{map, tri}, points, n_points, cell_keys, order, table, mask, recs, wide_recs, n_wide, cnt, max2, signed_distance,
+                  nearest, distance, closest, best_out);
+}
+__global__ void __launch_bounds__(kDBlock)
+k_dscene_query(const uint32_t* __restrict__ first_rec, const float* __restrict__ points, uint32_t n_points,
+               const unsigned long long* __restrict__ cell_keys, const uint32_t* __restrict__ order, const TgCell* __restrict__ table,
+               uint32_t mask, const TgRec* __restrict__ recs, const TgRec* __restrict__ wide_recs, uint32_t n_wide,
+               const uint32_t* __restrict__ cnt, float max2, int signed_distance, uint32_t* __restrict__ nearest, float* __restrict__ distance,
+               float* __restrict__ closest, unsigned long long* __restrict__ best_out) {
+  dist_query_tile(DistCornersFromRecs{first_rec, recs, wide_recs}, points, n_points, cell_keys, order, table, mask, recs, wide_recs, n_wide, cnt, max2,
+                  signed_distance, nearest, distance, closest, best_out);
 }
 
 __global__ void __launch_bounds__(kDBlock)
@@ -193,6 +241,76 @@ k_dist_stats(const float* __restrict__ points, uint32_t n_points, const unsigned
 }
 
 }  // namespace
+
+unsigned long long DistQueryWork::bytes() const {
+  auto of = [](const auto& b) { return (unsigned long long)b.capacity() * sizeof(*b.get()); };
+  return of(keys[0]) + of(keys[1]) + of(vals[0]) + of(vals[1]) + of(hist) + of(best) + of(pts) + of(out_distance) + of(out_closest) +
+         of(out_nearest) + of(counters);
+}
+
+int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_distance_params* p, const float* points, uint32_t n_points,
+                     uint32_t* nearest, float* distance, float* closest, bool dev, hipStream_t st, PhaseStamps<2>& stamps,
+                     smx_distance_stats* stats) {
+  // ---- every allocation of the query: the counters, the keys, the sort's buffers, the staging
+  if (!w.counters.get()) SMX_CALL(w.counters.alloc(kDistWords, false));
+  SMX_CALL(w.best.reserve(n_points));
+  for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(n_points)); SMX_CALL(w.vals[k].reserve(n_points)); }
+  SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(n_points)));
+  const float* dpts = nullptr;
+  SMX_CALL(stage_in(w.pts, points, (size_t)3 * n_points, dev, st, &dpts));
+  uint32_t* d_nearest = nearest;
+  float* d_distance = distance;
+  float* d_closest = closest;
+  if (!dev && n_points > 0) {
+    SMX_CALL(w.out_nearest.reserve(n_points));
+    SMX_CALL(w.out_distance.reserve(n_points));
+    if (closest) SMX_CALL(w.out_closest.reserve((size_t)3 * n_points));
+    d_nearest = w.out_nearest.get(); d_distance = w.out_distance.get(); d_closest = closest ? w.out_closest.get() : nullptr;
+  }
+  SMX_CALL(stamps.begin(st));
+  auto finish = [&](int rc) -> int {     // (the stamps are complete before they are published)
+    SMX_HIP(hipStreamSynchronize(st));
+    stamps.publish();
+    return rc;
+  };
+  uint32_t* cnt = w.counters.get();
+  SMX_HIP(hipMemsetAsync(cnt, 0, kDistWords * sizeof(uint32_t), st));
+  const dim3 b(kDistBlock);
+
+  // ---- query
+  if (n_points > 0) {
+    const dim3 g_pts(blocks_for(n_points));
+    hipLaunchKernelGGL(k_dist_point_keys, g_pts, b, 0, st, dpts, n_points, ix.cnt, w.keys[0].get(), w.vals[0].get());
+    SMX_LAUNCH_CHECK();
+    const int cur = radix_sort(w.keys, w.vals, n_points, 63, w.hist.get(), st);
+    hipLaunchKernelGGL(k_dscene_query, g_pts, b, 0, st, ix.first_rec, dpts, n_points, w.keys[cur].get(), w.vals[cur].get(), ix.table, ix.mask, ix.recs,
+                       ix.wide_recs, ix.n_wide, ix.cnt, p->max_distance * p->max_distance, (int)p->signed_distance, d_nearest, d_distance, d_closest,
+                       w.best.get());
+    SMX_LAUNCH_CHECK();
+  }
+  SMX_CALL(stamps.mark(st));
+
+  // ---- stats
+  if (n_points > 0) {
+    hipLaunchKernelGGL(k_dist_stats, dim3(blocks_for(n_points)), b, 0, st, dpts, n_points, w.best.get(), p->max_distance, cnt);
+    SMX_LAUNCH_CHECK();
+    if (!dev) {
+      SMX_HIP(hipMemcpyAsync(nearest, d_nearest, (size_t)n_points * 4, hipMemcpyDeviceToHost, st));
+      SMX_HIP(hipMemcpyAsync(distance, d_distance, (size_t)n_points * 4, hipMemcpyDeviceToHost, st));
+      if (closest) SMX_HIP(hipMemcpyAsync(closest, d_closest, (size_t)n_points * 12, hipMemcpyDeviceToHost, st));
+    }
+  }
+  uint32_t h[kDistWords];
+  SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+  SMX_HIP(hipStreamSynchronize(st));
+  if (stats) {
+    stats->n_bad_points = h[kDistBadPoints]; stats->n_matched = h[kDistMatched]; stats->max_dist2_bits = h[kDistMaxBits];
+    for (uint32_t k = 0; k < kDistBins; ++k) stats->histogram[k] = h[kDistHist + k];
+  }
+  SMX_CALL(stamps.mark(st));
+  return finish(SMX_OK);
+}
+
 }  // namespace smx
 
 using namespace smx;

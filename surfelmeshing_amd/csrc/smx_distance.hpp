@@ -5,7 +5,8 @@
 // point).  smx_distance.hip calls them from its kernels; a test compiles this part alone for the host
 // (SMX_DISTANCE_HOST_ONLY) and walks the same passes with plain words.  The classes of step 1, the cell functions, the cell
 // table and the packed records are the triangle grid's (smx_trigrid.hpp).
-// Part 2: the counter words and the workspace the object keeps for the call (kernels and glue: smx_distance.hip).
+// Part 2: the counter words, the workspace the object keeps for the call, and what the query of a kept index (smx_distscene.hpp)
+// needs of this file (kernels and glue: smx_distance.hip).
 #pragma once
 
 #include <stdint.h>
@@ -132,6 +133,32 @@ struct DistanceWork {
   DevBuf<uint32_t> counters;               // [kDistWords]
   PhaseStamps<SMX_DIST_PHASES> stamps;     // of the last call; a refused call publishes the phases it completed
 };
+
+// ---- the query of a kept index (smx_distscene) -------------------------------------------------------------------
+// What a scene's query needs besides the index: the points' sort, the winning keys, the staging, its own counter words.
+struct DistQueryWork {
+  DevBuf<unsigned long long> keys[2];      // [n_points] the points' cell keys, sorted
+  DevBuf<uint32_t> vals[2];
+  DevBuf<uint32_t> hist;                   // the sort's workspace
+  DevBuf<unsigned long long> best;         // [n_points] the winning key of every point
+  DevBuf<float> pts, out_distance, out_closest;      // staging when the caller's arrays are host memory
+  DevBuf<uint32_t> out_nearest;
+  DevBuf<uint32_t> counters;               // [kDistWords]; only the words from kTgWords on are used
+  unsigned long long bytes() const;
+};
+// A view of the index a scene keeps.  cnt = the build's device counters (c at [kTgCellBits]).
+struct DistSceneIndex {
+  const TgCell* table; uint32_t mask;
+  const TgRec *recs, *wide_recs; uint32_t n_wide;
+  const uint32_t* first_rec;
+  const uint32_t* cnt;
+};
+// k_dist_point_keys -> the sort -> k_dscene_query -> k_dist_stats on st, synchronous: the query and stats phases of
+// smx_recon_mesh_distance with the winner's corners read from the records (smx_distance.hip).  Every allocation lies before the
+// first write to an output.  Fills the point words of *stats (may be null): n_bad_points, n_matched, max_dist2_bits, histogram.
+int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_distance_params* p, const float* points, uint32_t n_points,
+                     uint32_t* nearest, float* distance, float* closest, bool on_device, hipStream_t st, PhaseStamps<2>& stamps,
+                     smx_distance_stats* stats);
 #endif
 
 }  // namespace smx

@@ -1,0 +1,63 @@
+// smx_distscene.hpp -- a distance scene: the index of smx_recon_mesh_distance kept between queries (smx_distscene).
+//
+// Part 1: what only a kept scene needs, as plain inline functions: the first-record rule (which of a triangle's records
+// first_rec[t] names) and the read of the winner's corners through it.  The distance arithmetic, the walk and the query of one
+// point are smx_distance.hpp's.  The kernels call them; a test compiles this part alone for the host (SMX_DISTSCENE_HOST_ONLY)
+// and walks the same passes with plain words.
+// Part 2: what the scene object holds (kernels and glue: smx_distscene.hip; the query's kernels: smx_distance.hip).
+#pragma once
+
+#include <stdint.h>
+
+#if defined(SMX_DISTSCENE_HOST_ONLY)
+#if !defined(SMX_DISTANCE_HOST_ONLY)
+#define SMX_DISTANCE_HOST_ONLY 1
+#endif
+#endif
+#include "smx_distance.hpp"
+
+namespace smx {
+
+// ---- the first record of a triangle ----------------------------------------------------------------------------------------
+// first_rec[t] = the smallest position among the records that hold triangle t: a position in the sorted cell records (below
+// 2^30), or a position in the wide list (below 2^28) with the top bit set.  A triangle of R is in cells or on the wide list,
+// never both, so the two kinds never meet in one word; a triangle outside R keeps kDsceneNoRec and is never a winner.  The
+// smallest position is one integer minimum per record, so the word does not depend on the order the records arrive in.
+constexpr uint32_t kDsceneWideBit = 0x80000000u;
+constexpr uint32_t kDsceneNoRec = 0xFFFFFFFFu;
+SMX_DIST_FN uint32_t dscene_first_word(uint32_t position, bool wide) { return wide ? (position | kDsceneWideBit) : position; }
+SMX_DIST_FN uint32_t dscene_first_min(uint32_t held, uint32_t word) { return word < held ? word : held; }
+// The corners of triangle t as ANY of its records holds them: the float32 words the map held at the build, in input order.
+// Recs: void load(j, &A, &B, &C, &t) as in dist_walk.  *t_held = the triangle the record names (t itself).
+template <class Recs>
+SMX_DIST_FN void dscene_winner(uint32_t first_word, const Recs& cell_recs, const Recs& wide_recs, TgVec* A, TgVec* B, TgVec* C, uint32_t* t_held) {
+  if (first_word & kDsceneWideBit) wide_recs.load(first_word & ~kDsceneWideBit, A, B, C, t_held);
+  else cell_recs.load(first_word, A, B, C, t_held);
+}
+
+#if !defined(SMX_DISTSCENE_HOST_ONLY)
+// ---- part 2 ----------------------------------------------------------------------------------------------------------
+constexpr int kDsceneBuildWords = 32;                        // the build's counters: the grid's words; device_bytes counts 32
+static_assert(kTgWords <= kDsceneBuildWords, "the build's counters");
+#endif
+
+}  // namespace smx
+
+#if !defined(SMX_DISTSCENE_HOST_ONLY)
+// A snapshot: after a build a query reads nothing but these.
+struct smx_distscene_s {
+  int device = 0;
+  bool built = false;
+  // the build's
+  smx::DevBuf<float> recs, wide_recs;              // [n_entries] / [n_wide] TgRec
+  smx::DevBuf<unsigned long long> table;           // [mask + 1][2] TgCell
+  smx::DevBuf<uint32_t> first_rec;                 // [n_in] dscene_first_word of every triangle of R
+  smx::DevBuf<uint32_t> counters;                  // [kDsceneBuildWords] as the build left them: c
+  uint32_t h[smx::kDsceneBuildWords] = {};         // ... and on the host
+  uint32_t mask = 0, n_entries = 0, n_wide = 0, n_in = 0;
+  float max_distance = 0.0f;                       // the bound of the build: a query asks for no more
+  smx::DistQueryWork query;                        // a query's
+  smx::PhaseStamps<3> build_stamps;                // mark, index, first of the last build
+  smx::PhaseStamps<2> query_stamps;                // query, stats of the last query
+};
+#endif

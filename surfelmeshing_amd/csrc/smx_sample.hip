@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "smx_recon_state.hpp"
+#include "smx_distscene.hpp"
 #include "smx_sample.hpp"
 
 namespace smx {
@@ -346,6 +347,52 @@ int smx_recon_compare_meshes(smx_recon r, smx_stream s, const smx_compare_params
     SMX_CALL(side_of(1, db, n_b, da, n_a, &out->b_to_a));
     SMX_HIP(hipStreamSynchronize(st));
     w.stamps.publish();
+    return SMX_OK;
+  };
+  const int rc = run();
+  if (rc != SMX_OK) {                                        // (a refusal by either half is the call's)
+    (void)hipStreamSynchronize(st);
+    memset(out, 0, sizeof(*out));
+  }
+  return rc;
+}
+
+// One side of the comparison against a kept index: the samples of `triangles` on r's map as it stands, measured against the
+// scene's snapshot.  The two calls it is defined by, on device arrays: the samples stay in the comparison's workspace.
+int smx_recon_compare_to_distscene(smx_recon r, smx_stream s, smx_distscene sc, float max_distance, uint32_t n_samples, uint32_t seed,
+                                   const uint32_t* triangles, uint32_t n_in, int32_t on_device, smx_compare_side* out) {
+  SMX_CHECK_ARG(out != nullptr);
+  memset(out, 0, sizeof(*out));
+  SMX_CHECK_ARG(r != nullptr && sc != nullptr);
+  SMX_CHECK_ARG(sc->device == r->device);
+  // the limits of the two halves, before anything is allocated or launched
+  SMX_CHECK_ARG(finite_f(max_distance) && max_distance >= 1e-3f && max_distance <= 16.0f);
+  SMX_CHECK_ARG(sample_limits_ok(n_in, n_samples));
+  SMX_CHECK_ARG(triangles != nullptr || n_in == 0);
+  SMX_ON_DEVICE(r->device);
+  hipStream_t st = (hipStream_t)s;
+  CompareWork& w = r->compare;
+  auto run = [&]() -> int {
+    if (!w.counters.get()) SMX_CALL(w.counters.alloc(kSmpWords, false));
+    SMX_CALL(w.points.reserve((size_t)3 * n_samples));
+    SMX_CALL(w.tri.reserve(n_samples));
+    SMX_CALL(w.nearest.reserve(n_samples));
+    SMX_CALL(w.distance.reserve(n_samples));
+    const uint32_t* din = nullptr;
+    SMX_CALL(stage_in(w.in_a, triangles, (size_t)3 * n_in, on_device != 0, st, &din));
+    const smx_distance_params dp{max_distance, 0.0f, 0};
+    SMX_CALL(smx_recon_sample_mesh(r, s, din, n_in, n_samples, seed, w.points.get(), w.tri.get(), nullptr, nullptr, 1, &out->sample));
+    SMX_CALL(smx_distscene_query(sc, s, &dp, w.points.get(), n_samples, w.nearest.get(), w.distance.get(), nullptr, 1, &out->distance));
+    uint32_t* cnt = w.counters.get();
+    SMX_HIP(hipMemsetAsync(cnt, 0, kSmpWords * sizeof(uint32_t), st));
+    if (n_samples > 0) {
+      hipLaunchKernelGGL(k_cmp_sums, dim3(blocks_for(n_samples)), dim3(kSmpBlock), 0, st, w.nearest.get(), w.distance.get(), n_samples, cnt);
+      SMX_LAUNCH_CHECK();
+    }
+    uint32_t h[kSmpWords];
+    SMX_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    SMX_HIP(hipStreamSynchronize(st));
+    out->sum_d = word64(h, kCmpSumD); out->sum_sq_lo = word64(h, kCmpSumSqLo); out->sum_sq_hi = word64(h, kCmpSumSqHi);
     return SMX_OK;
   };
   const int rc = run();

@@ -204,7 +204,7 @@ int tg_read_counts(const uint32_t* cnt, uint32_t* h, int n_words, uint32_t n_slo
 
 int tg_enqueue_index(TgWork& w, TgBoxes boxes, const TgMap& map, const uint32_t* din, uint32_t n_in, uint32_t E, uint32_t Wd, uint32_t min_sort,
                      uint32_t* cnt, DevBuf<float>& recs_buf, DevBuf<float>& wide_buf, DevBuf<unsigned long long>& table_buf, uint32_t* mask_out,
-                     const unsigned long long** sorted_keys, hipStream_t st) {
+                     const unsigned long long** sorted_keys, hipStream_t st, const uint32_t** sorted_vals) {
   const dim3 b(kTgBlock), g_in(div_up(n_in, kTgBlock));
   const uint32_t sort_n = E > min_sort ? E : min_sort;
   const uint32_t entries = dec_table_size(E), mask = entries - 1;
@@ -218,6 +218,7 @@ int tg_enqueue_index(TgWork& w, TgBoxes boxes, const TgMap& map, const uint32_t*
   TgRec* wide_recs = reinterpret_cast<TgRec*>(wide_buf.get());
   *mask_out = mask;
   if (sorted_keys) *sorted_keys = nullptr;
+  if (sorted_vals) *sorted_vals = nullptr;
   SMX_HIP(hipMemsetAsync(table, 0, (size_t)entries * sizeof(TgCell), st));
   if (E > 0) {
     const auto fill = boxes == TgBoxes::kForRays ? k_tg_entries<Variant<TgBoxes::kForRays>> : k_tg_entries<Variant<TgBoxes::kExact>>;
@@ -227,6 +228,7 @@ int tg_enqueue_index(TgWork& w, TgBoxes boxes, const TgMap& map, const uint32_t*
     hipLaunchKernelGGL(k_tg_records, dim3(blocks_for(E)), b, 0, st, map, din, w.vals[cur].get(), E, recs);
     hipLaunchKernelGGL(k_tg_table, dim3(blocks_for(E)), b, 0, st, w.keys[cur].get(), E, table, mask, cnt);
     if (sorted_keys) *sorted_keys = w.keys[cur].get();
+    if (sorted_vals) *sorted_vals = w.vals[cur].get();
   }
   if (Wd > 0) hipLaunchKernelGGL(k_tg_records, dim3(blocks_for(Wd)), b, 0, st, map, din, w.wide_t.get(), Wd, wide_recs);
   SMX_LAUNCH_CHECK();

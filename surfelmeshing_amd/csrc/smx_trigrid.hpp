@@ -1,10 +1,12 @@
 // smx_trigrid.hpp -- the triangle grid: a triangle array over the map, searched through a uniform grid of cells.
-// smx_recon_mesh_distance, smx_recon_raycast_mesh and smx_recon_build_rayscene all build it, and build it here.
+// smx_recon_mesh_distance, smx_recon_raycast_mesh, smx_recon_build_rayscene and smx_recon_build_distscene all build it, and
+// build it here.
 //
 // Part 1: what the contracts of the three services share, as plain inline functions (the vector type, step 1's classes, the
 // cell of a coordinate, the box of a triangle and its entry count, the cell table's insert and look-up templated on how an
 // entry is read, claimed and bumped, the float in a key).  The kernels call them; a test compiles this part alone for the host
-// (SMX_TRIGRID_HOST_ONLY, which the host-only switches of smx_distance.hpp, smx_raycast.hpp and smx_rayscene.hpp set) and walks
+// (SMX_TRIGRID_HOST_ONLY, which the host-only switches of smx_distance.hpp, smx_distscene.hpp, smx_raycast.hpp and
+// smx_rayscene.hpp set) and walks
 // the same passes with plain words.
 // Part 2: the device-side records, the counter words, the workspace of the build and its three steps (kernels and glue:
 // smx_trigrid.hip).
@@ -212,12 +214,11 @@ int tg_enqueue_mark(TgWork& w, TgBoxes boxes, const TgMap& map, const uint32_t* 
 // SMX_ERR_INVALID_ARGUMENT with the error text set.  *E = the entries, *Wd = the length of the wide list.
 int tg_read_counts(const uint32_t* cnt, uint32_t* h, int n_words, uint32_t n_slots, hipStream_t st, uint32_t* E, uint32_t* Wd);
 // Reserves the sort's buffers in w for max(E, min_sort) records, then recs, wide_recs and table (the caller's), in the order
-// the call always has; *sorted_keys (may be null) = the E sorted cell keys, in w until its next
-// use.  Nothing is reserved after the sort is
-// enqueued.
+// the call always has; *sorted_keys (may be null) = the E sorted cell keys, *sorted_vals (may be null) = the triangle of every
+// sorted entry beside them, both in w until its next use.  Nothing is reserved after the sort is enqueued.
 int tg_enqueue_index(TgWork& w, TgBoxes boxes, const TgMap& map, const uint32_t* din, uint32_t n_in, uint32_t E, uint32_t Wd, uint32_t min_sort,
                      uint32_t* cnt, DevBuf<float>& recs, DevBuf<float>& wide_recs, DevBuf<unsigned long long>& table, uint32_t* mask,
-                     const unsigned long long** sorted_keys, hipStream_t st);
+                     const unsigned long long** sorted_keys, hipStream_t st, const uint32_t** sorted_vals = nullptr);
 #endif
 
 }  // namespace smx

@@ -210,11 +210,25 @@ class MapMesher:
             self._index = None
 
 
-def mesh_distance(rec, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False, stream=None):
+def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=None):
+    """A DistanceScene of `triangles` over the map as it stands (CUDASurfelReconstruction.BuildDistanceScene), for queries within
+    max_distance: build it once, then pass it as scene= to mesh_distance or decimation_error, or as scene_b= to compare_meshes,
+    as often as needed.  It is a snapshot: later changes of the map do not reach it.  ValueError on parameters the library would
+    refuse."""
+    from .api import distscene_params
+    distscene_params(max_distance, cell_size)
+    return rec.BuildDistanceScene(stream, triangles, max_distance, cell_size)
+
+
+def mesh_distance(rec, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False, stream=None, scene=None):
     """For every point its closest triangle of `triangles` within max_distance, on the device: (nearest, distance[, closest],
-    stats) as CUDASurfelReconstruction.MeshDistance returns them.  ValueError on parameters the library would refuse."""
-    from .api import distance_params
-    distance_params(max_distance, cell_size, signed)
+    stats) as CUDASurfelReconstruction.MeshDistance returns them.  With scene (build_distance_scene) the points are measured
+    against that scene instead: rec, triangles and cell_size are not used.  ValueError on parameters the library would refuse."""
+    from .api import distance_params, distscene_check_query
+    p = distance_params(max_distance, cell_size, signed)
+    if scene is not None:
+        distscene_check_query(scene, p.max_distance)
+        return scene.Query(stream, points, max_distance, signed, return_closest)
     return rec.MeshDistance(stream, triangles, points, max_distance, cell_size, signed, return_closest)
 
 
@@ -262,12 +276,13 @@ def map_positions(rec, slots=None, stream=None):
     return pos if slots is None else pos[np.asarray(slots, np.int64)]
 
 
-def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None):
+def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None, scene=None):
     """How far a decimation moved the surface: the points are the positions of the vertices `fine` uses (ascending by slot),
-    measured against `coarse`.  Returns (distance_summary, nearest, distance, stats)."""
+    measured against `coarse`.  scene: a DistanceScene of `coarse` (build_distance_scene) to measure against; coarse and
+    cell_size are then not used.  Returns (distance_summary, nearest, distance, stats)."""
     import numpy as np
     used = np.unique(np.ascontiguousarray(fine, np.uint32))
-    nearest, distance, stats = mesh_distance(rec, coarse, map_positions(rec, used, stream), max_distance, cell_size, stream=stream)
+    nearest, distance, stats = mesh_distance(rec, coarse, map_positions(rec, used, stream), max_distance, cell_size, stream=stream, scene=scene)
     return distance_summary(distance, stats), nearest, distance, stats
 
 
@@ -280,13 +295,26 @@ def sample_mesh(rec, triangles, n_samples, seed=0, return_bary=False, return_nor
     return rec.SampleMesh(stream, triangles, n_samples, seed, return_bary, return_normals)
 
 
-def compare_meshes(rec, a, b, max_distance, n_samples, seed=0, cell_size=0.0, directions=3, stream=None):
+def compare_meshes(rec, a, b, max_distance, n_samples, seed=0, cell_size=0.0, directions=3, stream=None, scene_b=None):
     """Both one-sided surface distances between the triangle arrays a and b, on the device: the dict
-    CUDASurfelReconstruction.CompareMeshes returns (comparison_summary reads it).  ValueError on parameters the library would
-    refuse."""
-    from .api import compare_params
-    compare_params(max_distance, n_samples, seed, cell_size, directions)
-    return rec.CompareMeshes(stream, a, b, max_distance, n_samples, seed, cell_size, directions)
+    CUDASurfelReconstruction.CompareMeshes returns (comparison_summary reads it).  scene_b: a DistanceScene of b
+    (build_distance_scene) for the A -> B side, which then builds no index of b: b and cell_size are not used on that side
+    (CUDASurfelReconstruction.CompareToDistanceScene); the B -> A side, if asked for, runs as without a scene.  ValueError on
+    parameters the library would refuse."""
+    from .api import compare_params, compare_stats_dict, distscene_check_query
+    p = compare_params(max_distance, n_samples, seed, cell_size, directions)
+    if scene_b is None:
+        return rec.CompareMeshes(stream, a, b, max_distance, n_samples, seed, cell_size, directions)
+    if directions & 1:
+        distscene_check_query(scene_b, p.max_distance)
+    if directions & 2:
+        out = rec.CompareMeshes(stream, a, b, max_distance, n_samples, seed, cell_size, 2)
+    else:
+        from ._lib import CompareStats
+        out = compare_stats_dict(CompareStats(), p.max_distance)
+    if directions & 1:
+        out["a_to_b"] = rec.CompareToDistanceScene(stream, a, scene_b, max_distance, n_samples, seed)
+    return out
 
 
 def _side_summary(side):

@@ -7,6 +7,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --components [--decimate CELL[,CELL...]] [--compare_json OTHER.json] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --fill [EDGES] [--decimate CELL[,CELL...]] [--small_target N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --distance METRES[,METRES...] [--decimate CELL[,CELL...]] [--points N] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --distance METRES[,METRES...] --scene [--decimate METRES] [--compare N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH --scene [--decimate METRES] [--json OUT] [--txt OUT]
 
@@ -52,6 +53,16 @@ arrays, whole calls by device events and the four phases by the library's own (s
 every count of smx_distance_stats and the summary line of meshing.distance_summary; bytes by distance_traffic_bytes below
 against the HBM peak, the query phase's share on its own; the full triangulation re-measured beside it.  Writes
 profiles/distance_bench.{txt,json} unless --txt / --json say otherwise.
+
+--distance METRES[,METRES...] --scene measures smx_distscene on the same points and the same two meshes (the
+decimated one at the first --decimate cell, 0.05 m by default), everything in one process, for every max_distance given as the
+scene's bound: smx_recon_mesh_distance re-measured first (its call and its four phases, each as the median, min and max of --reps
+calls: the spread every comparison allows); the scene's build by phase (mark, index, first: smx_distscene_debug_timings, over
+--reps rebuilds in place), its structure and its device memory; a query at the bound and at a fifth of it (whole calls by device
+events and the phases query and stats by the library's own); the bytes and statistics of the query at the bound are compared with
+the call's.  With --compare N one side of a comparison, the decimated mesh's N samples against the full mesh within
+--compare_distance, through meshing.compare_meshes(scene_b=) against the plain call.  Writes profiles/distscene_bench.{txt,json}
+unless --txt / --json say otherwise.
 
 --raycast WxH measures smx_recon_raycast_mesh: the W x H camera rays (meshing.camera_rays) of the bench pose --
 the pose of the first frame after the growth, render_bench.py's capture pose -- against the same map's full mesh and against the
@@ -101,7 +112,8 @@ ap.add_argument("--compare", type=int, default=0, metavar="N", help="measure smx
 ap.add_argument("--compare_distance", type=float, default=0.05, metavar="METRES", help="with --compare: max_distance")
 ap.add_argument("--raycast", default=None, metavar="WxH", help="measure smx_recon_raycast_mesh with the camera rays of the bench pose")
 ap.add_argument("--scene", action="store_true", help="with --raycast: measure smx_rayscene (build by phase, cast for every occupancy setting) "
-                                                      "beside smx_recon_raycast_mesh, on the full mesh and the one decimated at the first --decimate cell")
+                                                      "beside smx_recon_raycast_mesh, on the full mesh and the one decimated at the first --decimate cell; "
+                                                      "with --distance: measure smx_distscene (build by phase, queries) beside smx_recon_mesh_distance")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -666,6 +678,146 @@ def distance_main():
     nn.close()
 
 
+DISTSCENE_BUILD_PHASES = ("mark", "index", "first")
+DISTSCENE_QUERY_PHASES = ("query", "stats")
+
+
+def distscene_main():
+    """--distance METRES[,METRES...] --scene: smx_distscene beside smx_recon_mesh_distance in one process."""
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    maxes = [float(c) for c in args.distance.split(",")]
+    cell = float(args.decimate.split(",")[0]) if args.decimate else 0.05
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    from surfelmeshing_amd import meshing, synth
+    pts = np.ascontiguousarray(synth.room_surface_points(args.points)[0], np.float32)
+    P = pts.shape[0]
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    dpts, dnear, ddist = api.CUDABuffer(1, 3 * P, np.float32), api.CUDABuffer(1, P, np.uint32), api.CUDABuffer(1, P, np.float32)
+    dpts.Upload(pts.reshape(1, -1))
+    say("# %d query points of synth.room_surface_points; medians of %d repetitions after one that allocates" % (P, args.reps))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def spread(v):
+        return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+    def show(s):
+        return "%.3f ms (min %.3f, max %.3f)" % (s["median"], s["min"], s["max"])
+
+    def answer():
+        return dnear.Download()[0][:100000].tobytes() + ddist.Download()[0][:100000].tobytes()
+    T, mst = C.c_uint32(0), _lib.MeshStats()
+    _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(cap),
+                                       C.c_int32(1), C.byref(T), C.byref(mst)))
+    T_in = T.value
+    Tc, dst = C.c_uint32(0), _lib.DecimateStats()
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(Tc), C.byref(dst)))
+    inputs = [("full mesh", dtri, T_in), ("decimated at %g m" % cell, dout, Tc.value)]
+    out_rows = []
+    for what, src, n_in in inputs:
+        tri = _DeviceArray(src, 3 * n_in)
+        for md in maxes:
+            # ---- the call, re-measured beside the rest
+            prm, st = api.distance_params(md), _lib.DistanceStats()
+            whole, phs = [], []
+            for _ in range(args.reps + 1):
+                whole.append(timed(lambda: _lib.check(L.smx_recon_mesh_distance(
+                    rec._h, None, C.byref(prm), C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in), C.c_void_p(dpts.ToCUDA().address), C.c_uint32(P),
+                    C.c_void_p(dnear.ToCUDA().address), C.c_void_p(ddist.ToCUDA().address), None, C.c_int32(1), C.byref(st))))[0])
+                phs.append(rec.debug_distance_timings())
+            want = answer()
+            call = {"call": spread(whole[1:]), "phases": {k: spread([q[k] for q in phs[1:]]) for k in DIST_PHASES}}
+            cst = api.distance_stats_dict(st)
+            say("%s, max_distance %g m, %d triangles: smx_recon_mesh_distance %s | %s" % (
+                what, md, n_in, show(call["call"]), " | ".join("%s %s" % (k, show(call["phases"][k])) for k in DIST_PHASES)))
+            # ---- the scene's build
+            scene = rec.BuildDistanceScene(None, tri, md)
+            builds = []
+            for _ in range(args.reps):
+                rec.BuildDistanceScene(None, tri, md, scene=scene)
+                builds.append(scene.debug_timings())
+            build = {k: spread([q[k] for q in builds]) for k in DISTSCENE_BUILD_PHASES}
+            bst = scene.stats
+            assert all(bst[k] == cst[k] for k in ("n_wide", "n_entries", "n_cells", "cell_size_used")), "the scene's structure differs from the call's"
+            say("  scene build: %s | sum of medians %.3f ms against the call's mark + index %.3f ms; cell %.4f m, %d entries in %d cells, %d wide, "
+                "%.1f MiB on the device (first_rec %.1f MiB)" % (
+                    " | ".join("%s %s" % (k, show(build[k])) for k in DISTSCENE_BUILD_PHASES), sum(build[k]["median"] for k in DISTSCENE_BUILD_PHASES),
+                    call["phases"]["mark"]["median"] + call["phases"]["index"]["median"], bst["cell_size_used"], bst["n_entries"], bst["n_cells"],
+                    bst["n_wide"], bst["device_bytes"] / 2.0 ** 20, 4.0 * n_in / 2.0 ** 20))
+            # ---- queries at the bound and at a fifth of it
+            queries = {}
+            for q in [md] + ([md / 5.0] if md / 5.0 >= 1e-3 else []):
+                qp, qst = api.distance_params(q), _lib.DistanceStats()
+                whole, phs = [], []
+                for _ in range(args.reps + 1):
+                    whole.append(timed(lambda: _lib.check(L.smx_distscene_query(
+                        scene._h, None, C.byref(qp), C.c_void_p(dpts.ToCUDA().address), C.c_uint32(P), C.c_void_p(dnear.ToCUDA().address),
+                        C.c_void_p(ddist.ToCUDA().address), None, C.c_int32(1), C.byref(qst))))[0])
+                    phs.append(scene.debug_timings())
+                if q == md:
+                    assert answer() == want, "the scene's bytes differ from smx_recon_mesh_distance's"
+                    assert api.distance_stats_dict(qst) == cst, "the scene's statistics differ from smx_recon_mesh_distance's"
+                row = {"whole": spread(whole[1:]), "phases": {k: spread([v[k] for v in phs[1:]]) for k in DISTSCENE_QUERY_PHASES},
+                       "n_matched": int(qst.n_matched)}
+                queries["%g" % q] = row
+                say("  scene query at %g m: %s = %.2f M points/s | %s | %d of %d matched" % (
+                    q, show(row["whole"]), P / (row["whole"]["median"] * 1e-3) / 1e6,
+                    " | ".join("%s %s" % (k, show(row["phases"][k])) for k in DISTSCENE_QUERY_PHASES), row["n_matched"], P))
+            at = queries["%g" % md]
+            say("  query + stats of the scene %.3f ms against the call's %.3f ms; the whole query is %.2f x the whole call" % (
+                sum(at["phases"][k]["median"] for k in DISTSCENE_QUERY_PHASES), call["phases"]["query"]["median"] + call["phases"]["stats"]["median"],
+                at["whole"]["median"] / call["call"]["median"]))
+            out_rows.append({"input": what, "max_distance": md, "triangles_in": n_in, "points": P, "reps": args.reps, "call": call, "stats": cst,
+                             "build_phases_ms": build, "scene_stats": bst, "first_rec_bytes": 4 * n_in, "queries": queries})
+            scene.close()
+    res = {"metric": "distscene_query_ms", "slots": n, "live": live, "triangles_in": T_in, "rows": out_rows}
+    # ---- one side of a comparison through scene_b= against the plain comparison
+    if args.compare:
+        a, b, md = _DeviceArray(dout, 3 * Tc.value), _DeviceArray(dtri, 3 * T_in), args.compare_distance
+        plain, through, got, want = [], [], None, None
+        with meshing.build_distance_scene(rec, b, md) as scene:
+            for _ in range(args.reps + 1):
+                ms, want = timed(lambda: meshing.compare_meshes(rec, a, b, md, args.compare, 1, scene.stats["cell_size_used"], directions=1))
+                plain.append(ms)
+                ms, got = timed(lambda: meshing.compare_meshes(rec, a, b, md, args.compare, 1, directions=1, scene_b=scene))
+                through.append(ms)
+            assert got == want, "the comparison through the scene differs from smx_recon_compare_meshes"
+            build_ms = sum(scene.debug_timings()[k] for k in DISTSCENE_BUILD_PHASES)
+        res["compare"] = {"samples": args.compare, "max_distance": md, "plain_ms": spread(plain[1:]), "scene_b_ms": spread(through[1:]),
+                          "scene_build_ms": build_ms, "matched": got["a_to_b"]["distance"]["n_matched"]}
+        say("decimated -> full, %d samples within %g m: smx_recon_compare_meshes (directions 1) %s | through scene_b %s, the scene built once in "
+            "%.3f ms | the same words, %d matched" % (args.compare, md, show(res["compare"]["plain_ms"]), show(res["compare"]["scene_b_ms"]), build_ms,
+                                                     res["compare"]["matched"]))
+    with open(args.json or os.path.join(ROOT, "profiles", "distscene_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "distscene_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 SAMPLE_PHASES = ("weights", "scan", "draw")
 COMPARE_PHASES = ("a_to_b.sample", "a_to_b.distance", "a_to_b.sums", "b_to_a.sample", "b_to_a.distance", "b_to_a.sums")
 
@@ -1199,4 +1351,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

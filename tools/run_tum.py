@@ -7,7 +7,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
-                              [--mesh_eval METRES] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
+                              [--mesh_eval METRES [--mesh_eval_frames N]] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
                               [--mesh_compare_samples N [--mesh_compare_distance METRES]]
                               [--export_mesh_samples FILE.ply --mesh_samples N]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
@@ -29,6 +29,9 @@ limits of the triangle filter the new triangles have to pass (default 10 / 170 d
 prints one summary line per measurement: with --synthetic the noise-free surface points of the integrated frames (every 8th
 pixel) against the final mesh -- with --track that is what the tracker's drift does to the surface --, with --mesh_decimate the
 fine mesh's vertices against the decimated one.  Without --synthetic and without --mesh_decimate the flag is refused.
+--mesh_eval_frames N (with --mesh_eval, --synthetic and --mesh or --mesh_every) builds one distance scene (smx_distscene) of the
+final mesh and measures the surface points of each of the last N integrated frames against it: one line per frame under the
+head "scene points" and a total, whose figures are those of the --mesh_eval line when N covers every integrated frame.
 --mesh_compare_samples N prints, for every stage of the chain that was asked for (cleaning, hole filling, decimation), the
 two-sided surface error between the mesh before and after it on N area-weighted samples per side (smx_recon_compare_meshes).
 --export_mesh_samples FILE.ply with --mesh_samples N writes N such samples of the final mesh with the face normals.
@@ -199,6 +202,10 @@ def parse_args(argv=None):
                     help="with --mesh or --mesh_every: measure point-to-mesh distances up to this far (smx_recon_mesh_distance): with "
                          "--synthetic the noise-free surface points of the integrated frames (every 8th pixel) against the final "
                          "mesh, with --mesh_decimate also the fine mesh's vertices against the decimated one")
+    ap.add_argument("--mesh_eval_frames", type=int, default=0, metavar="N",
+                    help="with --mesh_eval METRES --synthetic N --mesh: build one distance scene (smx_distscene) of the final mesh and "
+                         "measure the noise-free surface points of each of the last N integrated frames against it: one line per "
+                         "frame and a total")
     ap.add_argument("--mesh_eval_rays", action="store_true",
                     help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
                          "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
@@ -265,6 +272,10 @@ def parse_args(argv=None):
                      "(the fine mesh's vertices)")
         if not 1e-3 <= args.mesh_eval <= 16.0:
             ap.error("--mesh_eval needs a distance within 0.001 .. 16 metres")
+    if args.mesh_eval_frames < 0:
+        ap.error("--mesh_eval_frames needs a frame count >= 0")
+    if args.mesh_eval_frames and not (args.mesh_eval is not None and args.synthetic and (args.mesh or args.mesh_every > 0)):
+        ap.error("--mesh_eval_frames needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_rays and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_rays needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_rays_frames < 0:
@@ -297,6 +308,23 @@ def print_mesh_comparison(args, rec, stage, before, after):
     stats = meshing.compare_meshes(rec, before, after, args.mesh_compare_distance, args.mesh_compare_samples)
     print("surface error of %s within %g m, %d samples per side:" % (stage, args.mesh_compare_distance, args.mesh_compare_samples))
     print(meshing.format_mesh_comparison(meshing.comparison_summary(stats), ("before", "after")))
+
+
+def merge_distance_stats(parts):
+    """The statistics of several MeshDistance / DistanceScene.Query results over one mesh as those of one call on all their
+    points: what distance_summary reads (the counts and the histogram add up, the largest squared distance is the maximum)."""
+    out = dict(parts[0])
+    for k in ("n_points", "n_bad_points", "n_matched"):
+        out[k] = sum(int(p[k]) for p in parts)
+    out["histogram"] = [sum(int(p["histogram"][b]) for p in parts) for b in range(len(parts[0]["histogram"]))]
+    out["max_dist2_bits"] = max(int(p["max_dist2_bits"]) for p in parts)
+    return out
+
+
+def format_point_eval(summary, what, head="scene points"):
+    """A line of --mesh_eval_frames: `what` is "frame 6" or "3 frames"; the figures are format_distance_summary's."""
+    from surfelmeshing_amd import meshing
+    return "%s of %s: %s" % (head, what, meshing.format_distance_summary(summary))
 
 
 def format_ray_eval(hit, t, d, frame, head="surface error along the rays"):
@@ -480,6 +508,24 @@ def main():
             print("surface error within %g m, ground truth of %d frames to the mesh (%s poses): %s" % (
                 args.mesh_eval, max(0, n - 2 * half_ - args.start_frame), "tracked" if args.track else "true",
                 meshing.format_distance_summary(meshing.distance_summary(distance, dstats))))
+    if args.mesh_eval_frames:
+        from surfelmeshing_amd import meshing
+        half_ = args.outlier_filtering_frame_count // 2
+        last = n - half_ - 1
+        frames = [f for f in range(last - args.mesh_eval_frames + 1, last + 1) if f >= args.start_frame + half_]
+        t1 = time.time()
+        parts = []
+        with meshing.build_distance_scene(rec, triangles, args.mesh_eval) as scene:
+            built = time.time()
+            for f in frames:
+                _, distance, dstats = meshing.mesh_distance(rec, triangles, s.surface_points(f, 8), args.mesh_eval, scene=scene)
+                print(format_point_eval(meshing.distance_summary(distance, dstats), "frame %d" % f))
+                parts.append((distance, dstats))
+        if parts:
+            total = meshing.distance_summary(np.concatenate([d for d, _ in parts]), merge_distance_stats([st for _, st in parts]))
+            print(format_point_eval(total, "%d frames" % len(frames)))
+        print("scene points: one scene of %d triangles (%d bytes on the device) built in %.1f ms, %d frames queried in %.1f ms" % (
+            triangles.shape[0], scene.device_bytes, 1e3 * (built - t1), len(frames), 1e3 * (time.time() - built)))
     if args.mesh_eval_rays:
         from surfelmeshing_amd import meshing
         half_ = args.outlier_filtering_frame_count // 2
