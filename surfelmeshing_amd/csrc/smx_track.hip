@@ -27,9 +27,6 @@
 namespace smx {
 namespace {
 
-constexpr int kTrackBlock = 256;
-constexpr int kTrackPixelsPerLane = 8;    // sampled pixels a lane visits before the grid is widened
-
 __global__ void k_track_begin(TrackDev* st) {
   for (int k = 0; k < 12; ++k) {
     const double v = (k == 0 || k == 5 || k == 10) ? 1.0 : 0.0;
@@ -163,8 +160,7 @@ TrackLevel track_level(int l, int W, int H, float fx, float fy, float cx, float 
   k.fx = fx; k.fy = fy; k.cx = cx; k.cy = cy; k.depth_scaling = depth_scaling;
   k.max_distance_sq = p.max_distance * p.max_distance;
   k.cos_max_angle = (float)cos((double)p.max_normal_angle_deg * (M_PI / 180.0));
-  const long long n = (long long)k.sw * k.sh;
-  t.grid = (int)std::min<long long>(std::max<long long>(div_up(n, kTrackBlock * kTrackPixelsPerLane), 1), kTrackMaxSlabs);
+  t.grid = track_grid((long long)k.sw * k.sh);
   TrackSolveK& sk = t.sk;
   sk.level = l; sk.stride = s; sk.n_slabs = t.grid; sk.final_launch = 0;
   sk.min_inliers = p.min_inliers; sk.photo = photo ? 1 : 0;

@@ -1,9 +1,10 @@
 // smx_track.hpp -- camera tracking against the rendered map (smx_recon_track, smx_recon_track_rgbd).
 //
 // Part 1: the arithmetic as plain inline functions -- one sampled pixel's contribution to the sums (with and without the
-// photometric term), the prepare kernel's pixel, the solve, the SE(3) exponential, the end of a call.  smx_track.hip calls
-// them from its kernels; a test compiles this part alone for the host (SMX_TRACK_HOST_ONLY) and runs the same functions.
-// Part 2: the constants of the slabs and the workspace the object keeps for the calls (their glue is in smx_track.hip).
+// photometric term), the prepare kernel's pixel, the solve, the SE(3) exponential, the end of a call, and the launch rule of
+// the reduce kernel (workgroup size, grid, slab strides).  smx_track.hip calls them from its kernels; a test compiles this
+// part alone for the host (SMX_TRACK_HOST_ONLY) and runs the same functions in the launch's order.
+// Part 2: the workspace the object keeps for the calls (its glue is in smx_track.hip).
 #pragma once
 
 #include <math.h>
@@ -64,6 +65,18 @@ struct TrackSolveK {
 
 // Samples along an axis of `size` pixels at stride s: the pixels s/2 + i s.
 SMX_TRACK_FN int track_samples(int size, int s) { return size > s / 2 ? (size - s / 2 + s - 1) / s : 0; }
+
+// The reduce launch: kTrackBlock lanes per workgroup; a lane visits kTrackPixelsPerLane samples before the grid is widened,
+// up to kTrackMaxSlabs workgroups (one slab each), beyond which a lane visits more.  Workgroups for n samples:
+constexpr int kTrackBlock = 256;
+constexpr int kTrackPixelsPerLane = 8;
+constexpr int kTrackMaxSlabs = 256;
+constexpr int kTrackSlabStride = 32;       // doubles per workgroup slab without the photometric term (31 used)
+constexpr int kTrackRgbdSlabStride = 40;   // ... with it (33 used)
+SMX_TRACK_FN int track_grid(long long n) {
+  const long long g = (n + kTrackBlock * kTrackPixelsPerLane - 1) / (kTrackBlock * kTrackPixelsPerLane);
+  return (int)(g < 1 ? 1 : g > kTrackMaxSlabs ? kTrackMaxSlabs : g);
+}
 
 // One row's share of the normal equations, in the order every sum keeps: the 21 products of the upper triangle row by
 // row, the 6 of the right-hand side, then the square of e into its own sum.  Products in float, sums in double.
@@ -305,10 +318,6 @@ SMX_TRACK_FN void track_finish(const TrackSolveK& k, TrackDev* st) {
 
 #if !defined(SMX_TRACK_HOST_ONLY)
 // ---- part 2 ----
-constexpr int kTrackSlabStride = 32;       // doubles per workgroup slab without the photometric term (31 used)
-constexpr int kTrackRgbdSlabStride = 40;   // ... with it (33 used)
-constexpr int kTrackMaxSlabs = 256;        // workgroups of the reduce kernel, at most
-
 // The workspace of the two calls, a member of smx_recon_s; allocated by the first call that needs each part.
 struct TrackWork {
   // smx_recon_track / _rgbd, all four or none: the model images [H][W] of the last call, the reduce kernel's per-workgroup

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import track_exact as tx
 import track_ref as tr
 from common import ROOT, assert_surfels_match, run_both, small_stream
 from test_gpu_parity import _compare_state, _pipes
@@ -127,7 +128,8 @@ def sized(smx, request):
 @pytest.mark.parametrize("stride", [1, 2, 4, 8])
 def test_one_iteration_matches_the_restatement(smx, sized, stride):
     """From the identity (record 0) and from a perturbed T_rel (record 1: the pose the first iteration left) of a
-    (stride, 1), (stride, 1) schedule, for predictions 1, 3 and 5 frames old."""
+    (stride, 1), (stride, 1) schedule, for predictions 1, 3 and 5 frames old.  Beside the bound: the sums are the exact
+    model's (tests/track_exact.py) as float64 bits, evaluated on the model images the call returned."""
     s, pg, rec = sized
     intr = (s.fx, s.fy, s.cx, s.cy)
     pred = s.pose(11)
@@ -154,6 +156,9 @@ def test_one_iteration_matches_the_restatement(smx, sized, stride):
                 s.width, s.height, g, st, "identity" if k == 0 else "perturbed", inl, pix, got[tr.S_INLIERS],
                 mg["flagged"], ratio))
             assert np.all(diff <= bound), (g, k, int(np.argmax(diff / bound)), ratio)
+            Tf = tr.IDENTITY if k == 0 else tx.next_pose(recs[0]["x"], tr.IDENTITY)
+            exact, _ = tx.exact_sums(D, M, depth, normals, intr, Tf.astype(np.float32), st, rp.gates(), s.depth_scaling)
+            assert np.array_equal(got.view(np.uint64), exact.view(np.uint64)), (g, k, np.nonzero(got != exact)[0])
         # the solution of the second record follows from its sums by the restatement's solve
         status, x, _ = tr.solve(recs[1]["sums"], T1, rp)
         assert status == recs[1]["status"] and np.allclose(x, recs[1]["x"], rtol=1e-9, atol=1e-14)

@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import track_exact as tx
 import track_ref as tr
 import track_rgbd_ref as trr
 from common import ROOT, run_both, small_stream
@@ -103,7 +104,8 @@ def test_model_photo_is_the_restatement_of_the_gpus_own_renders(smx, sized):
 @pytest.mark.parametrize("stride", [1, 2, 4, 8])
 def test_one_iteration_matches_the_restatement(smx, sized, stride):
     """From the identity (record 0) and from a perturbed T_rel (record 1) of a (stride, 1), (stride, 1) schedule, for
-    predictions 1, 3 and 5 frames old: all 33 sums."""
+    predictions 1, 3 and 5 frames old: all 33 sums.  Beside the bound: the sums are the exact model's (tests/track_exact.py)
+    as float64 bits, evaluated on the model images the call returned."""
     s, pg, rec = sized
     intr = (s.fx, s.fy, s.cx, s.cy)
     pred = s.pose(11)
@@ -127,6 +129,10 @@ def test_one_iteration_matches_the_restatement(smx, sized, stride):
                   "max |diff| / bound %.3g" % (s.width, s.height, g, stride, "identity" if k == 0 else "perturbed", inl, pix,
                                                 ph["inliers"], got[trr.S_PHOTO_INLIERS], fl, ratio))
             assert np.all(diff <= bound), (g, k, int(np.argmax(diff / bound)), ratio)
+            Tf = tr.IDENTITY if k == 0 else tx.next_pose(recs[0]["x"], tr.IDENTITY)
+            exact, _ = tx.exact_sums(D, M, depth, normals, intr, Tf.astype(np.float32), stride, rp.gates(), s.depth_scaling,
+                                     (P, color, rp))
+            assert np.array_equal(got.view(np.uint64), exact.view(np.uint64)), (g, k, np.nonzero(got != exact)[0])
         status, x, _ = trr.solve(recs[1]["sums"], T1, rp)
         assert status == recs[1]["status"] and np.allclose(x, recs[1]["x"], rtol=1e-9, atol=1e-14)
 

@@ -2,11 +2,14 @@
 through its host library: track_photo_pixel, track_pixel<true> and the solve with colour, the inline functions of
 smx_track.hpp that k_track_photo_prepare, k_track_reduce_rgbd and k_track_solve call.  The prepare output must equal the
 float32 restatement of tests/track_rgbd_ref.py bit for bit; the 33 sums stay within the bound derived there and in
-tests/test_gpu_track.py -- the comparison tests/test_gpu_track_rgbd.py makes on the device."""
+tests/test_gpu_track.py -- the comparison tests/test_gpu_track_rgbd.py makes on the device -- and, walked in the launch's
+order (tests/track_host.py), equal the exact model's (tests/track_exact.py) bit for bit."""
 import ctypes as C
 
 import numpy as np
 
+import track_exact as tx
+import track_host
 import track_ref as tr
 import track_rgbd_ref as trr
 import viz_ref as vr
@@ -56,6 +59,11 @@ def test_rgbd_kernel_arithmetic_on_the_host_matches_the_restatement(orc, tmp_pat
                     assert abs(slab[e] - want[e]) <= fl, (g, stride, e)
                 diff, bound = trr.compare_sums(slab, want, mg, p, _sum_bounds)
                 assert np.all(diff <= bound), (g, stride, int(np.argmax(diff / bound)), float((diff / bound).max()))
+                # the same launch walked with its lanes, wavefronts, workgroups and slabs: the exact model's bits, all 33
+                exact, _ = tx.exact_sums(D, M, depth, normals, intr, Tf, stride, p.gates(), s.depth_scaling, (P, color, p))
+                walked, _ = track_host.walk_reduce(L, D, M, depth, normals, intr, Tf, stride, p, s.depth_scaling, (P, color))
+                assert np.array_equal(walked.view(np.uint64), exact.view(np.uint64)), (g, stride)
+                assert np.array_equal(slab[28:31], exact[28:31]) and slab[32] == exact[32]
                 # the term is there: the same bound would not cover leaving it out
                 geo = reduce(0.0, False)
                 assert np.all(geo[31:33] == 0) and np.any(np.abs(geo[:28] - want[:28]) > bound[:28])

@@ -24,6 +24,11 @@ FLOOR_MARGIN = 2e-6   # relative distance of a projected coordinate from an inte
 GATE_MARGIN = 1e-4    # relative distance from a gate's threshold
 
 f32 = np.float32
+# Where track_pixel leaves a sample (the `code` of iteration's `detail`), in the order of its tests.
+(EXIT_NO_DEPTH, EXIT_BEHIND, EXIT_LEFT, EXIT_RIGHT, EXIT_TOP, EXIT_BOTTOM, EXIT_HOLE, EXIT_DISTANCE, EXIT_ANGLE,
+ EXIT_INLIER) = range(10)
+EXITS = ("depth 0", "pz <= 0", "uf < 0", "uf >= W", "wf < 0", "wf >= H", "hole in D", "distance gate failed",
+         "angle gate failed", "inlier")
 
 
 class Params:
@@ -46,8 +51,9 @@ class Params:
 
     def gates(self):
         """(max_distance^2, cos(max_normal_angle)) as the float32 values the kernel compares against."""
-        return (float(f32(self.max_distance) * f32(self.max_distance)),
-                float(f32(np.cos(np.deg2rad(np.float64(self.max_normal_angle_deg))))))
+        with np.errstate(over="ignore"):    # (a max_distance whose square is no float any more gives +inf, as in the library)
+            d2 = float(f32(self.max_distance) * f32(self.max_distance))
+        return (d2, float(f32(np.cos(np.deg2rad(np.float64(self.max_normal_angle_deg))))))
 
 
 IDENTITY = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)
@@ -101,12 +107,17 @@ def pose_difference(A, B):
     return float(np.linalg.norm(E[:, 3])), rotation_vector_norm(E[:, :3])
 
 
-def iteration(D, M, depth, normals, intrinsics, T_rel, stride, gates, depth_scaling=5000.0, dtype=np.float64, handover=f32):
+def iteration(D, M, depth, normals, intrinsics, T_rel, stride, gates, depth_scaling=5000.0, dtype=np.float64, handover=f32,
+              detail=None, mutant=None):
     """One iteration's sums.  D [H, W] model depth (0 = empty), M [H, W, >=3] model normals, depth [H, W] uint16,
     normals [H, W, 2]; intrinsics (fx, fy, cx, cy); gates (max_distance^2, cos_max_angle).
     Returns (JtJ [6, 6], Jtr [6], sum r^2, inliers, pixels, margins) with margins a dict: `associated`, `flagged` (number
     of pixels with depth within FLOOR_MARGIN / GATE_MARGIN of a floor or a gate), `flagged_term` (the largest |J|^2 + |J r|
-    + r^2 scale such a pixel can contribute) and `sums` (the 31 numbers in the library's order)."""
+    + r^2 scale such a pixel can contribute) and `sums` (the 31 numbers in the library's order).
+    For the exact model (tests/track_exact.py, which adds the terms in the launch's order): a dict given as `detail` receives
+    the per-sample terms -- `n` samples in the kernel's index order, `code` [n] (EXITS: where track_pixel left), `clamped`
+    [n] (the fmaxf of the frame normal's z took the 0), `index` (the samples with a geometric row), their `J` [k, 6] and
+    `r` [k] in `dtype`, and `p` [n, 3] (NaN without depth); `mutant` flips one decision (tests/track_exact.py::MUTANTS)."""
     dt = dtype
     fx, fy, cx, cy = (dt(f32(v)) for v in intrinsics)
     H, W = depth.shape
@@ -129,11 +140,13 @@ def iteration(D, M, depth, normals, intrinsics, T_rel, stride, gates, depth_scal
     pz = T[2, 0] * vx + T[2, 1] * vy + T[2, 2] * z + T[2, 3]
     flagged = np.zeros(len(z), bool)
     alive = pz > 0
+    a_pz = alive.copy()
     flagged |= np.abs(pz) < FLOOR_MARGIN * z
     with np.errstate(divide="ignore", invalid="ignore"):
         uu = fx * px / pz + cx
         ww = fy * py / pz + cy
-    uf, wf = np.floor(uu), np.floor(ww)
+    to_pixel = np.rint if mutant == "rint" else np.floor
+    uf, wf = to_pixel(uu), to_pixel(ww)
 
     def near_integer(a):
         with np.errstate(invalid="ignore"):
@@ -141,10 +154,12 @@ def iteration(D, M, depth, normals, intrinsics, T_rel, stride, gates, depth_scal
     flagged |= alive & (near_integer(uu) | near_integer(ww))
     with np.errstate(invalid="ignore"):
         alive &= (uf >= 0) & (uf < W) & (wf >= 0) & (wf < H)
+    a_in = alive.copy()
     ui = np.where(alive, uf, 0).astype(np.int64)
     wi = np.where(alive, wf, 0).astype(np.int64)
     Dq = np.asarray(D)[wi, ui].astype(dt)
     alive &= Dq > 0
+    a_as = alive.copy()
     associated = int(alive.sum())
     Mq = np.asarray(M)[wi, ui, :3].astype(dt)
     qx = Dq * ((uf + half - cx) / fx)
@@ -153,18 +168,35 @@ def iteration(D, M, depth, normals, intrinsics, T_rel, stride, gates, depth_scal
         dx, dy, dz = px - qx, py - qy, pz - Dq
         d2 = dx * dx + dy * dy + dz * dz
         flagged |= alive & (np.abs(d2 - maxd2) < GATE_MARGIN * maxd2)
-        alive &= d2 <= maxd2
+        alive &= (d2 < maxd2) if mutant == "distance_lt" else (d2 <= maxd2)
+        a_di = alive.copy()
         mx = T[0, 0] * nx + T[0, 1] * ny + T[0, 2] * nz
         my = T[1, 0] * nx + T[1, 1] * ny + T[1, 2] * nz
         mz = T[2, 0] * nx + T[2, 1] * ny + T[2, 2] * nz
         dot = mx * Mq[:, 0] + my * Mq[:, 1] + mz * Mq[:, 2]
         flagged |= alive & (np.abs(dot - cosang) < GATE_MARGIN)
-        alive &= dot >= cosang
+        alive &= (dot > cosang) if mutant == "angle_gt" else (dot >= cosang)
     a = np.nonzero(alive)[0]
+    if detail is not None:
+        with np.errstate(invalid="ignore"):
+            side = np.where(~(uf >= 0), EXIT_LEFT, np.where(~(uf < W), EXIT_RIGHT, np.where(~(wf >= 0), EXIT_TOP, EXIT_BOTTOM)))
+        code = np.where(~a_pz, EXIT_BEHIND, np.where(~a_in, side, np.where(~a_as, EXIT_HOLE, np.where(
+            ~a_di, EXIT_DISTANCE, np.where(~alive, EXIT_ANGLE, EXIT_INLIER)))))
+        at = np.nonzero(keep)[0]
+        detail["n"] = len(keep)
+        detail["code"] = np.full(len(keep), EXIT_NO_DEPTH, np.int64)
+        detail["code"][at] = code
+        detail["clamped"] = np.zeros(len(keep), bool)
+        detail["clamped"][at] = (dt(1) - nx * nx - ny * ny) < 0
+        detail["index"] = at[a]
+        detail["p"] = np.full((len(keep), 3), np.nan)
+        detail["p"][at] = np.stack([px, py, pz], axis=1)
     px, py, pz, dx, dy, dz, Mq = px[a], py[a], pz[a], dx[a], dy[a], dz[a], Mq[a]
     r = Mq[:, 0] * dx + Mq[:, 1] * dy + Mq[:, 2] * dz
     J = np.stack([py * Mq[:, 2] - pz * Mq[:, 1], pz * Mq[:, 0] - px * Mq[:, 2], px * Mq[:, 1] - py * Mq[:, 0],
                   Mq[:, 0], Mq[:, 1], Mq[:, 2]], axis=1)
+    if detail is not None:
+        detail["J"], detail["r"] = J, r
     JtJ = np.zeros((6, 6))
     sums = np.zeros(N_SUMS)
     e = 0

@@ -82,11 +82,15 @@ def prepare(D, C, max_relative_depth_step, with_flags=False):
 
 
 def photometric(D, P, depth, color, intrinsics, T_rel, stride, params, depth_scaling=5000.0, dtype=np.float64,
-                handover=f32):
+                handover=f32, detail=None, mutant=None):
     """The photometric sums of one iteration: dict with `JtJ` [21] (upper triangle, row by row), `Jtr` [6], `ee`,
     `inliers`, `flagged` (pixels near a photometric gate that are not near a floor or the distance gate -- those
     track_ref.iteration counts already), `k_rot` / `k_tra` (largest |K| entry, rotational / translational, over the
-    candidate pixels), `e_error` (largest error bound of e over the inliers)."""
+    candidate pixels), `e_error` (largest error bound of e over the inliers).
+    As in track_ref.iteration, a dict given as `detail` receives the per-sample terms for the exact model: `reached` (the
+    samples, in the kernel's index order, that pass the distance gate and so reach the term), per reached sample `valid`
+    (P.w != 0), `gradient` and `intensity` (those two gates alone), `inlier`, and per inlier `index`, `K` [k, 6], `se`
+    (weight e) and `e` in `dtype`; `mutant` flips one decision (tests/track_exact.py::MUTANTS)."""
     dt = dtype
     fx, fy, cx, cy = (dt(f32(v)) for v in intrinsics)
     H, W = depth.shape
@@ -109,7 +113,8 @@ def photometric(D, P, depth, color, intrinsics, T_rel, stride, params, depth_sca
     with np.errstate(divide="ignore", invalid="ignore"):
         uu = fx * px / pz + cx
         ww = fy * py / pz + cy
-        uf, wf = np.floor(uu), np.floor(ww)
+        to_pixel = np.rint if mutant == "rint" else np.floor
+        uf, wf = to_pixel(uu), to_pixel(ww)
         alive &= (uf >= 0) & (uf < W) & (wf >= 0) & (wf < H)
 
         def near_integer(a):
@@ -125,20 +130,26 @@ def photometric(D, P, depth, color, intrinsics, T_rel, stride, params, depth_sca
         dx, dy, dz = px - qx, py - qy, pz - Dq
         d2 = dx * dx + dy * dy + dz * dz
         counted |= alive & (np.abs(d2 - maxd2) < GATE_MARGIN * maxd2)
-        alive &= d2 <= maxd2
+        alive &= (d2 < maxd2) if mutant == "distance_lt" else (d2 <= maxd2)
     a = np.nonzero(alive)[0]
     px, py, pz, uu, ww, uf, wf, counted = px[a], py[a], pz[a], uu[a], ww[a], uf[a], wf[a], counted[a]
     Pq = np.asarray(P)[wi[a], ui[a]].astype(dt)
     L, gx, gy, valid = Pq[:, 0], Pq[:, 1], Pq[:, 2], Pq[:, 3] != 0
     col = np.asarray(color)[ys[a], xs[a]]
     If = luma(col[:, 0], col[:, 1], col[:, 2]).astype(dt)
-    Lm = (L + gx * (uu - (uf + half))) + gy * (ww - (wf + half))
+    centre = dt(0) if mutant == "no_half" else half
+    Lm = (L + gx * (uu - (uf + centre))) + gy * (ww - (wf + centre))
     e = Lm - If
     g2 = gx * gx + gy * gy
     e_err = FLOOR_MARGIN * (np.abs(gx) * np.maximum(np.abs(uu), 1.0) + np.abs(gy) * np.maximum(np.abs(ww), 1.0)) + 4 * EPS
     flagged = valid & (g2 >= ming2 * (1 - GATE_MARGIN)) & (np.abs(np.abs(e) - maxe) < e_err)
     flagged |= valid & (np.abs(e) <= maxe + e_err) & (np.abs(g2 - ming2) < GATE_MARGIN * ming2)
-    inl = valid & (g2 >= ming2) & (np.abs(e) <= maxe)
+    g_ok = (g2 > ming2) if mutant == "gradient_gt" else (g2 >= ming2)
+    e_ok = (np.abs(e) < maxe) if mutant == "intensity_lt" else (np.abs(e) <= maxe)
+    inl = valid & g_ok & e_ok
+    if detail is not None:
+        at = np.nonzero(keep)[0][a]
+        detail.update(reached=at, valid=valid, gradient=g_ok, intensity=e_ok, inlier=inl, index=at[inl])
     gfx, gfy = gx * fx, gy * fy
     a0, a1, a2 = gfx / pz, gfy / pz, -((gfx * px + gfy * py) / (pz * pz))
     K = np.stack([lam * (py * a2 - pz * a1), lam * (pz * a0 - px * a2), lam * (px * a1 - py * a0),
@@ -147,6 +158,8 @@ def photometric(D, P, depth, color, intrinsics, T_rel, stride, params, depth_sca
     k_rot = float(np.abs(K[cand, :3]).max()) if cand.any() else 0.0
     k_tra = float(np.abs(K[cand, 3:]).max()) if cand.any() else 0.0
     K, e, se = K[inl], e[inl], (lam * e)[inl]
+    if detail is not None:
+        detail.update(K=K, se=se, e=e)
     JtJ = np.array([float((K[:, i] * K[:, j]).astype(np.float64).sum()) for i in range(6) for j in range(i, 6)])
     Jtr = np.array([float((K[:, i] * se).astype(np.float64).sum()) for i in range(6)])
     return {"JtJ": JtJ, "Jtr": Jtr, "ee": float((e * e).astype(np.float64).sum()), "inliers": int(inl.sum()),
