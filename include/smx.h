@@ -416,7 +416,9 @@ int smx_recon_debug_count_skipped_segments(smx_recon r, smx_stream s, uint32_t* 
  * bit 8: the list kernels run on a grid of four workgroups, so that every workgroup walks many steps;
  * bit 9: the regulariser's pass B and its edge kernel as ONE launch (the workgroup of a segment does the segment's edge work
  * itself, the work list stays in LDS) instead of two (pass B writes the work lists to memory, k_reg_accumulate walks
- * them: the default -- the fused launch is shorter alone and longer in the frame). */
+ * them: the default -- the fused launch is shorter alone and longer in the frame);
+ * bit 10: the neighbour update gathers its candidates' records with plain loads instead of range-checked buffer loads (the
+ * route of capacities from 2^28 slots, whose arrays 32-bit buffer offsets do not reach). */
 int smx_recon_set_scan_mode(smx_recon r, int32_t mode);
 /* TIMING ONLY -- the map is WRONG afterwards: leaves launches of smx_recon_integrate out, for the upper-bound runs of
  * bench.py --ub (what would the frame rate be without this chain?).  bit 0: no regulariser (pass B, edges, step);

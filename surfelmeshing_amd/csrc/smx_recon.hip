@@ -186,7 +186,10 @@ constexpr int kFarHash = 1024;          // destinations one sender workgroup can
 // built per image TILE in LDS by k_assoc_tiles instead of with device-scope atomics on five dense images: pass A
 // appends one (slot, pixel) PAIR per pixel a visible slot touches (<= 2) to the bin of the pixel's tile; the tile's
 // workgroup reduces its pairs with LDS atomics (all of the reductions are order-independent and exact: min, integer
-// add) and writes the five images with plain stores.  Nothing is cleared per frame.
+// add) and writes them with plain stores: supporting surfel, count and depth sum as images, and z-buffer minimum,
+// conflict key, count and supporting surfel once more as ONE 16-byte record per pixel (Scratch::assoc) -- the
+// integration and the flag pass gather per pixel, and each 4-byte image they read there is a cache-line request of its
+// own.  Nothing is cleared per frame.
 constexpr int kTileW = 32, kTileH = 8, kTilePx = kTileW * kTileH;   // one 256-lane workgroup per tile
 static_assert(kTilePx == kBlock, "the tile kernel runs choose_segment_direction in one of its workgroups");
 // pair code: bits 0-7 pixel inside the tile (row-major, kTileW wide); bit 8: the slot's second ("quadrant") pixel;
@@ -907,11 +910,11 @@ k_assoc_tiles(Surfels S, FrameCtx c, Scratch sc, Img<const uint16_t> depth, Img<
   SMX_STAMP(stamps, 4);
   if (in_image) {
     const size_t k = (size_t)y * c.W + x;
-    sc.first_depth[k] = __int_as_float(t.zmin[lane]);
-    sc.supporting[k] = t.sup[lane];
-    sc.counts[k] = t.cnt[lane];
+    const uint32_t sup = t.sup[lane], cnt = t.cnt[lane];
+    sc.assoc[k] = make_uint4((uint32_t)t.zmin[lane], t.confl[lane], cnt, sup);   // (one 16-byte store: see Scratch)
+    sc.supporting[k] = sup;
+    sc.counts[k] = cnt;
     sc.depth_sums[k] = (long long)t.sum[lane];
-    sc.confl_key[k] = t.confl[lane];
   }
   SMX_STAMP(stamps, 5);
   ts_end(c.ts, kTsTilesEnd, blockIdx.x, gridDim.x);
@@ -1325,7 +1328,8 @@ __device__ __forceinline__ void new_flags_scan_body(const NewFlagsArgs& a, const
   for (int j = 0; j < kScanPxPerThread; ++j) {
     const int k = min(k0 + j, P - 1);
     const int y = k / W, x = k - y * W;
-    dv[j] = depth(y, x); sv[j] = sc.supporting[k]; cv[j] = sc.confl_key[k];
+    const uint4 a4 = sc.assoc[k];   // (supporting surfel and conflict key in one request)
+    dv[j] = depth(y, x); sv[j] = a4.w; cv[j] = a4.y;
   }
 #pragma unroll
   for (int j = 0; j < kScanPxPerThread; ++j) { keep(dv[j]); keep(sv[j]); keep(cv[j]); }
@@ -1381,15 +1385,16 @@ struct FrameIn {
   Img<const uint16_t> depth; Img<const float2> normals; Img<const float> radius; Img<const uchar3> color;
 };
 
-// Everything the integration reads at one pixel, requested in one go (7 independent loads) before any of it
-// is used -- for both pixels of a surfel at once, see k_integrate.
+// Everything the integration reads at one pixel, requested in one go (5 independent loads: the association record and
+// the caller's four images) before any of it is used -- for both pixels of a surfel at once, see k_integrate.
 struct PixelIn {
   uint16_t depth; float first; uint32_t key; uint32_t count; float2 nxy; uchar3 col; float radius;
 };
 __device__ __forceinline__ PixelIn load_pixel(const FrameCtx& c, const Scratch& sc, const FrameIn& in, int x, int y) {
   const size_t k = (size_t)y * c.W + x;
   PixelIn p;
-  p.depth = in.depth(y, x); p.first = sc.first_depth[k]; p.key = sc.confl_key[k]; p.count = sc.counts[k];
+  const uint4 a4 = sc.assoc[k];
+  p.depth = in.depth(y, x); p.first = __uint_as_float(a4.x); p.key = a4.y; p.count = a4.z;
   p.nxy = in.normals(y, x); p.col = in.color(y, x); p.radius = in.radius(y, x);
   return p;
 }
@@ -1574,6 +1579,94 @@ k_integrate(Surfels S, FrameCtx c, Scratch sc, FrameIn in, Lists L,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Gathers of one group's records by slot number in which a lane that passes kInvalid sends NO request and gets zeros --
+// without a branch, so that a lane's gathers still leave together: conditional loads are what one would write, and the
+// compiler then waits for each one's data inside its branch, a round trip per candidate instead of one for all.  The
+// group array is addressed as a raw buffer (byte offset = slot * 16, range-checked by the address unit against the
+// array's size: an offset past the end is answered with zeros and never reaches the cache), and kInvalid * 16 = 2^32 - 16
+// lies past the end of every array this covers.  Arrays of 4 GB and more (capacities from 2^28 slots) have no 32-bit
+// offsets: for them (kRanged = false, Lists::plain_gathers) kInvalid reads the record of `self`, a slot whose records
+// the lane has requested already.
+constexpr size_t kRangedGatherMaxPitch = (size_t)1 << 28;   // (exclusive)
+template <bool kRanged>
+struct RecordGather {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  __amdgpu_buffer_rsrc_t rs;
+  const float4* base;
+  __device__ __forceinline__ RecordGather(const Surfels& S, int g) : base(S.group(g, 0)) {
+    // (word 3: 32-bit data format, the raw-buffer descriptor of gfx9; stride 0)
+    if (kRanged) rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(base), 0, (int)((uint32_t)S.pitch * 16u), 0x00020000);
+  }
+  __device__ __forceinline__ float4 at(uint32_t slot, uint32_t self) const {
+    if (!kRanged) return base[slot == kInvalid ? self : slot];
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(slot * 16u), 0, 0);
+    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+  }
+};
+
+// The second half of the neighbour update for one lane (kernels.cu:1293-1380): slot i at g with normal gn and r^2, its
+// links t4, the supporting surfels of the four adjacent pixels in cand[].
+template <bool kRanged>
+__device__ __forceinline__ void relink(const Surfels& S, const FrameCtx& c, const Lists& L, uint32_t i, const Vec3& g, const Vec3& gn,
+                                       float r2, const uint4& t4, uint32_t (&cand)[4]) {
+  // Only a candidate that is a surfel, not the slot itself and not yet one of its links can change a link: a candidate
+  // that is a link meets itself in the index compare below (best_n = -2) -- and if an earlier candidate has taken its
+  // place by then, it was the farthest link, so every link left is at most as far as it and `d2 < best_d2` fails.  No
+  // record decides any of that, so the lane asks for records only where something can change: a 16-byte gather is a
+  // cache-line request of its own, and the requests are what this kernel's time is made of.
+  // So such candidates are struck from the list (kInvalid = nothing to evaluate) before anything is gathered.
+  uint32_t ni[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+    if (cand[d] == i || cand[d] == t4.x || cand[d] == t4.y || cand[d] == t4.z || cand[d] == t4.w) cand[d] = kInvalid;
+  if ((cand[0] & cand[1] & cand[2] & cand[3]) == kInvalid) return;   // (all four struck: nothing to store, as before)
+  // gathers of the 4 current neighbours (P) and of the candidates left (P, N), all issued before the first use;
+  // empty link slots read the slot's own record, struck candidates nothing (RecordGather)
+  const RecordGather<kRanged> gather_p(S, kGroupP), gather_n(S, kGroupN);
+  float4 np4[4], cp4[4], cn4[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) np4[q] = *S.group(kGroupP, ni[q] == kInvalid ? i : ni[q]);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) { cp4[d] = gather_p.at(cand[d], i); cn4[d] = gather_n.at(cand[d], i); }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { keep(np4[q].x); keep(np4[q].y); keep(np4[q].z); }   // (or the first link's record is fetched behind the others' arrival)
+  float nd2[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (ni[q] == kInvalid) nd2[q] = __builtin_inff();
+    else {
+      const float dx = g.x - np4[q].x, dy = g.y - np4[q].y, dz = g.z - np4[q].z;
+      nd2[q] = dx * dx + dy * dy + dz * dz;
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const uint32_t nb = cand[d];
+    if (nb == kInvalid) continue;
+    const float dx = cp4[d].x - g.x, dy = cp4[d].y - g.y, dz = cp4[d].z - g.z;
+    const float d2 = dx * dx + dy * dy + dz * dz;
+    if (d2 > c.rf2 * r2) continue;
+    const float nd = gn.x * cn4[d].x + gn.y * cn4[d].y + gn.z * cn4[d].z;
+    if (nd <= 0) continue;
+    int best_n = -1; float best_d2 = -1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (best_n == -2) continue;
+      if (nb == ni[q]) { best_n = -2; }
+      else if (nd2[q] > best_d2) { best_n = q; best_d2 = nd2[q]; }
+    }
+    if (best_n >= 0 && d2 < best_d2) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) if (q == best_n) { ni[q] = nb; nd2[q] = d2; }
+    }
+  }
+  if (ni[0] != t4.x || ni[1] != t4.y || ni[2] != t4.z || ni[3] != t4.w) {
+    S.set_neighbors(i, make_uint4(ni[0], ni[1], ni[2], ni[3]));
+    L.hot_epoch[i >> L.hot_shift] = (uint8_t)L.epoch;   // (new links)
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // UpdateNeighborsCUDAKernel, kernels.cu:1197-1380.
 template <bool kUseList>
 __device__ __forceinline__ void update_neighbors_body(const Surfels& S, const FrameCtx& c, const Scratch& sc, const FrameIn& in,
@@ -1617,52 +1710,9 @@ __device__ __forceinline__ void update_neighbors_body(const Surfels& S, const Fr
     if (r2 < 0) continue;
     if (obs_r2 / r2 > 1.5f * 1.5f) continue;  // :1287-1291
 
-    // gathers of the 4 current neighbours (P) and the 4 candidates (P, N), all issued before the first use;
-    // empty slots read the slot's own records
-    uint32_t ni[4] = {t4.x, t4.y, t4.z, t4.w};
-    float4 np4[4], cp4[4], cn4[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) np4[q] = *S.group(kGroupP, ni[q] == kInvalid ? i : ni[q]);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const uint32_t gidx = (cand[d] == kInvalid) ? i : cand[d];
-      cp4[d] = *S.group(kGroupP, gidx);
-      cn4[d] = *S.group(kGroupN, gidx);
-    }
-    float nd2[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (ni[q] == kInvalid) nd2[q] = __builtin_inff();
-      else {
-        const float dx = g.x - np4[q].x, dy = g.y - np4[q].y, dz = g.z - np4[q].z;
-        nd2[q] = dx * dx + dy * dy + dz * dz;
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const uint32_t nb = cand[d];
-      if (nb == kInvalid || nb == i) continue;
-      const float dx = cp4[d].x - g.x, dy = cp4[d].y - g.y, dz = cp4[d].z - g.z;
-      const float d2 = dx * dx + dy * dy + dz * dz;
-      if (d2 > c.rf2 * r2) continue;
-      const float nd = gn.x * cn4[d].x + gn.y * cn4[d].y + gn.z * cn4[d].z;
-      if (nd <= 0) continue;
-      int best_n = -1; float best_d2 = -1;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (best_n == -2) continue;
-        if (nb == ni[q]) { best_n = -2; }
-        else if (nd2[q] > best_d2) { best_n = q; best_d2 = nd2[q]; }
-      }
-      if (best_n >= 0 && d2 < best_d2) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if (q == best_n) { ni[q] = nb; nd2[q] = d2; }
-      }
-    }
-    if (ni[0] != t4.x || ni[1] != t4.y || ni[2] != t4.z || ni[3] != t4.w) {
-      S.set_neighbors(i, make_uint4(ni[0], ni[1], ni[2], ni[3]));
-      L.hot_epoch[i >> L.hot_shift] = (uint8_t)L.epoch;   // (new links)
-    }
+    // (one uniform branch around the whole second half: a choice per gather would split the gathers again)
+    if (L.plain_gathers) relink<false>(S, c, L, i, g, gn, r2, t4, cand);
+    else relink<true>(S, c, L, i, g, gn, r2, t4, cand);
   }
   ts_end(c.ts, kTsUpdEnd, block, min(n_blocks, n_steps));   // (the workgroups that walked the last steps of the first round)
 }
@@ -2672,9 +2722,12 @@ k_delta_gather(Surfels S, uint8_t* __restrict__ dirty8, const uint32_t* __restri
 }
 
 __global__ void __launch_bounds__(kBlock)
-k_decode_conflicting(const uint32_t* __restrict__ key, uint32_t* __restrict__ out, int P) {
+k_decode_assoc(const uint4* __restrict__ assoc, uint32_t* __restrict__ out, int P, int first_depth) {
+  // the debug images that live in the association record only: the first depth (float bits) or the conflicting surfel
   const int k = blockIdx.x * kBlock + threadIdx.x;
-  if (k < P) out[k] = (key[k] == kInvalid) ? kInvalid : (key[k] & 0x7FFFFFFFu);
+  if (k >= P) return;
+  const uint4 a = assoc[k];
+  out[k] = first_depth ? a.x : (a.y == kInvalid) ? kInvalid : (a.y & 0x7FFFFFFFu);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -2911,6 +2964,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(r->mem.alloc(&r->L.hot_epoch, (size_t)r->L.n_hot_groups + 64, true));   // (zeros: "last active in call 0")
   SMX_TRY(r->mem.alloc(&r->L.seg_targets, (size_t)r->nsegB * kBlockB, true));   // (written by the unfiltered passes of the hold-off calls before anyone reads it)
   r->L.epoch = 128;   // (far from the zeros)
+  r->L.plain_gathers = r->S.pitch >= kRangedGatherMaxPitch ? 1u : 0u;
   r->hot_filter_enabled = 1;
   r->fuse_edges = kFuseEdgesDefault;
   r->hot_holdoff = 3;
@@ -2928,8 +2982,7 @@ int smx_recon_create(uint32_t max_surfel_count, int32_t width, int32_t height,
   SMX_TRY(r->mem.alloc(&r->sc.supporting, P, true));
   SMX_TRY(r->mem.alloc(&r->sc.counts, P, true));
   SMX_TRY(r->mem.alloc(&r->sc.depth_sums, P, true));
-  SMX_TRY(r->mem.alloc(&r->sc.confl_key, P, true));
-  SMX_TRY(r->mem.alloc(&r->sc.first_depth, P, true));
+  SMX_TRY(r->mem.alloc(&r->sc.assoc, P, true));
   for (int k = 0; k < 2; ++k) {
     SMX_TRY(r->mem.alloc(&r->vis_count_set[k], (size_t)kSubLists * kCountStride, true));
     SMX_TRY(r->mem.alloc(&r->ovf_count_set[k], 1, true));
@@ -3093,7 +3146,7 @@ int smx_recon_get_handover_mode(smx_recon r, int32_t* mode) {
 }
 
 int smx_recon_set_scan_mode(smx_recon r, int32_t mode) {
-  SMX_CHECK_ARG(r != nullptr && mode >= 0 && mode <= 1023);
+  SMX_CHECK_ARG(r != nullptr && mode >= 0 && mode <= 2047);
   SMX_ON_DEVICE(r->device);
   r->grid_list = ((mode >> 8) & 1) ? 4 : r->grid_list_full;   // four workgroups walk every list: many steps each
   r->scan_mode = mode & 1;
@@ -3105,6 +3158,7 @@ int smx_recon_set_scan_mode(smx_recon r, int32_t mode) {
   r->fb.hash_mask = ((mode >> 6) & 1) ? 1u : (uint32_t)kFarHash - 1u;   // 2 destinations per sender workgroup: the rest spills
   r->fuse_edges = ((mode >> 9) & 1) ? 1 : kFuseEdgesDefault;   // one launch: the segment's workgroup of pass B does the segment's edge work itself
   r->blend_other_tile = (mode >> 7) & 1;                  // the blend's other tile size (40 x 40 where it would take 32 x 32 and vice versa)
+  r->L.plain_gathers = (((mode >> 10) & 1) || r->S.pitch >= kRangedGatherMaxPitch) ? 1u : 0u;   // the neighbour update's route for capacities from 2^28 slots
   return SMX_OK;
 }
 
@@ -3629,10 +3683,11 @@ int smx_recon_debug_download_scratch(smx_recon r, smx_stream s, int32_t which, v
     case SMX_SCRATCH_SUPPORTING: src = r->sc.supporting; bytes = P * 4; break;
     case SMX_SCRATCH_SUPPORT_COUNTS: src = r->sc.counts; bytes = P * 4; break;
     case SMX_SCRATCH_DEPTH_SUMS: src = r->sc.depth_sums; bytes = P * 8; break;
-    case SMX_SCRATCH_FIRST_DEPTH: src = r->sc.first_depth; bytes = P * 4; break;
     case SMX_SCRATCH_NEW_FLAGS: src = r->new_flags; bytes = P; break;
+    case SMX_SCRATCH_FIRST_DEPTH:
     case SMX_SCRATCH_CONFLICTING:
-      hipLaunchKernelGGL(k_decode_conflicting, dim3(div_up((long long)P, kBlock)), dim3(kBlock), 0, st, r->sc.confl_key, r->tmp_u32, (int)P);
+      hipLaunchKernelGGL(k_decode_assoc, dim3(div_up((long long)P, kBlock)), dim3(kBlock), 0, st, r->sc.assoc, r->tmp_u32, (int)P,
+                         which == SMX_SCRATCH_FIRST_DEPTH ? 1 : 0);
       src = r->tmp_u32; bytes = P * 4; break;
     case SMX_SCRATCH_NEW_INDICES:
       hipLaunchKernelGGL(k_global_ranks, dim3(div_up((long long)P, kBlock)), dim3(kBlock), 0, st, r->new_ranks, r->block_offsets, r->tmp_u32, (int)P);

@@ -92,13 +92,15 @@ struct Surfels {
   View view(int g) const { return View{reinterpret_cast<const float4*>(base) + quad(g, 0), quad(g, 1) - quad(g, 0)}; }
 };
 
-// The association images of a frame (built per image tile by k_assoc_tiles).
+// The association images of a frame (built per image tile by k_assoc_tiles).  `assoc` is one 16-byte record per pixel,
+// {first depth (float bits), conflict key, count, supporting surfel}: what the integration and the flag pass need of a
+// pixel in one request.  The supporting surfel and the count are ALSO kept as images, for the kernels that read them
+// alone or next to the depth sums (the blend, the neighbour update, the creation).
 struct Scratch {
   uint32_t* supporting;
   uint32_t* counts;
   long long* depth_sums;
-  uint32_t* confl_key;
-  float* first_depth;
+  uint4* assoc;
 };
 
 constexpr int kBlock = 256;
@@ -156,6 +158,8 @@ struct Lists {
   // flag byte / link record of it was written.  `epoch` = this call's number.  (At C2 a group is 2048 slots, at C3 8192.)
   uint8_t* seg_act;       // per pass-A segment: 1 = pass A found visible or recently updated slots in it this frame
   uint32_t descending;    // != 0: this call's all-slot kernels walk the segments downwards (segment_of_block)
+  uint32_t plain_gathers; // != 0: the neighbour update gathers without range-checked buffers (RecordGather): group arrays of
+                          // 4 GB and more, or scan mode bit 10
   uint8_t* hot_epoch;
   uint16_t* seg_targets;  // per pass-B segment: bitmap of the groups its links point into (see k_neighbor_scan)
   uint32_t n_hot_groups;
