@@ -1490,7 +1490,7 @@ int smx_rayscene_debug_timings(smx_rayscene sc, float* out_ms, int32_t capacity)
  *    call's refusal, and `out` is zeroed.  on_device says where triangles lives.
  * All scene memory is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation.
  * Not done: incremental updates of a scene; an index shared with a smx_rayscene (their boxes differ); a BVH; an enqueue-only
- * query without host synchronisation; point-to-mesh registration on top of the scene. */
+ * query without host synchronisation (smx_distscene_register below enqueues the query's kernels itself). */
 typedef struct smx_distscene_s* smx_distscene;
 typedef struct {
   float max_distance;        /* the bound: a query asks for this much or less */
@@ -1521,6 +1521,87 @@ int smx_recon_compare_to_distscene(smx_recon r, smx_stream s, smx_distscene sc, 
  * SMX_DISTSCENE_PHASES. */
 #define SMX_DISTSCENE_PHASES 5
 int smx_distscene_debug_timings(smx_distscene sc, float* out_ms, int32_t capacity);
+
+/* ---- registration of a point set to a distance scene: point-to-plane ICP against the triangles (not in the reference;
+ * DESIGN.md 5q) ----
+ * Inputs: a built scene, points [n][3] float32 in their own frame, optionally a unit normal per point, and a start pose T_init
+ * (scene <- points, row-major 3x4).  State: T, the pose scene <- points, kept on the device in double; it starts as T_init
+ * exactly, and every iteration reads it as 12 floats, Tf.  Every float32 expression below is evaluated as written, one
+ * rounding per operation, no contraction.
+ * One iteration of a level with stride s and gate q visits the samples j < ceil(n / s), sample j being point j s:
+ *   Move.       p' = ((R00 x + R01 y) + R02 z) + t0 from Tf, likewise the other two rows; with normals m = R n, summed in the
+ *               same order.
+ *   Associate.  The answer for p' is exactly smx_distscene_query's at max_distance = q, unsigned: nearest t, closest Q.  A
+ *               BAD p' (not finite, or a coordinate beyond 64 m) is BAD by that call's rule.  The winner's corners a, b, c
+ *               are the float32 words its first record holds, as the query reads them.
+ *   Row.        e1 = b - a, e2 = c - a, g = e1 x e2 (g.x = e1.y e2.z - e1.z e2.y, the others cyclic), len2 = (g.x g.x + g.y
+ *               g.y) + g.z g.z.  A winner with !(len2 > 0) is collinear: the sample counts as matched and is no inlier.  N = g
+ *               / sqrtf(len2) per component (smx_recon_triangulate winds counter-clockwise about the surfel normals, so N
+ *               needs no flip).  With normals the sample needs (m.x N.x + m.y N.y) + m.z N.z >= cos(max_normal_angle), the
+ *               cosine formed on the host as smx_recon_track forms it.  d = p' - Q, r = (N.x d.x + N.y d.y) + N.z d.z, J = (p'
+ *               x N, N) -- rotation first: the update is a twist applied on the left, in the scene's frame.
+ *   Sums.       The layout and the order of smx_recon_track: [0..20] JtJ, [21..26] Jtr, [27] sum r^2, [28] inliers, [29]
+ *               samples that are not BAD, [30] samples matched within q; products in float, sums in double, a lane of a
+ *               workgroup of 256 visiting the samples i, i + 256 grid, ..., the cross-lane tree, the wavefronts in index
+ *               order, the workgroups' slabs in index order.  Two calls give the same bits.
+ *   Solve.      That call's, unchanged: the finiteness test, DEGENERATE where [29] > 0 and [30] == 0 or on a small pivot,
+ *               TOO_FEW_INLIERS, the LDL^T factorisation, T <- exp(x) Tf.  CONVERGED skips the rest of the level, the next
+ *               level still runs; a bad status is sticky and T keeps the value it had before the failing iteration; the last
+ *               iteration run is also judged against min_inlier_fraction x [29].
+ * Launches per iteration: the move, the query's own three steps (the points' keys, the sort, the walk), the reduce, the
+ * solve; every iteration of every level is enqueued back to back on s and nothing is read back until the end.  In a skipped
+ * iteration (a bad status, a converged level) the move writes NaN points, so that the query's kernels find no work, and the
+ * reduce and the solve return at once.  result is a device pointer if result_on_device, else a host pointer (the call returns
+ * with it filled); with on_device points (and normals) and result_on_device the call returns without waiting for the device.
+ * level_max_distance[l] = 0 means the scene's bound.  n_points == 0 is valid (TOO_FEW_INLIERS, or DEGENERATE at min_inliers ==
+ * 0).  The call is ordered on s, behind the scene's previous registration on whatever stream; one caller thread per scene (it
+ * uses the scene's query workspace and a workspace of its own, both counted by smx_debug_live_allocations and reached by
+ * smx_debug_fail_allocation; every allocation happens before the first launch).  It touches no smx_recon: a scene is a
+ * snapshot, and a registration gives the same bytes after the map has changed or the object it was built from is gone.
+ * SMX_ERR_INVALID_ARGUMENT, nothing launched and nothing written: a scene without a build, no level with iterations, more than
+ * 32 iterations in a level, a stride outside 1 .. 65536, a level's distance that is neither 0 nor in 1e-3f .. the scene's
+ * bound, a T_init that is not finite, non-positive gates, points == NULL with n_points > 0, n_points > 2^28.
+ * Not done: robust (Huber) weights; rejecting matches on the mesh boundary; scale or non-rigid alignment; mesh-to-mesh in one
+ * call (compose smx_recon_sample_mesh with this); an incremental scene. */
+typedef struct {             /* smx_register_params_default() fills the defaults */
+  int32_t level_stride[3];          /* sample j of a level is point j * stride, j < ceil(n / stride); 1 .. 65536 */
+  int32_t level_iterations[3];      /* 0 = level unused; at most 32 */
+  float   level_max_distance[3];    /* the gate q of the level; 0 = the scene's bound; else 1e-3f .. the bound */
+  float   max_normal_angle_deg;     /* used only when normals != NULL */
+  float   convergence_rotation, convergence_translation;
+  int32_t min_inliers;  float min_inlier_fraction;  float min_pivot_ratio;
+} smx_register_params;
+/* Defaults: strides 4, 2, 1; iterations 4, 5, 10; distances 0, 0, 0; 30 degrees; convergence 1e-5 rad / 1e-5 m; min_inliers
+ * 50, min_inlier_fraction 0.1, min_pivot_ratio 1e-6 (the tracker's). */
+typedef struct {
+  float scene_T_points[12];   /* T_init itself, bit for bit, if nothing could be solved */
+  int32_t status, iterations_run;               /* status: the SMX_TRACK_* values, same meaning and order */
+  uint32_t inliers, points_used;                /* of the last iteration run: sums [28] and [29] */
+  float rms_residual, last_update_rotation, last_update_translation;
+  float information[36];                        /* JtJ of the last iteration, row-major 6x6 */
+} smx_register_result;
+int smx_register_params_default(smx_register_params* out);
+int smx_distscene_register(smx_distscene sc, smx_stream s, const smx_register_params* p,
+                           const float* points /* [n_points][3] */, const float* normals /* [n_points][3], may be NULL */,
+                           uint32_t n_points, int32_t on_device, const float T_init[12],
+                           smx_register_result* result, int32_t result_on_device);
+/* Tests and tuning: one record per iteration of the scene's last registration that produced sums (the one that raised a bad
+ * status included), with the pose it linearised at.  Synchronises s; *count = records of the call (at most `capacity` are
+ * written). */
+#define SMX_REGISTER_SUMS 31
+typedef struct {
+  int32_t level, stride, status, reserved;
+  float Tf[12];               /* the pose this iteration linearised at */
+  double sums[SMX_REGISTER_SUMS];
+  double x[6];
+} smx_register_iteration;
+int smx_distscene_debug_register_iterations(smx_distscene sc, smx_stream s, smx_register_iteration* recs,
+                                            int32_t capacity, int32_t* count);
+/* Tools: milliseconds of the last registration by timed events on its stream: [0] the whole call, [1..4] the move, the query,
+ * the reduce and the solve of the LAST iteration enqueued (a refused call leaves the figures of the one before).  capacity >=
+ * SMX_REGISTER_PHASES. */
+#define SMX_REGISTER_PHASES 5
+int smx_distscene_debug_register_timings(smx_distscene sc, float* out_ms, int32_t capacity);
 
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----

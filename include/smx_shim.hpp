@@ -516,6 +516,15 @@ class DistanceScene {
                                        n_points ? nearest->data() : nullptr, n_points ? distance->data() : nullptr,
                                        closest && n_points ? closest->data() : nullptr, 0, stats));
   }
+  // Point-to-plane ICP of `points` ([n][3], their own frame) against the scene's triangles from the pose T_init (scene <-
+  // points, row-major 3x4), smx_distscene_register in smx.h; normals (may be null) holds a unit normal per point and switches
+  // the normal gate on.  Returns with *result filled.
+  void Register(cudaStream_t stream, const std::vector<float>& points, const std::vector<float>* normals,
+                const smx_register_params& params, const float T_init[12], smx_register_result* result) {
+    const u32 n_points = (u32)(points.size() / 3);
+    SMX_SHIM_CHECK(smx_distscene_register(handle_, stream, &params, n_points ? points.data() : nullptr,
+                                          normals && n_points ? normals->data() : nullptr, n_points, 0, T_init, result, 0));
+  }
   const smx_distscene_stats& stats() const { return stats_; }
   smx_distscene handle() const { return handle_; }
 

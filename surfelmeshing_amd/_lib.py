@@ -324,6 +324,52 @@ class DistSceneStats(C.Structure):
                 [("cell_size_used", C.c_float), ("max_distance", C.c_float), ("device_bytes", C.c_uint64)])
 
 
+class RegisterParams(C.Structure):
+    """smx_register_params: schedule, gates and status thresholds of smx_distscene_register."""
+    _fields_ = [("level_stride", C.c_int32 * 3), ("level_iterations", C.c_int32 * 3), ("level_max_distance", C.c_float * 3),
+                ("max_normal_angle_deg", C.c_float), ("convergence_rotation", C.c_float), ("convergence_translation", C.c_float),
+                ("min_inliers", C.c_int32), ("min_inlier_fraction", C.c_float), ("min_pivot_ratio", C.c_float)]
+
+    @classmethod
+    def defaults(cls, levels=None, **kw):
+        """smx_register_params_default(), then `levels` (up to three (stride, iterations) or (stride, iterations,
+        max_distance) tuples, coarse to fine) and any field by name."""
+        p = cls()
+        check(load().smx_register_params_default(C.byref(p)))
+        if levels is not None:
+            levels = [tuple(lv) for lv in levels]
+            if not 1 <= len(levels) <= 3 or any(len(lv) not in (2, 3) for lv in levels):
+                raise ValueError("one to three (stride, iterations[, max_distance]) levels")
+            for k in range(3):
+                lv = levels[k] if k < len(levels) else (1, 0, 0.0)
+                p.level_stride[k], p.level_iterations[k], p.level_max_distance[k] = lv[0], lv[1], lv[2] if len(lv) == 3 else 0.0
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(k)
+            kind = dict(cls._fields_)[k]
+            setattr(p, k, kind(*v) if issubclass(kind, C.Array) else v)
+        return p
+
+
+class RegisterResult(C.Structure):
+    """smx_register_result"""
+    _fields_ = [("scene_T_points", C.c_float * 12), ("status", C.c_int32), ("iterations_run", C.c_int32),
+                ("inliers", C.c_uint32), ("points_used", C.c_uint32), ("rms_residual", C.c_float),
+                ("last_update_rotation", C.c_float), ("last_update_translation", C.c_float), ("information", C.c_float * 36)]
+
+
+REGISTER_SUMS = 31      # SMX_REGISTER_SUMS
+REGISTER_PHASES = 5     # SMX_REGISTER_PHASES
+REGISTER_MAX_STRIDE = 65536
+REGISTER_MAX_POINTS = 1 << 28
+
+
+class RegisterIteration(C.Structure):
+    """smx_register_iteration"""
+    _fields_ = [("level", C.c_int32), ("stride", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+                ("Tf", C.c_float * 12), ("sums", C.c_double * REGISTER_SUMS), ("x", C.c_double * 6)]
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -409,6 +455,7 @@ EXPORTS = [
     "smx_rayscene_debug_timings",
     "smx_distscene_create", "smx_distscene_destroy", "smx_distscene_params_default", "smx_recon_build_distscene", "smx_distscene_query",
     "smx_recon_compare_to_distscene", "smx_distscene_debug_timings",
+    "smx_register_params_default", "smx_distscene_register", "smx_distscene_debug_register_iterations", "smx_distscene_debug_register_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

@@ -30,6 +30,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
                    RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
                    DISTSCENE_PHASES, CompareSide, DistSceneParams, DistSceneStats,
+                   REGISTER_MAX_POINTS, REGISTER_MAX_STRIDE, REGISTER_PHASES, RegisterIteration, RegisterParams, RegisterResult,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -264,6 +265,38 @@ def distscene_check_query(scene, max_distance):
         raise ValueError("max_distance %g is above the %g the scene was built for" % (max_distance, scene.stats["max_distance"]))
 
 
+def register_check_params(p, bound):
+    """ValueError on what smx_distscene_register would refuse of a RegisterParams for a scene built for `bound`, before
+    anything is called."""
+    used = 0
+    for k in range(3):
+        it, s, q = int(p.level_iterations[k]), int(p.level_stride[k]), np.float32(p.level_max_distance[k])
+        if not 0 <= it <= 32:
+            raise ValueError("level_iterations must lie in 0 .. 32")
+        if it == 0:
+            continue
+        used += 1
+        if not 1 <= s <= REGISTER_MAX_STRIDE:
+            raise ValueError("level_stride must lie in 1 .. %d" % REGISTER_MAX_STRIDE)
+        if not (q == 0 or (np.isfinite(q) and np.float32(1e-3) <= q <= np.float32(bound))):
+            raise ValueError("level_max_distance %g must be 0 (the scene's bound) or lie in 0.001 .. %g, the bound" % (q, bound))
+    if used == 0:
+        raise ValueError("no level with iterations")
+    if not (0 < p.max_normal_angle_deg <= 180):
+        raise ValueError("max_normal_angle_deg must lie in (0, 180]")
+    if not (p.convergence_rotation >= 0 and p.convergence_translation >= 0 and p.min_inliers >= 0 and 0 <= p.min_inlier_fraction <= 1 and
+            p.min_pivot_ratio >= 0):
+        raise ValueError("convergence bounds, min_inliers, min_inlier_fraction (at most 1) and min_pivot_ratio must not be negative")
+
+
+def register_result_dict(res):
+    """smx_register_result as a dict: scene_T_points [3,4] and information [6,6] float32 arrays, the rest numbers."""
+    d = {n: getattr(res, n) for n, _ in RegisterResult._fields_ if n not in ("scene_T_points", "information")}
+    d["scene_T_points"] = np.array(res.scene_T_points, np.float32).reshape(3, 4)
+    d["information"] = np.array(res.information, np.float32).reshape(6, 6)
+    return d
+
+
 def compare_side_dict(side, max_distance=None):
     """smx_compare_side as a dict, as one side of compare_stats_dict."""
     dist = distance_stats_dict(side.distance)
@@ -348,6 +381,81 @@ class DistanceScene:
         stats = distance_stats_dict(st)
         stats["max_distance"] = float(p.max_distance)      # (what the histogram's bins are fractions of)
         return (nearest, distance, closest, stats) if return_closest else (nearest, distance, stats)
+
+    def Register(self, stream, points, normals=None, T_init=None, params=None, result_buffer=None):
+        """Point-to-plane ICP of `points` ([P,3] float32, in their own frame) against the scene's triangles
+        (smx_distscene_register): every iteration moves the samples by the pose, asks the scene's own query for their closest
+        triangles and solves for a left twist; all iterations are enqueued back to back on `stream`.  normals ([P,3], optional)
+        switches the normal gate on.  T_init: the start pose scene <- points ([3,4] or 12 values; None = the identity).
+        params: a RegisterParams (RegisterParams.defaults()).  points (and normals) are numpy arrays or contiguous float32
+        device tensors.  Without result_buffer the call is synchronous and returns a dict: scene_T_points [3,4] float32,
+        status, iterations_run, inliers, points_used, rms_residual, last_update_rotation, last_update_translation, information
+        [6,6].  With result_buffer (a CUDABuffer of at least ctypes.sizeof(RegisterResult) bytes in one row, or a device
+        address) the smx_register_result stays on the device, and with device points nothing waits for the host."""
+        if not getattr(self, "_h", None):
+            raise ValueError("the scene is closed")
+        if not getattr(self, "stats", None):
+            raise ValueError("the scene holds no build")
+        p = params if params is not None else RegisterParams.defaults()
+        register_check_params(p, self.stats["max_distance"])
+        T = np.ascontiguousarray(np.asarray(np.eye(3, 4) if T_init is None else T_init, np.float32).reshape(-1))
+        if T.size != 12 or not np.all(np.isfinite(T)):
+            raise ValueError("T_init must hold 12 finite values")
+        dev = _device_address(points) is not None
+        if normals is not None and (_device_address(normals) is not None) != dev:
+            raise ValueError("points and normals must both be device tensors or both be host arrays")
+        keep = []
+        if dev:
+            import torch
+            for a in (points, normals):
+                if a is not None and not (a.is_contiguous() and a.dtype == torch.float32 and a.numel() % 3 == 0):
+                    raise ValueError("a device tensor of points or normals must be contiguous [P,3] float32")
+            n_points = points.numel() // 3
+            if normals is not None and normals.numel() != points.numel():
+                raise ValueError("normals must have the shape of points")
+            pin = points.data_ptr() if n_points else None
+            nin = normals.data_ptr() if normals is not None and n_points else None
+            torch.cuda.current_stream(points.device).synchronize()      # (the tensors' producers; the call runs on `stream`)
+        else:
+            pts = np.ascontiguousarray(points, np.float32)
+            if pts.size % 3:
+                raise ValueError("points must hold three values per row")
+            n_points = pts.size // 3
+            nr = None
+            if normals is not None:
+                nr = np.ascontiguousarray(normals, np.float32)
+                if nr.size != pts.size:
+                    raise ValueError("normals must have the shape of points")
+            keep = [pts, nr]
+            pin = pts.ctypes.data if n_points else None
+            nin = nr.ctypes.data if nr is not None and n_points else None
+        if n_points > REGISTER_MAX_POINTS:
+            raise ValueError("at most 2^28 points")
+        on_device = result_buffer is not None
+        res = RegisterResult()
+        if on_device:
+            out = C.c_void_p(result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer))
+        _lib.check(_lib.load().smx_distscene_register(self._h, _sv(stream), C.byref(p), C.c_void_p(pin), C.c_void_p(nin), C.c_uint32(n_points),
+                                                      C.c_int32(1 if dev else 0), T.ctypes.data_as(C.c_void_p), out if on_device else C.byref(res),
+                                                      C.c_int32(1 if on_device else 0)))
+        del keep
+        return None if on_device else register_result_dict(res)
+
+    def RegisterIterations(self, stream=None):
+        """One dict per iteration of the scene's last Register call (smx_distscene_debug_register_iterations): level, stride,
+        status, Tf (the 12 floats the iteration linearised at), sums (31 float64: JtJ upper triangle, Jtr, sum r^2, inliers,
+        samples that are not BAD, samples matched), x (6)."""
+        recs = (RegisterIteration * 96)()
+        n = C.c_int32(0)
+        _lib.check(_lib.load().smx_distscene_debug_register_iterations(self._h, _sv(stream), recs, C.c_int32(96), C.byref(n)))
+        return [{"level": r.level, "stride": r.stride, "status": r.status, "Tf": np.array(r.Tf, np.float32), "sums": np.array(r.sums, np.float64),
+                 "x": np.array(r.x, np.float64)} for r in recs[:n.value]]
+
+    def debug_register_timings(self):
+        """Milliseconds of the last Register call: the whole call, then move, query, reduce and solve of its last iteration."""
+        out = (C.c_float * REGISTER_PHASES)()
+        _lib.check(_lib.load().smx_distscene_debug_register_timings(self._h, out, C.c_int32(REGISTER_PHASES)))
+        return dict(zip(("call", "move", "query", "reduce", "solve"), [float(v) for v in out]))
 
     def debug_timings(self):
         """Milliseconds of the last build (mark, index, first) and of the last query (query, stats)."""

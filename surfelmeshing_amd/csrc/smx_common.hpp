@@ -211,6 +211,11 @@ class StreamMark {
     if (busy_) SMX_HIP(hipStreamWaitEvent(st, ev_, 0));
     return SMX_OK;
   }
+  int sync() {   // (the host waits: for an owner about to let go of a block the marked work may still use)
+    if (busy_) SMX_HIP(hipEventSynchronize(ev_));
+    busy_ = false;
+    return SMX_OK;
+  }
   int record(hipStream_t st) {
     if (!ev_) SMX_HIP(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
     SMX_HIP(hipEventRecord(ev_, st));

@@ -16,7 +16,9 @@
 //
 // One query body serves two kernels: k_dist_query for the call, which re-reads the winner's corners from the map, and
 // k_dscene_query for a kept scene (smx_distscene.hip), which reads them from a record of the winner.
-// dist_scene_query, behind the kernels, is the host side of a scene's query: the query and stats phases on a kept index.
+// dist_scene_query, behind the kernels, is the host side of a scene's query: the query and stats phases on a kept index.  Its
+// enqueue-only half (dist_scene_reserve, then dist_scene_enqueue: keys, sort, walk) is what smx_distscene_register runs per
+// iteration (smx_register.hip).
 //
 // smx_recon_mesh_distance itself is at the end of the file: it owns the order of the phases, the workspace (DistanceWork,
 // smx_distance.hpp) and the second read of the counters (the first is tg_read_counts).
@@ -248,14 +250,32 @@ unsigned long long DistQueryWork::bytes() const {
          of(out_nearest) + of(counters);
 }
 
-int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_distance_params* p, const float* points, uint32_t n_points,
-                     uint32_t* nearest, float* distance, float* closest, bool dev, hipStream_t st, PhaseStamps<2>& stamps,
-                     smx_distance_stats* stats) {
-  // ---- every allocation of the query: the counters, the keys, the sort's buffers, the staging
+int dist_scene_reserve(DistQueryWork& w, uint32_t n_points) {
   if (!w.counters.get()) SMX_CALL(w.counters.alloc(kDistWords, false));
   SMX_CALL(w.best.reserve(n_points));
   for (int k = 0; k < 2; ++k) { SMX_CALL(w.keys[k].reserve(n_points)); SMX_CALL(w.vals[k].reserve(n_points)); }
   SMX_CALL(w.hist.reserve(radix_sort_workspace_elems(n_points)));
+  return SMX_OK;
+}
+
+int dist_scene_enqueue(const DistQueryWork& w, const DistSceneIndex& ix, const float* dpts, uint32_t n_points, float max_distance,
+                       int signed_distance, uint32_t* d_nearest, float* d_distance, float* d_closest, hipStream_t st) {
+  if (n_points == 0) return SMX_OK;
+  const dim3 g_pts(blocks_for(n_points)), b(kDistBlock);
+  hipLaunchKernelGGL(k_dist_point_keys, g_pts, b, 0, st, dpts, n_points, ix.cnt, w.keys[0].get(), w.vals[0].get());
+  SMX_LAUNCH_CHECK();
+  const int cur = radix_sort(w.keys, w.vals, n_points, 63, w.hist.get(), st);
+  hipLaunchKernelGGL(k_dscene_query, g_pts, b, 0, st, ix.first_rec, dpts, n_points, w.keys[cur].get(), w.vals[cur].get(), ix.table, ix.mask, ix.recs,
+                     ix.wide_recs, ix.n_wide, ix.cnt, max_distance * max_distance, signed_distance, d_nearest, d_distance, d_closest, w.best.get());
+  SMX_LAUNCH_CHECK();
+  return SMX_OK;
+}
+
+int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_distance_params* p, const float* points, uint32_t n_points,
+                     uint32_t* nearest, float* distance, float* closest, bool dev, hipStream_t st, PhaseStamps<2>& stamps,
+                     smx_distance_stats* stats) {
+  // ---- every allocation of the query: the counters, the keys, the sort's buffers, the staging
+  SMX_CALL(dist_scene_reserve(w, n_points));
   const float* dpts = nullptr;
   SMX_CALL(stage_in(w.pts, points, (size_t)3 * n_points, dev, st, &dpts));
   uint32_t* d_nearest = nearest;
@@ -278,16 +298,7 @@ int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_dista
   const dim3 b(kDistBlock);
 
   // ---- query
-  if (n_points > 0) {
-    const dim3 g_pts(blocks_for(n_points));
-    hipLaunchKernelGGL(k_dist_point_keys, g_pts, b, 0, st, dpts, n_points, ix.cnt, w.keys[0].get(), w.vals[0].get());
-    SMX_LAUNCH_CHECK();
-    const int cur = radix_sort(w.keys, w.vals, n_points, 63, w.hist.get(), st);
-    hipLaunchKernelGGL(k_dscene_query, g_pts, b, 0, st, ix.first_rec, dpts, n_points, w.keys[cur].get(), w.vals[cur].get(), ix.table, ix.mask, ix.recs,
-                       ix.wide_recs, ix.n_wide, ix.cnt, p->max_distance * p->max_distance, (int)p->signed_distance, d_nearest, d_distance, d_closest,
-                       w.best.get());
-    SMX_LAUNCH_CHECK();
-  }
+  SMX_CALL(dist_scene_enqueue(w, ix, dpts, n_points, p->max_distance, (int)p->signed_distance, d_nearest, d_distance, d_closest, st));
   SMX_CALL(stamps.mark(st));
 
   // ---- stats

@@ -159,6 +159,12 @@ struct DistSceneIndex {
 int dist_scene_query(DistQueryWork& w, const DistSceneIndex& ix, const smx_distance_params* p, const float* points, uint32_t n_points,
                      uint32_t* nearest, float* distance, float* closest, bool on_device, hipStream_t st, PhaseStamps<2>& stamps,
                      smx_distance_stats* stats);
+// Its enqueue-only half, which smx_distscene_register runs once per iteration: dist_scene_reserve holds every allocation (the
+// counters, the winning keys, the points' sort) for n_points points, in the order the query always had; dist_scene_enqueue
+// then launches k_dist_point_keys -> the sort -> k_dscene_query on st for device arrays and looks at nothing on the host.
+int dist_scene_reserve(DistQueryWork& w, uint32_t n_points);
+int dist_scene_enqueue(const DistQueryWork& w, const DistSceneIndex& ix, const float* dpts, uint32_t n_points, float max_distance,
+                       int signed_distance, uint32_t* d_nearest, float* d_distance, float* d_closest, hipStream_t st);
 #endif
 
 }  // namespace smx

@@ -135,6 +135,7 @@ int smx_recon_build_distscene(smx_recon r, smx_stream s, smx_distscene sc, const
                               int32_t on_device, smx_distscene_stats* stats) {
   SMX_CHECK_ARG(sc != nullptr);
   SMX_ON_DEVICE(sc->device);
+  SMX_CALL(sc->reg.mark.sync());         // (a registration may still be running: the one call on a scene that does not wait)
   dscene_clear(sc);                      // (a refused build leaves the scene empty too; queries are synchronous: nothing reads what goes)
   SMX_CHECK_ARG(r != nullptr && p != nullptr);
   SMX_CHECK_ARG(finite_f(p->max_distance) && p->max_distance >= 1e-3f && p->max_distance <= 16.0f);
@@ -182,6 +183,7 @@ int smx_distscene_query(smx_distscene sc, smx_stream s, const smx_distance_param
   }
   SMX_ON_DEVICE(sc->device);
   hipStream_t st = (hipStream_t)s;
+  SMX_CALL(sc->reg.mark.sync());         // (a registration still running uses the query's workspace, which may grow here)
   smx_distance_stats out;
   memset(&out, 0, sizeof(out));
   const DistSceneIndex ix{reinterpret_cast<const TgCell*>(sc->table.get()), sc->mask, reinterpret_cast<const TgRec*>(sc->recs.get()),

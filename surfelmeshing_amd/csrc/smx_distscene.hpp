@@ -37,6 +37,22 @@ SMX_DIST_FN void dscene_winner(uint32_t first_word, const Recs& cell_recs, const
 
 #if !defined(SMX_DISTSCENE_HOST_ONLY)
 // ---- part 2 ----------------------------------------------------------------------------------------------------------
+struct RegDev;                                               // smx_register.hpp
+// What smx_distscene_register keeps with the scene besides the query's workspace (glue: smx_register.hip).  The one call on a
+// scene that may return before its kernels are done: `mark` lies behind them, and whoever frees or grows a block of the scene
+// waits for it on the host first.
+struct RegisterWork {
+  DevBuf<float> pts, nrm;                  // staging when the caller's arrays are host memory
+  DevBuf<float> moved;                     // [m][3] the samples of an iteration as the pose moved them: the query's points
+  DevBuf<uint32_t> nearest;                // [m] the query's outputs
+  DevBuf<float> distance, closest;         // [m], [m][3]
+  DevBuf<double> slabs;                    // [kTrackMaxSlabs][kTrackSlabStride] the reduce kernel's per-workgroup sums
+  DevBuf<RegDev> state;                    // [1]
+  StreamMark mark;
+  PhaseStamps<1> whole;                    // the last call
+  PhaseStamps<4> last;                     // move, query, reduce, solve of its last iteration
+};
+
 constexpr int kDsceneBuildWords = 32;                        // the build's counters: the grid's words; device_bytes counts 32
 static_assert(kTgWords <= kDsceneBuildWords, "the build's counters");
 #endif
@@ -56,7 +72,8 @@ struct smx_distscene_s {
   uint32_t h[smx::kDsceneBuildWords] = {};         // ... and on the host
   uint32_t mask = 0, n_entries = 0, n_wide = 0, n_in = 0;
   float max_distance = 0.0f;                       // the bound of the build: a query asks for no more
-  smx::DistQueryWork query;                        // a query's
+  smx::DistQueryWork query;                        // a query's, and a registration's
+  smx::RegisterWork reg;                           // a registration's own
   smx::PhaseStamps<3> build_stamps;                // mark, index, first of the last build
   smx::PhaseStamps<2> query_stamps;                // query, stats of the last query
 };

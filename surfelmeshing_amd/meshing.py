@@ -220,6 +220,23 @@ def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=Non
     return rec.BuildDistanceScene(stream, triangles, max_distance, cell_size)
 
 
+def register_params(**kw):
+    """The parameters of register_points as a RegisterParams: the library's defaults (strides 4, 2, 1; iterations 4, 5, 10; every
+    level gated at the scene's bound; 30 degrees; the tracker's thresholds), then levels=[(stride, iterations[, max_distance]),
+    ...] and any field of smx_register_params by name.  AttributeError on a name that is no field."""
+    from ._lib import RegisterParams
+    return RegisterParams.defaults(**kw)
+
+
+def register_points(scene, points, normals=None, T_init=None, params=None, stream=None):
+    """Aligns `points` ([P,3], their own frame) to the mesh a DistanceScene holds (build_distance_scene) by point-to-plane ICP
+    from the pose T_init (scene <- points, [3,4]; None = the identity): the dict of DistanceScene.Register, whose scene_T_points
+    is the pose found and whose status is one of the tracker's.  normals ([P,3], optional) adds the normal gate.  params: a
+    register_params(...) (None = the defaults).  The scene's bound limits how far a point may lie from the mesh and still
+    count, so build the scene for the misalignment expected.  ValueError on what the library would refuse."""
+    return scene.Register(stream, points, normals, T_init, params if params is not None else register_params())
+
+
 def mesh_distance(rec, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False, stream=None, scene=None):
     """For every point its closest triangle of `triangles` within max_distance, on the device: (nearest, distance[, closest],
     stats) as CUDASurfelReconstruction.MeshDistance returns them.  With scene (build_distance_scene) the points are measured

@@ -10,6 +10,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --distance METRES[,METRES...] --scene [--decimate METRES] [--compare N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH --scene [--decimate METRES] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --register POINTS [--distance METRES[,METRES...]] [--decimate METRES] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -72,6 +73,12 @@ ray; the index rebuild's share (mark + index) of the call; and smx_recon_render_
 beside it, with the share of pixels whose index equals the rasteriser's.  Writes profiles/raycast_bench.{txt,json} unless --txt
 / --json say otherwise.
 
+--register POINTS measures smx_distscene_register: POINTS points of synth.room_surface_points (on the device, with
+the walls' normals) registered from the identity to a distance scene of the full mesh and of the decimated one (--decimate,
+default 0.05 m), built for every bound of --distance (default 0.01,0.05), with the default schedule; per call the whole time and
+the move, query, reduce and solve of the last iteration by the library's events, and beside them, in the same process, the
+scene's plain query of the same points at the bound.  Writes profiles/register_bench.{txt,json} unless --txt / --json say otherwise.
+
 --raycast WxH --scene measures smx_rayscene on the same rays and the same two meshes (the decimated one at the
 first --decimate cell, 0.05 m by default), everything in one process: smx_recon_raycast_mesh re-measured first (its call, its
 phases, and the min and max of its cast + stats over the repetitions: the spread every comparison allows); then for occupancy
@@ -114,6 +121,8 @@ ap.add_argument("--raycast", default=None, metavar="WxH", help="measure smx_reco
 ap.add_argument("--scene", action="store_true", help="with --raycast: measure smx_rayscene (build by phase, cast for every occupancy setting) "
                                                       "beside smx_recon_raycast_mesh, on the full mesh and the one decimated at the first --decimate cell; "
                                                       "with --distance: measure smx_distscene (build by phase, queries) beside smx_recon_mesh_distance")
+ap.add_argument("--register", type=int, default=0, metavar="POINTS", help="measure smx_distscene_register of this many room-surface points "
+                                                                           "against the full and the decimated mesh at the --distance bounds")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -818,6 +827,120 @@ def distscene_main():
     nn.close()
 
 
+REGISTER_PHASES = ("move", "query", "reduce", "solve")
+
+
+def register_main():
+    """--register POINTS: smx_distscene_register beside the scene's plain query of the same points in one process."""
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    maxes = [float(c) for c in (args.distance or "0.01,0.05").split(",")]
+    cell = float(args.decimate.split(",")[0]) if args.decimate else 0.05
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    from surfelmeshing_amd import meshing, synth
+    pts = synth.room_surface_points(args.register + args.register // 50 + 64)[0]        # (about that many: a few more, thinned to the count)
+    if pts.shape[0] > args.register:
+        pts = pts[np.sort(np.random.default_rng(7).permutation(pts.shape[0])[:args.register])]
+    pts = np.ascontiguousarray(pts, np.float32)
+    P = pts.shape[0]
+    # the wall a point lies on is the axis along which it is nearest to the room's half extent; its normal looks into the room
+    wall = np.argmax(np.abs(pts) / np.asarray(synth.ROOM_HALF, np.float32), axis=1)
+    nrm = np.zeros_like(pts)
+    nrm[np.arange(P), wall] = -np.sign(pts[np.arange(P), wall])
+    tp, tn = torch.from_numpy(pts).cuda(), torch.from_numpy(nrm).cuda()
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    dnear, ddist = api.CUDABuffer(1, P, np.uint32), api.CUDABuffer(1, P, np.float32)
+    dres = api.CUDABuffer(1, C.sizeof(_lib.RegisterResult) // 4 + 4, np.uint32)
+    say("# %d points of synth.room_surface_points with their normals, on the device; the default schedule (strides 4, 2, 1; 4 + 5 + 10 iterations, "
+        "every level gated at the scene's bound) from the identity; medians of %d repetitions after one that allocates" % (P, args.reps))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def spread(v):
+        return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+    def show(s):
+        return "%.3f ms (min %.3f, max %.3f)" % (s["median"], s["min"], s["max"])
+    T, mst = C.c_uint32(0), _lib.MeshStats()
+    _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(cap),
+                                       C.c_int32(1), C.byref(T), C.byref(mst)))
+    T_in = T.value
+    Tc, dst = C.c_uint32(0), _lib.DecimateStats()
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(Tc), C.byref(dst)))
+    prm = meshing.register_params()
+    out_rows = []
+    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at %g m" % cell, dout, Tc.value)):
+        tri = _DeviceArray(src, 3 * n_in)
+        for md in maxes:
+            with rec.BuildDistanceScene(None, tri, md) as scene:
+                # ---- the scene's plain query of the same points at the bound
+                qp, qst = api.distance_params(md), _lib.DistanceStats()
+                qs, qph = [], []
+                for _ in range(args.reps + 1):
+                    qs.append(timed(lambda: _lib.check(L.smx_distscene_query(
+                        scene._h, None, C.byref(qp), C.c_void_p(tp.data_ptr()), C.c_uint32(P), C.c_void_p(dnear.ToCUDA().address),
+                        C.c_void_p(ddist.ToCUDA().address), None, C.c_int32(1), C.byref(qst))))[0])
+                    qph.append(scene.debug_timings()["query"])
+                # ---- the registration, with and without normals; the result stays on the device, so the call itself does not wait
+                rows = {}
+                for name, normals in (("with normals", tn), ("without normals", None)):
+                    whole, host, phs, first = [], [], [], None
+                    for _ in range(args.reps + 1):
+                        t1 = time.perf_counter()
+                        ms, _ = timed(lambda: scene.Register(None, tp, normals, None, prm, result_buffer=dres))
+                        whole.append(ms)
+                        host.append(1e3 * (time.perf_counter() - t1))
+                        phs.append(scene.debug_register_timings())
+                        got = dres.Download()[0].tobytes()
+                        first = got if first is None else first
+                        assert got == first, "two calls gave different bytes"
+                    res = api.register_result_dict(_lib.RegisterResult.from_buffer_copy(first[:C.sizeof(_lib.RegisterResult)]))
+                    its = scene.RegisterIterations()
+                    ph = {k: spread([q[k] for q in phs[1:]]) for k in ("call",) + REGISTER_PHASES}
+                    own = sum(ph[k]["median"] for k in ("move", "reduce", "solve"))
+                    rows[name] = {"call_ms": spread(whole[1:]), "phases_ms": ph, "status": int(res["status"]), "iterations_run": int(res["iterations_run"]),
+                                  "inliers": int(res["inliers"]), "points_used": int(res["points_used"]), "rms_residual": float(res["rms_residual"]),
+                                  "matched_last": float(its[-1]["sums"][30]) if its else 0.0, "own_kernels_ms": own,
+                                  "own_over_plain_query": own / max(float(np.median(qph[1:])), 1e-9)}
+                    say("%s, bound %g m, %d triangles, %s: call %s, by the library's events %s | last iteration: %s | move + reduce + solve %.3f ms = "
+                        "%.2f x the scene's plain query phase of the same points (%.3f ms; the whole plain query %s) | status %d after %d iterations, %d "
+                        "inliers of %d used (%d matched), rms %.2f mm" % (
+                            what, md, n_in, name, show(rows[name]["call_ms"]), show(ph["call"]), " | ".join("%s %s" % (k, show(ph[k])) for k in REGISTER_PHASES),
+                            own, rows[name]["own_over_plain_query"], float(np.median(qph[1:])), show(spread(qs[1:])), res["status"], res["iterations_run"],
+                            res["inliers"], res["points_used"], rows[name]["matched_last"], 1e3 * res["rms_residual"]))
+                out_rows.append({"input": what, "bound": md, "triangles_in": n_in, "points": P, "reps": args.reps, "plain_query_ms": spread(qs[1:]),
+                                 "plain_query_phase_ms": spread(qph[1:]), "plain_query_matched": int(qst.n_matched), "register": rows,
+                                 "cell_size_used": scene.stats["cell_size_used"]})
+    res = {"metric": "register_call_ms", "slots": n, "live": live, "triangles_in": T_in, "rows": out_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "register_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "register_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 SAMPLE_PHASES = ("weights", "scan", "draw")
 COMPARE_PHASES = ("a_to_b.sample", "a_to_b.distance", "a_to_b.sums", "b_to_a.sample", "b_to_a.distance", "b_to_a.sums")
 
@@ -1351,4 +1474,4 @@ def main():
 
 
 if __name__ == "__main__":
-    distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    register_main() if args.register else distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -7,7 +7,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh] [--mesh_every N [--mesh_check]] [--mesh_decimate METRES]
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
-                              [--mesh_eval METRES [--mesh_eval_frames N]] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
+                              [--mesh_eval METRES [--mesh_eval_frames N]] [--mesh_eval_register] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
                               [--mesh_compare_samples N [--mesh_compare_distance METRES]]
                               [--export_mesh_samples FILE.ply --mesh_samples N]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
@@ -32,6 +32,10 @@ fine mesh's vertices against the decimated one.  Without --synthetic and without
 --mesh_eval_frames N (with --mesh_eval, --synthetic and --mesh or --mesh_every) builds one distance scene (smx_distscene) of the
 final mesh and measures the surface points of each of the last N integrated frames against it: one line per frame under the
 head "scene points" and a total, whose figures are those of the --mesh_eval line when N covers every integrated frame.
+--mesh_eval_register (with --mesh_eval, --synthetic and --mesh or --mesh_every) splits that surface error into a rigid part and a
+surface part: the ground-truth points of each evaluated frame (the last --mesh_eval_frames N, or every integrated frame) are
+registered to one distance scene of the final mesh from the identity (smx_distscene_register); one line per frame with the
+status, the rotation and translation recovered (the drift) and the surface error before and after the alignment, and a total.
 --mesh_compare_samples N prints, for every stage of the chain that was asked for (cleaning, hole filling, decimation), the
 two-sided surface error between the mesh before and after it on N area-weighted samples per side (smx_recon_compare_meshes).
 --export_mesh_samples FILE.ply with --mesh_samples N writes N such samples of the final mesh with the face normals.
@@ -206,6 +210,9 @@ def parse_args(argv=None):
                     help="with --mesh_eval METRES --synthetic N --mesh: build one distance scene (smx_distscene) of the final mesh and "
                          "measure the noise-free surface points of each of the last N integrated frames against it: one line per "
                          "frame and a total")
+    ap.add_argument("--mesh_eval_register", action="store_true",
+                    help="with --mesh_eval METRES --synthetic N --mesh: register the ground-truth points of each evaluated frame to the "
+                         "final mesh from the identity (smx_distscene_register): the pose recovered and the surface error before and after")
     ap.add_argument("--mesh_eval_rays", action="store_true",
                     help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
                          "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
@@ -276,6 +283,8 @@ def parse_args(argv=None):
         ap.error("--mesh_eval_frames needs a frame count >= 0")
     if args.mesh_eval_frames and not (args.mesh_eval is not None and args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_frames needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
+    if args.mesh_eval_register and not (args.mesh_eval is not None and args.synthetic and (args.mesh or args.mesh_every > 0)):
+        ap.error("--mesh_eval_register needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_rays and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_rays needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_rays_frames < 0:
@@ -319,6 +328,29 @@ def merge_distance_stats(parts):
     out["histogram"] = [sum(int(p["histogram"][b]) for p in parts) for b in range(len(parts[0]["histogram"]))]
     out["max_dist2_bits"] = max(int(p["max_dist2_bits"]) for p in parts)
     return out
+
+
+def register_figures(result, before, after):
+    """What --mesh_eval_register prints of one frame: status, iterations, the angle (mrad) and length (mm) of the pose recovered,
+    mean and rms surface error (mm) before and after it (distance_summary dicts; 0 where nothing matched)."""
+    T = np.asarray(result["scene_T_points"], np.float64).reshape(3, 4)
+    s = 0.5 * np.linalg.norm([T[2, 1] - T[1, 2], T[0, 2] - T[2, 0], T[1, 0] - T[0, 1]])
+    angle = float(np.arctan2(s, 0.5 * (np.trace(T[:, :3]) - 1.0)))
+    mm = lambda d, k: 1e3 * (d[k] or 0.0)                                                        # noqa: E731
+    return dict(status=int(result["status"]), iterations=int(result["iterations_run"]), mrad=1e3 * angle, mm=1e3 * float(np.linalg.norm(T[:, 3])),
+                mean=(mm(before, "mean"), mm(after, "mean")), rms=(mm(before, "rms"), mm(after, "rms")))
+
+
+def format_register_line(f, fig):
+    return "registered frame %d: status %d after %d iterations, %.3f mrad and %.3f mm from the identity; surface error %.3f -> %.3f mm mean, %.3f -> %.3f mm rms" % (
+        f, fig["status"], fig["iterations"], fig["mrad"], fig["mm"], fig["mean"][0], fig["mean"][1], fig["rms"][0], fig["rms"][1])
+
+
+def format_register_total(figs):
+    ok = [g for g in figs if g["status"] <= 1]
+    mean = lambda v: float(np.mean(v)) if len(v) else 0.0                                         # noqa: E731
+    return "registered %d frames: %d solved, mean %.3f mrad and %.3f mm from the identity; surface error %.3f -> %.3f mm mean" % (
+        len(figs), len(ok), mean([g["mrad"] for g in ok]), mean([g["mm"] for g in ok]), mean([g["mean"][0] for g in ok]), mean([g["mean"][1] for g in ok]))
 
 
 def format_point_eval(summary, what, head="scene points"):
@@ -526,6 +558,22 @@ def main():
             print(format_point_eval(total, "%d frames" % len(frames)))
         print("scene points: one scene of %d triangles (%d bytes on the device) built in %.1f ms, %d frames queried in %.1f ms" % (
             triangles.shape[0], scene.device_bytes, 1e3 * (built - t1), len(frames), 1e3 * (time.time() - built)))
+    if args.mesh_eval_register:
+        from surfelmeshing_amd import meshing
+        half_ = args.outlier_filtering_frame_count // 2
+        last = n - half_ - 1
+        first = last - args.mesh_eval_frames + 1 if args.mesh_eval_frames else args.start_frame + half_
+        figs = []
+        with meshing.build_distance_scene(rec, triangles, args.mesh_eval) as scene:
+            for f in range(max(first, args.start_frame + half_), last + 1):
+                pts = np.ascontiguousarray(s.surface_points(f, 8), np.float32)
+                res = meshing.register_points(scene, pts)
+                T = res["scene_T_points"].astype(np.float64)
+                moved = np.ascontiguousarray(pts.astype(np.float64) @ T[:, :3].T + T[:, 3], np.float32)
+                summaries = [meshing.distance_summary(*meshing.mesh_distance(None, None, p, args.mesh_eval, scene=scene)[1:]) for p in (pts, moved)]
+                figs.append(register_figures(res, *summaries))
+                print(format_register_line(f, figs[-1]))
+        print(format_register_total(figs))
     if args.mesh_eval_rays:
         from surfelmeshing_amd import meshing
         half_ = args.outlier_filtering_frame_count // 2
