@@ -1561,8 +1561,8 @@ int smx_distscene_debug_timings(smx_distscene sc, float* out_ms, int32_t capacit
  * SMX_ERR_INVALID_ARGUMENT, nothing launched and nothing written: a scene without a build, no level with iterations, more than
  * 32 iterations in a level, a stride outside 1 .. 65536, a level's distance that is neither 0 nor in 1e-3f .. the scene's
  * bound, a T_init that is not finite, non-positive gates, points == NULL with n_points > 0, n_points > 2^28.
- * Not done: robust (Huber) weights; rejecting matches on the mesh boundary; scale or non-rigid alignment; mesh-to-mesh in one
- * call (compose smx_recon_sample_mesh with this); an incremental scene. */
+ * Not done: scale or non-rigid alignment; an incremental scene.  (Robust weights, rejecting matches on the mesh boundary and
+ * mesh-to-mesh in one call: smx_distscene_register_robust and smx_recon_register_mesh below) */
 typedef struct {             /* smx_register_params_default() fills the defaults */
   int32_t level_stride[3];          /* sample j of a level is point j * stride, j < ceil(n / stride); 1 .. 65536 */
   int32_t level_iterations[3];      /* 0 = level unused; at most 32 */
@@ -1602,6 +1602,85 @@ int smx_distscene_debug_register_iterations(smx_distscene sc, smx_stream s, smx_
  * SMX_REGISTER_PHASES. */
 #define SMX_REGISTER_PHASES 5
 int smx_distscene_debug_register_timings(smx_distscene sc, float* out_ms, int32_t capacity);
+
+/* ---- the rim of a triangle array: which corners and edges of a triangle lie on the boundary of the surface (not in the
+ * reference) ----
+ * A function of the map as it stands and of `triangles` (uint32 [n_in][3], slot indices, in any order), made of integers only.
+ * R is the triangle set of smx_recon_mesh_distance step 1: live corners, three different ones, within SMX_DIST_MAX_COORD; the
+ * counts n_not_live, n_repeated and n_out_of_range are that step's.  c(u, v) is the number of triangles of R that have the
+ * undirected edge {u, v}, whatever their winding; a triangle given twice counts twice.  An edge is a RIM EDGE iff c == 1, and a
+ * slot is a RIM VERTEX iff it ends a rim edge.  rim[t] for t in R has bit k set for region k of that call's step 3, in its
+ * order: bit 0 corner A is a rim vertex, bit 1 corner B, bit 2 edge AB is a rim edge, bit 3 corner C, bit 4 edge AC, bit 5
+ * edge BC.  So "the closest point of that call lies on the rim" is (rim[t] >> region) & 1 with region 0 .. 5 as the branches
+ * of step 3 come (A, B, AB, C, AC, BC), and the interior branch never is.  rim[t] = 0 outside R.  A corner's bit may be set
+ * while none of the triangle's own edges is a rim edge: the rim edge belongs to a neighbour.
+ * smx_rim_stats: the four counts of step 1; n_edges = the pairs with c >= 1; n_rim_edges (c == 1; on an array none of whose
+ * triangles is repeated or out of range this is smx_fill_stats.n_boundary_edges); n_nonmanifold_edges (c >= 3; not that
+ * call's word, which also counts two triangles wound alike); n_rim_vertices; n_rim_triangles = the bytes that are not 0.
+ * Refused like smx_recon_mesh_distance refuses the array, nothing written: an index >= n, n_in > 2^28, triangles or rim NULL
+ * with n_in > 0; also rim overlapping triangles.  n_in == 0 is valid.  on_device says where triangles and rim live.  Ordered
+ * after everything enqueued on the object, synchronous; two calls give the same bytes.  Changes no map state.  The workspace
+ * (the edge table of smx_recon_fill_holes, one bit per slot, the bytes) belongs to the object, grows on demand, is freed with
+ * the object, is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation; every allocation comes before
+ * the first write to an output.
+ * smx_recon_build_distscene_rim is BY DEFINITION smx_recon_build_distscene followed by smx_recon_mesh_rim of the same array; the
+ * bytes are kept with the scene, n_in of them, indexed like `nearest`, a snapshot like the rest of the scene (they survive what
+ * the scene survives).  If either half fails the scene is left empty.  smx_distscene_stats keeps its meaning; device_bytes
+ * includes the rim bytes.  A scene built by smx_recon_build_distscene has no rim.
+ * Not done: rim flags on the samples' side; an incremental rim. */
+typedef struct {
+  uint32_t n_in, n_not_live, n_repeated, n_out_of_range;   /* as smx_distance_stats */
+  uint32_t n_edges, n_rim_edges, n_nonmanifold_edges;
+  uint32_t n_rim_vertices, n_rim_triangles;
+} smx_rim_stats;
+int smx_recon_mesh_rim(smx_recon r, smx_stream s, const uint32_t* triangles, uint32_t n_in, int32_t on_device,
+                       uint8_t* rim /* [n_in] */, smx_rim_stats* stats /* may be NULL */);
+int smx_recon_build_distscene_rim(smx_recon r, smx_stream s, smx_distscene sc, const smx_distscene_params* p,
+                                  const uint32_t* triangles, uint32_t n_in, int32_t on_device,
+                                  smx_distscene_stats* stats /* may be NULL */, smx_rim_stats* rim_stats /* may be NULL */);
+
+/* ---- registration of partly overlapping surfaces: rim rejection and robust weights ----
+ * smx_distscene_register_robust is smx_distscene_register with two more decisions per sample.  Everything of that call holds:
+ * the move, the association by the scene's own query, the sum order, the solve, the status rules, every iteration enqueued back
+ * to back with no host read until the end.  Per sample the order of decisions is: BAD -> not matched -> collinear winner -> rim
+ * -> normal gate -> weight -> inlier.
+ *   Rim.     region = the branch of smx_recon_mesh_distance step 3 that dist_closest takes for p' on the winner's first-record
+ *            corners (the computation the query's Q came from).  With reject_rim a sample with (rim[t] >> region) & 1 counts as
+ *            matched, is no inlier, and adds 1 to sum [31].
+ *   Weights. float32, evaluated as written; a = fabsf(r), c = level_scale of the level; c == 0 or kernel 0: no weights.
+ *            Huber: a <= c leaves the row unchanged; otherwise s = sqrtf(c / a), the row is (s J[k], s r) with e = r -- so [27]
+ *            stays the geometric sum of r * r -- the sample stays an inlier and adds 1 to sum [32].
+ *            Tukey: !(a < c): the sample is matched, is no inlier, and adds 1 to sum [32]; otherwise u = a / c, s = 1.0f - u * u
+ *            (the weight is s * s), the row is (s J[k], s r) with e = r.
+ *   Sums.    The 31 sums keep their meaning and their order; [31] and [32] are the two counts, carried in the 33-sum slabs of
+ *            smx_recon_track_rgbd.  smx_distscene_debug_register_iterations serves this call's records too;
+ *            smx_distscene_debug_register_robust_counts returns [31] and [32] of every recorded iteration.
+ * With kernel 0 and reject_rim 0 the call IS smx_distscene_register: the same kernels, the same bytes in the result and in
+ * every iteration record.  Refused (SMX_ERR_INVALID_ARGUMENT, nothing launched): what that call refuses; kernel outside 0 .. 2;
+ * with kernel != 0 a level_scale of a used level that is neither 0 nor finite in 1e-6f .. 16.0f; reject_rim not 0 / 1;
+ * reject_rim on a scene without a rim.
+ * smx_recon_register_mesh is BY DEFINITION smx_recon_sample_mesh(triangles, n_samples, seed) on r's map as it stands with its
+ * normals, then smx_distscene_register_robust of those points and normals.  The samples never leave the device.  r and sc on
+ * different devices: refused.  A refusal by either half is the call's refusal.  Synchronous.  on_device says where triangles
+ * lives.
+ * Not done: rim flags on the samples' side; scale or non-rigid alignment; an initialisation-free registration; an incremental
+ * scene; other kernels (Cauchy, Geman-McClure). */
+typedef struct {             /* smx_register_robust_params_default() fills the defaults: 0, {0, 0, 0}, 0 */
+  int32_t kernel;            /* 0 none, 1 Huber, 2 Tukey */
+  float   level_scale[3];    /* c of the level in metres; 0 = no weights on this level; else finite, 1e-6f .. 16.0f */
+  int32_t reject_rim;        /* 1: a match whose closest point lies on the rim is no inlier; needs a scene with a rim */
+} smx_register_robust_params;
+int smx_register_robust_params_default(smx_register_robust_params* out);
+int smx_distscene_register_robust(smx_distscene sc, smx_stream s, const smx_register_params* p,
+                                  const smx_register_robust_params* rp, const float* points, const float* normals,
+                                  uint32_t n_points, int32_t on_device, const float T_init[12],
+                                  smx_register_result* result, int32_t result_on_device);
+int smx_distscene_debug_register_robust_counts(smx_distscene sc, smx_stream s, uint32_t (*counts)[2], int32_t capacity,
+                                               int32_t* count);
+int smx_recon_register_mesh(smx_recon r, smx_stream s, smx_distscene sc, const uint32_t* triangles, uint32_t n_in,
+                            int32_t on_device, uint32_t n_samples, uint32_t seed, const smx_register_params* p,
+                            const smx_register_robust_params* rp, const float T_init[12],
+                            smx_register_result* result, int32_t result_on_device);
 
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----

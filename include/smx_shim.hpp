@@ -525,13 +525,24 @@ class DistanceScene {
     SMX_SHIM_CHECK(smx_distscene_register(handle_, stream, &params, n_points ? points.data() : nullptr,
                                           normals && n_points ? normals->data() : nullptr, n_points, 0, T_init, result, 0));
   }
+  // Register with Huber or Tukey weights on the rows and / or rejection of the matches on the rim of the scene's mesh
+  // (smx_distscene_register_robust in smx.h); robust.reject_rim needs a scene built by BuildDistanceSceneRim.
+  void RegisterRobust(cudaStream_t stream, const std::vector<float>& points, const std::vector<float>* normals,
+                      const smx_register_params& params, const smx_register_robust_params& robust, const float T_init[12],
+                      smx_register_result* result) {
+    const u32 n_points = (u32)(points.size() / 3);
+    SMX_SHIM_CHECK(smx_distscene_register_robust(handle_, stream, &params, &robust, n_points ? points.data() : nullptr,
+                                                 normals && n_points ? normals->data() : nullptr, n_points, 0, T_init, result, 0));
+  }
   const smx_distscene_stats& stats() const { return stats_; }
+  const smx_rim_stats& rim_stats() const { return rim_stats_; }      // (of a build by BuildDistanceSceneRim)
   smx_distscene handle() const { return handle_; }
 
  private:
   friend class CUDASurfelReconstruction;
   smx_distscene handle_ = nullptr;
   smx_distscene_stats stats_{};
+  smx_rim_stats rim_stats_{};
 };
 
 class CUDASurfelReconstruction {
@@ -752,6 +763,14 @@ class CUDASurfelReconstruction {
                                          n_samples ? points->data() : nullptr, n_samples ? tri->data() : nullptr,
                                          bary && n_samples ? bary->data() : nullptr, normals && n_samples ? normals->data() : nullptr, 0, stats));
   }
+  // Not in the reference: per triangle one byte that says which of its corners and edges lie on the boundary of the surface
+  // the array shows, bit k for region k of MeshDistance's closest point (smx_recon_mesh_rim in smx.h); stats may be null.
+  // Synchronous.
+  void MeshRim(cudaStream_t stream, const std::vector<u32>& triangles, std::vector<uint8_t>* rim, smx_rim_stats* stats = nullptr) {
+    const u32 n_in = (u32)(triangles.size() / 3);
+    rim->resize(n_in);
+    SMX_SHIM_CHECK(smx_recon_mesh_rim(handle_, stream, n_in ? triangles.data() : nullptr, n_in, 0, n_in ? rim->data() : nullptr, stats));
+  }
   // Not in the reference: both one-sided surface distances between two triangle arrays over the map, on params.n_samples
   // samples per side that never leave the device (smx_recon_compare_meshes in smx.h).  Synchronous.
   void CompareMeshes(cudaStream_t stream, const std::vector<u32>& triangles_a, const std::vector<u32>& triangles_b,
@@ -796,6 +815,26 @@ class CUDASurfelReconstruction {
     p.cell_size = cell_size;
     const u32 n_in = (u32)(triangles.size() / 3);
     SMX_SHIM_CHECK(smx_recon_build_distscene(handle_, stream, scene->handle_, &p, n_in ? triangles.data() : nullptr, n_in, 0, &scene->stats_));
+  }
+  // BuildDistanceScene that also keeps MeshRim's bytes of the array with the scene (smx_recon_build_distscene_rim in smx.h).
+  void BuildDistanceSceneRim(cudaStream_t stream, const std::vector<u32>& triangles, DistanceScene* scene, float max_distance,
+                             float cell_size = 0.0f) {
+    smx_distscene_params p;
+    SMX_SHIM_CHECK(smx_distscene_params_default(&p));
+    p.max_distance = max_distance;
+    p.cell_size = cell_size;
+    const u32 n_in = (u32)(triangles.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_build_distscene_rim(handle_, stream, scene->handle_, &p, n_in ? triangles.data() : nullptr, n_in, 0, &scene->stats_,
+                                                 &scene->rim_stats_));
+  }
+  // Not in the reference: mesh to mesh in one call (smx_recon_register_mesh in smx.h): n_samples points with their normals drawn
+  // on `triangles` over the map, registered to `scene` as DistanceScene::RegisterRobust does.  Synchronous.
+  void RegisterMesh(cudaStream_t stream, const DistanceScene& scene, const std::vector<u32>& triangles, u32 n_samples, u32 seed,
+                    const smx_register_params& params, const smx_register_robust_params& robust, const float T_init[12],
+                    smx_register_result* result) {
+    const u32 n_in = (u32)(triangles.size() / 3);
+    SMX_SHIM_CHECK(smx_recon_register_mesh(handle_, stream, scene.handle_, n_in ? triangles.data() : nullptr, n_in, 0, n_samples, seed, &params,
+                                           &robust, T_init, result, 0));
   }
   // Not in the reference: n_samples points drawn on `triangles` over the map as it stands, measured against `scene` within
   // max_distance (smx_recon_compare_to_distscene in smx.h): one side of CompareMeshes without a rebuild of the other mesh's index.

@@ -235,6 +235,12 @@ class DistanceStats(C.Structure):
                 [(n, C.c_uint32) for n in ("n_wide", "n_entries", "n_cells")] + [("cell_size_used", C.c_float)])
 
 
+class RimStats(C.Structure):
+    """smx_rim_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_edges", "n_rim_edges", "n_nonmanifold_edges",
+                                          "n_rim_vertices", "n_rim_triangles")]
+
+
 class SampleStats(C.Structure):
     """smx_sample_stats"""
     _fields_ = ([(n, C.c_uint32) for n in ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_zero_weight", "n_samples", "n_none",
@@ -351,6 +357,15 @@ class RegisterParams(C.Structure):
         return p
 
 
+class RegisterRobustParams(C.Structure):
+    """smx_register_robust_params: the weight kernel (0 none, 1 Huber, 2 Tukey), its scale per level in metres (0 = no weights on
+    that level) and whether a match whose closest point lies on the rim of the scene's mesh is rejected."""
+    _fields_ = [("kernel", C.c_int32), ("level_scale", C.c_float * 3), ("reject_rim", C.c_int32)]
+
+
+REGISTER_KERNELS = {"none": 0, "huber": 1, "tukey": 2}
+
+
 class RegisterResult(C.Structure):
     """smx_register_result"""
     _fields_ = [("scene_T_points", C.c_float * 12), ("status", C.c_int32), ("iterations_run", C.c_int32),
@@ -449,6 +464,8 @@ EXPORTS = [
     "smx_components_params_default", "smx_recon_mesh_components", "smx_recon_debug_components_timings",
     "smx_fill_params_default", "smx_recon_fill_holes", "smx_recon_debug_fill_timings",
     "smx_distance_params_default", "smx_recon_mesh_distance", "smx_recon_debug_distance_timings",
+    "smx_recon_mesh_rim", "smx_recon_build_distscene_rim", "smx_register_robust_params_default", "smx_distscene_register_robust",
+    "smx_distscene_debug_register_robust_counts", "smx_recon_register_mesh",
     "smx_recon_sample_mesh", "smx_recon_debug_sample_timings", "smx_recon_compare_meshes", "smx_recon_debug_compare_timings",
     "smx_raycast_params_default", "smx_recon_raycast_mesh", "smx_recon_debug_raycast_timings",
     "smx_rayscene_create", "smx_rayscene_destroy", "smx_rayscene_params_default", "smx_recon_build_rayscene", "smx_rayscene_cast",

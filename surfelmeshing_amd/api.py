@@ -26,11 +26,11 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    COMPONENTS_PHASES, ComponentsParams, ComponentsStats,
                    FILL_MAX_HOLE_EDGES, FILL_PHASES, FillParams, FillStats,
                    DIST_BINS, DIST_PHASES, DistanceParams, DistanceStats,
-                   COMPARE_PHASES, SAMPLE_MAX, SAMPLE_PHASES, CompareParams, CompareStats, SampleStats,
+                   COMPARE_PHASES, SAMPLE_MAX, SAMPLE_PHASES, CompareParams, CompareStats, SampleStats, RimStats,
                    RAY_MAX_T, RAY_PHASES, RaycastParams, RaycastStats,
                    RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
                    DISTSCENE_PHASES, CompareSide, DistSceneParams, DistSceneStats,
-                   REGISTER_MAX_POINTS, REGISTER_MAX_STRIDE, REGISTER_PHASES, RegisterIteration, RegisterParams, RegisterResult,
+                   REGISTER_MAX_POINTS, REGISTER_MAX_STRIDE, REGISTER_PHASES, RegisterIteration, RegisterParams, RegisterResult, RegisterRobustParams, REGISTER_KERNELS,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -306,6 +306,30 @@ def compare_side_dict(side, max_distance=None):
                 sum_sq_hi=int(side.sum_sq_hi))
 
 
+def register_robust_params(kernel="none", scale=0.0, reject_rim=False):
+    """The robust part of a registration as smx_register_robust_params; ValueError on what the library would refuse, before
+    anything is launched.  kernel: "none", "huber" or "tukey" (or 0, 1, 2); scale: the kernel's c in metres, one value for all
+    levels or three (0 = no weights on that level, else 1e-6 .. 16); reject_rim: reject matches on the rim of the scene's mesh."""
+    if isinstance(kernel, str):
+        if kernel not in REGISTER_KERNELS:
+            raise ValueError("kernel must be one of %s" % ", ".join(REGISTER_KERNELS))
+        kernel = REGISTER_KERNELS[kernel]
+    if isinstance(kernel, bool) or not isinstance(kernel, (int, np.integer)) or not 0 <= int(kernel) <= 2:
+        raise ValueError("kernel must be 0 (none), 1 (Huber) or 2 (Tukey)")
+    if not isinstance(reject_rim, (bool, np.bool_)) and reject_rim not in (0, 1):
+        raise ValueError("reject_rim must be False or True")
+    scales = [float(v) for v in (np.asarray(scale, np.float64).reshape(-1).tolist())]
+    if len(scales) == 1:
+        scales = scales * 3
+    if len(scales) != 3:
+        raise ValueError("scale must be one value or three, one per level")
+    for c in scales:
+        c32 = float(np.float32(c))
+        if not (c32 == 0.0 or (np.isfinite(c32) and np.float32(1e-6) <= np.float32(c) <= np.float32(16.0))):
+            raise ValueError("a scale must be 0 or finite in 1e-6 .. 16 metres")
+    return RegisterRobustParams(int(kernel), (C.c_float * 3)(*scales), 1 if reject_rim else 0)
+
+
 class DistanceScene:
     """Not in the reference: a snapshot of a triangle array over the map with the search structure of MeshDistance
     (smx_distscene), built once by CUDASurfelReconstruction.BuildDistanceScene for one bound on max_distance and queried many
@@ -317,6 +341,8 @@ class DistanceScene:
     def __init__(self, device_id=-1):
         self._h = C.c_void_p()
         self.stats = None
+        self.has_rim = False           # the last build kept the rim bytes of its triangles (BuildDistanceScene(rim=True))
+        self.rim_stats = None
         _lib.check(_lib.load().smx_distscene_create(C.c_int32(device_id), C.byref(self._h)))
 
     def close(self):
@@ -382,7 +408,7 @@ class DistanceScene:
         stats["max_distance"] = float(p.max_distance)      # (what the histogram's bins are fractions of)
         return (nearest, distance, closest, stats) if return_closest else (nearest, distance, stats)
 
-    def Register(self, stream, points, normals=None, T_init=None, params=None, result_buffer=None):
+    def Register(self, stream, points, normals=None, T_init=None, params=None, result_buffer=None, robust=None):
         """Point-to-plane ICP of `points` ([P,3] float32, in their own frame) against the scene's triangles
         (smx_distscene_register): every iteration moves the samples by the pose, asks the scene's own query for their closest
         triangles and solves for a left twist; all iterations are enqueued back to back on `stream`.  normals ([P,3], optional)
@@ -391,13 +417,21 @@ class DistanceScene:
         device tensors.  Without result_buffer the call is synchronous and returns a dict: scene_T_points [3,4] float32,
         status, iterations_run, inliers, points_used, rms_residual, last_update_rotation, last_update_translation, information
         [6,6].  With result_buffer (a CUDABuffer of at least ctypes.sizeof(RegisterResult) bytes in one row, or a device
-        address) the smx_register_result stays on the device, and with device points nothing waits for the host."""
+        address) the smx_register_result stays on the device, and with device points nothing waits for the host.
+        robust: a RegisterRobustParams (register_robust_params(...)) -- Huber or Tukey weights on the rows and / or rejection of
+        the matches whose closest point lies on the rim of the scene's mesh, which needs a scene built with rim=True
+        (smx_distscene_register_robust); None is the plain call."""
         if not getattr(self, "_h", None):
             raise ValueError("the scene is closed")
         if not getattr(self, "stats", None):
             raise ValueError("the scene holds no build")
         p = params if params is not None else RegisterParams.defaults()
         register_check_params(p, self.stats["max_distance"])
+        if robust is not None:
+            if not isinstance(robust, RegisterRobustParams):
+                raise ValueError("robust must be a RegisterRobustParams (register_robust_params(...))")
+            if robust.reject_rim and not self.has_rim:
+                raise ValueError("reject_rim needs a scene built with rim=True")
         T = np.ascontiguousarray(np.asarray(np.eye(3, 4) if T_init is None else T_init, np.float32).reshape(-1))
         if T.size != 12 or not np.all(np.isfinite(T)):
             raise ValueError("T_init must hold 12 finite values")
@@ -435,11 +469,24 @@ class DistanceScene:
         res = RegisterResult()
         if on_device:
             out = C.c_void_p(result_buffer.ToCUDA().address if isinstance(result_buffer, CUDABuffer) else int(result_buffer))
-        _lib.check(_lib.load().smx_distscene_register(self._h, _sv(stream), C.byref(p), C.c_void_p(pin), C.c_void_p(nin), C.c_uint32(n_points),
-                                                      C.c_int32(1 if dev else 0), T.ctypes.data_as(C.c_void_p), out if on_device else C.byref(res),
-                                                      C.c_int32(1 if on_device else 0)))
+        tail = (C.c_void_p(pin), C.c_void_p(nin), C.c_uint32(n_points), C.c_int32(1 if dev else 0), T.ctypes.data_as(C.c_void_p),
+                out if on_device else C.byref(res), C.c_int32(1 if on_device else 0))
+        if robust is None:
+            _lib.check(_lib.load().smx_distscene_register(self._h, _sv(stream), C.byref(p), *tail))
+        else:
+            _lib.check(_lib.load().smx_distscene_register_robust(self._h, _sv(stream), C.byref(p), C.byref(robust), *tail))
         del keep
         return None if on_device else register_result_dict(res)
+
+    def RegisterRobustCounts(self, stream=None):
+        """Per iteration of the scene's last Register call the two counts of the robust row, [iterations, 2] uint32
+        (smx_distscene_debug_register_robust_counts): the matches rejected on the rim (sum [31]) and the samples Huber
+        down-weighted or Tukey rejected (sum [32]).  Zeros after a plain call; like RegisterIterations, empty once a later
+        Query or build on the scene has waited for the registration."""
+        counts = (C.c_uint32 * 2 * 96)()
+        n = C.c_int32(0)
+        _lib.check(_lib.load().smx_distscene_debug_register_robust_counts(self._h, _sv(stream), counts, C.c_int32(96), C.byref(n)))
+        return np.array([[row[0], row[1]] for row in counts[:n.value]], np.uint32).reshape(-1, 2)
 
     def RegisterIterations(self, stream=None):
         """One dict per iteration of the scene's last Register call (smx_distscene_debug_register_iterations): level, stride,
@@ -1351,6 +1398,34 @@ class CUDASurfelReconstruction:
         _lib.check(_lib.load().smx_recon_debug_distance_timings(self._h, out, C.c_int32(DIST_PHASES)))
         return dict(zip(("mark", "index", "query", "stats"), [float(v) for v in out]))
 
+    def MeshRim(self, stream, triangles):
+        """Not in the reference: per triangle of `triangles` ([T,3] slot indices in any order) one byte that says which of its
+        corners and edges lie on the boundary of the surface the array shows (smx_recon_mesh_rim).  An edge is a rim edge iff
+        exactly one triangle of the array has it, a slot a rim vertex iff it ends one; bit k of the byte stands for region k of
+        MeshDistance's closest point (A, B, AB, C, AC, BC), so (rim[t] >> region) & 1 says whether that point lies on the rim.
+        Integers only.  Synchronous.  `triangles` is a numpy array or a contiguous device tensor (uint32 / int32); the bytes
+        then are a device tensor too.  Returns (rim [T] uint8, the dict of smx_rim_stats)."""
+        st = RimStats()
+        dev = _device_address(triangles) is not None
+        if dev:
+            import torch
+            if not (triangles.is_contiguous() and triangles.element_size() == 4 and triangles.numel() % 3 == 0):
+                raise ValueError("a device tensor must be contiguous: [T,3] 32-bit integers")
+            n_in = triangles.numel() // 3
+            rim = torch.empty(n_in, dtype=torch.uint8, device=triangles.device)
+            tin, out = (triangles.data_ptr(), rim.data_ptr()) if n_in else (None, None)
+            torch.cuda.current_stream(triangles.device).synchronize()      # (the tensor's producers; the call runs on `stream`)
+        else:
+            t = np.ascontiguousarray(triangles, np.uint32)
+            if t.size % 3:
+                raise ValueError("triangles must hold three values per row")
+            n_in = t.size // 3
+            rim = np.zeros(n_in, np.uint8)
+            tin, out = (t.ctypes.data, rim.ctypes.data) if n_in else (None, None)
+        _lib.check(_lib.load().smx_recon_mesh_rim(self._h, _sv(stream), C.c_void_p(tin), C.c_uint32(n_in), C.c_int32(1 if dev else 0),
+                                                  C.c_void_p(out), C.byref(st)))
+        return rim, {n: int(getattr(st, n)) for n, _ in RimStats._fields_}
+
     def SampleMesh(self, stream, triangles, n_samples, seed=0, return_bary=False, return_normals=False):
         """Not in the reference: n_samples points on `triangles` ([T,3] slot indices in any order) over the map's smooth
         positions, drawn in proportion to area, one per stratum of the total area, in the order of the triangles
@@ -1505,26 +1580,61 @@ class CUDASurfelReconstruction:
         sc.stats = rayscene_stats_dict(st)
         return sc
 
-    def BuildDistanceScene(self, stream, triangles, max_distance, cell_size=0.0, scene=None):
+    def BuildDistanceScene(self, stream, triangles, max_distance, cell_size=0.0, scene=None, rim=False):
         """Not in the reference: a DistanceScene of `triangles` ([T,3] slot indices, a numpy array or a contiguous 32-bit device
         tensor) over the map as it stands (smx_recon_build_distscene).  max_distance is the bound on what a query may ask for;
         cell_size as in MeshDistance.  Synchronous.  scene: an existing DistanceScene to rebuild in place.  A refused build
-        leaves the scene empty (and closes a scene made here)."""
+        leaves the scene empty (and closes a scene made here).  rim=True also keeps MeshRim's bytes of the array with the scene
+        (smx_recon_build_distscene_rim): .has_rim, .rim_stats; Register(robust=...) can then reject matches on the rim."""
         p = distscene_params(max_distance, cell_size)
         n_in, tin, dev, _keep = _triangles_arg(triangles)
         own = scene is None
         sc = DistanceScene() if own else scene
-        st = DistSceneStats()
+        st, rst = DistSceneStats(), RimStats()
+        sc.has_rim, sc.rim_stats = False, None
         try:
-            _lib.check(_lib.load().smx_recon_build_distscene(self._h, _sv(stream), sc._h, C.byref(p), C.c_void_p(tin), C.c_uint32(n_in),
-                                                             C.c_int32(1 if dev else 0), C.byref(st)))
+            if rim:
+                _lib.check(_lib.load().smx_recon_build_distscene_rim(self._h, _sv(stream), sc._h, C.byref(p), C.c_void_p(tin), C.c_uint32(n_in),
+                                                                     C.c_int32(1 if dev else 0), C.byref(st), C.byref(rst)))
+            else:
+                _lib.check(_lib.load().smx_recon_build_distscene(self._h, _sv(stream), sc._h, C.byref(p), C.c_void_p(tin), C.c_uint32(n_in),
+                                                                 C.c_int32(1 if dev else 0), C.byref(st)))
         except Exception:
             sc.stats = None
             if own:
                 sc.close()
             raise
         sc.stats = distscene_stats_dict(st)
+        if rim:
+            sc.has_rim, sc.rim_stats = True, {n: int(getattr(rst, n)) for n, _ in RimStats._fields_}
         return sc
+
+    def RegisterMesh(self, stream, scene, triangles, n_samples, seed=0, T_init=None, params=None, robust=None):
+        """Not in the reference: mesh to mesh in one call (smx_recon_register_mesh): n_samples points with their normals drawn
+        on `triangles` over this object's map as SampleMesh draws them, registered to `scene` as DistanceScene.Register does
+        with robust (None: no weights, no rim rejection).  The samples never leave the device.  Synchronous.  Returns
+        Register's dict."""
+        if not getattr(scene, "_h", None):
+            raise ValueError("the scene is closed")
+        if not getattr(scene, "stats", None):
+            raise ValueError("the scene holds no build")
+        n, sd = sample_params(n_samples, seed)
+        p = params if params is not None else RegisterParams.defaults()
+        register_check_params(p, scene.stats["max_distance"])
+        rp = robust if robust is not None else register_robust_params()
+        if not isinstance(rp, RegisterRobustParams):
+            raise ValueError("robust must be a RegisterRobustParams (register_robust_params(...))")
+        if rp.reject_rim and not scene.has_rim:
+            raise ValueError("reject_rim needs a scene built with rim=True")
+        T = np.ascontiguousarray(np.asarray(np.eye(3, 4) if T_init is None else T_init, np.float32).reshape(-1))
+        if T.size != 12 or not np.all(np.isfinite(T)):
+            raise ValueError("T_init must hold 12 finite values")
+        n_in, tin, dev, _keep = _triangles_arg(triangles)
+        res = RegisterResult()
+        _lib.check(_lib.load().smx_recon_register_mesh(self._h, _sv(stream), scene._h, C.c_void_p(tin), C.c_uint32(n_in), C.c_int32(1 if dev else 0),
+                                                       C.c_uint32(n), C.c_uint32(sd), C.byref(p), C.byref(rp), T.ctypes.data_as(C.c_void_p),
+                                                       C.byref(res), C.c_int32(0)))
+        return register_result_dict(res)
 
     def CompareToDistanceScene(self, stream, triangles, scene, max_distance, n_samples, seed=0):
         """Not in the reference: n_samples points drawn on `triangles` over the map as it stands as SampleMesh draws them,

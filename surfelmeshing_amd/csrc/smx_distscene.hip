@@ -5,6 +5,7 @@
 //   build:  tg_enqueue_mark and tg_enqueue_index of smx_trigrid.hip as smx_recon_mesh_distance calls them, writing
 //           the records and the cell table into the scene's own buffers -> k_dscene_first (a lane per record, cell records and
 //           wide records alike: one integer minimum into first_rec[t])
+//   rim:    smx_recon_build_distscene_rim = the build, then rim_run of smx_rim.hip on the same array, its bytes copied into the scene
 //   query:  dist_scene_query of smx_distance.hip (k_dist_point_keys -> the sort -> k_dscene_query -> k_dist_stats) on the index
 //           the scene keeps
 //
@@ -37,7 +38,8 @@ k_dscene_first(const uint32_t* __restrict__ sorted_t, uint32_t n_entries, const 
 // empty: the build's buffers go; the query workspace and the counters stay for the next build
 void dscene_clear(smx_distscene_s* sc) {
   sc->built = false;
-  sc->recs.reset(); sc->wide_recs.reset(); sc->table.reset(); sc->first_rec.reset();
+  sc->recs.reset(); sc->wide_recs.reset(); sc->table.reset(); sc->first_rec.reset(); sc->rim.reset();
+  sc->has_rim = false;
   sc->mask = sc->n_entries = sc->n_wide = sc->n_in = 0;
   sc->max_distance = 0.0f;
 }
@@ -154,6 +156,39 @@ int smx_recon_build_distscene(smx_recon r, smx_stream s, smx_distscene sc, const
     dscene_clear(sc);
   }
   return rc;
+}
+
+// By definition smx_recon_build_distscene followed by smx_recon_mesh_rim of the same array, the bytes kept with the scene.
+int smx_recon_build_distscene_rim(smx_recon r, smx_stream s, smx_distscene sc, const smx_distscene_params* p, const uint32_t* triangles,
+                                  uint32_t n_in, int32_t on_device, smx_distscene_stats* stats, smx_rim_stats* rim_stats) {
+  SMX_CALL(smx_recon_build_distscene(r, s, sc, p, triangles, n_in, on_device, stats));
+  SMX_ON_DEVICE(sc->device);
+  hipStream_t st = (hipStream_t)s;
+  auto rim = [&]() -> int {
+    uint32_t n = 0;
+    SMX_CALL(read_surfel_count(r, st, &n));
+    SMX_CALL(sc->rim.alloc(n_in, false));
+    smx_rim_stats out;
+    memset(&out, 0, sizeof(out));
+    const uint8_t* d_rim = nullptr;
+    SMX_CALL(rim_run(r, st, triangles, n_in, on_device != 0, n, &d_rim, &out));
+    if (n_in > 0) {
+      SMX_HIP(hipMemcpyAsync(sc->rim.get(), d_rim, n_in, hipMemcpyDeviceToDevice, st));
+      SMX_HIP(hipStreamSynchronize(st));
+    }
+    if (rim_stats) *rim_stats = out;
+    return SMX_OK;
+  };
+  const int rc = rim();
+  if (rc != SMX_OK) {                    // (if either half fails the scene is left empty)
+    (void)hipStreamSynchronize(st);
+    dscene_clear(sc);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return rc;
+  }
+  sc->has_rim = true;
+  if (stats) stats->device_bytes += dscene_bytes(sc->rim);
+  return SMX_OK;
 }
 
 int smx_distscene_query(smx_distscene sc, smx_stream s, const smx_distance_params* p, const float* points, uint32_t n_points, uint32_t* nearest,

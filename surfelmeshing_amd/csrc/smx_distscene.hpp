@@ -47,7 +47,9 @@ struct RegisterWork {
   DevBuf<uint32_t> nearest;                // [m] the query's outputs
   DevBuf<float> distance, closest;         // [m], [m][3]
   DevBuf<double> slabs;                    // [kTrackMaxSlabs][kTrackSlabStride] the reduce kernel's per-workgroup sums
+  DevBuf<uint32_t> robust_counts;          // [kTrackMaxSlabs][2] the robust reduce kernel's two counts per workgroup; its first call allocates it
   DevBuf<RegDev> state;                    // [1]
+  bool last_robust = false;                // the last call ran the robust reduce kernel
   StreamMark mark;
   PhaseStamps<1> whole;                    // the last call
   PhaseStamps<4> last;                     // move, query, reduce, solve of its last iteration
@@ -68,6 +70,8 @@ struct smx_distscene_s {
   smx::DevBuf<float> recs, wide_recs;              // [n_entries] / [n_wide] TgRec
   smx::DevBuf<unsigned long long> table;           // [mask + 1][2] TgCell
   smx::DevBuf<uint32_t> first_rec;                 // [n_in] dscene_first_word of every triangle of R
+  smx::DevBuf<uint8_t> rim;                        // [n_in] smx_recon_mesh_rim's bytes, indexed like nearest (smx_recon_build_distscene_rim only)
+  bool has_rim = false;
   smx::DevBuf<uint32_t> counters;                  // [kDsceneBuildWords] as the build left them: c
   uint32_t h[smx::kDsceneBuildWords] = {};         // ... and on the host
   uint32_t mask = 0, n_entries = 0, n_wide = 0, n_in = 0;

@@ -3,8 +3,8 @@
 // smx_recon.hip holds the frame loop (Integrate / Regularize, their kernels, the changed-surfel delta),
 // smx_recon_map.hip the map services that read or rewrite the finished map outside of it (row transfers, export,
 // viewer buffers, the splat render, neighbour and meshing glue, compaction, deformation); tracking, decimation, the
-// components, hole filling, the mesh distance, the ray cast, the mesh sampler and the mesh render live with their kernels in smx_track.hip, smx_decimate.hip,
-// smx_components.hip, smx_fill.hip, smx_distance.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
+// components, hole filling, the mesh distance, the rim, the ray cast, the mesh sampler and the mesh render live with their kernels in smx_track.hip, smx_decimate.hip,
+// smx_components.hip, smx_fill.hip, smx_distance.hip, smx_rim.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
 // they all need: the attribute layout, the plain structs that are members of smx_recon_s, the object itself -- the
 // frame loop's state, then one workspace per service, each defined in the service's own header -- and the few host
 // helpers every entry point starts with.  Kernels stay in anonymous namespaces of the .hip files.
@@ -17,6 +17,7 @@
 #include "smx_fill.hpp"
 #include "smx_raycast.hpp"
 #include "smx_render.hpp"
+#include "smx_rim.hpp"
 #include "smx_sample.hpp"
 #include "smx_track.hpp"
 
@@ -412,9 +413,11 @@ struct smx_recon_s {
   smx::ComponentsWork components; // smx_recon_mesh_components
   smx::FillWork fill;             // smx_recon_fill_holes
   smx::DistanceWork distance;     // smx_recon_mesh_distance
+  smx::RimWork rim;               // smx_recon_mesh_rim
   smx::RaycastWork raycast;       // smx_recon_raycast_mesh
   smx::SampleWork sample;         // smx_recon_sample_mesh
   smx::CompareWork compare;       // smx_recon_compare_meshes
+  smx::RegisterMeshWork register_mesh;   // smx_recon_register_mesh
   smx::CompactWork compact;       // smx_recon_compact
   smx::CandidateWork candidates;  // smx_recon_neighbor_candidates
   smx::MeshWorkspace* mesh;       // smx_recon_triangulate / _update (created by the first call): lists, rings, counts, output staging

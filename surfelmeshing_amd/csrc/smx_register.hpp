@@ -72,6 +72,60 @@ SMX_REG_FN void reg_sample(const TgVec& P, uint32_t t, const TgVec& Q, const TgV
   track_accumulate(acc, acc[kSumRR], J, r, r);
 }
 
+// ---- the robust row (smx_distscene_register_robust) -----------------------------------------------------------
+enum : int { kRegKernelNone = 0, kRegKernelHuber = 1, kRegKernelTukey = 2 };
+// "The closest point of p' lies on the rim": the region of dist_closest on the winner's first-record corners -- the computation
+// the query's Q came from -- picks the bit of the triangle's rim byte (smx_rim.hpp; the interior, region 6, has none).
+SMX_REG_FN bool reg_rim_hit(uint32_t rim_byte, const TgVec& P, const TgVec& A, const TgVec& B, const TgVec& C) {
+  uint32_t region;
+  (void)dist_closest(P, A, B, C, &region);
+  return ((rim_byte >> region) & 1u) != 0;
+}
+// The weight of a row with residual r at scale c > 0, as the factor s on J and r (the weight is s * s); a = |r|.
+//   Huber: a <= c leaves the row as it is (s = 1, not applied); else s = sqrtf(c / a) and the sample is counted as down-weighted.
+//   Tukey: !(a < c) rejects the sample (counted); else u = a / c, s = 1 - u u, always applied.
+// kept = the sample stays an inlier, apply = multiply the row by s, counted = the sample adds 1 to sum [32].
+struct RegWeight { float s; int kept, apply, counted; };
+SMX_REG_FN RegWeight reg_weight(int kernel, float c, float r) {
+  const float a = fabsf(r);
+  if (kernel == kRegKernelHuber) {
+    if (a <= c) return RegWeight{1.0f, 1, 0, 0};
+    return RegWeight{sqrtf(c / a), 1, 1, 1};
+  }
+  if (kernel == kRegKernelTukey) {
+    if (!(a < c)) return RegWeight{1.0f, 0, 0, 1};
+    const float u = a / c;
+    return RegWeight{1.0f - u * u, 1, 1, 0};
+  }
+  return RegWeight{1.0f, 1, 0, 0};
+}
+// reg_sample with the two new decisions, in this order per sample: BAD -> not matched -> collinear winner -> rim -> normal gate
+// -> weight -> inlier.  c == 0 (or kernel 0): no weights.  The weighted row is (s J, s r) with e = r, so sum [27] stays the
+// geometric sum of r * r.  n_rim and n_weight are the sums [31] and [32].
+SMX_REG_FN void reg_sample_robust(const TgVec& P, uint32_t t, const TgVec& Q, const TgVec& A, const TgVec& B, const TgVec& C, bool with_normal,
+                                  const TgVec& m, float cos_max, uint32_t rim_byte, bool reject_rim, int kernel, float c, double* acc,
+                                  uint32_t& n_in, uint32_t& n_ok, uint32_t& n_matched, uint32_t& n_rim, uint32_t& n_weight) {
+  if (!tg_point_ok(P)) return;
+  ++n_ok;
+  if (t == 0xFFFFFFFFu) return;
+  ++n_matched;
+  const TgVec g = tg_cross(tg_sub(B, A), tg_sub(C, A));
+  if (!(tg_dot(g, g) > 0.0f)) return;
+  if (reject_rim && reg_rim_hit(rim_byte, P, A, B, C)) { ++n_rim; return; }
+  float J[6], r;
+  if (reg_row(P, Q, A, B, C, with_normal, m, cos_max, J, &r) != kRegInlier) return;
+  const RegWeight w = (kernel == kRegKernelNone || c == 0.0f) ? RegWeight{1.0f, 1, 0, 0} : reg_weight(kernel, c, r);
+  if (w.counted) ++n_weight;
+  if (!w.kept) return;
+  ++n_in;
+  float rw = r;
+  if (w.apply) {
+    for (int k = 0; k < 6; ++k) J[k] = w.s * J[k];
+    rw = w.s * r;
+  }
+  track_accumulate(acc, acc[kSumRR], J, rw, r);
+}
+
 #if !defined(SMX_REGISTER_HOST_ONLY)
 // ---- part 2 ----------------------------------------------------------------------------------------------------------
 // The device state of a call: the tracker's (T_rel = scene <- points, the ring of records) with what a registration adds: the
@@ -81,9 +135,12 @@ struct RegDev {
   TrackDev t;
   float ring_Tf[kTrackRing][12];
   smx_register_result result;
+  uint32_t ring_counts[kTrackRing][2];     // sums [31] and [32] of every recorded iteration of a robust call (behind what the plain kernels address)
 };
 
 struct RegPose { float m[12]; };
+// what the robust reduce kernel needs besides the plain one's arguments
+struct RegRobustK { const uint8_t* rim; int reject_rim, kernel; float c; };
 #endif
 
 }  // namespace smx

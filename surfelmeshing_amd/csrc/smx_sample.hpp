@@ -128,6 +128,12 @@ struct CompareWork {
   PhaseStamps<SMX_COMPARE_PHASES> stamps;
   int32_t directions = 0;                  // of the last call: a side not asked for reads 0 ms whatever lies between its stamps
 };
+// The workspace of smx_recon_register_mesh: the triangle array on the device, the samples and their normals.
+struct RegisterMeshWork {
+  DevBuf<uint32_t> in;                     // staging when the caller's array is host memory
+  DevBuf<float> points, normals;           // [n_samples][3]
+  DevBuf<uint32_t> tri;                    // [n_samples]
+};
 #endif
 
 }  // namespace smx

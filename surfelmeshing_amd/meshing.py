@@ -210,13 +210,16 @@ class MapMesher:
             self._index = None
 
 
-def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=None):
+def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=None, rim=False):
     """A DistanceScene of `triangles` over the map as it stands (CUDASurfelReconstruction.BuildDistanceScene), for queries within
     max_distance: build it once, then pass it as scene= to mesh_distance or decimation_error, or as scene_b= to compare_meshes,
-    as often as needed.  It is a snapshot: later changes of the map do not reach it.  ValueError on parameters the library would
-    refuse."""
+    as often as needed.  It is a snapshot: later changes of the map do not reach it.  rim=True keeps mesh_rim's bytes with the
+    scene, which register_points(robust=register_robust_params(reject_rim=True)) needs.  ValueError on parameters the library
+    would refuse."""
     from .api import distscene_params
     distscene_params(max_distance, cell_size)
+    if rim:
+        return rec.BuildDistanceScene(stream, triangles, max_distance, cell_size, rim=True)
     return rec.BuildDistanceScene(stream, triangles, max_distance, cell_size)
 
 
@@ -228,12 +231,32 @@ def register_params(**kw):
     return RegisterParams.defaults(**kw)
 
 
-def register_points(scene, points, normals=None, T_init=None, params=None, stream=None):
+def register_robust_params(**kw):
+    """The robust part of a registration (smx_register_robust_params): kernel "none" / "huber" / "tukey", scale (the kernel's c in
+    metres, one value or one per level; 0 = no weights on that level), reject_rim (matches whose closest point lies on the rim of
+    the scene's mesh are no inliers; the scene must have been built with rim=True).  Where two surfaces overlap only in part,
+    reject_rim removes the pull of the samples beyond the mesh's edge, and Tukey at a few times the noise removes points that
+    belong to nothing in the mesh.  ValueError on what the library would refuse."""
+    from .api import register_robust_params as make
+    return make(**kw)
+
+
+def register_mesh(rec, scene, triangles, n_samples, seed=0, T_init=None, params=None, robust=None, stream=None):
+    """Mesh to mesh in one call: n_samples points with their normals drawn on `triangles` over rec's map (as sample_mesh draws
+    them), registered to the mesh `scene` holds (as register_points does): the dict of DistanceScene.Register.  The samples
+    never leave the device.  ValueError on what the library would refuse."""
+    return rec.RegisterMesh(stream, scene, triangles, n_samples, seed, T_init, params if params is not None else register_params(), robust)
+
+
+def register_points(scene, points, normals=None, T_init=None, params=None, stream=None, robust=None):
     """Aligns `points` ([P,3], their own frame) to the mesh a DistanceScene holds (build_distance_scene) by point-to-plane ICP
     from the pose T_init (scene <- points, [3,4]; None = the identity): the dict of DistanceScene.Register, whose scene_T_points
     is the pose found and whose status is one of the tracker's.  normals ([P,3], optional) adds the normal gate.  params: a
     register_params(...) (None = the defaults).  The scene's bound limits how far a point may lie from the mesh and still
-    count, so build the scene for the misalignment expected.  ValueError on what the library would refuse."""
+    count, so build the scene for the misalignment expected.  robust: a register_robust_params(...) (None = the plain call).
+    ValueError on what the library would refuse."""
+    if robust is not None:
+        return scene.Register(stream, points, normals, T_init, params if params is not None else register_params(), robust=robust)
     return scene.Register(stream, points, normals, T_init, params if params is not None else register_params())
 
 
@@ -301,6 +324,18 @@ def decimation_error(rec, fine, coarse, max_distance, cell_size=0.0, stream=None
     used = np.unique(np.ascontiguousarray(fine, np.uint32))
     nearest, distance, stats = mesh_distance(rec, coarse, map_positions(rec, used, stream), max_distance, cell_size, stream=stream, scene=scene)
     return distance_summary(distance, stats), nearest, distance, stats
+
+
+RIM_STAT_NAMES = ("n_in", "n_not_live", "n_repeated", "n_out_of_range", "n_edges", "n_rim_edges", "n_nonmanifold_edges", "n_rim_vertices",
+                  "n_rim_triangles")
+RIM_REGIONS = ("A", "B", "AB", "C", "AC", "BC")      # bit k of a triangle's byte: region k of the distance call's closest point
+
+
+def mesh_rim(rec, triangles, stream=None):
+    """Which corners and edges of every triangle lie on the boundary of the surface `triangles` shows: (rim [T] uint8, stats) as
+    CUDASurfelReconstruction.MeshRim returns them.  An edge is a rim edge iff one triangle alone has it; a closest point of
+    mesh_distance in region k of triangle t lies on the rim iff (rim[t] >> k) & 1."""
+    return rec.MeshRim(stream, triangles)
 
 
 def sample_mesh(rec, triangles, n_samples, seed=0, return_bary=False, return_normals=False, stream=None):

@@ -10,7 +10,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --distance METRES[,METRES...] --scene [--decimate METRES] [--compare N] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH --scene [--decimate METRES] [--json OUT] [--txt OUT]
-    python tools/mesh_bench.py --register POINTS [--distance METRES[,METRES...]] [--decimate METRES] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --register POINTS [--register_robust] [--distance METRES[,METRES...]] [--decimate METRES] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -78,6 +78,10 @@ the walls' normals) registered from the identity to a distance scene of the full
 default 0.05 m), built for every bound of --distance (default 0.01,0.05), with the default schedule; per call the whole time and
 the move, query, reduce and solve of the last iteration by the library's events, and beside them, in the same process, the
 scene's plain query of the same points at the bound.  Writes profiles/register_bench.{txt,json} unless --txt / --json say otherwise.
+--register POINTS --register_robust measures smx_distscene_register_robust and smx_recon_build_distscene_rim beside
+the plain call and the plain build in the same process: the rim build against the scene build it extends, the robust call (rim
+rejection and Tukey weights at bound, bound / 2, bound / 4) against the plain call of the same points, the robust reduce kernel
+against the plain one in the last iteration.  Writes profiles/register_robust_bench.{txt,json}.
 
 --raycast WxH --scene measures smx_rayscene on the same rays and the same two meshes (the decimated one at the
 first --decimate cell, 0.05 m by default), everything in one process: smx_recon_raycast_mesh re-measured first (its call, its
@@ -123,6 +127,8 @@ ap.add_argument("--scene", action="store_true", help="with --raycast: measure sm
                                                       "with --distance: measure smx_distscene (build by phase, queries) beside smx_recon_mesh_distance")
 ap.add_argument("--register", type=int, default=0, metavar="POINTS", help="measure smx_distscene_register of this many room-surface points "
                                                                            "against the full and the decimated mesh at the --distance bounds")
+ap.add_argument("--register_robust", action="store_true", help="with --register: the robust call (rim rejection and Tukey weights) and the rim build, "
+                                                               "timed beside the plain call and the plain build")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -830,6 +836,114 @@ def distscene_main():
 REGISTER_PHASES = ("move", "query", "reduce", "solve")
 
 
+def register_robust_main():
+    """--register POINTS --register_robust: the rim build beside the scene build, the robust call beside the plain one."""
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    maxes = [float(c) for c in (args.distance or "0.01,0.05").split(",")]
+    cell = float(args.decimate.split(",")[0]) if args.decimate else 0.05
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    from surfelmeshing_amd import meshing, synth
+    pts = synth.room_surface_points(args.register + args.register // 50 + 64)[0]
+    if pts.shape[0] > args.register:
+        pts = pts[np.sort(np.random.default_rng(7).permutation(pts.shape[0])[:args.register])]
+    pts = np.ascontiguousarray(pts, np.float32)
+    P = pts.shape[0]
+    tp = torch.from_numpy(pts).cuda()
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    dres = api.CUDABuffer(1, C.sizeof(_lib.RegisterResult) // 4 + 4, np.uint32)
+    drim = api.CUDABuffer(1, cap, np.uint8)
+    say("# %d points of synth.room_surface_points, no normals, on the device; the default schedule from the identity; robust = rim rejection and "
+        "Tukey weights at bound, bound / 2, bound / 4; medians of %d repetitions after one that allocates" % (P, args.reps))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def spread(v):
+        return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+    def show(s):
+        return "%.3f ms (min %.3f, max %.3f)" % (s["median"], s["min"], s["max"])
+    T, mst = C.c_uint32(0), _lib.MeshStats()
+    _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(cap),
+                                       C.c_int32(1), C.byref(T), C.byref(mst)))
+    T_in = T.value
+    Tc, dst = C.c_uint32(0), _lib.DecimateStats()
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(Tc), C.byref(dst)))
+    prm = meshing.register_params()
+    out_rows = []
+    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at %g m" % cell, dout, Tc.value)):
+        tri = _DeviceArray(src, 3 * n_in)
+        # ---- the rim alone
+        rim_ms, rim_st = [], _lib.RimStats()
+        for _ in range(args.reps + 1):
+            rim_ms.append(timed(lambda: _lib.check(L.smx_recon_mesh_rim(rec._h, None, C.c_void_p(src.ToCUDA().address), C.c_uint32(n_in), C.c_int32(1),
+                                                                        C.c_void_p(drim.ToCUDA().address), C.byref(rim_st))))[0])
+        rst = {k: int(getattr(rim_st, k)) for k, _ in _lib.RimStats._fields_}
+        for md in maxes:
+            builds = {"plain": [], "with rim": []}
+            scene = api.DistanceScene()
+            for _ in range(args.reps + 1):
+                builds["plain"].append(timed(lambda: rec.BuildDistanceScene(None, tri, md, scene=scene))[0])
+                builds["with rim"].append(timed(lambda: rec.BuildDistanceScene(None, tri, md, scene=scene, rim=True))[0])
+            robust = meshing.register_robust_params(kernel="tukey", scale=(md, md / 2, md / 4), reject_rim=True)
+            rows = {}
+            for name, rp in (("plain", None), ("robust", robust)):
+                whole, phs, first = [], [], None
+                for _ in range(args.reps + 1):
+                    ms, _ = timed(lambda: scene.Register(None, tp, None, None, prm, result_buffer=dres, robust=rp))
+                    whole.append(ms)
+                    phs.append(scene.debug_register_timings())
+                    got = dres.Download()[0].tobytes()
+                    first = got if first is None else first
+                    assert got == first, "two calls gave different bytes"
+                res = api.register_result_dict(_lib.RegisterResult.from_buffer_copy(first[:C.sizeof(_lib.RegisterResult)]))
+                counts = scene.RegisterRobustCounts()
+                ph = {k: spread([q[k] for q in phs[1:]]) for k in ("call",) + REGISTER_PHASES}
+                rows[name] = {"call_ms": spread(whole[1:]), "phases_ms": ph, "status": int(res["status"]), "iterations_run": int(res["iterations_run"]),
+                              "inliers": int(res["inliers"]), "points_used": int(res["points_used"]), "rms_residual": float(res["rms_residual"]),
+                              "last_counts": [int(v) for v in counts[-1]] if len(counts) else [0, 0]}
+                say("%s, bound %g m, %d triangles, %s call: %s | last iteration: %s | status %d after %d iterations, %d inliers of %d used, rms %.2f mm, "
+                    "%d on the rim, %d rejected by Tukey" % (
+                        what, md, n_in, name, show(rows[name]["call_ms"]), " | ".join("%s %s" % (k, show(ph[k])) for k in REGISTER_PHASES), res["status"],
+                        res["iterations_run"], res["inliers"], res["points_used"], 1e3 * res["rms_residual"], *rows[name]["last_counts"]))
+            say("%s, bound %g m, %d triangles: scene build %s, with the rim %s; the rim alone %s (%d edges, %d of them rim, %d rim triangles); robust reduce "
+                "%.3f ms against %.3f ms plain and a query of %.3f ms in the last iteration" % (
+                    what, md, n_in, show(spread(builds["plain"][1:])), show(spread(builds["with rim"][1:])), show(spread(rim_ms[1:])), rst["n_edges"],
+                    rst["n_rim_edges"], rst["n_rim_triangles"], rows["robust"]["phases_ms"]["reduce"]["median"], rows["plain"]["phases_ms"]["reduce"]["median"],
+                    rows["robust"]["phases_ms"]["query"]["median"]))
+            out_rows.append({"input": what, "bound": md, "triangles_in": n_in, "points": P, "reps": args.reps, "rim_ms": spread(rim_ms[1:]),
+                             "rim_stats": rst, "build_ms": {k: spread(v[1:]) for k, v in builds.items()}, "register": rows})
+            scene.close()
+    res = {"metric": "register_robust_call_ms", "slots": n, "live": live, "triangles_in": T_in, "rows": out_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "register_robust_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "register_robust_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 def register_main():
     """--register POINTS: smx_distscene_register beside the scene's plain query of the same points in one process."""
     import ctypes as C
@@ -1474,4 +1588,4 @@ def main():
 
 
 if __name__ == "__main__":
-    register_main() if args.register else distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    register_robust_main() if (args.register and args.register_robust) else register_main() if args.register else distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -36,6 +36,11 @@ head "scene points" and a total, whose figures are those of the --mesh_eval line
 surface part: the ground-truth points of each evaluated frame (the last --mesh_eval_frames N, or every integrated frame) are
 registered to one distance scene of the final mesh from the identity (smx_distscene_register); one line per frame with the
 status, the rotation and translation recovered (the drift) and the surface error before and after the alignment, and a total.
+--mesh_eval_register_reject_rim and --mesh_eval_register_kernel {none,huber,tukey} --mesh_eval_register_scale METRES (beside
+--mesh_eval_register) run the robust call as well (smx_distscene_register_robust; the scene is built with its rim when asked): the
+ground-truth points reach beyond the reconstructed surface, and the plain call is pulled by the matches on the mesh's edge.
+Per frame a second line, "robustly registered frame ...", with the two counts of the last iteration (matches rejected on the
+rim, samples down-weighted or rejected by the kernel), and a second total.
 --mesh_compare_samples N prints, for every stage of the chain that was asked for (cleaning, hole filling, decimation), the
 two-sided surface error between the mesh before and after it on N area-weighted samples per side (smx_recon_compare_meshes).
 --export_mesh_samples FILE.ply with --mesh_samples N writes N such samples of the final mesh with the face normals.
@@ -213,6 +218,12 @@ def parse_args(argv=None):
     ap.add_argument("--mesh_eval_register", action="store_true",
                     help="with --mesh_eval METRES --synthetic N --mesh: register the ground-truth points of each evaluated frame to the "
                          "final mesh from the identity (smx_distscene_register): the pose recovered and the surface error before and after")
+    ap.add_argument("--mesh_eval_register_reject_rim", action="store_true",
+                    help="with --mesh_eval_register: also run the robust call with the matches on the mesh's rim rejected")
+    ap.add_argument("--mesh_eval_register_kernel", choices=("none", "huber", "tukey"), default="none",
+                    help="with --mesh_eval_register: also run the robust call with this weight kernel (needs --mesh_eval_register_scale)")
+    ap.add_argument("--mesh_eval_register_scale", type=float, default=None, metavar="METRES",
+                    help="the kernel's scale c, 1e-6 .. 16 metres")
     ap.add_argument("--mesh_eval_rays", action="store_true",
                     help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
                          "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
@@ -285,6 +296,17 @@ def parse_args(argv=None):
         ap.error("--mesh_eval_frames needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_register and not (args.mesh_eval is not None and args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_register needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
+    if (args.mesh_eval_register_reject_rim or args.mesh_eval_register_kernel != "none" or args.mesh_eval_register_scale is not None) and \
+            not args.mesh_eval_register:
+        ap.error("--mesh_eval_register_reject_rim, --mesh_eval_register_kernel and --mesh_eval_register_scale need --mesh_eval_register")
+    if (args.mesh_eval_register_kernel != "none") != (args.mesh_eval_register_scale is not None):
+        ap.error("--mesh_eval_register_kernel huber|tukey and --mesh_eval_register_scale METRES go together")
+    if args.mesh_eval_register_scale is not None and not (1e-6 <= args.mesh_eval_register_scale <= 16.0):
+        ap.error("--mesh_eval_register_scale needs 1e-6 .. 16 metres")
+    args.mesh_eval_register_robust = None
+    if args.mesh_eval_register_reject_rim or args.mesh_eval_register_kernel != "none":
+        args.mesh_eval_register_robust = dict(kernel=args.mesh_eval_register_kernel, scale=args.mesh_eval_register_scale or 0.0,
+                                              reject_rim=args.mesh_eval_register_reject_rim)
     if args.mesh_eval_rays and not (args.synthetic and (args.mesh or args.mesh_every > 0)):
         ap.error("--mesh_eval_rays needs --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
     if args.mesh_eval_rays_frames < 0:
@@ -344,6 +366,12 @@ def register_figures(result, before, after):
 def format_register_line(f, fig):
     return "registered frame %d: status %d after %d iterations, %.3f mrad and %.3f mm from the identity; surface error %.3f -> %.3f mm mean, %.3f -> %.3f mm rms" % (
         f, fig["status"], fig["iterations"], fig["mrad"], fig["mm"], fig["mean"][0], fig["mean"][1], fig["rms"][0], fig["rms"][1])
+
+
+def format_robust_register_line(f, fig, counts):
+    """The second line of a frame with --mesh_eval_register_reject_rim / _kernel: the robust call's figures and the two counts of
+    its last iteration."""
+    return "robustly " + format_register_line(f, fig) + "; last iteration: %d on the rim, %d weighted or rejected" % (int(counts[0]), int(counts[1]))
 
 
 def format_register_total(figs):
@@ -563,17 +591,26 @@ def main():
         half_ = args.outlier_filtering_frame_count // 2
         last = n - half_ - 1
         first = last - args.mesh_eval_frames + 1 if args.mesh_eval_frames else args.start_frame + half_
-        figs = []
-        with meshing.build_distance_scene(rec, triangles, args.mesh_eval) as scene:
-            for f in range(max(first, args.start_frame + half_), last + 1):
-                pts = np.ascontiguousarray(s.surface_points(f, 8), np.float32)
-                res = meshing.register_points(scene, pts)
+        figs, robust_figs = [], []
+        robust = meshing.register_robust_params(**args.mesh_eval_register_robust) if args.mesh_eval_register_robust else None
+        with meshing.build_distance_scene(rec, triangles, args.mesh_eval, rim=bool(robust is not None and robust.reject_rim)) as scene:
+            def figures(pts, res):
                 T = res["scene_T_points"].astype(np.float64)
                 moved = np.ascontiguousarray(pts.astype(np.float64) @ T[:, :3].T + T[:, 3], np.float32)
                 summaries = [meshing.distance_summary(*meshing.mesh_distance(None, None, p, args.mesh_eval, scene=scene)[1:]) for p in (pts, moved)]
-                figs.append(register_figures(res, *summaries))
+                return register_figures(res, *summaries)
+            for f in range(max(first, args.start_frame + half_), last + 1):
+                pts = np.ascontiguousarray(s.surface_points(f, 8), np.float32)
+                figs.append(figures(pts, meshing.register_points(scene, pts)))
                 print(format_register_line(f, figs[-1]))
+                if robust is not None:
+                    res = meshing.register_points(scene, pts, robust=robust)
+                    counts = scene.RegisterRobustCounts()          # (before the queries below: the records belong to the scene's last call)
+                    robust_figs.append(figures(pts, res))
+                    print(format_robust_register_line(f, robust_figs[-1], counts[-1] if len(counts) else (0, 0)))
         print(format_register_total(figs))
+        if robust is not None:
+            print("robustly " + format_register_total(robust_figs))
     if args.mesh_eval_rays:
         from surfelmeshing_amd import meshing
         half_ = args.outlier_filtering_frame_count // 2
