@@ -1663,8 +1663,8 @@ int smx_recon_build_distscene_rim(smx_recon r, smx_stream s, smx_distscene sc, c
  * normals, then smx_distscene_register_robust of those points and normals.  The samples never leave the device.  r and sc on
  * different devices: refused.  A refusal by either half is the call's refusal.  Synchronous.  on_device says where triangles
  * lives.
- * Not done: rim flags on the samples' side; scale or non-rigid alignment; an initialisation-free registration; an incremental
- * scene; other kernels (Cauchy, Geman-McClure). */
+ * Not done: rim flags on the samples' side; scale or non-rigid alignment; an incremental scene; other kernels (Cauchy,
+ * Geman-McClure).  (A registration without a start pose: smx_distscene_register_global below) */
 typedef struct {             /* smx_register_robust_params_default() fills the defaults: 0, {0, 0, 0}, 0 */
   int32_t kernel;            /* 0 none, 1 Huber, 2 Tukey */
   float   level_scale[3];    /* c of the level in metres; 0 = no weights on this level; else finite, 1e-6f .. 16.0f */
@@ -1681,6 +1681,106 @@ int smx_recon_register_mesh(smx_recon r, smx_stream s, smx_distscene sc, const u
                             int32_t on_device, uint32_t n_samples, uint32_t seed, const smx_register_params* p,
                             const smx_register_robust_params* rp, const float T_init[12],
                             smx_register_result* result, int32_t result_on_device);
+
+/* ---- registration without a start pose: score a lattice of poses, refine the best (not in the reference) ----
+ * Three calls: the candidate poses (host only), the score of many poses in one pass over the scene, and the whole search.
+ * Every word of a score is an integer, so the scores, the selection and the winner are held to equality with a model.
+ *
+ * smx_register_pose_lattice.  A pure function on the host, in double with + - * / only.  Rotations: the integer quaternions (w, x,
+ *    y, z) in [-k, k]^4 whose largest absolute component is exactly k, of each +- pair the one whose first non-zero component is
+ *    positive, in ascending lexicographic order of (w, x, y, z); no two are parallel, so no rotation repeats; (k, 0, 0, 0) is the
+ *    identity; N_k = ((2k+1)^4 - (2k-1)^4) / 2 of them (40, 272, 888, 2080, ...), k in 1 .. 8.  With n = w w + x x + y y + z z an
+ *    exact integer every entry of R is one exact integer numerator divided once by n: R00 = (w w + x x - y y - z z) / n, R01 = 2 (x
+ *    y - w z) / n, R02 = 2 (x z + w y) / n, R10 = 2 (x y + w z) / n, R11 = (w w - x x + y y - z z) / n, R12 = 2 (y z - w x) / n, R20 =
+ *    2 (x z - w y) / n, R21 = 2 (y z + w x) / n, R22 = (w w - x x - y y + z z) / n.  For anchor a: t_i = a_i - ((R_i0 c_0 + R_i1 c_1) +
+ *    R_i2 c_2), c = centre: a point in the points' frame, every anchor a point in the scene's frame where it may lie.  Each of
+ *    the 12 values is rounded once to float32 (row-major 3x4, scene <- points).  Pose index = rotation index * A + anchor index.
+ *    *count = N_k A is written whenever k, A (1 .. 2^20 / N_k) and the pointers are valid; poses are written only if capacity >=
+ *    count and centre and anchors are finite, otherwise SMX_ERR_INVALID_ARGUMENT with *count set.  The largest angle from a
+ *    rotation to the nearest lattice rotation, SAMPLED over 2000 rotations (a maximum of a sample, no bound): DESIGN.md 5s.
+ *
+ * smx_distscene_score_poses.  Sample j of every pose is point j * stride, j < m = ceil(n_points / stride), m <= 2^16.  For pose T
+ *    (12 floats) and sample j: p' by the registration's move, float32 as written there.  The association is exactly
+ *    smx_distscene_query's answer for p' at max_distance = q, unsigned (q = p->max_distance, 0 = the scene's bound).  Per pose:
+ *      n_ok       samples whose p' is not BAD by the registration's rule
+ *      n_matched  samples matched within q (sum [30] of a registration iteration at this pose, stride and gate)
+ *      n_rim      with reject_rim: matched samples whose winner has an area (len2 > 0 as in that call's row) and whose closest
+ *                 point lies on the rim -- the region of smx_recon_mesh_distance step 3 for p' on the winner's first-record
+ *                 corners picks the bit of rim[t] -- which is sum [31] of smx_distscene_register_robust with reject_rim; else 0
+ *      cost       the sum over all m samples of (uint32)(distance * 1048576.0f), the 2^-20 m word of smx_recon_compare_meshes,
+ *                 if the sample is matched and not counted in n_rim, else of that word of q.  A BAD sample pays q's word too.
+ *    Integers only: the bytes do not depend on schedule, chunking or search structure; two calls give the same bytes.  Poses are
+ *    processed in chunks of floor(chunk_points / m) poses, at least one (chunk_points = 2^22 unless
+ *    smx_distscene_debug_set_score_chunk says otherwise, 1 .. 2^24), which bounds the workspace; the chunks are enqueued back to
+ *    back -- per chunk the move, the query's three steps, the score kernel -- and the host reads nothing until all P are scored.
+ *    Synchronous; waits for a registration still running on the scene.  1 <= P <= 2^20.  poses and scores are host memory;
+ *    on_device says where points live.  One caller thread per scene; touches no smx_recon: a scene is a snapshot.  The workspace
+ *    belongs to the scene, is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation; every allocation
+ *    comes before the first launch.  SMX_ERR_INVALID_ARGUMENT, nothing launched and nothing written: an empty scene, a pose entry
+ *    that is not finite, stride outside 1 .. 65536, m > 2^16, P outside 1 .. 2^20, q neither 0 nor finite in 1e-3f .. the scene's
+ *    bound, reject_rim not 0 / 1 or on a scene without a rim, points == NULL with n_points > 0, n_points > 2^28, scores
+ *    overlapping poses or host points.
+ *
+ * smx_distscene_register_global.  BY DEFINITION, in this order:
+ *    1. smx_distscene_score_poses of all P poses with gp->score.
+ *    2. The poses ordered by (cost, pose index) ascending; the first M = min(n_starts, P) are the starts.  One read-back.
+ *    3. For rank r = 0 .. M - 1: smx_distscene_register -- or smx_distscene_register_robust iff rp != NULL and asks for a kernel or
+ *       reject_rim -- with T_init = poses[index_r], p, the points and normals given: its result, byte for byte.  A start that
+ *       fails keeps its T_init, as that call's contract says.
+ *    4. smx_distscene_score_poses of the M result poses with gp->score: cost_after, n_matched_after.
+ *    5. The winner is the start with the smallest (cost_after, rank).
+ *    out->result = the winner's smx_register_result; found = 1 iff its status is OK or CONVERGED and (float)n_matched_after >=
+ *    min_matched_fraction * (float)n_ok_after; winner_rank; n_starts_run = M; starts[r] for r < M, zeros behind.  all_scores
+ *    (may be NULL) receives step 1's P scores.  Refused, nothing written: what either of the two calls refuses; n_starts outside
+ *    1 .. 64; min_matched_fraction outside 0 .. 1; out or all_scores overlapping poses, host points or normals, or each other.
+ *    Synchronous.
+ *    Not built: suppressing starts that fall into one basin; feature matching; scale; a search over translations beyond the
+ *    anchors given; an enqueue-only variant. */
+typedef struct {
+  int32_t stride;            /* sample j is point j * stride; 1 .. 65536 */
+  float   max_distance;      /* the gate q; 0 = the scene's bound; else 1e-3f .. the bound */
+  int32_t reject_rim;        /* 1: a match whose closest point lies on the rim pays q; needs a scene with a rim */
+} smx_score_params;
+typedef struct {
+  uint64_t cost;
+  uint32_t n_ok, n_matched, n_rim, reserved;
+} smx_pose_score;
+typedef struct {             /* smx_global_params_default() fills the defaults: {1, 0, 0}, 8, 0.5 */
+  smx_score_params score;
+  int32_t n_starts;          /* 1 .. 64 */
+  float   min_matched_fraction;
+} smx_global_params;
+#define SMX_GLOBAL_MAX_STARTS 64
+typedef struct {
+  uint32_t pose_index;
+  int32_t  status, iterations_run;   /* of the registration from this start */
+  uint32_t n_matched_after;
+  uint64_t cost_before, cost_after;
+} smx_global_start;
+typedef struct {
+  smx_register_result result;        /* the winner's */
+  int32_t found, winner_rank, n_starts_run, reserved;
+  smx_global_start starts[SMX_GLOBAL_MAX_STARTS];
+} smx_global_result;
+int smx_register_pose_lattice(int32_t k, const double centre[3], const double* anchors /* [A][3] */, uint32_t A,
+                              float* poses /* [capacity][12] */, uint32_t capacity, uint32_t* count);
+int smx_global_params_default(smx_global_params* out);
+int smx_distscene_score_poses(smx_distscene sc, smx_stream s, const smx_score_params* p, const float* points /* [n_points][3] */,
+                              uint32_t n_points, int32_t on_device, const float* poses /* [P][12], host */, uint32_t P,
+                              smx_pose_score* scores /* [P], host */);
+int smx_distscene_register_global(smx_distscene sc, smx_stream s, const smx_global_params* gp, const smx_register_params* p,
+                                  const smx_register_robust_params* rp /* may be NULL */, const float* points,
+                                  const float* normals /* may be NULL */, uint32_t n_points, int32_t on_device,
+                                  const float* poses /* [P][12], host */, uint32_t P, smx_global_result* out,
+                                  smx_pose_score* all_scores /* [P], host, may be NULL */);
+/* Tests: the samples a chunk of smx_distscene_score_poses may hold (1 .. 2^24), so that a small case crosses chunk edges. */
+int smx_distscene_debug_set_score_chunk(smx_distscene sc, uint32_t chunk_points);
+/* Tools: milliseconds of the scene's last pose scoring and search: [0] the score phase (step 1, or the last
+ * smx_distscene_score_poses) by timed events on its stream, [1..3] the move, the query and the score kernel of its LAST chunk, [4..6]
+ * select, refine and rescore of the last smx_distscene_register_global on the host's clock (0 after a bare score).  capacity >=
+ * SMX_GLOBAL_PHASES. */
+#define SMX_GLOBAL_PHASES 7
+int smx_distscene_debug_global_timings(smx_distscene sc, float* out_ms, int32_t capacity);
 
 /* ---- a triangle array drawn to images: a software rasteriser (not in the reference, whose viewer draws the mesh with
  * OpenGL) ----

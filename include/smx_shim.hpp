@@ -534,6 +534,25 @@ class DistanceScene {
     SMX_SHIM_CHECK(smx_distscene_register_robust(handle_, stream, &params, &robust, n_points ? points.data() : nullptr,
                                                  normals && n_points ? normals->data() : nullptr, n_points, 0, T_init, result, 0));
   }
+  // The integer score of every pose of `poses` ([P][12], scene <- points) for `points`, all poses in one pass over the scene
+  // (smx_distscene_score_poses in smx.h); scores is resized to P.
+  void ScorePoses(cudaStream_t stream, const std::vector<float>& points, const smx_score_params& score, const std::vector<float>& poses,
+                  std::vector<smx_pose_score>* scores) {
+    const u32 n_points = (u32)(points.size() / 3), n_poses = (u32)(poses.size() / 12);
+    scores->resize(n_poses);
+    SMX_SHIM_CHECK(smx_distscene_score_poses(handle_, stream, &score, n_points ? points.data() : nullptr, n_points, 0, poses.data(), n_poses,
+                                             scores->data()));
+  }
+  // Registration without a start pose (smx_distscene_register_global in smx.h): the poses (smx_register_pose_lattice) are scored,
+  // the cheapest global.n_starts refined as Register / RegisterRobust (robust may be null) do, the cheapest result wins.
+  void RegisterGlobal(cudaStream_t stream, const std::vector<float>& points, const std::vector<float>* normals, const smx_global_params& global,
+                      const smx_register_params& params, const smx_register_robust_params* robust, const std::vector<float>& poses,
+                      smx_global_result* result) {
+    const u32 n_points = (u32)(points.size() / 3), n_poses = (u32)(poses.size() / 12);
+    SMX_SHIM_CHECK(smx_distscene_register_global(handle_, stream, &global, &params, robust, n_points ? points.data() : nullptr,
+                                                 normals && n_points ? normals->data() : nullptr, n_points, 0, poses.data(), n_poses, result,
+                                                 nullptr));
+  }
   const smx_distscene_stats& stats() const { return stats_; }
   const smx_rim_stats& rim_stats() const { return rim_stats_; }      // (of a build by BuildDistanceSceneRim)
   smx_distscene handle() const { return handle_; }

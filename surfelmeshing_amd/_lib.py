@@ -385,6 +385,43 @@ class RegisterIteration(C.Structure):
                 ("Tf", C.c_float * 12), ("sums", C.c_double * REGISTER_SUMS), ("x", C.c_double * 6)]
 
 
+class ScoreParams(C.Structure):
+    """smx_score_params: which samples a pose is scored on (stride), the gate q (0 = the scene's bound) and whether a match on
+    the rim of the scene's mesh pays q."""
+    _fields_ = [("stride", C.c_int32), ("max_distance", C.c_float), ("reject_rim", C.c_int32)]
+
+
+class PoseScore(C.Structure):
+    """smx_pose_score"""
+    _fields_ = [("cost", C.c_uint64), ("n_ok", C.c_uint32), ("n_matched", C.c_uint32), ("n_rim", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+POSE_SCORE_DTYPE = [("cost", "<u8"), ("n_ok", "<u4"), ("n_matched", "<u4"), ("n_rim", "<u4"), ("reserved", "<u4")]   # numpy's view of it
+
+
+class GlobalParams(C.Structure):
+    """smx_global_params: the score's parameters, the number of starts refined and the matched fraction `found` asks for."""
+    _fields_ = [("score", ScoreParams), ("n_starts", C.c_int32), ("min_matched_fraction", C.c_float)]
+
+
+GLOBAL_MAX_STARTS = 64      # SMX_GLOBAL_MAX_STARTS
+GLOBAL_PHASES = 7           # SMX_GLOBAL_PHASES
+GLOBAL_MAX_POSES = 1 << 20
+GLOBAL_MAX_SAMPLES = 1 << 16
+
+
+class GlobalStart(C.Structure):
+    """smx_global_start"""
+    _fields_ = [("pose_index", C.c_uint32), ("status", C.c_int32), ("iterations_run", C.c_int32), ("n_matched_after", C.c_uint32),
+                ("cost_before", C.c_uint64), ("cost_after", C.c_uint64)]
+
+
+class GlobalResult(C.Structure):
+    """smx_global_result"""
+    _fields_ = [("result", RegisterResult), ("found", C.c_int32), ("winner_rank", C.c_int32), ("n_starts_run", C.c_int32),
+                ("reserved", C.c_int32), ("starts", GlobalStart * GLOBAL_MAX_STARTS)]
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -473,6 +510,8 @@ EXPORTS = [
     "smx_distscene_create", "smx_distscene_destroy", "smx_distscene_params_default", "smx_recon_build_distscene", "smx_distscene_query",
     "smx_recon_compare_to_distscene", "smx_distscene_debug_timings",
     "smx_register_params_default", "smx_distscene_register", "smx_distscene_debug_register_iterations", "smx_distscene_debug_register_timings",
+    "smx_register_pose_lattice", "smx_global_params_default", "smx_distscene_score_poses", "smx_distscene_register_global",
+    "smx_distscene_debug_set_score_chunk", "smx_distscene_debug_global_timings",
     "smx_mesh_render_params_default", "smx_recon_render_mesh", "smx_recon_debug_mesh_render_timings",
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",

@@ -31,6 +31,7 @@ from ._lib import (BufferDesc, IntegrateParams, RenderParams, SmxError, SurfelBu
                    RAYSCENE_MAX_LOG2, RAYSCENE_PHASES, RaySceneCastStats, RaySceneParams, RaySceneStats,
                    DISTSCENE_PHASES, CompareSide, DistSceneParams, DistSceneStats,
                    REGISTER_MAX_POINTS, REGISTER_MAX_STRIDE, REGISTER_PHASES, RegisterIteration, RegisterParams, RegisterResult, RegisterRobustParams, REGISTER_KERNELS,
+                   GLOBAL_MAX_POSES, GLOBAL_MAX_SAMPLES, GLOBAL_MAX_STARTS, GLOBAL_PHASES, GlobalParams, GlobalResult, POSE_SCORE_DTYPE, ScoreParams,
                    DECIMATE_PHASES, DecimateStats, MeshParams, MeshRenderParams, MeshRenderStats, MeshStats, MeshUpdateStats, TrackIteration, TrackParams, TrackResult,
                    TrackRGBDIteration, TrackRGBDParams, TrackRGBDResult)
 
@@ -330,6 +331,76 @@ def register_robust_params(kernel="none", scale=0.0, reject_rim=False):
     return RegisterRobustParams(int(kernel), (C.c_float * 3)(*scales), 1 if reject_rim else 0)
 
 
+def pose_lattice(k, centre, anchors):
+    """The candidate poses of a registration without a start (smx_register_pose_lattice), [N_k * A, 3, 4] float32, scene <- points:
+    every rotation of the integer-quaternion lattice of order k (40, 272, 888, 2080, ... for k = 1, 2, 3, 4; k <= 8) about
+    `centre` (a point in the points' frame), its image placed on every anchor ([A,3], points in the scene's frame where the
+    centre may lie).  Pose index = rotation index * A + anchor index.  Host only.  ValueError on what the library would refuse."""
+    c = np.ascontiguousarray(centre, np.float64).reshape(-1)
+    a = np.ascontiguousarray(anchors, np.float64).reshape(-1)
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 8:
+        raise ValueError("k must lie in 1 .. 8")
+    if c.size != 3 or a.size == 0 or a.size % 3 or not (np.all(np.isfinite(c)) and np.all(np.isfinite(a))):
+        raise ValueError("centre must hold three finite values and anchors at least one finite [A,3] row")
+    n = C.c_uint32(0)
+    _lib.load().smx_register_pose_lattice(C.c_int32(int(k)), c.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), C.c_uint32(a.size // 3),
+                                          None, C.c_uint32(0), C.byref(n))
+    if n.value == 0:
+        raise ValueError("more than 2^20 poses: fewer anchors or a smaller k")
+    poses = np.zeros((n.value, 3, 4), np.float32)
+    _lib.check(_lib.load().smx_register_pose_lattice(C.c_int32(int(k)), c.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p),
+                                                     C.c_uint32(a.size // 3), poses.ctypes.data_as(C.c_void_p), C.c_uint32(n.value), C.byref(n)))
+    return poses
+
+
+def score_params(stride=1, max_distance=0.0, reject_rim=False):
+    """smx_score_params; ValueError on what the library would refuse whatever the scene."""
+    if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= REGISTER_MAX_STRIDE:
+        raise ValueError("stride must lie in 1 .. %d" % REGISTER_MAX_STRIDE)
+    q = np.float32(max_distance)
+    if not (q == 0 or (np.isfinite(q) and np.float32(1e-3) <= q <= np.float32(16.0))):
+        raise ValueError("max_distance must be 0 (the scene's bound) or lie in 0.001 .. 16")
+    if not isinstance(reject_rim, (bool, np.bool_)) and reject_rim not in (0, 1):
+        raise ValueError("reject_rim must be False or True")
+    return ScoreParams(int(stride), float(q), 1 if reject_rim else 0)
+
+
+def global_result_dict(res):
+    """smx_global_result as a dict: result (register_result_dict of the winner), found, winner_rank, n_starts_run, starts (a list
+    of dicts, one per start run)."""
+    starts = [{n: int(getattr(s, n)) for n, _ in s._fields_} for s in res.starts[:res.n_starts_run]]
+    return dict(result=register_result_dict(res.result), found=int(res.found), winner_rank=int(res.winner_rank),
+                n_starts_run=int(res.n_starts_run), starts=starts)
+
+
+def _points_for_call(points, normals=None):
+    """(device?, n_points, address of points, address of normals, what to keep alive) of a numpy array or a contiguous float32
+    device tensor of points, and of normals of the same kind and shape."""
+    dev = _device_address(points) is not None
+    if normals is not None and (_device_address(normals) is not None) != dev:
+        raise ValueError("points and normals must both be device tensors or both be host arrays")
+    if dev:
+        import torch
+        for a in (points, normals):
+            if a is not None and not (a.is_contiguous() and a.dtype == torch.float32 and a.numel() % 3 == 0):
+                raise ValueError("a device tensor of points or normals must be contiguous [P,3] float32")
+        n_points = points.numel() // 3
+        if normals is not None and normals.numel() != points.numel():
+            raise ValueError("normals must have the shape of points")
+        torch.cuda.current_stream(points.device).synchronize()      # (the tensors' producers; the call runs on its own stream)
+        return True, n_points, points.data_ptr() if n_points else None, normals.data_ptr() if normals is not None and n_points else None, [points, normals]
+    pts = np.ascontiguousarray(points, np.float32)
+    if pts.size % 3:
+        raise ValueError("points must hold three values per row")
+    n_points = pts.size // 3
+    nr = None
+    if normals is not None:
+        nr = np.ascontiguousarray(normals, np.float32)
+        if nr.size != pts.size:
+            raise ValueError("normals must have the shape of points")
+    return False, n_points, pts.ctypes.data if n_points else None, nr.ctypes.data if nr is not None and n_points else None, [pts, nr]
+
+
 class DistanceScene:
     """Not in the reference: a snapshot of a triangle array over the map with the search structure of MeshDistance
     (smx_distscene), built once by CUDASurfelReconstruction.BuildDistanceScene for one bound on max_distance and queried many
@@ -435,34 +506,7 @@ class DistanceScene:
         T = np.ascontiguousarray(np.asarray(np.eye(3, 4) if T_init is None else T_init, np.float32).reshape(-1))
         if T.size != 12 or not np.all(np.isfinite(T)):
             raise ValueError("T_init must hold 12 finite values")
-        dev = _device_address(points) is not None
-        if normals is not None and (_device_address(normals) is not None) != dev:
-            raise ValueError("points and normals must both be device tensors or both be host arrays")
-        keep = []
-        if dev:
-            import torch
-            for a in (points, normals):
-                if a is not None and not (a.is_contiguous() and a.dtype == torch.float32 and a.numel() % 3 == 0):
-                    raise ValueError("a device tensor of points or normals must be contiguous [P,3] float32")
-            n_points = points.numel() // 3
-            if normals is not None and normals.numel() != points.numel():
-                raise ValueError("normals must have the shape of points")
-            pin = points.data_ptr() if n_points else None
-            nin = normals.data_ptr() if normals is not None and n_points else None
-            torch.cuda.current_stream(points.device).synchronize()      # (the tensors' producers; the call runs on `stream`)
-        else:
-            pts = np.ascontiguousarray(points, np.float32)
-            if pts.size % 3:
-                raise ValueError("points must hold three values per row")
-            n_points = pts.size // 3
-            nr = None
-            if normals is not None:
-                nr = np.ascontiguousarray(normals, np.float32)
-                if nr.size != pts.size:
-                    raise ValueError("normals must have the shape of points")
-            keep = [pts, nr]
-            pin = pts.ctypes.data if n_points else None
-            nin = nr.ctypes.data if nr is not None and n_points else None
+        dev, n_points, pin, nin, keep = _points_for_call(points, normals)
         if n_points > REGISTER_MAX_POINTS:
             raise ValueError("at most 2^28 points")
         on_device = result_buffer is not None
@@ -503,6 +547,85 @@ class DistanceScene:
         out = (C.c_float * REGISTER_PHASES)()
         _lib.check(_lib.load().smx_distscene_debug_register_timings(self._h, out, C.c_int32(REGISTER_PHASES)))
         return dict(zip(("call", "move", "query", "reduce", "solve"), [float(v) for v in out]))
+
+    def _score_inputs(self, score, points, normals, poses):
+        """What ScorePoses and RegisterGlobal check and marshal alike."""
+        if not getattr(self, "_h", None):
+            raise ValueError("the scene is closed")
+        if not getattr(self, "stats", None):
+            raise ValueError("the scene holds no build")
+        sp = score if score is not None else score_params()
+        if not isinstance(sp, ScoreParams):
+            raise ValueError("score must be a ScoreParams (score_params(...))")
+        if np.float32(sp.max_distance) > np.float32(self.stats["max_distance"]):
+            raise ValueError("max_distance %g is above the %g the scene was built for" % (sp.max_distance, self.stats["max_distance"]))
+        if sp.reject_rim and not self.has_rim:
+            raise ValueError("reject_rim needs a scene built with rim=True")
+        T = np.ascontiguousarray(poses, np.float32).reshape(-1)
+        if T.size == 0 or T.size % 12 or T.size // 12 > GLOBAL_MAX_POSES or not np.all(np.isfinite(T)):
+            raise ValueError("poses must hold 1 .. 2^20 finite [3,4] poses")
+        dev, n_points, pin, nin, keep = _points_for_call(points, normals)
+        if n_points > REGISTER_MAX_POINTS or -(-n_points // sp.stride) > GLOBAL_MAX_SAMPLES:
+            raise ValueError("at most 2^28 points and 2^16 samples of them: a larger stride")
+        return sp, T, dev, n_points, pin, nin, keep
+
+    def ScorePoses(self, stream, points, poses, score=None):
+        """The integer score of every pose of `poses` ([P,3,4] float32, scene <- points) for `points` ([n,3] float32, a numpy
+        array or a contiguous device tensor) against the scene's triangles, all poses in one pass over the scene
+        (smx_distscene_score_poses): a numpy record array [P] with cost (the sum over the samples of the matched distance in
+        units of 2^-20 m, the gate's word for a sample that is not matched, BAD or rejected on the rim), n_ok, n_matched, n_rim.
+        score: a ScoreParams (score_params(stride, max_distance, reject_rim)).  Synchronous."""
+        sp, T, dev, n_points, pin, _, keep = self._score_inputs(score, points, None, poses)
+        out = np.zeros(T.size // 12, np.dtype(POSE_SCORE_DTYPE))
+        _lib.check(_lib.load().smx_distscene_score_poses(self._h, _sv(stream), C.byref(sp), C.c_void_p(pin), C.c_uint32(n_points),
+                                                         C.c_int32(1 if dev else 0), T.ctypes.data_as(C.c_void_p), C.c_uint32(T.size // 12),
+                                                         out.ctypes.data_as(C.c_void_p)))
+        del keep
+        return out
+
+    def RegisterGlobal(self, stream, points, normals, poses, params=None, robust=None, score=None, n_starts=8, min_matched_fraction=0.5,
+                       return_scores=False):
+        """Registration without a start pose (smx_distscene_register_global): every pose of `poses` ([P,3,4], pose_lattice(...))
+        is scored as ScorePoses does, the n_starts cheapest -- ties to the smaller index -- are each refined by Register (params,
+        robust as there; byte for byte that call's result from that start), the results are scored again and the cheapest wins.
+        Returns global_result_dict: result (the winner's Register dict), found (its status is OK or CONVERGED and at least
+        min_matched_fraction of its samples that are not BAD are matched), winner_rank, n_starts_run, starts (pose_index, status,
+        iterations_run, n_matched_after, cost_before, cost_after per start); with return_scores also the [P] record array of all
+        scores.  Synchronous."""
+        sp, T, dev, n_points, pin, nin, keep = self._score_inputs(score, points, normals, poses)
+        p = params if params is not None else RegisterParams.defaults()
+        register_check_params(p, self.stats["max_distance"])
+        if robust is not None:
+            if not isinstance(robust, RegisterRobustParams):
+                raise ValueError("robust must be a RegisterRobustParams (register_robust_params(...))")
+            if robust.reject_rim and not self.has_rim:
+                raise ValueError("reject_rim needs a scene built with rim=True")
+        if isinstance(n_starts, bool) or int(n_starts) != n_starts or not 1 <= int(n_starts) <= GLOBAL_MAX_STARTS:
+            raise ValueError("n_starts must lie in 1 .. %d" % GLOBAL_MAX_STARTS)
+        if not 0.0 <= float(min_matched_fraction) <= 1.0:
+            raise ValueError("min_matched_fraction must lie in 0 .. 1")
+        gp = GlobalParams(sp, int(n_starts), float(min_matched_fraction))
+        res = GlobalResult()
+        scores = np.zeros(T.size // 12, np.dtype(POSE_SCORE_DTYPE)) if return_scores else None
+        _lib.check(_lib.load().smx_distscene_register_global(
+            self._h, _sv(stream), C.byref(gp), C.byref(p), C.byref(robust) if robust is not None else None, C.c_void_p(pin), C.c_void_p(nin),
+            C.c_uint32(n_points), C.c_int32(1 if dev else 0), T.ctypes.data_as(C.c_void_p), C.c_uint32(T.size // 12), C.byref(res),
+            scores.ctypes.data_as(C.c_void_p) if return_scores else None))
+        del keep
+        out = global_result_dict(res)
+        return (out, scores) if return_scores else out
+
+    def debug_set_score_chunk(self, chunk_points):
+        """Tests: the samples a chunk of ScorePoses may hold (smx_distscene_debug_set_score_chunk; the library's 2^22 bounds the
+        workspace), so that a small case crosses chunk edges."""
+        _lib.check(_lib.load().smx_distscene_debug_set_score_chunk(self._h, C.c_uint32(int(chunk_points))))
+
+    def debug_global_timings(self):
+        """Milliseconds of the last ScorePoses / RegisterGlobal: the score phase, then move, query and score kernel of its last
+        chunk, then select, refine and rescore of the last RegisterGlobal (0 after a bare ScorePoses)."""
+        out = (C.c_float * GLOBAL_PHASES)()
+        _lib.check(_lib.load().smx_distscene_debug_global_timings(self._h, out, C.c_int32(GLOBAL_PHASES)))
+        return dict(zip(("score", "move", "query", "score_kernel", "select", "refine", "rescore"), [float(v) for v in out]))
 
     def debug_timings(self):
         """Milliseconds of the last build (mark, index, first) and of the last query (query, stats)."""

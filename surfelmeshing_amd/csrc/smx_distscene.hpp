@@ -55,6 +55,21 @@ struct RegisterWork {
   PhaseStamps<4> last;                     // move, query, reduce, solve of its last iteration
 };
 
+// What smx_distscene_score_poses and smx_distscene_register_global keep with the scene (glue and kernels: smx_global.hip).  Both
+// calls are synchronous, so nothing reads a block that goes; the association runs in the query's workspace.
+struct GlobalWork {
+  DevBuf<float> pts;                       // staging when the caller's points are host memory
+  DevBuf<float> poses;                     // [P][12] every candidate pose of a call
+  DevBuf<float> moved;                     // [chunk poses][m][3] a chunk's samples as its poses moved them: the query's points
+  DevBuf<uint32_t> nearest;                // [chunk poses][m] the query's outputs
+  DevBuf<float> distance;
+  DevBuf<smx_pose_score> scores;           // [P]
+  uint32_t chunk_points = 1u << 22;        // samples a chunk may hold (smx_distscene_debug_set_score_chunk)
+  PhaseStamps<1> whole;                    // the score phase of the last call
+  PhaseStamps<3> last;                     // move, query, score kernel of its last chunk
+  float host_ms[3] = {0.0f, 0.0f, 0.0f};   // select, refine, rescore of the last smx_distscene_register_global, on the host's clock
+};
+
 constexpr int kDsceneBuildWords = 32;                        // the build's counters: the grid's words; device_bytes counts 32
 static_assert(kTgWords <= kDsceneBuildWords, "the build's counters");
 #endif
@@ -78,6 +93,7 @@ struct smx_distscene_s {
   float max_distance = 0.0f;                       // the bound of the build: a query asks for no more
   smx::DistQueryWork query;                        // a query's, and a registration's
   smx::RegisterWork reg;                           // a registration's own
+  smx::GlobalWork glob;                            // the pose scores' own
   smx::PhaseStamps<3> build_stamps;                // mark, index, first of the last build
   smx::PhaseStamps<2> query_stamps;                // query, stats of the last query
 };

@@ -260,6 +260,46 @@ def register_points(scene, points, normals=None, T_init=None, params=None, strea
     return scene.Register(stream, points, normals, T_init, params if params is not None else register_params())
 
 
+def pose_lattice(k, centre, anchors):
+    """The candidate poses of register_global, [N_k * A, 3, 4] float32 (api.pose_lattice): every rotation of the integer-quaternion
+    lattice of order k about `centre` (points' frame), placed on every one of `anchors` ([A,3], scene's frame).  N_k = 40, 272,
+    888, 2080 for k = 1 .. 4; the largest angle from a rotation to the nearest of them, sampled: 60, 41, 28, 23 degrees."""
+    from .api import pose_lattice as make
+    return make(k, centre, anchors)
+
+
+def register_global(scene, points, normals=None, k=3, anchors=None, centre=None, n_starts=8, params=None, robust=None, stride=1,
+                    max_distance=0.0, reject_rim=False, min_matched_fraction=0.5, mesh=None, n_anchors=8, seed=0, stream=None,
+                    return_scores=False):
+    """Aligns `points` ([P,3], their own frame; a numpy array or a device tensor, as register_points takes them) to the mesh a
+    DistanceScene holds WITHOUT a start pose: the poses of pose_lattice(k, centre, anchors) are scored in one pass over the scene,
+    the n_starts cheapest are refined by register_points' ICP (params, robust as there) and the cheapest result wins: the dict of
+    DistanceScene.RegisterGlobal, whose result["scene_T_points"] is the pose found and whose found says whether to believe it.
+    centre: None = the float64 mean of the finite points.  anchors ([A,3], scene's frame): where that centre may lie -- required,
+    unless mesh=(rec, triangles) is given: then n_anchors points of sample_mesh(rec, triangles, n_anchors, seed) are used.
+    stride, max_distance (0 = the scene's bound) and reject_rim are the score's; at most 2^16 samples are scored per pose, so a
+    large point set needs a stride.  ValueError on what the library would refuse."""
+    import numpy as np
+    from .api import _device_address, score_params
+    if centre is None:
+        host = points.detach().cpu().numpy() if _device_address(points) is not None else np.asarray(points)
+        host = np.asarray(host, np.float64).reshape(-1, 3)
+        ok = np.all(np.isfinite(host), axis=1)
+        if not np.any(ok):
+            raise ValueError("no finite point to take the centre from")
+        centre = host[ok].mean(axis=0)
+    if anchors is None:
+        if mesh is None:
+            raise ValueError("anchors is required unless mesh=(rec, triangles) is given")
+        rec, triangles = mesh
+        drawn = sample_mesh(rec, triangles, n_anchors, seed, stream=stream)[0]
+        anchors = np.asarray(drawn.cpu().numpy() if _device_address(drawn) is not None else drawn, np.float64).reshape(-1, 3)
+        anchors = anchors[np.all(np.isfinite(anchors), axis=1)]
+    poses = pose_lattice(k, centre, anchors)
+    return scene.RegisterGlobal(stream, points, normals, poses, params if params is not None else register_params(), robust,
+                                score_params(stride, max_distance, reject_rim), n_starts, min_matched_fraction, return_scores)
+
+
 def mesh_distance(rec, triangles, points, max_distance, cell_size=0.0, signed=False, return_closest=False, stream=None, scene=None):
     """For every point its closest triangle of `triangles` within max_distance, on the device: (nearest, distance[, closest],
     stats) as CUDASurfelReconstruction.MeshDistance returns them.  With scene (build_distance_scene) the points are measured

@@ -11,6 +11,7 @@ tools/compact_bench.py grows).
     python tools/mesh_bench.py --raycast WxH [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --raycast WxH --scene [--decimate METRES] [--json OUT] [--txt OUT]
     python tools/mesh_bench.py --register POINTS [--register_robust] [--distance METRES[,METRES...]] [--decimate METRES] [--json OUT] [--txt OUT]
+    python tools/mesh_bench.py --register_global K[,M] [--distance METRES] [--decimate METRES] [--json OUT] [--txt OUT]
 
 Times whole calls with device events around them (the call is synchronous: the window includes its host round trips)
 and, from the library's own timed events (smx_recon_debug_mesh_timings), the index build, the list query, the star
@@ -82,6 +83,11 @@ scene's plain query of the same points at the bound.  Writes profiles/register_b
 the plain call and the plain build in the same process: the rim build against the scene build it extends, the robust call (rim
 rejection and Tukey weights at bound, bound / 2, bound / 4) against the plain call of the same points, the robust reduce kernel
 against the plain one in the last iteration.  Writes profiles/register_robust_bench.{txt,json}.
+--register_global K[,M] measures smx_distscene_register_global: 4096 area samples of the full mesh, put into a frame
+100 degrees and 0.44 m away, are searched for with the lattice of order K on one anchor and M starts (8), against a scene of the
+full mesh and of the decimated one: the score phase and its move, query and score kernel by the library's events, the scene's
+plain query of the identical P m moved points in the same process, the whole call with select, refine and rescore, and how far the
+winner lies from the truth.  Writes profiles/register_global_bench.{txt,json}.
 
 --raycast WxH --scene measures smx_rayscene on the same rays and the same two meshes (the decimated one at the
 first --decimate cell, 0.05 m by default), everything in one process: smx_recon_raycast_mesh re-measured first (its call, its
@@ -129,6 +135,8 @@ ap.add_argument("--register", type=int, default=0, metavar="POINTS", help="measu
                                                                            "against the full and the decimated mesh at the --distance bounds")
 ap.add_argument("--register_robust", action="store_true", help="with --register: the robust call (rim rejection and Tukey weights) and the rim build, "
                                                                "timed beside the plain call and the plain build")
+ap.add_argument("--register_global", default=None, metavar="K[,M]", help="measure smx_distscene_register_global: the lattice of order K, M starts (8), "
+                                                                          "against the full and the decimated mesh at the first --distance bound (0.05)")
 ap.add_argument("--label", default="this build", help="with --components: the name of the build under test in the output")
 args = ap.parse_args()
 sys.argv = [sys.argv[0]]
@@ -1055,6 +1063,137 @@ def register_main():
     nn.close()
 
 
+GLOBAL_PHASES = ("score", "move", "query", "score_kernel", "select", "refine", "rescore")
+
+
+def register_global_main():
+    """--register_global K[,M]: smx_distscene_register_global beside the scene's plain query of the identical moved points in one
+    process."""
+    import ctypes as C
+    _lib.require_gpu()
+    L = _lib.load()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+    spec = [int(v) for v in args.register_global.split(",")]
+    k, n_starts = spec[0], spec[1] if len(spec) > 1 else 8
+    md = float(args.distance.split(",")[0]) if args.distance else 0.05
+    cell = float(args.decimate.split(",")[0]) if args.decimate else 0.05
+    wl = bench.Workload(api, 640, 480, args.target, args.target + args.target // 10, 0x5EED0001, 0.0)
+    t0 = time.time()
+    wl.grow(False)
+    rec = wl.pipe.reconstruction
+    n, live = rec.surfels_size(), rec.surfel_count()
+    say("# grown in %.1f s: %d slots, %d live" % (time.time() - t0, n, live))
+    from surfelmeshing_amd import meshing, synth
+    nn = api.SurfelNeighborIndex()
+    p = _lib.MeshParams.defaults()
+    cap = 3 * n
+    dtri, dout = api.CUDABuffer(1, 3 * cap, np.uint32), api.CUDABuffer(1, 3 * cap, np.uint32)
+    T, mst = C.c_uint32(0), _lib.MeshStats()
+    _lib.check(L.smx_recon_triangulate(rec._h, None, nn._h, C.c_float(0.05), C.byref(p), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(cap),
+                                       C.c_int32(1), C.byref(T), C.byref(mst)))
+    T_in = T.value
+    Tc, dst = C.c_uint32(0), _lib.DecimateStats()
+    _lib.check(L.smx_recon_decimate_mesh(rec._h, None, C.c_float(cell), C.c_void_p(dtri.ToCUDA().address), C.c_uint32(T_in),
+                                         C.c_void_p(dout.ToCUDA().address), C.c_uint32(T_in), None, C.c_int32(1), C.byref(Tc), C.byref(dst)))
+    # 4096 area samples of the full mesh (the part of the room the map holds), seen from a frame 100 degrees and 0.44 m away
+    room = meshing.sample_mesh(rec, _DeviceArray(dtri, 3 * T_in), 4096, 7)[0].cpu().numpy().astype(np.float64)
+    room = np.ascontiguousarray(room[np.all(np.isfinite(room), axis=1)])
+    axis = np.array([0.48, -0.6, 0.64])
+    a = np.deg2rad(100.0)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    R_true = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    t_true = np.array([0.3, -0.2, 0.25])
+    pts = np.ascontiguousarray((room - t_true) @ R_true, np.float32)             # (R^T (p - t) row by row)
+    m = pts.shape[0]
+    centre = pts.astype(np.float64).mean(axis=0)
+    anchors = (R_true @ centre + t_true).reshape(1, 3)                           # (the position is known roughly: one anchor)
+    poses = api.pose_lattice(k, centre, anchors)
+    P = poses.shape[0]
+    tp = torch.from_numpy(pts).cuda()
+    # the identical P m moved points for the plain query, by the move's own float32 expression
+    Tt = torch.from_numpy(poses).cuda()
+    x, y, z = (tp[None, :, c] for c in range(3))
+    moved = torch.stack([((Tt[:, r, 0, None] * x + Tt[:, r, 1, None] * y) + Tt[:, r, 2, None] * z) + Tt[:, r, 3, None] for r in range(3)], dim=2).reshape(-1, 3).contiguous()
+    dnear, ddist = api.CUDABuffer(1, P * m, np.uint32), api.CUDABuffer(1, P * m, np.float32)
+    say("# %d area samples of the full mesh in a frame 100 degrees and 0.44 m away, the k = %d lattice (%d poses) on one anchor, %d starts, gate %g m, "
+        "the default schedule; P m = %d moved points; medians of %d repetitions after one that allocates" % (m, k, P, n_starts, md, P * m, args.reps))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def spread(v):
+        return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+    def show(s):
+        return "%.3f ms (min %.3f, max %.3f)" % (s["median"], s["min"], s["max"])
+    prm = meshing.register_params()
+    out_rows = []
+    for what, src, n_in in (("full mesh", dtri, T_in), ("decimated at %g m" % cell, dout, Tc.value)):
+        tri = _DeviceArray(src, 3 * n_in)
+        with rec.BuildDistanceScene(None, tri, md) as scene:
+            # ---- the scene's plain query of the identical moved points at the gate
+            qp, qst = api.distance_params(md), _lib.DistanceStats()
+            qs, qph = [], []
+            for _ in range(args.reps + 1):
+                qs.append(timed(lambda: _lib.check(L.smx_distscene_query(
+                    scene._h, None, C.byref(qp), C.c_void_p(moved.data_ptr()), C.c_uint32(P * m), C.c_void_p(dnear.ToCUDA().address),
+                    C.c_void_p(ddist.ToCUDA().address), None, C.c_int32(1), C.byref(qst))))[0])
+                qph.append(scene.debug_timings()["query"])
+            # ---- the scores alone, then the whole search
+            sc_ms, sc_ph, first = [], [], None
+            for _ in range(args.reps + 1):
+                ms, got = timed(lambda: scene.ScorePoses(None, tp, poses, api.score_params(1, md)))
+                sc_ms.append(ms)
+                sc_ph.append(scene.debug_global_timings())
+                first = got if first is None else first
+                assert got.tobytes() == first.tobytes(), "two calls gave different bytes"
+            whole, phs, res = [], [], None
+            for _ in range(args.reps + 1):
+                ms, res = timed(lambda: scene.RegisterGlobal(None, tp, None, poses, prm, score=api.score_params(1, md), n_starts=n_starts))
+                whole.append(ms)
+                phs.append(scene.debug_global_timings())
+            ph = {key: spread([q[key] for q in phs[1:]]) for key in GLOBAL_PHASES}
+            sph = {key: spread([q[key] for q in sc_ph[1:]]) for key in GLOBAL_PHASES[:4]}
+            own = sph["move"]["median"] + sph["score_kernel"]["median"]
+            plain = float(np.median(qph[1:]))
+            Tw = res["result"]["scene_T_points"].astype(np.float64)
+            angle = float(np.degrees(np.arccos(np.clip((np.trace(Tw[:, :3].T @ R_true) - 1) / 2, -1, 1))))
+            shift = float(np.linalg.norm(Tw[:, 3] - t_true))
+            costs = sorted(s["cost_after"] for s in res["starts"])
+            row = {"input": what, "triangles_in": n_in, "points": m, "poses": P, "moved_points": P * m, "n_starts": n_starts, "gate": md, "reps": args.reps,
+                   "plain_query_ms": spread(qs[1:]), "plain_query_phase_ms": spread(qph[1:]), "plain_query_matched": int(qst.n_matched),
+                   "score_call_ms": spread(sc_ms[1:]), "score_phases_ms": sph, "own_kernels_ms": own, "score_phase_over_plain_query_plus_own": sph["score"]["median"] / max(plain + own, 1e-9),
+                   "call_ms": spread(whole[1:]), "phases_ms": ph, "found": res["found"], "winner_rank": res["winner_rank"],
+                   "winner_status": res["result"]["status"], "angle_from_truth_deg": angle, "shift_from_truth_m": shift,
+                   "cost_after_winner": costs[0], "cost_after_runner_up": costs[1] if len(costs) > 1 else None, "starts": res["starts"],
+                   "cell_size_used": scene.stats["cell_size_used"]}
+            out_rows.append(row)
+            say("%s, gate %g m, %d triangles: score call %s | score phase by the library's events %s = move %s + query %s + score kernel %s | the scene's plain "
+                "query phase of the identical %d points %.3f ms (the whole plain query %s, %d matched): the score phase is %.2f x (plain query + move + score "
+                "kernel = %.3f ms) | whole search %s: select %s, refine %s, rescore %s | found %d, winner rank %d (status %d), %.4f degrees and %.3f mm from the "
+                "truth, cost after %d against the runner-up's %s" % (
+                    what, md, n_in, show(spread(sc_ms[1:])), show(sph["score"]), show(sph["move"]), show(sph["query"]), show(sph["score_kernel"]), P * m, plain,
+                    show(spread(qs[1:])), int(qst.n_matched), row["score_phase_over_plain_query_plus_own"], plain + own, show(spread(whole[1:])), show(ph["select"]),
+                    show(ph["refine"]), show(ph["rescore"]), res["found"], res["winner_rank"], res["result"]["status"], angle, 1e3 * shift, costs[0],
+                    costs[1] if len(costs) > 1 else "-"))
+    res = {"metric": "register_global_call_ms", "slots": n, "live": live, "triangles_in": T_in, "rows": out_rows}
+    with open(args.json or os.path.join(ROOT, "profiles", "register_global_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.txt or os.path.join(ROOT, "profiles", "register_global_bench.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    nn.close()
+
+
 SAMPLE_PHASES = ("weights", "scan", "draw")
 COMPARE_PHASES = ("a_to_b.sample", "a_to_b.distance", "a_to_b.sums", "b_to_a.sample", "b_to_a.distance", "b_to_a.sums")
 
@@ -1588,4 +1727,4 @@ def main():
 
 
 if __name__ == "__main__":
-    register_robust_main() if (args.register and args.register_robust) else register_main() if args.register else distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()
+    register_global_main() if args.register_global else register_robust_main() if (args.register and args.register_robust) else register_main() if args.register else distscene_main() if (args.distance and args.scene) else sample_main() if (args.sample or args.compare) else (rayscene_main() if args.scene else raycast_main()) if args.raycast else distance_main() if args.distance else fill_main() if args.fill is not None else components_main() if args.components else decimate_main() if args.decimate else update_main() if args.update else main()

@@ -8,6 +8,7 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh_min_component TRIANGLES] [--mesh_min_extent METRES] [--mesh_keep_largest K]
                               [--mesh_fill_holes EDGES [--mesh_fill_min_angle DEG] [--mesh_fill_max_angle DEG]]
                               [--mesh_eval METRES [--mesh_eval_frames N]] [--mesh_eval_register] [--mesh_eval_rays] [--mesh_eval_rays_frames N]
+                              [--mesh_eval_register_global [--mesh_eval_global_k K] [--mesh_eval_global_anchors A] [--mesh_eval_global_starts M]]
                               [--mesh_compare_samples N [--mesh_compare_distance METRES]]
                               [--export_mesh_samples FILE.ply --mesh_samples N]
                               [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
@@ -41,6 +42,11 @@ status, the rotation and translation recovered (the drift) and the surface error
 ground-truth points reach beyond the reconstructed surface, and the plain call is pulled by the matches on the mesh's edge.
 Per frame a second line, "robustly registered frame ...", with the two counts of the last iteration (matches rejected on the
 rim, samples down-weighted or rejected by the kernel), and a second total.
+--mesh_eval_register_global [--mesh_eval_global_k K --mesh_eval_global_anchors A --mesh_eval_global_starts M] (with --mesh_eval,
+--synthetic and --mesh or --mesh_every) takes the ground-truth points of each evaluated frame in the CAMERA's frame, as if the
+camera pose were lost, and searches the final mesh's scene for them without a start pose (smx_distscene_register_global: the
+lattice of order K about the points' mean on A area samples of the mesh, M starts): one line per frame -- found or not, the pose
+error against the true camera pose, the winner's rank, the cost margin to the runner-up, the milliseconds -- and a total.
 --mesh_compare_samples N prints, for every stage of the chain that was asked for (cleaning, hole filling, decimation), the
 two-sided surface error between the mesh before and after it on N area-weighted samples per side (smx_recon_compare_meshes).
 --export_mesh_samples FILE.ply with --mesh_samples N writes N such samples of the final mesh with the face normals.
@@ -224,6 +230,14 @@ def parse_args(argv=None):
                     help="with --mesh_eval_register: also run the robust call with this weight kernel (needs --mesh_eval_register_scale)")
     ap.add_argument("--mesh_eval_register_scale", type=float, default=None, metavar="METRES",
                     help="the kernel's scale c, 1e-6 .. 16 metres")
+    ap.add_argument("--mesh_eval_register_global", action="store_true",
+                    help="with --mesh_eval METRES --synthetic N --mesh: take the ground-truth points of each evaluated frame in the CAMERA's "
+                         "frame, as if its pose were lost, and search the final mesh's scene for them without a start pose "
+                         "(smx_distscene_register_global): found or not, the pose error against the true camera pose, the winner's rank, "
+                         "the cost margin to the runner-up, the milliseconds")
+    ap.add_argument("--mesh_eval_global_k", type=int, default=3, metavar="K", help="the order of the pose lattice, 1 .. 8 (3: 888 rotations)")
+    ap.add_argument("--mesh_eval_global_anchors", type=int, default=8, metavar="A", help="anchors: area samples of the final mesh")
+    ap.add_argument("--mesh_eval_global_starts", type=int, default=8, metavar="M", help="starts refined, 1 .. 64")
     ap.add_argument("--mesh_eval_rays", action="store_true",
                     help="with --synthetic N --mesh: cast rays (smx_recon_raycast_mesh) from the last integrated frame's camera "
                          "towards its noise-free surface points (every 8th pixel) and print the share of rays with a hit and the "
@@ -303,6 +317,10 @@ def parse_args(argv=None):
         ap.error("--mesh_eval_register_kernel huber|tukey and --mesh_eval_register_scale METRES go together")
     if args.mesh_eval_register_scale is not None and not (1e-6 <= args.mesh_eval_register_scale <= 16.0):
         ap.error("--mesh_eval_register_scale needs 1e-6 .. 16 metres")
+    if args.mesh_eval_register_global and not (args.mesh_eval is not None and args.synthetic and (args.mesh or args.mesh_every > 0)):
+        ap.error("--mesh_eval_register_global needs --mesh_eval METRES, --synthetic N (the ground-truth surface) and --mesh or --mesh_every")
+    if not (1 <= args.mesh_eval_global_k <= 8 and 1 <= args.mesh_eval_global_anchors <= 64 and 1 <= args.mesh_eval_global_starts <= 64):
+        ap.error("--mesh_eval_global_k needs 1 .. 8, --mesh_eval_global_anchors and --mesh_eval_global_starts 1 .. 64")
     args.mesh_eval_register_robust = None
     if args.mesh_eval_register_reject_rim or args.mesh_eval_register_kernel != "none":
         args.mesh_eval_register_robust = dict(kernel=args.mesh_eval_register_kernel, scale=args.mesh_eval_register_scale or 0.0,
@@ -379,6 +397,26 @@ def format_register_total(figs):
     mean = lambda v: float(np.mean(v)) if len(v) else 0.0                                         # noqa: E731
     return "registered %d frames: %d solved, mean %.3f mrad and %.3f mm from the identity; surface error %.3f -> %.3f mm mean" % (
         len(figs), len(ok), mean([g["mrad"] for g in ok]), mean([g["mm"] for g in ok]), mean([g["mean"][0] for g in ok]), mean([g["mean"][1] for g in ok]))
+
+
+def global_register_figures(out, R, t, call_ms, timings):
+    """What --mesh_eval_register_global prints of one frame: found, the winner's status and rank, the angle (degrees) and length
+    (mm) between the pose found and the true camera pose (R, t), the winner's cost after refinement and the runner-up's, and the
+    milliseconds of the call with the library's own phases."""
+    T = np.asarray(out["result"]["scene_T_points"], np.float64).reshape(3, 4)
+    c = 0.5 * (np.trace(T[:, :3].T @ np.asarray(R, np.float64)) - 1.0)
+    costs = sorted(st["cost_after"] for st in out["starts"])
+    return dict(found=int(out["found"]), status=int(out["result"]["status"]), rank=int(out["winner_rank"]), starts=int(out["n_starts_run"]),
+                deg=float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0)))), mm=1e3 * float(np.linalg.norm(T[:, 3] - np.asarray(t, np.float64))),
+                cost=int(costs[0]), runner_up=int(costs[1]) if len(costs) > 1 else int(costs[0]), call_ms=float(call_ms), timings=dict(timings))
+
+
+def format_global_register_line(f, fig):
+    tm = fig["timings"]
+    return ("globally registered frame %d: %s, status %d, winner rank %d of %d, %.3f degrees and %.3f mm from the true camera pose; cost %d, "
+            "runner-up %d (margin %d); %.1f ms: score %.2f, select %.2f, refine %.2f, rescore %.2f" % (
+                f, "found" if fig["found"] else "NOT found", fig["status"], fig["rank"], fig["starts"], fig["deg"], fig["mm"], fig["cost"], fig["runner_up"],
+                fig["runner_up"] - fig["cost"], fig["call_ms"], tm["score"], tm["select"], tm["refine"], tm["rescore"]))
 
 
 def format_point_eval(summary, what, head="scene points"):
@@ -611,6 +649,24 @@ def main():
         print(format_register_total(figs))
         if robust is not None:
             print("robustly " + format_register_total(robust_figs))
+    if args.mesh_eval_register_global:
+        from surfelmeshing_amd import meshing
+        half_ = args.outlier_filtering_frame_count // 2
+        last = n - half_ - 1
+        first = last - args.mesh_eval_frames + 1 if args.mesh_eval_frames else args.start_frame + half_
+        figs = []
+        with meshing.build_distance_scene(rec, triangles, args.mesh_eval) as scene:
+            for f in range(max(first, args.start_frame + half_), last + 1):
+                R, t = s.pose64(f)
+                world = s.surface_points(f, 8).astype(np.float64)
+                pts = np.ascontiguousarray((world - t) @ R, np.float32)          # (the camera's frame: R^T (p - t) row by row)
+                stride = max(1, -(-pts.shape[0] // 4096))                        # (a few thousand samples score a pose)
+                t1 = time.time()
+                out = meshing.register_global(scene, pts, k=args.mesh_eval_global_k, n_starts=args.mesh_eval_global_starts, stride=stride,
+                                              mesh=(rec, triangles), n_anchors=args.mesh_eval_global_anchors, seed=f)
+                figs.append(global_register_figures(out, R, t, 1e3 * (time.time() - t1), scene.debug_global_timings()))
+                print(format_global_register_line(f, figs[-1]))
+        print("globally registered %d frames: %d found" % (len(figs), sum(g["found"] for g in figs)))
     if args.mesh_eval_rays:
         from surfelmeshing_amd import meshing
         half_ = args.outlier_filtering_frame_count // 2
