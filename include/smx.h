@@ -1866,6 +1866,81 @@ int smx_recon_render_mesh(smx_recon r, smx_stream s, const smx_mesh_render_param
  * k_mrast_large and k_mrast_resolve, by timed events on the call's stream.  Zeros before the first call. */
 int smx_recon_debug_mesh_render_timings(smx_recon r, float out_ms[3]);
 
+/* ---- merging another session's map into this one (not in the reference: its map comes from one camera stream) ----
+ * smx_recon_merge_map puts the surfels of `src` into `dst` under the pose dst_T_src (row-major 3x4, as smx_distscene_register
+ * and its relatives return it): a source surfel that finds a compatible surfel of dst is dropped (KEEP_DST) or blended into
+ * it (BLEND), every other one is appended.  Integers and float32 expressions only, each evaluated as written (no
+ * contraction); rows are those of SURVEY.md Appendix A.  "dst as it stood" = dst before the call: all matching is against
+ * that, so the result does not depend on any order of writes, and two calls give the same bytes.
+ * 1. Live.  Source slot i < surfels_size(src) is live iff !(RadiusSquared_i < 0) (a NaN radius is live).
+ * 2. Move.  x' = ((R00 x + R01 y) + R02 z) + t0 and likewise y', z' (the move of smx_distscene_register), applied to the raw
+ *    position (rows 0-2), to the smooth position (rows 3-5), and without t to the normal (rows 8-10).  A live slot with a
+ *    non-finite word among the nine moved ones is BAD: neither matched nor appended, counted in n_bad.
+ * 3. Candidates.  The index is smx_recon_build_neighbor_index(dst, s, nn, cell_size): dst's smooth positions, merged slots
+ *    left out.  The candidates of i are smx_nn_query_batch's answer for the moved smooth position with r2 =
+ *    radius_factor_squared * RadiusSquared_i and k: up to k slots of dst, ascending by (dist^2, index).
+ * 4. Match.  m(i) = the first candidate d with (n'.x N_d.x + n'.y N_d.y) + n'.z N_d.z >= cos_max, N_d from dst as it stood,
+ *    cos_max = (float)cos((double)max_normal_angle_deg * (pi / 180)) as smx_recon_track forms it.  Without such a candidate i
+ *    is unmatched; an unmatched i whose list was full (count == k) is counted in n_saturated as well: a compatible surfel may
+ *    lie behind the k nearest, raise k if that number matters.
+ * 5. Append.  The unmatched live slots that are not BAD take the slots old_size + rank of dst, in ascending order of i.
+ *    old_size + n_appended > max_surfel_count(dst): SMX_ERR_INVALID_ARGUMENT, dst byte for byte unchanged, stats filled (so
+ *    that the caller sees the room needed).  Rows of an appended slot: 0-5 and 8-10 the moved words; 6, 7 copied; 11-16 and
+ *    23 zero; 17, 18 = frame_index; 24 the 32 colour bits copied; 19-22 the source's links through the map: a link to an
+ *    appended source slot becomes that slot's new index, every other one (invalid, or to a merged, BAD or matched slot)
+ *    0xFFFFFFFF.  links_dropped = the links of appended slots that were not 0xFFFFFFFF in src and are now.
+ * 6. SMX_MERGE_KEEP_DST.  Matched source slots leave no trace in dst.
+ * 7. SMX_MERGE_BLEND.  For a slot d of dst with the matched sources i1 < i2 < ...: start from dst's raw position P, smooth
+ *    position S, normal N, c = row 6, r = row 7, and take the sources in ascending order: w = Confidence_i, W = c + w;
+ *    !(W > 0): this source changes nothing; else a = c / W, b = w / W, P = (a P) + (b P'), S = (a S) + (b S'), M = (a N) +
+ *    (b n') per component, len2 = (M.x M.x + M.y M.y) + M.z M.z, N = M / sqrtf(len2) per component if len2 > 0 (else N stays),
+ *    r = fminf(r, RadiusSquared_i), c = fminf(W, confidence_cap).  Then rows 0-10 of d are written and row 18 = frame_index;
+ *    creation stamp, links and colour stay.  n_blended_dst = the number of such d.
+ * 8. src_to_dst (may be NULL; capacity >= surfels_size(src) entries; device pointer if on_device, host pointer otherwise):
+ *    m(i) for a matched slot, the new index for an appended one (told apart by >= old_size), 0xFFFFFFFF for dead and BAD
+ *    slots.  A triangle array over src goes through it as a mesh goes through compaction's old_to_new: a triangle that
+ *    loses a corner is dropped.
+ * 9. State.  Afterwards surfels_size(dst) = new_size and the merge count is unchanged; the derived frame-loop state is what
+ *    smx_recon_compact leaves (a superset of a state upload's resets), except that with delta tracking on exactly the
+ *    appended and blended slots are marked; the next smx_recon_integrate may use any frame_index.  nn is stale after the call
+ *    (it indexes dst as it stood).  Scenes are snapshots and are unaffected.  src is read only.
+ * Calling rules: synchronous like smx_recon_compact; ordered behind everything enqueued on both objects (the pipelined
+ *   regulariser of each included).  Refused with SMX_ERR_INVALID_ARGUMENT, nothing launched and nothing written: a NULL
+ *   pointer other than src_to_dst or stats, src == dst, objects on different devices, k outside 1..64, frame_index == 0,
+ *   cell_size or radius_factor_squared not > 0, an angle outside 0..180, a non-finite dst_T_src, an unknown mode, a NaN
+ *   confidence_cap, a capacity below surfels_size(src).  An empty src is valid and changes nothing; an empty dst is valid
+ *   and appends everything.  The workspace belongs to dst, is counted by smx_debug_live_allocations and reached by
+ *   smx_debug_fail_allocation; every allocation comes before the first write to dst, so a failed one leaves dst unchanged.
+ * Not built: colour blending, links between the two sessions' surfels, de-duplication inside src, a merge that keeps the
+ *   source's stamps. */
+enum { SMX_MERGE_KEEP_DST = 0, SMX_MERGE_BLEND = 1 };
+#define SMX_MERGE_PHASES 7
+typedef struct {            /* smx_merge_params_default() fills the defaults */
+  float   cell_size;                 /* of the neighbour index built over dst; > 0; default 0.05 */
+  float   radius_factor_squared;     /* ball of a source surfel: r2 = factor * its RadiusSquared; default 1.0f */
+  float   max_normal_angle_deg;      /* default 30; cosine formed on the host as smx_recon_track forms it */
+  int32_t k;                         /* candidates looked at per source surfel, 1 .. 64; default 8 */
+  int32_t mode;                      /* SMX_MERGE_KEEP_DST = 0 | SMX_MERGE_BLEND = 1 */
+  float   confidence_cap;            /* BLEND only; default FLT_MAX */
+  uint32_t frame_index;              /* >= 1: stamp of appended and blended slots; default 1 */
+} smx_merge_params;
+typedef struct {
+  uint32_t n_src_slots, n_src_live, n_bad, n_matched, n_appended, n_blended_dst, n_saturated, links_dropped;
+  uint32_t old_size, new_size;
+} smx_merge_stats;
+int smx_merge_params_default(smx_merge_params* out);
+int smx_recon_merge_map(smx_recon dst, smx_stream s, smx_nn nn, smx_recon src, const float dst_T_src[12],
+                        const smx_merge_params* p, uint32_t* src_to_dst, uint32_t capacity, int32_t on_device,
+                        smx_merge_stats* stats);
+/* Tools: milliseconds of dst's last smx_recon_merge_map call by timed events on its stream: out_ms[0] the whole call, then
+ * the SMX_MERGE_PHASES phases index build, move, query + select (all chunks), number, append, blend, finish; at most
+ * `capacity` values are written.  The waits of the call's read-backs fall into the phase they end.  Zeros before the first
+ * call and after a call that failed. */
+int smx_recon_debug_merge_timings(smx_recon dst, float* out_ms, int32_t capacity);
+/* Tests: the queries of a merge run in chunks of chunk_queries source slots (0 = the default, 2^22), which bounds the
+ * [chunk][k] candidate workspace; results must not depend on it. */
+int smx_recon_debug_set_merge_chunk(smx_recon dst, uint32_t chunk_queries);
+
 /* ---- benchmark input generator (not part of the reference's interface) ----
  * Renders one frame of the synthetic room stream into device buffers:
  * depth u16 = round(depth_scaling * z) with sigma = noise_sigma * z^2 noise and coherent 8x8

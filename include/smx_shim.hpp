@@ -649,6 +649,25 @@ class CUDASurfelReconstruction {
     SMX_SHIM_CHECK(smx_recon_compact(handle_, stream, old_to_new && n ? old_to_new->data() : nullptr, n, 0, nullptr,
                                      links_dropped));
   }
+  // Not in the reference: merges the map of `src` (read only, same device) into this one under dst_T_src (3x4 row-major, this
+  // <- src): matched source surfels are dropped or blended, the others appended (synchronous; see smx_recon_merge_map in
+  // smx.h).  src_to_dst (resized to src's slot count) receives each source slot's slot here or 0xFFFFFFFF; index: a
+  // neighbour index to rebuild and use (one is created for the call if null; stale afterwards); stats may be null and is
+  // filled also when the call throws for lack of room.
+  void MergeMap(cudaStream_t stream, CUDASurfelReconstruction& src, const float* dst_T_src, const smx_merge_params& params,
+                std::vector<u32>* src_to_dst = nullptr, smx_nn index = nullptr, smx_merge_stats* stats = nullptr) {
+    smx_nn nn = index;
+    if (!nn) SMX_SHIM_CHECK(smx_nn_create(-1, &nn));
+    u32 n = 0;
+    if (src_to_dst) {
+      n = src.surfels_size();
+      src_to_dst->resize(n);
+    }
+    const int rc = smx_recon_merge_map(handle_, stream, nn, src.handle_, dst_T_src, &params, src_to_dst && n ? src_to_dst->data() : nullptr, n, 0,
+                                       stats);
+    if (!index) (void)smx_nn_destroy(nn);
+    SMX_SHIM_CHECK(rc);
+  }
   // Not in the reference: triangulates the map as it stands on the device (smx_recon_triangulate in smx.h: a localized
   // Delaunay triangulation).  *triangles receives three slot indices per triangle, in the order smx.h describes.
   // index: a neighbour index to rebuild and use (one is created for the call if null); stats may be null.  Synchronous.

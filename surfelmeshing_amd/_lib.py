@@ -422,6 +422,34 @@ class GlobalResult(C.Structure):
                 ("reserved", C.c_int32), ("starts", GlobalStart * GLOBAL_MAX_STARTS)]
 
 
+class MergeParams(C.Structure):
+    """smx_merge_params: the index cell, the ball and the normal gate of the match, k, the mode and the stamp of smx_recon_merge_map."""
+    _fields_ = [("cell_size", C.c_float), ("radius_factor_squared", C.c_float), ("max_normal_angle_deg", C.c_float), ("k", C.c_int32),
+                ("mode", C.c_int32), ("confidence_cap", C.c_float), ("frame_index", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """smx_merge_params_default(), then any field by name."""
+        p = cls()
+        check(load().smx_merge_params_default(C.byref(p)))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+MERGE_MODES = {"keep": 0, "blend": 1}      # SMX_MERGE_KEEP_DST, SMX_MERGE_BLEND
+MERGE_PHASES = 7                           # SMX_MERGE_PHASES
+MERGE_PHASE_NAMES = ("whole", "build", "move", "query_select", "number", "append", "blend", "finish")
+
+
+class MergeStats(C.Structure):
+    """smx_merge_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_src_slots", "n_src_live", "n_bad", "n_matched", "n_appended", "n_blended_dst", "n_saturated",
+                                          "links_dropped", "old_size", "new_size")]
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -516,6 +544,7 @@ EXPORTS = [
     "smx_recon_set_timing_enabled", "smx_recon_counts", "smx_recon_get_stats", "smx_recon_set_stats_enabled",
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",
+    "smx_merge_params_default", "smx_recon_merge_map", "smx_recon_debug_merge_timings", "smx_recon_debug_set_merge_chunk",
     "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_track_params_default", "smx_recon_track", "smx_recon_debug_track_iterations", "smx_track_rgbd_params_default", "smx_recon_track_rgbd", "smx_recon_debug_track_rgbd_iterations", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
     "smx_recon_set_scan_mode", "smx_recon_debug_set_skip", "smx_recon_set_overlap", "smx_recon_integrate_hooks", "smx_recon_integrate_inputs_ready",
     "smx_nn_create", "smx_nn_destroy", "smx_nn_build", "smx_nn_query_batch", "smx_nn_query_self", "smx_nn_set_query_mode", "smx_nn_set_stats_enabled", "smx_nn_get_stats",

@@ -634,6 +634,34 @@ class DistanceScene:
         return dict(zip(("mark", "index", "first", "query", "stats"), [float(v) for v in out]))
 
 
+def merge_params(cell_size=0.05, radius_factor_squared=1.0, max_normal_angle_deg=30.0, k=8, mode="keep", confidence_cap=None,
+                 frame_index=1):
+    """smx_merge_params from keyword arguments: mode "keep" / "blend" (or 0 / 1); confidence_cap None = FLT_MAX.  ValueError on
+    what the library would refuse."""
+    if isinstance(mode, str):
+        if mode not in _lib.MERGE_MODES:
+            raise ValueError("mode must be one of %s" % ", ".join(_lib.MERGE_MODES))
+        mode = _lib.MERGE_MODES[mode]
+    cap = float(np.finfo(np.float32).max) if confidence_cap is None else float(confidence_cap)
+    if not (float(cell_size) > 0 and float(radius_factor_squared) > 0):
+        raise ValueError("cell_size and radius_factor_squared must be > 0")
+    if not 0.0 <= float(max_normal_angle_deg) <= 180.0:
+        raise ValueError("max_normal_angle_deg must be within 0 .. 180")
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be within 1 .. 64")
+    if int(mode) not in (0, 1):
+        raise ValueError("mode must be 0 (keep) or 1 (blend)")
+    if not 1 <= int(frame_index) <= 0xFFFFFFFF:
+        raise ValueError("frame_index must be >= 1")
+    if cap != cap:
+        raise ValueError("confidence_cap must not be NaN")
+    return _lib.MergeParams(cell_size, radius_factor_squared, max_normal_angle_deg, int(k), int(mode), cap, int(frame_index))
+
+
+def merge_stats_dict(st):
+    return {n: int(getattr(st, n)) for n, _ in _lib.MergeStats._fields_}
+
+
 def _device_address(a):
     """The device address of a device tensor (anything with is_cuda / data_ptr), None for everything else."""
     if getattr(a, "is_cuda", False) and hasattr(a, "data_ptr"):
@@ -1250,6 +1278,50 @@ class CUDASurfelReconstruction:
         _lib.check(_lib.load().smx_recon_compact(self._h, _sv(stream), ptr, C.c_uint32(cap), C.c_int32(0),
                                                  C.byref(new_size), C.byref(dropped)))
         return old_to_new, int(new_size.value), int(dropped.value)
+
+    def MergeMap(self, stream, src, dst_T_src, index=None, return_map=False, **params):
+        """Not in the reference: merges the map of `src` (another CUDASurfelReconstruction on the same device, read only) into
+        this one under the pose dst_T_src ([3,4], this <- src, e.g. the scene_T_points of a registration): a source surfel
+        with a compatible surfel of this map among its k nearest is dropped (mode "keep") or blended into it ("blend"),
+        every other one is appended (smx_recon_merge_map; synchronous).  params: the keywords of merge_params, or
+        params=<MergeParams>.  index: a SurfelNeighborIndex to build and use (stale afterwards); one is created and closed
+        here if None.  Returns the statistics dict, or (dict, src_to_dst [uint32 per slot of src: its slot here, 0xFFFFFFFF
+        for dead and BAD slots]) with return_map.  Too little room for the appended slots raises SmxError and leaves the map
+        as it was; .last_merge_stats then says how much was needed."""
+        pod = params.pop("params", None)
+        if pod is None:
+            pod = merge_params(**params)
+        elif params:
+            raise ValueError("either params= or keywords")
+        if not isinstance(src, CUDASurfelReconstruction) or src is self:
+            raise ValueError("src must be another CUDASurfelReconstruction")
+        T = np.ascontiguousarray(np.asarray(dst_T_src, np.float32).reshape(12))
+        own = index is None
+        nn = SurfelNeighborIndex(self._device_id) if own else index
+        try:
+            s2d = np.empty(src._counts_on(stream)[1], np.uint32) if return_map else None
+            st = _lib.MergeStats()
+            rc = _lib.load().smx_recon_merge_map(
+                self._h, _sv(stream), nn._h, src._h, T.ctypes.data_as(C.c_void_p), C.byref(pod),
+                s2d.ctypes.data_as(C.c_void_p) if s2d is not None and s2d.size else None, C.c_uint32(s2d.size if s2d is not None else 0),
+                C.c_int32(0), C.byref(st))
+            self.last_merge_stats = merge_stats_dict(st)
+            _lib.check(rc)
+            return (self.last_merge_stats, s2d) if return_map else self.last_merge_stats
+        finally:
+            if own:
+                nn.close()
+
+    def debug_merge_timings(self):
+        """Milliseconds of the last MergeMap into this object by the library's events: {whole, build, move, query_select, number,
+        append, blend, finish}."""
+        out = (C.c_float * (_lib.MERGE_PHASES + 1))()
+        _lib.check(_lib.load().smx_recon_debug_merge_timings(self._h, out, C.c_int32(_lib.MERGE_PHASES + 1)))
+        return dict(zip(_lib.MERGE_PHASE_NAMES, (float(v) for v in out)))
+
+    def debug_set_merge_chunk(self, chunk_queries):
+        """Tests: MergeMap queries in chunks of this many source slots (0 = the default); results do not depend on it."""
+        _lib.check(_lib.load().smx_recon_debug_set_merge_chunk(self._h, C.c_uint32(int(chunk_queries))))
 
     def DeformByCreationFrame(self, stream, frame_T, reactivate=None, frame_index=0):
         """The loop-closure hook the reference describes but does not ship (README.md:152-176): surfels created at

@@ -376,14 +376,6 @@ k_deform_by_creation_frame(Surfels S, const float* __restrict__ frame_T, uint32_
   }
 }
 
-// The regulariser's accumulators and the merge marks, as a state upload leaves them.
-int reset_accumulators(smx_recon r, hipStream_t st) {
-  SMX_HIP(hipMemsetAsync(r->grad_acc, 0, 2 * r->S.pitch * sizeof(long long), st));
-  SMX_HIP(hipMemsetAsync(r->fb.count, 0, (size_t)r->nsegB * kCountStride * sizeof(uint32_t), st));
-  SMX_HIP(hipMemsetAsync(r->merge_flag, 0, r->S.pitch, st));
-  return SMX_OK;
-}
-
 // A temporary device buffer of one call: freed on every way out of the function, behind a synchronisation of the
 // stream whose work uses it.
 template <typename T>
@@ -397,6 +389,40 @@ struct DevTemp {
 };
 
 }  // namespace
+
+// The regulariser's accumulators and the merge marks, as a state upload leaves them.
+int smx::reset_accumulators(smx_recon r, hipStream_t st) {
+  SMX_HIP(hipMemsetAsync(r->grad_acc, 0, 2 * r->S.pitch * sizeof(long long), st));
+  SMX_HIP(hipMemsetAsync(r->fb.count, 0, (size_t)r->nsegB * kCountStride * sizeof(uint32_t), st));
+  SMX_HIP(hipMemsetAsync(r->merge_flag, 0, r->S.pitch, st));
+  return SMX_OK;
+}
+
+// After slots were rewritten, moved or added behind the frame loop's back (compaction, a map merge).
+// Derived state: everything a state upload resets (smx_recon_debug_upload_surfels), and the state an upload of the
+// same slots never had to care about, because these calls change WHICH SLOT a byte belongs to:
+//  * both copies of the double-buffered flag table: zeroed, the current one rebuilt from the records, and copied
+//    into the other (pass A of the next call reads the current copy; the other one is relied on through seg_streak);
+//  * seg_streak = 0: a streak >= 2 means "the copy written two calls ago already holds this segment's bytes";
+//  * hot_epoch = this call's epoch: every group counts as hot for the next calls (a group that looks hot only costs
+//    gathers; the hold-off of invalidate_derived keeps pass B unfiltered for two calls in any case, after which
+//    every mark it reads has been written after the call);
+//  * seg_targets = all groups: a superset of the groups a segment's links point into, which is all the skip test
+//    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
+// The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
+// has been read again, and reading a segment resets its streak).
+int smx::reset_derived_after_rewrite(smx_recon r, hipStream_t st) {
+  SMX_CALL(reset_accumulators(r, st));
+  SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
+  SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
+  SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
+  SMX_HIP(hipMemsetAsync(r->L.hot_epoch, (int)(r->L.epoch & 255u), (size_t)r->L.n_hot_groups + 64, st));
+  SMX_HIP(hipMemsetAsync(r->L.seg_targets, 0xFF, (size_t)r->nsegB * kBlockB * sizeof(uint16_t), st));
+  SMX_CALL(invalidate_derived(r, st));   // (rebuilds the current flag table)
+  uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
+  SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
+  return SMX_OK;
+}
 
 // ---- the render front end (smx_render.hpp) ----
 int smx::render_begin(smx_recon r, hipStream_t st, size_t px, bool caller_grows) {
@@ -726,30 +752,10 @@ int smx_recon_compact(smx_recon r, smx_stream s, uint32_t* old_to_new, uint32_t 
     SMX_LAUNCH_CHECK();
     SMX_CALL(release_staging(r, st));
   }
-  // Derived state: everything a state upload resets (smx_recon_debug_upload_surfels), and the state an upload of the
-  // same slots never had to care about, because compaction changes WHICH SLOT a byte belongs to:
-  //  * both copies of the double-buffered flag table: zeroed, the current one rebuilt from the records, and copied
-  //    into the other (pass A of the next call reads the current copy; the other one is relied on through seg_streak);
-  //  * seg_streak = 0: a streak >= 2 means "the copy written two calls ago already holds this segment's bytes";
-  //  * hot_epoch = this call's epoch: every group counts as hot for the next calls (a group that looks hot only costs
-  //    gathers; the hold-off of invalidate_derived keeps pass B unfiltered for two calls in any case, after which
-  //    every mark it reads has been written after the compaction);
-  //  * seg_targets = all groups: a superset of the groups a segment's links point into, which is all the skip test
-  //    of pass B needs (the first unfiltered pass rebuilds the bitmaps).
-  // The boxes and visible lists are dropped by invalidate_derived (count 0 = no box: no segment is culled before it
-  // has been read again, and reading a segment resets its streak).
   hipLaunchKernelGGL(k_compact_finish, dim3(1), dim3(64), 0, st, r->st, w.out.get());
-  SMX_CALL(reset_accumulators(r, st));
   if (r->L.dirty8)
     hipLaunchKernelGGL(k_compact_dirty, dim3(r->grid_surfels), b, 0, st, r->L.dirty8, (uint32_t)((size_t)r->nseg * kSeg), w.out.get());
-  SMX_HIP(hipMemsetAsync(r->flags_buf[0], 0, (size_t)r->nsegB * kSegB, st));
-  SMX_HIP(hipMemsetAsync(r->flags_buf[1], 0, (size_t)r->nsegB * kSegB, st));
-  SMX_HIP(hipMemsetAsync(r->L.seg_streak, 0, (size_t)r->nseg, st));
-  SMX_HIP(hipMemsetAsync(r->L.hot_epoch, (int)(r->L.epoch & 255u), (size_t)r->L.n_hot_groups + 64, st));
-  SMX_HIP(hipMemsetAsync(r->L.seg_targets, 0xFF, (size_t)r->nsegB * kBlockB * sizeof(uint16_t), st));
-  SMX_CALL(invalidate_derived(r, st));   // (rebuilds the current flag table)
-  uint8_t* other_flags = (r->L.flags8 == r->flags_buf[0]) ? r->flags_buf[1] : r->flags_buf[0];
-  SMX_HIP(hipMemcpyAsync(other_flags, r->L.flags8, (size_t)r->nsegB * kSegB, hipMemcpyDeviceToDevice, st));
+  SMX_CALL(reset_derived_after_rewrite(r, st));
   if (old_to_new && n)
     SMX_HIP(hipMemcpyAsync(old_to_new, w.map.get(), (size_t)n * sizeof(uint32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   uint32_t out[2] = {0, 0};

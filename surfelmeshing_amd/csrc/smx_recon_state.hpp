@@ -4,7 +4,7 @@
 // smx_recon_map.hip the map services that read or rewrite the finished map outside of it (row transfers, export,
 // viewer buffers, the splat render, neighbour and meshing glue, compaction, deformation); tracking, decimation, the
 // components, hole filling, the mesh distance, the rim, the ray cast, the mesh sampler and the mesh render live with their kernels in smx_track.hip, smx_decimate.hip,
-// smx_components.hip, smx_fill.hip, smx_distance.hip, smx_rim.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
+// smx_components.hip, smx_fill.hip, smx_merge.hip, smx_distance.hip, smx_rim.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
 // they all need: the attribute layout, the plain structs that are members of smx_recon_s, the object itself -- the
 // frame loop's state, then one workspace per service, each defined in the service's own header -- and the few host
 // helpers every entry point starts with.  Kernels stay in anonymous namespaces of the .hip files.
@@ -15,6 +15,7 @@
 #include "smx_decimate.hpp"
 #include "smx_distance.hpp"
 #include "smx_fill.hpp"
+#include "smx_merge.hpp"
 #include "smx_raycast.hpp"
 #include "smx_render.hpp"
 #include "smx_rim.hpp"
@@ -420,6 +421,7 @@ struct smx_recon_s {
   smx::RegisterMeshWork register_mesh;   // smx_recon_register_mesh
   smx::CompactWork compact;       // smx_recon_compact
   smx::CandidateWork candidates;  // smx_recon_neighbor_candidates
+  smx::MergeWork merge;           // smx_recon_merge_map (this object as the destination)
   smx::MeshWorkspace* mesh;       // smx_recon_triangulate / _update (created by the first call): lists, rings, counts, output staging
 };
 
@@ -438,5 +440,10 @@ int acquire_staging(smx_recon r, hipStream_t st, size_t floats);
 int release_staging(smx_recon r, hipStream_t st);
 // After surfel attributes were changed from outside the frame loop (state upload, compaction, deformation).
 int invalidate_derived(smx_recon r, hipStream_t st);
+// The regulariser's accumulators and the merge marks, as a state upload leaves them (smx_recon_map.hip).
+int reset_accumulators(smx_recon r, hipStream_t st);
+// ... and what compaction and a map merge reset beyond that: both flag tables, the streaks, the hot marks, the link bitmaps
+// (smx_recon_map.hip; calls reset_accumulators and invalidate_derived).
+int reset_derived_after_rewrite(smx_recon r, hipStream_t st);
 
 }  // namespace smx

@@ -36,6 +36,12 @@ the segments from the vertices to a camera (visibility):
     o, d = meshing.camera_rays(fx, fy, cx, cy, width, height, global_T_camera)
     slots, visible = meshing.vertex_visibility(rec, triangles, camera_centre)
 
+Another session's map into this one (smx_recon_merge_map) -- under the pose a registration found; a mesh of the
+source follows through src_to_dst:
+
+    stats, src_to_dst = meshing.merge_maps(rec, other, dst_T_src, mode="blend", return_map=True)
+    moved_mesh = meshing.remap_triangles(other_triangles, src_to_dst)
+
 The order of the chain is clean -> fill -> decimate: cleaning first, so that no hole of a piece that goes is filled, and
 decimation last, because it does not keep the mesh manifold and puts the whole array back into (p, a, b) order.
 """
@@ -208,6 +214,27 @@ class MapMesher:
         if self._index is not None:
             self._index.close()
             self._index = None
+
+
+def merge_maps(dst, src, dst_T_src, stream=None, index=None, return_map=False, **params):
+    """Merges the map of `src` into the map of `dst` (two CUDASurfelReconstruction objects on one device) under the pose
+    dst_T_src ([3,4], dst <- src): CUDASurfelReconstruction.MergeMap.  params: the keywords of api.merge_params (cell_size,
+    radius_factor_squared, max_normal_angle_deg, k, mode "keep" / "blend", confidence_cap, frame_index).  Returns the statistics
+    dict and, with return_map, src_to_dst.  A neighbour index, a MapMesher's kept state and every slot array over dst stay
+    valid for dst's old slots (they keep their indices); the index itself is stale.  ValueError on what the library would refuse."""
+    return dst.MergeMap(stream, src, dst_T_src, index=index, return_map=return_map, **params)
+
+
+def remap_triangles(triangles, src_to_dst):
+    """A triangle array over the source map through a merge's src_to_dst (or a compaction's old_to_new): every index is replaced,
+    a triangle that loses a corner (0xFFFFFFFF) is dropped.  Returns [T_out,3] uint32."""
+    import numpy as np
+    t = np.asarray(triangles, np.uint32).reshape(-1, 3)
+    m = np.asarray(src_to_dst, np.uint32)
+    if t.size and int(t.max()) >= m.size:
+        raise ValueError("a triangle index lies beyond the map")
+    out = m[t]
+    return np.ascontiguousarray(out[(out != 0xFFFFFFFF).all(1)])
 
 
 def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=None, rim=False):

@@ -11,7 +11,8 @@ RGB-D folder: reader -> upload -> preprocessing -> Integrate per frame -> option
                               [--mesh_eval_register_global [--mesh_eval_global_k K] [--mesh_eval_global_anchors A] [--mesh_eval_global_starts M]]
                               [--mesh_compare_samples N [--mesh_compare_distance METRES]]
                               [--export_mesh_samples FILE.ply --mesh_samples N]
-                              [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]] ...
+                              [--render_dir DIR [--render_every N] [--render_overview] [--render_source splats|mesh]]
+                              [--merge_split F [--merge_mode keep|blend]] ...
 With --mesh the map is triangulated on the device at the end (smx_recon_triangulate) and --export_mesh writes the faces;
 without it the OBJ holds the vertices only.
 With --mesh_every N the mesh follows the map instead: every N integrated frames smx_recon_triangulate_update recomputes it
@@ -57,6 +58,11 @@ With --track the folder needs no trajectory: every frame is tracked against the 
 ahead of its integration, because the outlier cull of frame f needs the poses of f - half .. f + half.  A trajectory file
 that is there is used for the first pose and for an error report only.  --track_rgbd (which implies --track) adds the
 photometric term to the tracking (smx_recon_track_rgbd), --track_photometric_weight sets its weight.
+--merge_split F reconstructs two sessions and makes one map of them: frames [start, F) go into one object and [F, end) into a
+second; the second's mesh is registered to the first's from the identity (smx_recon_register_mesh: the poses are given, so the
+line printed says how far from the identity the registration ends), and the second map is merged into the first under that
+pose (smx_recon_merge_map, --merge_mode keep drops matched surfels, blend averages them in); the statistics line is printed and
+the rest of the chain (--mesh, --mesh_eval, the exports) runs on the merged map.  Not with --track or --mesh_every.
 With --synthetic N it first writes an N-frame synthetic dataset into the folder (the test stream), so that the whole
 path can be exercised without data."""
 import argparse
@@ -261,7 +267,16 @@ def parse_args(argv=None):
                     help="track with the photometric term as well (implies --track)")
     ap.add_argument("--track_photometric_weight", type=float, default=None,
                     help="with --track_rgbd: metres per unit intensity (default: the library's, 0.1)")
+    ap.add_argument("--merge_split", type=int, default=0, metavar="F",
+                    help="two sessions: frames before F into one map, from F on into a second, which is registered to the first and "
+                         "merged into it (smx_recon_merge_map); the rest of the chain runs on the merged map (0 = one session)")
+    ap.add_argument("--merge_mode", choices=["keep", "blend"], default="keep",
+                    help="with --merge_split: what a matched surfel of the second session does to the first's (default: nothing)")
     args = ap.parse_args(argv)
+    if args.merge_split < 0:
+        ap.error("--merge_split needs a frame index >= 0")
+    if args.merge_split and (args.track or args.track_rgbd or args.mesh_every > 0):
+        ap.error("--merge_split does not go with --track or --mesh_every")
     if args.track_photometric_weight is not None and not args.track_rgbd:
         ap.error("--track_photometric_weight needs --track_rgbd")
     args.track = args.track or args.track_rgbd
@@ -419,6 +434,41 @@ def format_global_register_line(f, fig):
                 fig["runner_up"] - fig["cost"], fig["call_ms"], tm["score"], tm["select"], tm["refine"], tm["rescore"]))
 
 
+def format_merge_register_line(res):
+    """The first line of --merge_split: where the registration of the second session's mesh to the first's ended."""
+    T = np.asarray(res["scene_T_points"], np.float64).reshape(3, 4)
+    angle = float(np.arccos(np.clip(0.5 * (np.trace(T[:, :3]) - 1.0), -1.0, 1.0)))
+    return "second session registered to the first: status %d after %d iterations, %d inliers, %.3f mrad and %.3f mm from the identity" % (
+        int(res["status"]), int(res["iterations_run"]), int(res["inliers"]), 1e3 * angle, 1e3 * float(np.linalg.norm(T[:, 3])))
+
+
+def format_merge_line(mode, stats, ms, timings):
+    """The statistics line of --merge_split."""
+    return ("merged (%s) in %.1f ms (device %.2f ms: build %.2f, move %.2f, query + select %.2f, number %.2f, append %.2f, blend %.2f, "
+            "finish %.2f): %s" % (mode, ms, timings["whole"], timings["build"], timings["move"], timings["query_select"], timings["number"],
+                                  timings["append"], timings["blend"], timings["finish"], ", ".join("%s %d" % kv for kv in stats.items())))
+
+
+def merge_sessions(args, first, second, frame_index):
+    """Registers the second session's mesh to the first's from the identity, merges the second map into the first under the pose
+    found (the identity if the registration did not solve) and prints both lines."""
+    from surfelmeshing_amd import meshing
+    tri_first, _ = meshing.mesh_map(first)
+    tri_second, _ = meshing.mesh_map(second)
+    bound = args.mesh_eval if args.mesh_eval is not None else 0.05
+    with meshing.build_distance_scene(first, tri_first, bound) as scene:
+        res = meshing.register_mesh(second, scene, tri_second, 20000)
+    print(format_merge_register_line(res))
+    T = np.asarray(res["scene_T_points"], np.float32).reshape(3, 4)
+    if int(res["status"]) > 1:
+        print("the registration did not solve: merging under the identity")
+        T = np.eye(4, dtype=np.float32)[:3]
+    t1 = time.time()
+    stats = meshing.merge_maps(first, second, T, mode=args.merge_mode, frame_index=max(1, frame_index))
+    print(format_merge_line(args.merge_mode, stats, 1e3 * (time.time() - t1), first.debug_merge_timings()), flush=True)
+    return stats
+
+
 def format_point_eval(summary, what, head="scene points"):
     """A line of --mesh_eval_frames: `what` is "frame 6" or "3 frames"; the figures are format_distance_summary's."""
     from surfelmeshing_amd import meshing
@@ -472,6 +522,9 @@ def main():
                            pyramid_level=args.pyramid_level,
                            median_filter_and_densify_iterations=args.median_filter_and_densify_iterations)
     pipe = FramePipeline(cam.width(), cam.height(), fx, fy, cx, cy, args.max_surfel_count, pre)
+    # --merge_split: the second session's pipeline; both hold every frame either needs (the cull of a frame reads its neighbours)
+    second = FramePipeline(cam.width(), cam.height(), fx, fy, cx, cy, args.max_surfel_count, pre) if args.merge_split else None
+    pipes = [pipe] + ([second] if second is not None else [])
     half = args.outlier_filtering_frame_count // 2
     n = min(video.frame_count(), args.end_frame)
     mesher = None
@@ -514,7 +567,8 @@ def main():
         # main.cc:905-968: everything up to f + half + 1 is on the GPU before frame f is processed
         for g in range(f, min(n - 1, f + half + 1) + 1):
             if g not in uploaded:
-                pipe.upload(g, video.depth_frame(g).GetImage(), video.color_frame(g).GetImage())
+                for p_ in pipes:
+                    p_.upload(g, video.depth_frame(g).GetImage(), video.color_frame(g).GetImage())
                 video.depth_frame(g).ClearImageAndDerivedData()
                 video.color_frame(g).ClearImageAndDerivedData()
                 uploaded.add(g)
@@ -529,7 +583,7 @@ def main():
             before = pipe.reconstruction.surfels_size()
             _, after, _ = pipe.compact(return_map=False)
             compactions, removed = compactions + 1, removed + before - after
-        pipe.process(f, others, T, G)
+        (second if second is not None and f >= args.merge_split else pipe).process(f, others, T, G)
         done += 1
         if mesher is not None and done % args.mesh_every == 0:
             update_mesh(done)
@@ -538,10 +592,15 @@ def main():
                          current_mesh() if args.render_source == "mesh" else None)
         old = f - half - 1                                                                      # main.cc:1226-1240
         if old in uploaded:
-            pipe.release(old)
+            for p_ in pipes:
+                p_.release(old)
     api.StreamSynchronize(None)
     dt = time.time() - t0
     rec = pipe.reconstruction
+    if second is not None:
+        print("two sessions: %d surfels from the frames before %d, %d from the rest" % (
+            rec.surfels_size(), args.merge_split, second.reconstruction.surfels_size()))
+        merge_sessions(args, rec, second.reconstruction, n)
     print("%d frames integrated in %.2f s (%.1f frames/s incl. PNG decoding); %d surfels (%d merged)" % (
         done, dt, done / max(dt, 1e-9), rec.surfels_size(), rec.surfels_size() - rec.surfel_count()))
     if compactions:
