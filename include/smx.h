@@ -1941,6 +1941,89 @@ int smx_recon_debug_merge_timings(smx_recon dst, float* out_ms, int32_t capacity
  * [chunk][k] candidate workspace; results must not depend on it. */
 int smx_recon_debug_set_merge_chunk(smx_recon dst, uint32_t chunk_queries);
 
+/* ---- importing a point cloud as surfels (not in the reference: its map comes from RGB-D frames) ----
+ * smx_recon_import_points turns n points -- positions, perhaps colours, perhaps the sensor origin each was seen from -- into
+ * surfels behind the map's slots: the normal is the smallest eigenvector of the covariance of the point's k nearest
+ * neighbours, the radius comes from a neighbour distance.  float32 and double expressions as stated, each evaluated as
+ * written (no contraction); rows are those of SURVEY.md Appendix A.
+ * 1. BAD.  A point with a non-finite coordinate is BAD; with orient = SMX_IMPORT_ORIENT_ORIGINS a point with a non-finite
+ *    origin word is BAD too.  A BAD point is left out of the index, so it is never a neighbour.  (A finite coordinate the
+ *    index does not take, |v| > 3.0e38f, is not BAD: the point gets an empty list and is SPARSE.)
+ * 2. List.  nn is built by smx_nn_build over the points that are not BAD with cell_size.  The list of point i is
+ *    smx_nn_query_self's answer with r^2 = search_radius * search_radius (float32) and k: m entries (j, d2), ascending by
+ *    (d2, index), the point itself included.  n_saturated counts the points with m == k.
+ * 3. SPARSE.  m < min_neighbors.
+ * 4. Covariance.  Over the entries e = 0 .. m-1 in list order, j the entry's point: d = (x_j - x_i, y_j - y_i, z_j - z_i),
+ *    each a float32 subtraction; s_a += (double)d_a and q_ab += (double)d_a * (double)d_b for the six a <= b, nine double
+ *    sums.  inv = 1.0 / (double)m, mean_a = s_a * inv, C_ab = q_ab * inv - mean_a * mean_b.
+ * 5. Eigenvectors.  Cyclic Jacobi in double on A = C, V = identity: SMX_IMPORT_JACOBI_SWEEPS sweeps over the pairs (p, q) =
+ *    (0,1), (0,2), (1,2), r the third index.  A pair with a_pq == 0 is skipped.  Otherwise theta = (a_qq - a_pp) / (2.0 * a_pq),
+ *    t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0)) (an infinite theta gives t = 0),
+ *    c = 1.0 / sqrt(t * t + 1.0), sn = t * c, and from the old values
+ *      a_pp' = a_pp - t * a_pq,  a_qq' = a_qq + t * a_pq,  a_pq' = 0,
+ *      a_rp' = c * a_rp - sn * a_rq,  a_rq' = sn * a_rp + c * a_rq,
+ *      v_ip' = c * v_ip - sn * v_iq,  v_iq' = sn * v_ip + c * v_iq  for the rows i = 0, 1, 2.
+ *    lam0 = the smallest diagonal entry afterwards (ties: the lowest column), the normal that column of V; lam1, lam2 = the
+ *    other two diagonal entries in ascending column order.
+ * 6. ROUGH.  lam0 > (double)max_surface_variation * ((lam0 + lam1) + lam2).
+ * 7. Normal.  (nx, ny, nz) = the three doubles as floats; len2 = (nx nx + ny ny) + nz nz; n = n / sqrtf(len2) per component.
+ *    !(len2 > 0) or a non-finite component: DEGENERATE.  Orientation (VIEW_POINT: o = view_point, ORIGINS: o = the point's
+ *    origin): v = o - p per component in float32; (nx vx + ny vy) + nz vz < 0 negates the normal, a zero dot keeps it.
+ *    SMX_IMPORT_ORIENT_NONE keeps the sign Jacobi left.
+ * 8. Radius.  RadiusSquared = radius_scale_squared * d2[min(radius_rank, m - 1)], d2 the list's own float32 words.
+ *    !(RadiusSquared > 0): DEGENERATE (a point whose list up to that rank is duplicates of itself).
+ * 9. Class.  BAD, SPARSE, DEGENERATE (by the radius, then by the normal), ROUGH, else imported: the first that holds.  Each
+ *    point is counted once: n_points = n_bad + n_sparse + n_degenerate + n_rough + n_imported.
+ * 10. Append.  The imported points take the slots old_size + rank, in ascending point order.  old_size + n_imported >
+ *    max_surfel_count(r): SMX_ERR_INVALID_ARGUMENT, the map byte for byte unchanged, stats filled, point_to_slot not written.
+ *    Rows of an appended slot: 0-2 and 3-5 the point; 6 confidence; 7 RadiusSquared; 8-10 the normal; 11-16 and 23 zero;
+ *    17, 18 = frame_index; 19-22 = 0xFFFFFFFF; 24 = colors[i], or default_color where colors is NULL.
+ * 11. point_to_slot (may be NULL; capacity >= n entries; device pointer if on_device, host pointer otherwise): the slot of an
+ *    imported point, 0xFFFFFFFF for every other.
+ * 12. State.  Afterwards surfels_size(r) = new_size and the merge count is unchanged; the derived frame-loop state is what
+ *    smx_recon_merge_map leaves, with delta marks on exactly the appended slots.  Nothing is matched against the surfels the
+ *    map already holds (that is smx_recon_merge_map's job).  nn indexes the cloud afterwards, not the map.
+ * Calling rules: synchronous; ordered behind everything enqueued on the object.  points, colors and origins are device
+ *   pointers if inputs_on_device, host pointers otherwise, and are read only.  Refused with SMX_ERR_INVALID_ARGUMENT, nothing
+ *   launched and nothing written: a NULL r, nn or p; NULL points with n > 0; NULL origins with ORIGINS; a field of p outside
+ *   the range below; a capacity below n with a point_to_slot.  n == 0 is valid and changes nothing.  The workspace belongs to
+ *   r, is counted by smx_debug_live_allocations and reached by smx_debug_fail_allocation; every allocation comes before the
+ *   first write to the map, so a failed one leaves the map unchanged.
+ * Not built: voxel thinning of dense clouds, projecting the smooth position onto the fitted plane, links among imported
+ *   surfels (rows 19-22), orientation without origins by propagation over the neighbour graph, per-point confidences. */
+enum { SMX_IMPORT_ORIENT_NONE = 0, SMX_IMPORT_ORIENT_VIEW_POINT = 1, SMX_IMPORT_ORIENT_ORIGINS = 2 };
+#define SMX_IMPORT_PHASES 7
+#define SMX_IMPORT_JACOBI_SWEEPS 6
+typedef struct {            /* smx_import_params_default() fills the defaults */
+  float   cell_size;                 /* of the neighbour index built over the cloud; > 0; default 0.05 */
+  float   search_radius;             /* metres, > 0; default 0.1 */
+  int32_t k;                         /* entries of a point's list, 4 .. 64; default 16 */
+  int32_t min_neighbors;             /* 3 .. k; default 6 */
+  float   max_surface_variation;     /* lam0 / (lam0 + lam1 + lam2) above which a point is ROUGH, 0 .. 1/3; default 1/3 */
+  int32_t radius_rank;               /* the list entry whose d2 gives the radius, 1 .. 63; default 8 */
+  float   radius_scale_squared;      /* > 0; default 2.0 */
+  float   confidence;                /* row 6 of every imported slot; finite; default 1.0 */
+  uint32_t default_color;            /* row 24 where colors is NULL; default 0 */
+  uint32_t frame_index;              /* >= 1: rows 17 and 18; default 1 */
+  int32_t orient;                    /* SMX_IMPORT_ORIENT_*; default NONE */
+  float   view_point[3];             /* finite; default 0, 0, 0 */
+} smx_import_params;
+typedef struct {
+  uint32_t n_points, n_bad, n_sparse, n_degenerate, n_rough, n_imported, n_saturated;
+  uint32_t old_size, new_size;
+} smx_import_stats;
+int smx_import_params_default(smx_import_params* out);
+int smx_recon_import_points(smx_recon r, smx_stream s, smx_nn nn,
+                            const float* points /* [n][3] */, const uint32_t* colors /* [n] or NULL */,
+                            const float* origins /* [n][3] or NULL */, uint32_t n, int32_t inputs_on_device,
+                            const smx_import_params* p, uint32_t* point_to_slot, uint32_t capacity, int32_t on_device,
+                            smx_import_stats* stats);
+/* Tools: milliseconds of r's last smx_recon_import_points call by timed events on its stream: out_ms[0] the whole call, then
+ * the SMX_IMPORT_PHASES phases stage, index build, self-query, fit, number, write, finish; at most `capacity` values are
+ * written.  The waits of the call's read-backs fall into the phase they end.  Zeros before the first call and after a call
+ * that failed. */
+int smx_recon_debug_import_timings(smx_recon r, float* out_ms, int32_t capacity);
+
 /* ---- benchmark input generator (not part of the reference's interface) ----
  * Renders one frame of the synthetic room stream into device buffers:
  * depth u16 = round(depth_scaling * z) with sigma = noise_sigma * z^2 noise and coherent 8x8

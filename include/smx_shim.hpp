@@ -668,6 +668,22 @@ class CUDASurfelReconstruction {
     if (!index) (void)smx_nn_destroy(nn);
     SMX_SHIM_CHECK(rc);
   }
+  // Not in the reference: appends n host points ([n][3] floats; colors [n] words or null; origins [n][3] or null, needed by
+  // SMX_IMPORT_ORIENT_ORIGINS) to this map as surfels with fitted normals and radii (synchronous; see smx_recon_import_points
+  // in smx.h).  point_to_slot (resized to n) receives each point's slot or 0xFFFFFFFF; index: a neighbour index to rebuild and
+  // use (one is created for the call if null; it indexes the cloud afterwards); stats may be null and is filled also when the
+  // call throws for lack of room.
+  void ImportPoints(cudaStream_t stream, const float* points, const u32* colors, const float* origins, u32 n,
+                    const smx_import_params& params, std::vector<u32>* point_to_slot = nullptr, smx_nn index = nullptr,
+                    smx_import_stats* stats = nullptr) {
+    smx_nn nn = index;
+    if (!nn) SMX_SHIM_CHECK(smx_nn_create(-1, &nn));
+    if (point_to_slot) point_to_slot->resize(n);
+    const int rc = smx_recon_import_points(handle_, stream, nn, points, colors, origins, n, 0, &params,
+                                           point_to_slot && n ? point_to_slot->data() : nullptr, point_to_slot ? n : 0, 0, stats);
+    if (!index) (void)smx_nn_destroy(nn);
+    SMX_SHIM_CHECK(rc);
+  }
   // Not in the reference: triangulates the map as it stands on the device (smx_recon_triangulate in smx.h: a localized
   // Delaunay triangulation).  *triangles receives three slot indices per triangle, in the order smx.h describes.
   // index: a neighbour index to rebuild and use (one is created for the call if null); stats may be null.  Synchronous.

@@ -450,6 +450,37 @@ class MergeStats(C.Structure):
                                           "links_dropped", "old_size", "new_size")]
 
 
+class ImportParams(C.Structure):
+    """smx_import_params: the index cell, the search ball, k, the gates, the radius rule, the constant rows and the orientation of
+    smx_recon_import_points."""
+    _fields_ = [("cell_size", C.c_float), ("search_radius", C.c_float), ("k", C.c_int32), ("min_neighbors", C.c_int32),
+                ("max_surface_variation", C.c_float), ("radius_rank", C.c_int32), ("radius_scale_squared", C.c_float),
+                ("confidence", C.c_float), ("default_color", C.c_uint32), ("frame_index", C.c_uint32), ("orient", C.c_int32),
+                ("view_point", C.c_float * 3)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """smx_import_params_default(), then any field by name."""
+        p = cls()
+        check(load().smx_import_params_default(C.byref(p)))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(k)
+            setattr(p, k, (C.c_float * 3)(*v) if k == "view_point" else v)
+        return p
+
+
+IMPORT_ORIENTS = {"none": 0, "view_point": 1, "origins": 2}      # SMX_IMPORT_ORIENT_*
+IMPORT_PHASES = 7                                                # SMX_IMPORT_PHASES
+IMPORT_PHASE_NAMES = ("whole", "stage", "build", "query", "fit", "number", "write", "finish")
+
+
+class ImportStats(C.Structure):
+    """smx_import_stats"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_points", "n_bad", "n_sparse", "n_degenerate", "n_rough", "n_imported", "n_saturated",
+                                          "old_size", "new_size")]
+
+
 class MeshRenderParams(C.Structure):
     """smx_mesh_render_params: camera, colour mode, culling and normal mode of smx_recon_render_mesh."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32),
@@ -545,6 +576,7 @@ EXPORTS = [
     "smx_recon_kernel_slot_count", "smx_recon_kernel_slot_name", "smx_recon_get_kernel_timings",
     "smx_recon_profile_begin", "smx_recon_profile_end",
     "smx_merge_params_default", "smx_recon_merge_map", "smx_recon_debug_merge_timings", "smx_recon_debug_set_merge_chunk",
+    "smx_import_params_default", "smx_recon_import_points", "smx_recon_debug_import_timings",
     "smx_recon_compact", "smx_recon_update_visualization_buffers", "smx_recon_render", "smx_track_params_default", "smx_recon_track", "smx_recon_debug_track_iterations", "smx_track_rgbd_params_default", "smx_recon_track_rgbd", "smx_recon_debug_track_rgbd_iterations", "smx_recon_debug_download_surfels", "smx_recon_debug_upload_surfels", "smx_recon_debug_download_scratch", "smx_recon_debug_count_skipped_segments",
     "smx_recon_set_scan_mode", "smx_recon_debug_set_skip", "smx_recon_set_overlap", "smx_recon_integrate_hooks", "smx_recon_integrate_inputs_ready",
     "smx_nn_create", "smx_nn_destroy", "smx_nn_build", "smx_nn_query_batch", "smx_nn_query_self", "smx_nn_set_query_mode", "smx_nn_set_stats_enabled", "smx_nn_get_stats",

@@ -662,6 +662,55 @@ def merge_stats_dict(st):
     return {n: int(getattr(st, n)) for n, _ in _lib.MergeStats._fields_}
 
 
+def import_params(cell_size=0.05, search_radius=0.1, k=16, min_neighbors=6, max_surface_variation=None, radius_rank=8,
+                  radius_scale_squared=2.0, confidence=1.0, default_color=0, frame_index=1, orient="none", view_point=(0.0, 0.0, 0.0)):
+    """smx_import_params from keyword arguments: orient "none" / "view_point" / "origins" (or 0 / 1 / 2);
+    max_surface_variation None = 1/3, which rejects nothing.  ValueError on what the library would refuse."""
+    if isinstance(orient, str):
+        if orient not in _lib.IMPORT_ORIENTS:
+            raise ValueError("orient must be one of %s" % ", ".join(_lib.IMPORT_ORIENTS))
+        orient = _lib.IMPORT_ORIENTS[orient]
+    third = float(np.float32(1.0 / 3.0))
+    msv = third if max_surface_variation is None else float(np.float32(max_surface_variation))
+    if not (float(cell_size) > 0 and float(search_radius) > 0 and float(radius_scale_squared) > 0):
+        raise ValueError("cell_size, search_radius and radius_scale_squared must be > 0")
+    if not 4 <= int(k) <= 64:
+        raise ValueError("k must be within 4 .. 64")
+    if not 3 <= int(min_neighbors) <= int(k):
+        raise ValueError("min_neighbors must be within 3 .. k")
+    if not 0.0 <= msv <= third:
+        raise ValueError("max_surface_variation must be within 0 .. 1/3")
+    if not 1 <= int(radius_rank) <= 63:
+        raise ValueError("radius_rank must be within 1 .. 63")
+    if not 1 <= int(frame_index) <= 0xFFFFFFFF:
+        raise ValueError("frame_index must be >= 1")
+    if int(orient) not in (0, 1, 2):
+        raise ValueError("orient must be 0 (none), 1 (view_point) or 2 (origins)")
+    vp = [float(v) for v in np.asarray(view_point, np.float64).reshape(3)]
+    if not (np.isfinite(float(confidence)) and np.all(np.isfinite(vp))):
+        raise ValueError("confidence and view_point must be finite")
+    return _lib.ImportParams(cell_size, search_radius, int(k), int(min_neighbors), msv, int(radius_rank), radius_scale_squared,
+                             confidence, int(default_color) & 0xFFFFFFFF, int(frame_index), int(orient), (C.c_float * 3)(*vp))
+
+
+def import_stats_dict(st):
+    return {n: int(getattr(st, n)) for n, _ in _lib.ImportStats._fields_}
+
+
+def _cloud_arg(a, width, dtype, what):
+    """A per-point input of ImportPoints: (points it holds, address or None, on_device, the object that keeps it alive)."""
+    if _device_address(a) is not None:
+        if not (a.is_contiguous() and a.element_size() == 4 and a.numel() % width == 0):
+            raise ValueError("a device tensor of %s must be contiguous 32-bit values, %d per point" % (what, width))
+        import torch
+        torch.cuda.current_stream(a.device).synchronize()      # (the tensor's producers; the call runs on its own stream)
+        return a.numel() // width, (a.data_ptr() if a.numel() else None), True, a
+    h = np.ascontiguousarray(a, dtype)
+    if h.size % width:
+        raise ValueError("%s must hold %d values per point" % (what, width))
+    return h.size // width, (h.ctypes.data if h.size else None), False, h
+
+
 def _device_address(a):
     """The device address of a device tensor (anything with is_cuda / data_ptr), None for everything else."""
     if getattr(a, "is_cuda", False) and hasattr(a, "data_ptr"):
@@ -1322,6 +1371,60 @@ class CUDASurfelReconstruction:
     def debug_set_merge_chunk(self, chunk_queries):
         """Tests: MergeMap queries in chunks of this many source slots (0 = the default); results do not depend on it."""
         _lib.check(_lib.load().smx_recon_debug_set_merge_chunk(self._h, C.c_uint32(int(chunk_queries))))
+
+    def ImportPoints(self, stream, points, colors=None, origins=None, index=None, return_map=False, **params):
+        """Not in the reference: appends a point cloud to this map as surfels (smx_recon_import_points; synchronous).  points
+        [n,3] float32, colors [n] 32-bit words for row 24 (None: default_color), origins [n,3] float32 (the sensor position each
+        point was seen from; needed by orient="origins") -- numpy arrays, or device tensors, all on the same side.  Every point
+        gets the smallest eigenvector of its k nearest neighbours' covariance as its normal and a neighbour distance as its
+        radius; points without enough neighbours, with a degenerate fit or a rough neighbourhood are left out.  params: the
+        keywords of import_params, or params=<ImportParams>.  index: a SurfelNeighborIndex to build and use (it indexes the
+        cloud afterwards); one is created and closed here if None.  Returns the statistics dict, or (dict, point_to_slot
+        [uint32 per point: its slot, 0xFFFFFFFF if it was not imported]) with return_map.  Too little room raises SmxError and
+        leaves the map as it was; .last_import_stats then says how much was needed."""
+        pod = params.pop("params", None)
+        if pod is None:
+            pod = import_params(**params)
+        elif params:
+            raise ValueError("either params= or keywords")
+        n, p_addr, on_device, keep_p = _cloud_arg(points, 3, np.float32, "points")
+        keep = [keep_p]
+        c_addr = o_addr = None
+        for a, width, dtype, what in ((colors, 1, np.uint32, "colors"), (origins, 3, np.float32, "origins")):
+            if a is None:
+                continue
+            m, addr, dev, k = _cloud_arg(a, width, dtype, what)
+            if m != n or (dev != on_device and n):
+                raise ValueError("%s must hold one entry per point, on the same side as points" % what)
+            keep.append(k)
+            if what == "colors":
+                c_addr = addr
+            else:
+                o_addr = addr
+        if pod.orient == _lib.IMPORT_ORIENTS["origins"] and origins is None:
+            raise ValueError('orient="origins" needs origins')
+        own = index is None
+        nn = SurfelNeighborIndex(self._device_id) if own else index
+        try:
+            p2s = np.empty(n, np.uint32) if return_map else None
+            st = _lib.ImportStats()
+            rc = _lib.load().smx_recon_import_points(
+                self._h, _sv(stream), nn._h, C.c_void_p(p_addr), C.c_void_p(c_addr), C.c_void_p(o_addr), C.c_uint32(n),
+                C.c_int32(1 if on_device else 0), C.byref(pod), p2s.ctypes.data_as(C.c_void_p) if p2s is not None and n else None,
+                C.c_uint32(n if p2s is not None else 0), C.c_int32(0), C.byref(st))
+            self.last_import_stats = import_stats_dict(st)
+            _lib.check(rc)
+            return (self.last_import_stats, p2s) if return_map else self.last_import_stats
+        finally:
+            if own:
+                nn.close()
+
+    def debug_import_timings(self):
+        """Milliseconds of the last ImportPoints into this object by the library's events: {whole, stage, build, query, fit, number,
+        write, finish}."""
+        out = (C.c_float * (_lib.IMPORT_PHASES + 1))()
+        _lib.check(_lib.load().smx_recon_debug_import_timings(self._h, out, C.c_int32(_lib.IMPORT_PHASES + 1)))
+        return dict(zip(_lib.IMPORT_PHASE_NAMES, (float(v) for v in out)))
 
     def DeformByCreationFrame(self, stream, frame_T, reactivate=None, frame_index=0):
         """The loop-closure hook the reference describes but does not ship (README.md:152-176): surfels created at

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libsmx.so")
 SOURCES = ["smx_buffer.hip", "smx_depth.hip", "smx_recon.hip", "smx_recon_map.hip", "smx_track.hip", "smx_mesh.hip", "smx_decimate.hip",
-           "smx_components.hip", "smx_fill.hip", "smx_merge.hip", "smx_distance.hip", "smx_rim.hip", "smx_raycast.hip", "smx_rayscene.hip", "smx_distscene.hip", "smx_register.hip", "smx_global.hip", "smx_trigrid.hip", "smx_sample.hip", "smx_mesh_raster.hip", "smx_nn.hip", "smx_synth.hip", "smx_driver.cpp"]
+           "smx_components.hip", "smx_fill.hip", "smx_merge.hip", "smx_import.hip", "smx_distance.hip", "smx_rim.hip", "smx_raycast.hip", "smx_rayscene.hip", "smx_distscene.hip", "smx_register.hip", "smx_global.hip", "smx_trigrid.hip", "smx_sample.hip", "smx_mesh_raster.hip", "smx_nn.hip", "smx_synth.hip", "smx_driver.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 

@@ -24,24 +24,6 @@ struct MergePose { float m[12]; };
 
 __device__ __forceinline__ MgVec mg_xyz(const float4& v) { return MgVec{v.x, v.y, v.z}; }
 
-// The counts of a launch: every lane counts in registers over its grid-stride loop, the wavefronts fold their lanes by ballots'
-// kin (wave_sum) and add to the workgroup's LDS words, and one lane adds each word to the device counter: one global atomic per
-// workgroup and counter (the counters of a launch are consecutive words, ctr[0 .. kCounters)).  (One per wavefront and loop trip was 57 k atomics on one address for 3.6 M slots, at ~12 ns apiece
-// longer than the kernel's memory traffic.)  Every lane of the workgroup calls this, once, behind its loop.
-template <int kCounters>
-__device__ __forceinline__ void block_counts(uint32_t* __restrict__ ctr, const uint32_t (&mine)[kCounters]) {
-  __shared__ uint32_t tot[kCounters];
-  if (threadIdx.x < kCounters) tot[threadIdx.x] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < kCounters; ++c) {
-    const uint32_t s = wave_sum(mine[c]);
-    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tot[c], s);
-  }
-  __syncthreads();
-  if (threadIdx.x < kCounters && tot[threadIdx.x]) atomicAdd(ctr + threadIdx.x, tot[threadIdx.x]);
-}
-
 // Streams the source's P, S and N records (48 B per slot), writes 16 B of query rows and 48 B of moved records per slot.
 __global__ void __launch_bounds__(kBlock)
 k_merge_move(Surfels src, uint32_t n, MergePose T, float factor_sq, float* __restrict__ q, float4* __restrict__ moved,

@@ -4,7 +4,7 @@
 // smx_recon_map.hip the map services that read or rewrite the finished map outside of it (row transfers, export,
 // viewer buffers, the splat render, neighbour and meshing glue, compaction, deformation); tracking, decimation, the
 // components, hole filling, the mesh distance, the rim, the ray cast, the mesh sampler and the mesh render live with their kernels in smx_track.hip, smx_decimate.hip,
-// smx_components.hip, smx_fill.hip, smx_merge.hip, smx_distance.hip, smx_rim.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
+// smx_components.hip, smx_fill.hip, smx_merge.hip, smx_import.hip, smx_distance.hip, smx_rim.hip, smx_raycast.hip, smx_sample.hip and smx_mesh_raster.hip.  This header is what
 // they all need: the attribute layout, the plain structs that are members of smx_recon_s, the object itself -- the
 // frame loop's state, then one workspace per service, each defined in the service's own header -- and the few host
 // helpers every entry point starts with.  Kernels stay in anonymous namespaces of the .hip files.
@@ -15,6 +15,7 @@
 #include "smx_decimate.hpp"
 #include "smx_distance.hpp"
 #include "smx_fill.hpp"
+#include "smx_import.hpp"
 #include "smx_merge.hpp"
 #include "smx_raycast.hpp"
 #include "smx_render.hpp"
@@ -250,6 +251,24 @@ __device__ __forceinline__ int32_t wave_imax(int32_t v) {
   return v;
 }
 
+// The counts of a launch: every lane counts in registers over its grid-stride loop, the wavefronts fold their lanes by ballots'
+// kin (wave_sum) and add to the workgroup's LDS words, and one lane adds each word to the device counter: one global atomic per
+// workgroup and counter (the counters of a launch are consecutive words, ctr[0 .. kCounters)).  (One per wavefront and loop trip was 57 k atomics on one address for 3.6 M slots, at ~12 ns apiece
+// longer than the kernel's memory traffic.)  Every lane of the workgroup calls this, once, behind its loop.
+template <int kCounters>
+__device__ __forceinline__ void block_counts(uint32_t* __restrict__ ctr, const uint32_t (&mine)[kCounters]) {
+  __shared__ uint32_t tot[kCounters];
+  if (threadIdx.x < kCounters) tot[threadIdx.x] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < kCounters; ++c) {
+    const uint32_t s = wave_sum(mine[c]);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tot[c], s);
+  }
+  __syncthreads();
+  if (threadIdx.x < kCounters && tot[threadIdx.x]) atomicAdd(ctr + threadIdx.x, tot[threadIdx.x]);
+}
+
 // The maps of the multi-launch blend fallback (kernels.cc:165-166).
 struct BlendBufs {
   uint8_t* distance_map; uint8_t* new_distance_map; float* deltas; float* new_deltas;
@@ -422,6 +441,7 @@ struct smx_recon_s {
   smx::CompactWork compact;       // smx_recon_compact
   smx::CandidateWork candidates;  // smx_recon_neighbor_candidates
   smx::MergeWork merge;           // smx_recon_merge_map (this object as the destination)
+  smx::ImportWork import;         // smx_recon_import_points
   smx::MeshWorkspace* mesh;       // smx_recon_triangulate / _update (created by the first call): lists, rings, counts, output staging
 };
 

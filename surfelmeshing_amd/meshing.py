@@ -42,6 +42,12 @@ source follows through src_to_dst:
     stats, src_to_dst = meshing.merge_maps(rec, other, dst_T_src, mode="blend", return_map=True)
     moved_mesh = meshing.remap_triangles(other_triangles, src_to_dst)
 
+A point cloud -- positions, perhaps colours and sensor origins -- as surfels (smx_recon_import_points), into a map
+of its own or through a merge into an existing one:
+
+    rec, stats = meshing.map_from_points(points, colors, search_radius=0.05, orient="view_point", view_point=(0, 0, 1.5))
+    import_stats, merge_stats = meshing.merge_points(rec, scan_points, rec_T_scan, origins=scan_origins, mode="blend")
+
 The order of the chain is clean -> fill -> decimate: cleaning first, so that no hole of a piece that goes is filled, and
 decimation last, because it does not keep the mesh manifold and puts the whole array back into (p, a, b) order.
 """
@@ -235,6 +241,49 @@ def remap_triangles(triangles, src_to_dst):
         raise ValueError("a triangle index lies beyond the map")
     out = m[t]
     return np.ascontiguousarray(out[(out != 0xFFFFFFFF).all(1)])
+
+
+def import_points(rec, points, colors=None, origins=None, stream=None, index=None, return_map=False, **params):
+    """Appends a point cloud -- a LiDAR scan, a photogrammetry cloud, the vertices of a PLY -- to the map of `rec` as surfels:
+    CUDASurfelReconstruction.ImportPoints.  params: the keywords of api.import_params (cell_size, search_radius, k,
+    min_neighbors, max_surface_variation, radius_rank, radius_scale_squared, confidence, default_color, frame_index, orient
+    "none" / "view_point" / "origins", view_point).  Returns the statistics dict and, with return_map, point_to_slot."""
+    return rec.ImportPoints(stream, points, colors=colors, origins=origins, index=index, return_map=return_map, **params)
+
+
+def pack_colors(rgb):
+    """[n,3] uint8 colours as the 32-bit words row 24 holds (red in the low byte)."""
+    import numpy as np
+    c = np.asarray(rgb, np.uint8).reshape(-1, 3).astype(np.uint32)
+    return np.ascontiguousarray(c[:, 0] | (c[:, 1] << 8) | (c[:, 2] << 16))
+
+
+def map_from_points(points, colors=None, origins=None, camera=None, room=0, stream=None, index=None, return_map=False, **params):
+    """A fresh CUDASurfelReconstruction sized to the cloud (its point count + room slots) that holds the imported cloud.  camera: a
+    PinholeCamera4f for frames to come (a small default otherwise: the map services do not use it).  Returns (rec, statistics
+    dict[, point_to_slot]); the caller closes rec."""
+    import numpy as np
+    from . import api
+    n = int(points.numel() // 3) if hasattr(points, "numel") else int(np.asarray(points).size // 3)
+    rec = api.CUDASurfelReconstruction(max(n + int(room), 1), camera or api.PinholeCamera4f(64, 48, 50.0, 50.0, 32.0, 24.0))
+    try:
+        out = import_points(rec, points, colors, origins, stream=stream, index=index, return_map=return_map, **params)
+    except Exception:
+        rec.close()
+        raise
+    return (rec,) + (out if return_map else (out,))
+
+
+def merge_points(rec, points, dst_T_src, colors=None, origins=None, stream=None, import_params=None, **merge_params):
+    """A cloud given in its own frame into the map of `rec` under the pose dst_T_src ([3,4], rec <- cloud, e.g. the scene_T_points of
+    a registration): the cloud is imported into a temporary object (import_params: a dict of api.import_params keywords) and
+    that map is merged (merge_maps with merge_params), so that points the map already covers are dropped or blended.
+    Returns (import statistics, merge statistics)."""
+    tmp, ist = map_from_points(points, colors, origins, camera=rec.depth_camera, stream=stream, **(import_params or {}))
+    try:
+        return ist, merge_maps(rec, tmp, dst_T_src, stream=stream, **merge_params)
+    finally:
+        tmp.close()
 
 
 def build_distance_scene(rec, triangles, max_distance, cell_size=0.0, stream=None, rim=False):
